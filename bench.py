@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: rendered rays/s of the A-NeRF hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One step = one 512x512 frame per GPU (262 144 rays, 64 coarse + 16 importance samples per
 ray -> 144 MLP point evaluations per ray, both nets, synthetic surreal-config weights),
@@ -13,13 +13,19 @@ GPU.  Every rank renders its own frame (image-parallel, weak scaling) and the fr
 reassembled on every rank by one all-gather of the packed (rgb, disp, acc) maps, fed from
 device memory, inside the timed region.  Rank 0 prints ONE JSON line (README / DESIGN.md).
 
-Besides the headline the line carries (N = 1 only, each after the timed region):
-  roofline       hipEvent time of the fused embed+MLP kernel vs the MFMA peak
-  cpu_baseline   the oracle (CPU port of the reference path) on a bounded sample, config 2
+A plain run sets up, warms up, times the K steps and prints the line: the headline, `ms_per_step`, and
+  roofline       hipEvent time of the fused embed+MLP kernel in the timed steps vs the MFMA peak
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (dump_outputs).
+`--full` adds what takes runs or checks of its own (N = 1 only unless noted, each after the timed region):
+  strong_scaling the multi-GPU frame path beside the weak headline (any N); frames_sha256 of --scaling strong
+  roofline.*     bare-MFMA calibration, limb masks, far_skip_off, folded_pose
+  cpu_baseline   the oracle (CPU port of the reference path) on a bounded sample, config 2, and `parity` on it
   cpu_baselines  the same for config 1 (128x128, 32 samples per ray)
   host_to_host   SURVEY 8(d)'s frame metric: poses on host -> frames on host through render_path
   workloads      BASELINE config 4 (h36m: 128+16 samples, frame codes) on one 512x512 frame
-  modes          the other precision modes on the headline workload
+  modes          the other precision modes on the headline workload (and north_star_mode)
+  train_step     the training step in both training precisions
+the --no-* switches leave parts of it out.
 `--dry-run` replaces the renderer by a stub and the backend by gloo: the launch / barrier /
 max-over-ranks / gather / JSON plumbing on CPU (tests/test_host_logic.py).
 """
@@ -55,9 +61,40 @@ def parse_args(argv=None):
                     help="weak: one all-hit frame per GPU per step (the headline); strong: --frames culled frames per step "
                          "shared by all GPUs through dist.render_frames_distributed (the GAN loop's call pattern)")
     ap.add_argument("--frames", type=int, default=20, help="frames per step of --scaling strong (run_gan.py:104: rpi = 20)")
-    ap.add_argument("--no-strong", action="store_true", help="skip the strong-scaling side measurement of the default run")
+    ap.add_argument("--no-strong", action="store_true", help="skip the strong-scaling side measurement of a --full run")
     ap.add_argument("--dry-run", action="store_true", help="stub renderer on CPU, gloo backend (plumbing test)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also the side measurements and checks (strong scaling, calibration, CPU baselines, parity, modes, "
+                         "other workloads, training step); a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step returned as DIR/<name>.npy (float32, at most 64 MB in all)")
+    a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if a.dump_outputs is not None:
+        a.dump_outputs = os.path.abspath(a.dump_outputs)
+    return a
+
+
+DUMP_BYTES = 60 << 20       # --dump-outputs: budget of all arrays together (the .npy headers stay well inside 64 MB)
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: each array as d/<name>.npy, float32 (float64 stays float64), C order.  An array larger than its
+    equal share of DUMP_BYTES is cut to a sample of its rows (rows = the last axis' entries), the same rows in every run
+    with the same arguments (seeded permutation, sorted)."""
+    import numpy as np
+    import torch
+    os.makedirs(d, exist_ok=True)
+    share = DUMP_BYTES // max(len(arrays), 1)
+    for name, x in arrays.items():
+        x = x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
+        x = np.ascontiguousarray(x, dtype=np.float64 if x.dtype == np.float64 else np.float32)
+        if x.nbytes > share:
+            rows = x.reshape(-1, x.shape[-1] if x.ndim > 1 else 1)
+            keep = share // (rows.shape[1] * x.itemsize)
+            x = np.ascontiguousarray(rows[np.sort(np.random.default_rng(0).permutation(rows.shape[0])[:keep])])
+        np.save(os.path.join(d, f"{name}.npy"), x)
 
 
 def self_launch(a) -> int:
@@ -427,13 +464,22 @@ def main():
     if world > 1 and a.dry_run and not strong:      # the gathered frames are every rank's frame, in rank order
         for k in range(world):
             assert float(gathered[k * n, 0]) == float(k), "all-gather order"
+    if a.dump_outputs and rank == 0:
+        # what a caller of the timed path received from its last step
+        if strong:
+            dumped = {"rgb": out[0], "disp": out[1], "acc": out[2], "bboxes": [np.concatenate(b) for b in out[4]]}
+        else:
+            dumped = {k: out[k] for k in ("rgb_map", "disp_map", "acc_map", "rgb0", "disp0", "acc0") if k in out}
+            if world > 1:
+                dumped["gathered"] = gathered
+        dump_outputs(a.dump_outputs, dumped)
 
     # Strong scaling beside the weak headline, on every rank (it has a collective): the product's multi-GPU path
     # (dist.render_frames_distributed: plan of nanmean groups, one all-gather, compose) on the GAN loop's call
     # pattern -- `--frames` culled frames per step for ALL GPUs together -- so that a scaling run also says
     # something about load balance.
     side = None
-    if not strong and not a.no_strong:
+    if a.full and not strong and not a.no_strong:
         strong_step()
         sync()
         reps = 3
@@ -467,7 +513,7 @@ def main():
                         "inside the boxes, whole job"}
 
     frames_sha = None
-    if strong and rank == 0 and out is not None and out[0] is not None:
+    if a.full and strong and rank == 0 and out is not None and out[0] is not None:
         # checksum of the last step's assembled frames: a multi-GPU run must reproduce the single-device bytes
         # (groups stay whole) -- tests/test_gpu_configs.py compares the two
         import hashlib
@@ -553,7 +599,7 @@ def main():
                 result["roofline"]["issued_from"] = (f"SQ_INSTS_MFMA {ins:.4g} per launch x {per} FLOP (profiles/{tname}, commit "
                                                      f"{tj.get('commit', 'unrecorded')}) over points per launch x {flops_pt} algorithmic FLOP")
             break
-    if a.prec in ("bf16", "fp16", "fp16c") and world == 1 and not a.no_extras:    # (not in the profiled command: their launches carry the headline kernel's name)
+    if a.full and a.prec in ("bf16", "fp16", "fp16c") and world == 1 and not a.no_extras:    # (not in the profiled command: their launches carry the headline kernel's name)
         nf, z = r.stage_sample_coarse(rb, cyl, cfg.n_samples)
         result["roofline"]["limb_masks"] = dict(r.limb_skip_stats(0, rb, z, skts),
                                                 what=f"coarse launch of the benchmark frame ({cfg.n_samples} samples per ray), counted by the kernel: "
@@ -578,7 +624,7 @@ def main():
     # What this box SUSTAINS on bare 32x32x16 MFMAs (register operands, 2 waves per SIMD on every CU,
     # nothing else in the loop, one >= 20 ms launch): `peak` stays the nominal dense figure, this says how
     # much of the gap is the chip's clock management under MFMA load rather than the kernel's stalls.
-    if a.prec != "fp32" and world == 1:
+    if a.full and a.prec != "fp32" and world == 1:
         # the shape of the kernel that ran: 16x16x32 for the 16-bit modes (pg_eval16r.hip), 32x32x16 for the compensated one
         small = 2 if a.prec in ("bf16", "fp16", "fp16c") else 0
         shape = "16x16x32" if small else "32x32x16"
@@ -623,7 +669,7 @@ def main():
             break
 
     sel = ref = None
-    if world == 1 and not a.no_cpu_baseline:
+    if a.full and world == 1 and not a.no_cpu_baseline:
         base, sel, ref = cpu_baseline(rb_cpu, skts_cpu, cyl_cpu, cfg, model, a.cpu_rays, f"the same {H}x{W} frame")
         result["cpu_baseline"] = base
         # parity of the measured configuration on the CPU-baseline sample
@@ -636,7 +682,7 @@ def main():
                             "max_abs": err, "rgb_rmse": mse ** 0.5, "rgb_mse": mse,
                             "rgb_psnr_db": -10 * np.log10(max(mse, 1e-30))}
 
-    if world == 1 and not a.no_modes:
+    if a.full and world == 1 and not a.no_modes:
         modes = {}
         for name in ("fp16m", "fp16c", "fp16", "bf16x3", "fp32"):
             if name == a.prec or name not in PREC_BY_NAME:
@@ -680,7 +726,7 @@ def main():
             else:
                 result["north_star_mode"] = None
 
-    if world == 1 and not a.no_extras:
+    if a.full and world == 1 and not a.no_extras:
         result["host_to_host"] = host_to_host(caster, cfg, dev, H, W)
         # SURVEY 8(d)'s metric on the HEADLINE workload: the same all-hit frame, pose tensors on the host -> float
         # frames on the host through render_path (the cylinder of radius 2.5 projects to the whole frame)

@@ -344,7 +344,7 @@ def test_two_process_rccl_strong_scaling_equals_the_single_device_frames():
     from bench import strong_workload
     from posegen_amd.raycaster import HipRayCaster
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--scaling", "strong", "--frames", "5", "--res", "128",
-           "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-modes", "--no-extras"]
+           "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-modes", "--no-extras"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=REPO)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]

@@ -286,7 +286,7 @@ def test_bench_launches_itself_for_n_gpus_dry_run():
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                          "--res", "64", "--dry-run"], capture_output=True, text=True, timeout=300, env=env)
+                          "--res", "64", "--dry-run", "--full"], capture_output=True, text=True, timeout=300, env=env)
     assert out.returncode == 0, out.stdout[-1000:] + out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, lines
@@ -310,6 +310,45 @@ def test_bench_launches_itself_for_n_gpus_dry_run():
     bad = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--prec", "nope", "--dry-run"],
                          capture_output=True, text=True, timeout=300, env=env)
     assert bad.returncode != 0 and not bad.stdout.strip()
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_last_step(tmp_path, monkeypatch):
+    """A plain `bench.py` run carries the headline and nothing that `--full` adds; `--dump-outputs DIR` writes the
+    arrays the last timed step returned as float32 .npy files, the same bytes from run to run; an array over its share
+    of the budget is cut to the same seeded rows every time."""
+    import json
+    import bench
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    full_only = ("strong_scaling", "cpu_baseline", "cpu_baselines", "parity", "modes", "north_star_mode", "host_to_host",
+                 "workloads", "train_step", "frames_sha256")
+    for scaling, names in (("weak", ("rgb_map", "disp_map", "acc_map")), ("strong", ("rgb", "disp", "acc", "bboxes"))):
+        dumps = []
+        for run in range(2):
+            d = tmp_path / f"{scaling}{run}"
+            out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "3", "--warmup", "1", "--res", "64",
+                                  "--dry-run", "--scaling", scaling, "--frames", "3", "--dump-outputs", str(d)],
+                                 capture_output=True, text=True, timeout=300, env=env)
+            assert out.returncode == 0, out.stdout[-1000:] + out.stderr[-3000:]
+            lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+            assert len(lines) == 1, lines
+            j = json.loads(lines[0])
+            assert j["steps"] == 3 and j["warmup"] == 1 and j["ms_per_step"] > 0 and j["value"] > 0
+            assert not set(full_only) & set(j), sorted(set(full_only) & set(j))
+            got = {p.stem: np.load(p) for p in d.iterdir()}
+            assert sorted(got) == sorted(names)
+            assert all(v.dtype == np.float32 for v in got.values())
+            dumps.append(got)
+        for k in names:
+            assert np.array_equal(dumps[0][k], dumps[1][k], equal_nan=True), k
+    # over budget: a seeded sample of whole rows, float64 kept as float64
+    monkeypatch.setattr(bench, "DUMP_BYTES", 2 * 3000)
+    x = torch.arange(3 * 1000, dtype=torch.float32).reshape(1000, 3)
+    for d in ("s0", "s1"):
+        bench.dump_outputs(str(tmp_path / d), {"x": x, "y": np.arange(10, dtype=np.float64)})
+    s0, s1 = np.load(tmp_path / "s0" / "x.npy"), np.load(tmp_path / "s1" / "x.npy")
+    assert s0.shape == (250, 3) and np.array_equal(s0, s1) and s0.nbytes <= 3000
+    assert np.array_equal(s0[:, 1] - s0[:, 0], np.ones(250, np.float32)), "whole rows"
+    assert np.load(tmp_path / "s0" / "y.npy").dtype == np.float64
 
 
 def test_inline_asm_ring_reads_are_not_touched_by_the_compiler():
