@@ -365,7 +365,7 @@ def embed_points(pts, rays_d, skts, cfg: OracleConfig, cams=None):
     xd = _cutoff_embed(e, v, cfg.multires_views, cfg.tau_d, cfg.cutoff_dist, 3)
     parts = [xv, r, xd]
     if cams is not None:
-        parts.append(cams.view(-1, 1, 1).to(torch.float32).expand(n, s, 1))
+        parts.append(cams.view(-1, 1, 1).to(pts.dtype).expand(n, s, 1))
     return torch.cat(parts, dim=-1)
 
 

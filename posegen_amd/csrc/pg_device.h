@@ -277,7 +277,7 @@ struct Stream {
         return;
 #endif
         const uint8_t* sbase = wstream + (cur_src + i * 1024);      // wave-uniform
-        asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, %2"
+        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2"
                      :: "s"(ring_lds + cur_dst + i * 1024), "v"(lane16), "s"(sbase) : "memory");
     }
     __device__ __forceinline__ const uint8_t* at(int /*chunk*/, int byte_off) const {

@@ -84,7 +84,7 @@ static_assert(LDSO_Y % 16 == 0 && LDSO_SK % 16 == 0 && LDSO_STAGE % 16 == 0 && L
 // one LDS-DMA piece (1 KiB, lane-linear) from a wave-uniform source to a wave-uniform LDS address; counted by the
 // chunk entries' vmcnt like the ring's own pieces
 __device__ __forceinline__ void dma_piece_c(const uint8_t* src, uint32_t lds_dst, uint32_t lane16) {
-    asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, %2" PG_REC_POLICY :: "s"(lds_dst), "v"(lane16), "s"(src) : "memory");
+    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" PG_REC_POLICY :: "s"(lds_dst), "v"(lane16), "s"(src) : "memory");
 }
 
 // ---- the A operand pair pipe -------------------------------------------------------------------
@@ -128,7 +128,7 @@ __device__ __forceinline__ void piece_c(PairPipe<NS>& p, const ST& st, int i) {
         asm volatile("" : "+s"(p.g), "+s"(p.m));
     }
     switch (i & 3) {
-#define PG_PC(K) case K: asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, %2 offset:" #K "*1024" \
+#define PG_PC(K) case K: asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 offset:" #K "*1024" \
                                       :: "s"(p.m), "v"(st.lane16), "s"(p.g) : "memory"); break;
         PG_PC(0) PG_PC(1) PG_PC(2) PG_PC(3)
 #undef PG_PC

@@ -550,7 +550,7 @@ using LG256 = LG<16, 0, PG_LG_ROWS, PG_LG_NBUF>;             // a 256 x 256 laye
 using LG432 = LG<27, 0, 32, 4>;                              // layer 0: K = 432
 using LGSKIP = LG<16, 27, 32, 3>;                            // the skip layer: [h (256) | x (432)]
 __device__ __forceinline__ void lg_dma(const bf16_t* base, unsigned lane_off, unsigned lds_dst) {
-    asm volatile("s_nop 4\n\ts_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, %2" :: "s"(lds_dst), "v"(lane_off), "s"(base) : "memory");
+    asm volatile("s_nop 4\n\ts_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" :: "s"(lds_dst), "v"(lane_off), "s"(base) : "memory");
 }
 template <typename G>
 struct LGK;
@@ -1072,6 +1072,37 @@ bool lgemm_enabled() {
     static const bool on = [] { const char* e = std::getenv("POSEGEN_LGEMM"); return !(e && e[0] == '0'); }();
     return on;
 }
+// 16-byte loads: the contiguous index in runs of 4 floats / 8 bf16, every other stride and the base aligned likewise
+inline bool aligned16(const void* p, long long stride, bool bf) { return reinterpret_cast<uintptr_t>(p) % 16 == 0 && stride % (bf ? 8 : 4) == 0; }
+// the shapes and layouts the 128-tile kernels (and the persistent kernel) load with 16-byte loads: M, N >= 64, aligned operands
+inline bool tile128_ok(bool a_kcont, bool b_kcont, int M, int N, int K, const void* A, long long sam, long long sak,
+                       const void* B, long long sbk, long long sbn, int dt) {
+    const bool abf = dt & DT_A, bbf = dt & DT_B;
+    const int qa = abf ? 8 : 4, qb = bbf ? 8 : 4;
+    return M >= 64 && N >= 64 && aligned16(A, a_kcont ? sam : sak, abf) && aligned16(B, b_kcont ? sbn : sbk, bbf) &&
+           (a_kcont ? K % qa == 0 : M % qa == 0) && (b_kcont ? K % qb == 0 : N % qb == 0);
+}
+// a second k segment in the 128-tile kernel: bf16 k-contiguous operands, the first segment a multiple of the k-step
+inline bool seg2_tile_ok(const Tape& t, bool a_kcont, bool b_kcont, int K, int ksplit, int dt, const KSeg2* seg2) {
+    return t.bf16 && (dt & DT_A) && (dt & DT_B) && a_kcont && b_kcont && ksplit == 1 && K % BK == 0 && seg2->K % 8 == 0 && seg2->sam % 8 == 0 &&
+           seg2->sbn % 8 == 0 && reinterpret_cast<uintptr_t>(seg2->A) % 16 == 0 && reinterpret_cast<uintptr_t>(seg2->B) % 16 == 0;
+}
+// Does gemm() with these arguments run on the persistent layer kernel (a 256-wide layer of the 16-bit mode: K = 256, K = 432,
+// or the skip layer's two segments [h (256) | x (432)])?  Only that kernel takes a second k segment or a rank-1 term, so the
+// callers that would pass one ask this first and otherwise split the work into plain GEMMs.
+bool lgemm_takes(const Tape& t, bool a_kcont, bool b_kcont, int M, int N, int K, const void* A, long long sam, long long sak,
+                 const void* B, long long sbk, long long sbn, const void* C, long long ldc, int flags, int ksplit, const void* mask,
+                 long long ldm, const float* rowsum, int dt, const float* cin, long long ldcin, const KSeg2* seg2) {
+    const bool abf = dt & DT_A, bbf = dt & DT_B;
+    const bool seg_skip = seg2 && K == 256 && seg2->K == 432 && seg2->sam % 8 == 0 && seg2->sbn % 8 == 0 &&
+                          reinterpret_cast<uintptr_t>(seg2->A) % 16 == 0 && reinterpret_cast<uintptr_t>(seg2->B) % 16 == 0;
+    return lgemm_enabled() && tile128_ok(a_kcont, b_kcont, M, N, K, A, sam, sak, B, sbk, sbn, dt) &&
+           t.bf16 && abf && bbf && (dt & DT_C) && a_kcont && b_kcont && N == 256 && ksplit == 1 && !rowsum &&
+           ((!seg2 && (K == 256 || K == 432)) || seg_skip) &&
+           sak == 1 && sbk == 1 && ldc % 8 == 0 && reinterpret_cast<uintptr_t>(C) % 16 == 0 &&
+           (!mask || ((dt & DT_M) && ldm % 8 == 0 && reinterpret_cast<uintptr_t>(mask) % 16 == 0)) &&
+           (!(flags & GEMM_ACC) || (ldcin % 4 == 0 && reinterpret_cast<uintptr_t>(cin) % 16 == 0));
+}
 int gemm(pg_handle* h, hipStream_t s, bool a_kcont, bool b_kcont, int M, int N, int K, const void* A, long long sam, long long sak,
          const void* B, long long sbk, long long sbn, void* C, long long ldc, const float* bias, int flags, int ksplit = 1,
          const void* mask = nullptr, long long ldm = 0, float* rowsum = nullptr, int dt = 0, const float* cin = nullptr, long long ldcin = 0,
@@ -1092,22 +1123,10 @@ int gemm(pg_handle* h, hipStream_t s, bool a_kcont, bool b_kcont, int M, int N, 
     auto reduce = [&](const float* part, int nz, int rows, int cols, float* out, long long ldo) {
         hipLaunchKernelGGL(reduce_parts_kernel, dim3((unsigned)(((long long)rows * cols + 255) / 256)), dim3(256), 0, s, part, nz, rows, cols, out, ldo);
     };
-    // 16-byte loads: the contiguous index in runs of 4 floats / 8 bf16, every other stride and the base aligned likewise
-    auto aligned = [](const void* p, long long stride, bool bf) { return reinterpret_cast<uintptr_t>(p) % 16 == 0 && stride % (bf ? 8 : 4) == 0; };
     const bool abf = dt & DT_A, bbf = dt & DT_B;
-    const int qa = abf ? 8 : 4, qb = bbf ? 8 : 4;
-    bool big = M >= 64 && N >= 64 && aligned(A, a_kcont ? sam : sak, abf) && aligned(B, b_kcont ? sbn : sbk, bbf) &&
-               (a_kcont ? K % qa == 0 : M % qa == 0) && (b_kcont ? K % qb == 0 : N % qb == 0);
+    const bool big = tile128_ok(a_kcont, b_kcont, M, N, K, A, sam, sak, B, sbk, sbn, dt);
     if ((abf || bbf) && !t.bf16) return pg_fail(h, PG_EINVAL, "bf16 GEMM operands outside the 16-bit mode");
-    // a 256-wide layer of the 16-bit mode on the persistent kernel: K = 256 (forward / dX of the trunk's plain layers, feature_linear),
-    // K = 432 (layer 0) or the skip layer's two segments [h (256) | x (432)]
-    const bool seg_skip = seg2 && K == 256 && seg2->K == 432 && seg2->sam % 8 == 0 && seg2->sbn % 8 == 0 &&
-                          reinterpret_cast<uintptr_t>(seg2->A) % 16 == 0 && reinterpret_cast<uintptr_t>(seg2->B) % 16 == 0;
-    if (lgemm_enabled() && big && t.bf16 && abf && bbf && (dt & DT_C) && a_kcont && b_kcont && N == 256 && ksplit == 1 && !rowsum &&
-        ((!seg2 && (K == 256 || K == 432)) || seg_skip) &&
-        sak == 1 && sbk == 1 && ldc % 8 == 0 && reinterpret_cast<uintptr_t>(C) % 16 == 0 &&
-        (!mask || ((dt & DT_M) && ldm % 8 == 0 && reinterpret_cast<uintptr_t>(mask) % 16 == 0)) &&
-        (!(flags & GEMM_ACC) || (ldcin % 4 == 0 && reinterpret_cast<uintptr_t>(cin) % 16 == 0))) {
+    if (lgemm_takes(t, a_kcont, b_kcont, M, N, K, A, sam, sak, B, sbk, sbn, C, ldc, flags, ksplit, mask, ldm, rowsum, dt, cin, ldcin, seg2)) {
         auto launch = [&](auto kern, int lds, int rows, int wgs, std::atomic<unsigned long long>& attr_done) -> int {
             if (!(attr_done.load(std::memory_order_acquire) & (1ull << (h->device & 63)))) {      // the opt-in to > 64 KiB of dynamic LDS is per (kernel, device)
                 PG_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
@@ -1133,8 +1152,7 @@ int gemm(pg_handle* h, hipStream_t s, bool a_kcont, bool b_kcont, int M, int N, 
         bool launched = true;
 #define PG_BGEMM(AK, BK_) hipLaunchKernelGGL((bgemm128_kernel<AK, BK_>), g, dim3(256), 0, s, M, N, K, static_cast<const bf16_t*>(A), sam, sak, static_cast<const bf16_t*>(B), sbk, sbn, C, ldc, bias, flags, mask, ldm, rowsum, t.part, t.rs_part, dt, cin, ldcin, sg)
         const KSeg2 sg = seg2 ? *seg2 : KSeg2{nullptr, nullptr, 0, 0, 0};
-        if (seg2 && !(t.bf16 && abf && bbf && a_kcont && b_kcont && ksplit == 1 && K % BK == 0 && seg2->K % 8 == 0 && seg2->sam % 8 == 0 &&
-                      seg2->sbn % 8 == 0 && reinterpret_cast<uintptr_t>(seg2->A) % 16 == 0 && reinterpret_cast<uintptr_t>(seg2->B) % 16 == 0))
+        if (seg2 && !seg2_tile_ok(t, a_kcont, b_kcont, K, ksplit, dt, seg2))
             return pg_fail(h, PG_EINVAL, "two-segment GEMM: bf16 k-contiguous operands, first segment a multiple of the k-step");
         if (t.bf16) {       // the operand layouts the 16-bit training step uses: forward, dX, dW
             if (!(abf && bbf)) launched = false;
@@ -1214,11 +1232,19 @@ int linear_fwd(pg_handle* h, hipStream_t s, long long P, int out, int in, const 
     return gemm(h, s, true, true, (int)P, out, in, X, ldx, 1, W, 1, ldw, Y, ldy, b, flags, 1, nullptr, 0, nullptr, dt, cin, ldcin);
 }
 // Y[P,out] = [X1 | X2] [W1 | W2]^T + b (relu): a layer on the concatenation of two inputs in ONE pass (16-bit mode: no fp32
-// partial sum through HBM); in1 a multiple of the k-step
+// partial sum through HBM); in1 a multiple of the k-step.  Where neither two-segment kernel takes the shape (the persistent
+// kernel and the 128-tile kernel both want M >= 64), the X2 part goes to the fp32 array tmp and the X1 part adds it, rounded once
 int linear_fwd2(pg_handle* h, hipStream_t s, long long P, int out, int in1, const void* X1, long long ldx1, const void* W1, long long ldw1,
-                int in2, const void* X2, long long ldx2, const void* W2, long long ldw2, void* Y, long long ldy, const float* b, int flags) {
+                int in2, const void* X2, long long ldx2, const void* W2, long long ldw2, void* Y, long long ldy, const float* b, int flags,
+                float* tmp) {
     const KSeg2 sg{static_cast<const bf16_t*>(X2), static_cast<const bf16_t*>(W2), ldx2, ldw2, in2};
-    return gemm(h, s, true, true, (int)P, out, in1, X1, ldx1, 1, W1, 1, ldw1, Y, ldy, b, flags, 1, nullptr, 0, nullptr, DT_A | DT_B | DT_C, nullptr, 0, &sg);
+    const int ABC = DT_A | DT_B | DT_C;
+    const Tape& t = *tape_of(h);
+    if (lgemm_takes(t, true, true, (int)P, out, in1, X1, ldx1, 1, W1, 1, ldw1, Y, ldy, flags, 1, nullptr, 0, nullptr, ABC, nullptr, 0, &sg) ||
+        (tile128_ok(true, true, (int)P, out, in1, X1, ldx1, 1, W1, 1, ldw1, ABC) && seg2_tile_ok(t, true, true, in1, 1, ABC, &sg)))
+        return gemm(h, s, true, true, (int)P, out, in1, X1, ldx1, 1, W1, 1, ldw1, Y, ldy, b, flags, 1, nullptr, 0, nullptr, ABC, nullptr, 0, &sg);
+    const int rc = linear_fwd(h, s, P, out, in2, X2, ldx2, W2, ldw2, tmp, out, nullptr, 0, DT_A | DT_B);
+    return rc ? rc : linear_fwd(h, s, P, out, in1, X1, ldx1, W1, ldw1, Y, ldy, b, flags | GEMM_ACC, ABC, tmp, out);
 }
 // dX[P,in] (+)= dY[P,out] W[out,in]
 // relu_of: the stored post-activation the consumer of dX was ReLU'd to -- dX is zeroed where it is <= 0 (fused ReLU backward)
@@ -1313,7 +1339,7 @@ int mlp_forward(pg_handle* h, hipStream_t s, Tape& t, int net, const Pass& p, co
         if (l == SKIP + 1 && bf) {  // h = cat([x, h]) in front of layer 5 (nerf.py:99-101): the h part's 256 columns first (a whole
                                     // number of k-steps), then the x part's 432
             PG_TRY(linear_fwd2(h, s, P, W, W, p.H[l - 1], W, WT(2 * l, CH_X), CH_X + W, CH_X, p.X, XW, WT(2 * l, 0), CH_X + W, p.H[l], W,
-                               w.w[2 * l + 1], GEMM_RELU));
+                               w.w[2 * l + 1], GEMM_RELU, t.tmpF));
         } else if (l == SKIP + 1) {
             PG_TRY(linear_fwd(h, s, P, W, CH_X, p.X, XW, WT(2 * l, 0), CH_X + W, p.H[l], W, nullptr, 0, AB));
             PG_TRY(linear_fwd(h, s, P, W, W, p.H[l - 1], W, WT(2 * l, CH_X), CH_X + W, p.H[l], W, w.w[2 * l + 1], GEMM_ACC | GEMM_RELU, ABC));
@@ -1325,7 +1351,7 @@ int mlp_forward(pg_handle* h, hipStream_t s, Tape& t, int net, const Pass& p, co
     PG_TRY(linear_fwd(h, s, P, 1, W, h7, W, w.w[16], W, p.raw + 3, 4, w.w[17], 0, A_));
     PG_TRY(linear_fwd(h, s, P, W, W, h7, W, WT(18, 0), W, p.F, W, w.w[19], 0, ABC));
     if (bf) {
-        PG_TRY(linear_fwd2(h, s, P, VW, W, p.F, W, WT(20, 0), vcols, vk, el_off(p.X, CH_X, es), XW, WT(20, W), vcols, p.G, VW, w.w[21], GEMM_RELU));
+        PG_TRY(linear_fwd2(h, s, P, VW, W, p.F, W, WT(20, 0), vcols, vk, el_off(p.X, CH_X, es), XW, WT(20, W), vcols, p.G, VW, w.w[21], GEMM_RELU, t.tmpF));
     } else {
         PG_TRY(linear_fwd(h, s, P, VW, W, p.F, W, WT(20, 0), vcols, p.G, VW, nullptr, 0, AB));
         PG_TRY(linear_fwd(h, s, P, VW, vk, el_off(p.X, CH_X, es), XW, WT(20, W), vcols, p.G, VW, w.w[21], GEMM_ACC | GEMM_RELU, ABC));
@@ -1368,7 +1394,9 @@ int mlp_backward(pg_handle* h, hipStream_t s, Tape& t, int net, const Pass& p, c
     const void* h7 = p.H[DEPTH - 1];
     PG_TRY(linear_bwd_w(h, s, P, W, W, dF, W, h7, W, g.w[18], W, g.w[19], AB));
     void* dH = t.tmpB;              // dH7 = (alpha's part + feature's part) * [H7 > 0]: the mask rides on the second GEMM
-    if (bf && lgemm_enabled()) {    // 16-bit mode: alpha's part d sigma (x) w_alpha rides in the feature GEMM's epilogue as a rank-1 term (fp32)
+    // 16-bit mode on the persistent kernel: alpha's part d sigma (x) w_alpha rides in the feature GEMM's epilogue as a rank-1 term
+    // (fp32); the arguments are those linear_bwd_x hands gemm() below
+    if (bf && lgemm_takes(t, true, true, (int)P, W, W, dF, W, 1, t.wbT[net][18], 1, W, dH, W, 0, 1, h7, W, nullptr, ABCM, nullptr, 0, nullptr)) {
         const Rank1 r1{d_raw + 3, 4, w.w[16]};
         PG_TRY(linear_bwd_x(h, s, P, W, W, dF, W, WT(18, 0), W, dH, W, 0, h7, ABCM, nullptr, 0, t.wbT[net][18], &r1));
     } else {
@@ -1499,13 +1527,13 @@ int pg_train_forward(pg_handle* h, void* stream, int64_t n, const float* ray_bat
             for (int i = 0; i < 24; ++i) {
                 if (!wsize[i]) continue;
                 const float* src = (k ? fine : coarse)->w[i];
+                if (nj + (tblock[i].rows ? 2 : 1) > WJOBS_MAX) return pg_fail(h, PG_EINVAL, "weight conversion: more than %d jobs", WJOBS_MAX);
                 js.j[nj++] = WJob{src, t.wb[k][i], 0, 1, (int)wsize[i], 0};
                 if (tblock[i].rows) {
                     const long long ldw = (long long)(wsize[i] / tblock[i].rows);       // (= the matrix's column count)
                     js.j[nj++] = WJob{src + tblock[i].col0, t.wbT[k][i], ldw, tblock[i].rows, tblock[i].cols, 1};
                 }
             }
-        if (nj > WJOBS_MAX) return pg_fail(h, PG_EINVAL, "weight conversion: %d jobs", nj);
         hipLaunchKernelGGL(cvt_weights_kernel, dim3(64, nj), dim3(256), 0, s, js);
         PG_LAUNCH_CHECK(h, "weight conversion");
     }

@@ -1,4 +1,5 @@
 """Shared test helpers: fixture loading and oracle plumbing."""
+import contextlib
 import os
 
 import numpy as np
@@ -70,3 +71,42 @@ def oracle_render_rays(g, cfg, extras=True):
                            torch.tensor(g["cyl"]), ocfg, torch_weights(wc), torch_weights(wf),
                            cfg.n_samples, cfg.n_importance, cams=cams, return_extras=extras,
                            draws=golden_draws(g))
+
+
+def loss_of(out, target):
+    """Trainer.compute_loss for the shipped surreal config (core/trainer.py:321-383): both passes' photometric losses."""
+    loss = torch.mean((out["rgb_map"] + (1. - out["acc_map"])[..., None] - target) ** 2)
+    if "rgb0" in out:
+        loss = loss + torch.mean((out["rgb0"] + (1. - out["acc0"])[..., None] - target) ** 2)
+    return loss
+
+
+@contextlib.contextmanager
+def default_dtype(dtype):
+    """torch's default dtype set for the block (the oracle makes its constants -- linspace, ones, tau -- in it)."""
+    prev = torch.get_default_dtype()
+    torch.set_default_dtype(dtype)
+    try:
+        yield
+    finally:
+        torch.set_default_dtype(prev)
+
+
+def oracle_grads(cfg, wc, wf, tau_v, tau_d, ray_batch, skts, cyls, target, n_samples, n_importance, cams=None, draws=None,
+                 lindisp=False, dtype=torch.float64):
+    """One training step of the oracle under torch autograd on the CPU, every input and constant in `dtype`:
+    render_rays + loss_of + backward().  Returns (loss, maps, grads): the four maps the loss reads, and the gradient of
+    every parameter tensor of both nets as float64 numpy arrays keyed (tag, name), tag "coarse" / "fine" (no "fine"
+    entries when n_importance == 0: the fine net is not on the tape)."""
+    cast = lambda x: None if x is None else torch.as_tensor(x).detach().cpu().to(dtype)
+    with default_dtype(dtype):
+        nets = {"coarse": {k: torch.tensor(np.asarray(v), dtype=dtype, requires_grad=True) for k, v in wc.items()},
+                "fine": {k: torch.tensor(np.asarray(v), dtype=dtype, requires_grad=True) for k, v in wf.items()}}
+        dr = {k: cast(v) for k, v in draws.items()} if draws else None
+        out = orc.render_rays(cast(ray_batch), cast(skts), cast(cyls), oracle_cfg(cfg, tau_v, tau_d), nets["coarse"], nets["fine"],
+                              n_samples, n_importance, cams=cast(cams), lindisp=lindisp, draws=dr)
+        loss = loss_of(out, cast(target))
+        loss.backward()
+    maps = {k: out[k].detach().double().numpy() for k in ("rgb_map", "acc_map", "rgb0", "acc0") if k in out}
+    grads = {(tag, k): p.grad.double().numpy() for tag, net in nets.items() for k, p in net.items() if p.grad is not None}
+    return float(loss.detach()), maps, grads

@@ -514,3 +514,74 @@ def test_hazard_audit_flags_a_transcendental_result_read_by_the_next_instruction
         f.write_text(text)
         r = subprocess.run([sys.executable, tool, str(f)], capture_output=True, text=True)
         assert r.returncode == rc, (name, r.stdout)
+
+
+def _hazard_audit(tmp_path, cases):
+    """run tools/audit_asm_hazards.py on each snippet; {name: exit status}"""
+    import subprocess
+    import sys
+    tool = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools", "audit_asm_hazards.py")
+    got = {}
+    for name, text in cases.items():
+        f = tmp_path / f"{name}.s"
+        f.write_text(text)
+        got[name] = subprocess.run([sys.executable, tool, str(f)], capture_output=True, text=True).returncode
+    return got
+
+
+def test_hazard_audit_flags_an_lds_dma_right_behind_a_write_of_m0(tmp_path):
+    """The M0 rule: an LDS-DMA instruction (global_load_lds_* / buffer_load_* .. lds) takes its LDS address from M0 and needs
+    one wait state behind the SALU write of M0; hipcc pads its own, not the `s_mov_b32 m0` + load of one inline-asm statement.
+    Checked in every kernel, MFMA or not, in program order (a label in between falls through)."""
+    asm = lambda body: "\t;;#ASMSTART\n" + body + "\t;;#ASMEND\n"
+    plain = "_Z4copyv:\n\tv_mov_b32_e32 v2, 0\n"              # no MFMA in this kernel
+    mfma = "_Z6kernelv:\n\tv_mfma_f32_32x32x16_f16 a[0:15], v[0:3], v[4:7], a[0:15]\n"
+    cases = {
+        "bad": plain + asm("\ts_nop 4\n\ts_mov_b32 m0, s50\n\tglobal_load_lds_dwordx4 v2, s[4:5]\n") + "\ts_endpgm\n",
+        "good": plain + asm("\ts_nop 4\n\ts_mov_b32 m0, s50\n\ts_nop 0\n\tglobal_load_lds_dwordx4 v2, s[4:5]\n") + "\ts_endpgm\n",
+        "bad_mfma_kernel": mfma + asm("\ts_mov_b32 m0, s3\n\tglobal_load_lds_dword v2, s[4:5] offset:1024\n") + "\ts_endpgm\n",
+        "bad_buffer": plain + "\ts_add_u32 m0, s3, 0x400\n\tbuffer_load_dword v1, s[0:3], 0 offen lds\n\ts_endpgm\n",
+        "good_other": plain + asm("\ts_mov_b32 m0, s50\n\tv_add_u32_e32 v2, 16, v2\n\tglobal_load_lds_dwordx4 v2, s[4:5]\n") + "\ts_endpgm\n",
+        "good_second": plain + asm("\ts_mov_b32 m0, s50\n\ts_nop 0\n\tglobal_load_lds_dwordx4 v2, s[4:5]\n"
+                                   "\tglobal_load_lds_dwordx4 v3, s[4:5] offset:1024\n") + "\ts_endpgm\n",
+        "bad_fallthrough": plain + "\ts_mov_b32 m0, s50\n.LBB0_1:\n\tglobal_load_lds_dwordx4 v2, s[4:5]\n\ts_endpgm\n",
+    }
+    got = _hazard_audit(tmp_path, cases)
+    assert got == {"bad": 1, "good": 0, "bad_mfma_kernel": 1, "bad_buffer": 1, "good_other": 0, "good_second": 0, "bad_fallthrough": 1}, got
+
+
+def test_hazard_audit_flags_an_inline_asm_memory_read_of_an_sgpr_a_valu_has_just_written(tmp_path):
+    """Round-5 rule: a VALU write of an SGPR (v_readlane / v_readfirstlane, a carry-out) read by an inline-asm vector-memory
+    instruction needs 5 wait states (hipcc pads its own memory instructions only)."""
+    head = "_Z6kernelv:\n\tv_mfma_f32_32x32x16_f16 a[0:15], v[0:3], v[4:7], a[0:15]\n"
+    load = "\t;;#ASMSTART\n\tglobal_load_dwordx4 v[2:5], v6, s[8:9]\n\t;;#ASMEND\n\ts_endpgm\n"
+    cases = {
+        "bad": head + "\tv_readlane_b32 s9, v1, 0\n" + load,
+        "bad_nop3": head + "\tv_readlane_b32 s9, v1, 0\n\ts_nop 3\n" + load,             # 4 wait states: one short
+        "good_nop4": head + "\tv_readlane_b32 s9, v1, 0\n\ts_nop 4\n" + load,
+        "bad_carry": head + "\tv_add_co_u32_e32 v1, s[8:9], v2, v3\n" + load,
+        "good_other_sgpr": head + "\tv_readfirstlane_b32 s12, v1\n" + load,
+        "good_compiler": head + "\tv_readlane_b32 s9, v1, 0\n\tglobal_load_dwordx4 v[2:5], v6, s[8:9]\n\ts_endpgm\n",
+    }
+    got = _hazard_audit(tmp_path, cases)
+    assert got == {"bad": 1, "bad_nop3": 1, "good_nop4": 0, "bad_carry": 1, "good_other_sgpr": 0, "good_compiler": 0}, got
+
+
+def test_hazard_audit_flags_an_inline_asm_valu_read_of_an_mfma_result_too_early(tmp_path):
+    """Round-5 rule: a VALU instruction reading an MFMA's result needs passes + 2 + 1 wait states on gfx950 -- 7 behind a 4-pass
+    16x16x32, 11 behind an 8-pass 32x32x16; the audit asks one more as margin and checks inline-asm readers (hipcc pads its own)."""
+    m16 = "_Z6kernelv:\n\tv_mfma_f32_16x16x32_bf16 v[0:3], v[4:7], v[8:11], v[0:3]\n"
+    m32 = "_Z6kernelv:\n\tv_mfma_f32_32x32x16_bf16 v[0:15], v[16:19], v[20:23], v[0:15]\n"
+    rd = "\t;;#ASMSTART\n\tv_cvt_pk_bf16_f32 v40, v0, v1\n\t;;#ASMEND\n\ts_endpgm\n"
+    cases = {
+        "bad16": m16 + rd,
+        "bad16_nop5": m16 + "\ts_nop 5\n" + rd,
+        "good16_nop6": m16 + "\ts_nop 6\n" + rd,
+        "bad32_nop9": m32 + "\ts_nop 9\n" + rd,
+        "good32_nop10": m32 + "\ts_nop 10\n" + rd,
+        "good_other_reg": m16 + "\t;;#ASMSTART\n\tv_cvt_pk_bf16_f32 v40, v30, v31\n\t;;#ASMEND\n\ts_endpgm\n",
+        "good_compiler": m16 + "\tv_cvt_pk_bf16_f32 v40, v0, v1\n\ts_endpgm\n",
+    }
+    got = _hazard_audit(tmp_path, cases)
+    assert got == {"bad16": 1, "bad16_nop5": 1, "good16_nop6": 0, "bad32_nop9": 1, "good32_nop10": 0, "good_other_reg": 0,
+                   "good_compiler": 0}, got

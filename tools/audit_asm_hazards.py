@@ -25,6 +25,11 @@ Fourth check (round 5): "XDL (MFMA) writes a VGPR -> a VALU instruction reads it
 conversion block scheduled 5 instructions behind the last MFMA of its accumulator read it stale (pg_evalc2.hip, the first
 build with conversions between the MFMA blocks: one column tile off by a few percent).  The audit fails when an inline-asm
 VALU instruction reads a register an MFMA wrote fewer than 8 / 12 wait states before.
+
+Fifth check: "SALU writes M0 -> an LDS-DMA instruction (global_load_lds_* / buffer_load_* .. lds, whose LDS destination is
+M0) reads it" needs one wait state on gfx9-family parts (LLVM: hasReadM0LdsDmaHazard).  hipcc pads its own LDS-DMA issues,
+not an inline-asm `s_mov_b32 m0, ..` directly followed by the load in the same statement.  The audit fails on any LDS-DMA
+instruction with no wait state between it and the last write of M0, in every kernel (not only the MFMA ones).
 usage: audit_asm_hazards.py kernel.s"""
 import re
 import sys
@@ -159,11 +164,44 @@ def mfma_valu_hazards(kernel_text):
     return hits
 
 
+LDS_DMA = re.compile(r"(?:global|buffer|flat|scratch)_load_lds_\w+|buffer_load_\w+\s.*\blds\b")
+M0_WRITE = re.compile(r"s_\w+\s+m0\s*,|v_readfirstlane_b32\s+m0\s*,|v_readlane_b32\s+m0\s*,")
+
+
+def m0_lds_dma_hazards(kernel_text):
+    """LDS-DMA instructions (they read their LDS address from M0) issued in the slot right behind a write of M0"""
+    hits = []
+    since = None                # wait states since the last write of M0 in program order (a label falls through: no reset)
+    for ln in kernel_text.split("\n"):
+        code = ln.split(";")[0].strip()
+        if not code or code.startswith(".") or code.endswith(":"):
+            continue
+        if LDS_DMA.match(code):
+            if since is not None and since < 1:
+                hits.append(code)
+            since = None if since is None else since + 1
+            continue
+        m = re.match(r"s_nop\s+(\d+)", code)
+        if M0_WRITE.match(code):
+            since = 0
+        elif since is not None:
+            since += int(m.group(1)) + 1 if m else 1
+    return hits
+
+
 txt = open(sys.argv[1]).read()
 bad = 0
 for k in re.split(r'\n(?=_Z\w+:)', txt):
     m = re.match(r'(_Z\w+):', k)
-    if not m or 'v_mfma' not in k:
+    if not m:
+        continue
+    mh = m0_lds_dma_hazards(k)
+    for t in mh[:5]:
+        print(f"{m.group(1)[:70]}: LDS-DMA in the slot right behind a write of M0: {t}")
+    if mh:
+        print(f"{m.group(1)[:70]}: {len(mh)} LDS-DMA instructions right behind a write of M0")
+    bad += len(mh)
+    if 'v_mfma' not in k:
         continue
     hits = [(i, ln.strip()) for i, ln in enumerate(k.split('\n')) if re.match(r'\s+v_pk_(mul|add|fma)_f32', ln)]
     n_mfma = len(re.findall(r'\n\s+v_mfma', k))
