@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define PG_ABI_VERSION 10
+#define PG_ABI_VERSION 11
 
 /* error codes */
 #define PG_OK 0
@@ -55,7 +55,8 @@ extern "C" {
                              * a speed / accuracy point between fp16 (2.5e-4 / 2.9e-4) and fp16c (5e-6 /
                              * 8e-6) at 1.3x fp16c's rate, not as an in-tolerance mode; bound asserted in the
                              * tests: 2e-4.
-                             * rgb0/disp0/acc0/alpha0 are plain fp16's. */
+                             * rgb0/disp0/acc0/alpha0 are plain fp16's.  With single_net the coarse raw enters
+                             * the returned maps, so no pass is a guide pass: fp16c throughout. */
 #define PG_PREC_MODES 7
 
 /* density activation of raw2outputs (get_density_fn, core/raycasters.py:230-238) */
@@ -68,12 +69,15 @@ extern "C" {
 /* Network / embedding description: the subset of the reference's flags that shapes
  * the renderer (run_nerf.py:186-490; create_raycaster, core/raycasters.py:17-184).
  * The kernels are specialised for the architecture every shipped reference config
- * uses: 24 joints, multires 7/4/0, 8x256 trunk with the skip after layer 4,
- * 128-wide view layer; pg_create rejects anything else with PG_EINVAL. */
+ * uses: 24 joints, multires 7/{4,0}/0, 8x256 trunk with the skip after layer 4,
+ * 128-wide view layer; pg_create rejects anything else with PG_EINVAL.
+ * multires_views = 0 (configs/surreal/surreal_single.txt) is the row 0 (v * w) of the
+ * multires_views = 4 embedding: its [128, 256+72(+16)] view weight is widened once where
+ * weights enter the handle (sin/cos columns zero), and every kernel runs the 4-band layout. */
 typedef struct pg_config {
     int32_t n_joints;        /* 24                       SMPLSkeleton                 */
     int32_t multires;        /* 7                        --multires                   */
-    int32_t multires_views;  /* 4                        --multires_views             */
+    int32_t multires_views;  /* 4 or 0                   --multires_views             */
     int32_t multires_bones;  /* 0                        --multires_bones             */
     int32_t net_depth;       /* 8                        --netdepth                   */
     int32_t net_width;       /* 256                      --netwidth                   */
@@ -89,7 +93,13 @@ typedef struct pg_config {
     float softplus_shift;    /* --softplus_shift (used when density_act == PG_ACT_SOFTPLUS)       */
     int32_t density_act;     /* --density_type: PG_ACT_RELU | PG_ACT_SOFTPLUS (get_density_fn,
                               * core/raycasters.py:230-238: the act_fn of raw2outputs, nerf.py:164) */
-    int32_t reserved0;
+    int32_t single_net;      /* 0 | 1                    --single_net: network_fine is network
+                              * (core/raycasters.py:99-104, 446-469): one set of weights (net 0);
+                              * the importance pass evaluates only the N_importance new points,
+                              * drawn from the is_only pdf (ray_utils.py:255-289), and the fine
+                              * maps composite the coarse and new raw merged in depth order.
+                              * PG_PREC_FP16M runs fp16c throughout (the coarse raw enters the
+                              * fine maps: no pass is a guide pass). */
 } pg_config;
 
 /* Device output pointers of one pg_render_rays call; any may be NULL (not wanted).
@@ -108,7 +118,8 @@ typedef struct pg_outputs {
     float* z_coarse;  /* [n, N_samples]                 sample_from_lineseg           */
     float* z_fine;    /* [n, N_samples+N_importance]    isample_from_lineseg (sorted) */
     float* raw_coarse;/* [n, N_samples, 4]              run_network(network)          */
-    float* raw_fine;  /* [n, N_samples+N_importance, 4] run_network(network_fine)     */
+    float* raw_fine;  /* [n, N_samples+N_importance, 4] run_network(network_fine)
+                       * (single_net: the coarse and the new raw merged in depth order) */
     float* weights0;  /* [n, N_samples]                 raw2outputs 'weights'         */
 } pg_outputs;
 
@@ -131,12 +142,13 @@ const char* pg_last_error(const pg_handle* h);   /* h may be NULL: last global e
 
 /* Replaces RayCaster.load_state_dict / load_ckpt_from_path (core/raycasters.py:768-788,
  * core/cutoff_embedder.py:227-238).  which_net: 0 = 'network_fn_state_dict' (coarse),
- * 1 = 'network_fine_state_dict'.  tensors[i] are HOST fp32 arrays in nn.Linear layout
+ * 1 = 'network_fine_state_dict' (not with single_net).  tensors[i] are HOST fp32 arrays in nn.Linear layout
  * [out,in] row-major, in this fixed order (n_tensors = 24):
  *   pts_linears.{0..7}.weight, pts_linears.{0..7}.bias,        (index 2*l, 2*l+1)
  *   alpha_linear.{weight,bias}, feature_linear.{weight,bias},
  *   views_linears.0.{weight,bias}, rgb_linear.{weight,bias}
- * shapes: 2 int64 per tensor (rows, cols; cols = 1 for biases); checked. */
+ * shapes: 2 int64 per tensor (rows, cols; cols = 1 for biases); checked.  With multires_views = 0
+ * views_linears.0.weight is [128, 256+72(+16)] (the reference's shape) and is widened here. */
 int pg_load_weights(pg_handle* h, int which_net, const float* const* tensors,
                     const int64_t* shapes, int n_tensors);
 
@@ -364,12 +376,13 @@ int pg_stage_eval(pg_handle* h, void* stream, int which_net, int64_t n, int n_sa
  * bone-relative embedding of pts [n_points,3] (device) + the trunk of net `which_net`.
  * raw [n_points,4] device: raw[:,3] = alpha_linear output (the reference's raw density, no
  * activation); raw[:,0:3] = rgb_raw for a zero view direction (ignore).  The frame code, if the
- * model has one, is the mean code. */
+ * model has one, is the mean code.  which_net = 1 on a single_net handle is PG_EINVAL. */
 int pg_query_density(pg_handle* h, void* stream, int which_net, int64_t n_points, const float* pts,
                      const float* skts, float* raw);
 
 /* raw2outputs (nerf.py:150-205) and, if n_importance > 0, isample_from_lineseg
- * (ray_utils.py:157-201, 255-289): wave-per-ray prefix-product compositing. */
+ * (ray_utils.py:157-201, 255-289): wave-per-ray prefix-product compositing.  The pdf follows the
+ * handle: is_only weights 0.5 (max(w_l, w_k) + max(w_k, w_u)) + 0.01 with single_net. */
 int pg_stage_composite(pg_handle* h, void* stream, int64_t n, int n_samples,
                        const float* ray_batch, const float* z, const float* raw,
                        float* rgb, float* disp, float* acc, float* alpha, float* weights,
@@ -440,6 +453,13 @@ int pg_debug_pack(const float* const* tensors, const int64_t* shapes, int n_tens
  * form 0: the on-chip stream of the 16x16x32 kernel, 1: pg_evalc2.hip's image, 2: the 16-row bias table. */
 int pg_debug_pack_map(const float* const* tensors, const int64_t* shapes, int n_tensors, int framecode_ch, int form,
                       int32_t* map_out, int64_t map_cap, int64_t* map_n, float* src_out, int64_t src_cap, int64_t* src_n);
+
+/* Host-only: the widening of a multires_views = 0 view weight that pg_load_weights and pg_load_weights_device apply:
+ * view_w [128, 256+72+framecode_ch] -> out [128, 256+648+framecode_ch]: columns 256..327 copied (row 0 of the 4-band
+ * embedding is v * w, the whole 0-band embedding), every sin/cos column zero, the frame-code columns moved behind.
+ * out may be NULL to query the size (floats). */
+int pg_debug_widen_views(const float* view_w, int64_t rows, int64_t cols, int framecode_ch, float* out, int64_t cap,
+                         int64_t* out_n);
 
 /* Host-only: the Y-stage weights of the factorised view layer (16-bit precisions), laid out
  * [wave 8][unit][64 lanes x 16 B] as the kernel reads them.  out may be NULL to query the size. */

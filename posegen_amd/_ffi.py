@@ -18,7 +18,7 @@ LIB_PATH = os.path.join(_HERE, "_lib", "libposegen_hip.so")
 PG_OK, PG_EINVAL, PG_ENOMEM, PG_EHIP, PG_ESTATE = 0, -1, -2, -3, -4
 PG_FLAG_LINDISP = 1
 PG_ACT_RELU, PG_ACT_SOFTPLUS = 0, 1
-PG_ABI_VERSION = 10
+PG_ABI_VERSION = 11
 
 
 class HipLibraryError(RuntimeError):
@@ -37,7 +37,7 @@ class PgConfig(C.Structure):
                 ("skip_layer", C.c_int32), ("view_width", C.c_int32), ("framecode_ch", C.c_int32),
                 ("n_framecodes", C.c_int32), ("chunk", C.c_int32), ("precision", C.c_int32),
                 ("cutoff_dist", C.c_float), ("density_scale", C.c_float), ("rgb_eps", C.c_float),
-                ("softplus_shift", C.c_float), ("density_act", C.c_int32), ("reserved0", C.c_int32)]
+                ("softplus_shift", C.c_float), ("density_act", C.c_int32), ("single_net", C.c_int32)]
 
 
 _FP = C.c_void_p  # device float*
@@ -103,6 +103,7 @@ PROTOTYPES = {
     "pg_query_density": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pg_debug_pack_map": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64,
                                     C.POINTER(C.c_int64), C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
+    "pg_debug_widen_views": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
     "pg_debug_pack_vy": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, C.c_void_p,
                                    C.c_int64, C.POINTER(C.c_int64)]),
     "pg_device_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),

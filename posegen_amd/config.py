@@ -48,6 +48,7 @@ class RenderConfig:
     softplus_shift: float = 1.0    # --softplus_shift: softplus(x - shift)
     lindisp: bool = False
     white_bkgd: bool = True
+    single_net: bool = False       # --single_net: network_fine is network (raycasters.py:99-104, 446-469)
 
     @property
     def cutoff_dist(self) -> float:
@@ -83,6 +84,8 @@ class RenderConfig:
         return 2 * mac
 
     def evals_per_ray(self) -> int:
+        if self.single_net:         # the fine pass evaluates only the N_importance new points
+            return self.n_samples + self.n_importance
         return self.n_samples + ((self.n_samples + self.n_importance) if self.n_importance > 0 else 0)
 
     def to_dict(self):
@@ -92,6 +95,13 @@ class RenderConfig:
 def surreal_config(**kw) -> RenderConfig:
     """configs/surreal/surreal.txt"""
     return RenderConfig(**kw)
+
+
+def surreal_single_config(**kw) -> RenderConfig:
+    """configs/surreal/surreal_single.txt: one net, no view frequencies, 96 coarse + 48 importance samples."""
+    base = dict(single_net=True, multires_views=0, n_samples=96, n_importance=48)
+    base.update(kw)
+    return RenderConfig(**base)
 
 
 def h36m_config(**kw) -> RenderConfig:

@@ -37,6 +37,13 @@ int pg_launch_sample_coarse(const float* rays, const float* cyls, long long cyl_
 long long pg_sample_coarse_scratch(long long n, int chunk);
 int pg_launch_gather_noise(const float* src, long long n, int stride, int S, const int* order, float* dst, void* stream);
 int pg_launch_mfma_rate(int f16, int lds_fed, int blocks, int iters, float* sink, void* stream);
+int pg_launch_composite_iso(const float* rays, const float* z, const float* raw, long long n, int S, float density_scale,
+                            float rgb_eps, int density_act, float act_shift, float* rgb, float* disp, float* acc, float* alpha,
+                            float* weights, int n_imp, float* z_fine, const float* noise, const float* u_rand, int* order,
+                            float* z_new, int ld_new, void* stream);
+int pg_launch_composite_merged(const float* rays, const float* z_fine, const float* raw_c, const float* raw_new, int ld_new, const int* order,
+                               long long n, int S0, int N, float density_scale, float rgb_eps, int density_act, float act_shift,
+                               float* rgb, float* disp, float* acc, float* alpha, const float* noise, float* raw_out, void* stream);
 int pg_launch_composite(const float* rays, const float* z, const float* raw, long long n, int S,
                         float density_scale, float rgb_eps, int density_act, float act_shift, float* rgb, float* disp, float* acc,
                         float* alpha, float* weights, int n_imp, float* z_fine, const float* noise, const float* u_rand, int* order,
@@ -70,6 +77,7 @@ void pg_launch_gather16(const int32_t* map, const float* src, uint16_t* out, lon
 void pg_launch_gather32(const int32_t* map, const float* src, float* out, long long n, void* stream);
 void pg_launch_codes(const float* codes, int n_codes, float* out, void* stream);
 void pg_launch_ycode(const float* view_w, int vcols, const float* codes, int n_codes, float* yc, void* stream);
+void pg_launch_widen_views(const float* src, int framecode_ch, float* dst, void* stream);
 }
 
 namespace {
@@ -131,6 +139,33 @@ pgpack::NetTensors tensors_of(const NetState& ns, const pg_config& cfg) {
     if (ns.fold_w.empty()) { t.fold(); ns.fold_w = t.viewf_w; ns.fold_b = t.viewf_b; }      // (every packer of the net shares it)
     else { t.viewf_w = ns.fold_w; t.viewf_b = ns.fold_b; }
     return t;
+}
+
+// multires_views = 0 (cutoff_embedder.py:20-31, 199-213 with no frequency bands): the view input is v * w, 72 channels,
+// which is row 0 of the 4-band embedding (channel row*72 + 3j + c).  Its view weight [128, 256+72(+fc)] becomes the
+// [128, 256+648(+fc)] matrix with the sin/cos columns zero: a zero weight adds exact zeros in every precision (and splits
+// to zeros in the bf16x3 / fp16c forms), so no kernel changes.
+constexpr int CH_D0 = J * 3;
+void widen_view_w(const float* src, int fc, float* dst) {
+    const int sc = W + CH_D0 + fc, dc = W + CH_D + fc;
+    for (int o = 0; o < VW; ++o) {
+        const float* r = src + (size_t)o * sc;
+        float* d = dst + (size_t)o * dc;
+        std::memcpy(d, r, (size_t)(W + CH_D0) * sizeof(float));
+        std::memset(d + W + CH_D0, 0, (size_t)(CH_D - CH_D0) * sizeof(float));
+        std::memcpy(d + W + CH_D, r + W + CH_D0, (size_t)fc * sizeof(float));
+    }
+}
+
+// host copies of one net's 24 tensors (the debug packers): a [128, 256+72(+fc)] view weight is widened as the load does
+void host_copy(NetState& ns, const float* const* tensors, const int64_t* shapes, int fc) {
+    ns.host.assign(24, {});
+    for (int i = 0; i < 24; ++i) {
+        if (i == 20 && shapes[2 * i + 1] == W + CH_D0 + fc) {
+            ns.host[i].resize((size_t)VW * (W + CH_D + fc));
+            widen_view_w(tensors[i], fc, ns.host[i].data());
+        } else ns.host[i].assign(tensors[i], tensors[i] + shapes[2 * i] * shapes[2 * i + 1]);
+    }
 }
 
 // ... of a handle's net: first the host copies are brought up to date if the last weights came from the device
@@ -383,7 +418,7 @@ int ensure_mode_streams(pg_handle* h, int which, int mode) {
     };
     if (mode != PG_PREC_FP16M) return one(mode);
     int rc = one(PG_PREC_FP16C);
-    if (!rc && which == 0) rc = one(PG_PREC_FP16);
+    if (!rc && which == 0 && !h->cfg.single_net) rc = one(PG_PREC_FP16);      // (single_net: no guide pass)
     return rc;
 }
 
@@ -400,6 +435,7 @@ int ensure_ws(pg_handle* h, size_t bytes) {
 
 int check_ready(pg_handle* h, bool need_fine) {
     if (!h) return pg_fail(nullptr, PG_EINVAL, "null handle");
+    need_fine = need_fine && !h->cfg.single_net;        // single_net: network_fine is network (raycasters.py:99-104)
     if (!h->net[0].loaded) return pg_fail(h, PG_ESTATE, "coarse network weights not loaded (pg_load_weights)");
     if (need_fine && !h->net[1].loaded) return pg_fail(h, PG_ESTATE, "fine network weights not loaded (pg_load_weights)");
     if (!h->emb_set[0] || !h->emb_set[1]) return pg_fail(h, PG_ESTATE, "embedder state not set (pg_set_embedder)");
@@ -563,12 +599,13 @@ int pg_create(const pg_config* cfg, int n_devices, const int* device_ids, pg_han
     *out = nullptr;
     if (n_devices < 1 || n_devices > 64) return pg_fail(nullptr, PG_EINVAL, "pg_create: n_devices must be 1..64, got %d", n_devices);
     if (n_devices > 1 && !device_ids) return pg_fail(nullptr, PG_EINVAL, "pg_create: device_ids required for n_devices > 1");
-    if (cfg->n_joints != J || cfg->multires != LV || cfg->multires_views != LD || cfg->multires_bones != 0 ||
+    if (cfg->n_joints != J || cfg->multires != LV || (cfg->multires_views != LD && cfg->multires_views != 0) || cfg->multires_bones != 0 ||
         cfg->net_depth != DEPTH || cfg->net_width != W || cfg->skip_layer != SKIP || cfg->view_width != VW ||
         (cfg->framecode_ch != 0 && cfg->framecode_ch != FC_CH))
         return pg_fail(nullptr, PG_EINVAL,
-                    "pg_create: unsupported architecture (kernels are built for 24 joints, multires 7/4/0, "
+                    "pg_create: unsupported architecture (kernels are built for 24 joints, multires 7/{4,0}/0, "
                     "8x256 trunk, skip 4, view width 128, frame code 0|16)");
+    if (cfg->single_net != 0 && cfg->single_net != 1) return pg_fail(nullptr, PG_EINVAL, "pg_create: single_net must be 0 or 1, got %d", cfg->single_net);
     if (cfg->precision < 0 || cfg->precision >= PG_PREC_MODES) return pg_fail(nullptr, PG_EINVAL, "pg_create: bad precision %d", cfg->precision);
     if (is_x3(cfg->precision) && !x3_allowed())
         return pg_fail(nullptr, PG_EINVAL, "pg_create: split-operand precision %d is experimental (set POSEGEN_EXPERIMENTAL_X3=1)", cfg->precision);
@@ -671,6 +708,7 @@ void pg_destroy(pg_handle* h) {
         if (ns.d_map_ro) (void)hipFree(ns.d_map_ro);
         if (ns.d_map_c2) (void)hipFree(ns.d_map_c2);
         if (ns.d_map_bias_s) (void)hipFree(ns.d_map_bias_s);
+        if (ns.d_vwide) (void)hipFree(ns.d_vwide);
     }
     for (auto& pr : h->ev_used) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
     for (auto& ev : h->ev_free) (void)hipEventDestroy(ev);
@@ -683,7 +721,9 @@ int pg_load_weights(pg_handle* h, int which, const float* const* tensors, const 
     if (!h || !tensors || !shapes) return pg_fail(h, PG_EINVAL, "pg_load_weights: null argument");
     if (which < 0 || which > 1) return pg_fail(h, PG_EINVAL, "pg_load_weights: which_net must be 0 or 1");
     if (n_tensors != 24) return pg_fail(h, PG_EINVAL, "pg_load_weights: expected 24 tensors, got %d", n_tensors);
-    const int vcols = W + CH_D + h->cfg.framecode_ch;
+    if (which == 1 && h->cfg.single_net) return pg_fail(h, PG_EINVAL, "pg_load_weights: a single_net handle has one net (which_net 0)");
+    const bool views0 = h->cfg.multires_views == 0;
+    const int vcols = W + (views0 ? CH_D0 : CH_D) + h->cfg.framecode_ch;
     int64_t want[24][2];
     for (int l = 0; l < DEPTH; ++l) {
         want[2 * l][0] = W; want[2 * l][1] = l == 0 ? CH_X : (l == SKIP + 1 ? CH_X + W : W);
@@ -705,6 +745,10 @@ int pg_load_weights(pg_handle* h, int which, const float* const* tensors, const 
     ns.host.assign(24, {});
     ns.fold_w.clear(); ns.fold_b.clear();
     for (int i = 0; i < 24; ++i) ns.host[i].assign(tensors[i], tensors[i] + want[i][0] * want[i][1]);
+    if (views0) {       // every image, fold and record below sees the 4-band matrix
+        ns.host[20].assign((size_t)VW * (W + CH_D + h->cfg.framecode_ch), 0.0f);
+        widen_view_w(tensors[20], h->cfg.framecode_ch, ns.host[20].data());
+    }
     ns.loaded = true;
     ns.host_stale = false;
     PG_HIP(h, hipSetDevice(h->device));
@@ -747,6 +791,7 @@ int pg_load_weights(pg_handle* h, int which, const float* const* tensors, const 
 int pg_load_weights_device(pg_handle* h, void* stream, int which, const float* const* d_tensors, int n_tensors, const float* d_codes, int n_codes) {
     if (!h || !d_tensors) return pg_fail(h, PG_EINVAL, "pg_load_weights_device: null argument");
     if (which < 0 || which > 1) return pg_fail(h, PG_EINVAL, "pg_load_weights_device: which_net must be 0 or 1");
+    if (which == 1 && h->cfg.single_net) return pg_fail(h, PG_EINVAL, "pg_load_weights_device: a single_net handle has one net (which_net 0)");
     if (n_tensors != 24) return pg_fail(h, PG_EINVAL, "pg_load_weights_device: expected 24 tensors, got %d", n_tensors);
     if (!h->peers.empty()) return pg_fail(h, PG_EINVAL, "pg_load_weights_device: a multi-device handle takes its weights from the host (pg_load_weights)");
     NetState& ns = h->net[which];
@@ -765,8 +810,15 @@ int pg_load_weights_device(pg_handle* h, void* stream, int which, const float* c
         return t;
     };
     if (!ns.d_src) PG_HIP(h, hipMalloc(reinterpret_cast<void**>(&ns.d_src), (size_t)lay.off[pgpack::NetTensors::N_SRC] * sizeof(float)));
-    pg_launch_collect(d_tensors, lay.off, ns.d_src, stream);        // (off[24] = the end of tensor 23: the folded view layer follows)
     const int vcols = W + CH_D + h->cfg.framecode_ch;
+    const float* tens[24];
+    for (int i = 0; i < 24; ++i) tens[i] = d_tensors[i];
+    if (h->cfg.multires_views == 0) {       // the caller's [128, 256+72(+fc)] view weight, widened as pg_load_weights does
+        if (!ns.d_vwide) PG_HIP(h, hipMalloc(reinterpret_cast<void**>(&ns.d_vwide), (size_t)VW * vcols * sizeof(float)));
+        pg_launch_widen_views(d_tensors[20], h->cfg.framecode_ch, ns.d_vwide, stream);
+        tens[20] = ns.d_vwide;
+    }
+    pg_launch_collect(tens, lay.off, ns.d_src, stream);        // (off[24] = the end of tensor 23: the folded view layer follows)
     pg_launch_fold(ns.d_src, lay.off[20], vcols, lay.off[21], lay.off[18], lay.off[19], lay.off[pgpack::NetTensors::SRC_VIEWF_W],
                    lay.off[pgpack::NetTensors::SRC_VIEWF_B], stream);
     auto upload_map = [&](const std::vector<int32_t>& m, int32_t** d, size_t* n) -> int {
@@ -958,8 +1010,7 @@ int pg_debug_pack(const float* const* tensors, const int64_t* shapes, int n_tens
     if (!tensors || !shapes || n_tensors != 24) return pg_fail(nullptr, PG_EINVAL, "pg_debug_pack: need 24 tensors");
     if (precision < 0 || precision >= PG_PREC_COUNT) return pg_fail(nullptr, PG_EINVAL, "pg_debug_pack: bad precision");
     NetState ns;
-    ns.host.assign(24, {});
-    for (int i = 0; i < 24; ++i) ns.host[i].assign(tensors[i], tensors[i] + shapes[2 * i] * shapes[2 * i + 1]);
+    host_copy(ns, tensors, shapes, framecode_ch);
     pg_config cfg{};
     cfg.framecode_ch = framecode_ch;
     std::vector<uint8_t> packed;
@@ -992,8 +1043,7 @@ int pg_debug_pack_map(const float* const* tensors, const int64_t* shapes, int n_
                       int32_t* map_out, int64_t map_cap, int64_t* map_n, float* src_out, int64_t src_cap, int64_t* src_n) {
     if (!tensors || !shapes || n_tensors != 24) return pg_fail(nullptr, PG_EINVAL, "pg_debug_pack_map: need 24 tensors");
     NetState ns;
-    ns.host.assign(24, {});
-    for (int i = 0; i < 24; ++i) ns.host[i].assign(tensors[i], tensors[i] + shapes[2 * i] * shapes[2 * i + 1]);
+    host_copy(ns, tensors, shapes, framecode_ch);
     pg_config cfg{};
     cfg.framecode_ch = framecode_ch;
     pgpack::NetTensors t = tensors_of(ns, cfg);
@@ -1023,12 +1073,27 @@ int pg_debug_pack_map(const float* const* tensors, const int64_t* shapes, int n_
     return PG_OK;
 }
 
+int pg_debug_widen_views(const float* view_w, int64_t rows, int64_t cols, int framecode_ch, float* out, int64_t cap,
+                         int64_t* out_n) {
+    if (!view_w) return pg_fail(nullptr, PG_EINVAL, "pg_debug_widen_views: null argument");
+    if (framecode_ch != 0 && framecode_ch != FC_CH) return pg_fail(nullptr, PG_EINVAL, "pg_debug_widen_views: frame code 0 or 16");
+    if (rows != VW || cols != W + CH_D0 + framecode_ch)
+        return pg_fail(nullptr, PG_EINVAL, "pg_debug_widen_views: view weight [%lld,%lld], expected [%d,%d]", (long long)rows,
+                       (long long)cols, VW, W + CH_D0 + framecode_ch);
+    const int64_t need = (int64_t)VW * (W + CH_D + framecode_ch);
+    if (out_n) *out_n = need;
+    if (out) {
+        if (cap < need) return pg_fail(nullptr, PG_EINVAL, "pg_debug_widen_views: buffer too small");
+        widen_view_w(view_w, framecode_ch, out);
+    }
+    return PG_OK;
+}
+
 int pg_debug_pack_vy(const float* const* tensors, const int64_t* shapes, int n_tensors, int framecode_ch,
                      int precision, uint8_t* out, int64_t cap, int64_t* out_bytes) {
     if (!tensors || !shapes || n_tensors != 24) return pg_fail(nullptr, PG_EINVAL, "pg_debug_pack_vy: need 24 tensors");
     NetState ns;
-    ns.host.assign(24, {});
-    for (int i = 0; i < 24; ++i) ns.host[i].assign(tensors[i], tensors[i] + shapes[2 * i] * shapes[2 * i + 1]);
+    host_copy(ns, tensors, shapes, framecode_ch);
     pg_config cfg{};
     cfg.framecode_ch = framecode_ch;
     std::vector<uint8_t> vy;
@@ -1151,6 +1216,7 @@ int pg_stage_eval(pg_handle* h, void* stream, int which, int64_t n, int n_sample
     int rc = check_ready(h, which == 1);
     if (rc) return rc;
     if (which < 0 || which > 1) return pg_fail(h, PG_EINVAL, "pg_stage_eval: which_net must be 0 or 1");
+    if (which == 1 && h->cfg.single_net) return pg_fail(h, PG_EINVAL, "pg_stage_eval: a single_net handle has one net (which_net 0)");
     if (n < 0 || !ray_batch || !z || !skts || !raw) return pg_fail(h, PG_EINVAL, "pg_stage_eval: null/negative argument");
     if (pose_stride != 0 && pose_stride != 384) return pg_fail(h, PG_EINVAL, "pose_stride must be 0 or 384");
     if (n == 0) return PG_OK;
@@ -1163,6 +1229,7 @@ int pg_query_density(pg_handle* h, void* stream, int which, int64_t n_points, co
     int rc = check_ready(h, which == 1);
     if (rc) return rc;
     if (which < 0 || which > 1) return pg_fail(h, PG_EINVAL, "pg_query_density: which_net must be 0 or 1");
+    if (which == 1 && h->cfg.single_net) return pg_fail(h, PG_EINVAL, "pg_query_density: a single_net handle has one net (which_net 0)");
     if (n_points < 0 || !pts || !skts || !raw) return pg_fail(h, PG_EINVAL, "pg_query_density: null/negative argument");
     if (n_points > 0x7fffffffLL) return pg_fail(h, PG_EINVAL, "pg_query_density: at most 2^31-1 points per call");
     if (n_points == 0) return PG_OK;
@@ -1186,8 +1253,11 @@ int pg_stage_composite(pg_handle* h, void* stream, int64_t n, int n_samples, con
         return pg_fail(h, PG_EINVAL, "pg_stage_composite: N_importance %d outside {0, 2..%d}", n_importance, pg_composite_max_importance());
     if (n_importance > 0 && n_samples < 3) return pg_fail(h, PG_EINVAL, "importance sampling needs N_samples >= 3");
     PG_HIP(h, hipSetDevice(h->device));
-    int e = pg_launch_composite(ray_batch, z, raw, n, n_samples, h->cfg.density_scale, h->cfg.rgb_eps, h->cfg.density_act, h->cfg.softplus_shift, rgb, disp, acc,
-                                alpha, weights, n_importance, z_fine, nullptr, nullptr, nullptr, stream);
+    int e = h->cfg.single_net
+        ? pg_launch_composite_iso(ray_batch, z, raw, n, n_samples, h->cfg.density_scale, h->cfg.rgb_eps, h->cfg.density_act, h->cfg.softplus_shift,
+                                  rgb, disp, acc, alpha, weights, n_importance, z_fine, nullptr, nullptr, nullptr, nullptr, 0, stream)
+        : pg_launch_composite(ray_batch, z, raw, n, n_samples, h->cfg.density_scale, h->cfg.rgb_eps, h->cfg.density_act, h->cfg.softplus_shift, rgb, disp, acc,
+                              alpha, weights, n_importance, z_fine, nullptr, nullptr, nullptr, stream);
     if (e) return pg_fail(h, PG_EHIP, "composite launch failed: %s", hipGetErrorString((hipError_t)e));
     return PG_OK;
 }
@@ -1214,6 +1284,77 @@ int pg_render_rays_train(pg_handle* h, void* stream, int64_t n, const float* ray
 }
 
 namespace {
+// single_net (core/raycasters.py:446-469): one net evaluates the S coarse points, then only the N new points drawn from the
+// is_only pdf (sample_pts_is, is_only=True); the fine maps composite the S + N raw merged in depth order.  Arguments are
+// checked by render_rays_impl.  S + N evaluations per ray instead of S + (S + N).
+int render_rays_single(pg_handle* h, void* stream, int64_t n, const float* ray_batch, const float* skts, int64_t pose_stride,
+                       const float* cyls, int64_t cyl_stride, const float* cams, int S, int N, int flags,
+                       const pg_train_draws* dr, const pg_outputs* out) {
+    PG_HIP(h, hipSetDevice(h->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int SF = S + N;
+    // the new points are one pass of NP >= N points per ray: the direct 16-bit kernel needs points_per_pass / (MAXR - 1)
+    // per ray (32); the columns behind N repeat the last new depth and are not read back
+    const int prec = h->cfg.precision == PG_PREC_FP16M ? PG_PREC_FP16C : h->cfg.precision;
+    const int NP = is_shape_a(prec) ? std::max(N, pg_eval16_points_per_pass() / (MAXR - 1)) : N;
+    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
+    const bool rnoise = dr && dr->ray_noise;
+    const size_t b_nf = al((size_t)n * 2 * 4), b_zc = al((size_t)n * S * 4), b_rc = al((size_t)n * S * 16),
+                 b_w0 = al((size_t)n * S * 4), b_zf = al((size_t)n * SF * 4), b_ord = al((size_t)n * SF * 4),
+                 b_zn = al((size_t)n * NP * 4), b_rn = al((size_t)n * NP * 16),
+                 b_pn = rnoise ? al((size_t)n * std::max(S, NP) * 12) : 0;
+    int rc = ensure_ws(h, b_nf + b_zc + b_rc + b_w0 + b_zf + b_ord + b_zn + b_rn + b_pn);
+    if (rc) return rc;
+    uint8_t* p = h->ws;
+    float* nf = reinterpret_cast<float*>(p); p += b_nf;
+    float* zc = reinterpret_cast<float*>(p); p += b_zc;
+    float* rawc = reinterpret_cast<float*>(p); p += b_rc;
+    float* w0 = reinterpret_cast<float*>(p); p += b_w0;
+    float* zf = reinterpret_cast<float*>(p); p += b_zf;
+    int* order = reinterpret_cast<int*>(p); p += b_ord;
+    float* zn = reinterpret_cast<float*>(p); p += b_zn;
+    float* rawn = reinterpret_cast<float*>(p); p += b_rn;
+    float* pn = b_pn ? reinterpret_cast<float*>(p) : nullptr;
+    {
+        double* scs = nullptr;
+        if (int rc2 = pg_sc_scratch(h, n, h->cfg.chunk, &scs)) return rc2;
+        int e0 = pg_launch_sample_coarse(ray_batch, cyls, cyl_stride, n, h->cfg.chunk, S, (flags & PG_FLAG_LINDISP) ? 1 : 0, nf, zc,
+                                         dr ? dr->t_rand : nullptr, scs, stream);
+        if (e0) return pg_fail(h, PG_EHIP, "coarse sampling launch failed: %s", hipGetErrorString((hipError_t)e0));
+    }
+    if (rnoise) {       // position noise of the coarse points: rows [:S] of every ray's draws
+        int e0 = pg_launch_gather_noise(dr->ray_noise, n, SF, S, nullptr, pn, stream);
+        if (e0) return pg_fail(h, PG_EHIP, "noise gather launch failed: %s", hipGetErrorString((hipError_t)e0));
+    }
+    // the coarse raw enters the fine maps: not a guide pass (PG_PREC_FP16M runs fp16c)
+    rc = launch_eval(h, stream, 0, n, S, ray_batch, zc, skts, pose_stride, cams, rawc, nullptr, 0, nullptr, rnoise ? pn : nullptr, false);
+    if (rc) return rc;
+    int e = pg_launch_composite_iso(ray_batch, zc, rawc, n, S, h->cfg.density_scale, h->cfg.rgb_eps, h->cfg.density_act,
+                                    h->cfg.softplus_shift, out->rgb0, out->disp0, out->acc0, out->alpha0,
+                                    out->weights0 ? out->weights0 : w0, N, zf, dr ? dr->noise0 : nullptr, dr ? dr->u_rand : nullptr,
+                                    order, zn, NP, stream);
+    if (e) return pg_fail(h, PG_EHIP, "composite launch failed: %s", hipGetErrorString((hipError_t)e));
+    if (rnoise) {       // the new points' noise: rows [S:] in z_samples order (sample_pts_is, raycasters.py:665-674)
+        e = NP == N ? pg_launch_gather_noise(dr->ray_noise + (size_t)S * 3, n, SF, N, nullptr, pn, stream)
+                    : (int)hipMemsetAsync(pn, 0, (size_t)n * NP * 12, s);
+        if (!e && NP != N)      // rows of NP: the N draws, then zeros for the padding points
+            e = (int)hipMemcpy2DAsync(pn, (size_t)NP * 12, dr->ray_noise + (size_t)S * 3, (size_t)SF * 12, (size_t)N * 12, (size_t)n,
+                                      hipMemcpyDeviceToDevice, s);
+        if (e) return pg_fail(h, PG_EHIP, "noise gather failed: %s", hipGetErrorString((hipError_t)e));
+    }
+    rc = launch_eval(h, stream, 0, n, NP, ray_batch, zn, skts, pose_stride, cams, rawn, nullptr, 0, nullptr, rnoise ? pn : nullptr, false);
+    if (rc) return rc;
+    e = pg_launch_composite_merged(ray_batch, zf, rawc, rawn, NP, order, n, S, N, h->cfg.density_scale, h->cfg.rgb_eps, h->cfg.density_act,
+                                   h->cfg.softplus_shift, out->rgb_map, out->disp_map, out->acc_map, out->alpha,
+                                   dr ? dr->noise1 : nullptr, out->raw_fine, stream);
+    if (e) return pg_fail(h, PG_EHIP, "composite launch failed: %s", hipGetErrorString((hipError_t)e));
+    if (out->near_far) PG_HIP(h, hipMemcpyAsync(out->near_far, nf, (size_t)n * 8, hipMemcpyDeviceToDevice, s));
+    if (out->z_coarse) PG_HIP(h, hipMemcpyAsync(out->z_coarse, zc, (size_t)n * S * 4, hipMemcpyDeviceToDevice, s));
+    if (out->raw_coarse) PG_HIP(h, hipMemcpyAsync(out->raw_coarse, rawc, (size_t)n * S * 16, hipMemcpyDeviceToDevice, s));
+    if (out->z_fine) PG_HIP(h, hipMemcpyAsync(out->z_fine, zf, (size_t)n * SF * 4, hipMemcpyDeviceToDevice, s));
+    return PG_OK;
+}
+
 int render_rays_impl(pg_handle* h, void* stream, int64_t n, const float* ray_batch, const float* skts,
                      int64_t pose_stride, const float* cyls, int64_t cyl_stride, const float* cams, int n_samples,
                      int n_importance, int flags, const pg_train_draws* dr, const pg_outputs* out) {
@@ -1228,6 +1369,8 @@ int render_rays_impl(pg_handle* h, void* stream, int64_t n, const float* ray_bat
     if (n_importance > 0 && n_samples + n_importance > pg_composite_max_samples())
         return pg_fail(h, PG_EINVAL, "N_samples + N_importance exceeds %d", pg_composite_max_samples());
     if (n == 0) return PG_OK;
+    if (h->cfg.single_net && n_importance > 0)
+        return render_rays_single(h, stream, n, ray_batch, skts, pose_stride, cyls, cyl_stride, cams, n_samples, n_importance, flags, dr, out);
     PG_HIP(h, hipSetDevice(h->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int S = n_samples, SF = n_samples + n_importance;

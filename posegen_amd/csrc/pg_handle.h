@@ -34,6 +34,7 @@ struct NetState {
     int32_t* d_map_ro = nullptr;   size_t n_map_ro = 0;      // on-chip stream of the 16x16x32 kernel (one map for bf16 and fp16)
     int32_t* d_map_c2 = nullptr;   size_t n_map_c2 = 0;      // pg_evalc2.hip's weight image
     int32_t* d_map_bias_s = nullptr;
+    float* d_vwide = nullptr;      // multires_views = 0: the caller's view weight widened to the 4-band layout (pg_launch_widen_views)
     bool host_stale = false;
 };
 

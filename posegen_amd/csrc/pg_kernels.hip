@@ -299,7 +299,25 @@ __device__ __forceinline__ float density_act(float x, int act, float shift) {
     return t > 20.0f ? t : log1pf(expf(t));
 }
 
+// The single-net pipeline (core/raycasters.py:446-469) adds two forms (template MODE; 0 = the two-net / coarse-only form):
+//   CP_ISO    the coarse pass: the pdf of the importance samples is built from the is_only weights
+//             0.5 (max(w_l, w_k) + max(w_k, w_u)) + 0.01 (ray_utils.py:269-276), and the new depths are also stored in
+//             sample order (z_new [n, ld_new]: the points the one net evaluates next; columns n_imp.. repeat the last new
+//             depth, a padding for kernels that need more points per ray than n_imp);
+//   CP_MERGE  the fine pass over z_fine [n, S] (S = S0 + N): sample s reads its raw from the coarse raw [n, S0] or the new
+//             raw [n, ld_new] by order[ray, s] (sorted_idxs: _merge_encodings of the two raw tensors, raycasters.py:466-469)
+//             and, if asked, stores the merged raw.
+constexpr int CP_PLAIN = 0, CP_ISO = 1, CP_MERGE = 2;
+struct CompMerge {
+    const float4* raw_new;      // [n, ld_new]
+    const int* order;           // [n, S0 + N]: index into cat([z, z_samples])
+    float4* raw_out;            // [n, S0 + N] or null
+    int S0, N;
+    int ld_new;                 // row length of z_new / raw_new (>= N)
+};
+
 // one ray by one wave (sh_*: the wave's rows of the workgroup's LDS arrays)
+template <int MODE>
 __device__ __forceinline__ void composite_ray(
         const long long ray, const int lane, const int wave,
         float (*sh_w)[CP_MAXS], float (*sh_z)[CP_MAXS + CP_MAXI], float (*sh_cdf)[CP_MAXS],
@@ -308,7 +326,7 @@ __device__ __forceinline__ void composite_ray(
         float* __restrict__ rgb_out, float* __restrict__ disp_out, float* __restrict__ acc_out,
         float* __restrict__ alpha_out, float* __restrict__ w_out,
         int n_imp, float* __restrict__ z_fine, const float* __restrict__ noise, const float* __restrict__ u_rand,
-        int* __restrict__ order) {
+        int* __restrict__ order, float* __restrict__ z_new, const CompMerge mg) {
     const int E = (S + 63) >> 6;
     const float* rb = rays + ray * 11;
     const float dnorm = sqrtf(rb[3] * rb[3] + rb[4] * rb[4] + rb[5] * rb[5]);
@@ -322,7 +340,16 @@ __device__ __forceinline__ void composite_ray(
         const int s = lane * E + e;
         a_[e] = 0.0f; z_[e] = 0.0f; cr[e] = cg[e] = cb[e] = 0.0f;
         if (e < E && s < S) {
-            const float4 q = rr[s];
+            float4 q;
+            if (MODE == CP_MERGE) {
+                // (a ray whose depths are NaN -- a nanmean group without a hit -- can leave ranks unwritten: clamped, so that
+                // the read stays inside the two buffers whatever the rank map holds)
+                const int o = min(max(mg.order[ray * S + s], 0), S - 1);
+                q = o < mg.S0 ? raw[ray * mg.S0 + o] : mg.raw_new[ray * mg.ld_new + (o - mg.S0)];
+                if (mg.raw_out) mg.raw_out[ray * S + s] = q;
+            } else {
+                q = rr[s];
+            }
             const float zs = zr[s];
             const float delta = (s + 1 < S ? zr[s + 1] - zs : 1e10f) * dnorm;
             // raw2alpha(raw / B + noise): `noise` [n,S] is the caller's draw (training, nerf.py:175-186), else 0
@@ -374,7 +401,15 @@ __device__ __forceinline__ void composite_ray(
     for (int e = 0; e < CP_MAXE; ++e) {
         const int i = lane * E + e;
         pw[e] = 0.0f;
-        if (e < E && i < NB) { pw[e] = sh_w[wave][i + 1] + 1e-5f; part += pw[e]; }
+        if (e < E && i < NB) {
+            if (MODE == CP_ISO) {       // neighbours' weights from the wave's LDS row (written above, fenced)
+                const float wl = sh_w[wave][i], wk = sh_w[wave][i + 1], wu = sh_w[wave][i + 2];
+                pw[e] = (0.5f * (fmaxf(wl, wk) + fmaxf(wk, wu)) + 0.01f) + 1e-5f;
+            } else {
+                pw[e] = sh_w[wave][i + 1] + 1e-5f;
+            }
+            part += pw[e];
+        }
     }
     const float total = wave_sum(part);
     // cdf[0] = 0, cdf[i+1] = cumsum(pdf)[i]
@@ -410,8 +445,11 @@ __device__ __forceinline__ void composite_ray(
         if (den < 1e-5f) den = 1.0f;
         const float t = (u - c0) / den;
         sh_z[wave][S + k] = b0 + t * (b1 - b0);
+        if (MODE == CP_ISO && z_new) z_new[ray * mg.ld_new + k] = sh_z[wave][S + k];
     }
     PG_WAVE_SYNC();
+    if (MODE == CP_ISO && z_new)
+        for (int k = n_imp + lane; k < mg.ld_new; k += 64) z_new[ray * mg.ld_new + k] = sh_z[wave][S + n_imp - 1];
     // ---- stable merge of the S + n_imp depths by rank (== torch.sort of the concat) ----
     // rank of element i = #{j : z_j < z_i or (z_j == z_i and j < i)}.  The coarse depths are increasing and,
     // with deterministic u, so are the new ones (the inverse cdf is monotone): then
@@ -455,20 +493,21 @@ __device__ __forceinline__ void composite_ray(
 
 // A wave takes rays blockIdx.x * CP_WAVES + wave, + gridDim.x * CP_WAVES, ...: a few rays per wave instead of one
 // (262 144 one-ray waves per 512 x 512 launch are bound by the rate waves can be dispatched, not by their 2 KB of traffic).
+template <int MODE>
 __global__ __launch_bounds__(CP_WAVES * 64) void composite_kernel(
         const float* __restrict__ rays, const float* __restrict__ z, const float4* __restrict__ raw,
         long long n, int S, float density_scale, float rgb_eps, int act, float act_shift,
         float* __restrict__ rgb_out, float* __restrict__ disp_out, float* __restrict__ acc_out,
         float* __restrict__ alpha_out, float* __restrict__ w_out,
         int n_imp, float* __restrict__ z_fine, const float* __restrict__ noise, const float* __restrict__ u_rand,
-        int* __restrict__ order) {
+        int* __restrict__ order, float* __restrict__ z_new, const CompMerge mg) {
     __shared__ float sh_w[CP_WAVES][CP_MAXS];
     __shared__ float sh_z[CP_WAVES][CP_MAXS + CP_MAXI];
     __shared__ float sh_cdf[CP_WAVES][CP_MAXS];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (long long ray = (long long)blockIdx.x * CP_WAVES + wave; ray < n; ray += (long long)gridDim.x * CP_WAVES) {
-        composite_ray(ray, lane, wave, sh_w, sh_z, sh_cdf, rays, z, raw, S, density_scale, rgb_eps, act, act_shift, rgb_out, disp_out, acc_out,
-                      alpha_out, w_out, n_imp, z_fine, noise, u_rand, order);
+        composite_ray<MODE>(ray, lane, wave, sh_w, sh_z, sh_cdf, rays, z, raw, S, density_scale, rgb_eps, act, act_shift, rgb_out, disp_out,
+                            acc_out, alpha_out, w_out, n_imp, z_fine, noise, u_rand, order, z_new, mg);
         PG_WAVE_SYNC();                         // the wave's LDS rows are reused by its next ray
     }
 }
@@ -739,9 +778,43 @@ extern "C" int pg_launch_composite(const float* rays, const float* z, const floa
     if (n <= 0) return 0;
     long long blocks = (n + pgk::CP_WAVES - 1) / pgk::CP_WAVES;
     if (blocks > 16384) blocks = 16384;         // a wave takes several rays (measured flat from 4 k to 32 k blocks, -0.05 ms per frame against one ray per wave)
-    hipLaunchKernelGGL(pgk::composite_kernel, dim3((unsigned)blocks), dim3(pgk::CP_WAVES * 64), 0,
+    hipLaunchKernelGGL(pgk::composite_kernel<pgk::CP_PLAIN>, dim3((unsigned)blocks), dim3(pgk::CP_WAVES * 64), 0,
                        static_cast<hipStream_t>(stream), rays, z, reinterpret_cast<const float4*>(raw), n, S,
-                       density_scale, rgb_eps, density_act, act_shift, rgb, disp, acc, alpha, weights, n_imp, z_fine, noise, u_rand, order);
+                       density_scale, rgb_eps, density_act, act_shift, rgb, disp, acc, alpha, weights, n_imp, z_fine, noise, u_rand, order,
+                       nullptr, pgk::CompMerge{});
+    return (int)hipGetLastError();
+}
+
+// single_net, coarse pass: pg_launch_composite with the is_only pdf; z_new [n, ld_new] (may be null) receives the new depths
+// in sample order (columns n_imp.. repeat the last one)
+extern "C" int pg_launch_composite_iso(const float* rays, const float* z, const float* raw, long long n, int S,
+                                       float density_scale, float rgb_eps, int density_act, float act_shift, float* rgb, float* disp,
+                                       float* acc, float* alpha, float* weights, int n_imp, float* z_fine, const float* noise,
+                                       const float* u_rand, int* order, float* z_new, int ld_new, void* stream) {
+    if (n <= 0) return 0;
+    long long blocks = (n + pgk::CP_WAVES - 1) / pgk::CP_WAVES;
+    if (blocks > 16384) blocks = 16384;
+    hipLaunchKernelGGL(pgk::composite_kernel<pgk::CP_ISO>, dim3((unsigned)blocks), dim3(pgk::CP_WAVES * 64), 0,
+                       static_cast<hipStream_t>(stream), rays, z, reinterpret_cast<const float4*>(raw), n, S,
+                       density_scale, rgb_eps, density_act, act_shift, rgb, disp, acc, alpha, weights, n_imp, z_fine, noise, u_rand, order,
+                       z_new, pgk::CompMerge{nullptr, nullptr, nullptr, 0, n_imp, ld_new < n_imp ? n_imp : ld_new});
+    return (int)hipGetLastError();
+}
+
+// single_net, fine pass over z_fine [n, S0 + N]: raw of sample s = raw_c[order < S0] or raw_new[order - S0] (order: the rank
+// map of pg_launch_composite_iso; raw_new [n, ld_new, 4]); raw_out [n, S0 + N, 4] (may be null) receives the merged raw
+extern "C" int pg_launch_composite_merged(const float* rays, const float* z_fine, const float* raw_c, const float* raw_new, int ld_new,
+                                          const int* order, long long n, int S0, int N, float density_scale, float rgb_eps,
+                                          int density_act, float act_shift, float* rgb, float* disp, float* acc, float* alpha,
+                                          const float* noise, float* raw_out, void* stream) {
+    if (n <= 0) return 0;
+    long long blocks = (n + pgk::CP_WAVES - 1) / pgk::CP_WAVES;
+    if (blocks > 16384) blocks = 16384;
+    const pgk::CompMerge mg{reinterpret_cast<const float4*>(raw_new), order, reinterpret_cast<float4*>(raw_out), S0, N, ld_new};
+    hipLaunchKernelGGL(pgk::composite_kernel<pgk::CP_MERGE>, dim3((unsigned)blocks), dim3(pgk::CP_WAVES * 64), 0,
+                       static_cast<hipStream_t>(stream), rays, z_fine, reinterpret_cast<const float4*>(raw_c), n, S0 + N,
+                       density_scale, rgb_eps, density_act, act_shift, rgb, disp, acc, alpha, nullptr, 0, nullptr, noise, nullptr,
+                       nullptr, nullptr, mg);
     return (int)hipGetLastError();
 }
 

@@ -91,6 +91,18 @@ __global__ __launch_bounds__(128) void ycode_kernel(const float* __restrict__ vi
     for (int k = 0; k < FC_CH; ++k) s = __dadd_rn(s, __dmul_rn((double)view_w[(long long)o * vcols + W + CH_D + k], (double)codes[(long long)c * FC_CH + k]));
     yc[(long long)c * VW + o] = (float)s;
 }
+// multires_views = 0: view weight [128, 256+72+fc] -> [128, 256+648+fc] (pg_api.hip widen_view_w): columns 256..327 are row 0
+// of the 4-band embedding, the sin/cos columns zero, the frame-code columns behind.  Block o = output row.
+__global__ __launch_bounds__(256) void widen_views_kernel(const float* __restrict__ src, int fc, float* __restrict__ dst) {
+    const int o = blockIdx.x;
+    const int sc = W + J * 3 + fc, dc = W + CH_D + fc;
+    for (int k = threadIdx.x; k < dc; k += 256) {
+        float v = 0.0f;
+        if (k < W + J * 3) v = src[(long long)o * sc + k];
+        else if (k >= W + CH_D) v = src[(long long)o * sc + (k - (CH_D - J * 3))];
+        dst[(long long)o * dc + k] = v;
+    }
+}
 }  // namespace pgr
 
 extern "C" {
@@ -113,6 +125,9 @@ void pg_launch_gather32(const int32_t* map, const float* src, float* out, long l
 }
 void pg_launch_codes(const float* codes, int n_codes, float* out, void* stream) {
     hipLaunchKernelGGL(pgr::codes_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), codes, n_codes, out);
+}
+void pg_launch_widen_views(const float* src, int framecode_ch, float* dst, void* stream) {
+    hipLaunchKernelGGL(pgr::widen_views_kernel, dim3(pgl::VW), dim3(256), 0, static_cast<hipStream_t>(stream), src, framecode_ch, dst);
 }
 void pg_launch_ycode(const float* view_w, int vcols, const float* codes, int n_codes, float* yc, void* stream) {
     hipLaunchKernelGGL(pgr::ycode_kernel, dim3(n_codes + 1), dim3(128), 0, static_cast<hipStream_t>(stream), view_w, vcols, codes, yc);

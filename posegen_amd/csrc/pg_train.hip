@@ -1446,6 +1446,9 @@ int pg_train_forward(pg_handle* h, void* stream, int64_t n, const float* ray_bat
     if (!h) return pg_fail(nullptr, PG_EINVAL, "null handle");
     if (n <= 0 || !ray_batch || !skts || !cyls || !coarse || !out) return pg_fail(h, PG_EINVAL, "pg_train_forward: null / non-positive argument");
     if (!h->emb_set[0] || !h->emb_set[1]) return pg_fail(h, PG_ESTATE, "embedder state not set (pg_set_embedder)");
+    if (h->cfg.single_net || h->cfg.multires_views != pgl::LD)
+        return pg_fail(h, PG_EINVAL, "pg_train_forward: the training step is built for two nets with multires_views = 4 (single_net / "
+                                     "multires_views = 0 models render only)");
     if (pose_stride != 0 && pose_stride != 384) return pg_fail(h, PG_EINVAL, "pose_stride must be 0 (shared) or 384 (per ray)");
     if (cyl_stride != 0 && cyl_stride != 5) return pg_fail(h, PG_EINVAL, "cyl_stride must be 0 (shared) or 5 (per ray)");
     const int S = n_samples, N = n_importance, SF = S + N;

@@ -74,7 +74,8 @@ class HipRenderer:
                            framecode_ch=cfg.framecode_ch, n_framecodes=cfg.n_framecodes, chunk=cfg.chunk,
                            precision=self.precision, cutoff_dist=cfg.cutoff_dist,
                            density_scale=cfg.density_scale, rgb_eps=cfg.rgb_eps,
-                           softplus_shift=float(cfg.softplus_shift), density_act=_density_act(cfg.density_type), reserved0=0)
+                           softplus_shift=float(cfg.softplus_shift), density_act=_density_act(cfg.density_type),
+                           single_net=1 if cfg.single_net else 0)
         idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
         dev_ids = [idx] if devices is None else devices
         ids = (C.c_int * len(dev_ids))(*dev_ids)
@@ -107,7 +108,8 @@ class HipRenderer:
 
     # -- state ------------------------------------------------------------------------
     def load_network(self, which: int, sd: Dict[str, np.ndarray]):
-        """which 0 = coarse ('network_fn_state_dict'), 1 = fine ('network_fine_state_dict')."""
+        """which 0 = coarse ('network_fn_state_dict'), 1 = fine ('network_fine_state_dict').  With multires_views = 0 the
+        view weight keeps the reference's [128, 256+72(+16)] shape here and in state_dict(); the library widens its copy."""
         arrs = [_np32(sd[k]) for k in NET_TENSOR_ORDER]
         ptrs = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
         shp = (C.c_int64 * (2 * len(arrs)))()
@@ -118,8 +120,10 @@ class HipRenderer:
         if self.cfg.framecode_ch > 0:
             codes = _np32(sd["framecodes.codes.weight"])
             self._check(self.lib.pg_set_framecodes(self.handle, which, codes.ctypes.data, codes.shape[0]))
-        self._state["network_fn_state_dict" if which == 0 else "network_fine_state_dict"] = {
-            k: torch.from_numpy(_np32(v).copy()) for k, v in sd.items()}
+        st = {k: torch.from_numpy(_np32(v).copy()) for k, v in sd.items()}
+        self._state["network_fn_state_dict" if which == 0 else "network_fine_state_dict"] = st
+        if self.cfg.single_net:     # network_fine is network: the reference's checkpoint holds both keys (raycasters.py:751-766)
+            self._state["network_fine_state_dict"] = st
 
     def load_network_device(self, which: int, tensors, codes=None, state_provider=None):
         """New values of an already loaded net from DEVICE tensors (pg_load_weights_device): `tensors` = the 24 parameters in
@@ -444,10 +448,10 @@ class HipRenderer:
 
     def query_density(self, pts: torch.Tensor, skts: torch.Tensor, which: Optional[int] = None) -> torch.Tensor:
         """Raw density (alpha_linear output, no activation) of net `which` (default: the fine net if
-        loaded, like the reference) at explicit points [...,3] for one pose: render_pts_density
+        loaded, like the reference; net 0 with single_net) at explicit points [...,3] for one pose: render_pts_density
         (core/raycasters.py:598-646).  Returns a device tensor [..., 1]."""
         if which is None:
-            which = 1 if "network_fine_state_dict" in self._state else 0
+            which = 1 if "network_fine_state_dict" in self._state and not self.cfg.single_net else 0
         p = _dev_f32(torch.as_tensor(pts).reshape(-1, 3), self.device)
         n = p.shape[0]
         sk, _ = self._pose_args(skts, 1)
@@ -574,6 +578,13 @@ class HipRenderer:
         return o
 
 
+def _same_state(a, b) -> bool:
+    """two state dicts with the same keys and bitwise equal values"""
+    if set(a) != set(b):
+        return False
+    return all(np.array_equal(_np32(a[k]), _np32(b[k])) for k in a)
+
+
 class HipRayCaster:
     """Call-compatible stand-in for `RayCaster` / `nn.DataParallel(RayCaster)`.
 
@@ -593,9 +604,12 @@ class HipRayCaster:
     # ---- construction helpers -------------------------------------------------------
     @classmethod
     def from_weights(cls, cfg, w_coarse, w_fine, tau_v, tau_d, device="cuda:0", precision=PREC_BF16, devices=None):
+        """`w_fine` may be None (coarse-only renders, or single_net: network_fine is network)."""
+        if cfg.single_net and w_fine is not None and not _same_state(w_coarse, w_fine):
+            raise ValueError("single_net: the fine weights differ from the coarse ones (the reference has one net)")
         rc = cls(cfg, device, precision, devices=devices)
         rc.renderer.load_network(0, w_coarse)
-        if w_fine is not None:
+        if w_fine is not None and not cfg.single_net:
             rc.renderer.load_network(1, w_fine)
         rc.renderer.set_embedder(0, tau_v)
         rc.renderer.set_embedder(1, tau_d)
@@ -636,9 +650,12 @@ class HipRayCaster:
 
     def parameters(self):
         self.renderer._refresh_state()
+        seen = set()
         for sd in self.renderer._state.values():
             for v in sd.values():
-                yield v
+                if id(v) not in seen:       # (single_net: both net keys hold the same tensors)
+                    seen.add(id(v))
+                    yield v
 
     def state_dict(self):
         self.renderer._refresh_state()
@@ -648,12 +665,18 @@ class HipRayCaster:
 
     def load_state_dict(self, ckpt, strict=True):
         r = self.renderer
+        fine = ckpt.get("network_fine_state_dict")
+        if self.cfg.single_net and fine is not None and "network_fn_state_dict" in ckpt \
+                and not _same_state(ckpt["network_fn_state_dict"], fine):
+            # the reference saves the one module under both keys (raycasters.py:751-766): differing dicts are not its checkpoint
+            raise ValueError("single_net checkpoint: network_fine_state_dict differs from network_fn_state_dict "
+                             "(a single-net caster has one net; not guessing which one to render)")
         if "network_fn_state_dict" in ckpt:
             r.load_network(0, ckpt["network_fn_state_dict"])
         elif strict:
             raise KeyError("network_fn_state_dict")
-        if ckpt.get("network_fine_state_dict") is not None:
-            r.load_network(1, ckpt["network_fine_state_dict"])
+        if fine is not None and not self.cfg.single_net:
+            r.load_network(1, fine)
         for which, key in ((0, "embed_state_dict"), (1, "embeddirs_state_dict")):
             e = ckpt.get(key)
             if e is not None and "tau" in e:

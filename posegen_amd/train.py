@@ -175,6 +175,10 @@ class TrainableRayCaster(torch.nn.Module):
         super().__init__()
         if train_precision not in ("fp32", "bf16"):
             raise ValueError(f"train_precision must be 'fp32' or 'bf16', not {train_precision!r}")
+        if caster.cfg.single_net or caster.cfg.multires_views != 4:
+            # refuse rather than train the wrong thing: the training step has two nets and the 4-band view embedding
+            raise NotImplementedError("TrainableRayCaster: training of single_net / multires_views != 4 models is not on the HIP "
+                                      "path (they render through HipRayCaster)")
         self.caster = caster
         self.train_precision = train_precision
         caster.renderer.set_train_precision(train_precision)

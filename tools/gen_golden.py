@@ -100,7 +100,7 @@ def _nerf_args(cfg, workdir) -> Namespace:
         cutoff_viewdir=True, multires_views=cfg.multires_views, N_importance=cfg.n_importance,
         netdepth=cfg.net_depth, netwidth=cfg.net_width, opt_framecode=cfg.framecode_ch > 0,
         framecode_size=cfg.framecode_ch if cfg.framecode_ch else 16, density_scale=cfg.density_scale,
-        single_net=False, lrate=5e-4, basedir=workdir, expname="golden", ft_path=None,
+        single_net=bool(cfg.single_net), lrate=5e-4, basedir=workdir, expname="golden", ft_path=None,
         no_reload=True, finetune=False, perturb=0., N_samples=cfg.n_samples, raw_noise_std=0.,
         ray_noise_std=0., lindisp=False, nerf_type="nerf", debug=False, density_type=cfg.density_type,
         softplus_shift=cfg.softplus_shift, pts_tr_type="local", kp_dist_type="reldist", view_type="relray",
@@ -122,10 +122,13 @@ def _build_reference_caster(cfg, seed, workdir):
     _, kw_test, *_ = create_raycaster(_nerf_args(cfg, workdir), attrs)
     caster = kw_test["ray_caster"]
     wc, wf, tau_v, tau_d = syn.make_model(cfg, seed)
+    if cfg.single_net:              # network_fine is network: loading wf would overwrite the coarse weights
+        assert caster.network_fine is None or caster.network_fine is caster.network
+        wf = wc
     sd = {"network_fn_state_dict": {k: torch.tensor(v) for k, v in wc.items()},
           "network_fine_state_dict": {k: torch.tensor(v) for k, v in wf.items()}}
     caster.network.load_state_dict(sd["network_fn_state_dict"])
-    if caster.network_fine is not None:
+    if caster.network_fine is not None and not cfg.single_net:
         caster.network_fine.load_state_dict(sd["network_fine_state_dict"])
     caster.embed_fn.tau = torch.tensor(tau_v)
     caster.embeddirs_fn.tau = torch.tensor(tau_d)
@@ -202,12 +205,18 @@ def _stagewise(caster, kw, batch, kp_b, skt_b, cyl_b, bones_b, cams_b, n_samples
            "disp0": rd["disp_map"], "acc0": rd["acc_map"]}
     if n_importance > 0:
         pts_is, z_all, z_new, order = caster.sample_pts_is(o, d, z, rd["weights"], n_importance,
-                                                           det=True, is_only=False)
+                                                           det=True, is_only=caster.single_net)
         enc_is = caster.encode_inputs(pts_is, [o[:, None, :], d[:, None, :]], kp_b, skt_b, bones_b,
                                       cam_idxs=cams_b, subject_idxs=None, joint_coords=jc,
                                       network=caster.network_fine, **pk)
-        merged = caster._merge_encodings(enc, enc_is, order, n, n_samples + n_importance)
-        raw_f = caster.run_network(merged, caster.network_fine)
+        if caster.single_net:       # raycasters.py:462-469: only the new points through the one net, raw merged by depth
+            raw_is = caster.run_network(enc_is, caster.network_fine)
+            caster._merge_encodings(enc, enc_is, order, n, n_samples + n_importance)
+            raw_f = caster._merge_encodings({"raw": raw}, {"raw": raw_is}, order, n,
+                                            n_samples + n_importance)["raw"]
+        else:
+            merged = caster._merge_encodings(enc, enc_is, order, n, n_samples + n_importance)
+            raw_f = caster.run_network(merged, caster.network_fine)
         rf = caster.network_fine.raw2outputs(raw_f, z_all, d, 0., B=pk["density_scale"],
                                              act_fn=pk["density_fn"])
         res.update({"z_fine": z_all, "z_new": z_new, "order": order, "raw_fine": raw_f,
@@ -219,8 +228,14 @@ def _stagewise(caster, kw, batch, kp_b, skt_b, cyl_b, bones_b, cams_b, n_samples
     return res
 
 
+def _model_keys(d, cfg):
+    """the keys of the single-net / multires_views = 0 fixtures (the older fixtures are two-net, 4 bands)"""
+    d["single_net"] = int(cfg.single_net)
+    d["multires_views"] = int(cfg.multires_views)
+
+
 def gen_render_rays(out, name, cfg, *, n_rays, H, all_hit, seed_model=0, seed_pose=1,
-                    use_cams=False, keep_x=16):
+                    use_cams=False, keep_x=16, model_keys=False):
     """a-5..a-16: one `RayCaster.__call__` on a strided subset of a culled frame."""
     import torch
     from core.utils.ray_utils import kp_to_valid_rays
@@ -281,6 +296,9 @@ def gen_render_rays(out, name, cfg, *, n_rays, H, all_hit, seed_model=0, seed_po
             continue
         d[k] = v.numpy()
     d["n_rays"] = n
+    if model_keys:
+        _model_keys(d, cfg)
+        d["weights0"] = d["weights_coarse"]
     np.savez_compressed(os.path.join(out, f"{name}.npz"), **d)
     acc = st["acc_map"].numpy()
     print(f"[{name}] rays={n} acc in [{acc.min():.3f},{acc.max():.3f}] "
@@ -288,7 +306,7 @@ def gen_render_rays(out, name, cfg, *, n_rays, H, all_hit, seed_model=0, seed_po
 
 
 def gen_render_rays_train(out, name, cfg, *, n_rays, H, seed_model=0, seed_pose=1, perturb=1.,
-                          raw_noise_std=1., ray_noise_std=0.005):
+                          raw_noise_std=1., ray_noise_std=0.005, model_keys=False):
     """Training-mode `RayCaster.__call__` (render_kwargs_train: perturb, raw_noise_std,
     ray_noise_std) in the reference's own deterministic test mode, pytest=True: the stratified
     jitter, the inverse-cdf positions and the density noise are numpy draws after
@@ -360,6 +378,8 @@ def gen_render_rays_train(out, name, cfg, *, n_rays, H, seed_model=0, seed_pose=
     for k, v in full.items():
         if torch.is_tensor(v):
             d[k] = v.numpy()
+    if model_keys:
+        _model_keys(d, cfg)
     np.savez_compressed(os.path.join(out, f"{name}.npz"), **d)
     acc = full["acc_map"].numpy()
     print(f"[{name}] rays={n} keys={sorted(k for k in full)} acc in [{acc.min():.3f},{acc.max():.3f}]")
@@ -553,7 +573,7 @@ def main():
     import torch
     torch.manual_seed(0)
     torch.set_num_threads(max(1, os.cpu_count() or 1))
-    from posegen_amd.config import surreal_config, h36m_config
+    from posegen_amd.config import surreal_config, surreal_single_config, h36m_config
     os.makedirs(a.out, exist_ok=True)
     only = set(filter(None, a.only.split(",")))
     want = lambda k: not only or k in only
@@ -596,6 +616,20 @@ def main():
                         seed_model=5, seed_pose=5, use_cams=True)
     if want("frame64"):
         gen_frame(a.out, "frame64", surreal_config(), H=64, chunk=1024)
+    # single-net / multires_views = 0 models (configs/surreal/surreal_single.txt); after every older case, so that the
+    # torch RNG state those consume does not move
+    if want("rays_single"):      # the shipped single-net config: one net, multires_views = 0, 96 + 48, culled frame
+        gen_render_rays(a.out, "rays_single", surreal_single_config(), n_rays=80, H=128, all_hit=False,
+                        seed_pose=13, model_keys=True)
+    if want("rays_single_v4"):   # the single-net algorithm alone: multires_views = 4, 64 + 16
+        gen_render_rays(a.out, "rays_single_v4", surreal_config(single_net=True), n_rays=80, H=128, all_hit=False,
+                        seed_pose=14, model_keys=True)
+    if want("rays_views0"):      # the 0-band view embedding alone: two nets, 64 + 16
+        gen_render_rays(a.out, "rays_views0", surreal_config(multires_views=0), n_rays=80, H=128, all_hit=False,
+                        seed_pose=15, model_keys=True)
+    if want("rays_single_train"):  # the rays_train recipe on the single-net model
+        gen_render_rays_train(a.out, "rays_single_train", surreal_single_config(), n_rays=64, H=128, seed_pose=6,
+                              model_keys=True)
 
 
 if __name__ == "__main__":
