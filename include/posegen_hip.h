@@ -259,6 +259,19 @@ int pg_train_forward(pg_handle* h, void* stream, int64_t n, const float* ray_bat
 int pg_train_backward(pg_handle* h, void* stream, int64_t tape_id, const float* d_rgb_map, const float* d_acc_map,
                       const float* d_rgb0, const float* d_acc0, const pg_net_grads* coarse, const pg_net_grads* fine);
 
+/* pg_train_backward plus the gradient of L with respect to the poses the forward pass read: pose refinement, the
+ * reference's opt_pose (PoseOptLayer's kps / bones / skts with autograd history, core/pose_opt.py:240-447,
+ * core/trainer.py:286-313; loss.backward() reaching them through the bone-relative transform and the embedding,
+ * core/raycasters.py:476-555, core/encoders.py:8-37, 101-122, 172-193, core/cutoff_embedder.py:111-174; the pose
+ * optimiser's step, trainer.py:453-485).  Only skts reaches the network inputs of the shipped encoders: kps and bones get
+ * no gradient.  d_skts (device) is OVERWRITTEN with dL/dskts: d_pose_stride 384 -> [n,24,4,4], one gradient per ray
+ * (whatever pose_stride the forward had: an expanded single pose is summed by the caller); 0 -> [24,4,4], the sum over
+ * the rays in a fixed order.  Row 3 of every 4x4 is 0.  Bitwise repeatable.  The skts the forward read must still be
+ * alive.  PG_EINVAL: d_pose_stride other than 0 / 384, d_skts null or not 16-byte aligned; PG_ESTATE: a stale tape. */
+int pg_train_backward_pose(pg_handle* h, void* stream, int64_t tape_id, const float* d_rgb_map, const float* d_acc_map,
+                           const float* d_rgb0, const float* d_acc0, const pg_net_grads* coarse, const pg_net_grads* fine,
+                           float* d_skts, int64_t d_pose_stride);
+
 /* One frame with its front and back end on the device.  Replaces, per
  * frame: get_rays + the bounding-box gather of kp_to_valid_rays (core/utils/ray_utils.py:6-28,
  * 83-136), render()'s ray_batch packing (core/trainer.py:118-137), RayCaster.forward on the

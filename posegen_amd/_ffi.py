@@ -124,6 +124,8 @@ PROTOTYPES = {
                                    C.POINTER(PgTrainDraws), C.POINTER(PgNetParams), C.POINTER(PgNetParams), C.POINTER(PgOutputs),
                                    C.POINTER(C.c_int64)]),
     "pg_train_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _FP, _FP, _FP, _FP, C.POINTER(PgNetGrads), C.POINTER(PgNetGrads)]),
+    "pg_train_backward_pose": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _FP, _FP, _FP, _FP, C.POINTER(PgNetGrads),
+                                         C.POINTER(PgNetGrads), _FP, C.c_int64]),
     "pg_plan_frames": (C.c_int, [C.c_int, C.POINTER(C.c_int64), C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int,
                                  C.POINTER(C.c_int)]),
 }

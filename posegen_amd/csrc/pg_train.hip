@@ -7,8 +7,11 @@
 // (rgb_map, acc_map, rgb0, acc0) -- what Trainer.compute_loss reads (trainer.py:321-383) -- with respect to every
 // tensor of both networks (core/networks/nerf.py:57-88) and the frame codes (core/networks/embedding.py).  The
 // importance samples are constants of the backward pass, as in the reference (`z_samples.detach()`,
-// core/utils/ray_utils.py:285); poses, rays and the embedder's cutoff parameters get no gradient (the reference's
-// cutoff_dist has requires_grad=False; pose optimisation is out of scope).
+// core/utils/ray_utils.py:285); rays and the embedder's cutoff parameters get no gradient (the reference's cutoff_dist has
+// requires_grad=False).  Poses get one on request (pg_train_backward_pose: the reference's opt_pose, core/trainer.py:286-313,
+// 453-485): the three input-gradient GEMMs of the embedding (dZ0 W0 + dZ5 W5[:, x], dG W_view[:, view]) into an fp32
+// workspace and embed_bwd_kernel, the transpose of embed_rows_kernel, which chains them to dL/dskts per ray; only skts reaches
+// the network inputs of the shipped encoders (kps and bones get none, as in the reference).
 //
 // Training batches are small (N_rand = 2048 rays -> 131 k + 164 k points, configs/surreal/surreal.txt:34), so the
 // 1080-wide embedding and the layer activations are MATERIALISED in HBM (the tape: 14 KB per point in fp32) and every layer
@@ -137,6 +140,125 @@ __global__ __launch_bounds__(256) void embed_rows_kernel(const float* __restrict
             for (int k = 0; k < FC_CH; ++k) put(xc, k, 0.0f);
         }
     }
+}
+
+// ---- the pose gradient: the transpose of embed_rows_kernel, one thread per (ray, joint) -------------------------------
+// dX: dL/d(the 1080 embedding inputs) of every point of the pass, fp32, rows of DXW (v part, direction part, view part in the
+// channel order above).  The thread walks its ray's points in sample order, recomputes what embed_rows_kernel formed (p, q =
+// R p + t, v = |q|, the cutoff weights and their derivatives w' = -tau s (1 - s), r = q / max(v, 1e-12), l = R d,
+// e = l / max(|l|, 1e-12), the octaves) and accumulates
+//   dv = sum_rows dXv (w_v f'(v) + w_v' f(v)) + sum_rows,c dXd w_d' g(e_c),   de_c = sum_rows dXd w_d g'(e_c),
+//   dq = r dv + (I - r r^T) / v dr,   dl = (I - e e^T) / |l| de,   dR += dq (x) p + dl (x) d,   dt += dq
+// (at v or |l| below 1e-12 torch's subgradients: norm -> 0, normalize -> 1 / eps).  The 3 x 4 of each bone goes to
+// out[ray * 384 + j * 16 ..] (row 3 written 0); accumulate: added to what is there (the coarse pass behind the fine one).
+constexpr int DXW = CH_X + CH_D;              // 1080: a row of the embedding-input gradient
+__global__ __launch_bounds__(256) void embed_bwd_kernel(const float* __restrict__ rays, const float* __restrict__ z,
+                                                        const float* __restrict__ pnoise, const float* __restrict__ skts,
+                                                        long long pose_stride, const float* __restrict__ cutoff, float tau_v,
+                                                        float tau_d, long long n_rays, int S, const float* __restrict__ dX,
+                                                        float* __restrict__ out, int accumulate) {
+    const long long idx = blockIdx.x * 256ll + threadIdx.x;
+    if (idx >= n_rays * J) return;
+    const long long ray = idx / J;
+    const int j = (int)(idx - ray * J);
+    const float* rb = rays + ray * 11;
+    const float* sk = skts + ray * pose_stride + j * 16;
+    const float dx_ = rb[3], dy_ = rb[4], dz_ = rb[5];
+    // the direction part depends on the ray only: e and its Jacobian once
+    const float l[3] = {fmaf(sk[2], dz_, fmaf(sk[1], dy_, sk[0] * dx_)), fmaf(sk[6], dz_, fmaf(sk[5], dy_, sk[4] * dx_)),
+                        fmaf(sk[10], dz_, fmaf(sk[9], dy_, sk[8] * dx_))};
+    const float ln = sqrtf(l[0] * l[0] + l[1] * l[1] + l[2] * l[2]);
+    const float lden = fmaxf(ln, 1e-12f);
+    const float e[3] = {l[0] / lden, l[1] / lden, l[2] / lden};
+    const float cut_v = cutoff[j], cut_d = cutoff[J + j];
+    float gR[3][3] = {}, gt[3] = {}, gde[3] = {};
+    for (int i = 0; i < S; ++i) {
+        const long long pt = ray * S + i;
+        const float zz = z[pt];
+        float p[3] = {__fadd_rn(rb[0], __fmul_rn(dx_, zz)), __fadd_rn(rb[1], __fmul_rn(dy_, zz)), __fadd_rn(rb[2], __fmul_rn(dz_, zz))};
+        if (pnoise) { p[0] = __fadd_rn(p[0], pnoise[pt * 3]); p[1] = __fadd_rn(p[1], pnoise[pt * 3 + 1]); p[2] = __fadd_rn(p[2], pnoise[pt * 3 + 2]); }
+        const float q[3] = {fmaf(sk[2], p[2], fmaf(sk[1], p[1], fmaf(sk[0], p[0], sk[3]))),
+                            fmaf(sk[6], p[2], fmaf(sk[5], p[1], fmaf(sk[4], p[0], sk[7]))),
+                            fmaf(sk[10], p[2], fmaf(sk[9], p[1], fmaf(sk[8], p[0], sk[11])))};
+        const float v = sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2]);
+        const float* dxv = dX + pt * DXW;
+        const float* dxd = dxv + CH_X;
+        // v part: rows (v, sin 2^k v, cos 2^k v) x w_v(v)
+        const float sv = 1.0f / (1.0f + expf(-tau_v * (v - cut_v)));
+        const float wv = 1.0f - sv, dwv = -tau_v * sv * (1.0f - sv);
+        float dv = dxv[j] * fmaf(dwv, v, wv);
+        {
+            float f = 1.0f;
+#pragma unroll
+            for (int k = 0; k < LV; ++k, f *= 2.0f) {
+                float s, c;
+                sincosf(f * v, &s, &c);
+                const float gs = dxv[(1 + 2 * k) * J + j], gc = dxv[(2 + 2 * k) * J + j];
+                dv += gs * fmaf(wv * f, c, dwv * s) + gc * fmaf(-wv * f, s, dwv * c);
+            }
+        }
+        // view part: rows (e_c, sin 2^k e_c, cos 2^k e_c) x w_d(v)
+        const float sd = 1.0f / (1.0f + expf(-tau_d * (v - cut_d)));
+        const float wd = 1.0f - sd, dwd = -tau_d * sd * (1.0f - sd);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float g0 = dxd[3 * j + c];
+            float de = g0 * wd, gw = g0 * e[c];
+            float f = 1.0f;
+#pragma unroll
+            for (int k = 0; k < LD; ++k, f *= 2.0f) {
+                float s, co;
+                sincosf(f * e[c], &s, &co);
+                const float gs = dxd[(1 + 2 * k) * (3 * J) + 3 * j + c], gc = dxd[(2 + 2 * k) * (3 * J) + 3 * j + c];
+                de += wd * f * (gs * co - gc * s);
+                gw += gs * s + gc * co;
+            }
+            gde[c] += de;
+            dv += dwd * gw;
+        }
+        // r = q / max(v, eps) and v = |q|
+        const float dr[3] = {dxv[CH_V + 3 * j], dxv[CH_V + 3 * j + 1], dxv[CH_V + 3 * j + 2]};
+        float dq[3];
+        if (v >= 1e-12f) {
+            const float inv = 1.0f / v;
+            const float r[3] = {q[0] * inv, q[1] * inv, q[2] * inv};
+            const float rdr = r[0] * dr[0] + r[1] * dr[1] + r[2] * dr[2];
+#pragma unroll
+            for (int a = 0; a < 3; ++a) dq[a] = fmaf(r[a], dv, (dr[a] - r[a] * rdr) * inv);
+        } else {
+            const float inv = v > 0.0f ? dv / v : 0.0f;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) dq[a] = fmaf(q[a], inv, dr[a] * 1e12f);
+        }
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+#pragma unroll
+            for (int b = 0; b < 3; ++b) gR[a][b] = fmaf(dq[a], p[b], gR[a][b]);
+            gt[a] += dq[a];
+        }
+    }
+    // l = R d, e = l / max(|l|, eps): dl = (I - e e^T) / |l| de (the summed de: d is the ray's, one outer product)
+    float dl[3];
+    if (ln >= 1e-12f) {
+        const float ede = e[0] * gde[0] + e[1] * gde[1] + e[2] * gde[2];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) dl[a] = (gde[a] - e[a] * ede) / ln;
+    } else {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) dl[a] = gde[a] * 1e12f;
+    }
+    const float dd[3] = {dx_, dy_, dz_};
+    float* o = out + ray * (J * 16) + j * 16;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        float g[4];
+#pragma unroll
+        for (int b = 0; b < 3; ++b) g[b] = fmaf(dl[a], dd[b], gR[a][b]);
+        g[3] = gt[a];
+        if (accumulate) { g[0] += o[4 * a]; g[1] += o[4 * a + 1]; g[2] += o[4 * a + 2]; g[3] += o[4 * a + 3]; }
+        *reinterpret_cast<float4*>(o + 4 * a) = make_float4(g[0], g[1], g[2], g[3]);
+    }
+    *reinterpret_cast<float4*>(o + 12) = make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
 // ---- fp32 GEMM: C[M,N] (op)= A[M,K] B[K,N] with element strides, 64 x 64 x 16 tiles on v_mfma_f32_32x32x2_f32 ------
@@ -1045,6 +1167,16 @@ struct Tape {
     pg_net_params params[2];
     bool has_fine = false;
     bool bf16 = false;          // 16-bit training mode (pg_set_train_precision PG_PREC_BF16): bf16 tape, bf16 operands in the large GEMMs
+    // what the pose gradient (pg_train_backward_pose) recomputes the embedding from: the caller's poses (kept alive by the caller
+    // until the backward), their stride, whether the points carry ray noise, the taus of the forward
+    const float* skts = nullptr;
+    long long pose_stride = 0;
+    bool rnoise = false;
+    float tau[2] = {0.f, 0.f};
+    // the pose gradient's workspace, allocated by the first pg_train_backward_pose (a step without one never touches it):
+    // dX [P, DXW] fp32 of one pass, then the per-ray 4 x 4s [n, 384] when the caller asks for their sum
+    uint8_t* pbuf = nullptr;
+    size_t pbytes = 0;
     int es() const { return bf16 ? 2 : 4; }                     // bytes per tape element
 };
 inline const void* el_off(const void* p, long long elems, int es) { return static_cast<const uint8_t*>(p) + elems * es; }
@@ -1360,7 +1492,10 @@ int mlp_forward(pg_handle* h, hipStream_t s, Tape& t, int net, const Pass& p, co
     return PG_OK;
 }
 
-int mlp_backward(pg_handle* h, hipStream_t s, Tape& t, int net, const Pass& p, const pg_net_params& w, const pg_net_grads& g) {
+// dX (null: no pose gradient): dL/d(the embedding inputs) [P, DXW] fp32 -- the x part dZ0 W0 + dZ5 W5[:, x], the view part
+// dG W_view[:, view]; each product after the weight gradient that reads the same activations, none of them writes the tape
+int mlp_backward(pg_handle* h, hipStream_t s, Tape& t, int net, const Pass& p, const pg_net_params& w, const pg_net_grads& g,
+                 float* dX = nullptr) {
     const long long P = p.P;
     const int fc = t.fc, vk = CH_D + (fc ? FC_CH : 0), vcols = W + vk;
     const int bf = t.bf16 ? 1 : 0, es = t.es();
@@ -1380,6 +1515,7 @@ int mlp_backward(pg_handle* h, hipStream_t s, Tape& t, int net, const Pass& p, c
     // views_linears.0 on [feature | view embedding (| frame code)]
     PG_TRY(linear_bwd_w(h, s, P, VW, W, dG, VW, p.F, W, g.w[20], vcols, g.w[21], AB));
     PG_TRY(linear_bwd_w(h, s, P, VW, vk, dG, VW, el_off(p.X, CH_X, es), XW, g.w[20] + W, vcols, nullptr, AB));
+    if (dX) PG_TRY(linear_bwd_x(h, s, P, VW, CH_D, dG, VW, WT(20, W), vcols, dX + CH_X, DXW, 0, nullptr, AB));
     void* dF = t.tmpA;
     PG_TRY(linear_bwd_x(h, s, P, VW, W, dG, VW, WT(20, 0), vcols, dF, W, 0, nullptr, ABC, nullptr, 0, bf ? t.wbT[net][20] : nullptr));
     if (fc && g.codes) {
@@ -1412,9 +1548,11 @@ int mlp_backward(pg_handle* h, hipStream_t s, Tape& t, int net, const Pass& p, c
     for (int l = DEPTH - 1; l >= 0; --l) {
         if (l == 0) {
             PG_TRY(linear_bwd_w(h, s, P, W, CH_X, dH, W, p.X, XW, g.w[0], CH_X, g.w[1], AB));
+            if (dX) PG_TRY(linear_bwd_x(h, s, P, W, CH_X, dH, W, WT(0, 0), CH_X, dX, DXW, GEMM_ACC, nullptr, AB));     // + the skip layer's share
         } else if (l == SKIP + 1) {
             PG_TRY(linear_bwd_w(h, s, P, W, CH_X, dH, W, p.X, XW, g.w[2 * l], CH_X + W, g.w[2 * l + 1], AB));
             PG_TRY(linear_bwd_w(h, s, P, W, W, dH, W, p.H[l - 1], W, g.w[2 * l] + CH_X, CH_X + W, nullptr, AB));
+            if (dX) PG_TRY(linear_bwd_x(h, s, P, W, CH_X, dH, W, WT(2 * l, 0), CH_X + W, dX, DXW, 0, nullptr, AB));
             PG_TRY(linear_bwd_x(h, s, P, W, W, dH, W, WT(2 * l, CH_X), CH_X + W, other, W, 0, p.H[l - 1], ABCM, nullptr, 0, bf ? t.wbT[net][2 * l] : nullptr));
             std::swap(dH, other);
         } else {
@@ -1434,6 +1572,7 @@ void pg_train_release(pg_handle* h) {
     if (!h || !h->train) return;
     pgt::Tape* t = static_cast<pgt::Tape*>(h->train);
     if (t->buf) (void)hipFree(t->buf);
+    if (t->pbuf) (void)hipFree(t->pbuf);
     delete t;
     h->train = nullptr;
 }
@@ -1543,6 +1682,7 @@ int pg_train_forward(pg_handle* h, void* stream, int64_t n, const float* ray_bat
     t.part = take(PART_FLOATS * 4); t.rs_part = take(RS_FLOATS * 4); t.ray_g = take((size_t)n * FC_CH * 4);
     t.params[0] = *coarse;
     if (N > 0) t.params[1] = *fine;
+    t.skts = skts; t.pose_stride = pose_stride; t.rnoise = rnoise; t.tau[0] = h->tau[0]; t.tau[1] = h->tau[1];
     PG_HIP(h, hipMemcpyAsync(t.rays, ray_batch, (size_t)n * 44, hipMemcpyDeviceToDevice, s));
     if (cams) PG_HIP(h, hipMemcpyAsync(t.cams, cams, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
 
@@ -1601,10 +1741,10 @@ int pg_train_forward(pg_handle* h, void* stream, int64_t n, const float* ray_bat
     return PG_OK;
 }
 
-int pg_train_backward(pg_handle* h, void* stream, int64_t tape_id, const float* d_rgb_map, const float* d_acc_map, const float* d_rgb0,
-                      const float* d_acc0, const pg_net_grads* coarse, const pg_net_grads* fine) {
+// the backward of both entries; d_skts null: no pose gradient (the kernels of pg_train_backward, nothing else)
+static int train_backward(pg_handle* h, void* stream, int64_t tape_id, const float* d_rgb_map, const float* d_acc_map, const float* d_rgb0,
+                          const float* d_acc0, const pg_net_grads* coarse, const pg_net_grads* fine, float* d_skts, int64_t d_pose_stride) {
     using namespace pgt;
-    if (!h) return pg_fail(nullptr, PG_EINVAL, "null handle");
     if (!h->train || !static_cast<Tape*>(h->train)->valid) return pg_fail(h, PG_ESTATE, "pg_train_backward: no forward pass on the tape (pg_train_forward)");
     Tape& t = *static_cast<Tape*>(h->train);
     // ONE forward is outstanding per handle: a later pg_train_forward reuses the tape, and its activations must not be
@@ -1616,12 +1756,35 @@ int pg_train_backward(pg_handle* h, void* stream, int64_t tape_id, const float* 
     if (!coarse || (t.has_fine && !fine)) return pg_fail(h, PG_EINVAL, "pg_train_backward: null gradient struct");
     PG_HIP(h, hipSetDevice(h->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
+    const bool pose = d_skts != nullptr;
+    float *dX = nullptr, *per_ray = nullptr;
+    if (pose) {
+        const long long Pm = std::max(t.pass[0].P, t.pass[1].P);
+        const size_t dx_bytes = ((size_t)Pm * DXW * 4 + 255) & ~size_t(255);
+        const size_t need = dx_bytes + (d_pose_stride == 0 ? (size_t)t.n * J * 16 * 4 : 0);
+        if (need > t.pbytes) {
+            if (t.pbuf) { PG_HIP(h, hipDeviceSynchronize()); PG_HIP(h, hipFree(t.pbuf)); t.pbuf = nullptr; t.pbytes = 0; }
+            hipError_t e = hipMalloc(reinterpret_cast<void**>(&t.pbuf), need);
+            if (e != hipSuccess) return pg_fail(h, PG_ENOMEM, "pose gradient workspace of %zu bytes failed: %s", need, hipGetErrorString(e));
+            t.pbytes = need;
+        }
+        dX = reinterpret_cast<float*>(t.pbuf);
+        per_ray = d_pose_stride == 0 ? reinterpret_cast<float*>(t.pbuf + dx_bytes) : d_skts;
+    }
+    bool first = true;
     auto run = [&](int k, const float* d_rgb, const float* d_acc, const pg_net_grads& g) -> int {
         const Pass& p = t.pass[k];
         hipLaunchKernelGGL(composite_bwd_kernel, dim3((unsigned)((t.n + 63) / 64)), dim3(64), 0, s, t.rays, p.z, p.raw, p.noise, (long long)t.n, p.S,
                            h->cfg.density_scale, h->cfg.rgb_eps, h->cfg.density_act, h->cfg.softplus_shift, d_rgb, d_acc, t.d_raw);
         PG_LAUNCH_CHECK(h, "composite backward");
-        return mlp_backward(h, s, t, k, p, t.params[k], g);
+        PG_TRY(mlp_backward(h, s, t, k, p, t.params[k], g, dX));
+        if (pose) {         // this pass's share of every ray's 4 x 4s: the fine pass writes them, the coarse pass adds its own
+            hipLaunchKernelGGL(embed_bwd_kernel, dim3((unsigned)((t.n * J + 255) / 256)), dim3(256), 0, s, t.rays, p.z, t.rnoise ? p.pn : nullptr,
+                               t.skts, t.pose_stride, h->d_cut, t.tau[0], t.tau[1], (long long)t.n, p.S, dX, per_ray, first ? 0 : 1);
+            PG_LAUNCH_CHECK(h, "embedding backward");
+            first = false;
+        }
+        return PG_OK;
     };
     if (t.has_fine) {
         PG_TRY(run(1, d_rgb_map, d_acc_map, *fine));
@@ -1629,7 +1792,28 @@ int pg_train_backward(pg_handle* h, void* stream, int64_t tape_id, const float* 
     } else {
         PG_TRY(run(0, d_rgb_map, d_acc_map, *coarse));
     }
+    if (pose && d_pose_stride == 0) {      // the sum over the rays, in ray order (slices of reduce_parts_kernel)
+        hipLaunchKernelGGL(reduce_parts_kernel, dim3((unsigned)((J * 16 + 255) / 256)), dim3(256), 0, s, per_ray, (int)t.n, 1, J * 16, d_skts, (long long)(J * 16));
+        PG_LAUNCH_CHECK(h, "pose gradient reduction");
+    }
     return PG_OK;
+}
+
+int pg_train_backward(pg_handle* h, void* stream, int64_t tape_id, const float* d_rgb_map, const float* d_acc_map, const float* d_rgb0,
+                      const float* d_acc0, const pg_net_grads* coarse, const pg_net_grads* fine) {
+    if (!h) return pg_fail(nullptr, PG_EINVAL, "null handle");
+    return train_backward(h, stream, tape_id, d_rgb_map, d_acc_map, d_rgb0, d_acc0, coarse, fine, nullptr, 0);
+}
+
+int pg_train_backward_pose(pg_handle* h, void* stream, int64_t tape_id, const float* d_rgb_map, const float* d_acc_map, const float* d_rgb0,
+                           const float* d_acc0, const pg_net_grads* coarse, const pg_net_grads* fine, float* d_skts, int64_t d_pose_stride) {
+    if (!h) return pg_fail(nullptr, PG_EINVAL, "null handle");
+    if (d_pose_stride != 0 && d_pose_stride != 384)
+        return pg_fail(h, PG_EINVAL, "pg_train_backward_pose: d_pose_stride must be 0 (the sum over the rays) or 384 (one 4 x 4 per joint and ray), not %lld",
+                       (long long)d_pose_stride);
+    if (!d_skts || reinterpret_cast<uintptr_t>(d_skts) % 16 != 0)
+        return pg_fail(h, PG_EINVAL, "pg_train_backward_pose: d_skts must be a non-null, 16-byte aligned device array");
+    return train_backward(h, stream, tape_id, d_rgb_map, d_acc_map, d_rgb0, d_acc0, coarse, fine, d_skts, d_pose_stride);
 }
 
 }  // extern "C"

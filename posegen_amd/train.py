@@ -21,14 +21,17 @@ from .raycaster import NET_TENSOR_ORDER, HipRayCaster, _dev_f32, _ptr, make_trai
 
 class _RenderRaysFn(torch.autograd.Function):
     """outputs (rgb_map, acc_map, rgb0, acc0, disp_map, disp0) of one training-mode render_rays call; differentiable
-    with respect to the 24 (+ frame codes) tensors of each net."""
+    with respect to the 24 (+ frame codes) tensors of each net and, with opt_pose, to `skts` (the caller's tensor as passed:
+    [n,24,4,4] gets one gradient per ray -- an expanded single pose included, autograd's ExpandBackward sums them --,
+    [1,24,4,4] / [24,4,4] the sum over the rays)."""
 
     @staticmethod
-    def forward(ctx, caster, call, *params):
+    def forward(ctx, caster, call, skts, *params):
         r = caster.renderer
         lib, dev = r.lib, r.device
         rb, sk, ps, cy, cs, cam, S, N, flags, draws = call
         n = rb.shape[0]
+        ctx.skts_shape, ctx.skts_dtype, ctx.skts_device = tuple(skts.shape), skts.dtype, skts.device
         nper = 24 + (1 if caster.cfg.framecode_ch > 0 else 0)
         nets = [params[:nper], params[nper:2 * nper]] if N > 0 else [params[:nper]]
         keep = [rb, sk, cy, cam]
@@ -90,10 +93,19 @@ class _RenderRaysFn(torch.autograd.Function):
         gp = lambda g: None if g is None or g.numel() == 0 else _dev_f32(g, dev)
         a, b, c, d = gp(g_rgb), gp(g_acc), gp(g_rgb0), gp(g_acc0)
         # (a forward pass in between has overwritten the handle's one tape: the library refuses the stale id)
-        r._check(r.lib.pg_train_backward(r.handle, r._stream(), ctx.tape_id, _ptr(a), _ptr(b), _ptr(c), _ptr(d), C.byref(structs[0]),
-                                         C.byref(structs[1]) if ctx.n_nets > 1 else None))
+        nets = (C.byref(structs[0]), C.byref(structs[1]) if ctx.n_nets > 1 else None)
+        d_skts = None
+        if ctx.needs_input_grad[2]:                     # pose refinement: dL/dskts with the parameter gradients, in one pass
+            shape = ctx.skts_shape
+            per_ray = len(shape) == 4 and shape[0] > 1
+            d_skts = torch.empty((shape[0] if per_ray else 1, 24, 4, 4), device=dev, dtype=torch.float32)
+            r._check(r.lib.pg_train_backward_pose(r.handle, r._stream(), ctx.tape_id, _ptr(a), _ptr(b), _ptr(c), _ptr(d), *nets,
+                                                  _ptr(d_skts), 384 if per_ray else 0))
+            d_skts = d_skts.reshape(shape).to(device=ctx.skts_device, dtype=ctx.skts_dtype)
+        else:
+            r._check(r.lib.pg_train_backward(r.handle, r._stream(), ctx.tape_id, _ptr(a), _ptr(b), _ptr(c), _ptr(d), *nets))
         caster._stale = True                            # (an optimiser step follows: the inference kernels' packed weights lag from here)
-        return (None, None) + tuple(grads)
+        return (None, None, d_skts) + tuple(grads)
 
 
 class _NetParams(torch.nn.Module):
@@ -169,9 +181,14 @@ class TrainableRayCaster(torch.nn.Module):
 
     `train_precision`: "fp32" (default: the reference trains in fp32, trainer.py:232-275; gradients within 1e-4 of its
     autograd) or "bf16" (opt-in: the tape and the large GEMMs' operands in bf16, fp32 accumulate).  It is the TRAINING
-    step's arithmetic only and independent of the caster's rendering precision (`set_precision`)."""
+    step's arithmetic only and independent of the caster's rendering precision (`set_precision`).
 
-    def __init__(self, caster: HipRayCaster, train_precision: str = "fp32"):
+    `opt_pose` (the reference's flag, set in its h36m / mixamo / perfcap configs): `skts` may require a gradient -- the
+    output of PoseOptLayer (core/pose_opt.py:240-447, core/trainer.py:286-313) -- and `loss.backward()` reaches it through
+    the bone-relative transform and the embedding (pg_train_backward_pose).  `kp_batch` / `bones` may require one too and
+    receive none, as in the reference (the shipped encoders do not read them).  Rays and cylinders get no gradient."""
+
+    def __init__(self, caster: HipRayCaster, train_precision: str = "fp32", opt_pose: bool = False):
         super().__init__()
         if train_precision not in ("fp32", "bf16"):
             raise ValueError(f"train_precision must be 'fp32' or 'bf16', not {train_precision!r}")
@@ -181,6 +198,7 @@ class TrainableRayCaster(torch.nn.Module):
                                       "path (they render through HipRayCaster)")
         self.caster = caster
         self.train_precision = train_precision
+        self.opt_pose = bool(opt_pose)
         caster.renderer.set_train_precision(train_precision)
         self._stale = False                              # the inference kernels' packed weights lag the parameters
         self.cfg = caster.cfg
@@ -303,13 +321,16 @@ class TrainableRayCaster(torch.nn.Module):
             raise NotImplementedError("subject_idxs (multi-subject nets) are not supported")
         if skts is None or cyls is None:
             raise ValueError("skts and cyls are required (A-NeRF bone-relative rendering)")
-        # The backward pass differentiates with respect to the networks' tensors only.  The reference's pose
-        # optimisation (popt_layer, trainer.py:496-515) backpropagates into skts / kp through the embedding: refused
-        # here rather than left without a gradient (out of scope).
+        # Without opt_pose the backward pass differentiates with respect to the networks' tensors only: a pose that wants a
+        # gradient is refused rather than left without one.  With opt_pose (the reference's pose refinement, popt_layer,
+        # trainer.py:286-313, 453-485) skts gets dL/dskts; kp_batch / bones are accepted and get none, as in the reference,
+        # whose shipped encoders read only skts.  Rays and cylinders are refused either way.
+        wanted = ("ray_batch", "cyls") if self.opt_pose else ("ray_batch", "skts", "kp_batch", "cyls", "bones")
         for name, t in (("ray_batch", ray_batch), ("skts", skts), ("kp_batch", kp_batch), ("cyls", cyls), ("bones", bones)):
-            if torch.is_tensor(t) and t.requires_grad:
-                raise NotImplementedError(f"{name} requires a gradient: the HIP training step has no gradient for poses / rays "
-                                          "(pose optimisation is not on the HIP path); pass a detached tensor")
+            if name in wanted and torch.is_tensor(t) and t.requires_grad:
+                why = "rays and cylinders get no gradient" if self.opt_pose else \
+                    "the HIP training step has no gradient for poses / rays without opt_pose=True"
+                raise NotImplementedError(f"{name} requires a gradient: {why}; pass a detached tensor")
         r = self.caster.renderer
         cfg = self.cfg
         S = cfg.n_samples if N_samples is None else int(N_samples)
@@ -322,7 +343,8 @@ class TrainableRayCaster(torch.nn.Module):
             pad = torch.zeros(n, 11, device=r.device)
             pad[:, :min(11, rb.shape[1])] = rb[:, :11]
             rb = pad
-        sk, ps = r._pose_args(skts, n)
+        skts = torch.as_tensor(skts)
+        sk, ps = r._pose_args(skts.detach(), n)
         cy, cs = r._cyl_args(cyls, n)
         cam = None
         if cams is not None:
@@ -338,7 +360,8 @@ class TrainableRayCaster(torch.nn.Module):
         r.set_chunk(max(n, 1))                          # one call = one nanmean group (ray_utils.py:292-344)
         try:
             flags = _ffi.PG_FLAG_LINDISP if lindisp else 0
-            rgb, acc, rgb0, acc0, disp, disp0 = _RenderRaysFn.apply(self, (rb, sk, ps, cy, cs, cam, S, N, flags, draws or None), *self._flat())
+            rgb, acc, rgb0, acc0, disp, disp0 = _RenderRaysFn.apply(self, (rb, sk, ps, cy, cs, cam, S, N, flags, draws or None), skts,
+                                                                    *self._flat())
         finally:
             r.set_chunk(keep)
         out = {"rgb_map": rgb, "disp_map": disp, "acc_map": acc}

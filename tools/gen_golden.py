@@ -536,6 +536,121 @@ def gen_train_grads(out, name, cfg, *, n_rays, H, seed_model=0, seed_pose=1, per
     print(f"[{name}] rays={n} loss={float(loss):.6f} max |grad| {worst:.3e}, {sum(1 for k in d if k.startswith('gnorm_'))} gradient tensors")
 
 
+def gen_train_grads_pose(out, name, cfg, *, n_rays, H, n_poses, seed_model=0, seed_pose=1, perturb=1., raw_noise_std=1.,
+                         use_cams=False, max_seed_tries=16, max_sens=1e-5):
+    """gen_train_grads with pose refinement (opt_pose, core/trainer.py:286-313): the reference's training step with `skts`
+    requiring a gradient, one pose per ray as PoseOptLayer hands them over by kp_idx -- `n_poses` frames, each seen by its own
+    camera frame's rays, the batch split evenly between them.  Stored besides what gen_train_grads stores: the per-frame
+    poses and cylinders (`skts`, `kps`, `bones`, `cyl` [n_poses, ...]), `kp_idx` [n] and dL/dskts of every ray in full
+    (`dskts` [n,24,4,4]: n x 384 floats).  The conditioning filter is gen_train_grads', with the pose gradient among the
+    values it watches."""
+    import torch
+    from core.trainer import img2mse
+    from core.utils.ray_utils import kp_to_valid_rays
+    from posegen_amd import synthetic as syn
+    with tempfile.TemporaryDirectory() as wd:
+        caster, kw, (wc, wf, tau_v, tau_d) = _build_reference_caster(cfg, seed_model, wd)
+    W = H
+    per = n_rays // n_poses
+    for seed_pose in range(seed_pose, seed_pose + max_seed_tries):
+        bones, kps, skts = syn.make_pose(n_poses, seed_pose)
+        c2ws, focals = syn.make_camera(n_poses, H, W)
+        rays, vids, cyls, boxes = kp_to_valid_rays(torch.tensor(c2ws), H, W, focals,
+                                                   kps=torch.tensor(kps), ext_scale=cfg.ext_scale)
+        ros, rds, kp_idx = [], [], []
+        for f in range(n_poses):
+            ro, rd = rays[f]
+            sel = np.unique(np.linspace(0, ro.shape[0] - 1, per).round().astype(np.int64))
+            ros.append(ro[sel].float()); rds.append(rd[sel].float()); kp_idx += [f] * len(sel)
+        ro, rd = torch.cat(ros), torch.cat(rds)
+        kp_idx = np.asarray(kp_idx, dtype=np.int64)
+        n = ro.shape[0]
+        vd = rd / torch.norm(rd, dim=-1, keepdim=True)
+        ones = torch.ones(n, 1)
+        batch = torch.cat([ro, rd, 0. * ones, 1. * ones, vd], -1)
+        kp_b = torch.tensor(kps)[kp_idx]
+        skt_b = torch.tensor(skts)[kp_idx].clone().requires_grad_(True)
+        cyl_b = cyls[kp_idx]
+        bones_b = torch.tensor(bones)[kp_idx]
+        S, N = cfg.n_samples, cfg.n_importance
+        rng = np.random.RandomState(11)
+        target = torch.tensor(rng.uniform(0, 1, size=(n, 3)).astype(np.float32))
+        cams = torch.tensor(rng.randint(0, cfg.n_framecodes, size=n).astype(np.float32)) if use_cams else None
+        call_kw = {k: v for k, v in kw.items() if k != "ray_caster"}
+        call_kw.pop("use_viewdirs", None)
+        call_kw.update(perturb=perturb, raw_noise_std=raw_noise_std, ray_noise_std=0., pytest=True)
+
+        def step():
+            caster.train()
+            for p_ in caster.parameters():
+                p_.grad = None
+            skt_b.grad = None
+            full = caster(batch, kp_batch=kp_b, skts=skt_b, cyls=cyl_b, bones=bones_b, cams=cams, subject_idxs=None, **call_kw)
+            loss = img2mse(full["rgb_map"] + (1. - full["acc_map"])[..., None] * 1.0, target, reduction="mean")
+            if "rgb0" in full:
+                loss = loss + img2mse(full["rgb0"] + (1. - full["acc0"])[..., None] * 1.0, target, reduction="mean") * 1.0
+            loss.backward()
+            return full, loss
+
+        def pose_sens():
+            """_grad_sensitivity over the parameters and the pose gradient (relative to its largest entry)"""
+            base = skt_b.grad.detach().clone()
+            params = list(caster.parameters())
+            keep = [p_.detach().clone() for p_ in params]
+            gen = torch.Generator().manual_seed(5)
+            worst = 0.0
+            for _ in range(N_COND):
+                with torch.no_grad():
+                    for p_, k_ in zip(params, keep):
+                        p_.copy_(k_ * (1 + 1e-7 * torch.randn(k_.shape, generator=gen)))
+                step()
+                worst = max(worst, float((skt_b.grad - base).abs().max()) / max(float(base.abs().max()), 1e-12))
+            with torch.no_grad():
+                for p_, k_ in zip(params, keep):
+                    p_.copy_(k_)
+            step()
+            return worst
+
+        full, loss = step()
+        sens = max(_grad_sensitivity(caster, step), pose_sens())
+        print(f"[{name}] seed_pose={seed_pose}: gradient sensitivity to 1e-7 weight noise {sens:.2e}")
+        if max_sens is None or sens <= max_sens:
+            break
+    else:
+        raise SystemExit(f"[{name}] no well-conditioned batch in {max_seed_tries} pose seeds")
+    full, loss = step()             # the gradients of the unperturbed weights back in .grad
+    caster.eval()
+    d = {"ray_batch": batch.numpy(), "kps": kps, "skts": skts, "bones": bones, "cyl": cyls.numpy(), "kp_idx": kp_idx,
+         "target": target.numpy(), "tau_v": tau_v, "tau_d": tau_d, "seed_model": seed_model, "n_samples": S, "n_importance": N,
+         "framecode_ch": cfg.framecode_ch, "n_framecodes": cfg.n_framecodes,
+         "digest_coarse": _weights_digest(wc), "digest_fine": _weights_digest(wf),
+         "perturb": perturb, "raw_noise_std": raw_noise_std, "ray_noise_std": 0., "n_rays": n, "loss": float(loss.detach()),
+         "seed_pose": seed_pose, "grad_sensitivity": sens, "dskts": skt_b.grad.detach().numpy().copy()}
+    if cams is not None:
+        d["cams"] = cams.numpy()
+    f32 = lambda a: torch.Tensor(a).numpy()
+    if perturb > 0:
+        np.random.seed(0); d["t_rand"] = f32(np.random.rand(n, S))
+        if N > 0:
+            np.random.seed(0); d["u_rand"] = f32(np.random.rand(n, N))
+    if raw_noise_std > 0:
+        np.random.seed(0); d["noise0"] = f32(np.random.rand(n, S) * raw_noise_std)
+        if N > 0:
+            np.random.seed(0); d["noise1"] = f32(np.random.rand(n, S + N) * raw_noise_std)
+    for k in ("rgb_map", "acc_map", "rgb0", "acc0"):
+        if k in full:
+            d[k] = full[k].detach().numpy()
+    for tag, net in (("coarse", caster.network), ("fine", caster.network_fine)):
+        if net is None:
+            continue
+        for pname, p_ in net.named_parameters():
+            g = p_.grad.detach().numpy().reshape(-1)
+            d[f"gnorm_{tag}_{pname}"] = np.float64(np.linalg.norm(g.astype(np.float64)))
+            d[f"gval_{tag}_{pname}"] = g[grad_sample_index(g.size)]
+    np.savez_compressed(os.path.join(out, f"{name}.npz"), **d)
+    print(f"[{name}] rays={n} poses={n_poses} loss={float(loss.detach()):.6f} max |dL/dskts| {float(np.abs(d['dskts']).max()):.3e}")
+
+
 def gen_frame(out, name, cfg, H, chunk, seed_model=0, seed_pose=1, n_frames=2):
     """a-1/a-3: whole frames through the reference's render_path (bbox cull,
     chunk loop with a chunk boundary inside the frame, white background)."""
@@ -630,6 +745,12 @@ def main():
     if want("rays_single_train"):  # the rays_train recipe on the single-net model
         gen_render_rays_train(a.out, "rays_single_train", surreal_single_config(), n_rays=64, H=128, seed_pose=6,
                               model_keys=True)
+    # pose refinement (opt_pose): dL/dskts of the reference's training step, after every older case
+    if want("train_grads_pose"):     # per-ray poses, half the rays from each of two frames (PoseOptLayer by kp_idx)
+        gen_train_grads_pose(a.out, "train_grads_pose", surreal_config(), n_rays=48, H=128, n_poses=2, seed_pose=16)
+    if want("train_grads_pose_h36m"):  # frame codes, 64 + 16 samples, one pose for every ray
+        gen_train_grads_pose(a.out, "train_grads_pose_h36m", h36m_config(n_samples=64, n_importance=16), n_rays=24, H=128,
+                             n_poses=1, seed_model=5, seed_pose=17, use_cams=True)
 
 
 if __name__ == "__main__":
