@@ -246,7 +246,11 @@ typedef struct pg_net_grads {
  * NULL when n_importance == 0.  The parameter tensors and the tape stay in use until pg_train_backward.  The handle
  * holds ONE tape: *tape_id (may be NULL) receives the id of this pass, which pg_train_backward must present -- a
  * forward pass in between overwrites the tape and makes the older id stale (PG_ESTATE) instead of silently
- * differentiating the wrong activations. */
+ * differentiating the wrong activations.
+ * single_net handles: ONE net -- `coarse` holds its parameters, `fine` is not read (may be NULL) -- evaluated at the
+ * n_samples coarse and the n_importance new points of every ray; pg_train_backward / pg_train_backward_pose write ONE set of
+ * gradients into their `coarse` argument (`fine` not read).  With multires_views = 0 tensor 20 and its gradient are the
+ * reference's [128, 256 + 72 (+16)] view weight.  Two nets with multires_views = 0 are refused (PG_EINVAL). */
 int pg_train_forward(pg_handle* h, void* stream, int64_t n, const float* ray_batch, const float* skts, int64_t pose_stride,
                      const float* cyls, int64_t cyl_stride, const float* cams, int n_samples, int n_importance, int flags,
                      const pg_train_draws* draws, const pg_net_params* coarse, const pg_net_params* fine, const pg_outputs* out,

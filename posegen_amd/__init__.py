@@ -12,3 +12,13 @@ from .config import (RenderConfig, surreal_config, surreal_single_config, h36m_c
 __all__ = ["RenderConfig", "surreal_config", "surreal_single_config", "h36m_config", "PREC_FP32", "PREC_BF16",
            "PREC_BF16X3", "PREC_FP16", "PREC_FP16X3", "PREC_FP16C", "PREC_FP16M", "PREC_NAMES", "PREC_BY_NAME"]
 __version__ = "0.1.0"
+
+_TRAIN_NAMES = ("make_trainable", "TrainableRayCaster", "SingleNetTrainableRayCaster")
+
+
+def __getattr__(name):
+    # the training wrappers live in posegen_amd.train (imports torch): resolved on first use
+    if name in _TRAIN_NAMES:
+        from . import train
+        return getattr(train, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -42,6 +42,13 @@ int pg_launch_composite(const float* rays, const float* z, const float* raw, lon
                         float density_scale, float rgb_eps, int density_act, float act_shift, float* rgb, float* disp, float* acc,
                         float* alpha, float* weights, int n_imp, float* z_fine, const float* noise, const float* u_rand, int* order,
                         void* stream);
+int pg_launch_composite_iso(const float* rays, const float* z, const float* raw, long long n, int S, float density_scale, float rgb_eps,
+                            int density_act, float act_shift, float* rgb, float* disp, float* acc, float* alpha, float* weights, int n_imp,
+                            float* z_fine, const float* noise, const float* u_rand, int* order, float* z_new, int ld_new, void* stream);
+int pg_launch_composite_merged(const float* rays, const float* z_fine, const float* raw_c, const float* raw_new, int ld_new, const int* order,
+                               long long n, int S0, int N, float density_scale, float rgb_eps, int density_act, float act_shift, float* rgb,
+                               float* disp, float* acc, float* alpha, const float* noise, float* raw_out, void* stream);
+void pg_launch_widen_views(const float* src, int framecode_ch, float* dst, void* stream);
 int pg_composite_max_samples(void);
 int pg_composite_max_importance(void);
 }
@@ -1141,10 +1148,121 @@ __global__ __launch_bounds__(64) void composite_bwd_kernel(const float* __restri
     }
 }
 
+// ---- backward of the single-net model's two composites (core/raycasters.py:446-469), one thread per ray ------------------
+// One net has produced raw [P, 4]: rows [0, n S0) the coarse points (ray-major), rows [n S0, P) the N new points of every ray
+// in z_new order.  The coarse maps composite a ray's S0 coarse rows over z_c with noise0; the fine maps composite its S0 + N
+// rows MERGED by depth -- sample i of z_f reads source order[i] of cat([coarse, new]) (the rank map of the forward's
+// composite_kernel<CP_ISO>, clamped like composite_kernel<CP_MERGE> clamps it) -- with noise1 indexed by the merged position.
+// d_raw of a row is therefore the sum of up to two terms, formed in a FIXED order by the ray's one thread: the fine composite
+// writes every row it reads (d_raw arrives zeroed), then the coarse composite adds its share to the coarse rows.  The scan of
+// one composite is composite_bwd_kernel's, operation for operation; the transmittances of the forward sweep are kept in
+// Tbuf [S0 + N][n] (sample-major: the rays of a wave read neighbouring floats) instead of a per-thread array -- no scratch.
+struct CBwd { float density_scale, rgb_eps, act_shift; int act; };
+template <bool MERGED, bool ADD>
+__device__ __forceinline__ void composite_bwd_ray(const float* __restrict__ zr, const float* __restrict__ nz, const int* __restrict__ ord,
+                                                  int S, int S0, long long row0, long long new0, float dn, const float* __restrict__ raw,
+                                                  float* d_raw, float* Tb, long long ts, const CBwd c, float gr, float gg, float gb,
+                                                  bool has_acc, float d_acc) {
+    auto actf = [&](float x) { if (c.act == 0) return fmaxf(x, 0.0f); const float t = x - c.act_shift; return t > 20.0f ? t : log1pf(expf(t)); };
+    auto dact = [&](float x) { if (c.act == 0) return x > 0.0f ? 1.0f : 0.0f; const float t = x - c.act_shift; return t > 20.0f ? 1.0f : 1.0f / (1.0f + expf(-t)); };
+    auto row = [&](int i) -> long long {
+        if (!MERGED) return row0 + i;
+        const int o = min(max(ord[i], 0), S - 1);
+        return o < S0 ? row0 + o : new0 + (o - S0);
+    };
+    // front to back: the transmittances and the sum of the weights (for the min(.., 1) of acc_map)
+    float T = 1.0f, wsum = 0.0f;
+    for (int i = 0; i < S; ++i) {
+        const float delta = (i + 1 < S ? zr[i + 1] - zr[i] : 1e10f) * dn;
+        const float s = actf(raw[row(i) * 4 + 3] / c.density_scale + (nz ? nz[i] : 0.0f));
+        const float a = 1.0f - expf(-s * delta);
+        Tb[i * ts] = T;
+        wsum += a * T;
+        T *= 1.0f - a + 1e-10f;
+    }
+    const float ga = (has_acc && wsum < 1.0f) ? d_acc : 0.0f;
+    float suffix = 0.0f;        // sum_{k>i} g_k w_k
+    for (int i = S - 1; i >= 0; --i) {
+        const long long rw = row(i) * 4;
+        const float Ti = Tb[i * ts];
+        const float delta = (i + 1 < S ? zr[i + 1] - zr[i] : 1e10f) * dn;
+        const float4 q = *reinterpret_cast<const float4*>(raw + rw);
+        const float pre = q.w / c.density_scale + (nz ? nz[i] : 0.0f);
+        const float s = actf(pre);
+        const float e = expf(-s * delta);
+        const float a = 1.0f - e;
+        const float w = a * Ti;
+        const float sr = 1.0f / (1.0f + expf(-q.x)), sg = 1.0f / (1.0f + expf(-q.y)), sb = 1.0f / (1.0f + expf(-q.z));
+        const float k = 1.0f + 2.0f * c.rgb_eps;
+        const float g = gr * (sr * k - c.rgb_eps) + gg * (sg * k - c.rgb_eps) + gb * (sb * k - c.rgb_eps) + ga;
+        const float dA = g * Ti - suffix / (1.0f - a + 1e-10f);
+        const float da = dact(pre);
+        float4 d = make_float4(gr * w * k * sr * (1.0f - sr), gg * w * k * sg * (1.0f - sg), gb * w * k * sb * (1.0f - sb),
+                               da > 0.0f ? dA * delta * e * da / c.density_scale : 0.0f);
+        if (ADD) {
+            const float4 o = *reinterpret_cast<const float4*>(d_raw + rw);
+            d = make_float4(o.x + d.x, o.y + d.y, o.z + d.z, o.w + d.w);
+        }
+        *reinterpret_cast<float4*>(d_raw + rw) = d;
+        suffix += g * w;
+    }
+}
+// d_rgb / d_acc: of the fine maps (both null: that composite is left out and its rows keep their zeros); d_rgb0 / d_acc0: of the
+// coarse maps.  N == 0 (no importance samples): the caller passes the one composite as the coarse one.
+__global__ __launch_bounds__(64) void merged_composite_bwd_kernel(const float* __restrict__ rays, const float* __restrict__ z_c,
+                                                                 const float* __restrict__ z_f, const float* __restrict__ raw,
+                                                                 const float* __restrict__ noise0, const float* __restrict__ noise1,
+                                                                 const int* __restrict__ order, long long n, int S0, int N, const CBwd c,
+                                                                 const float* __restrict__ d_rgb, const float* __restrict__ d_acc,
+                                                                 const float* __restrict__ d_rgb0, const float* __restrict__ d_acc0,
+                                                                 float* d_raw, float* Tbuf) {
+    const long long r = blockIdx.x * 64ll + threadIdx.x;
+    if (r >= n) return;
+    const float* rb = rays + r * 11;
+    const float dn = sqrtf(rb[3] * rb[3] + rb[4] * rb[4] + rb[5] * rb[5]);
+    const int SF = S0 + N;
+    const long long row0 = r * S0, new0 = n * S0 + r * N;
+    float* Tb = Tbuf + r;
+    if (N > 0 && (d_rgb || d_acc))
+        composite_bwd_ray<true, false>(z_f + r * SF, noise1 ? noise1 + r * SF : nullptr, order + r * SF, SF, S0, row0, new0, dn, raw, d_raw, Tb, n, c,
+                                       d_rgb ? d_rgb[r * 3] : 0.0f, d_rgb ? d_rgb[r * 3 + 1] : 0.0f, d_rgb ? d_rgb[r * 3 + 2] : 0.0f,
+                                       d_acc != nullptr, d_acc ? d_acc[r] : 0.0f);
+    if (d_rgb0 || d_acc0)
+        composite_bwd_ray<false, true>(z_c + r * S0, noise0 ? noise0 + r * S0 : nullptr, nullptr, S0, S0, row0, new0, dn, raw, d_raw, Tb, n, c,
+                                       d_rgb0 ? d_rgb0[r * 3] : 0.0f, d_rgb0 ? d_rgb0[r * 3 + 1] : 0.0f, d_rgb0 ? d_rgb0[r * 3 + 2] : 0.0f,
+                                       d_acc0 != nullptr, d_acc0 ? d_acc0[r] : 0.0f);
+}
+
+// frame-code gradient of the single-net tape, first step (code_ray_sum_kernel for a pass of two row segments): per ray the sum of
+// dxc over its S coarse rows, then over its S2 new rows [P1 + ray S2, ..), in that order
+__global__ __launch_bounds__(256) void code_ray_sum2_kernel(const float* __restrict__ dxc, long long n_rays, int S, long long P1, int S2,
+                                                           float* __restrict__ ray_g) {
+    const long long i = blockIdx.x * 256ll + threadIdx.x;
+    if (i >= n_rays * FC_CH) return;
+    const long long ray = i / FC_CH;
+    const int k = (int)(i - ray * FC_CH);
+    float s = 0.0f;
+    for (int p = 0; p < S; ++p) s += dxc[(ray * S + p) * FC_CH + k];
+    for (int p = 0; p < S2; ++p) s += dxc[(P1 + ray * S2 + p) * FC_CH + k];
+    ray_g[i] = s;
+}
+
+// multires_views = 0: the tape trains in the widened 4-band layout (widen_views_kernel: the parameter's 72 view columns are row
+// 0 of the 4-band embedding, the sin / cos columns exact zeros, rebuilt from the parameter every step).  This takes the view
+// weight's gradient back: [128, 256 + 648 + fc] -> the parameter's [128, 256 + 72 + fc]; what the zero columns received is
+// dropped (they are no parameters).  Every kept element is one dot product over the points: independent of the padding.
+__global__ __launch_bounds__(256) void narrow_views_kernel(const float* __restrict__ src, int fc, float* __restrict__ dst) {
+    const int o = blockIdx.x;
+    const int dc = W + J * 3 + fc, sc = W + CH_D + fc;
+    for (int k = threadIdx.x; k < dc; k += 256) dst[(long long)o * dc + k] = src[(long long)o * sc + (k < W + J * 3 ? k : k + (CH_D - J * 3))];
+}
+
 // ---- host side -------------------------------------------------------------------------------------------------
 struct Pass {               // one network evaluation kept for the backward pass
     long long P = 0;        // points
     int S = 0;
+    long long P1 = 0;       // single-net tape: rows [0, P1) are S per ray (the coarse points), rows [P1, P) S2 per ray (the new points)
+    int S2 = 0;
     void *X = nullptr, *H[DEPTH] = {}, *F = nullptr, *G = nullptr;       // tape element type: fp32, or bf16 in the 16-bit mode
     float *raw = nullptr, *z = nullptr, *noise = nullptr, *pn = nullptr;
 };
@@ -1177,8 +1295,25 @@ struct Tape {
     // dX [P, DXW] fp32 of one pass, then the per-ray 4 x 4s [n, 384] when the caller asks for their sum
     uint8_t* pbuf = nullptr;
     size_t pbytes = 0;
+    // single_net (one net, pass[0] holds the S coarse + N new rows of every ray): the merged depths, the rank map, noise1 by merged
+    // position, the transmittances of the composite backward; multires_views = 0: the view weight widened for this step and the
+    // gradient in that layout (narrow_views_kernel takes it back)
+    bool single = false, views0 = false;
+    float *zf = nullptr, *noise1 = nullptr, *Tb = nullptr, *vwide = nullptr, *gwide = nullptr;
+    int* order = nullptr;
     int es() const { return bf16 ? 2 : 4; }                     // bytes per tape element
 };
+// rows [row0, row0 + rows) of a pass as a pass of its own with S points per ray (the two stages of the single-net forward)
+inline Pass sub_pass(const Pass& p, long long row0, long long rows, int S, int es) {
+    Pass q;
+    q.P = rows; q.S = S;
+    auto off = [&](void* b, long long width) { return static_cast<void*>(static_cast<uint8_t*>(b) + row0 * width * es); };
+    q.X = off(p.X, XW);
+    for (int l = 0; l < DEPTH; ++l) q.H[l] = off(p.H[l], W);
+    q.F = off(p.F, W); q.G = off(p.G, VW);
+    q.raw = p.raw + row0 * 4; q.z = p.z + row0; q.noise = p.noise ? p.noise + row0 : nullptr; q.pn = p.pn + row0 * 3;
+    return q;
+}
 inline const void* el_off(const void* p, long long elems, int es) { return static_cast<const uint8_t*>(p) + elems * es; }
 
 constexpr size_t PART_FLOATS = 20u << 20;        // split-K scratch: slices x M x N of the largest weight gradient (80 MB)
@@ -1521,7 +1656,10 @@ int mlp_backward(pg_handle* h, hipStream_t s, Tape& t, int net, const Pass& p, c
     if (fc && g.codes) {
         PG_HIP(h, hipMemsetAsync(g.codes, 0, (size_t)w.n_codes * FC_CH * sizeof(float), s));
         PG_TRY(linear_bwd_x(h, s, P, VW, FC_CH, dG, VW, w.w[20] + W + CH_D, vcols, t.dC, FC_CH, 0, nullptr, A_));
-        hipLaunchKernelGGL(code_ray_sum_kernel, dim3((unsigned)((t.n * FC_CH + 255) / 256)), dim3(256), 0, s, t.dC, (long long)t.n, p.S, t.ray_g);
+        if (p.S2 > 0)
+            hipLaunchKernelGGL(code_ray_sum2_kernel, dim3((unsigned)((t.n * FC_CH + 255) / 256)), dim3(256), 0, s, t.dC, (long long)t.n, p.S, p.P1, p.S2, t.ray_g);
+        else
+            hipLaunchKernelGGL(code_ray_sum_kernel, dim3((unsigned)((t.n * FC_CH + 255) / 256)), dim3(256), 0, s, t.dC, (long long)t.n, p.S, t.ray_g);
         PG_LAUNCH_CHECK(h, "code_ray_sum");
         hipLaunchKernelGGL(code_gather_kernel, dim3((unsigned)w.n_codes), dim3(64), 0, s, t.ray_g, (long long)t.n, t.cams, w.n_codes, g.codes);
         PG_LAUNCH_CHECK(h, "code_gather");
@@ -1564,6 +1702,152 @@ int mlp_backward(pg_handle* h, hipStream_t s, Tape& t, int net, const Pass& p, c
     return PG_OK;
 }
 
+// ---- the single-net training step (core/raycasters.py:99-104, 446-469; arguments checked by pg_train_forward) -----------------
+// ONE net on ONE tape pass of P = n (S + N) rows: rows [0, n S) the coarse points, rows [n S, P) the new points in z_new order.
+// The forward is the renderer's (render_rays_single, pg_api.hip) with the activations kept: coarse stage on the first rows,
+// composite_kernel<CP_ISO> (is_only pdf, rank map, z_new written straight into the pass's depth array), the new points on the
+// rows behind, composite_kernel<CP_MERGE> over both.  The backward (train_backward) then runs ONE mlp_backward over the P rows.
+int train_forward_single(pg_handle* h, void* stream, int64_t n, const float* ray_batch, const float* skts, int64_t pose_stride,
+                         const float* cyls, int64_t cyl_stride, const float* cams, int S, int N, int flags, const pg_train_draws* dr,
+                         const pg_net_params* net, const pg_outputs* out, int64_t* tape_id) {
+    PG_HIP(h, hipSetDevice(h->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    Tape& t = *tape_of(h);
+    t.valid = false;
+    const int SF = S + N, fc = h->cfg.framecode_ch > 0;
+    const bool views0 = h->cfg.multires_views == 0, hier = N > 0;
+    const long long Pc = n * S, Pn = n * N, P = Pc + Pn;
+    const bool rnoise = dr && dr->ray_noise;
+    const bool bf = h->train_precision == PG_PREC_BF16;
+    const size_t es = bf ? 2 : 4;
+    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
+    const int vcols_ = W + CH_D + (fc ? FC_CH : 0);
+    const size_t wsize[24] = {(size_t)W * CH_X, 0, (size_t)W * W, 0, (size_t)W * W, 0, (size_t)W * W, 0, (size_t)W * W, 0, (size_t)W * (CH_X + W), 0,
+                              (size_t)W * W, 0, (size_t)W * W, 0, 0, 0, (size_t)W * W, 0, (size_t)VW * vcols_, 0, 0, 0};     // (as pg_train_forward)
+    struct TB_ { int rows, cols, col0; };
+    const TB_ tblock[24] = {{0, 0, 0}, {}, {W, W, 0}, {}, {W, W, 0}, {}, {W, W, 0}, {}, {W, W, 0}, {}, {W, W, CH_X}, {}, {W, W, 0}, {}, {W, W, 0}, {}, {}, {},
+                            {W, W, 0}, {}, {VW, W, 0}, {}, {}, {}};
+    size_t need = al((size_t)n * 44) + al((size_t)n * 4) + al((size_t)n * 8) + al((size_t)n * S * 4) /*w0*/ + 4 * al((size_t)n * SF * 4) /*order, zf, noise1, Tb*/;
+    need += al((size_t)P * XW * es) + (DEPTH + 1) * al((size_t)P * W * es) + al((size_t)P * VW * es) + al((size_t)P * 16) + 2 * al((size_t)P * 4) + al((size_t)P * 12);
+    need += 2 * al((size_t)P * W * es) + al((size_t)P * VW * es) + al((size_t)P * FC_CH * 4) + al((size_t)P * 16) + (bf ? al((size_t)P * W * 4) : 0);
+    need += al(PART_FLOATS * 4) + al(RS_FLOATS * 4) + al((size_t)n * FC_CH * 4) + 2 * al((size_t)VW * vcols_ * 4);
+    if (bf) for (int i = 0; i < 24; ++i) need += al(wsize[i] * 2) + al((size_t)tblock[i].rows * tblock[i].cols * 2);
+    if (need > t.bytes) {
+        if (t.buf) { PG_HIP(h, hipDeviceSynchronize()); PG_HIP(h, hipFree(t.buf)); t.buf = nullptr; t.bytes = 0; }
+        hipError_t e = hipMalloc(reinterpret_cast<void**>(&t.buf), need);
+        if (e != hipSuccess) return pg_fail(h, PG_ENOMEM, "training tape of %zu bytes failed: %s", need, hipGetErrorString(e));
+        t.bytes = need;
+    }
+    uint8_t* q = t.buf;
+    auto take = [&](size_t b) { float* r = reinterpret_cast<float*>(q); q += al(b); return r; };
+    t.n = n; t.S = S; t.N = N; t.fc = fc; t.has_fine = false; t.bf16 = bf; t.single = true; t.views0 = views0;
+    t.rays = take((size_t)n * 44);
+    t.cams = cams ? take((size_t)n * 4) : (take((size_t)n * 4), nullptr);
+    float* nf = take((size_t)n * 8);
+    float* w0 = take((size_t)n * S * 4);
+    t.order = reinterpret_cast<int*>(take((size_t)n * SF * 4));
+    t.zf = take((size_t)n * SF * 4); t.noise1 = take((size_t)n * SF * 4); t.Tb = take((size_t)n * SF * 4);
+    t.pass[1] = Pass();
+    Pass& p = t.pass[0];
+    p = Pass();
+    p.P = P; p.S = S; p.P1 = Pc; p.S2 = N;
+    p.X = take((size_t)P * XW * es);
+    for (int l = 0; l < DEPTH; ++l) p.H[l] = take((size_t)P * W * es);
+    p.F = take((size_t)P * W * es);
+    p.G = take((size_t)P * VW * es);
+    p.raw = take((size_t)P * 16);
+    p.z = take((size_t)P * 4);
+    p.noise = take((size_t)P * 4);          // (noise0: the first n S entries)
+    p.pn = take((size_t)P * 12);
+    t.tmpA = take((size_t)P * W * es); t.tmpB = take((size_t)P * W * es);
+    t.dG = take((size_t)P * VW * es); t.dC = take((size_t)P * FC_CH * 4); t.d_raw = take((size_t)P * 16);
+    t.tmpF = bf ? take((size_t)P * W * 4) : nullptr;
+    t.vwide = take((size_t)VW * vcols_ * 4); t.gwide = take((size_t)VW * vcols_ * 4);
+    for (int i = 0; i < 24; ++i) {
+        t.wb[0][i] = (bf && wsize[i]) ? reinterpret_cast<bf16_t*>(take(wsize[i] * 2)) : nullptr;
+        t.wbT[0][i] = (bf && tblock[i].rows) ? reinterpret_cast<bf16_t*>(take((size_t)tblock[i].rows * tblock[i].cols * 2)) : nullptr;
+        t.wb[1][i] = t.wbT[1][i] = nullptr;
+    }
+    t.part = take(PART_FLOATS * 4); t.rs_part = take(RS_FLOATS * 4); t.ray_g = take((size_t)n * FC_CH * 4);
+    // the parameters the tape's GEMMs read: the caller's, with the view weight widened to the 4-band layout when the model has
+    // no view frequencies (its [128, 256 + 72 (+16)] tensor stays the parameter)
+    pg_net_params eff = *net;
+    if (views0) {
+        pg_launch_widen_views(net->w[20], h->cfg.framecode_ch, t.vwide, stream);
+        PG_LAUNCH_CHECK(h, "view weight widening");
+        eff.w[20] = t.vwide;
+    }
+    if (bf) {
+        WJobs js{};
+        int nj = 0;
+        for (int i = 0; i < 24; ++i) {
+            if (!wsize[i]) continue;
+            if (nj + (tblock[i].rows ? 2 : 1) > WJOBS_MAX) return pg_fail(h, PG_EINVAL, "weight conversion: more than %d jobs", WJOBS_MAX);
+            js.j[nj++] = WJob{eff.w[i], t.wb[0][i], 0, 1, (int)wsize[i], 0};
+            if (tblock[i].rows) js.j[nj++] = WJob{eff.w[i] + tblock[i].col0, t.wbT[0][i], (long long)(wsize[i] / tblock[i].rows), tblock[i].rows, tblock[i].cols, 1};
+        }
+        hipLaunchKernelGGL(cvt_weights_kernel, dim3(64, nj), dim3(256), 0, s, js);
+        PG_LAUNCH_CHECK(h, "weight conversion");
+    }
+    t.params[0] = eff;
+    t.skts = skts; t.pose_stride = pose_stride; t.rnoise = rnoise; t.tau[0] = h->tau[0]; t.tau[1] = h->tau[1];
+    PG_HIP(h, hipMemcpyAsync(t.rays, ray_batch, (size_t)n * 44, hipMemcpyDeviceToDevice, s));
+    if (cams) PG_HIP(h, hipMemcpyAsync(t.cams, cams, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+
+    Pass pc = sub_pass(p, 0, Pc, S, (int)es);
+    double* scs = nullptr;
+    { const int rc_ = pg_sc_scratch(h, n, h->cfg.chunk, &scs); if (rc_) return rc_; }
+    int e = pg_launch_sample_coarse(t.rays, cyls, cyl_stride, n, h->cfg.chunk, S, (flags & PG_FLAG_LINDISP) ? 1 : 0, nf, pc.z, dr ? dr->t_rand : nullptr, scs, stream);
+    if (e) return pg_fail(h, PG_EHIP, "coarse sampling launch failed: %s", hipGetErrorString((hipError_t)e));
+    if (dr && dr->noise0) PG_HIP(h, hipMemcpyAsync(p.noise, dr->noise0, (size_t)Pc * 4, hipMemcpyDeviceToDevice, s));
+    else p.noise = nullptr;
+    if (rnoise) {       // position noise of the coarse points: rows [:S] of every ray's draws
+        e = pg_launch_gather_noise(dr->ray_noise, n, SF, S, nullptr, pc.pn, stream);
+        if (e) return pg_fail(h, PG_EHIP, "noise gather launch failed: %s", hipGetErrorString((hipError_t)e));
+    }
+    auto embed = [&](const Pass& sp) {
+        const dim3 grid((unsigned)((sp.P * J + 255) / 256));
+        if (bf) hipLaunchKernelGGL(embed_rows_kernel<bf16_t>, grid, dim3(256), 0, s, t.rays, sp.z, rnoise ? sp.pn : nullptr, skts, (long long)pose_stride,
+                                   t.cams, net->codes, net->n_codes, fc, h->d_cut, h->tau[0], h->tau[1], sp.P, sp.S, static_cast<bf16_t*>(sp.X));
+        else hipLaunchKernelGGL(embed_rows_kernel<float>, grid, dim3(256), 0, s, t.rays, sp.z, rnoise ? sp.pn : nullptr, skts, (long long)pose_stride,
+                                t.cams, net->codes, net->n_codes, fc, h->d_cut, h->tau[0], h->tau[1], sp.P, sp.S, static_cast<float*>(sp.X));
+        return hipGetLastError();
+    };
+    if (embed(pc) != hipSuccess) return pg_fail(h, PG_EHIP, "embedding kernel launch failed");
+    PG_TRY(mlp_forward(h, s, t, 0, pc, eff, fc));
+    const float ds = h->cfg.density_scale, eps = h->cfg.rgb_eps, shift = h->cfg.softplus_shift;
+    const int act = h->cfg.density_act;
+    if (!hier) {
+        e = pg_launch_composite(t.rays, pc.z, pc.raw, n, S, ds, eps, act, shift, out->rgb_map, out->disp_map, out->acc_map, out->alpha,
+                                out->weights0 ? out->weights0 : w0, 0, nullptr, p.noise, nullptr, nullptr, stream);
+        if (e) return pg_fail(h, PG_EHIP, "composite launch failed: %s", hipGetErrorString((hipError_t)e));
+    } else {
+        Pass pn = sub_pass(p, Pc, Pn, N, (int)es);
+        e = pg_launch_composite_iso(t.rays, pc.z, pc.raw, n, S, ds, eps, act, shift, out->rgb0, out->disp0, out->acc0, out->alpha0,
+                                    out->weights0 ? out->weights0 : w0, N, t.zf, p.noise, dr ? dr->u_rand : nullptr, t.order, pn.z, N, stream);
+        if (e) return pg_fail(h, PG_EHIP, "composite launch failed: %s", hipGetErrorString((hipError_t)e));
+        if (rnoise) {   // the new points' noise: rows [S:] in z_samples order (sample_pts_is, raycasters.py:665-674)
+            e = pg_launch_gather_noise(dr->ray_noise + (size_t)S * 3, n, SF, N, nullptr, pn.pn, stream);
+            if (e) return pg_fail(h, PG_EHIP, "noise gather launch failed: %s", hipGetErrorString((hipError_t)e));
+        }
+        if (embed(pn) != hipSuccess) return pg_fail(h, PG_EHIP, "embedding kernel launch failed");
+        PG_TRY(mlp_forward(h, s, t, 0, pn, eff, fc));
+        if (dr && dr->noise1) PG_HIP(h, hipMemcpyAsync(t.noise1, dr->noise1, (size_t)n * SF * 4, hipMemcpyDeviceToDevice, s));
+        else t.noise1 = nullptr;
+        e = pg_launch_composite_merged(t.rays, t.zf, pc.raw, pn.raw, N, t.order, n, S, N, ds, eps, act, shift, out->rgb_map, out->disp_map,
+                                       out->acc_map, out->alpha, t.noise1, out->raw_fine, stream);
+        if (e) return pg_fail(h, PG_EHIP, "composite launch failed: %s", hipGetErrorString((hipError_t)e));
+    }
+    if (out->near_far) PG_HIP(h, hipMemcpyAsync(out->near_far, nf, (size_t)n * 8, hipMemcpyDeviceToDevice, s));
+    if (out->z_coarse) PG_HIP(h, hipMemcpyAsync(out->z_coarse, pc.z, (size_t)Pc * 4, hipMemcpyDeviceToDevice, s));
+    if (out->raw_coarse) PG_HIP(h, hipMemcpyAsync(out->raw_coarse, pc.raw, (size_t)Pc * 16, hipMemcpyDeviceToDevice, s));
+    if (hier && out->z_fine) PG_HIP(h, hipMemcpyAsync(out->z_fine, t.zf, (size_t)n * SF * 4, hipMemcpyDeviceToDevice, s));
+    t.valid = true;
+    t.generation += 1;
+    if (tape_id) *tape_id = t.generation;
+    return PG_OK;
+}
+
 }  // namespace pgt
 
 extern "C" {
@@ -1585,21 +1869,25 @@ int pg_train_forward(pg_handle* h, void* stream, int64_t n, const float* ray_bat
     if (!h) return pg_fail(nullptr, PG_EINVAL, "null handle");
     if (n <= 0 || !ray_batch || !skts || !cyls || !coarse || !out) return pg_fail(h, PG_EINVAL, "pg_train_forward: null / non-positive argument");
     if (!h->emb_set[0] || !h->emb_set[1]) return pg_fail(h, PG_ESTATE, "embedder state not set (pg_set_embedder)");
-    if (h->cfg.single_net || h->cfg.multires_views != pgl::LD)
-        return pg_fail(h, PG_EINVAL, "pg_train_forward: the training step is built for two nets with multires_views = 4 (single_net / "
-                                     "multires_views = 0 models render only)");
+    const bool single = h->cfg.single_net != 0;
+    if (!single && h->cfg.multires_views != pgl::LD)
+        return pg_fail(h, PG_EINVAL, "pg_train_forward: two nets with multires_views = 0 are not trained on this path (no shipped config; the "
+                                     "0-band view embedding trains with single_net, and such two-net models render only)");
     if (pose_stride != 0 && pose_stride != 384) return pg_fail(h, PG_EINVAL, "pose_stride must be 0 (shared) or 384 (per ray)");
     if (cyl_stride != 0 && cyl_stride != 5) return pg_fail(h, PG_EINVAL, "cyl_stride must be 0 (shared) or 5 (per ray)");
     const int S = n_samples, N = n_importance, SF = S + N;
     if (S < 2 || SF > pg_composite_max_samples() || N < 0 || N == 1 || N > pg_composite_max_importance())
         return pg_fail(h, PG_EINVAL, "pg_train_forward: N_samples %d / N_importance %d outside the supported range", S, N);
-    if (N > 0 && !fine) return pg_fail(h, PG_EINVAL, "pg_train_forward: importance sampling needs the fine network's parameters");
+    if (single && N > 0 && S < 3) return pg_fail(h, PG_EINVAL, "pg_train_forward: importance sampling needs N_samples >= 3");
+    if (N > 0 && !fine && !single) return pg_fail(h, PG_EINVAL, "pg_train_forward: importance sampling needs the fine network's parameters");
     const int fc = h->cfg.framecode_ch > 0;
-    for (int k = 0; k < (N > 0 ? 2 : 1); ++k) {
+    for (int k = 0; k < (N > 0 && !single ? 2 : 1); ++k) {
         const pg_net_params* p = k ? fine : coarse;
         for (int i = 0; i < 24; ++i) if (!p->w[i]) return pg_fail(h, PG_EINVAL, "pg_train_forward: parameter tensor %d of net %d is null", i, k);
         if (fc && (!p->codes || p->n_codes <= 0)) return pg_fail(h, PG_EINVAL, "pg_train_forward: frame codes of net %d missing", k);
     }
+    if (single)         // one net, S + N rows per ray on one tape pass (`fine` is not read: network_fine is network)
+        return train_forward_single(h, stream, n, ray_batch, skts, pose_stride, cyls, cyl_stride, cams, S, N, flags, dr, coarse, out, tape_id);
     PG_HIP(h, hipSetDevice(h->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     Tape& t = *tape_of(h);
@@ -1770,6 +2058,42 @@ static int train_backward(pg_handle* h, void* stream, int64_t tape_id, const flo
         }
         dX = reinterpret_cast<float*>(t.pbuf);
         per_ray = d_pose_stride == 0 ? reinterpret_cast<float*>(t.pbuf + dx_bytes) : d_skts;
+    }
+    if (t.single) {
+        // d_raw of the P rows: zeroed, then per ray the fine (merged) composite's share of every row it reads and the coarse
+        // composite's share added to the coarse rows -- in that order, by one thread; then ONE backward of the one net
+        const Pass& p = t.pass[0];
+        if (t.views0 && !coarse->w[20]) return pg_fail(h, PG_EINVAL, "pg_train_backward: gradient tensor 20 is null");
+        PG_HIP(h, hipMemsetAsync(t.d_raw, 0, (size_t)p.P * 16, s));
+        const CBwd cb{h->cfg.density_scale, h->cfg.rgb_eps, h->cfg.softplus_shift, h->cfg.density_act};
+        const bool hier = t.N > 0;
+        hipLaunchKernelGGL(merged_composite_bwd_kernel, dim3((unsigned)((t.n + 63) / 64)), dim3(64), 0, s, t.rays, p.z, t.zf, p.raw, p.noise,
+                           t.noise1, t.order, (long long)t.n, t.S, t.N, cb, hier ? d_rgb_map : nullptr, hier ? d_acc_map : nullptr,
+                           hier ? d_rgb0 : d_rgb_map, hier ? d_acc0 : d_acc_map, t.d_raw, t.Tb);
+        PG_LAUNCH_CHECK(h, "merged composite backward");
+        pg_net_grads ge = *coarse;
+        if (t.views0) ge.w[20] = t.gwide;
+        PG_TRY(mlp_backward(h, s, t, 0, p, t.params[0], ge, dX));
+        if (t.views0) {
+            hipLaunchKernelGGL(narrow_views_kernel, dim3(VW), dim3(256), 0, s, t.gwide, t.fc ? FC_CH : 0, coarse->w[20]);
+            PG_LAUNCH_CHECK(h, "view gradient narrowing");
+        }
+        if (pose) {     // a ray's S coarse points write its 4 x 4s, its N new points (their own depths and noise rows) add theirs
+            const dim3 grid((unsigned)((t.n * J + 255) / 256));
+            hipLaunchKernelGGL(embed_bwd_kernel, grid, dim3(256), 0, s, t.rays, p.z, t.rnoise ? p.pn : nullptr, t.skts, t.pose_stride, h->d_cut,
+                               t.tau[0], t.tau[1], (long long)t.n, t.S, dX, per_ray, 0);
+            PG_LAUNCH_CHECK(h, "embedding backward");
+            if (hier) {
+                hipLaunchKernelGGL(embed_bwd_kernel, grid, dim3(256), 0, s, t.rays, p.z + p.P1, t.rnoise ? p.pn + p.P1 * 3 : nullptr, t.skts,
+                                   t.pose_stride, h->d_cut, t.tau[0], t.tau[1], (long long)t.n, t.N, dX + p.P1 * DXW, per_ray, 1);
+                PG_LAUNCH_CHECK(h, "embedding backward");
+            }
+            if (d_pose_stride == 0) {
+                hipLaunchKernelGGL(reduce_parts_kernel, dim3((unsigned)((J * 16 + 255) / 256)), dim3(256), 0, s, per_ray, (int)t.n, 1, J * 16, d_skts, (long long)(J * 16));
+                PG_LAUNCH_CHECK(h, "pose gradient reduction");
+            }
+        }
+        return PG_OK;
     }
     bool first = true;
     auto run = [&](int k, const float* d_rgb, const float* d_acc, const pg_net_grads& g) -> int {

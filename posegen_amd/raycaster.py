@@ -150,6 +150,8 @@ class HipRenderer:
         for key, provider in list(self._state_lazy.items()):
             if provider is not None:
                 self._state[key] = {k: v.detach().cpu().clone() for k, v in provider().items()}
+                if self.cfg.single_net and key == "network_fn_state_dict":      # (one net under both keys, as load_network keeps it)
+                    self._state["network_fine_state_dict"] = self._state[key]
             del self._state_lazy[key]
 
     def set_embedder(self, which: int, tau: float, cutoff_dist=None):

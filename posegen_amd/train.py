@@ -20,7 +20,8 @@ from .raycaster import NET_TENSOR_ORDER, HipRayCaster, _dev_f32, _ptr, make_trai
 
 
 class _RenderRaysFn(torch.autograd.Function):
-    """outputs (rgb_map, acc_map, rgb0, acc0, disp_map, disp0) of one training-mode render_rays call; differentiable
+    """outputs (rgb_map, acc_map, rgb0, acc0, disp_map, disp0, alpha, alpha0) of one training-mode render_rays call (the alphas
+    only for a single-net caster, empty otherwise); differentiable
     with respect to the 24 (+ frame codes) tensors of each net and, with opt_pose, to `skts` (the caller's tensor as passed:
     [n,24,4,4] gets one gradient per ray -- an expanded single pose included, autograd's ExpandBackward sums them --,
     [1,24,4,4] / [24,4,4] the sum over the rays)."""
@@ -33,7 +34,8 @@ class _RenderRaysFn(torch.autograd.Function):
         n = rb.shape[0]
         ctx.skts_shape, ctx.skts_dtype, ctx.skts_device = tuple(skts.shape), skts.dtype, skts.device
         nper = 24 + (1 if caster.cfg.framecode_ch > 0 else 0)
-        nets = [params[:nper], params[nper:2 * nper]] if N > 0 else [params[:nper]]
+        single = bool(caster.cfg.single_net)             # one parameter set: network_fine is network
+        nets = [params[:nper], params[nper:2 * nper]] if N > 0 and not single else [params[:nper]]
         keep = [rb, sk, cy, cam]
         structs = []
         for tens in nets:
@@ -53,6 +55,10 @@ class _RenderRaysFn(torch.autograd.Function):
         out = {"rgb_map": new(n, 3), "disp_map": new(n), "acc_map": new(n)}
         if N > 0:
             out.update({"rgb0": new(n, 3), "disp0": new(n), "acc0": new(n)})
+        if single:                                       # what the reference's single-net call returns besides the maps
+            out["alpha"] = new(n, S + N)
+            if N > 0:
+                out["alpha0"] = new(n, S)
         po = _ffi.PgOutputs()
         for k, v in out.items():
             setattr(po, k, v.data_ptr())
@@ -66,16 +72,16 @@ class _RenderRaysFn(torch.autograd.Function):
         tape = C.c_int64(0)
         r._check(lib.pg_train_forward(r.handle, r._stream(), n, _ptr(rb), _ptr(sk), ps, _ptr(cy), cs, _ptr(cam), S, N, flags,
                                       None if pd is None else C.byref(pd), C.byref(structs[0]),
-                                      C.byref(structs[1]) if N > 0 else None, C.byref(po), C.byref(tape)))
+                                      C.byref(structs[1]) if len(structs) > 1 else None, C.byref(po), C.byref(tape)))
         ctx.caster, ctx.n_nets, ctx.nper, ctx.keep, ctx.tape_id = caster, len(nets), nper, keep, tape.value
         ctx.shapes = [tuple(p.shape) for p in params]
         zero = lambda k: out[k] if k in out else torch.zeros(0, device=dev)
-        outs = (out["rgb_map"], out["acc_map"], zero("rgb0"), zero("acc0"), out["disp_map"], zero("disp0"))
-        ctx.mark_non_differentiable(outs[4], outs[5])
+        outs = (out["rgb_map"], out["acc_map"], zero("rgb0"), zero("acc0"), out["disp_map"], zero("disp0"), zero("alpha"), zero("alpha0"))
+        ctx.mark_non_differentiable(*outs[4:])
         return outs
 
     @staticmethod
-    def backward(ctx, g_rgb, g_acc, g_rgb0, g_acc0, _g_disp, _g_disp0):
+    def backward(ctx, g_rgb, g_acc, g_rgb0, g_acc0, _g_disp, _g_disp0, _g_alpha=None, _g_alpha0=None):
         caster = ctx.caster
         r = caster.renderer
         dev = r.device
@@ -192,10 +198,7 @@ class TrainableRayCaster(torch.nn.Module):
         super().__init__()
         if train_precision not in ("fp32", "bf16"):
             raise ValueError(f"train_precision must be 'fp32' or 'bf16', not {train_precision!r}")
-        if caster.cfg.single_net or caster.cfg.multires_views != 4:
-            # refuse rather than train the wrong thing: the training step has two nets and the 4-band view embedding
-            raise NotImplementedError("TrainableRayCaster: training of single_net / multires_views != 4 models is not on the HIP "
-                                      "path (they render through HipRayCaster)")
+        self._check_model(caster.cfg)
         self.caster = caster
         self.train_precision = train_precision
         self.opt_pose = bool(opt_pose)
@@ -208,10 +211,24 @@ class TrainableRayCaster(torch.nn.Module):
         fc = self.cfg.framecode_ch > 0
         self._names = list(NET_TENSOR_ORDER) + (["framecodes.codes.weight"] if fc else [])
         self.network = _NetParams(st["network_fn_state_dict"], fc, dev)
-        self.network_fine = _NetParams(st["network_fine_state_dict"], fc, dev) if "network_fine_state_dict" in st else None
+        if self.cfg.single_net:                         # ONE parameter set under both names (core/raycasters.py:99-104)
+            self.network_fine = self.network
+        else:
+            self.network_fine = _NetParams(st["network_fine_state_dict"], fc, dev) if "network_fine_state_dict" in st else None
         self.embed_fn = _EmbedState(caster.renderer, 0, st["embed_state_dict"])
         self.embedbones_fn = None                       # multires_bones = 0: a parameter-free identity Embedder
         self.embeddirs_fn = _EmbedState(caster.renderer, 1, st["embeddirs_state_dict"])
+
+    @staticmethod
+    def _check_model(cfg):
+        """This class is the two-net step with the 4-band view embedding; it refuses everything else rather than train the
+        wrong thing.  Single-net models train through SingleNetTrainableRayCaster (`make_trainable` picks the class)."""
+        if cfg.single_net:
+            raise NotImplementedError("TrainableRayCaster is the two-net training step: a single_net model trains through "
+                                      "SingleNetTrainableRayCaster (posegen_amd.make_trainable picks the class)")
+        if cfg.multires_views != 4:
+            raise NotImplementedError("TrainableRayCaster: two nets with multires_views != 4 are not trained on the HIP path (no "
+                                      "shipped config; such models render through HipRayCaster)")
 
     @property
     def module(self):
@@ -258,7 +275,7 @@ class TrainableRayCaster(torch.nn.Module):
 
     def _flat(self):
         out = self.network.tensors(self._names)
-        if self.network_fine is not None:
+        if self.network_fine is not None and self.network_fine is not self.network:
             out += self.network_fine.tensors(self._names)
         return out
 
@@ -282,7 +299,9 @@ class TrainableRayCaster(torch.nn.Module):
         r = self.caster.renderer
         if on_device is None:
             on_device = len(getattr(r, "devices", [0])) <= 1
-        nets = [(0, self.network)] + ([(1, self.network_fine)] if self.network_fine is not None else [])
+        nets = [(0, self.network)]
+        if self.network_fine is not None and self.network_fine is not self.network:      # (a single-net handle has net 0 only)
+            nets.append((1, self.network_fine))
         for which, net in nets:
             if on_device:
                 p = dict(net.named_parameters())
@@ -360,11 +379,50 @@ class TrainableRayCaster(torch.nn.Module):
         r.set_chunk(max(n, 1))                          # one call = one nanmean group (ray_utils.py:292-344)
         try:
             flags = _ffi.PG_FLAG_LINDISP if lindisp else 0
-            rgb, acc, rgb0, acc0, disp, disp0 = _RenderRaysFn.apply(self, (rb, sk, ps, cy, cs, cam, S, N, flags, draws or None), skts,
+            rgb, acc, rgb0, acc0, disp, disp0, alpha, alpha0 = _RenderRaysFn.apply(self, (rb, sk, ps, cy, cs, cam, S, N, flags, draws or None), skts,
                                                                     *self._flat())
         finally:
             r.set_chunk(keep)
         out = {"rgb_map": rgb, "disp_map": disp, "acc_map": acc}
         if N > 0:
             out.update({"rgb0": rgb0, "disp0": disp0, "acc0": acc0})
+        if cfg.single_net:
+            out["alpha"] = alpha
+            if N > 0:
+                out["alpha0"] = alpha0
         return out
+
+
+class SingleNetTrainableRayCaster(TrainableRayCaster):
+    """The training step of a single-net caster (`single_net = True`, configs/surreal/surreal_single.txt; the reference's
+    core/raycasters.py:99-104, 446-469): ONE parameter set -- `network_fine is network`, so `parameters()` yields each tensor
+    once and `get_grad_vars` builds the optimiser it builds for the reference's own single-net caster -- evaluated at a ray's S
+    coarse points and at its N importance points only (S + N rows per ray on the tape instead of 2 S + N).  The loss reads the
+    coarse maps and the fine maps, which composite the coarse and the new raw merged by depth; the one set of gradients sums
+    the three paths (pg_train.hip: merged_composite_bwd_kernel, one backward of the net over all rows).
+
+    `multires_views = 0`: `views_linears.0.weight` and its gradient have the reference's [128, 256 + 72 (+16)] shape.  The
+    library widens a copy to the 4-band layout every step (the sin / cos columns exact zeros) and narrows the gradient back:
+    those columns are never parameters.  `state_dict()` holds the one net under both `network_fn_state_dict` and
+    `network_fine_state_dict`, as the reference saves it.  A training-mode call also returns `alpha` / `alpha0` (no gradient).
+    Everything else -- `train_precision`, `opt_pose`, the refused keywords, the re-sync before an eval-mode render, one
+    outstanding tape -- is TrainableRayCaster's."""
+
+    @staticmethod
+    def _check_model(cfg):
+        if not cfg.single_net:
+            raise ValueError("SingleNetTrainableRayCaster needs a single_net caster (two-net models: TrainableRayCaster)")
+
+    def load_state_dict(self, ckpt, strict=True):
+        from .raycaster import _same_state
+        fine = ckpt.get("network_fine_state_dict")
+        if fine is not None and "network_fn_state_dict" in ckpt and not _same_state(ckpt["network_fn_state_dict"], fine):
+            raise ValueError("single_net checkpoint: network_fine_state_dict differs from network_fn_state_dict")
+        super().load_state_dict(ckpt, strict=strict)
+
+
+def make_trainable(caster: HipRayCaster, **kw) -> TrainableRayCaster:
+    """The trainable wrapper of `caster`: SingleNetTrainableRayCaster for a single-net caster, TrainableRayCaster otherwise
+    (keywords: `train_precision`, `opt_pose`)."""
+    cls = SingleNetTrainableRayCaster if caster.cfg.single_net else TrainableRayCaster
+    return cls(caster, **kw)

@@ -396,11 +396,18 @@ def grad_sample_index(numel):
 N_COND = 8
 
 
+def _grad_nets(caster):
+    """(tag, net) of every parameter set of the caster, each once: a single-net caster's `network_fine` IS its `network`
+    (core/raycasters.py:99-104), and its gradients are stored under "coarse" alone."""
+    nets = [("coarse", caster.network)]
+    if caster.network_fine is not None and caster.network_fine is not caster.network:
+        nets.append(("fine", caster.network_fine))
+    return nets
+
+
 def _sampled_grads(caster):
     out = {}
-    for tag, net in (("coarse", caster.network), ("fine", caster.network_fine)):
-        if net is None:
-            continue
+    for tag, net in _grad_nets(caster):
         for pname, p_ in net.named_parameters():
             g = p_.grad.detach().numpy().reshape(-1)
             out[(tag, pname)] = g[grad_sample_index(g.size)].copy()
@@ -431,7 +438,7 @@ def _grad_sensitivity(caster, step):
 
 
 def gen_train_grads(out, name, cfg, *, n_rays, H, seed_model=0, seed_pose=1, perturb=1., raw_noise_std=1.,
-                    use_cams=False, max_seed_tries=16, max_sens=1e-5):
+                    use_cams=False, max_seed_tries=16, max_sens=1e-5, model_keys=False):
     """One training step of the reference, up to the gradients: `RayCaster.__call__` in training mode with
     pytest=True draws (as rays_train), the loss of Trainer.compute_loss for the shipped surreal config
     (core/trainer.py:321-383: img2mse of rgb + (1 - acc) * bg, use_background=True, base_bg=1, for the fine and the
@@ -509,6 +516,8 @@ def gen_train_grads(out, name, cfg, *, n_rays, H, seed_model=0, seed_pose=1, per
         d["softplus_shift"] = float(cfg.softplus_shift)
     if cams is not None:
         d["cams"] = cams.numpy()
+    if model_keys:
+        _model_keys(d, cfg)
     f32 = lambda a: torch.Tensor(a).numpy()
     if perturb > 0:
         np.random.seed(0); d["t_rand"] = f32(np.random.rand(n, S))
@@ -522,9 +531,7 @@ def gen_train_grads(out, name, cfg, *, n_rays, H, seed_model=0, seed_pose=1, per
         if k in full:
             d[k] = full[k].detach().numpy()
     worst = 0.0
-    for tag, net in (("coarse", caster.network), ("fine", caster.network_fine)):
-        if net is None:
-            continue
+    for tag, net in _grad_nets(caster):
         for pname, p_ in net.named_parameters():
             g = p_.grad
             assert g is not None, (tag, pname)
@@ -537,7 +544,7 @@ def gen_train_grads(out, name, cfg, *, n_rays, H, seed_model=0, seed_pose=1, per
 
 
 def gen_train_grads_pose(out, name, cfg, *, n_rays, H, n_poses, seed_model=0, seed_pose=1, perturb=1., raw_noise_std=1.,
-                         use_cams=False, max_seed_tries=16, max_sens=1e-5):
+                         use_cams=False, max_seed_tries=16, max_sens=1e-5, model_keys=False):
     """gen_train_grads with pose refinement (opt_pose, core/trainer.py:286-313): the reference's training step with `skts`
     requiring a gradient, one pose per ray as PoseOptLayer hands them over by kp_idx -- `n_poses` frames, each seen by its own
     camera frame's rays, the batch split evenly between them.  Stored besides what gen_train_grads stores: the per-frame
@@ -628,6 +635,8 @@ def gen_train_grads_pose(out, name, cfg, *, n_rays, H, n_poses, seed_model=0, se
          "seed_pose": seed_pose, "grad_sensitivity": sens, "dskts": skt_b.grad.detach().numpy().copy()}
     if cams is not None:
         d["cams"] = cams.numpy()
+    if model_keys:
+        _model_keys(d, cfg)
     f32 = lambda a: torch.Tensor(a).numpy()
     if perturb > 0:
         np.random.seed(0); d["t_rand"] = f32(np.random.rand(n, S))
@@ -640,9 +649,7 @@ def gen_train_grads_pose(out, name, cfg, *, n_rays, H, n_poses, seed_model=0, se
     for k in ("rgb_map", "acc_map", "rgb0", "acc0"):
         if k in full:
             d[k] = full[k].detach().numpy()
-    for tag, net in (("coarse", caster.network), ("fine", caster.network_fine)):
-        if net is None:
-            continue
+    for tag, net in _grad_nets(caster):
         for pname, p_ in net.named_parameters():
             g = p_.grad.detach().numpy().reshape(-1)
             d[f"gnorm_{tag}_{pname}"] = np.float64(np.linalg.norm(g.astype(np.float64)))
@@ -751,6 +758,17 @@ def main():
     if want("train_grads_pose_h36m"):  # frame codes, 64 + 16 samples, one pose for every ray
         gen_train_grads_pose(a.out, "train_grads_pose_h36m", h36m_config(n_samples=64, n_importance=16), n_rays=24, H=128,
                              n_poses=1, seed_model=5, seed_pose=17, use_cams=True)
+    # the single-net training step (one parameter set, its gradients stored once under "coarse"), after every older case
+    if want("train_grads_single"):       # the shipped single-net config: multires_views = 0, 96 + 48
+        gen_train_grads(a.out, "train_grads_single", surreal_config(single_net=True, multires_views=0, n_samples=96, n_importance=48),
+                        n_rays=48, H=128, seed_pose=18, model_keys=True)
+    if want("train_grads_single_v4"):    # the single-net step alone: 4-band views, 64 + 16
+        gen_train_grads(a.out, "train_grads_single_v4", surreal_config(single_net=True), n_rays=48, H=128, seed_pose=19,
+                        model_keys=True)
+    if want("train_grads_single_pose"):  # pose refinement on the shipped single-net config, two frames
+        gen_train_grads_pose(a.out, "train_grads_single_pose",
+                             surreal_config(single_net=True, multires_views=0, n_samples=96, n_importance=48),
+                             n_rays=48, H=128, n_poses=2, seed_pose=20, model_keys=True)
 
 
 if __name__ == "__main__":
