@@ -1274,7 +1274,7 @@ struct Tape {
     int64_t generation = 0;     // id of the forward pass the tape holds (pg_train_forward returns it, pg_train_backward checks it)
     long long n = 0;
     int S = 0, N = 0, fc = 0;
-    float *rays = nullptr, *cams = nullptr;
+    float *rays = nullptr, *cams = nullptr, *near_far = nullptr, *w0 = nullptr;
     void *tmpA = nullptr, *tmpB = nullptr, *dG = nullptr;       // activation gradients (tape element type)
     bf16_t* wb[2][24] = {};                                     // 16-bit mode: bf16 copies of the weight matrices (even tensor indices)
     bf16_t* wbT[2][24] = {};                                    // ... and transposed copies [in][out] of the blocks the dX GEMMs multiply by
@@ -1324,157 +1324,191 @@ inline Tape* tape_of(pg_handle* h) {
     return static_cast<Tape*>(h->train);
 }
 
-#define PG_LAUNCH_CHECK(h, what)                                                                            \
-    do {                                                                                                    \
-        hipError_t e_ = hipGetLastError();                                                                  \
-        if (e_ != hipSuccess) return pg_fail(h, PG_EHIP, "%s launch failed: %s", what, hipGetErrorString(e_)); \
-    } while (0)
+// a step that fails: PG_TRY hands the callee's code up (the callee has recorded its message), PG_TRY_LAUNCH records a launcher's
+// hipError_t; PG_LAUNCH_CHECK is the latter behind a hipLaunchKernelGGL
+#define PG_TRY(call) do { const int rc_ = (call); if (rc_) return rc_; } while (0)
+#define PG_TRY_LAUNCH(h, what, call)                                                                                            \
+    do { const int e_ = (int)(call); if (e_) return pg_fail(h, PG_EHIP, "%s launch failed: %s", what, hipGetErrorString((hipError_t)e_)); } while (0)
+#define PG_LAUNCH_CHECK(h, what) PG_TRY_LAUNCH(h, what, hipGetLastError())
 
-// C[M,N] = A B (+ bias, relu, accumulate); ksplit > 1: K in slices, summed into C in slice order (C is overwritten)
-// dt (DT_*): which of A, B, C and the mask are bf16 arrays (16-bit mode: the tape's activations); GEMM_ACC adds cin (fp32,
-// leading dimension ldcin; null: C itself, fp32)
 // C += row (x) col in fp32, row[m ld] a column of another array (gemm(): persistent layer kernel only)
 struct Rank1 { const float* row; long long ld; const float* col; };
+// C[M,N] = A B (+ bias, relu, accumulate) with element strides (sam, sak: A's row and k strides; sbk, sbn: B's); a_kcont / b_kcont:
+// which of an operand's strides is 1.  ksplit > 1: K in slices, summed into C in slice order (C is overwritten)
+// dt (DT_*): which of A, B, C and the mask are bf16 arrays (16-bit mode: the tape's activations); GEMM_ACC adds cin (fp32,
+// leading dimension ldcin; null: C itself, fp32)
+struct Gemm {
+    bool a_kcont = true, b_kcont = true;
+    int M = 0, N = 0, K = 0;
+    const void *A = nullptr, *B = nullptr;
+    long long sam = 0, sak = 1, sbk = 1, sbn = 0;
+    void* C = nullptr;
+    long long ldc = 0;
+    const float *bias = nullptr, *cin = nullptr;
+    long long ldcin = 0;
+    int flags = 0, ksplit = 1, dt = 0;
+    const void* mask = nullptr;     // C is zeroed where mask (leading dimension ldm) is <= 0
+    long long ldm = 0;
+    float* rowsum = nullptr;        // rowsum[M] = the sums of A over k (the bias gradient beside a weight gradient)
+    const KSeg2* seg2 = nullptr;    // a second k segment [A2 | B2] behind the first
+    const Rank1* r1 = nullptr;
+};
 bool lgemm_enabled() {
     static const bool on = [] { const char* e = std::getenv("POSEGEN_LGEMM"); return !(e && e[0] == '0'); }();
     return on;
 }
+inline bool at16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
 // 16-byte loads: the contiguous index in runs of 4 floats / 8 bf16, every other stride and the base aligned likewise
-inline bool aligned16(const void* p, long long stride, bool bf) { return reinterpret_cast<uintptr_t>(p) % 16 == 0 && stride % (bf ? 8 : 4) == 0; }
+inline bool aligned16(const void* p, long long stride, bool bf) { return at16(p) && stride % (bf ? 8 : 4) == 0; }
 // the shapes and layouts the 128-tile kernels (and the persistent kernel) load with 16-byte loads: M, N >= 64, aligned operands
-inline bool tile128_ok(bool a_kcont, bool b_kcont, int M, int N, int K, const void* A, long long sam, long long sak,
-                       const void* B, long long sbk, long long sbn, int dt) {
-    const bool abf = dt & DT_A, bbf = dt & DT_B;
+inline bool tile128_ok(const Gemm& g) {
+    const bool abf = g.dt & DT_A, bbf = g.dt & DT_B;
     const int qa = abf ? 8 : 4, qb = bbf ? 8 : 4;
-    return M >= 64 && N >= 64 && aligned16(A, a_kcont ? sam : sak, abf) && aligned16(B, b_kcont ? sbn : sbk, bbf) &&
-           (a_kcont ? K % qa == 0 : M % qa == 0) && (b_kcont ? K % qb == 0 : N % qb == 0);
+    return g.M >= 64 && g.N >= 64 && aligned16(g.A, g.a_kcont ? g.sam : g.sak, abf) && aligned16(g.B, g.b_kcont ? g.sbn : g.sbk, bbf) &&
+           (g.a_kcont ? g.K % qa == 0 : g.M % qa == 0) && (g.b_kcont ? g.K % qb == 0 : g.N % qb == 0);
 }
+// the second k segment's operands: bf16 rows in whole 16-byte runs
+inline bool seg2_aligned(const KSeg2& sg) { return sg.sam % 8 == 0 && sg.sbn % 8 == 0 && at16(sg.A) && at16(sg.B); }
 // a second k segment in the 128-tile kernel: bf16 k-contiguous operands, the first segment a multiple of the k-step
-inline bool seg2_tile_ok(const Tape& t, bool a_kcont, bool b_kcont, int K, int ksplit, int dt, const KSeg2* seg2) {
-    return t.bf16 && (dt & DT_A) && (dt & DT_B) && a_kcont && b_kcont && ksplit == 1 && K % BK == 0 && seg2->K % 8 == 0 && seg2->sam % 8 == 0 &&
-           seg2->sbn % 8 == 0 && reinterpret_cast<uintptr_t>(seg2->A) % 16 == 0 && reinterpret_cast<uintptr_t>(seg2->B) % 16 == 0;
+inline bool seg2_tile_ok(const Tape& t, const Gemm& g) {
+    return t.bf16 && (g.dt & DT_A) && (g.dt & DT_B) && g.a_kcont && g.b_kcont && g.ksplit == 1 && g.K % BK == 0 && g.seg2->K % 8 == 0 &&
+           seg2_aligned(*g.seg2);
 }
-// Does gemm() with these arguments run on the persistent layer kernel (a 256-wide layer of the 16-bit mode: K = 256, K = 432,
+// Does gemm() run this product on the persistent layer kernel (a 256-wide layer of the 16-bit mode: K = 256, K = 432,
 // or the skip layer's two segments [h (256) | x (432)])?  Only that kernel takes a second k segment or a rank-1 term, so the
 // callers that would pass one ask this first and otherwise split the work into plain GEMMs.
-bool lgemm_takes(const Tape& t, bool a_kcont, bool b_kcont, int M, int N, int K, const void* A, long long sam, long long sak,
-                 const void* B, long long sbk, long long sbn, const void* C, long long ldc, int flags, int ksplit, const void* mask,
-                 long long ldm, const float* rowsum, int dt, const float* cin, long long ldcin, const KSeg2* seg2) {
-    const bool abf = dt & DT_A, bbf = dt & DT_B;
-    const bool seg_skip = seg2 && K == 256 && seg2->K == 432 && seg2->sam % 8 == 0 && seg2->sbn % 8 == 0 &&
-                          reinterpret_cast<uintptr_t>(seg2->A) % 16 == 0 && reinterpret_cast<uintptr_t>(seg2->B) % 16 == 0;
-    return lgemm_enabled() && tile128_ok(a_kcont, b_kcont, M, N, K, A, sam, sak, B, sbk, sbn, dt) &&
-           t.bf16 && abf && bbf && (dt & DT_C) && a_kcont && b_kcont && N == 256 && ksplit == 1 && !rowsum &&
-           ((!seg2 && (K == 256 || K == 432)) || seg_skip) &&
-           sak == 1 && sbk == 1 && ldc % 8 == 0 && reinterpret_cast<uintptr_t>(C) % 16 == 0 &&
-           (!mask || ((dt & DT_M) && ldm % 8 == 0 && reinterpret_cast<uintptr_t>(mask) % 16 == 0)) &&
-           (!(flags & GEMM_ACC) || (ldcin % 4 == 0 && reinterpret_cast<uintptr_t>(cin) % 16 == 0));
+bool lgemm_takes(const Tape& t, const Gemm& g) {
+    const bool seg_skip = g.seg2 && g.K == 256 && g.seg2->K == 432 && seg2_aligned(*g.seg2);
+    return lgemm_enabled() && tile128_ok(g) &&
+           t.bf16 && (g.dt & DT_A) && (g.dt & DT_B) && (g.dt & DT_C) && g.a_kcont && g.b_kcont && g.N == 256 && g.ksplit == 1 && !g.rowsum &&
+           ((!g.seg2 && (g.K == 256 || g.K == 432)) || seg_skip) &&
+           g.sak == 1 && g.sbk == 1 && g.ldc % 8 == 0 && at16(g.C) &&
+           (!g.mask || ((g.dt & DT_M) && g.ldm % 8 == 0 && at16(g.mask))) &&
+           (!(g.flags & GEMM_ACC) || (g.ldcin % 4 == 0 && at16(g.cin)));
 }
-int gemm(pg_handle* h, hipStream_t s, bool a_kcont, bool b_kcont, int M, int N, int K, const void* A, long long sam, long long sak,
-         const void* B, long long sbk, long long sbn, void* C, long long ldc, const float* bias, int flags, int ksplit = 1,
-         const void* mask = nullptr, long long ldm = 0, float* rowsum = nullptr, int dt = 0, const float* cin = nullptr, long long ldcin = 0,
-         const KSeg2* seg2 = nullptr, const Rank1* r1 = nullptr) {
-    if (M <= 0 || N <= 0 || K <= 0) return PG_OK;
+int gemm(pg_handle* h, hipStream_t s, const Gemm& desc) {
+    Gemm g = desc;      // (cin and ksplit are settled below)
+    if (g.M <= 0 || g.N <= 0 || g.K <= 0) return PG_OK;
     Tape& t = *tape_of(h);
-    if ((flags & GEMM_ACC) && !cin) {
-        if (dt & DT_C) return pg_fail(h, PG_EINVAL, "accumulating GEMM into a bf16 result needs an fp32 input array");
-        cin = static_cast<const float*>(C); ldcin = ldc;
+    if ((g.flags & GEMM_ACC) && !g.cin) {
+        if (g.dt & DT_C) return pg_fail(h, PG_EINVAL, "accumulating GEMM into a bf16 result needs an fp32 input array");
+        g.cin = static_cast<const float*>(g.C); g.ldcin = g.ldc;
     }
-    if (ksplit > 1) {
-        const long long fit = (long long)(PART_FLOATS / ((size_t)M * N));
-        if (fit < 2) return pg_fail(h, PG_EINVAL, "split-K scratch too small for a %d x %d result", M, N);
-        if (ksplit > fit) ksplit = (int)fit;
+    if (g.ksplit > 1) {
+        const long long fit = (long long)(PART_FLOATS / ((size_t)g.M * g.N));
+        if (fit < 2) return pg_fail(h, PG_EINVAL, "split-K scratch too small for a %d x %d result", g.M, g.N);
+        if (g.ksplit > fit) g.ksplit = (int)fit;
         if (!t.part) return pg_fail(h, PG_ESTATE, "split-K GEMM without a tape");
-        if (dt & DT_C) return pg_fail(h, PG_EINVAL, "split-K GEMM results are fp32");
+        if (g.dt & DT_C) return pg_fail(h, PG_EINVAL, "split-K GEMM results are fp32");
     }
     auto reduce = [&](const float* part, int nz, int rows, int cols, float* out, long long ldo) {
         hipLaunchKernelGGL(reduce_parts_kernel, dim3((unsigned)(((long long)rows * cols + 255) / 256)), dim3(256), 0, s, part, nz, rows, cols, out, ldo);
     };
-    const bool abf = dt & DT_A, bbf = dt & DT_B;
-    const bool big = tile128_ok(a_kcont, b_kcont, M, N, K, A, sam, sak, B, sbk, sbn, dt);
+    const bool abf = g.dt & DT_A, bbf = g.dt & DT_B;
+    const bool big = tile128_ok(g);
     if ((abf || bbf) && !t.bf16) return pg_fail(h, PG_EINVAL, "bf16 GEMM operands outside the 16-bit mode");
-    if (lgemm_takes(t, a_kcont, b_kcont, M, N, K, A, sam, sak, B, sbk, sbn, C, ldc, flags, ksplit, mask, ldm, rowsum, dt, cin, ldcin, seg2)) {
+    if (lgemm_takes(t, g)) {
+        const KSeg2* sg = g.seg2;
+        const Rank1* r1 = g.r1;
         auto launch = [&](auto kern, int lds, int rows, int wgs, std::atomic<unsigned long long>& attr_done) -> int {
             if (!(attr_done.load(std::memory_order_acquire) & (1ull << (h->device & 63)))) {      // the opt-in to > 64 KiB of dynamic LDS is per (kernel, device)
                 PG_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
                 attr_done.fetch_or(1ull << (h->device & 63), std::memory_order_release);
             }
-            const int tiles = (M + rows - 1) / rows;
-            hipLaunchKernelGGL(kern, dim3(std::min(tiles, wgs * h->n_cu)), dim3(512), lds, s, M, static_cast<const bf16_t*>(A), sam,
-                               static_cast<const bf16_t*>(B), sbn, seg2 ? seg2->A : nullptr, seg2 ? seg2->sam : 0, seg2 ? seg2->B : nullptr,
-                               seg2 ? seg2->sbn : 0, static_cast<bf16_t*>(C), ldc, bias, flags, static_cast<const bf16_t*>(mask), ldm, cin, ldcin,
+            const int tiles = (g.M + rows - 1) / rows;
+            hipLaunchKernelGGL(kern, dim3(std::min(tiles, wgs * h->n_cu)), dim3(512), lds, s, g.M, static_cast<const bf16_t*>(g.A), g.sam,
+                               static_cast<const bf16_t*>(g.B), g.sbn, sg ? sg->A : nullptr, sg ? sg->sam : 0, sg ? sg->B : nullptr,
+                               sg ? sg->sbn : 0, static_cast<bf16_t*>(g.C), g.ldc, g.bias, g.flags, static_cast<const bf16_t*>(g.mask), g.ldm, g.cin, g.ldcin,
                                r1 ? r1->row : nullptr, r1 ? r1->ld : 0, r1 ? r1->col : nullptr);
             PG_LAUNCH_CHECK(h, "persistent layer GEMM");
             return PG_OK;
         };
         static std::atomic<unsigned long long> done256{0}, done432{0}, done_skip{0};
-        if (seg2) return launch(lgemm_skip_kernel, LGSKIP::LDS, 32, 1, done_skip);
-        if (K == 432) return launch(lgemm432_kernel, LG432::LDS, 32, 1, done432);
+        if (sg) return launch(lgemm_skip_kernel, LGSKIP::LDS, 32, 1, done_skip);
+        if (g.K == 432) return launch(lgemm432_kernel, LG432::LDS, 32, 1, done432);
         return launch(lgemm256_kernel, LG256::LDS, PG_LG_ROWS, PG_LG_WGS, done256);
     }
-    if (r1) return pg_fail(h, PG_EINVAL, "a rank-1 term outside the persistent layer kernel");
-    if (big && !(a_kcont == false && b_kcont == true)) {
-        const dim3 g((N + TB - 1) / TB, (M + TB - 1) / TB, ksplit);
-        if (rowsum && (size_t)ksplit * g.x * M > RS_FLOATS) return pg_fail(h, PG_EINVAL, "row-sum scratch too small");
+    if (g.r1) return pg_fail(h, PG_EINVAL, "a rank-1 term outside the persistent layer kernel");
+    if (big && !(g.a_kcont == false && g.b_kcont == true)) {
+        const dim3 grid((g.N + TB - 1) / TB, (g.M + TB - 1) / TB, g.ksplit);
+        if (g.rowsum && (size_t)g.ksplit * grid.x * g.M > RS_FLOATS) return pg_fail(h, PG_EINVAL, "row-sum scratch too small");
         bool launched = true;
-#define PG_BGEMM(AK, BK_) hipLaunchKernelGGL((bgemm128_kernel<AK, BK_>), g, dim3(256), 0, s, M, N, K, static_cast<const bf16_t*>(A), sam, sak, static_cast<const bf16_t*>(B), sbk, sbn, C, ldc, bias, flags, mask, ldm, rowsum, t.part, t.rs_part, dt, cin, ldcin, sg)
-        const KSeg2 sg = seg2 ? *seg2 : KSeg2{nullptr, nullptr, 0, 0, 0};
-        if (seg2 && !seg2_tile_ok(t, a_kcont, b_kcont, K, ksplit, dt, seg2))
+#define PG_BGEMM(AK, BK_)                                                                                                                    \
+    hipLaunchKernelGGL((bgemm128_kernel<AK, BK_>), grid, dim3(256), 0, s, g.M, g.N, g.K, static_cast<const bf16_t*>(g.A), g.sam, g.sak,          \
+                       static_cast<const bf16_t*>(g.B), g.sbk, g.sbn, g.C, g.ldc, g.bias, g.flags, g.mask, g.ldm, g.rowsum, t.part, t.rs_part,   \
+                       g.dt, g.cin, g.ldcin, sg)
+        const KSeg2 sg = g.seg2 ? *g.seg2 : KSeg2{nullptr, nullptr, 0, 0, 0};
+        if (g.seg2 && !seg2_tile_ok(t, g))
             return pg_fail(h, PG_EINVAL, "two-segment GEMM: bf16 k-contiguous operands, first segment a multiple of the k-step");
         if (t.bf16) {       // the operand layouts the 16-bit training step uses: forward, dX, dW
             if (!(abf && bbf)) launched = false;
-            else if (a_kcont && b_kcont) PG_BGEMM(true, true);
-            else if (a_kcont) PG_BGEMM(true, false);
+            else if (g.a_kcont && g.b_kcont) PG_BGEMM(true, true);
+            else if (g.a_kcont) PG_BGEMM(true, false);
             else PG_BGEMM(false, false);
         } else {
-            if (dt) return pg_fail(h, PG_EINVAL, "bf16 GEMM operands outside the 16-bit mode");
-            float* Cf = static_cast<float*>(C);
-            const float* Af = static_cast<const float*>(A);
-            const float* Bf = static_cast<const float*>(B);
-            const float* mf = static_cast<const float*>(mask);
-#define PG_SGEMM(AK, BK_) hipLaunchKernelGGL((sgemm128_kernel<AK, BK_>), g, dim3(256), 0, s, M, N, K, Af, sam, sak, Bf, sbk, sbn, Cf, ldc, bias, flags, mf, ldm, rowsum, t.part, t.rs_part, cin, ldcin)
-            if (a_kcont && b_kcont) PG_SGEMM(true, true);
-            else if (a_kcont) PG_SGEMM(true, false);
+            if (g.dt) return pg_fail(h, PG_EINVAL, "bf16 GEMM operands outside the 16-bit mode");
+            float* Cf = static_cast<float*>(g.C);
+            const float* Af = static_cast<const float*>(g.A);
+            const float* Bf = static_cast<const float*>(g.B);
+            const float* mf = static_cast<const float*>(g.mask);
+#define PG_SGEMM(AK, BK_)                                                                                                                    \
+    hipLaunchKernelGGL((sgemm128_kernel<AK, BK_>), grid, dim3(256), 0, s, g.M, g.N, g.K, Af, g.sam, g.sak, Bf, g.sbk, g.sbn, Cf, g.ldc, g.bias,   \
+                       g.flags, mf, g.ldm, g.rowsum, t.part, t.rs_part, g.cin, g.ldcin)
+            if (g.a_kcont && g.b_kcont) PG_SGEMM(true, true);
+            else if (g.a_kcont) PG_SGEMM(true, false);
             else PG_SGEMM(false, false);
 #undef PG_SGEMM
         }
 #undef PG_BGEMM
         if (launched) {
             PG_LAUNCH_CHECK(h, "gemm128");
-            if (ksplit > 1) { reduce(t.part, ksplit, M, N, static_cast<float*>(C), ldc); PG_LAUNCH_CHECK(h, "split-K reduction"); }
-            if (rowsum && !a_kcont) { reduce(t.rs_part, ksplit * (int)g.x, 1, M, rowsum, M); PG_LAUNCH_CHECK(h, "row-sum reduction"); }
+            if (g.ksplit > 1) { reduce(t.part, g.ksplit, g.M, g.N, static_cast<float*>(g.C), g.ldc); PG_LAUNCH_CHECK(h, "split-K reduction"); }
+            if (g.rowsum && !g.a_kcont) { reduce(t.rs_part, g.ksplit * (int)grid.x, 1, g.M, g.rowsum, g.M); PG_LAUNCH_CHECK(h, "row-sum reduction"); }
             return PG_OK;
         }
     }
-    if (seg2) return pg_fail(h, PG_EINVAL, "two-segment GEMM outside the 128-tile bf16 kernel");
+    if (g.seg2) return pg_fail(h, PG_EINVAL, "two-segment GEMM outside the 128-tile bf16 kernel");
     // small or unaligned shapes (and operand type mixes the 128-tile kernel has no instantiation for): the 64-tile kernel,
     // then the mask / the row sums as kernels of their own
-    if (mask && (ldc != N || ldm != N || ((dt & DT_C) != 0) != ((dt & DT_M) != 0)))
+    if (g.mask && (g.ldc != g.N || g.ldm != g.N || ((g.dt & DT_C) != 0) != ((g.dt & DT_M) != 0)))
         return pg_fail(h, PG_EINVAL, "ReLU mask behind a strided small GEMM result is not supported");
-    if (rowsum && a_kcont) return pg_fail(h, PG_EINVAL, "row sums need the m-contiguous A operand");
-    const dim3 grid((N + GB - 1) / GB, (M + GB - 1) / GB, ksplit);
-#define PG_SMALL(AK, BK_) hipLaunchKernelGGL((sgemm_kernel<AK, BK_>), grid, dim3(256), 0, s, M, N, K, A, sam, sak, B, sbk, sbn, C, ldc, bias, flags, t.part, dt, cin, ldcin)
-    if (a_kcont && b_kcont) PG_SMALL(true, true);
-    else if (a_kcont) PG_SMALL(true, false);
-    else if (!b_kcont) PG_SMALL(false, false);
+    if (g.rowsum && g.a_kcont) return pg_fail(h, PG_EINVAL, "row sums need the m-contiguous A operand");
+    const dim3 grid((g.N + GB - 1) / GB, (g.M + GB - 1) / GB, g.ksplit);
+#define PG_SMALL(AK, BK_)                                                                                                                    \
+    hipLaunchKernelGGL((sgemm_kernel<AK, BK_>), grid, dim3(256), 0, s, g.M, g.N, g.K, g.A, g.sam, g.sak, g.B, g.sbk, g.sbn, g.C, g.ldc, g.bias,  \
+                       g.flags, t.part, g.dt, g.cin, g.ldcin)
+    if (g.a_kcont && g.b_kcont) PG_SMALL(true, true);
+    else if (g.a_kcont) PG_SMALL(true, false);
+    else if (!g.b_kcont) PG_SMALL(false, false);
     else return pg_fail(h, PG_EINVAL, "unsupported GEMM operand layout");
 #undef PG_SMALL
     PG_LAUNCH_CHECK(h, "sgemm");
-    if (ksplit > 1) { reduce(t.part, ksplit, M, N, static_cast<float*>(C), ldc); PG_LAUNCH_CHECK(h, "split-K reduction"); }
-    if (mask) {
-        const unsigned blocks = (unsigned)std::min<long long>(((long long)M * N + 255) / 256, 8192);
-        hipLaunchKernelGGL(relu_mask_kernel, dim3(blocks), dim3(256), 0, s, C, mask, (long long)M * N, (dt & DT_C) ? 1 : 0);
+    if (g.ksplit > 1) { reduce(t.part, g.ksplit, g.M, g.N, static_cast<float*>(g.C), g.ldc); PG_LAUNCH_CHECK(h, "split-K reduction"); }
+    if (g.mask) {
+        const unsigned blocks = (unsigned)std::min<long long>(((long long)g.M * g.N + 255) / 256, 8192);
+        hipLaunchKernelGGL(relu_mask_kernel, dim3(blocks), dim3(256), 0, s, g.C, g.mask, (long long)g.M * g.N, (g.dt & DT_C) ? 1 : 0);
         PG_LAUNCH_CHECK(h, "relu_mask");
     }
-    if (rowsum) {
-        const unsigned blocks = (unsigned)((K + 255) / 256);
-        if ((size_t)blocks * M > RS_FLOATS) return pg_fail(h, PG_EINVAL, "row-sum scratch too small");
-        hipLaunchKernelGGL(colsum_wide_kernel, dim3(blocks), dim3(256), 0, s, A, (long long)K, M, sak, t.rs_part, abf ? 1 : 0);
+    if (g.rowsum) {
+        const unsigned blocks = (unsigned)((g.K + 255) / 256);
+        if ((size_t)blocks * g.M > RS_FLOATS) return pg_fail(h, PG_EINVAL, "row-sum scratch too small");
+        hipLaunchKernelGGL(colsum_wide_kernel, dim3(blocks), dim3(256), 0, s, g.A, (long long)g.K, g.M, g.sak, t.rs_part, abf ? 1 : 0);
         PG_LAUNCH_CHECK(h, "colsum");
-        reduce(t.rs_part, (int)blocks, 1, M, rowsum, M);
+        reduce(t.rs_part, (int)blocks, 1, g.M, g.rowsum, g.M);
         PG_LAUNCH_CHECK(h, "column-sum reduction");
     }
     return PG_OK;
+}
+// Y[P,out] = X[P,in] W[out,in]^T (+ b, relu): the GEMM of an nn.Linear forward, both operands k-contiguous
+inline Gemm fwd_gemm(long long P, int out, int in, const void* X, long long ldx, const void* W, long long ldw, void* Y, long long ldy,
+                     const float* b, int flags, int dt) {
+    Gemm g;
+    g.M = (int)P; g.N = out; g.K = in;
+    g.A = X; g.sam = ldx;
+    g.B = W; g.sbn = ldw;
+    g.C = Y; g.ldc = ldy;
+    g.bias = b; g.flags = flags; g.dt = dt;
+    return g;
 }
 // Y[P,out] = X[P,in] W[out,in]^T (+ b, relu, accumulate)        (nn.Linear forward)
 // dt: DT_A = X is bf16, DT_C = Y is bf16; cin: the fp32 array GEMM_ACC adds (null: Y itself)
@@ -1496,7 +1530,9 @@ int linear_fwd(pg_handle* h, hipStream_t s, long long P, int out, int in, const 
         PG_LAUNCH_CHECK(h, "skinny forward");
         return PG_OK;
     }
-    return gemm(h, s, true, true, (int)P, out, in, X, ldx, 1, W, 1, ldw, Y, ldy, b, flags, 1, nullptr, 0, nullptr, dt, cin, ldcin);
+    Gemm g = fwd_gemm(P, out, in, X, ldx, W, ldw, Y, ldy, b, flags, dt);
+    g.cin = cin; g.ldcin = ldcin;
+    return gemm(h, s, g);
 }
 // Y[P,out] = [X1 | X2] [W1 | W2]^T + b (relu): a layer on the concatenation of two inputs in ONE pass (16-bit mode: no fp32
 // partial sum through HBM); in1 a multiple of the k-step.  Where neither two-segment kernel takes the shape (the persistent
@@ -1507,18 +1543,32 @@ int linear_fwd2(pg_handle* h, hipStream_t s, long long P, int out, int in1, cons
     const KSeg2 sg{static_cast<const bf16_t*>(X2), static_cast<const bf16_t*>(W2), ldx2, ldw2, in2};
     const int ABC = DT_A | DT_B | DT_C;
     const Tape& t = *tape_of(h);
-    if (lgemm_takes(t, true, true, (int)P, out, in1, X1, ldx1, 1, W1, 1, ldw1, Y, ldy, flags, 1, nullptr, 0, nullptr, ABC, nullptr, 0, &sg) ||
-        (tile128_ok(true, true, (int)P, out, in1, X1, ldx1, 1, W1, 1, ldw1, ABC) && seg2_tile_ok(t, true, true, in1, 1, ABC, &sg)))
-        return gemm(h, s, true, true, (int)P, out, in1, X1, ldx1, 1, W1, 1, ldw1, Y, ldy, b, flags, 1, nullptr, 0, nullptr, ABC, nullptr, 0, &sg);
-    const int rc = linear_fwd(h, s, P, out, in2, X2, ldx2, W2, ldw2, tmp, out, nullptr, 0, DT_A | DT_B);
-    return rc ? rc : linear_fwd(h, s, P, out, in1, X1, ldx1, W1, ldw1, Y, ldy, b, flags | GEMM_ACC, ABC, tmp, out);
+    Gemm g = fwd_gemm(P, out, in1, X1, ldx1, W1, ldw1, Y, ldy, b, flags, ABC);
+    g.seg2 = &sg;
+    if (lgemm_takes(t, g) || (tile128_ok(g) && seg2_tile_ok(t, g))) return gemm(h, s, g);
+    PG_TRY(linear_fwd(h, s, P, out, in2, X2, ldx2, W2, ldw2, tmp, out, nullptr, 0, DT_A | DT_B));
+    return linear_fwd(h, s, P, out, in1, X1, ldx1, W1, ldw1, Y, ldy, b, flags | GEMM_ACC, ABC, tmp, out);
+}
+// dX[P,in] (+)= dY[P,out] W[out,in]: the GEMM of linear_bwd_x (arguments as there).  WT: the step's transposed bf16 copy [in][out]
+// of W's block -- both operands k-contiguous (16-byte tile stores, no transposing ones); null: W itself, n-contiguous
+inline Gemm bwd_x_gemm(long long P, int out, int in, const void* dY, long long ldy, const void* W, long long ldw, void* dX, long long ldx,
+                       int flags, const void* relu_of, int dt, const float* cin, long long ldcin, const bf16_t* WT) {
+    Gemm g;
+    g.M = (int)P; g.N = in; g.K = out;
+    g.A = dY; g.sam = ldy;
+    if (WT) { g.B = WT; g.sbn = out; }
+    else { g.b_kcont = false; g.B = W; g.sbk = ldw; g.sbn = 1; }
+    g.C = dX; g.ldc = ldx;
+    g.flags = flags; g.mask = relu_of; g.ldm = ldx; g.dt = dt;
+    g.cin = cin; g.ldcin = ldcin;
+    return g;
 }
 // dX[P,in] (+)= dY[P,out] W[out,in]
 // relu_of: the stored post-activation the consumer of dX was ReLU'd to -- dX is zeroed where it is <= 0 (fused ReLU backward)
 // dt: DT_A = dY, DT_C = dX, DT_M = relu_of are bf16
 int linear_bwd_x(pg_handle* h, hipStream_t s, long long P, int out, int in, const void* dY, long long ldy, const void* W, long long ldw,
                  void* dX, long long ldx, int flags, const void* relu_of = nullptr, int dt = 0, const float* cin = nullptr, long long ldcin = 0,
-                 const bf16_t* WT = nullptr, const Rank1* r1 = nullptr) {
+                 const bf16_t* WT = nullptr) {
     // the heads (1 or 3 outputs, fp32 dY and weights): one pass that writes dX
     if ((out == 1 || out == 3) && !WT && flags == 0 && !(dt & (DT_A | DT_B)) && in % 8 == 0 && ldx % 8 == 0 && reinterpret_cast<uintptr_t>(dX) % 16 == 0 &&
         (!relu_of || reinterpret_cast<uintptr_t>(relu_of) % 16 == 0) &&
@@ -1533,10 +1583,7 @@ int linear_bwd_x(pg_handle* h, hipStream_t s, long long P, int out, int in, cons
         PG_LAUNCH_CHECK(h, "skinny input gradient");
         return PG_OK;
     }
-    // WT: the step's transposed bf16 copy [in][out] of W's block -- both operands k-contiguous (16-byte tile stores, no transposing ones)
-    if (WT) return gemm(h, s, true, true, (int)P, in, out, dY, ldy, 1, WT, 1, out, dX, ldx, nullptr, flags, 1, relu_of, ldx, nullptr, dt, cin, ldcin, nullptr, r1);
-    if (r1) return pg_fail(h, PG_EINVAL, "a rank-1 term needs the transposed weight copy");
-    return gemm(h, s, true, false, (int)P, in, out, dY, ldy, 1, W, ldw, 1, dX, ldx, nullptr, flags, 1, relu_of, ldx, nullptr, dt, cin, ldcin);
+    return gemm(h, s, bwd_x_gemm(P, out, in, dY, ldy, W, ldw, dX, ldx, flags, relu_of, dt, cin, ldcin, WT));
 }
 // dW[out,in] = dY[P,out]^T X[P,in] (split-K over the points, slices summed in order); dt: DT_A = dY, DT_B = X are bf16
 int linear_bwd_w(pg_handle* h, hipStream_t s, long long P, int out, int in, const void* dY, long long ldy, const void* X, long long ldx,
@@ -1566,8 +1613,15 @@ int linear_bwd_w(pg_handle* h, hipStream_t s, long long P, int out, int in, cons
     // step; POSEGEN_DW_WGS overrides): the GEMM streams dY and X once whatever the split, every slice costs a tile of partial
     // sums written and read again by the reduction
     static const int wg_target = [] { const char* e = std::getenv("POSEGEN_DW_WGS"); return e ? std::atoi(e) : 512; }();
-    int ksplit = (int)std::max<long long>(1, std::min<long long>(wg_target / std::max(tiles, 1), (P + 1023) / 1024));
-    return gemm(h, s, false, false, out, in, (int)P, dY, 1, ldy, X, ldx, 1, dW, ldw, nullptr, 0, std::max(ksplit, 2), nullptr, 0, db, dt);
+    const int ksplit = (int)std::max<long long>(1, std::min<long long>(wg_target / std::max(tiles, 1), (P + 1023) / 1024));
+    Gemm g;     // both operands m- / n-contiguous: k runs over the points
+    g.a_kcont = g.b_kcont = false;
+    g.M = out; g.N = in; g.K = (int)P;
+    g.A = dY; g.sam = 1; g.sak = ldy;
+    g.B = X; g.sbk = ldx; g.sbn = 1;
+    g.C = dW; g.ldc = ldw;
+    g.ksplit = std::max(ksplit, 2); g.rowsum = db; g.dt = dt;
+    return gemm(h, s, g);
 }
 int colsum(pg_handle* h, hipStream_t s, const float* d, long long rows, int N, long long ld, float* out) {
     Tape& t = *tape_of(h);
@@ -1580,14 +1634,6 @@ int colsum(pg_handle* h, hipStream_t s, const float* d, long long rows, int N, l
     PG_LAUNCH_CHECK(h, "column-sum reduction");
     return PG_OK;
 }
-int relu_mask(pg_handle* h, hipStream_t s, void* d, const void* hh, long long count, int bf) {
-    const unsigned blocks = (unsigned)std::min<long long>((count + 255) / 256, 8192);
-    hipLaunchKernelGGL(relu_mask_kernel, dim3(blocks), dim3(256), 0, s, d, hh, count, bf);
-    PG_LAUNCH_CHECK(h, "relu_mask");
-    return PG_OK;
-}
-
-#define PG_TRY(call) do { const int rc_ = (call); if (rc_) return rc_; } while (0)
 
 // tensor i of a net in pg_load_weights order: 2l / 2l+1 = pts_linears.l.{weight,bias}; 16,17 alpha; 18,19 feature; 20,21 views; 22,23 rgb
 // 16-bit mode: every activation of the tape is a bf16 array (A = DT_A, results DT_C); a layer made of two GEMMs (the skip
@@ -1667,17 +1713,18 @@ int mlp_backward(pg_handle* h, hipStream_t s, Tape& t, int net, const Pass& p, c
     // feature_linear and alpha_linear on the trunk output
     const void* h7 = p.H[DEPTH - 1];
     PG_TRY(linear_bwd_w(h, s, P, W, W, dF, W, h7, W, g.w[18], W, g.w[19], AB));
-    void* dH = t.tmpB;              // dH7 = (alpha's part + feature's part) * [H7 > 0]: the mask rides on the second GEMM
-    // 16-bit mode on the persistent kernel: alpha's part d sigma (x) w_alpha rides in the feature GEMM's epilogue as a rank-1 term
-    // (fp32); the arguments are those linear_bwd_x hands gemm() below
-    if (bf && lgemm_takes(t, true, true, (int)P, W, W, dF, W, 1, t.wbT[net][18], 1, W, dH, W, 0, 1, h7, W, nullptr, ABCM, nullptr, 0, nullptr)) {
-        const Rank1 r1{d_raw + 3, 4, w.w[16]};
-        PG_TRY(linear_bwd_x(h, s, P, W, W, dF, W, WT(18, 0), W, dH, W, 0, h7, ABCM, nullptr, 0, t.wbT[net][18], &r1));
+    void* dH = t.tmpB;              // dH7 = (alpha's part + feature's part) * [H7 > 0]: the mask rides on the feature GEMM
+    Gemm gh = bwd_x_gemm(P, W, W, dF, W, WT(18, 0), W, dH, W, 0, h7, ABCM, nullptr, 0, bf ? t.wbT[net][18] : nullptr);
+    const Rank1 r1{d_raw + 3, 4, w.w[16]};
+    if (lgemm_takes(t, gh)) {
+        // 16-bit mode on the persistent kernel: alpha's part d sigma (x) w_alpha rides in the feature GEMM's epilogue as a rank-1 term (fp32)
+        gh.r1 = &r1;
     } else {
         void* dpart = bf ? static_cast<void*>(t.tmpF) : dH;      // (16-bit mode: alpha's part in fp32, rounded once with the sum)
         PG_TRY(linear_bwd_x(h, s, P, 1, W, d_raw + 3, 4, w.w[16], W, dpart, W, 0));
-        PG_TRY(linear_bwd_x(h, s, P, W, W, dF, W, WT(18, 0), W, dH, W, GEMM_ACC, h7, ABCM, static_cast<const float*>(dpart), W, bf ? t.wbT[net][18] : nullptr));
+        gh.flags = GEMM_ACC; gh.cin = static_cast<const float*>(dpart); gh.ldcin = W;
     }
+    PG_TRY(gemm(h, s, gh));
     PG_TRY(linear_bwd_w(h, s, P, 1, W, d_raw + 3, 4, h7, W, g.w[16], W, nullptr, B_));
     PG_TRY(colsum(h, s, d_raw + 3, P, 1, 4, g.w[17]));
     // the trunk, back to front: dZ_l = dH_l * [H_l > 0]
@@ -1702,149 +1749,271 @@ int mlp_backward(pg_handle* h, hipStream_t s, Tape& t, int net, const Pass& p, c
     return PG_OK;
 }
 
-// ---- the single-net training step (core/raycasters.py:99-104, 446-469; arguments checked by pg_train_forward) -----------------
+// ---- the training tape: layout, the step's weight copies, the stages both models' forwards share -------------------------------
+// pg_train_forward's arguments (checked there), as the stages of the forward take them
+struct Step {
+    pg_handle* h;
+    hipStream_t s;
+    long long n, pose_stride, cyl_stride;
+    const float *ray_batch, *skts, *cyls, *cams;
+    int S, N, flags;
+    const pg_train_draws* dr;
+    const pg_outputs* out;
+    int64_t* tape_id;
+};
+// what the tape's layout depends on
+struct TapeShape {
+    long long n;
+    int S, N;
+    bool single, bf16, fc, views0;
+};
+// tensor i of a net (pg_load_weights order) as the large GEMMs read it: a [rows, cols] matrix the 16-bit mode keeps a bf16 copy
+// of, and the column block [tcol0, tcol0 + tcols) the dX GEMMs multiply by, kept transposed [tcols][rows] as well (tcols = 0:
+// none -- layer 0 has no dX).  rows = 0: a bias or a head's weight, read in fp32 where it is
+struct WMat { int rows, cols, tcols, tcol0; };
+inline WMat wmat(int i, int fc) {
+    if (i == 0) return {W, CH_X, 0, 0};
+    if (i == 2 * (SKIP + 1)) return {W, CH_X + W, W, CH_X};
+    if (i == 20) return {VW, W + CH_D + (fc ? FC_CH : 0), W, 0};
+    if (i % 2 == 0 && (i < 2 * DEPTH || i == 18)) return {W, W, W, 0};
+    return {0, 0, 0, 0};
+}
+// THE layout of the tape: sets every pointer of `t` into the buffer at `base` and returns the bytes used.  Run with a null base
+// first (the byte count; the pointers come out null), then with the allocation -- an array cannot be carved without being counted
+size_t plan_tape(Tape& t, const TapeShape& sh, uint8_t* base) {
+    // every array starts on a 256-byte boundary (the GEMMs pick kernels by the alignment of these pointers)
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        float* r = base ? reinterpret_cast<float*>(base + off) : nullptr;
+        off += (bytes + 255) & ~size_t(255);
+        return r;
+    };
+    auto take_weights = [&](int k, bool on) {       // net k's bf16 weight copies (on = false: none, the pointers are null)
+        for (int i = 0; i < 24; ++i) {
+            const WMat m = wmat(i, sh.fc);
+            t.wb[k][i] = (on && m.rows) ? reinterpret_cast<bf16_t*>(take((size_t)m.rows * m.cols * 2)) : nullptr;
+            t.wbT[k][i] = (on && m.tcols) ? reinterpret_cast<bf16_t*>(take((size_t)m.rows * m.tcols * 2)) : nullptr;
+        }
+    };
+    const size_t n = (size_t)sh.n, SF = sh.S + sh.N, es = sh.bf16 ? 2 : 4;
+    t.rays = take(n * 44);
+    t.cams = take(n * 4);           // (tape_begin: null when the call has no per-ray cameras)
+    t.near_far = take(n * 8);
+    t.w0 = take(n * sh.S * 4);
+    t.order = reinterpret_cast<int*>(take(n * SF * 4));
+    t.zf = t.noise1 = t.Tb = nullptr;
+    if (sh.single) { t.zf = take(n * SF * 4); t.noise1 = take(n * SF * 4); t.Tb = take(n * SF * 4); }
+    // the passes: one net on the S coarse + N new rows of every ray, or the coarse net on S and the fine net on S + N
+    t.pass[0] = t.pass[1] = Pass();
+    t.pass[0].S = sh.S;
+    if (sh.single) {
+        t.pass[0].P = sh.n * (sh.S + sh.N); t.pass[0].P1 = sh.n * sh.S; t.pass[0].S2 = sh.N;
+    } else {
+        t.pass[0].P = sh.n * sh.S;
+        if (sh.N > 0) { t.pass[1].P = sh.n * (sh.S + sh.N); t.pass[1].S = sh.S + sh.N; }
+    }
+    for (Pass& p : t.pass) {
+        if (!p.P) continue;
+        const size_t P = (size_t)p.P;
+        p.X = take(P * XW * es);
+        for (int l = 0; l < DEPTH; ++l) p.H[l] = take(P * W * es);
+        p.F = take(P * W * es);
+        p.G = take(P * VW * es);
+        p.raw = take(P * 16);
+        p.z = take(P * 4);
+        p.noise = take(P * 4);        // (single net: noise0 is the first n S entries)
+        p.pn = take(P * 12);
+    }
+    // the backward's scratch, sized for the larger pass
+    const size_t Pm = (size_t)std::max(t.pass[0].P, t.pass[1].P);
+    t.tmpA = take(Pm * W * es); t.tmpB = take(Pm * W * es);
+    t.dG = take(Pm * VW * es); t.dC = take(Pm * FC_CH * 4); t.d_raw = take(Pm * 16);
+    t.tmpF = sh.bf16 ? take(Pm * W * 4) : nullptr;
+    const size_t vwide = (size_t)wmat(20, sh.fc).rows * wmat(20, sh.fc).cols * 4;
+    t.vwide = (sh.single && sh.views0) ? take(vwide) : nullptr;     // (two nets never train in the widened layout)
+    t.gwide = (sh.single && sh.views0) ? take(vwide) : nullptr;
+    for (int k = 0; k < 2; ++k) take_weights(k, sh.bf16 && t.pass[k].P > 0);
+    t.part = take(PART_FLOATS * 4); t.rs_part = take(RS_FLOATS * 4); t.ray_g = take(n * FC_CH * 4);
+    return off;
+}
+// a device buffer that only ever grows (the old contents are void; what read them has to finish before they go)
+int grow(pg_handle* h, uint8_t*& buf, size_t& bytes, size_t need, const char* what) {
+    if (need <= bytes) return PG_OK;
+    if (buf) { PG_HIP(h, hipDeviceSynchronize()); PG_HIP(h, hipFree(buf)); buf = nullptr; bytes = 0; }
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&buf), need);
+    if (e != hipSuccess) return pg_fail(h, PG_ENOMEM, "%s of %zu bytes failed: %s", what, need, hipGetErrorString(e));
+    bytes = need;
+    return PG_OK;
+}
+// the start of a forward: the old tape is void from here on, the new one is laid out (the buffer only ever grows) and described
+int tape_begin(const Step& a, Tape& t) {
+    pg_handle* h = a.h;
+    PG_HIP(h, hipSetDevice(h->device));
+    t.valid = false;
+    const bool single = h->cfg.single_net != 0;
+    const TapeShape sh{a.n, a.S, a.N, single, h->train_precision == PG_PREC_BF16, h->cfg.framecode_ch > 0, h->cfg.multires_views == 0};
+    // (the counting run leaves every pointer of the tape null; should the allocation fail they stay so, behind valid = false)
+    PG_TRY(grow(h, t.buf, t.bytes, plan_tape(t, sh, nullptr), "training tape"));
+    if (plan_tape(t, sh, t.buf) > t.bytes) return pg_fail(h, PG_ESTATE, "training tape: the layout ends outside the allocation");
+    if (!a.cams) t.cams = nullptr;
+    t.n = a.n; t.S = a.S; t.N = a.N; t.fc = sh.fc; t.bf16 = sh.bf16;     // (16-bit mode: the tape's activations and their gradients are bf16 arrays)
+    t.single = single; t.views0 = sh.views0; t.has_fine = !single && a.N > 0;
+    t.skts = a.skts; t.pose_stride = a.pose_stride; t.rnoise = a.dr && a.dr->ray_noise; t.tau[0] = h->tau[0]; t.tau[1] = h->tau[1];
+    return PG_OK;
+}
+// net k's conversion jobs: a plain copy of every matrix of the table, a transposed copy of its dX block
+int add_weight_jobs(pg_handle* h, const Tape& t, int k, WJobs& js, int& nj) {
+    for (int i = 0; i < 24; ++i) {
+        const WMat m = wmat(i, t.fc);
+        if (!m.rows) continue;
+        if (nj + (m.tcols ? 2 : 1) > WJOBS_MAX) return pg_fail(h, PG_EINVAL, "weight conversion: more than %d jobs", WJOBS_MAX);
+        const float* src = t.params[k].w[i];
+        js.j[nj++] = WJob{src, t.wb[k][i], 0, 1, m.rows * m.cols, 0};
+        if (m.tcols) js.j[nj++] = WJob{src + m.tcol0, t.wbT[k][i], (long long)m.cols, m.rows, m.tcols, 1};
+    }
+    return PG_OK;
+}
+// 16-bit mode: this step's bf16 copies of the weight matrices of t.params (the parameters do not change between forward and
+// backward), all nets in ONE launch
+int convert_weights(pg_handle* h, hipStream_t s, const Tape& t) {
+    if (!t.bf16) return PG_OK;
+    WJobs js{};
+    int nj = 0;
+    for (int k = 0; k < (t.has_fine ? 2 : 1); ++k) PG_TRY(add_weight_jobs(h, t, k, js, nj));
+    hipLaunchKernelGGL(cvt_weights_kernel, dim3(64, nj), dim3(256), 0, s, js);
+    PG_LAUNCH_CHECK(h, "weight conversion");
+    return PG_OK;
+}
+// the network inputs of a pass's points.  frame codes: [n_codes + 1, 16], the caller appends the mean row (embedding.py:25-26)
+// that a negative index selects
+int launch_embed(pg_handle* h, hipStream_t s, const Tape& t, const Pass& p, const float* codes, int n_codes) {
+    const dim3 grid((unsigned)((p.P * J + 255) / 256));
+#define PG_EMBED(XT)                                                                                                                         \
+    hipLaunchKernelGGL(embed_rows_kernel<XT>, grid, dim3(256), 0, s, t.rays, p.z, t.rnoise ? p.pn : nullptr, t.skts, t.pose_stride, t.cams,      \
+                       codes, n_codes, t.fc, h->d_cut, t.tau[0], t.tau[1], p.P, p.S, static_cast<XT*>(p.X))
+    if (t.bf16) PG_EMBED(bf16_t);
+    else PG_EMBED(float);
+#undef PG_EMBED
+    if (hipGetLastError() != hipSuccess) return pg_fail(h, PG_EHIP, "embedding kernel launch failed");
+    return PG_OK;
+}
+// what follows once t.params is set: the step's weight copies, the rays onto the tape, then the coarse points -- rows [0, n S) of
+// pass 0, returned as `pc` -- through net 0: depths, their draws (density noise, position noise: rows [:S] of every ray's),
+// embedding, MLP
+int coarse_stage(const Step& a, Tape& t, Pass& pc) {
+    pg_handle* h = a.h;
+    const long long Pc = a.n * a.S;
+    PG_TRY(convert_weights(h, a.s, t));
+    PG_HIP(h, hipMemcpyAsync(t.rays, a.ray_batch, (size_t)a.n * 44, hipMemcpyDeviceToDevice, a.s));
+    if (a.cams) PG_HIP(h, hipMemcpyAsync(t.cams, a.cams, (size_t)a.n * 4, hipMemcpyDeviceToDevice, a.s));
+    if (!(a.dr && a.dr->noise0)) t.pass[0].noise = nullptr;
+    pc = sub_pass(t.pass[0], 0, Pc, a.S, t.es());
+    double* scs = nullptr;
+    PG_TRY(pg_sc_scratch(h, a.n, h->cfg.chunk, &scs));
+    PG_TRY_LAUNCH(h, "coarse sampling", pg_launch_sample_coarse(t.rays, a.cyls, a.cyl_stride, a.n, h->cfg.chunk, a.S, (a.flags & PG_FLAG_LINDISP) ? 1 : 0,
+                                                                 t.near_far, pc.z, a.dr ? a.dr->t_rand : nullptr, scs, a.s));
+    if (pc.noise) PG_HIP(h, hipMemcpyAsync(pc.noise, a.dr->noise0, (size_t)Pc * 4, hipMemcpyDeviceToDevice, a.s));
+    if (t.rnoise) PG_TRY_LAUNCH(h, "noise gather", pg_launch_gather_noise(a.dr->ray_noise, a.n, a.S + a.N, a.S, nullptr, pc.pn, a.s));
+    PG_TRY(launch_embed(h, a.s, t, pc, t.params[0].codes, t.params[0].n_codes));
+    return mlp_forward(h, a.s, t, 0, pc, t.params[0], t.fc);
+}
+// the end of a forward: the coarse stage's outputs and the merged depths `zf` [n, S + N] / the fine rows' `raw_fine` (null:
+// none, or written by a kernel already), then the tape is valid under a new id
+int finish_step(const Step& a, Tape& t, const Pass& pc, const float* zf, const float* raw_fine) {
+    pg_handle* h = a.h;
+    const size_t Pf = (size_t)a.n * (a.S + a.N);
+    if (a.out->near_far) PG_HIP(h, hipMemcpyAsync(a.out->near_far, t.near_far, (size_t)a.n * 8, hipMemcpyDeviceToDevice, a.s));
+    if (a.out->z_coarse) PG_HIP(h, hipMemcpyAsync(a.out->z_coarse, pc.z, (size_t)pc.P * 4, hipMemcpyDeviceToDevice, a.s));
+    if (a.out->raw_coarse) PG_HIP(h, hipMemcpyAsync(a.out->raw_coarse, pc.raw, (size_t)pc.P * 16, hipMemcpyDeviceToDevice, a.s));
+    if (zf && a.out->z_fine) PG_HIP(h, hipMemcpyAsync(a.out->z_fine, zf, Pf * 4, hipMemcpyDeviceToDevice, a.s));
+    if (raw_fine && a.out->raw_fine) PG_HIP(h, hipMemcpyAsync(a.out->raw_fine, raw_fine, Pf * 16, hipMemcpyDeviceToDevice, a.s));
+    t.valid = true;
+    t.generation += 1;
+    if (a.tape_id) *a.tape_id = t.generation;
+    return PG_OK;
+}
+
+// ---- two nets (core/raycasters.py:361-474): the coarse composite draws the importance samples, the fine net runs on all S + N ----
+int forward_two_nets(const Step& a, Tape& t, const pg_net_params& coarse, const pg_net_params* fine) {
+    pg_handle* h = a.h;
+    const pg_outputs* out = a.out;
+    const pg_train_draws* dr = a.dr;
+    const bool hier = a.N > 0;
+    const int SF = a.S + a.N;
+    t.params[0] = coarse;
+    if (hier) t.params[1] = *fine;
+    Pass pc;
+    PG_TRY(coarse_stage(a, t, pc));
+    const float ds = h->cfg.density_scale, eps = h->cfg.rgb_eps, shift = h->cfg.softplus_shift;
+    const int act = h->cfg.density_act;
+    Pass& pf = t.pass[1];
+    PG_TRY_LAUNCH(h, "composite", pg_launch_composite(t.rays, pc.z, pc.raw, a.n, a.S, ds, eps, act, shift, hier ? out->rgb0 : out->rgb_map,
+                                                      hier ? out->disp0 : out->disp_map, hier ? out->acc0 : out->acc_map, hier ? out->alpha0 : out->alpha,
+                                                      out->weights0 ? out->weights0 : t.w0, a.N, hier ? pf.z : nullptr, pc.noise,
+                                                      dr ? dr->u_rand : nullptr, (t.rnoise && hier) ? t.order : nullptr, a.s));
+    if (hier) {
+        if (dr && dr->noise1) PG_HIP(h, hipMemcpyAsync(pf.noise, dr->noise1, (size_t)pf.P * 4, hipMemcpyDeviceToDevice, a.s));
+        else pf.noise = nullptr;
+        // every point's position noise, in the merged order of its ray
+        if (t.rnoise) PG_TRY_LAUNCH(h, "noise gather", pg_launch_gather_noise(dr->ray_noise, a.n, SF, SF, t.order, pf.pn, a.s));
+        PG_TRY(launch_embed(h, a.s, t, pf, fine->codes, fine->n_codes));
+        PG_TRY(mlp_forward(h, a.s, t, 1, pf, *fine, t.fc));
+        PG_TRY_LAUNCH(h, "composite", pg_launch_composite(t.rays, pf.z, pf.raw, a.n, SF, ds, eps, act, shift, out->rgb_map, out->disp_map, out->acc_map,
+                                                          out->alpha, nullptr, 0, nullptr, pf.noise, nullptr, nullptr, a.s));
+    }
+    return finish_step(a, t, pc, hier ? pf.z : nullptr, hier ? pf.raw : nullptr);
+}
+
+// ---- the single-net training step (core/raycasters.py:99-104, 446-469) ------------------------------------------------------------
 // ONE net on ONE tape pass of P = n (S + N) rows: rows [0, n S) the coarse points, rows [n S, P) the new points in z_new order.
 // The forward is the renderer's (render_rays_single, pg_api.hip) with the activations kept: coarse stage on the first rows,
 // composite_kernel<CP_ISO> (is_only pdf, rank map, z_new written straight into the pass's depth array), the new points on the
 // rows behind, composite_kernel<CP_MERGE> over both.  The backward (train_backward) then runs ONE mlp_backward over the P rows.
-int train_forward_single(pg_handle* h, void* stream, int64_t n, const float* ray_batch, const float* skts, int64_t pose_stride,
-                         const float* cyls, int64_t cyl_stride, const float* cams, int S, int N, int flags, const pg_train_draws* dr,
-                         const pg_net_params* net, const pg_outputs* out, int64_t* tape_id) {
-    PG_HIP(h, hipSetDevice(h->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    Tape& t = *tape_of(h);
-    t.valid = false;
-    const int SF = S + N, fc = h->cfg.framecode_ch > 0;
-    const bool views0 = h->cfg.multires_views == 0, hier = N > 0;
-    const long long Pc = n * S, Pn = n * N, P = Pc + Pn;
-    const bool rnoise = dr && dr->ray_noise;
-    const bool bf = h->train_precision == PG_PREC_BF16;
-    const size_t es = bf ? 2 : 4;
-    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-    const int vcols_ = W + CH_D + (fc ? FC_CH : 0);
-    const size_t wsize[24] = {(size_t)W * CH_X, 0, (size_t)W * W, 0, (size_t)W * W, 0, (size_t)W * W, 0, (size_t)W * W, 0, (size_t)W * (CH_X + W), 0,
-                              (size_t)W * W, 0, (size_t)W * W, 0, 0, 0, (size_t)W * W, 0, (size_t)VW * vcols_, 0, 0, 0};     // (as pg_train_forward)
-    struct TB_ { int rows, cols, col0; };
-    const TB_ tblock[24] = {{0, 0, 0}, {}, {W, W, 0}, {}, {W, W, 0}, {}, {W, W, 0}, {}, {W, W, 0}, {}, {W, W, CH_X}, {}, {W, W, 0}, {}, {W, W, 0}, {}, {}, {},
-                            {W, W, 0}, {}, {VW, W, 0}, {}, {}, {}};
-    size_t need = al((size_t)n * 44) + al((size_t)n * 4) + al((size_t)n * 8) + al((size_t)n * S * 4) /*w0*/ + 4 * al((size_t)n * SF * 4) /*order, zf, noise1, Tb*/;
-    need += al((size_t)P * XW * es) + (DEPTH + 1) * al((size_t)P * W * es) + al((size_t)P * VW * es) + al((size_t)P * 16) + 2 * al((size_t)P * 4) + al((size_t)P * 12);
-    need += 2 * al((size_t)P * W * es) + al((size_t)P * VW * es) + al((size_t)P * FC_CH * 4) + al((size_t)P * 16) + (bf ? al((size_t)P * W * 4) : 0);
-    need += al(PART_FLOATS * 4) + al(RS_FLOATS * 4) + al((size_t)n * FC_CH * 4) + 2 * al((size_t)VW * vcols_ * 4);
-    if (bf) for (int i = 0; i < 24; ++i) need += al(wsize[i] * 2) + al((size_t)tblock[i].rows * tblock[i].cols * 2);
-    if (need > t.bytes) {
-        if (t.buf) { PG_HIP(h, hipDeviceSynchronize()); PG_HIP(h, hipFree(t.buf)); t.buf = nullptr; t.bytes = 0; }
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&t.buf), need);
-        if (e != hipSuccess) return pg_fail(h, PG_ENOMEM, "training tape of %zu bytes failed: %s", need, hipGetErrorString(e));
-        t.bytes = need;
-    }
-    uint8_t* q = t.buf;
-    auto take = [&](size_t b) { float* r = reinterpret_cast<float*>(q); q += al(b); return r; };
-    t.n = n; t.S = S; t.N = N; t.fc = fc; t.has_fine = false; t.bf16 = bf; t.single = true; t.views0 = views0;
-    t.rays = take((size_t)n * 44);
-    t.cams = cams ? take((size_t)n * 4) : (take((size_t)n * 4), nullptr);
-    float* nf = take((size_t)n * 8);
-    float* w0 = take((size_t)n * S * 4);
-    t.order = reinterpret_cast<int*>(take((size_t)n * SF * 4));
-    t.zf = take((size_t)n * SF * 4); t.noise1 = take((size_t)n * SF * 4); t.Tb = take((size_t)n * SF * 4);
-    t.pass[1] = Pass();
-    Pass& p = t.pass[0];
-    p = Pass();
-    p.P = P; p.S = S; p.P1 = Pc; p.S2 = N;
-    p.X = take((size_t)P * XW * es);
-    for (int l = 0; l < DEPTH; ++l) p.H[l] = take((size_t)P * W * es);
-    p.F = take((size_t)P * W * es);
-    p.G = take((size_t)P * VW * es);
-    p.raw = take((size_t)P * 16);
-    p.z = take((size_t)P * 4);
-    p.noise = take((size_t)P * 4);          // (noise0: the first n S entries)
-    p.pn = take((size_t)P * 12);
-    t.tmpA = take((size_t)P * W * es); t.tmpB = take((size_t)P * W * es);
-    t.dG = take((size_t)P * VW * es); t.dC = take((size_t)P * FC_CH * 4); t.d_raw = take((size_t)P * 16);
-    t.tmpF = bf ? take((size_t)P * W * 4) : nullptr;
-    t.vwide = take((size_t)VW * vcols_ * 4); t.gwide = take((size_t)VW * vcols_ * 4);
-    for (int i = 0; i < 24; ++i) {
-        t.wb[0][i] = (bf && wsize[i]) ? reinterpret_cast<bf16_t*>(take(wsize[i] * 2)) : nullptr;
-        t.wbT[0][i] = (bf && tblock[i].rows) ? reinterpret_cast<bf16_t*>(take((size_t)tblock[i].rows * tblock[i].cols * 2)) : nullptr;
-        t.wb[1][i] = t.wbT[1][i] = nullptr;
-    }
-    t.part = take(PART_FLOATS * 4); t.rs_part = take(RS_FLOATS * 4); t.ray_g = take((size_t)n * FC_CH * 4);
+int forward_single(const Step& a, Tape& t, const pg_net_params& net) {
+    pg_handle* h = a.h;
+    const pg_outputs* out = a.out;
+    const pg_train_draws* dr = a.dr;
+    const int S = a.S, N = a.N, SF = S + N;
+    const bool hier = N > 0;
     // the parameters the tape's GEMMs read: the caller's, with the view weight widened to the 4-band layout when the model has
     // no view frequencies (its [128, 256 + 72 (+16)] tensor stays the parameter)
-    pg_net_params eff = *net;
-    if (views0) {
-        pg_launch_widen_views(net->w[20], h->cfg.framecode_ch, t.vwide, stream);
+    t.params[0] = net;
+    if (t.views0) {
+        pg_launch_widen_views(net.w[20], h->cfg.framecode_ch, t.vwide, a.s);
         PG_LAUNCH_CHECK(h, "view weight widening");
-        eff.w[20] = t.vwide;
+        t.params[0].w[20] = t.vwide;
     }
-    if (bf) {
-        WJobs js{};
-        int nj = 0;
-        for (int i = 0; i < 24; ++i) {
-            if (!wsize[i]) continue;
-            if (nj + (tblock[i].rows ? 2 : 1) > WJOBS_MAX) return pg_fail(h, PG_EINVAL, "weight conversion: more than %d jobs", WJOBS_MAX);
-            js.j[nj++] = WJob{eff.w[i], t.wb[0][i], 0, 1, (int)wsize[i], 0};
-            if (tblock[i].rows) js.j[nj++] = WJob{eff.w[i] + tblock[i].col0, t.wbT[0][i], (long long)(wsize[i] / tblock[i].rows), tblock[i].rows, tblock[i].cols, 1};
-        }
-        hipLaunchKernelGGL(cvt_weights_kernel, dim3(64, nj), dim3(256), 0, s, js);
-        PG_LAUNCH_CHECK(h, "weight conversion");
-    }
-    t.params[0] = eff;
-    t.skts = skts; t.pose_stride = pose_stride; t.rnoise = rnoise; t.tau[0] = h->tau[0]; t.tau[1] = h->tau[1];
-    PG_HIP(h, hipMemcpyAsync(t.rays, ray_batch, (size_t)n * 44, hipMemcpyDeviceToDevice, s));
-    if (cams) PG_HIP(h, hipMemcpyAsync(t.cams, cams, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
-
-    Pass pc = sub_pass(p, 0, Pc, S, (int)es);
-    double* scs = nullptr;
-    { const int rc_ = pg_sc_scratch(h, n, h->cfg.chunk, &scs); if (rc_) return rc_; }
-    int e = pg_launch_sample_coarse(t.rays, cyls, cyl_stride, n, h->cfg.chunk, S, (flags & PG_FLAG_LINDISP) ? 1 : 0, nf, pc.z, dr ? dr->t_rand : nullptr, scs, stream);
-    if (e) return pg_fail(h, PG_EHIP, "coarse sampling launch failed: %s", hipGetErrorString((hipError_t)e));
-    if (dr && dr->noise0) PG_HIP(h, hipMemcpyAsync(p.noise, dr->noise0, (size_t)Pc * 4, hipMemcpyDeviceToDevice, s));
-    else p.noise = nullptr;
-    if (rnoise) {       // position noise of the coarse points: rows [:S] of every ray's draws
-        e = pg_launch_gather_noise(dr->ray_noise, n, SF, S, nullptr, pc.pn, stream);
-        if (e) return pg_fail(h, PG_EHIP, "noise gather launch failed: %s", hipGetErrorString((hipError_t)e));
-    }
-    auto embed = [&](const Pass& sp) {
-        const dim3 grid((unsigned)((sp.P * J + 255) / 256));
-        if (bf) hipLaunchKernelGGL(embed_rows_kernel<bf16_t>, grid, dim3(256), 0, s, t.rays, sp.z, rnoise ? sp.pn : nullptr, skts, (long long)pose_stride,
-                                   t.cams, net->codes, net->n_codes, fc, h->d_cut, h->tau[0], h->tau[1], sp.P, sp.S, static_cast<bf16_t*>(sp.X));
-        else hipLaunchKernelGGL(embed_rows_kernel<float>, grid, dim3(256), 0, s, t.rays, sp.z, rnoise ? sp.pn : nullptr, skts, (long long)pose_stride,
-                                t.cams, net->codes, net->n_codes, fc, h->d_cut, h->tau[0], h->tau[1], sp.P, sp.S, static_cast<float*>(sp.X));
-        return hipGetLastError();
-    };
-    if (embed(pc) != hipSuccess) return pg_fail(h, PG_EHIP, "embedding kernel launch failed");
-    PG_TRY(mlp_forward(h, s, t, 0, pc, eff, fc));
+    Pass pc;
+    PG_TRY(coarse_stage(a, t, pc));
+    const Pass& p = t.pass[0];
     const float ds = h->cfg.density_scale, eps = h->cfg.rgb_eps, shift = h->cfg.softplus_shift;
     const int act = h->cfg.density_act;
+    float* w0 = out->weights0 ? out->weights0 : t.w0;
     if (!hier) {
-        e = pg_launch_composite(t.rays, pc.z, pc.raw, n, S, ds, eps, act, shift, out->rgb_map, out->disp_map, out->acc_map, out->alpha,
-                                out->weights0 ? out->weights0 : w0, 0, nullptr, p.noise, nullptr, nullptr, stream);
-        if (e) return pg_fail(h, PG_EHIP, "composite launch failed: %s", hipGetErrorString((hipError_t)e));
-    } else {
-        Pass pn = sub_pass(p, Pc, Pn, N, (int)es);
-        e = pg_launch_composite_iso(t.rays, pc.z, pc.raw, n, S, ds, eps, act, shift, out->rgb0, out->disp0, out->acc0, out->alpha0,
-                                    out->weights0 ? out->weights0 : w0, N, t.zf, p.noise, dr ? dr->u_rand : nullptr, t.order, pn.z, N, stream);
-        if (e) return pg_fail(h, PG_EHIP, "composite launch failed: %s", hipGetErrorString((hipError_t)e));
-        if (rnoise) {   // the new points' noise: rows [S:] in z_samples order (sample_pts_is, raycasters.py:665-674)
-            e = pg_launch_gather_noise(dr->ray_noise + (size_t)S * 3, n, SF, N, nullptr, pn.pn, stream);
-            if (e) return pg_fail(h, PG_EHIP, "noise gather launch failed: %s", hipGetErrorString((hipError_t)e));
-        }
-        if (embed(pn) != hipSuccess) return pg_fail(h, PG_EHIP, "embedding kernel launch failed");
-        PG_TRY(mlp_forward(h, s, t, 0, pn, eff, fc));
-        if (dr && dr->noise1) PG_HIP(h, hipMemcpyAsync(t.noise1, dr->noise1, (size_t)n * SF * 4, hipMemcpyDeviceToDevice, s));
-        else t.noise1 = nullptr;
-        e = pg_launch_composite_merged(t.rays, t.zf, pc.raw, pn.raw, N, t.order, n, S, N, ds, eps, act, shift, out->rgb_map, out->disp_map,
-                                       out->acc_map, out->alpha, t.noise1, out->raw_fine, stream);
-        if (e) return pg_fail(h, PG_EHIP, "composite launch failed: %s", hipGetErrorString((hipError_t)e));
+        PG_TRY_LAUNCH(h, "composite", pg_launch_composite(t.rays, pc.z, pc.raw, a.n, S, ds, eps, act, shift, out->rgb_map, out->disp_map, out->acc_map,
+                                                          out->alpha, w0, 0, nullptr, p.noise, nullptr, nullptr, a.s));
+        return finish_step(a, t, pc, nullptr, nullptr);
     }
-    if (out->near_far) PG_HIP(h, hipMemcpyAsync(out->near_far, nf, (size_t)n * 8, hipMemcpyDeviceToDevice, s));
-    if (out->z_coarse) PG_HIP(h, hipMemcpyAsync(out->z_coarse, pc.z, (size_t)Pc * 4, hipMemcpyDeviceToDevice, s));
-    if (out->raw_coarse) PG_HIP(h, hipMemcpyAsync(out->raw_coarse, pc.raw, (size_t)Pc * 16, hipMemcpyDeviceToDevice, s));
-    if (hier && out->z_fine) PG_HIP(h, hipMemcpyAsync(out->z_fine, t.zf, (size_t)n * SF * 4, hipMemcpyDeviceToDevice, s));
-    t.valid = true;
-    t.generation += 1;
-    if (tape_id) *tape_id = t.generation;
+    Pass pn = sub_pass(p, p.P1, a.n * N, N, t.es());
+    PG_TRY_LAUNCH(h, "composite", pg_launch_composite_iso(t.rays, pc.z, pc.raw, a.n, S, ds, eps, act, shift, out->rgb0, out->disp0, out->acc0, out->alpha0,
+                                                          w0, N, t.zf, p.noise, dr ? dr->u_rand : nullptr, t.order, pn.z, N, a.s));
+    // the new points' noise: rows [S:] in z_samples order (sample_pts_is, raycasters.py:665-674)
+    if (t.rnoise) PG_TRY_LAUNCH(h, "noise gather", pg_launch_gather_noise(dr->ray_noise + (size_t)S * 3, a.n, SF, N, nullptr, pn.pn, a.s));
+    PG_TRY(launch_embed(h, a.s, t, pn, net.codes, net.n_codes));
+    PG_TRY(mlp_forward(h, a.s, t, 0, pn, t.params[0], t.fc));
+    if (dr && dr->noise1) PG_HIP(h, hipMemcpyAsync(t.noise1, dr->noise1, (size_t)a.n * SF * 4, hipMemcpyDeviceToDevice, a.s));
+    else t.noise1 = nullptr;
+    PG_TRY_LAUNCH(h, "composite", pg_launch_composite_merged(t.rays, t.zf, pc.raw, pn.raw, N, t.order, a.n, S, N, ds, eps, act, shift, out->rgb_map,
+                                                             out->disp_map, out->acc_map, out->alpha, t.noise1, out->raw_fine, a.s));
+    return finish_step(a, t, pc, t.zf, nullptr);
+}
+
+// one pass's share of every ray's 4 x 4s: S points per ray at the depths z with the noise rows pn, the input gradients dX;
+// add = 0 writes per_ray, 1 adds to it
+int launch_embed_bwd(pg_handle* h, hipStream_t s, const Tape& t, int S, const float* z, const float* pn, const float* dX, float* per_ray, int add) {
+    hipLaunchKernelGGL(embed_bwd_kernel, dim3((unsigned)((t.n * J + 255) / 256)), dim3(256), 0, s, t.rays, z, t.rnoise ? pn : nullptr, t.skts,
+                       t.pose_stride, h->d_cut, t.tau[0], t.tau[1], (long long)t.n, S, dX, per_ray, add);
+    PG_LAUNCH_CHECK(h, "embedding backward");
     return PG_OK;
 }
 
@@ -1886,147 +2055,11 @@ int pg_train_forward(pg_handle* h, void* stream, int64_t n, const float* ray_bat
         for (int i = 0; i < 24; ++i) if (!p->w[i]) return pg_fail(h, PG_EINVAL, "pg_train_forward: parameter tensor %d of net %d is null", i, k);
         if (fc && (!p->codes || p->n_codes <= 0)) return pg_fail(h, PG_EINVAL, "pg_train_forward: frame codes of net %d missing", k);
     }
-    if (single)         // one net, S + N rows per ray on one tape pass (`fine` is not read: network_fine is network)
-        return train_forward_single(h, stream, n, ray_batch, skts, pose_stride, cyls, cyl_stride, cams, S, N, flags, dr, coarse, out, tape_id);
-    PG_HIP(h, hipSetDevice(h->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
+    const Step a{h, static_cast<hipStream_t>(stream), n, pose_stride, cyl_stride, ray_batch, skts, cyls, cams, S, N, flags, dr, out, tape_id};
     Tape& t = *tape_of(h);
-    t.valid = false;
-    // carve the tape
-    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-    const long long Pc = n * S, Pf = N > 0 ? n * SF : 0, Pm = std::max(Pc, Pf);
-    const bool rnoise = dr && dr->ray_noise;
-    size_t need = al((size_t)n * 44) + al((size_t)n * 4) + al((size_t)n * 8) + al((size_t)n * S * 4) /*w0*/ + al((size_t)n * SF * 4) /*order*/;
-    const bool bf = h->train_precision == PG_PREC_BF16;     // 16-bit mode (pg_set_train_precision): the tape's activations and their gradients are bf16 arrays
-    const size_t es = bf ? 2 : 4;
-    auto pass_bytes = [&](long long P) {
-        return al((size_t)P * XW * es) + (DEPTH + 1) * al((size_t)P * W * es) + al((size_t)P * VW * es) + al((size_t)P * 16) + 2 * al((size_t)P * 4) + al((size_t)P * 12);
-    };
-    need += pass_bytes(Pc) + (N > 0 ? pass_bytes(Pf) : 0);
-    need += 2 * al((size_t)Pm * W * es) + al((size_t)Pm * VW * es) + al((size_t)Pm * FC_CH * 4) + al((size_t)Pm * 16) + (bf ? al((size_t)Pm * W * 4) : 0);
-    need += al(PART_FLOATS * 4) + al(RS_FLOATS * 4) + al((size_t)n * FC_CH * 4);
-    const int vcols_ = W + CH_D + (fc ? FC_CH : 0);
-    const size_t wsize[24] = {(size_t)W * CH_X, 0, (size_t)W * W, 0, (size_t)W * W, 0, (size_t)W * W, 0, (size_t)W * W, 0, (size_t)W * (CH_X + W), 0,
-                              (size_t)W * W, 0, (size_t)W * W, 0, 0, 0, (size_t)W * W, 0, (size_t)VW * vcols_, 0, 0, 0};     // the large GEMMs' weight matrices
-    // blocks of the weight matrices the dX GEMMs multiply by: (rows = out, cols = in, first column); layer 0 has no dX
-    struct TB_ { int rows, cols, col0; };
-    const TB_ tblock[24] = {{0, 0, 0}, {}, {W, W, 0}, {}, {W, W, 0}, {}, {W, W, 0}, {}, {W, W, 0}, {}, {W, W, CH_X}, {}, {W, W, 0}, {}, {W, W, 0}, {}, {}, {},
-                            {W, W, 0}, {}, {VW, W, 0}, {}, {}, {}};
-    if (bf) for (int i = 0; i < 24; ++i) need += 2 * al(wsize[i] * 2) + 2 * al((size_t)tblock[i].rows * tblock[i].cols * 2);
-    if (need > t.bytes) {
-        if (t.buf) { PG_HIP(h, hipDeviceSynchronize()); PG_HIP(h, hipFree(t.buf)); t.buf = nullptr; t.bytes = 0; }
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&t.buf), need);
-        if (e != hipSuccess) return pg_fail(h, PG_ENOMEM, "training tape of %zu bytes failed: %s", need, hipGetErrorString(e));
-        t.bytes = need;
-    }
-    uint8_t* q = t.buf;
-    auto take = [&](size_t b) { float* r = reinterpret_cast<float*>(q); q += al(b); return r; };
-    t.n = n; t.S = S; t.N = N; t.fc = fc; t.has_fine = N > 0;
-    t.bf16 = bf;
-    t.rays = take((size_t)n * 44);
-    t.cams = cams ? take((size_t)n * 4) : (take((size_t)n * 4), nullptr);
-    float* nf = take((size_t)n * 8);
-    float* w0 = take((size_t)n * S * 4);
-    int* order = reinterpret_cast<int*>(take((size_t)n * SF * 4));
-    for (int k = 0; k < 2; ++k) {
-        Pass& p = t.pass[k];
-        p = Pass();
-        if (k == 1 && N == 0) break;
-        p.P = k ? Pf : Pc; p.S = k ? SF : S;
-        p.X = take((size_t)p.P * XW * es);
-        for (int l = 0; l < DEPTH; ++l) p.H[l] = take((size_t)p.P * W * es);
-        p.F = take((size_t)p.P * W * es);
-        p.G = take((size_t)p.P * VW * es);
-        p.raw = take((size_t)p.P * 16);
-        p.z = take((size_t)p.P * 4);
-        p.noise = take((size_t)p.P * 4);
-        p.pn = take((size_t)p.P * 12);
-    }
-    t.tmpA = take((size_t)Pm * W * es); t.tmpB = take((size_t)Pm * W * es);
-    t.dG = take((size_t)Pm * VW * es); t.dC = take((size_t)Pm * FC_CH * 4); t.d_raw = take((size_t)Pm * 16);
-    t.tmpF = bf ? take((size_t)Pm * W * 4) : nullptr;
-    for (int k = 0; k < 2; ++k)
-        for (int i = 0; i < 24; ++i) {
-            t.wb[k][i] = (bf && wsize[i]) ? reinterpret_cast<bf16_t*>(take(wsize[i] * 2)) : nullptr;
-            t.wbT[k][i] = (bf && tblock[i].rows) ? reinterpret_cast<bf16_t*>(take((size_t)tblock[i].rows * tblock[i].cols * 2)) : nullptr;
-        }
-    if (bf) {       // this step's bf16 copies of the weight matrices (the parameters do not change between forward and backward): one launch
-        WJobs js{};
-        int nj = 0;
-        for (int k = 0; k < (N > 0 ? 2 : 1); ++k)
-            for (int i = 0; i < 24; ++i) {
-                if (!wsize[i]) continue;
-                const float* src = (k ? fine : coarse)->w[i];
-                if (nj + (tblock[i].rows ? 2 : 1) > WJOBS_MAX) return pg_fail(h, PG_EINVAL, "weight conversion: more than %d jobs", WJOBS_MAX);
-                js.j[nj++] = WJob{src, t.wb[k][i], 0, 1, (int)wsize[i], 0};
-                if (tblock[i].rows) {
-                    const long long ldw = (long long)(wsize[i] / tblock[i].rows);       // (= the matrix's column count)
-                    js.j[nj++] = WJob{src + tblock[i].col0, t.wbT[k][i], ldw, tblock[i].rows, tblock[i].cols, 1};
-                }
-            }
-        hipLaunchKernelGGL(cvt_weights_kernel, dim3(64, nj), dim3(256), 0, s, js);
-        PG_LAUNCH_CHECK(h, "weight conversion");
-    }
-    t.part = take(PART_FLOATS * 4); t.rs_part = take(RS_FLOATS * 4); t.ray_g = take((size_t)n * FC_CH * 4);
-    t.params[0] = *coarse;
-    if (N > 0) t.params[1] = *fine;
-    t.skts = skts; t.pose_stride = pose_stride; t.rnoise = rnoise; t.tau[0] = h->tau[0]; t.tau[1] = h->tau[1];
-    PG_HIP(h, hipMemcpyAsync(t.rays, ray_batch, (size_t)n * 44, hipMemcpyDeviceToDevice, s));
-    if (cams) PG_HIP(h, hipMemcpyAsync(t.cams, cams, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
-
-    // frame codes: [n_codes + 1, 16], the caller appends the mean row (embedding.py:25-26) that a negative index selects
-    const float* codes_dev[2] = {coarse->codes, N > 0 ? fine->codes : nullptr};
-
-    Pass& pc = t.pass[0];
-    double* scs = nullptr;
-    { const int rc_ = pg_sc_scratch(h, n, h->cfg.chunk, &scs); if (rc_) return rc_; }
-    int e = pg_launch_sample_coarse(t.rays, cyls, cyl_stride, n, h->cfg.chunk, S, (flags & PG_FLAG_LINDISP) ? 1 : 0, nf, pc.z, dr ? dr->t_rand : nullptr, scs, stream);
-    if (e) return pg_fail(h, PG_EHIP, "coarse sampling launch failed: %s", hipGetErrorString((hipError_t)e));
-    if (dr && dr->noise0) PG_HIP(h, hipMemcpyAsync(pc.noise, dr->noise0, (size_t)Pc * 4, hipMemcpyDeviceToDevice, s));
-    if (rnoise) {
-        e = pg_launch_gather_noise(dr->ray_noise, n, SF, S, nullptr, pc.pn, stream);
-        if (e) return pg_fail(h, PG_EHIP, "noise gather launch failed: %s", hipGetErrorString((hipError_t)e));
-    }
-    auto embed = [&](Pass& p, const float* codes, int n_codes) {
-        const dim3 grid((unsigned)((p.P * J + 255) / 256));
-        if (bf) hipLaunchKernelGGL(embed_rows_kernel<bf16_t>, grid, dim3(256), 0, s, t.rays, p.z, rnoise ? p.pn : nullptr, skts, (long long)pose_stride,
-                                   t.cams, codes, n_codes, fc, h->d_cut, h->tau[0], h->tau[1], p.P, p.S, static_cast<bf16_t*>(p.X));
-        else hipLaunchKernelGGL(embed_rows_kernel<float>, grid, dim3(256), 0, s, t.rays, p.z, rnoise ? p.pn : nullptr, skts, (long long)pose_stride,
-                                t.cams, codes, n_codes, fc, h->d_cut, h->tau[0], h->tau[1], p.P, p.S, static_cast<float*>(p.X));
-        return hipGetLastError();
-    };
-    if (embed(pc, codes_dev[0], coarse->n_codes) != hipSuccess) return pg_fail(h, PG_EHIP, "embedding kernel launch failed");
-    PG_TRY(mlp_forward(h, s, t, 0, pc, *coarse, fc));
-    const bool hier = N > 0;
-    e = pg_launch_composite(t.rays, pc.z, pc.raw, n, S, h->cfg.density_scale, h->cfg.rgb_eps, h->cfg.density_act, h->cfg.softplus_shift, hier ? out->rgb0 : out->rgb_map,
-                            hier ? out->disp0 : out->disp_map, hier ? out->acc0 : out->acc_map, hier ? out->alpha0 : out->alpha,
-                            out->weights0 ? out->weights0 : w0, N, hier ? t.pass[1].z : nullptr, (dr && dr->noise0) ? pc.noise : nullptr,
-                            dr ? dr->u_rand : nullptr, (rnoise && hier) ? order : nullptr, stream);
-    if (e) return pg_fail(h, PG_EHIP, "composite launch failed: %s", hipGetErrorString((hipError_t)e));
-    if (!(dr && dr->noise0)) pc.noise = nullptr;
-    if (hier) {
-        Pass& pf = t.pass[1];
-        if (dr && dr->noise1) PG_HIP(h, hipMemcpyAsync(pf.noise, dr->noise1, (size_t)Pf * 4, hipMemcpyDeviceToDevice, s));
-        else pf.noise = nullptr;
-        if (rnoise) {
-            e = pg_launch_gather_noise(dr->ray_noise, n, SF, SF, order, pf.pn, stream);
-            if (e) return pg_fail(h, PG_EHIP, "noise gather launch failed: %s", hipGetErrorString((hipError_t)e));
-        }
-        if (embed(pf, codes_dev[1], fine->n_codes) != hipSuccess) return pg_fail(h, PG_EHIP, "embedding kernel launch failed");
-        PG_TRY(mlp_forward(h, s, t, 1, pf, *fine, fc));
-        e = pg_launch_composite(t.rays, pf.z, pf.raw, n, SF, h->cfg.density_scale, h->cfg.rgb_eps, h->cfg.density_act, h->cfg.softplus_shift, out->rgb_map, out->disp_map, out->acc_map,
-                                out->alpha, nullptr, 0, nullptr, pf.noise, nullptr, nullptr, stream);
-        if (e) return pg_fail(h, PG_EHIP, "composite launch failed: %s", hipGetErrorString((hipError_t)e));
-    }
-    if (out->near_far) PG_HIP(h, hipMemcpyAsync(out->near_far, nf, (size_t)n * 8, hipMemcpyDeviceToDevice, s));
-    if (out->z_coarse) PG_HIP(h, hipMemcpyAsync(out->z_coarse, pc.z, (size_t)Pc * 4, hipMemcpyDeviceToDevice, s));
-    if (out->raw_coarse) PG_HIP(h, hipMemcpyAsync(out->raw_coarse, pc.raw, (size_t)Pc * 16, hipMemcpyDeviceToDevice, s));
-    if (hier && out->z_fine) PG_HIP(h, hipMemcpyAsync(out->z_fine, t.pass[1].z, (size_t)Pf * 4, hipMemcpyDeviceToDevice, s));
-    if (hier && out->raw_fine) PG_HIP(h, hipMemcpyAsync(out->raw_fine, t.pass[1].raw, (size_t)Pf * 16, hipMemcpyDeviceToDevice, s));
-    t.valid = true;
-    t.generation += 1;
-    if (tape_id) *tape_id = t.generation;
-    return PG_OK;
+    PG_TRY(tape_begin(a, t));
+    // one net, S + N rows per ray on one tape pass (`fine` is not read: network_fine is network), or two
+    return single ? forward_single(a, t, *coarse) : forward_two_nets(a, t, *coarse, fine);
 }
 
 // the backward of both entries; d_skts null: no pose gradient (the kernels of pg_train_backward, nothing else)
@@ -2050,12 +2083,7 @@ static int train_backward(pg_handle* h, void* stream, int64_t tape_id, const flo
         const long long Pm = std::max(t.pass[0].P, t.pass[1].P);
         const size_t dx_bytes = ((size_t)Pm * DXW * 4 + 255) & ~size_t(255);
         const size_t need = dx_bytes + (d_pose_stride == 0 ? (size_t)t.n * J * 16 * 4 : 0);
-        if (need > t.pbytes) {
-            if (t.pbuf) { PG_HIP(h, hipDeviceSynchronize()); PG_HIP(h, hipFree(t.pbuf)); t.pbuf = nullptr; t.pbytes = 0; }
-            hipError_t e = hipMalloc(reinterpret_cast<void**>(&t.pbuf), need);
-            if (e != hipSuccess) return pg_fail(h, PG_ENOMEM, "pose gradient workspace of %zu bytes failed: %s", need, hipGetErrorString(e));
-            t.pbytes = need;
-        }
+        PG_TRY(grow(h, t.pbuf, t.pbytes, need, "pose gradient workspace"));
         dX = reinterpret_cast<float*>(t.pbuf);
         per_ray = d_pose_stride == 0 ? reinterpret_cast<float*>(t.pbuf + dx_bytes) : d_skts;
     }
@@ -2079,42 +2107,28 @@ static int train_backward(pg_handle* h, void* stream, int64_t tape_id, const flo
             PG_LAUNCH_CHECK(h, "view gradient narrowing");
         }
         if (pose) {     // a ray's S coarse points write its 4 x 4s, its N new points (their own depths and noise rows) add theirs
-            const dim3 grid((unsigned)((t.n * J + 255) / 256));
-            hipLaunchKernelGGL(embed_bwd_kernel, grid, dim3(256), 0, s, t.rays, p.z, t.rnoise ? p.pn : nullptr, t.skts, t.pose_stride, h->d_cut,
-                               t.tau[0], t.tau[1], (long long)t.n, t.S, dX, per_ray, 0);
-            PG_LAUNCH_CHECK(h, "embedding backward");
-            if (hier) {
-                hipLaunchKernelGGL(embed_bwd_kernel, grid, dim3(256), 0, s, t.rays, p.z + p.P1, t.rnoise ? p.pn + p.P1 * 3 : nullptr, t.skts,
-                                   t.pose_stride, h->d_cut, t.tau[0], t.tau[1], (long long)t.n, t.N, dX + p.P1 * DXW, per_ray, 1);
-                PG_LAUNCH_CHECK(h, "embedding backward");
-            }
-            if (d_pose_stride == 0) {
-                hipLaunchKernelGGL(reduce_parts_kernel, dim3((unsigned)((J * 16 + 255) / 256)), dim3(256), 0, s, per_ray, (int)t.n, 1, J * 16, d_skts, (long long)(J * 16));
-                PG_LAUNCH_CHECK(h, "pose gradient reduction");
-            }
+            PG_TRY(launch_embed_bwd(h, s, t, t.S, p.z, p.pn, dX, per_ray, 0));
+            if (hier) PG_TRY(launch_embed_bwd(h, s, t, t.N, p.z + p.P1, p.pn + p.P1 * 3, dX + p.P1 * DXW, per_ray, 1));
         }
-        return PG_OK;
-    }
-    bool first = true;
-    auto run = [&](int k, const float* d_rgb, const float* d_acc, const pg_net_grads& g) -> int {
-        const Pass& p = t.pass[k];
-        hipLaunchKernelGGL(composite_bwd_kernel, dim3((unsigned)((t.n + 63) / 64)), dim3(64), 0, s, t.rays, p.z, p.raw, p.noise, (long long)t.n, p.S,
-                           h->cfg.density_scale, h->cfg.rgb_eps, h->cfg.density_act, h->cfg.softplus_shift, d_rgb, d_acc, t.d_raw);
-        PG_LAUNCH_CHECK(h, "composite backward");
-        PG_TRY(mlp_backward(h, s, t, k, p, t.params[k], g, dX));
-        if (pose) {         // this pass's share of every ray's 4 x 4s: the fine pass writes them, the coarse pass adds its own
-            hipLaunchKernelGGL(embed_bwd_kernel, dim3((unsigned)((t.n * J + 255) / 256)), dim3(256), 0, s, t.rays, p.z, t.rnoise ? p.pn : nullptr,
-                               t.skts, t.pose_stride, h->d_cut, t.tau[0], t.tau[1], (long long)t.n, p.S, dX, per_ray, first ? 0 : 1);
-            PG_LAUNCH_CHECK(h, "embedding backward");
-            first = false;
-        }
-        return PG_OK;
-    };
-    if (t.has_fine) {
-        PG_TRY(run(1, d_rgb_map, d_acc_map, *fine));
-        PG_TRY(run(0, d_rgb0, d_acc0, *coarse));
     } else {
-        PG_TRY(run(0, d_rgb_map, d_acc_map, *coarse));
+        bool first = true;
+        auto run = [&](int k, const float* d_rgb, const float* d_acc, const pg_net_grads& g) -> int {
+            const Pass& p = t.pass[k];
+            hipLaunchKernelGGL(composite_bwd_kernel, dim3((unsigned)((t.n + 63) / 64)), dim3(64), 0, s, t.rays, p.z, p.raw, p.noise, (long long)t.n, p.S,
+                               h->cfg.density_scale, h->cfg.rgb_eps, h->cfg.density_act, h->cfg.softplus_shift, d_rgb, d_acc, t.d_raw);
+            PG_LAUNCH_CHECK(h, "composite backward");
+            PG_TRY(mlp_backward(h, s, t, k, p, t.params[k], g, dX));
+            // this pass's share of every ray's 4 x 4s: the fine pass writes them, the coarse pass adds its own
+            if (pose) PG_TRY(launch_embed_bwd(h, s, t, p.S, p.z, p.pn, dX, per_ray, first ? 0 : 1));
+            first = false;
+            return PG_OK;
+        };
+        if (t.has_fine) {
+            PG_TRY(run(1, d_rgb_map, d_acc_map, *fine));
+            PG_TRY(run(0, d_rgb0, d_acc0, *coarse));
+        } else {
+            PG_TRY(run(0, d_rgb_map, d_acc_map, *coarse));
+        }
     }
     if (pose && d_pose_stride == 0) {      // the sum over the rays, in ray order (slices of reduce_parts_kernel)
         hipLaunchKernelGGL(reduce_parts_kernel, dim3((unsigned)((J * 16 + 255) / 256)), dim3(256), 0, s, per_ray, (int)t.n, 1, J * 16, d_skts, (long long)(J * 16));
