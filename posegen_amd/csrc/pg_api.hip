@@ -168,49 +168,135 @@ void host_copy(NetState& ns, const float* const* tensors, const int64_t* shapes,
     }
 }
 
-// ... of a handle's net: first the host copies are brought up to date if the last weights came from the device
-// (pg_load_weights_device leaves them stale: only the images it re-forms itself are current)
-int refresh_host(pg_handle* h, NetState& ns) {
-    if (!ns.host_stale) return PG_OK;
-    pgpack::NetTensors lay;
-    lay.layout(h->cfg.framecode_ch);
-    PG_HIP(h, hipSetDevice(h->device));
-    PG_HIP(h, hipDeviceSynchronize());
-    for (int i = 0; i < 24; ++i)
-        PG_HIP(h, hipMemcpy(ns.host[i].data(), ns.d_src + lay.off[i], ns.host[i].size() * sizeof(float), hipMemcpyDeviceToHost));
-    ns.fold_w.clear(); ns.fold_b.clear();
-    if (ns.d_codes && !ns.codes_host.empty())
-        PG_HIP(h, hipMemcpy(ns.codes_host.data(), ns.d_codes, ns.codes_host.size() * sizeof(float), hipMemcpyDeviceToHost));
-    ns.host_stale = false;
-    std::vector<float> bias;
-    pgpack::pack_bias(tensors_of(ns, h->cfg), bias);
-    if (!ns.d_bias) PG_HIP(h, hipMalloc(reinterpret_cast<void**>(&ns.d_bias), BIAS_FLOATS * sizeof(float)));
-    PG_HIP(h, hipMemcpy(ns.d_bias, bias.data(), BIAS_FLOATS * sizeof(float), hipMemcpyHostToDevice));
-    return PG_OK;
+// ---- which form of the fused kernel a call runs (pick_form), and what each form reads (FORMS) ---------------------------
+enum Form {
+    F_DIRECT16,         // pg_eval16.hip: bf16 / fp16, 32x32x16 MFMAs, direct view layer
+    F_REC16,            // pg_eval16r.hip: bf16 / fp16, 16x16x32 MFMAs, the view layer factorised over per-ray records (pg_rayrec.hip)
+    F_ONCHIP16,         // ... its on-chip variant: no per-ray records
+    F_C2,               // pg_evalc2.hip: compensated fp16, the out tiles split over the waves
+    F_COMP_DIRECT,      // pg_evalc.hip: compensated fp16, direct view layer
+    F_COMP_REC,         // ... record variant (per-ray records of ray_records_c_kernel)
+    F_COMP_ONCHIP,      // ... on-chip form of the record variant (one pose per launch, no frame codes)
+    F_KMAJOR,           // pg_eval32.hip, k-major: fp32, the split-operand precisions, and PG_PREC_FP16C where pg_evalc*.hip do not run
+    F_COUNT
+};
+
+// The process's switches (A/B, debugging), read once; "0" turns a form off
+struct Switches {
+    bool view_fact = true;          // POSEGEN_VIEW_FACT=0: the direct 32x32x16 kernel (pg_eval16.hip) for every 16-bit call
+    bool comp_kernel = true;        // POSEGEN_COMP_KERNEL=0: PG_PREC_FP16C in the k-major kernel of pg_eval32.hip, same arithmetic
+    bool comp_rec = true;           // POSEGEN_COMP_REC=0: the direct form of pg_evalc.hip whatever the sample count
+    bool evalc2 = true;             // POSEGEN_EVALC2=0: keeps fp16c calls on pg_evalc.hip (and the record / on-chip forms' tests)
+    int onchip = PG_ONCHIP_AUTO;    // POSEGEN_ONCHIP = 0 / 1 / 2: the pg_set_onchip mode a new handle starts in
+};
+const Switches& switches() {
+    static const Switches sw = [] {
+        auto off = [](const char* name) { const char* e = std::getenv(name); return e && e[0] == '0'; };
+        Switches s;
+        s.view_fact = !off("POSEGEN_VIEW_FACT");
+        s.comp_kernel = !off("POSEGEN_COMP_KERNEL");
+        s.comp_rec = !off("POSEGEN_COMP_REC");
+        s.evalc2 = !off("POSEGEN_EVALC2");
+        const char* e = std::getenv("POSEGEN_ONCHIP");
+        s.onchip = e && e[0] == '0' ? PG_ONCHIP_RECORDS : e && e[0] == '2' ? PG_ONCHIP_ALWAYS : PG_ONCHIP_AUTO;
+        return s;
+    }();
+    return sw;
 }
 
-// The 16-bit precisions factorise the view layer over rays when a pass cannot touch more than MAXR_F rays
-// (pg_layout.h): per-ray records (pg_rayrec.hip) + the 16x16x32 kernel (pg_eval16r.hip); POSEGEN_VIEW_FACT=0
-// forces the direct 32x32x16 kernel (pg_eval16.hip) everywhere (A/B, debugging).
-bool use_fact(int prec, int S) {
-    static const bool allowed = [] { const char* e = std::getenv("POSEGEN_VIEW_FACT"); return !(e && e[0] == '0'); }();
-    return allowed && is_shape_a(prec) && S >= FACT_MIN_S;
+// what pick_form looks at
+struct CallFacts {
+    int prec;                       // kernel arithmetic of the pass (pass_precision)
+    int S;                          // samples per ray
+    long long pose_stride;          // 0: one pose per launch
+    bool fc;                        // the config has frame codes
+    bool points, pnoise;            // explicit points / position noise
+    bool dbg; int dbg_stage;        // debug buffer given, and what it asks for
+    int onchip_mode;                // pg_set_onchip
+};
+
+// PG_PREC_FP16M: the coarse pass of a hierarchical render only places the importance samples (and fills
+// rgb0/acc0): plain fp16 there, compensated fp16 wherever the pass produces the returned maps
+int pass_precision(int mode, bool guide_pass) { return mode == PG_PREC_FP16M ? (guide_pass ? PG_PREC_FP16 : PG_PREC_FP16C) : mode; }
+
+// The on-chip variants run for rays of at most ONCHIP_MAX_S samples.  The 16x16x32 kernel's on-chip variant takes per-ray poses and
+// frame codes too; pg_evalc.hip's on-chip form needs one pose per launch and no frame codes and has no sample-count rule.
+// The on-chip variant forms a ray's rows in every pass the ray has points in, the record variant once
+// per ray in a kernel in front: measured on one box (profiles/r5_ab_onchip_by_samples.txt, bf16 512 x 512 frames) the two
+// tie at 64 + 16 samples (31.7 / 31.8 ms), on-chip wins at 96 + 16 (43.3 / 43.6) and records win from 128 + 16 on (59.3 /
+// 58.0; with frame codes 59.7 / 58.2) -- at a cost of 8.75 KiB of HBM per ray.  pg_set_onchip (initial value: POSEGEN_ONCHIP = 0 / 1 / 2)
+// forces the record variants (0) or the on-chip ones whatever the sample count (2).
+constexpr int ONCHIP_MAX_S = 112;
+
+// The one place that decides the form.  Pure: exercised over the whole product of its facts on the host.
+Form pick_form(const CallFacts& c, const Switches& sw) {
+    // explicit points and position noise need q = R p + t per point: the direct kernels (no per-ray a + z b table)
+    const bool from_rays = !c.points && !c.pnoise;
+    if (is_shape_a(c.prec)) {
+        // the 16-bit precisions factorise the view layer over rays when a pass cannot touch more than MAXR_F rays (pg_layout.h)
+        if (!(from_rays && sw.view_fact && c.S >= FACT_MIN_S)) return F_DIRECT16;
+        const bool by_mode = c.onchip_mode == PG_ONCHIP_ALWAYS || (c.onchip_mode == PG_ONCHIP_AUTO && c.S <= ONCHIP_MAX_S);
+        const bool dbg_ok = !c.dbg || (c.dbg_stage == 97 && c.pose_stride == 0 && !c.fc);     // (97: the on-chip variant's limb-mask counters)
+        return by_mode && dbg_ok ? F_ONCHIP16 : F_REC16;
+    }
+    // PG_PREC_FP16C runs in its dedicated kernels when a ray has >= COMP_MIN_S samples (then a 128-point pass touches
+    // <= MAXR_C rays) and the points come from rays; otherwise in the k-major kernel of pg_eval32.hip, same arithmetic
+    if (!(c.prec == PG_PREC_FP16C && from_rays && sw.comp_kernel && c.S >= COMP_MIN_S)) return F_KMAJOR;
+    // >= pgp::T::MIN_S samples per ray: out tiles over the waves (pg_evalc2.hip), whatever the pose stride, with or without frame codes
+    if (sw.evalc2 && c.S >= pgp::T::MIN_S && (!c.dbg || c.dbg_stage == 99 || c.dbg_stage == 97)) return F_C2;
+    // pg_evalc.hip: its record variant when a ray has >= FACT_MIN_S samples, that variant's on-chip form where it applies
+    if (!(sw.comp_rec && c.S >= FACT_MIN_S)) return F_COMP_DIRECT;
+    const bool plain = c.onchip_mode != PG_ONCHIP_RECORDS && !c.fc && c.pose_stride == 0;
+    const bool dbg_ok = !c.dbg || c.dbg_stage == 98 || c.dbg_stage == 99;                     // (98 / 99: diagnosis builds' dumps)
+    return plain && dbg_ok ? F_COMP_ONCHIP : F_COMP_REC;
 }
 
-// PG_PREC_FP16C runs in its dedicated kernel (pg_evalc.hip) when a ray has >= COMP_MIN_S samples (then a
-// 128-point pass touches <= MAXR_C rays) and the points come from rays; otherwise (and with
-// POSEGEN_COMP_KERNEL=0, for A/B) in the k-major kernel of pg_eval32.hip, same arithmetic.
-bool use_comp_kernel(int prec, int S, bool points) {
-    static const bool allowed = [] { const char* e = std::getenv("POSEGEN_COMP_KERNEL"); return !(e && e[0] == '0'); }();
-    return allowed && prec == PG_PREC_FP16C && !points && S >= COMP_MIN_S;
+// the usual call of a precision: rays with >= 64 samples, one pose per launch, no points, no noise, no debug.  Its form is what
+// pg_load_weights packs ahead of the first render (ensure_mode_streams) and what pg_query reports
+Form usual_form(const pg_handle* h, int prec) {
+    return pick_form(CallFacts{prec, FACT_MIN_S, 0, h->cfg.framecode_ch > 0, false, false, false, 0, h->onchip_mode}, switches());
 }
 
-// ... and in that kernel's record variant when a ray has >= FACT_MIN_S samples (per-ray records of
-// ray_records_c_kernel instead of the direct view layer); POSEGEN_COMP_REC=0 forces the direct form (A/B).
-bool use_comp_rec(int S) {
-    static const bool allowed = [] { const char* e = std::getenv("POSEGEN_COMP_REC"); return !(e && e[0] == '0'); }();
-    return allowed && S >= FACT_MIN_S;
-}
+int one_wg_per_cu(void) { return 1; }
+
+struct FormInfo {
+    int stream;                     // image the kernel streams (a per-precision kind: image_of adds the pass's precision)
+    int wy;                         // Y-stage weights of the record kernel in front, or the Yc table (IMG_YCODE: with frame codes only)
+    int bias;                       // IMG_BIAS or IMG_BIAS16
+    int rec_y_bytes;                // per-ray records: bytes of Y per ray (0: no record kernel)
+    int (*points_per_pass)(void);
+    int (*wgs_per_cu)(void);
+    // pg_query: weight bytes a pass reads; MFMAs per 32-point group in 32x32x16 equivalents (32 768 FLOP each)
+    int64_t (*stream_bytes)(int prec);
+    int64_t (*mfma_per_group)(int prec, bool fc);
+};
+// the fp32 / split kernels keep feature_linear and the direct view layer (13 + 4 out tiles)
+constexpr int64_t mfma_direct(bool fc) { return pgp::A::MFMA_PER_GROUP(fc) + (NT + 1 + NTV - (NTV + 1)) * pgp::A::HU; }
+#define PG_CHUNKS(n) [](int) -> int64_t { return (int64_t)(n) * CHUNK_BYTES; }
+#define PG_MFMA(expr) [](int prec, bool fc) -> int64_t { (void)prec; (void)fc; return (expr); }
+constexpr FormInfo FORMS[F_COUNT] = {
+    /* F_DIRECT16    */ {IMG_DIRECT, IMG_NONE, IMG_BIAS, 0, pg_eval16_points_per_pass, pg_eval16_wgs_per_cu,
+                         PG_CHUNKS(pgp::A::NCHUNK), PG_MFMA(pgp::A::MFMA_PER_GROUP(fc))},
+    /* F_REC16       */ {IMG_REC16, IMG_VY16, IMG_BIAS16, REC_Y_BYTES, pg_eval16_points_per_pass, pg_eval16_wgs_per_cu,
+                         PG_CHUNKS(pgp::R::NCHUNK), PG_MFMA(pgp::R::MFMA16_PER_GROUP / 2)},
+    /* F_ONCHIP16    */ {IMG_ONCHIP16, IMG_YCODE, IMG_BIAS16, 0, pg_eval16_points_per_pass, pg_eval16_wgs_per_cu,
+                         PG_CHUNKS(pgp::R::NCHUNK_OC), PG_MFMA(pgp::R::MFMA16_PER_GROUP / 2)},
+    /* F_C2 (no stream: the whole image) */
+                        {IMG_C2, IMG_NONE, IMG_BIAS16, 0, pg_evalc2_points_per_pass, one_wg_per_cu,
+                         [](int) -> int64_t { return pgp::T::TOTAL; }, PG_MFMA(pgp::T::MFMA16_PER_PASS / 2 / (pgp::T::PTS / 32))},
+    /* F_COMP_DIRECT */ {IMG_COMP_DIRECT, IMG_NONE, IMG_BIAS, 0, pg_evalc_points_per_pass, one_wg_per_cu,
+                         PG_CHUNKS(pgp::C::NCHUNK), PG_MFMA(pgp::C::MFMA_PER_GROUP(fc))},
+    /* F_COMP_REC    */ {IMG_COMP_REC, IMG_VYC, IMG_BIAS, RECC_Y_BYTES, pg_evalc_points_per_pass, one_wg_per_cu,
+                         PG_CHUNKS(pgp::C::NCHUNK_R), PG_MFMA(pgp::C::MFMA_PER_GROUP_R)},
+    /* F_COMP_ONCHIP */ {IMG_COMP_ONCHIP, IMG_NONE, IMG_BIAS, 0, pg_evalc_points_per_pass, one_wg_per_cu,
+                         PG_CHUNKS(pgp::C::NCHUNK_OC), PG_MFMA(pgp::C::MFMA_PER_GROUP_R)},
+    /* F_KMAJOR      */ {IMG_DIRECT, IMG_NONE, IMG_BIAS, 0, pg_eval32_points_per_pass, one_wg_per_cu,
+                         [](int prec) -> int64_t { return (int64_t)(prec == PG_PREC_FP32 ? pgp::B::NCHUNK : pgp::B::NCHUNK_FOLD) * CHUNK_BYTES; },
+                         PG_MFMA(prec == PG_PREC_FP32 ? mfma_direct(fc) * 8 : (mfma_direct(fc) - NT * pgp::A::HU) * (prec == PG_PREC_FP16C ? 2 : 3))},
+};
+#undef PG_CHUNKS
+#undef PG_MFMA
+constexpr int image_of(int image, int prec) { return image >= 0 && image < IMG_PER_PREC_END ? image + prec : image; }
 
 int ensure_rec(pg_handle* h, int64_t n, int y_bytes) {
     const size_t need = (size_t)(n + REC_PAD_RAYS) * ((size_t)y_bytes + REC_AB_BYTES);
@@ -225,202 +311,170 @@ int ensure_rec(pg_handle* h, int64_t n, int y_bytes) {
     return PG_OK;
 }
 
-int ensure_stream_r(pg_handle* h, int which, int prec) {
+// ---- the packed weight images of a net (NetState::img) ------------------------------------------------------------
+struct Packed {
+    std::vector<uint8_t> b;
+    std::vector<float> f;           // (the fp32 tables)
+    const void* data() const { return f.empty() ? static_cast<const void*>(b.data()) : f.data(); }
+    size_t bytes() const { return f.empty() ? b.size() : f.size() * sizeof(float); }
+};
+
+// Image `id` of net `which`, packed from the tensors `t`; `src`: its source map as well (the images of REFORMED)
+int pack_image(pg_handle* h, int which, const pgpack::NetTensors& t, int id, Packed& p, std::vector<int32_t>* src = nullptr) {
+    const NetState& ns = h->net[which];
+    const bool fc = h->cfg.framecode_ch > 0;
+    const int prec = id < IMG_PER_PREC_END ? id % PG_PREC_COUNT : PG_PREC_FP16C;
+    int rc = 0;
+    switch (id < IMG_PER_PREC_END ? id - prec : id) {
+    case IMG_DIRECT:
+        if ((rc = pgpack::pack_stream(t, prec, fc, false, p.b))) return pg_fail(h, PG_EINVAL, "weight stream packing failed (%d) for precision %d", rc, prec);
+        break;
+    case IMG_COMP_DIRECT:
+        if ((rc = pgpack::pack_stream(t, prec, fc, true, p.b))) return pg_fail(h, PG_EINVAL, "weight stream packing failed (%d) for precision %d", rc, prec);
+        break;
+    case IMG_REC16:
+        if ((rc = pgpack::pack_stream_r(t, prec, p.b))) return pg_fail(h, PG_EINVAL, "16x16x32 weight stream packing failed (%d) for precision %d", rc, prec);
+        break;
+    case IMG_ONCHIP16:
+        if ((rc = pgpack::pack_stream_r(t, prec, p.b, true, src))) return pg_fail(h, PG_EINVAL, "on-chip 16x16x32 weight stream packing failed (%d) for precision %d", rc, prec);
+        break;
+    case IMG_VY16:
+        if (pgpack::pack_vy(t, prec, fc, p.b) != 0) return pg_fail(h, PG_EINVAL, "Y-stage weight packing failed for precision %d", prec);
+        break;
+    case IMG_COMP_REC:
+        if ((rc = pgpack::pack_stream(t, prec, fc, true, p.b, nullptr, true))) return pg_fail(h, PG_EINVAL, "compensated-fp16 record-variant stream packing failed (%d)", rc);
+        break;
+    case IMG_VYC: pgpack::pack_vyc(t, fc, p.f); break;
+    case IMG_COMP_ONCHIP:
+        if ((rc = pgpack::pack_stream(t, prec, false, true, p.b, nullptr, true, true))) return pg_fail(h, PG_EINVAL, "compensated-fp16 on-chip stream packing failed (%d)", rc);
+        break;
+    case IMG_C2:
+        if ((rc = pgpack::pack_c2(t, fc, p.b, src))) return pg_fail(h, PG_EINVAL, "compensated-fp16 tile-split weight packing failed (%d)", rc);
+        break;
+    case IMG_YCODE: {
+        // The frame code's part of the view layer for every code (and the mean row, embedding.py:25-26), as the on-chip variant reads it:
+        // Yc[c][o] = sum_k W_view[o][256 + 648 + k] codes[c][k] in fp32 (sums in double) -- 16 products per value once per
+        // pg_set_framecodes / pg_load_weights instead of once per ray.
+        if (ns.codes_host.empty()) return pg_fail(h, PG_ESTATE, "frame codes of net %d not set (pg_set_framecodes)", which);
+        p.f.resize((size_t)(ns.n_codes + 1) * VW);
+        for (int c = 0; c <= ns.n_codes; ++c)
+            for (int o = 0; o < VW; ++o) {
+                double s = 0.0;
+                for (int k = 0; k < FC_CH; ++k) s += (double)t.view_w[(size_t)o * t.view_cols + W + CH_D + k] * (double)ns.codes_host[(size_t)c * FC_CH + k];
+                p.f[(size_t)c * VW + o] = (float)s;
+            }
+        break;
+    }
+    case IMG_BIAS16: pgpack::pack_bias_s(t, p.f, src); break;
+    case IMG_BIAS: pgpack::pack_bias(t, p.f); break;
+    default: return pg_fail(h, PG_EINVAL, "no weight image %d", id);
+    }
+    return PG_OK;
+}
+
+// host memory -> a new device allocation; *d is set only once the copy has succeeded
+int upload(pg_handle* h, const void* data, size_t bytes, void** d) {
+    void* m = nullptr;
+    PG_HIP(h, hipSetDevice(h->device));
+    PG_HIP(h, hipMalloc(&m, bytes));
+    const hipError_t e = hipMemcpy(m, data, bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(m);
+        return pg_fail(h, PG_EHIP, "upload of %zu bytes failed: %s", bytes, hipGetErrorString(e));
+    }
+    *d = m;
+    return PG_OK;
+}
+
+int refresh_host(pg_handle* h, int which);
+
+// Image `id` of net `which` on the device, packed and uploaded by the first call that needs it.  A slot that exists is current:
+// pg_load_weights releases them all, pg_load_weights_device all but those it re-forms (IMG_BIAS: see refresh_host)
+int ensure_image(pg_handle* h, int which, int id) {
     NetState& ns = h->net[which];
     if (!ns.loaded) return pg_fail(h, PG_ESTATE, "weights of net %d not loaded", which);
-    if (ns.d_stream_r[prec] && ns.d_bias_s && ns.d_vy[prec]) return PG_OK;
-    if (const int rr_ = refresh_host(h, ns)) return rr_;        // (the last weights may have come from the device)
-    const pgpack::NetTensors t = tensors_of(ns, h->cfg);        // (folds feature_linear into the view layer: milliseconds of host work)
-    PG_HIP(h, hipSetDevice(h->device));
-    if (!ns.d_stream_r[prec]) {
-        std::vector<uint8_t> packed;
-        const int rc = pgpack::pack_stream_r(t, prec, packed);
-        if (rc != 0) return pg_fail(h, PG_EINVAL, "16x16x32 weight stream packing failed (%d) for precision %d", rc, prec);
-        PG_HIP(h, hipMalloc(reinterpret_cast<void**>(&ns.d_stream_r[prec]), packed.size()));
-        PG_HIP(h, hipMemcpy(ns.d_stream_r[prec], packed.data(), packed.size(), hipMemcpyHostToDevice));
-    }
-    if (!ns.d_bias_s) {
-        std::vector<float> b;
-        pgpack::pack_bias_s(t, b);
-        PG_HIP(h, hipMalloc(reinterpret_cast<void**>(&ns.d_bias_s), b.size() * sizeof(float)));
-        PG_HIP(h, hipMemcpy(ns.d_bias_s, b.data(), b.size() * sizeof(float), hipMemcpyHostToDevice));
-    }
-    if (!ns.d_vy[prec]) {
-        std::vector<uint8_t> vy;
-        if (pgpack::pack_vy(t, prec, h->cfg.framecode_ch > 0, vy) != 0)
-            return pg_fail(h, PG_EINVAL, "Y-stage weight packing failed for precision %d", prec);
-        PG_HIP(h, hipMalloc(reinterpret_cast<void**>(&ns.d_vy[prec]), vy.size()));
-        PG_HIP(h, hipMemcpy(ns.d_vy[prec], vy.data(), vy.size(), hipMemcpyHostToDevice));
-    }
+    NetState::Slot& s = ns.img[id];
+    if (s.d) return PG_OK;
+    if (const int rr_ = refresh_host(h, which)) return rr_;     // (the last weights may have come from the device)
+    Packed p;
+    if (const int rc = pack_image(h, which, tensors_of(ns, h->cfg), id, p)) return rc;     // (tensors_of folds feature_linear into the view layer: milliseconds of host work, once per load)
+    if (const int rc = upload(h, p.data(), p.bytes(), reinterpret_cast<void**>(&s.d))) return rc;
+    s.bytes = p.bytes();
     return PG_OK;
 }
 
-// the on-chip variant of the 16x16x32 kernel (no per-ray records): its stream; the bias table is shared
-int ensure_stream_ro(pg_handle* h, int which, int prec) {
+constexpr uint64_t image_bit(int id) { return 1ull << id; }
+static_assert(IMG_COUNT <= 64, "release_images keeps by bit mask");
+
+// Frees every image whose bit is not in `keep`; `sync`: one device synchronise in front when there is anything to free
+// (without it hipFree itself waits for the device)
+hipError_t release_images(NetState& ns, uint64_t keep, bool sync) {
+    hipError_t first = hipSuccess;
+    for (int id = 0; id < IMG_COUNT; ++id) {
+        NetState::Slot& s = ns.img[id];
+        if (!s.d || (keep & image_bit(id))) continue;
+        if (sync) { first = hipDeviceSynchronize(); sync = false; }
+        const hipError_t e = hipFree(s.d);
+        if (first == hipSuccess) first = e;
+        s = {};
+    }
+    return first;
+}
+
+// The host copies of a net's tensors are brought up to date if the last weights came from the device
+// (pg_load_weights_device leaves them stale: only the images it re-forms itself are current) -- and with them the 32-row bias
+// table, the one image that is kept over a device load without being re-formed there: the streams it goes with are all released
+// by the load, so the first call that reads it comes through here first
+int refresh_host(pg_handle* h, int which) {
     NetState& ns = h->net[which];
-    if (!ns.loaded) return pg_fail(h, PG_ESTATE, "weights of net %d not loaded", which);
-    if (ns.d_stream_ro[prec] && ns.d_bias_s) return PG_OK;
-    if (const int rr_ = refresh_host(h, ns)) return rr_;        // (the last weights may have come from the device)
-    const pgpack::NetTensors t = tensors_of(ns, h->cfg);
+    if (!ns.host_stale) return PG_OK;
+    pgpack::NetTensors lay;
+    lay.layout(h->cfg.framecode_ch);
     PG_HIP(h, hipSetDevice(h->device));
-    if (!ns.d_stream_ro[prec]) {
-        std::vector<uint8_t> packed;
-        const int rc = pgpack::pack_stream_r(t, prec, packed, true);
-        if (rc != 0) return pg_fail(h, PG_EINVAL, "on-chip 16x16x32 weight stream packing failed (%d) for precision %d", rc, prec);
-        PG_HIP(h, hipMalloc(reinterpret_cast<void**>(&ns.d_stream_ro[prec]), packed.size()));
-        PG_HIP(h, hipMemcpy(ns.d_stream_ro[prec], packed.data(), packed.size(), hipMemcpyHostToDevice));
-    }
-    if (!ns.d_bias_s) {
-        std::vector<float> b;
-        pgpack::pack_bias_s(t, b);
-        PG_HIP(h, hipMalloc(reinterpret_cast<void**>(&ns.d_bias_s), b.size() * sizeof(float)));
-        PG_HIP(h, hipMemcpy(ns.d_bias_s, b.data(), b.size() * sizeof(float), hipMemcpyHostToDevice));
-    }
-    return PG_OK;
+    PG_HIP(h, hipDeviceSynchronize());
+    for (int i = 0; i < 24; ++i)
+        PG_HIP(h, hipMemcpy(ns.host[i].data(), ns.d_src + lay.off[i], ns.host[i].size() * sizeof(float), hipMemcpyDeviceToHost));
+    ns.fold_w.clear(); ns.fold_b.clear();
+    if (ns.d_codes && !ns.codes_host.empty())
+        PG_HIP(h, hipMemcpy(ns.codes_host.data(), ns.d_codes, ns.codes_host.size() * sizeof(float), hipMemcpyDeviceToHost));
+    ns.host_stale = false;
+    PG_HIP(h, release_images(ns, ~image_bit(IMG_BIAS), false));
+    return ensure_image(h, which, IMG_BIAS);
 }
 
-// ... which runs for rays of at most ONCHIP_MAX_S samples.  The 16x16x32 kernel's on-chip variant takes per-ray poses and
-// frame codes too; pg_evalc.hip's on-chip form needs one pose per launch and no frame codes (`plain_only`) and has no
-// sample-count rule.  The on-chip variant forms a ray's rows in every pass the ray has points in, the record variant once
-// per ray in a kernel in front: measured on one box (profiles/r5_ab_onchip_by_samples.txt, bf16 512 x 512 frames) the two
-// tie at 64 + 16 samples (31.7 / 31.8 ms), on-chip wins at 96 + 16 (43.3 / 43.6) and records win from 128 + 16 on (59.3 /
-// 58.0; with frame codes 59.7 / 58.2) -- at a cost of 8.75 KiB of HBM per ray.  pg_set_onchip (initial value: POSEGEN_ONCHIP = 0 / 1 / 2)
-// forces the record variants (0) or the on-chip ones whatever the sample count (2).
-constexpr int ONCHIP_MAX_S = 112;
-int onchip_mode_from_env() {
-    const char* e = std::getenv("POSEGEN_ONCHIP");
-    return e && e[0] == '0' ? PG_ONCHIP_RECORDS : e && e[0] == '2' ? PG_ONCHIP_ALWAYS : PG_ONCHIP_AUTO;
-}
-bool use_onchip(const pg_handle* h, bool fc, long long pose_stride, int S, bool plain_only = false) {
-    const int mode = h->onchip_mode;
-    if (plain_only) return mode != PG_ONCHIP_RECORDS && !fc && pose_stride == 0;
-    return mode == PG_ONCHIP_ALWAYS || (mode == PG_ONCHIP_AUTO && S <= ONCHIP_MAX_S);
-}
-
-// The frame code's part of the view layer for every code (and the mean row, embedding.py:25-26), as the on-chip variant reads it:
-// Yc[c][o] = sum_k W_view[o][256 + 648 + k] codes[c][k] in fp32 (sums in double) -- 16 products per value once per
-// pg_set_framecodes / pg_load_weights instead of once per ray.
-int ensure_ycode(pg_handle* h, int which) {
-    NetState& ns = h->net[which];
-    if (ns.d_ycode) return PG_OK;
-    if (!ns.loaded || ns.codes_host.empty()) return pg_fail(h, PG_ESTATE, "frame codes of net %d not set (pg_set_framecodes)", which);
-    if (const int rr_ = refresh_host(h, ns)) return rr_;        // (the last weights may have come from the device)
-    const int vcols = W + CH_D + FC_CH;
-    const std::vector<float>& wv = ns.host[20];
-    std::vector<float> yc((size_t)(ns.n_codes + 1) * VW);
-    for (int c = 0; c <= ns.n_codes; ++c)
-        for (int o = 0; o < VW; ++o) {
-            double s = 0.0;
-            for (int k = 0; k < FC_CH; ++k) s += (double)wv[(size_t)o * vcols + W + CH_D + k] * (double)ns.codes_host[(size_t)c * FC_CH + k];
-            yc[(size_t)c * VW + o] = (float)s;
-        }
-    PG_HIP(h, hipSetDevice(h->device));
-    PG_HIP(h, hipMalloc(reinterpret_cast<void**>(&ns.d_ycode), yc.size() * sizeof(float)));
-    PG_HIP(h, hipMemcpy(ns.d_ycode, yc.data(), yc.size() * sizeof(float), hipMemcpyHostToDevice));
-    return PG_OK;
-}
-
-int ensure_stream_cr(pg_handle* h, int which) {
-    NetState& ns = h->net[which];
-    if (!ns.loaded) return pg_fail(h, PG_ESTATE, "weights of net %d not loaded", which);
-    if (ns.d_stream_cr && ns.d_vyc) return PG_OK;
-    if (const int rr_ = refresh_host(h, ns)) return rr_;        // (the last weights may have come from the device)
-    const pgpack::NetTensors t = tensors_of(ns, h->cfg);
-    PG_HIP(h, hipSetDevice(h->device));
-    if (!ns.d_stream_cr) {
-        std::vector<uint8_t> packed;
-        const int rc = pgpack::pack_stream(t, PG_PREC_FP16C, h->cfg.framecode_ch > 0, true, packed, nullptr, true);
-        if (rc != 0) return pg_fail(h, PG_EINVAL, "compensated-fp16 record-variant stream packing failed (%d)", rc);
-        PG_HIP(h, hipMalloc(reinterpret_cast<void**>(&ns.d_stream_cr), packed.size()));
-        PG_HIP(h, hipMemcpy(ns.d_stream_cr, packed.data(), packed.size(), hipMemcpyHostToDevice));
-    }
-    if (!ns.d_vyc) {
-        std::vector<float> vy;
-        pgpack::pack_vyc(t, h->cfg.framecode_ch > 0, vy);
-        PG_HIP(h, hipMalloc(reinterpret_cast<void**>(&ns.d_vyc), vy.size() * sizeof(float)));
-        PG_HIP(h, hipMemcpy(ns.d_vyc, vy.data(), vy.size() * sizeof(float), hipMemcpyHostToDevice));
+// the images form `f` reads at precision `prec`; the Yc table only `with_codes` (a launch with frame codes)
+int ensure_form_images(pg_handle* h, int which, Form f, int prec, bool with_codes) {
+    const FormInfo& fi = FORMS[f];
+    for (const int image : {fi.stream, fi.wy, fi.bias}) {
+        if (image == IMG_NONE || (image == IMG_YCODE && !with_codes)) continue;
+        if (const int rc = ensure_image(h, which, image_of(image, prec))) return rc;
     }
     return PG_OK;
 }
 
-// the on-chip form of that variant (one pose per launch, no frame codes): its stream
-int ensure_stream_co(pg_handle* h, int which) {
-    NetState& ns = h->net[which];
-    if (!ns.loaded) return pg_fail(h, PG_ESTATE, "weights of net %d not loaded", which);
-    if (ns.d_stream_co) return PG_OK;
-    std::vector<uint8_t> packed;
-    if (const int rr_ = refresh_host(h, ns)) return rr_;        // (the last weights may have come from the device)
-    const int rc = pgpack::pack_stream(tensors_of(ns, h->cfg), PG_PREC_FP16C, false, true, packed, nullptr, true, true);
-    if (rc != 0) return pg_fail(h, PG_EINVAL, "compensated-fp16 on-chip stream packing failed (%d)", rc);
-    PG_HIP(h, hipSetDevice(h->device));
-    PG_HIP(h, hipMalloc(reinterpret_cast<void**>(&ns.d_stream_co), packed.size()));
-    PG_HIP(h, hipMemcpy(ns.d_stream_co, packed.data(), packed.size(), hipMemcpyHostToDevice));
-    return PG_OK;
-}
-
-// PG_PREC_FP16C with >= pgp::T::MIN_S samples per ray runs in the kernel that splits the OUT TILES over the waves
-// (pg_evalc2.hip: two waves per SIMD, activations in LDS, weights straight from L2) -- whatever the pose stride, with or
-// without frame codes; POSEGEN_EVALC2=0 keeps the calls on pg_evalc.hip (A/B, and the record / on-chip forms' tests)
-bool use_evalc2(int S) {
-    static const bool allowed = [] { const char* e = std::getenv("POSEGEN_EVALC2"); return !(e && e[0] == '0'); }();
-    return allowed && S >= pgp::T::MIN_S;
-}
-
-// its weights (pg_program.h T) and the 16-row bias table it shares with the 16x16x32 kernel
-int ensure_c2(pg_handle* h, int which) {
-    NetState& ns = h->net[which];
-    if (!ns.loaded) return pg_fail(h, PG_ESTATE, "weights of net %d not loaded", which);
-    if (ns.d_c2 && ns.d_bias_s) return PG_OK;
-    if (const int rr_ = refresh_host(h, ns)) return rr_;        // (the last weights may have come from the device)
-    const pgpack::NetTensors t = tensors_of(ns, h->cfg);
-    PG_HIP(h, hipSetDevice(h->device));
-    if (!ns.d_c2) {
-        std::vector<uint8_t> packed;
-        const int rc = pgpack::pack_c2(t, h->cfg.framecode_ch > 0, packed);
-        if (rc != 0) return pg_fail(h, PG_EINVAL, "compensated-fp16 tile-split weight packing failed (%d)", rc);
-        PG_HIP(h, hipMalloc(reinterpret_cast<void**>(&ns.d_c2), packed.size()));
-        PG_HIP(h, hipMemcpy(ns.d_c2, packed.data(), packed.size(), hipMemcpyHostToDevice));
-    }
-    if (!ns.d_bias_s) {
-        std::vector<float> b;
-        pgpack::pack_bias_s(t, b);
-        PG_HIP(h, hipMalloc(reinterpret_cast<void**>(&ns.d_bias_s), b.size() * sizeof(float)));
-        PG_HIP(h, hipMemcpy(ns.d_bias_s, b.data(), b.size() * sizeof(float), hipMemcpyHostToDevice));
-    }
-    return PG_OK;
-}
-
-int ensure_stream(pg_handle* h, int which, int prec, bool fact) {
-    NetState& ns = h->net[which];
-    if (!ns.loaded) return pg_fail(h, PG_ESTATE, "weights of net %d not loaded", which);
-    if (ns.d_stream[prec][fact]) return PG_OK;
-    std::vector<uint8_t> packed;
-    if (const int rr_ = refresh_host(h, ns)) return rr_;        // (the last weights may have come from the device)
-    const int rc = pgpack::pack_stream(tensors_of(ns, h->cfg), prec, h->cfg.framecode_ch > 0, fact, packed);
-    if (rc != 0) return pg_fail(h, PG_EINVAL, "weight stream packing failed (%d) for precision %d", rc, prec);
-    PG_HIP(h, hipSetDevice(h->device));
-    PG_HIP(h, hipMalloc(reinterpret_cast<void**>(&ns.d_stream[prec][fact]), packed.size()));
-    PG_HIP(h, hipMemcpy(ns.d_stream[prec][fact], packed.data(), packed.size(), hipMemcpyHostToDevice));
-    ns.stream_bytes[prec][fact] = packed.size();
-    return PG_OK;
-}
-
-// the packed weight stream a precision mode will use for net `which` in the usual call (rays with >= 64 samples; one pose
-// per call unless the config has frame codes), built ahead of the first render; the other forms of the mode (per-ray poses,
-// short rays, explicit points) are packed by the first call that needs them (launch_eval_one)
+// the images a precision mode will use for net `which` in the usual call (usual_form), built ahead of the first render; the
+// other forms of the mode (per-ray poses, short rays, explicit points) are packed by the first call that needs them
+// (launch_eval_one), and so is the Yc table: the frame codes are set after the weights
 int ensure_mode_streams(pg_handle* h, int which, int mode) {
-    auto one = [&](int prec) {
-        const bool fc = h->cfg.framecode_ch > 0;
-        if (is_shape_a(prec) && use_fact(prec, FACT_MIN_S)) return use_onchip(h, fc, 0, FACT_MIN_S) ? ensure_stream_ro(h, which, prec) : ensure_stream_r(h, which, prec);
-        if (prec == PG_PREC_FP16C && use_evalc2(FACT_MIN_S)) return ensure_c2(h, which);
-        if (prec == PG_PREC_FP16C && use_comp_rec(FACT_MIN_S)) return use_onchip(h, fc, 0, FACT_MIN_S, true) ? ensure_stream_co(h, which) : ensure_stream_cr(h, which);
-        return ensure_stream(h, which, prec, use_fact(prec, FACT_MIN_S));
-    };
+    auto one = [&](int prec) { return ensure_form_images(h, which, usual_form(h, prec), prec, false); };
     if (mode != PG_PREC_FP16M) return one(mode);
     int rc = one(PG_PREC_FP16C);
     if (!rc && which == 0 && !h->cfg.single_net) rc = one(PG_PREC_FP16);      // (single_net: no guide pass)
     return rc;
 }
+
+// The images pg_load_weights_device re-forms on the device (pg_repack.hip), bitwise as pack_image would pack them: by a gather
+// through a source map (built once, by pack_image in index mode) or, the Yc table, from the frame codes.  Every other image but
+// IMG_BIAS is released by that load.
+enum Gather { G_BF16, G_F16, G_F32, G_YCODE };
+struct Reformed { int image, map, gather; const char* what; };
+constexpr Reformed REFORMED[] = {
+    {IMG_ONCHIP16 + PG_PREC_BF16, MAP_ONCHIP16, G_BF16, "the on-chip stream"},
+    {IMG_ONCHIP16 + PG_PREC_FP16, MAP_ONCHIP16, G_F16, "the on-chip stream"},
+    {IMG_C2, MAP_C2, G_F16, "the tile-split image"},
+    {IMG_BIAS16, MAP_BIAS16, G_F32, "the 16-row bias table"},
+    {IMG_YCODE, MAP_NONE, G_YCODE, "the frame-code table"},         // (behind pg_launch_codes: it reads the new codes)
+};
 
 int ensure_ws(pg_handle* h, size_t bytes) {
     if (bytes <= h->ws_bytes) return PG_OK;
@@ -445,35 +499,23 @@ int check_ready(pg_handle* h, bool need_fine) {
 int launch_eval_one(pg_handle* h, void* stream, int which, long long n, int S, const float* rays, const float* z,
                     const float* skts, long long pose_stride, const float* cams, float* raw, float* dbg, int dbg_stage,
                     const float* points, const float* pnoise, bool guide_pass) {
-    // PG_PREC_FP16M: the coarse pass of a hierarchical render only places the importance samples (and fills
-    // rgb0/acc0): plain fp16 there, compensated fp16 wherever the pass produces the returned maps
-    const int prec = h->cfg.precision == PG_PREC_FP16M ? (guide_pass ? PG_PREC_FP16 : PG_PREC_FP16C) : h->cfg.precision;
-    // explicit points and position noise need q = R p + t per point: the direct kernels (no per-ray a + z b table)
-    const bool compk = !pnoise && use_comp_kernel(prec, S, points != nullptr);
-    const bool fact = compk || (!points && !pnoise && use_fact(prec, S));
-    const bool sa = is_shape_a(prec);
+    const int prec = pass_precision(h->cfg.precision, guide_pass);
     const bool fc = h->cfg.framecode_ch > 0;
-    const bool onchip = sa && fact && (!dbg || (dbg_stage == 97 && pose_stride == 0 && !fc)) && use_onchip(h, fc, pose_stride, S);     // the 16x16x32 kernel without per-ray records (97: its limb-mask counters)
-    const bool recs = sa && fact && !onchip;                      // per-ray records + the 16x16x32 kernel
-    const bool c2 = compk && (!dbg || dbg_stage == 99 || dbg_stage == 97) && use_evalc2(S);      // out tiles over the waves (pg_evalc2.hip): any pose stride, frame codes or not
-    const bool conchip = !c2 && compk && use_comp_rec(S) && (!dbg || dbg_stage == 98 || dbg_stage == 99) && use_onchip(h, fc, pose_stride, S, true);   // (98 / 99: diagnosis builds' dumps)   // the record variant of pg_evalc.hip without per-ray records
-    const bool crec = !c2 && compk && use_comp_rec(S) && !conchip;       // per-ray records + the record variant of pg_evalc.hip
-    int rc = onchip ? ensure_stream_ro(h, which, prec) : recs ? ensure_stream_r(h, which, prec) : c2 ? ensure_c2(h, which)
-           : conchip ? ensure_stream_co(h, which) : crec ? ensure_stream_cr(h, which) : ensure_stream(h, which, prec, fact);
+    const Form form = pick_form(CallFacts{prec, S, pose_stride, fc, points != nullptr, pnoise != nullptr, dbg != nullptr, dbg_stage, h->onchip_mode}, switches());
+    const FormInfo& fi = FORMS[form];
+    const int y_bytes = fi.rec_y_bytes;
+    int rc = ensure_form_images(h, which, form, prec, fc);
     if (rc) return rc;
-    if (onchip && fc && (rc = ensure_ycode(h, which))) return rc;
-    const int y_bytes = crec ? RECC_Y_BYTES : REC_Y_BYTES;
-    if ((recs || crec) && (rc = ensure_rec(h, n, y_bytes))) return rc;
+    if (y_bytes && (rc = ensure_rec(h, n, y_bytes))) return rc;
     NetState& ns = h->net[which];
     if (fc && !ns.d_codes) return pg_fail(h, PG_ESTATE, "frame codes of net %d not set (pg_set_framecodes)", which);
     pgd::EvalArgs a{};
     a.rays = rays; a.z = z; a.pts = points; a.pnoise = pnoise; a.skts = skts; a.cams = cams;
     a.codes = fc ? ns.d_codes : nullptr;
-    a.wstream = onchip ? ns.d_stream_ro[prec] : recs ? ns.d_stream_r[prec] : c2 ? ns.d_c2 : conchip ? ns.d_stream_co : crec ? ns.d_stream_cr
-              : ns.d_stream[prec][fact];
-    a.wy = recs ? ns.d_vy[prec] : crec ? reinterpret_cast<const uint8_t*>(ns.d_vyc) : (onchip && fc) ? reinterpret_cast<const uint8_t*>(ns.d_ycode) : nullptr;
-    a.bias = (recs || onchip || c2) ? ns.d_bias_s : ns.d_bias;
-    if (recs || crec) {
+    a.wstream = ns.img[image_of(fi.stream, prec)].d;
+    a.wy = fi.wy == IMG_NONE || (fi.wy == IMG_YCODE && !fc) ? nullptr : ns.img[image_of(fi.wy, prec)].d;
+    a.bias = reinterpret_cast<const float*>(ns.img[fi.bias].d);
+    if (y_bytes) {
         a.rec_y = h->rec;
         a.rec_ab = reinterpret_cast<const float*>(h->rec + (size_t)(n + REC_PAD_RAYS) * y_bytes);
         // the padding rays behind the last record are fetched by the last passes (their values are multiplied by
@@ -499,7 +541,7 @@ int launch_eval_one(pg_handle* h, void* stream, int which, long long n, int S, c
     a.tau_d = h->tau[1];
     a.dbg_stage = dbg_stage;
     a.far_skip = h->far_skip ? 1 : 0;
-    const int pts = sa ? pg_eval16_points_per_pass() : c2 ? pg_evalc2_points_per_pass() : compk ? pg_evalc_points_per_pass() : pg_eval32_points_per_pass();
+    const int pts = fi.points_per_pass();
     if (!points && S < pts / (MAXR - 1))      // explicit points are one pseudo ray: a pass touches one slot
         return pg_fail(h, PG_EINVAL, "N_samples=%d too small: the fused kernel needs >= %d samples per ray", S, pts / (MAXR - 1));
     const long long iters = (a.n_points + pts - 1) / pts;
@@ -507,7 +549,7 @@ int launch_eval_one(pg_handle* h, void* stream, int which, long long n, int S, c
     // POSEGEN_MAX_WG (measurement aid): fewer persistent workgroups than CUs, to see how much of a pass's time
     // is contention between CUs (the weight stream is pulled from L2 by every CU) rather than its own work
     static const long long wg_cap = [] { const char* e = std::getenv("POSEGEN_MAX_WG"); return e ? std::atoll(e) : 0ll; }();
-    long long max_wg = (long long)h->n_cu * (sa ? pg_eval16_wgs_per_cu() : 1);
+    long long max_wg = (long long)h->n_cu * fi.wgs_per_cu();
     if (wg_cap > 0 && wg_cap < max_wg) max_wg = wg_cap;
     const int grid = (int)(iters < max_wg ? iters : max_wg);
     hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -515,7 +557,7 @@ int launch_eval_one(pg_handle* h, void* stream, int which, long long n, int S, c
         if (!h->ev_free.empty()) { ev = h->ev_free.back(); h->ev_free.pop_back(); return hipSuccess; }
         return hipEventCreate(&ev);
     };
-    if (recs || crec) {     // what depends on the ray only, once per ray, in front of the fused kernel (pg_rayrec.hip)
+    if (y_bytes) {          // what depends on the ray only, once per ray, in front of the fused kernel (pg_rayrec.hip)
         pgd::RecArgs ra{};
         ra.rays = rays; ra.skts = skts; ra.cams = cams; ra.codes = a.codes; ra.wy = a.wy;
         ra.rec_ab = const_cast<float*>(a.rec_ab); ra.rec_y = const_cast<uint8_t*>(a.rec_y);
@@ -523,7 +565,7 @@ int launch_eval_one(pg_handle* h, void* stream, int which, long long n, int S, c
         ra.z = z; ra.S = S;
         hipEvent_t x0 = nullptr, x1 = nullptr;
         if (h->profiling) { PG_HIP(h, get(x0)); PG_HIP(h, get(x1)); PG_HIP(h, hipEventRecord(x0, static_cast<hipStream_t>(stream))); }
-        const int er = crec ? pg_launch_ray_records_c(&ra, fc, h->n_cu, stream) : pg_launch_ray_records(&ra, prec == PG_PREC_FP16, fc, h->n_cu, stream);
+        const int er = form == F_COMP_REC ? pg_launch_ray_records_c(&ra, fc, h->n_cu, stream) : pg_launch_ray_records(&ra, prec == PG_PREC_FP16, fc, h->n_cu, stream);
         if (h->profiling) {
             PG_HIP(h, hipEventRecord(x1, static_cast<hipStream_t>(stream)));
             if (er) { h->ev_free.push_back(x0); h->ev_free.push_back(x1); }      // a failed launch is not a sample
@@ -536,11 +578,17 @@ int launch_eval_one(pg_handle* h, void* stream, int which, long long n, int S, c
         PG_HIP(h, get(e1));
         PG_HIP(h, hipEventRecord(e0, static_cast<hipStream_t>(stream)));
     }
-    int e = (recs || onchip) ? pg_launch_eval16r(&a, prec == PG_PREC_FP16, fc, onchip, grid, stream)
-          : sa ? pg_launch_eval16(&a, prec == PG_PREC_FP16, fc, grid, stream)
-          : c2 ? pg_launch_evalc2(&a, fc, grid, stream)
-          : compk ? pg_launch_evalc(&a, fc, conchip ? 2 : crec ? 1 : 0, grid, stream)
-               : pg_launch_eval32(&a, prec, fc, grid, stream);
+    int e = 0;
+    switch (form) {
+    case F_DIRECT16:    e = pg_launch_eval16(&a, prec == PG_PREC_FP16, fc, grid, stream); break;
+    case F_REC16:       e = pg_launch_eval16r(&a, prec == PG_PREC_FP16, fc, 0, grid, stream); break;
+    case F_ONCHIP16:    e = pg_launch_eval16r(&a, prec == PG_PREC_FP16, fc, 1, grid, stream); break;
+    case F_C2:          e = pg_launch_evalc2(&a, fc, grid, stream); break;
+    case F_COMP_DIRECT: e = pg_launch_evalc(&a, fc, 0, grid, stream); break;
+    case F_COMP_REC:    e = pg_launch_evalc(&a, fc, 1, grid, stream); break;
+    case F_COMP_ONCHIP: e = pg_launch_evalc(&a, fc, 2, grid, stream); break;
+    default:            e = pg_launch_eval32(&a, prec, fc, grid, stream); break;
+    }
     if (h->profiling) {
         PG_HIP(h, hipEventRecord(e1, static_cast<hipStream_t>(stream)));
         h->ev_used.emplace_back(e0, e1);
@@ -614,7 +662,7 @@ int pg_create(const pg_config* cfg, int n_devices, const int* device_ids, pg_han
     if (cfg->density_act != PG_ACT_RELU && cfg->density_act != PG_ACT_SOFTPLUS)
         return pg_fail(nullptr, PG_EINVAL, "pg_create: density_act must be PG_ACT_RELU or PG_ACT_SOFTPLUS, got %d", cfg->density_act);
     pg_handle* h = new (std::nothrow) pg_handle();
-    if (h) h->onchip_mode = onchip_mode_from_env();
+    if (h) h->onchip_mode = switches().onchip;
     if (!h) return pg_fail(nullptr, PG_ENOMEM, "pg_create: out of host memory");
     h->cfg = *cfg;
     h->device = device_ids ? device_ids[0] : 0;
@@ -692,22 +740,10 @@ void pg_destroy(pg_handle* h) {
     frames_cache_release(h);
     for (auto& pr : h->ev_aux) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
     for (NetState& ns : h->net) {
-        for (auto& p : ns.d_stream_r) if (p) (void)hipFree(p);
-        for (auto& p : ns.d_stream_ro) if (p) (void)hipFree(p);
-        for (auto& pp : ns.d_stream) for (auto& p : pp) if (p) (void)hipFree(p);
-        for (auto& p : ns.d_vy) if (p) (void)hipFree(p);
-        if (ns.d_bias_s) (void)hipFree(ns.d_bias_s);
-        if (ns.d_ycode) (void)hipFree(ns.d_ycode);
-        if (ns.d_stream_cr) (void)hipFree(ns.d_stream_cr);
-        if (ns.d_stream_co) (void)hipFree(ns.d_stream_co);
-        if (ns.d_c2) (void)hipFree(ns.d_c2);
-        if (ns.d_vyc) (void)hipFree(ns.d_vyc);
-        if (ns.d_bias) (void)hipFree(ns.d_bias);
+        (void)release_images(ns, 0, false);
         if (ns.d_codes) (void)hipFree(ns.d_codes);
         if (ns.d_src) (void)hipFree(ns.d_src);
-        if (ns.d_map_ro) (void)hipFree(ns.d_map_ro);
-        if (ns.d_map_c2) (void)hipFree(ns.d_map_c2);
-        if (ns.d_map_bias_s) (void)hipFree(ns.d_map_bias_s);
+        for (int32_t* m : ns.d_map) if (m) (void)hipFree(m);
         if (ns.d_vwide) (void)hipFree(ns.d_vwide);
     }
     for (auto& pr : h->ev_used) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
@@ -752,24 +788,8 @@ int pg_load_weights(pg_handle* h, int which, const float* const* tensors, const 
     ns.loaded = true;
     ns.host_stale = false;
     PG_HIP(h, hipSetDevice(h->device));
-    for (int p = 0; p < PG_PREC_COUNT; ++p)
-        for (int f = 0; f < 2; ++f)
-            if (ns.d_stream[p][f]) { PG_HIP(h, hipDeviceSynchronize()); PG_HIP(h, hipFree(ns.d_stream[p][f])); ns.d_stream[p][f] = nullptr; }
-    for (int p = 0; p < PG_PREC_COUNT; ++p) {
-        if (ns.d_vy[p]) { PG_HIP(h, hipDeviceSynchronize()); PG_HIP(h, hipFree(ns.d_vy[p])); ns.d_vy[p] = nullptr; }
-        if (ns.d_stream_r[p]) { PG_HIP(h, hipDeviceSynchronize()); PG_HIP(h, hipFree(ns.d_stream_r[p])); ns.d_stream_r[p] = nullptr; }
-        if (ns.d_stream_ro[p]) { PG_HIP(h, hipDeviceSynchronize()); PG_HIP(h, hipFree(ns.d_stream_ro[p])); ns.d_stream_ro[p] = nullptr; }
-    }
-    if (ns.d_bias_s) { PG_HIP(h, hipDeviceSynchronize()); PG_HIP(h, hipFree(ns.d_bias_s)); ns.d_bias_s = nullptr; }
-    if (ns.d_ycode) { PG_HIP(h, hipDeviceSynchronize()); PG_HIP(h, hipFree(ns.d_ycode)); ns.d_ycode = nullptr; }
-    if (ns.d_stream_cr) { PG_HIP(h, hipDeviceSynchronize()); PG_HIP(h, hipFree(ns.d_stream_cr)); ns.d_stream_cr = nullptr; }
-    if (ns.d_stream_co) { PG_HIP(h, hipDeviceSynchronize()); PG_HIP(h, hipFree(ns.d_stream_co)); ns.d_stream_co = nullptr; }
-    if (ns.d_c2) { PG_HIP(h, hipDeviceSynchronize()); PG_HIP(h, hipFree(ns.d_c2)); ns.d_c2 = nullptr; }
-    if (ns.d_vyc) { PG_HIP(h, hipDeviceSynchronize()); PG_HIP(h, hipFree(ns.d_vyc)); ns.d_vyc = nullptr; }
-    std::vector<float> bias;
-    pgpack::pack_bias(tensors_of(ns, h->cfg), bias);
-    if (!ns.d_bias) PG_HIP(h, hipMalloc(reinterpret_cast<void**>(&ns.d_bias), BIAS_FLOATS * sizeof(float)));
-    PG_HIP(h, hipMemcpy(ns.d_bias, bias.data(), BIAS_FLOATS * sizeof(float), hipMemcpyHostToDevice));
+    PG_HIP(h, release_images(ns, 0, true));
+    if (const int rc = ensure_image(h, which, IMG_BIAS)) return rc;
     const auto tl1 = std::chrono::steady_clock::now();
     const int rc0 = ensure_mode_streams(h, which, h->cfg.precision);
     if (rc0) return rc0;
@@ -785,7 +805,7 @@ int pg_load_weights(pg_handle* h, int which, const float* const* tensors, const 
 // New values for a loaded net's tensors (and frame codes) from DEVICE memory -- what sits between optimiser steps and a
 // validation render (TrainableRayCaster.sync_inference_weights; the reference renders with the module it trains,
 // core/trainer.py:463).  The images of the fast paths -- the on-chip stream of the 16x16x32 kernel (bf16 / fp16), pg_evalc2.hip's
-// weight image, their bias table, the frame-code tables -- are re-formed on the device, bitwise as pg_load_weights would pack
+// weight image, their bias table, the frame-code tables: REFORMED -- are re-formed on the device, bitwise as pg_load_weights would pack
 // them (pg_repack.hip); every other image is dropped and re-packed from the host copies, which are refreshed from the device,
 // by the first call that needs it.  Enqueued on `stream`; the tensors may be reused as soon as the call returns in stream order.
 int pg_load_weights_device(pg_handle* h, void* stream, int which, const float* const* d_tensors, int n_tensors, const float* d_codes, int n_codes) {
@@ -821,54 +841,31 @@ int pg_load_weights_device(pg_handle* h, void* stream, int which, const float* c
     pg_launch_collect(tens, lay.off, ns.d_src, stream);        // (off[24] = the end of tensor 23: the folded view layer follows)
     pg_launch_fold(ns.d_src, lay.off[20], vcols, lay.off[21], lay.off[18], lay.off[19], lay.off[pgpack::NetTensors::SRC_VIEWF_W],
                    lay.off[pgpack::NetTensors::SRC_VIEWF_B], stream);
-    auto upload_map = [&](const std::vector<int32_t>& m, int32_t** d, size_t* n) -> int {
-        PG_HIP(h, hipMalloc(reinterpret_cast<void**>(d), m.size() * sizeof(int32_t)));
-        PG_HIP(h, hipMemcpy(*d, m.data(), m.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        if (n) *n = m.size();
-        return PG_OK;
-    };
     // images re-formed here (those that exist: the others are built by the first call that needs them)
-    bool any_ro = false;
-    for (int prec : {PG_PREC_BF16, PG_PREC_FP16}) any_ro = any_ro || ns.d_stream_ro[prec];
-    if (any_ro && !ns.d_map_ro) {
-        std::vector<uint8_t> img; std::vector<int32_t> m;
-        if (pgpack::pack_stream_r(map_tensors(), PG_PREC_BF16, img, true, &m) != 0) return pg_fail(h, PG_EINVAL, "pg_load_weights_device: source map of the on-chip stream");
-        if (const int rc = upload_map(m, &ns.d_map_ro, &ns.n_map_ro)) return rc;
-    }
-    for (int prec : {PG_PREC_BF16, PG_PREC_FP16})
-        if (ns.d_stream_ro[prec])
-            pg_launch_gather16(ns.d_map_ro, ns.d_src, reinterpret_cast<uint16_t*>(ns.d_stream_ro[prec]), (long long)ns.n_map_ro, prec == PG_PREC_BF16, stream);
-    if (ns.d_c2) {
-        if (!ns.d_map_c2) {
-            std::vector<uint8_t> img; std::vector<int32_t> m;
-            if (pgpack::pack_c2(map_tensors(), fc, img, &m) != 0) return pg_fail(h, PG_EINVAL, "pg_load_weights_device: source map of the tile-split image");
-            if (const int rc = upload_map(m, &ns.d_map_c2, &ns.n_map_c2)) return rc;
+    if (fc) pg_launch_codes(d_codes, ns.n_codes, ns.d_codes, stream);
+    uint64_t keep = image_bit(IMG_BIAS);                // (stale until refresh_host re-forms it)
+    for (const Reformed& r : REFORMED) {
+        const NetState::Slot& im = ns.img[r.image];
+        keep |= image_bit(r.image);
+        if (!im.d) continue;
+        if (r.map != MAP_NONE && !ns.d_map[r.map]) {
+            Packed p; std::vector<int32_t> m;
+            if (pack_image(h, which, map_tensors(), r.image, p, &m)) return pg_fail(h, PG_EINVAL, "pg_load_weights_device: source map of %s", r.what);
+            if (const int rc = upload(h, m.data(), m.size() * sizeof(int32_t), reinterpret_cast<void**>(&ns.d_map[r.map]))) return rc;
         }
-        pg_launch_gather16(ns.d_map_c2, ns.d_src, reinterpret_cast<uint16_t*>(ns.d_c2), (long long)ns.n_map_c2, 0, stream);
-    }
-    if (ns.d_bias_s) {
-        if (!ns.d_map_bias_s) {
-            std::vector<float> b; std::vector<int32_t> m;
-            pgpack::pack_bias_s(map_tensors(), b, &m);
-            if (const int rc = upload_map(m, &ns.d_map_bias_s, nullptr)) return rc;
+        switch (r.gather) {
+        case G_BF16: case G_F16:
+            pg_launch_gather16(ns.d_map[r.map], ns.d_src, reinterpret_cast<uint16_t*>(im.d), (long long)(im.bytes / 2), r.gather == G_BF16, stream);
+            break;
+        case G_F32: pg_launch_gather32(ns.d_map[r.map], ns.d_src, reinterpret_cast<float*>(im.d), (long long)(im.bytes / 4), stream); break;
+        case G_YCODE: pg_launch_ycode(ns.d_src + lay.off[20], vcols, ns.d_codes, ns.n_codes, reinterpret_cast<float*>(im.d), stream); break;
         }
-        pg_launch_gather32(ns.d_map_bias_s, ns.d_src, ns.d_bias_s, (long long)BIAS16_FLOATS, stream);
-    }
-    if (fc) {
-        pg_launch_codes(d_codes, ns.n_codes, ns.d_codes, stream);
-        if (ns.d_ycode) pg_launch_ycode(ns.d_src + lay.off[20], vcols, ns.d_codes, ns.n_codes, ns.d_ycode, stream);
     }
     PG_HIP(h, hipGetLastError());
     // everything else: dropped (hipFree waits for the device: only forms the run has used beside the fast paths pay it)
-    auto drop = [&](auto*& p) { if (p) { (void)hipFree(p); p = nullptr; } };
-    for (int p = 0; p < PG_PREC_COUNT; ++p) {
-        for (int f = 0; f < 2; ++f) drop(ns.d_stream[p][f]);
-        drop(ns.d_vy[p]); drop(ns.d_stream_r[p]);
-        if (p != PG_PREC_BF16 && p != PG_PREC_FP16) drop(ns.d_stream_ro[p]);
-    }
-    drop(ns.d_stream_cr); drop(ns.d_stream_co); drop(ns.d_vyc);
+    (void)release_images(ns, keep, false);
     ns.fold_w.clear(); ns.fold_b.clear();
-    ns.host_stale = true;               // (refresh_host also re-forms d_bias, the bias table of the other kernels)
+    ns.host_stale = true;               // (refresh_host also re-forms IMG_BIAS, the bias table of the other kernels)
     return ensure_mode_streams(h, which, h->cfg.precision);
 }
 
@@ -900,7 +897,7 @@ int pg_set_framecodes(pg_handle* h, int which, const float* codes, int n_codes) 
     ns.n_codes = n_codes;
     PG_HIP(h, hipSetDevice(h->device));
     if (ns.d_codes) { PG_HIP(h, hipDeviceSynchronize()); PG_HIP(h, hipFree(ns.d_codes)); ns.d_codes = nullptr; }
-    if (ns.d_ycode) { PG_HIP(h, hipFree(ns.d_ycode)); ns.d_ycode = nullptr; }
+    PG_HIP(h, release_images(ns, ~image_bit(IMG_YCODE), false));
     PG_HIP(h, hipMalloc(reinterpret_cast<void**>(&ns.d_codes), ns.codes_host.size() * sizeof(float)));
     PG_HIP(h, hipMemcpy(ns.d_codes, ns.codes_host.data(), ns.codes_host.size() * sizeof(float), hipMemcpyHostToDevice));
     PG_FORWARD(h, pg_set_framecodes(hh, which, codes, n_codes));
@@ -1163,35 +1160,9 @@ int pg_query(const pg_handle* h, int precision, int64_t* stream_bytes, int64_t* 
     if (!h) return pg_fail(nullptr, PG_EINVAL, "pg_query: null handle");
     if (precision < 0 || precision >= PG_PREC_MODES) return PG_EINVAL;
     if (precision == PG_PREC_FP16M) precision = PG_PREC_FP16C;      // the pass that produces the returned maps
-    const bool fc = h->cfg.framecode_ch > 0;
-    const bool sa = is_shape_a(precision);
-    // 16-bit kernels: the factorised-view program (rays with >= 64 samples, the usual case)
-    const bool fact = use_fact(precision, FACT_MIN_S);
-    const bool compk = use_comp_kernel(precision, FACT_MIN_S, false);
-    if (sa && fact) {                        // 16x16x32 kernel: reported in 32x32x16 equivalents (32 768 FLOP each)
-        if (stream_bytes) *stream_bytes = (int64_t)(use_onchip(h, fc, 0, FACT_MIN_S) ? pgp::R::NCHUNK_OC : pgp::R::NCHUNK) * CHUNK_BYTES;
-        if (mfma_per_group) *mfma_per_group = pgp::R::MFMA16_PER_GROUP / 2;
-        return PG_OK;
-    }
-    if (compk && use_evalc2(FACT_MIN_S)) {       // out tiles over the waves (pg_evalc2.hip): no stream; 16x16x32 MFMAs in 32x32x16 equivalents
-        if (stream_bytes) *stream_bytes = (int64_t)pgp::T::TOTAL;
-        if (mfma_per_group) *mfma_per_group = pgp::T::MFMA16_PER_PASS / 2 / (pgp::T::PTS / 32);
-        return PG_OK;
-    }
-    if (compk && use_comp_rec(FACT_MIN_S)) {     // record variant of the compensated kernel (the usual case)
-        if (stream_bytes) *stream_bytes = (int64_t)(use_onchip(h, fc, 0, FACT_MIN_S, true) ? pgp::C::NCHUNK_OC : pgp::C::NCHUNK_R) * CHUNK_BYTES;
-        if (mfma_per_group) *mfma_per_group = pgp::C::MFMA_PER_GROUP_R;
-        return PG_OK;
-    }
-    if (stream_bytes)
-        *stream_bytes = (int64_t)(compk ? pgp::C::NCHUNK : sa ? pgp::A::NCHUNK
-                                     : (precision == PG_PREC_FP32 ? pgp::B::NCHUNK : pgp::B::NCHUNK_FOLD)) * CHUNK_BYTES;
-    if (mfma_per_group) {
-        // the fp32 / split kernels keep feature_linear and the direct view layer (13 + 4 out tiles)
-        const int64_t direct = pgp::A::MFMA_PER_GROUP(fc) + (NT + 1 + NTV - (NTV + 1)) * pgp::A::HU;
-        *mfma_per_group = compk ? pgp::C::MFMA_PER_GROUP(fc) : sa ? pgp::A::MFMA_PER_GROUP(fc)
-                             : (precision == PG_PREC_FP32 ? direct * 8 : (direct - NT * pgp::A::HU) * (precision == PG_PREC_FP16C ? 2 : 3));
-    }
+    const FormInfo& fi = FORMS[usual_form(h, precision)];
+    if (stream_bytes) *stream_bytes = fi.stream_bytes(precision);
+    if (mfma_per_group) *mfma_per_group = fi.mfma_per_group(precision, h->cfg.framecode_ch > 0);
     return PG_OK;
 }
 

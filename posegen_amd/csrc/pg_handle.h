@@ -9,31 +9,39 @@
 #include "../../include/posegen_hip.h"
 #include "pg_layout.h"
 
+// The packed weight images of one net.  pg_api.hip packs and uploads one on first use (ensure_image) and says which of them a
+// form of the fused kernel reads (FORMS).  The first four kinds exist per kernel arithmetic: id = kind + PG_PREC_*.
+enum Image : int {
+    IMG_NONE = -1,
+    IMG_DIRECT = 0,                                 // stream of the direct-view kernels: pg_eval16.hip (bf16 / fp16, shape A), pg_eval32.hip (the others, k-major shape B)
+    IMG_REC16 = IMG_DIRECT + PG_PREC_COUNT,         // 16x16x32 kernel with per-ray records (pg_eval16r.hip): stream
+    IMG_ONCHIP16 = IMG_REC16 + PG_PREC_COUNT,       // ... its on-chip variant (no per-ray records): stream
+    IMG_VY16 = IMG_ONCHIP16 + PG_PREC_COUNT,        // Y-stage weights of the per-ray record kernel (pg_rayrec.hip)
+    IMG_PER_PREC_END = IMG_VY16 + PG_PREC_COUNT,
+    IMG_COMP_DIRECT = IMG_PER_PREC_END,             // compensated-fp16 kernel (pg_evalc.hip), direct view layer: stream (shape C)
+    IMG_COMP_REC,                                   // ... record variant (REC): stream,
+    IMG_VYC,                                        // ... and the fp32 Y-stage weights of its record kernel
+    IMG_COMP_ONCHIP,                                // ... on-chip form of the record variant (OC): stream
+    IMG_C2,                                         // compensated-fp16 kernel with the out tiles over the waves (pg_evalc2.hip): weights (pg_program.h T)
+    IMG_YCODE,                                      // on-chip 16x16x32 variant with frame codes: Yc[n_codes + 1][128] = W_view[:, 904:920] codes[c]
+    IMG_BIAS16,                                     // 16-row bias table (the 16x16x32 kernel, pg_evalc2.hip)
+    IMG_BIAS,                                       // 32-row bias table (every other kernel)
+    IMG_COUNT
+};
+enum SrcMap : int { MAP_NONE = -1, MAP_ONCHIP16 = 0 /* one map for bf16 and fp16 */, MAP_C2, MAP_BIAS16, MAP_COUNT };
+
 struct NetState {
     bool loaded = false;
     std::vector<std::vector<float>> host;      // 24 tensors, reference order (see header)
     std::vector<float> codes_host;             // [n_codes+1,16]
     mutable std::vector<float> fold_w, fold_b; // W_view[:, :256] W_feature and its bias (NetTensors::fold), formed once per pg_load_weights
     int n_codes = 0;
-    uint8_t* d_stream[PG_PREC_COUNT][2] = {};     // [precision][factorised view layer]
-    uint8_t* d_vy[PG_PREC_COUNT] = {};            // Y-stage weights of the per-ray record kernel (pg_rayrec.hip)
-    uint8_t* d_stream_ro[PG_PREC_COUNT] = {};     // 16x16x32 kernel, on-chip variant (no per-ray records): stream
-    uint8_t* d_stream_r[PG_PREC_COUNT] = {};      // 16x16x32 kernel with per-ray records (pg_eval16r.hip): stream,
-    float* d_bias_s = nullptr;                    // ... and its 16-row bias table
-    float* d_ycode = nullptr;                     // on-chip variant with frame codes: Yc[n_codes + 1][128] = W_view[:, 904:920] codes[c] (ensure_ycode)
-    uint8_t* d_c2 = nullptr;                      // compensated-fp16 kernel with the out tiles over the waves (pg_evalc2.hip): weights (pg_program.h T)
-    uint8_t* d_stream_co = nullptr;               // compensated-fp16 kernel, on-chip form of the record variant (pg_evalc.hip OC): stream
-    uint8_t* d_stream_cr = nullptr;               // compensated-fp16 kernel, record variant (pg_evalc.hip REC): stream,
-    float* d_vyc = nullptr;                       // ... and the fp32 Y-stage weights of its record kernel
-    size_t stream_bytes[PG_PREC_COUNT][2] = {};
-    float* d_bias = nullptr;
+    struct Slot { uint8_t* d = nullptr; size_t bytes = 0; } img[IMG_COUNT];
     float* d_codes = nullptr;
     // pg_load_weights_device: the net's tensors as one flat device vector (NetTensors::layout; + the folded view layer), the
     // source maps of the images that are re-formed by a gather, and whether `host` lags the device copy
     float* d_src = nullptr;
-    int32_t* d_map_ro = nullptr;   size_t n_map_ro = 0;      // on-chip stream of the 16x16x32 kernel (one map for bf16 and fp16)
-    int32_t* d_map_c2 = nullptr;   size_t n_map_c2 = 0;      // pg_evalc2.hip's weight image
-    int32_t* d_map_bias_s = nullptr;
+    int32_t* d_map[MAP_COUNT] = {};
     float* d_vwide = nullptr;      // multires_views = 0: the caller's view weight widened to the 4-band layout (pg_launch_widen_views)
     bool host_stale = false;
 };
