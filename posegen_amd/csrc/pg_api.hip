@@ -182,12 +182,17 @@ enum Form {
 };
 
 // The process's switches (A/B, debugging), read once; "0" turns a form off
+// Rotation of the pass walk per round (pg_device.h PassWalk), in passes.  Odd, and 99 / 256, 99 / 128 and 35 / 64 (what is left of it
+// on frames whose rows are 256, 128 or 64 passes) all have small partial quotients: the strips a workgroup visits in the few dozen
+// rounds of a frame are spread evenly over the row, not clustered.
+constexpr int PASS_WALK_RHO = 99;
 struct Switches {
     bool view_fact = true;          // POSEGEN_VIEW_FACT=0: the direct 32x32x16 kernel (pg_eval16.hip) for every 16-bit call
     bool comp_kernel = true;        // POSEGEN_COMP_KERNEL=0: PG_PREC_FP16C in the k-major kernel of pg_eval32.hip, same arithmetic
     bool comp_rec = true;           // POSEGEN_COMP_REC=0: the direct form of pg_evalc.hip whatever the sample count
     bool evalc2 = true;             // POSEGEN_EVALC2=0: keeps fp16c calls on pg_evalc.hip (and the record / on-chip forms' tests)
     int onchip = PG_ONCHIP_AUTO;    // POSEGEN_ONCHIP = 0 / 1 / 2: the pg_set_onchip mode a new handle starts in
+    int pass_walk = PASS_WALK_RHO;  // POSEGEN_PASS_WALK=0: the static pass walk of the kernels with limb masks (pg_device.h PassWalk); n > 0: rotation n
 };
 const Switches& switches() {
     static const Switches sw = [] {
@@ -199,6 +204,7 @@ const Switches& switches() {
         s.evalc2 = !off("POSEGEN_EVALC2");
         const char* e = std::getenv("POSEGEN_ONCHIP");
         s.onchip = e && e[0] == '0' ? PG_ONCHIP_RECORDS : e && e[0] == '2' ? PG_ONCHIP_ALWAYS : PG_ONCHIP_AUTO;
+        if (const char* w = std::getenv("POSEGEN_PASS_WALK")) s.pass_walk = std::max(0, std::atoi(w));
         return s;
     }();
     return sw;
@@ -552,6 +558,7 @@ int launch_eval_one(pg_handle* h, void* stream, int which, long long n, int S, c
     long long max_wg = (long long)h->n_cu * fi.wgs_per_cu();
     if (wg_cap > 0 && wg_cap < max_wg) max_wg = wg_cap;
     const int grid = (int)(iters < max_wg ? iters : max_wg);
+    a.walk_rho = switches().pass_walk % grid;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     auto get = [&](hipEvent_t& ev) {
         if (!h->ev_free.empty()) { ev = h->ev_free.back(); h->ev_free.pop_back(); return hipSuccess; }
@@ -1084,6 +1091,27 @@ int pg_debug_widen_views(const float* view_w, int64_t rows, int64_t cols, int fr
         widen_view_w(view_w, framecode_ch, out);
     }
     return PG_OK;
+}
+
+// Test aid (not in the header): every workgroup of a grid of G walks its passes of an (n_rays, S) call through pgd::PassWalk on the
+// host.  Returns the number of passes whose (first point, ray, sample) differ from the integer division plus the number of passes not
+// taken exactly once; -1: bad arguments.
+extern "C" long long pg_debug_pass_walk(long long n_rays, int S, int pts, int G, int rho) {
+    if (n_rays <= 0 || S <= 0 || pts <= 0 || G <= 0 || rho < 0 || rho >= G) return -1;
+    const long long n_iters = (n_rays * S + pts - 1) / pts;
+    std::vector<uint8_t> taken((size_t)n_iters, 0);
+    long long bad = 0;
+    for (int b = 0; b < G; ++b) {
+        int prev = -1;
+        for (pgd::PassWalk w(S, pts, b, G, rho); w.it < n_iters; w.advance(), w.peek()) {
+            const long long p0 = (long long)w.it * pts;
+            if (w.p0 != p0 || w.r0 != p0 / S || w.off0 != p0 % S || w.it <= prev || w.it / G != w.itn / G - 1 || taken[(size_t)w.it]) ++bad;
+            taken[(size_t)w.it] = 1;
+            prev = w.it;
+        }
+    }
+    for (long long i = 0; i < n_iters; ++i) bad += !taken[(size_t)i];
+    return bad;
 }
 
 int pg_debug_pack_vy(const float* const* tensors, const int64_t* shapes, int n_tensors, int framecode_ch,

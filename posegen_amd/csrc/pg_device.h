@@ -39,6 +39,7 @@ struct EvalArgs {
     float tau_v, tau_d;
     int dbg_stage;            // which activation `dbg` receives (see pg_stage_eval)
     int far_skip;             // 1: limbs out of cutoff range are skipped (pg_eval16r.hip, pg_evalc.hip REC); 0: every limb computed
+    int walk_rho;             // PassWalk: rotation of the pass walk per round, < grid (0: the static walk); kernels with limb masks only
 };
 
 // Kernel arguments of the per-ray record kernel (pg_rayrec.hip) in front of a factorised 16-bit launch.
@@ -55,6 +56,54 @@ struct RecArgs {
     int n_rays;
     int n_codes;
     int S;
+};
+
+// The passes of one workgroup of a persistent grid of G workgroups, for the kernels whose passes cost what their data
+// asks for (limb masks: pg_eval16r.hip, pg_evalc.hip, pg_evalc2.hip).  Round k of the grid is the passes k G .. k G + G - 1;
+// in round k workgroup b takes pass k G + ((b + k rho) mod G).  rho = 0 is the static walk `it = b + k G`: with rays in
+// row-major frame order and a row a whole number of passes that divides G (or a multiple of it), a workgroup then stays on
+// one column strip of the frame for the whole launch, and the strips that cross the body cost more than the others.  With
+// rho != 0 a workgroup's strip moves by rho passes per round, so every workgroup sees all of them.  Each round is a
+// permutation of the workgroups whatever rho is: every pass runs exactly once, and no pass depends on who runs it.
+// From a pass at place c of its round the next one is G + rho passes on, or rho passes on where c + rho wraps past G:
+// two constant steps, so the pass's first point p0 = sample off0 of ray r0 advances without a division per pass (a 64-bit
+// divide is ~150 VALU instructions).  Everything here is wave-uniform.  Host and device: pg_debug_pass_walk walks it on the host.
+struct PassWalk {
+    int S, G, rho, pts;
+    int dq[2], dr[2];           // rays and samples of the two steps: [0] G + rho passes, [1] rho passes
+    int it, c;                  // this pass, and its place in its round (it = k G + c)
+    long long p0;               // its first point = sample off0 of ray r0
+    int r0, off0;
+    int itn, cn, r0n, off0n;    // the workgroup's next pass (peek)
+    long long p0n;
+    static __host__ __device__ __forceinline__ int uni(int v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        return __builtin_amdgcn_readfirstlane(v);
+#else
+        return v;
+#endif
+    }
+    __host__ __device__ __forceinline__ PassWalk(int S_, int pts_, int b, int G_, int rho_) : S(S_), G(G_), rho(rho_), pts(pts_) {
+        const long long s0 = (long long)pts * (G + rho), s1 = (long long)pts * rho;
+        dq[0] = uni((int)(s0 / S)); dr[0] = uni((int)(s0 % S));
+        dq[1] = uni((int)(s1 / S)); dr[1] = uni((int)(s1 % S));
+        it = c = b;
+        p0 = (long long)b * pts;
+        r0 = uni((int)(p0 / S));
+        off0 = uni((int)(p0 - (long long)r0 * S));
+        peek();
+    }
+    __host__ __device__ __forceinline__ void peek() {
+        const int wrap = c + rho >= G ? 1 : 0;
+        const int di = wrap ? rho : G + rho;
+        itn = it + di;
+        cn = c + rho - (wrap ? G : 0);
+        p0n = p0 + (long long)di * pts;
+        off0n = off0 + dr[wrap];
+        r0n = r0 + dq[wrap];
+        if (off0n >= S) { off0n -= S; ++r0n; }
+    }
+    __host__ __device__ __forceinline__ void advance() { it = itn; c = cn; p0 = p0n; r0 = r0n; off0 = off0n; }
 };
 
 // slot -> joint tables of pg_layout.h (PERM16, PERMC) as a device lookup at a run-time index: 24 x 5 bits in two constants

@@ -398,14 +398,12 @@ __global__ __launch_bounds__(NTHR, 2) void eval16r_kernel(const EvalArgs a) {
     if (wave >= NWAVE / 2) __builtin_amdgcn_s_setprio(PG_YOUNG_PRIO);
 #endif
     const unsigned bbase = lds_addr_of(bias) + 16 * g;          // this lane group's rows of bias tile 0
-    // Ray bookkeeping without a division per pass (a 64-bit divide is ~150 VALU instructions, and both waves of a
-    // SIMD would run it at the same time): the pass's first point is sample `off0` of ray `r0`; a pass later both
-    // advance by the constant step of the persistent grid.
-    const long long step = (long long)PTS * gridDim.x;
-    const int dq = __builtin_amdgcn_readfirstlane((int)(step / a.S)), dr = __builtin_amdgcn_readfirstlane((int)(step % a.S));
-    long long p0 = (long long)blockIdx.x * PTS;
-    int r0 = __builtin_amdgcn_readfirstlane((int)(p0 / a.S));
-    int off0 = __builtin_amdgcn_readfirstlane((int)(p0 - (long long)r0 * a.S));
+    // Which passes this workgroup runs, and ray bookkeeping without a division per pass (both waves of a SIMD would run
+    // it at the same time): the pass's first point is sample `off0` of ray `r0`; a pass later both advance by one of the
+    // two constant steps of the walk (pg_device.h PassWalk).
+    PassWalk pw(a.S, PTS, (int)blockIdx.x, (int)gridDim.x, a.walk_rho);
+    long long p0 = pw.p0;
+    int r0 = pw.r0, off0 = pw.off0;
     // (a, b) of the first pass's rays into buffer 0; every later pass finds its own fetched (OC: formed) a pass ahead
     if (OC) {
         lds_barrier();                      // the bone rows are in LDS
@@ -457,7 +455,13 @@ __global__ __launch_bounds__(NTHR, 2) void eval16r_kernel(const EvalArgs a) {
 #if defined(PG_STAMPS)
     unsigned long long stamps[12];
 #endif
-    for (int it = blockIdx.x; it < a.n_iters; it += gridDim.x) {
+#if defined(PG_WALK_STAMPS)
+    // how even the walk is (tools/diag_pass_walk.py): the workgroup's clock at entry and exit, its passes and its limbs in range
+    unsigned long long walk_t0;
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(walk_t0) :: "memory");
+    unsigned walk_passes = 0, walk_limbs = 0;
+#endif
+    for (int it = pw.it; it < a.n_iters; it = pw.it) {
         PG_STAMP(0);
         // a per-pass copy of the lane index: LDS addresses derived from it are recomputed per pass (a few VALU operations)
         // instead of being hoisted out of the pass loop and spilled -- the kernel sits at exactly 256 registers
@@ -481,9 +485,8 @@ __global__ __launch_bounds__(NTHR, 2) void eval16r_kernel(const EvalArgs a) {
             abp[c] = opaque_ptr(reinterpret_cast<const float*>(smem + LDSR_AB + abuf * LDS_AB_BYTES + myr[c] * REC_AB_BYTES) + JG * g_p * 8);
         }
         // the next pass of this workgroup
-        const int itn = min(it + (int)gridDim.x, a.n_iters - 1);
-        int off0n = off0 + dr, r0n = r0 + dq;
-        if (off0n >= a.S) { off0n -= a.S; ++r0n; }
+        const int itn = min(pw.itn, a.n_iters - 1);
+        const int off0n = pw.off0n, r0n = pw.r0n;
         const float* cutd = opaque_ptr(cut + J + JG * g_p);
         const QFromAB q0{abp[0], zz[0]}, q1{abp[1], zz[1]};
         float cutv[JG];                         // the lane group's folded cutoff constants (6 registers)
@@ -505,6 +508,9 @@ __global__ __launch_bounds__(NTHR, 2) void eval16r_kernel(const EvalArgs a) {
             }
             farmask = __builtin_amdgcn_readfirstlane(a.far_skip ? farmask : 0);
         }
+#endif
+#if defined(PG_WALK_STAMPS)
+        walk_passes += 1; walk_limbs += (unsigned)__builtin_popcount(~gmask & 63);
 #endif
         if (CNT && lane == 0) {
             if (wave == 0) { atomicAdd(reinterpret_cast<unsigned*>(a.dbg), 1u); atomicAdd(reinterpret_cast<unsigned*>(a.dbg) + 1, (unsigned)__builtin_popcount(gmask)); }
@@ -626,7 +632,7 @@ __global__ __launch_bounds__(NTHR, 2) void eval16r_kernel(const EvalArgs a) {
         // prefetch pointer wraps to the head of the stream two chunk entries from here and must know it by then
         int gmask_n = 0;
 #if !defined(PG_NO_FAR_SKIP)
-        gmask_n = pass_far_mask(smem + LDSR_AB + (abuf ^ 1) * LDS_AB_BYTES, rays_of_pass(p0 + step, off0n),
+        gmask_n = pass_far_mask(smem + LDSR_AB + (abuf ^ 1) * LDS_AB_BYTES, rays_of_pass(pw.p0n, off0n),
                                 opaque_ptr(cut + 2 * J + JG * g_p), g_p, lane_p & 15);
         if (!a.far_skip) gmask_n = 0;
 #endif
@@ -698,7 +704,8 @@ __global__ __launch_bounds__(NTHR, 2) void eval16r_kernel(const EvalArgs a) {
             if (i + 16 <= last) *reinterpret_cast<float4*>(a.raw + (p0 + i + 16) * 4) = make_float4(c1[0], c1[1], c1[2], sigma[1]);
         }
         abuf ^= 1;
-        p0 += step; r0 = r0n; off0 = off0n;
+        pw.advance(); pw.peek();
+        p0 = pw.p0; r0 = pw.r0; off0 = pw.off0;
         gmask = gmask_n;
         PG_STAMP(8);
 #if defined(PG_STAMPS)
@@ -711,6 +718,16 @@ __global__ __launch_bounds__(NTHR, 2) void eval16r_kernel(const EvalArgs a) {
 #endif
     }
     st.drain();
+#if defined(PG_WALK_STAMPS)
+    if (CNT && tid == 0) {      // (record b of the launch: behind the 16 words of the CNT counters)
+        unsigned long long walk_t1;
+        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(walk_t1) :: "memory");
+        unsigned* rec = reinterpret_cast<unsigned*>(a.dbg) + 16 + 8 * blockIdx.x;
+        rec[0] = (unsigned)walk_t0; rec[1] = (unsigned)(walk_t0 >> 32);
+        rec[2] = (unsigned)walk_t1; rec[3] = (unsigned)(walk_t1 >> 32);
+        rec[4] = walk_passes; rec[5] = walk_limbs;
+    }
+#endif
 }
 
 template <typename V, bool FC, bool TAPS, bool OC, bool CNT = false, bool PP = false>

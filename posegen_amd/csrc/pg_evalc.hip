@@ -615,15 +615,13 @@ __global__ __launch_bounds__(NTHR_C, 1) void evalc_kernel(const EvalArgs a) {
 
     // record variant: ray bookkeeping without a division per pass (a 64-bit divide is ~150 VALU instructions and
     // nothing overlaps them with one wave per SIMD): the pass's first point is sample `off0` of ray `r0`, and both
-    // advance by the constant step of the persistent grid
-    const long long step = (long long)PTS_C * gridDim.x;
-    int dq = 0, dr = 0, r0 = 0, off0 = 0, abuf = 0;
-    long long p0 = (long long)blockIdx.x * PTS_C;
+    // advance by one of the two constant steps of the workgroup's pass walk (pg_device.h PassWalk; the direct form has no limb masks,
+    // its passes all cost the same: the static walk)
+    PassWalk pw(a.S, PTS_C, (int)blockIdx.x, (int)gridDim.x, REC ? a.walk_rho : 0);
+    int r0 = pw.r0, off0 = pw.off0, abuf = 0;
+    long long p0 = pw.p0;
     const uint8_t* rec_ab = reinterpret_cast<const uint8_t*>(a.rec_ab);
     if (REC) {
-        dq = __builtin_amdgcn_readfirstlane((int)(step / a.S)); dr = __builtin_amdgcn_readfirstlane((int)(step % a.S));
-        r0 = __builtin_amdgcn_readfirstlane((int)(p0 / a.S));
-        off0 = __builtin_amdgcn_readfirstlane((int)(p0 - (long long)r0 * a.S));
         // (a, b) of the first pass's rays into buffer 0; every later pass finds its own fetched (OC: formed) a pass ahead
         if (OC) {
             lds_barrier();                      // the bone rows are in LDS
@@ -660,7 +658,7 @@ __global__ __launch_bounds__(NTHR_C, 1) void evalc_kernel(const EvalArgs a) {
 #if defined(PG_STAMPS)
     unsigned long long stamps[14];
 #endif
-    for (int it = blockIdx.x; it < a.n_iters; it += gridDim.x) {
+    for (int it = pw.it; it < a.n_iters; it = pw.it) {
         PG_STAMP(0);
 #if defined(PG_STAMPS)
         { unsigned long long t_; asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); stamps[10] = t_; }
@@ -681,8 +679,7 @@ __global__ __launch_bounds__(NTHR_C, 1) void evalc_kernel(const EvalArgs a) {
             nrm1 = (tl_ >= S1) + (tl_ >= S2);
             myr = min((ti >= S1) + (ti >= S2), nrm1);
             ab = opaque_ptr(reinterpret_cast<const float*>(smem + LDSC_AB + abuf * ABSZ + myr * REC_AB_BYTES) + JH * h * 8);
-            off0n = off0 + dr; r0n = r0 + dq;
-            if (off0n >= a.S) { off0n -= a.S; ++r0n; }
+            off0n = pw.off0n; r0n = pw.r0n;
         } else {
             const long long plast = min(p0 + PTS_C - 1, a.n_points - 1);
             r0 = (int)(p0 / a.S);
@@ -826,7 +823,7 @@ __global__ __launch_bounds__(NTHR_C, 1) void evalc_kernel(const EvalArgs a) {
         if (REC) {      // the NEXT pass's mask, from its (a, b) records (in LDS since this pass's second chunk entry): the ring's
                         // prefetch pointer wraps to the head of the stream within the next segments and must know it by then
 #if !defined(PG_NO_FAR_SKIP)
-            gmask_n = pass_far_mask_c(smem + LDSC_AB + (abuf ^ 1) * ABSZ, rays_of_pass(p0 + step, off0n),
+            gmask_n = pass_far_mask_c(smem + LDSC_AB + (abuf ^ 1) * ABSZ, rays_of_pass(pw.p0n, off0n),
                                       opaque_ptr(cut + 2 * J + JH * h), h, pt);
             if (!a.far_skip) gmask_n = 0;
 #endif
@@ -906,7 +903,7 @@ __global__ __launch_bounds__(NTHR_C, 1) void evalc_kernel(const EvalArgs a) {
         }
         PG_STAMP(8);
         // ---- rgb head ----
-        if (REC) nx_z = a.z[min(p0 + step + wave * 32 + pt, a.n_points - 1)];       // in flight through the rgb head and the pass boundary
+        if (REC) nx_z = a.z[min(pw.p0n + wave * 32 + pt, a.n_points - 1)];       // in flight through the rgb head and the pass boundary
         f32x16 accr = load_bias(bias, TB_RGB, h);
         auto srcV = [&](int u, int e) { return av[1 + (u >> 1)][8 * (u & 1) + e]; };
 #if defined(PG_ABL_NORGB)       // timing ablation only (wrong results): the rgb head's chunk is entered and refilled, its work skipped
@@ -924,7 +921,8 @@ __global__ __launch_bounds__(NTHR_C, 1) void evalc_kernel(const EvalArgs a) {
             *reinterpret_cast<float4*>(a.raw + gp * 4) = make_float4(accr[0], accr[1], accr[2], sigma);
 #endif
         if (REC) { abuf ^= 1; r0 = r0n; off0 = off0n; gmask = gmask_n; }
-        p0 += step;
+        pw.advance(); pw.peek();
+        p0 = pw.p0;
 #if !defined(PG_STAMPS_RGB)
         PG_STAMP(9);
 #endif

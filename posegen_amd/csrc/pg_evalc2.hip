@@ -373,12 +373,10 @@ __global__ __launch_bounds__(NTHR2, 2) void evalc2_kernel(const EvalArgs a) {
     float s129 = (float)COMP_S;
     asm volatile("" : "+s"(s129));
 
-    // ---- ray bookkeeping (no division per pass): the pass's first point is sample off0 of ray r0 ----
-    const long long step = (long long)TT::PTS * gridDim.x;
-    const int dq = __builtin_amdgcn_readfirstlane((int)(step / a.S)), dr = __builtin_amdgcn_readfirstlane((int)(step % a.S));
-    long long p0 = (long long)blockIdx.x * TT::PTS;
-    int r0 = __builtin_amdgcn_readfirstlane((int)(p0 / a.S));
-    int off0 = __builtin_amdgcn_readfirstlane((int)(p0 - (long long)r0 * a.S));
+    // ---- the workgroup's passes (pg_device.h PassWalk) and ray bookkeeping (no division per pass): the pass's first point is sample off0 of ray r0 ----
+    PassWalk pw(a.S, TT::PTS, (int)blockIdx.x, (int)gridDim.x, a.walk_rho);
+    long long p0 = pw.p0;
+    int r0 = pw.r0, off0 = pw.off0;
     const int S1 = a.S, S2 = 2 * a.S, S3 = 3 * a.S, S4 = 4 * a.S;
     auto ray_of = [&](int t) { return (t >= S1) + (t >= S2) + (t >= S3) + (t >= S4); };
     // one (ray k of the pass that starts at ray rr, joint slot sl) row per item
@@ -428,7 +426,7 @@ __global__ __launch_bounds__(NTHR2, 2) void evalc2_kernel(const EvalArgs a) {
 #if defined(PG_STAMPS)
     unsigned long long stamp_acc[12] = {}, stamp_prev = 0;
 #endif
-    for (int it = blockIdx.x; it < a.n_iters; it += gridDim.x) {
+    for (; pw.it < a.n_iters; pw.advance(), pw.peek()) {
 #if defined(PG_STAMPS)
         { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); stamp_prev = t_; }
 #endif
@@ -449,8 +447,7 @@ __global__ __launch_bounds__(NTHR2, 2) void evalc2_kernel(const EvalArgs a) {
         const int myr = min(ray_of(off0 + i_pt), nrm1);
         const float zz = nx_z;
         const float* abp = opaque_ptr(reinterpret_cast<const float*>(smem + L_AB + abuf * L_ABSZ + myr * REC_AB_BYTES) + JG * g_p * 8);
-        int off0n = off0 + dr, r0n = r0 + dq;
-        if (off0n >= a.S) { off0n -= a.S; ++r0n; }
+        const int off0n = pw.off0n, r0n = pw.r0n;
         auto local = [&](int jj, float& qx, float& qy, float& qz) {
             const float4 lo = *reinterpret_cast<const float4*>(abp + jj * 8);
             const float4 hi = *reinterpret_cast<const float4*>(abp + jj * 8 + 4);
@@ -949,7 +946,7 @@ __global__ __launch_bounds__(NTHR2, 2) void evalc2_kernel(const EvalArgs a) {
             av[0][cc] = mma(e1, b3, av[0][cc]);
             av[1][cc] = mma(e3, b3, av[1][cc]);
         }
-        nx_z = a.z[min(p0 + step + 16 * wave + col_p, a.n_points - 1)];     // the next pass's depth: in flight through the rgb head
+        nx_z = a.z[min(pw.p0n + 16 * wave + col_p, a.n_points - 1)];     // the next pass's depth: in flight through the rgb head
         // rgb A fragments: the lanes of rows 0..2 hold weights, the others read the zero entry
         a128 rgA[VW / 32][2];
         {
@@ -991,7 +988,7 @@ __global__ __launch_bounds__(NTHR2, 2) void evalc2_kernel(const EvalArgs a) {
                 *reinterpret_cast<float4*>(a.raw + (p0 + ipt3) * 4) = make_float4(c3[0], c3[1], c3[2], al[0]);
         }
         abuf ^= 1;
-        p0 += step; r0 = r0n; off0 = off0n;
+        p0 = pw.p0n; r0 = r0n; off0 = off0n;
         C2_STAMP(10);
 #if defined(PG_STAMPS)
         stamp_acc[11] += 1;
