@@ -383,7 +383,9 @@ int pg_stage_sample_coarse(pg_handle* h, void* stream, int64_t n, const float* r
  * dbg_stage 97 (measurement aid; the 16-bit and compensated modes on rays with >= 64 samples): dbg is an array of >= 3
  * ZEROED unsigned counters instead, to which the launch adds: [0] workgroup passes, [1] limbs left out of whole passes
  * (of 6 per pass), [2] limbs left out per wave / column tile (of 48 per pass) -- what the cutoff embedding's limb masks
- * (pg_set_far_skip) are worth on this call. */
+ * (pg_set_far_skip) are worth on this call; [3] empty waves (of 8 per pass in pg_eval16r.hip: every valid point of the wave
+ * has sigma <= 0; the other kernels leave it 0), [4] those of them that left the colour branch out (pg_set_empty_skip).  A
+ * stage-97 call runs as a render call's launch would: `raw` holds rgb = 0 for the points of the waves counted in [4]. */
 int pg_stage_eval(pg_handle* h, void* stream, int which_net, int64_t n, int n_samples,
                   const float* ray_batch, const float* z, const float* skts,
                   int64_t pose_stride, const float* cams, float* raw, float* dbg, int dbg_stage);
@@ -410,6 +412,20 @@ int pg_stage_composite(pg_handle* h, void* stream, int64_t n, int n_samples,
  * cutoff_dist + 24 / (tau log2 e) has a cutoff weight 1 - sigmoid(tau (v - c)) below 2^-24, cutoff_embedder.py:139-146:
  * DESIGN.md 2.1).  Default on.  The two settings agree to ~1e-7 per skipped product. */
 int pg_set_far_skip(pg_handle* h, int on);
+
+/* The fused 16x16x32 kernel (pg_eval16r.hip; bf16 / fp16 renders of rays with >= 64 samples) leaves the colour branch --
+ * view layer, rgb head -- out for a wave whose 32 points all have sigma <= 0 and writes rgb_raw = 0 for them: under the
+ * ReLU density such a point composites with weight exactly +0, so the maps are bitwise the same.  Only launches of
+ * pg_render_rays / pg_render_rays_train (and the frame entry points on top of them) whose raw nobody else sees do so: ReLU
+ * density, no density noise (noise0 / noise1) in the call, no raw_coarse / raw_fine output.  on = 0 switches it off (tests,
+ * A/B); default on.  One difference, deliberate: a non-finite colour pre-activation at an empty point gave NaN maps
+ * (0 x NaN) before and gives finite ones now. */
+int pg_set_empty_skip(pg_handle* h, int on);
+
+/* Measurement aid: counts = >= 16 ZEROED 32-bit device words (or NULL: off).  While set, every pg_eval16r.hip launch of a
+ * render call on this handle that takes the on-chip form with one pose and no frame codes adds the counters of
+ * pg_stage_eval's dbg_stage 97 to them -- what the call's own launches skipped.  The caller owns the memory. */
+int pg_debug_wave_counts(pg_handle* h, uint32_t* counts);
 
 /* New values of a loaded net's 24 tensors (pg_load_weights order, fp32, DEVICE pointers; and of the frame codes [n_codes,16]
  * when the handle has them) between optimiser steps and a render -- the reference renders with the module it trains

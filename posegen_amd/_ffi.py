@@ -75,6 +75,8 @@ PROTOTYPES = {
     "pg_set_precision": (C.c_int, [C.c_void_p, C.c_int]),
     "pg_set_chunk": (C.c_int, [C.c_void_p, C.c_int]),
     "pg_set_far_skip": (C.c_int, [C.c_void_p, C.c_int]),
+    "pg_set_empty_skip": (C.c_int, [C.c_void_p, C.c_int]),
+    "pg_debug_wave_counts": (C.c_int, [C.c_void_p, C.c_void_p]),
     "pg_set_onchip": (C.c_int, [C.c_void_p, C.c_int]),
     "pg_load_weights_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_int]),
     "pg_set_train_precision": (C.c_int, [C.c_void_p, C.c_int]),

@@ -192,6 +192,7 @@ struct Switches {
     bool comp_rec = true;           // POSEGEN_COMP_REC=0: the direct form of pg_evalc.hip whatever the sample count
     bool evalc2 = true;             // POSEGEN_EVALC2=0: keeps fp16c calls on pg_evalc.hip (and the record / on-chip forms' tests)
     int onchip = PG_ONCHIP_AUTO;    // POSEGEN_ONCHIP = 0 / 1 / 2: the pg_set_onchip mode a new handle starts in
+    bool empty_skip = true;         // POSEGEN_EMPTY_SKIP=0: the pg_set_empty_skip setting a new handle starts in (A/B on one library)
     int pass_walk = PASS_WALK_RHO;  // POSEGEN_PASS_WALK=0: the static pass walk of the kernels with limb masks (pg_device.h PassWalk); n > 0: rotation n
 };
 const Switches& switches() {
@@ -202,6 +203,7 @@ const Switches& switches() {
         s.comp_kernel = !off("POSEGEN_COMP_KERNEL");
         s.comp_rec = !off("POSEGEN_COMP_REC");
         s.evalc2 = !off("POSEGEN_EVALC2");
+        s.empty_skip = !off("POSEGEN_EMPTY_SKIP");
         const char* e = std::getenv("POSEGEN_ONCHIP");
         s.onchip = e && e[0] == '0' ? PG_ONCHIP_RECORDS : e && e[0] == '2' ? PG_ONCHIP_ALWAYS : PG_ONCHIP_AUTO;
         if (const char* w = std::getenv("POSEGEN_PASS_WALK")) s.pass_walk = std::max(0, std::atoi(w));
@@ -502,12 +504,23 @@ int check_ready(pg_handle* h, bool need_fine) {
     return PG_OK;
 }
 
+// EvalArgs::skip_empty (pg_eval16r.hip): a wave whose points all have sigma <= 0 may leave the colour branch out only when
+// nothing can tell -- `colour_free`: the caller composites the launch's raw without density noise and hands the raw itself
+// to nobody (no raw output, no debug tap, not the training forward); the density is the ReLU one on a positive scale, so
+// sigma <= 0 is alpha = 0 exactly (softplus is positive everywhere); and the switch is on (pg_set_empty_skip).
+bool skip_empty_ok(const pg_handle* h, bool colour_free) {
+    return colour_free && h->empty_skip && h->cfg.density_act == PG_ACT_RELU && h->cfg.density_scale > 0.0f;
+}
+
 int launch_eval_one(pg_handle* h, void* stream, int which, long long n, int S, const float* rays, const float* z,
                     const float* skts, long long pose_stride, const float* cams, float* raw, float* dbg, int dbg_stage,
-                    const float* points, const float* pnoise, bool guide_pass) {
+                    const float* points, const float* pnoise, bool guide_pass, bool colour_free) {
     const int prec = pass_precision(h->cfg.precision, guide_pass);
     const bool fc = h->cfg.framecode_ch > 0;
-    const Form form = pick_form(CallFacts{prec, S, pose_stride, fc, points != nullptr, pnoise != nullptr, dbg != nullptr, dbg_stage, h->onchip_mode}, switches());
+    Form form = pick_form(CallFacts{prec, S, pose_stride, fc, points != nullptr, pnoise != nullptr, dbg != nullptr, dbg_stage, h->onchip_mode}, switches());
+    // pg_debug_wave_counts: a launch of the on-chip form that the counting instantiation covers (one pose, no frame codes) adds
+    // its counters to the caller's words -- what a render call's own launches did, not a stage call beside it
+    if (!dbg && h->wave_counts && form == F_ONCHIP16 && pose_stride == 0 && !fc) { dbg = reinterpret_cast<float*>(h->wave_counts); dbg_stage = 97; }
     const FormInfo& fi = FORMS[form];
     const int y_bytes = fi.rec_y_bytes;
     int rc = ensure_form_images(h, which, form, prec, fc);
@@ -547,6 +560,7 @@ int launch_eval_one(pg_handle* h, void* stream, int which, long long n, int S, c
     a.tau_d = h->tau[1];
     a.dbg_stage = dbg_stage;
     a.far_skip = h->far_skip ? 1 : 0;
+    a.skip_empty = skip_empty_ok(h, colour_free) ? 1 : 0;
     const int pts = fi.points_per_pass();
     if (!points && S < pts / (MAXR - 1))      // explicit points are one pseudo ray: a pass touches one slot
         return pg_fail(h, PG_EINVAL, "N_samples=%d too small: the fused kernel needs >= %d samples per ray", S, pts / (MAXR - 1));
@@ -610,16 +624,16 @@ int launch_eval_one(pg_handle* h, void* stream, int which, long long n, int S, c
 // of growing with the call (a 2048 x 2048 frame would ask for 72 GB).  POSEGEN_REC_BATCH overrides the size (tests).
 int launch_eval(pg_handle* h, void* stream, int which, long long n, int S, const float* rays, const float* z,
                 const float* skts, long long pose_stride, const float* cams, float* raw, float* dbg, int dbg_stage = 0,
-                const float* points = nullptr, const float* pnoise = nullptr, bool guide_pass = false) {
+                const float* points = nullptr, const float* pnoise = nullptr, bool guide_pass = false, bool colour_free = false) {
     long long batch = 1ll << 19;
     if (const char* e = std::getenv("POSEGEN_REC_BATCH")) { const long long v = std::atoll(e); if (v >= 64) batch = v; }
     if (points || dbg || n <= batch)
-        return launch_eval_one(h, stream, which, n, S, rays, z, skts, pose_stride, cams, raw, dbg, dbg_stage, points, pnoise, guide_pass);
+        return launch_eval_one(h, stream, which, n, S, rays, z, skts, pose_stride, cams, raw, dbg, dbg_stage, points, pnoise, guide_pass, colour_free);
     for (long long r0 = 0; r0 < n; r0 += batch) {
         const long long m = std::min(batch, n - r0);
         const int rc = launch_eval_one(h, stream, which, m, S, rays + r0 * 11, z + r0 * S, skts + r0 * pose_stride, pose_stride,
                                        cams ? cams + r0 : nullptr, raw + r0 * S * 4, nullptr, 0, nullptr,
-                                       pnoise ? pnoise + r0 * S * 3 : nullptr, guide_pass);
+                                       pnoise ? pnoise + r0 * S * 3 : nullptr, guide_pass, colour_free);
         if (rc) return rc;
     }
     return PG_OK;
@@ -669,7 +683,7 @@ int pg_create(const pg_config* cfg, int n_devices, const int* device_ids, pg_han
     if (cfg->density_act != PG_ACT_RELU && cfg->density_act != PG_ACT_SOFTPLUS)
         return pg_fail(nullptr, PG_EINVAL, "pg_create: density_act must be PG_ACT_RELU or PG_ACT_SOFTPLUS, got %d", cfg->density_act);
     pg_handle* h = new (std::nothrow) pg_handle();
-    if (h) h->onchip_mode = switches().onchip;
+    if (h) { h->onchip_mode = switches().onchip; h->empty_skip = switches().empty_skip; }
     if (!h) return pg_fail(nullptr, PG_ENOMEM, "pg_create: out of host memory");
     h->cfg = *cfg;
     h->device = device_ids ? device_ids[0] : 0;
@@ -935,6 +949,19 @@ int pg_set_far_skip(pg_handle* h, int on) {
     if (!h) return pg_fail(nullptr, PG_EINVAL, "pg_set_far_skip: null handle");
     h->far_skip = on != 0;
     PG_FORWARD(h, pg_set_far_skip(hh, on));
+    return PG_OK;
+}
+
+int pg_set_empty_skip(pg_handle* h, int on) {
+    if (!h) return pg_fail(nullptr, PG_EINVAL, "pg_set_empty_skip: null handle");
+    h->empty_skip = on != 0;
+    PG_FORWARD(h, pg_set_empty_skip(hh, on));
+    return PG_OK;
+}
+
+int pg_debug_wave_counts(pg_handle* h, uint32_t* counts) {
+    if (!h) return pg_fail(nullptr, PG_EINVAL, "pg_debug_wave_counts: null handle");
+    h->wave_counts = counts;        // (this handle's device only: the peers of pg_render_frames do not count)
     return PG_OK;
 }
 
@@ -1220,7 +1247,9 @@ int pg_stage_eval(pg_handle* h, void* stream, int which, int64_t n, int n_sample
     if (pose_stride != 0 && pose_stride != 384) return pg_fail(h, PG_EINVAL, "pose_stride must be 0 or 384");
     if (n == 0) return PG_OK;
     PG_HIP(h, hipSetDevice(h->device));
-    return launch_eval(h, stream, which, n, n_samples, ray_batch, z, skts, pose_stride, cams, raw, dbg, dbg_stage);
+    // (a counting call, stage 97, runs as a render call's launch would: empty waves leave their colours out of `raw`)
+    return launch_eval(h, stream, which, n, n_samples, ray_batch, z, skts, pose_stride, cams, raw, dbg, dbg_stage, nullptr, nullptr, false,
+                       dbg && dbg_stage == 97);
 }
 
 int pg_query_density(pg_handle* h, void* stream, int which, int64_t n_points, const float* pts, const float* skts,
@@ -1326,7 +1355,10 @@ int render_rays_single(pg_handle* h, void* stream, int64_t n, const float* ray_b
         if (e0) return pg_fail(h, PG_EHIP, "noise gather launch failed: %s", hipGetErrorString((hipError_t)e0));
     }
     // the coarse raw enters the fine maps: not a guide pass (PG_PREC_FP16M runs fp16c)
-    rc = launch_eval(h, stream, 0, n, S, ray_batch, zc, skts, pose_stride, cams, rawc, nullptr, 0, nullptr, rnoise ? pn : nullptr, false);
+    // (the coarse raw is composited twice, by the coarse maps and merged into the fine ones: neither may draw density noise)
+    const bool free_c = !out->raw_coarse && !out->raw_fine && !(dr && (dr->noise0 || dr->noise1));
+    const bool free_n = !out->raw_fine && !(dr && dr->noise1);
+    rc = launch_eval(h, stream, 0, n, S, ray_batch, zc, skts, pose_stride, cams, rawc, nullptr, 0, nullptr, rnoise ? pn : nullptr, false, free_c);
     if (rc) return rc;
     int e = pg_launch_composite_iso(ray_batch, zc, rawc, n, S, h->cfg.density_scale, h->cfg.rgb_eps, h->cfg.density_act,
                                     h->cfg.softplus_shift, out->rgb0, out->disp0, out->acc0, out->alpha0,
@@ -1341,7 +1373,7 @@ int render_rays_single(pg_handle* h, void* stream, int64_t n, const float* ray_b
                                       hipMemcpyDeviceToDevice, s);
         if (e) return pg_fail(h, PG_EHIP, "noise gather failed: %s", hipGetErrorString((hipError_t)e));
     }
-    rc = launch_eval(h, stream, 0, n, NP, ray_batch, zn, skts, pose_stride, cams, rawn, nullptr, 0, nullptr, rnoise ? pn : nullptr, false);
+    rc = launch_eval(h, stream, 0, n, NP, ray_batch, zn, skts, pose_stride, cams, rawn, nullptr, 0, nullptr, rnoise ? pn : nullptr, false, free_n);
     if (rc) return rc;
     e = pg_launch_composite_merged(ray_batch, zf, rawc, rawn, NP, order, n, S, N, h->cfg.density_scale, h->cfg.rgb_eps, h->cfg.density_act,
                                    h->cfg.softplus_shift, out->rgb_map, out->disp_map, out->acc_map, out->alpha,
@@ -1403,7 +1435,10 @@ int render_rays_impl(pg_handle* h, void* stream, int64_t n, const float* ray_bat
         int e0 = pg_launch_gather_noise(dr->ray_noise, n, SF, S, nullptr, pn, stream);
         if (e0) return pg_fail(h, PG_EHIP, "noise gather launch failed: %s", hipGetErrorString((hipError_t)e0));
     }
-    rc = launch_eval(h, stream, 0, n, S, ray_batch, zc, skts, pose_stride, cams, rawc, nullptr, 0, nullptr, rnoise ? pn : nullptr, hier);
+    // what the empty-wave skip needs to know (skip_empty_ok): the launch's raw goes to one composite, without density noise, and to nobody else
+    const bool free_c = !out->raw_coarse && !(dr && dr->noise0);
+    const bool free_f = !out->raw_fine && !(dr && dr->noise1);
+    rc = launch_eval(h, stream, 0, n, S, ray_batch, zc, skts, pose_stride, cams, rawc, nullptr, 0, nullptr, rnoise ? pn : nullptr, hier, free_c);
     if (rc) return rc;
     int e = pg_launch_composite(ray_batch, zc, rawc, n, S, h->cfg.density_scale, h->cfg.rgb_eps, h->cfg.density_act, h->cfg.softplus_shift,
                                 hier ? out->rgb0 : out->rgb_map, hier ? out->disp0 : out->disp_map,
@@ -1416,7 +1451,7 @@ int render_rays_impl(pg_handle* h, void* stream, int64_t n, const float* ray_bat
             e = pg_launch_gather_noise(dr->ray_noise, n, SF, SF, order, pn, stream);
             if (e) return pg_fail(h, PG_EHIP, "noise gather launch failed: %s", hipGetErrorString((hipError_t)e));
         }
-        rc = launch_eval(h, stream, 1, n, SF, ray_batch, zf, skts, pose_stride, cams, rawf, nullptr, 0, nullptr, rnoise ? pn : nullptr);
+        rc = launch_eval(h, stream, 1, n, SF, ray_batch, zf, skts, pose_stride, cams, rawf, nullptr, 0, nullptr, rnoise ? pn : nullptr, false, free_f);
         if (rc) return rc;
         e = pg_launch_composite(ray_batch, zf, rawf, n, SF, h->cfg.density_scale, h->cfg.rgb_eps, h->cfg.density_act, h->cfg.softplus_shift, out->rgb_map,
                                 out->disp_map, out->acc_map, out->alpha, nullptr, 0, nullptr, dr ? dr->noise1 : nullptr,

@@ -39,6 +39,7 @@ struct EvalArgs {
     float tau_v, tau_d;
     int dbg_stage;            // which activation `dbg` receives (see pg_stage_eval)
     int far_skip;             // 1: limbs out of cutoff range are skipped (pg_eval16r.hip, pg_evalc.hip REC); 0: every limb computed
+    int skip_empty;           // 1: a wave whose points all have sigma <= 0 leaves the colour branch out (pg_eval16r.hip); set only where the caller composites with the ReLU density, no density noise, and hands no raw out
     int walk_rho;             // PassWalk: rotation of the pass walk per round, < grid (0: the static walk); kernels with limb masks only
 };
 

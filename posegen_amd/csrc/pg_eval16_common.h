@@ -178,6 +178,24 @@ __device__ __forceinline__ V next_a(APipe<V, NS>& p, ST& st, int L, int c0 = -1)
     return __builtin_bit_cast(V, p.r[L % NS]);
 }
 
+// Units L0 .. T-1 of a segment WITHOUT reading them: the chunk entries and refill pieces next_a would issue at those units,
+// nothing else (pg_eval16r.hip: a wave that leaves a segment's remaining tiles out still keeps the shared ring going --
+// every entry, barrier and piece at the unit next_a places it, so the counted vmcnt of the entries holds).  The caller
+// has retired (or abandoned behind an lgkmcnt(0)) whatever the pipe had in flight.
+template <int T, int L0, typename ST>
+__device__ __forceinline__ void skip_units(ST& st, int c0 = -1) {
+    static_assert(PG_SPREAD_DMA, "the bulk enter() refills by itself");
+    constexpr int PER = ST::PER, PSTRIDE = UPC / PER;
+#pragma unroll
+    for (int L = L0; L < T; ++L) {
+        const int q = L % UPC;
+        if (q == 0) st.enter_split(c0 >= 0 && ST::plain_ok(c0 + L / UPC));
+        if (q % PSTRIDE == PG_DMA_PHASE) st.piece(q / PSTRIDE);
+        if (L == T - 1)
+            for (int i = (q < PG_DMA_PHASE ? 0 : (q - PG_DMA_PHASE) / PSTRIDE + 1); i < PER; ++i) st.piece(i);
+    }
+}
+
 // An LDS read that runs BESIDE the weight-ring pipe (a bias tile, the (a, b) rows of the next joint): issued by inline
 // asm like the ring reads, because a read hipcc can see makes it wait `lgkmcnt(0)` in front of the consumer -- it does
 // not count the hand-issued ring reads, so that wait drains the A pipe (every tile boundary and every joint of the

@@ -359,7 +359,8 @@ __device__ __forceinline__ void y_apply16(f32x4 (*vacc)[2], const uint8_t* ylds,
 // ahead from the rays themselves (LDS-DMA of their ray_batch rows and first / last depths, the pose's bone rows kept in
 // LDS), and the view layer's direction part Y by y_segment16 from limb chunks of the weight stream.
 // CNT (measurement aid, dbg_stage 97; its own instantiation): passes, limbs left out of whole passes (of 6 per pass) and
-// limbs left out per wave (of 48 per pass), summed over the launch into a.dbg[0..2] (unsigned)
+// limbs left out per wave (of 48 per pass), summed over the launch into a.dbg[0..2] (unsigned); [3] empty waves (of 8 per
+// pass: every valid point has sigma <= 0) and [4] those of them that left the colour branch out (a.skip_empty)
 // PP (on-chip variant only): per-ray poses (a.pose_stride != 0, as the reference's batchify_rays hands them over,
 // core/trainer.py:64-81) -- the bone rows of a pass's rays are read from a.skts instead of the LDS copy of the one pose
 template <typename V, bool FC, bool TAPS, bool OC, bool CNT = false, bool PP = false>
@@ -640,17 +641,15 @@ __global__ __launch_bounds__(NTHR, 2) void eval16r_kernel(const EvalArgs a) {
         // ---- sigma head + view layer (feature layer folded in, view directions from the Y records) + rgb head,
         // one stream segment: the rgb head's 4 units sit in the chunk the view tiles end in ----
         float sigma[2];
-        V fg[NTV16 / 2][2];
-        APipe<V> pv;
+        f32x4 c0, c1;
         {
-            f32x4 vacc[NTV16][2];
+            APipe<V> pv;
             constexpr int TAV = pgp::R::U_AV;
             static_assert(BS_VIEWF == BS_ALPHA + 1 && BS_RGB == BS_VIEWF + NTV16, "alpha, view and rgb bias tiles are consecutive");
             BiasPipe bp(bbase, BS_ALPHA);
             bp.fetch(0);
-#pragma unroll
-            for (int o = 0; o < NTV16 + 1; ++o) {       // tile 0: alpha (row 0), tiles 1..8: the folded view layer
-                f32x4 t0, t1;
+            // one out tile of the segment: tile 0 = alpha (row 0), tiles 1..8 = the folded view layer
+            auto av_tile = [&](int o, f32x4& t0, f32x4& t1) __attribute__((always_inline)) {
 #pragma unroll
                 for (int u = 0; u < HU16; ++u) {
                     const V av = next_a<V, TAV, true, PG_PIPE_H>(pv, st, o * HU16 + u, C_AV);
@@ -659,43 +658,76 @@ __global__ __launch_bounds__(NTHR, 2) void eval16r_kernel(const EvalArgs a) {
                     t1 = Op16<V>::mfma(av, fb[u][1], t1);
                     if (u == PG_R_BIAS_AT && o < NTV16) bp.fetch(o + 1);
                 }
-                if (o == 0) { sigma[0] = t0[0]; sigma[1] = t1[0]; }
-                else { vacc[o - 1][0] = t0; vacc[o - 1][1] = t1; }
+            };
+            {
+                f32x4 t0, t1;
+                av_tile(0, t0, t1);
+                sigma[0] = t0[0]; sigma[1] = t1[0];
             }
-            PG_STAMP(6);
-            float wd[2][JG];
-#pragma unroll
-            for (int jj = 0; jj < JG; ++jj) {
-                float qx, qy, qz;
-                q0(jj, qx, qy, qz);
-                wd[0][jj] = cutoff_weight_fast(__builtin_amdgcn_sqrtf(qx * qx + qy * qy + qz * qz), tld, cutd[jj]);
-                q1(jj, qx, qy, qz);
-                wd[1][jj] = cutoff_weight_fast(__builtin_amdgcn_sqrtf(qx * qx + qy * qy + qz * qz), tld, cutd[jj]);
-                // a limb left out of the pass has weights below 2^-24 in every point: exactly zero instead, so that what the
-                // on-chip variant's Y image still holds for the limb from an earlier pass can never reach a result
-                if (OC && ((gmask >> jj) & 1)) wd[0][jj] = wd[1][jj] = 0.0f;
+            // Empty wave: every valid point of the wave has sigma <= 0 (row 0 of the alpha tile lives in lane group 0).  Under
+            // the ReLU density without noise such a point composites with alpha = 0, weight exactly +0: its colour reaches the
+            // maps as +0 x sigmoid(rgb) = +0 whatever rgb is.  Where the launch says so (a.skip_empty: pg_api.hip sets it from
+            // the call's facts) the wave then leaves the colour branch out -- view tiles, cutoff weights, y_apply16, the
+            // pack of fg, the rgb head -- and writes rgb = 0.  A NaN sigma is not "empty".  Wave-uniform.
+            bool empty = false;
+            if (CNT || a.skip_empty) {
+                const int i = wave * 32 + (lane_p & 15);
+                const bool live = g_p == 0 && ((i <= last && !(sigma[0] <= 0.0f)) || (i + 16 <= last && !(sigma[1] <= 0.0f)));
+                empty = __builtin_amdgcn_ballot_w64(live) == 0ull;
+                if (CNT && lane == 0 && empty) {
+                    atomicAdd(reinterpret_cast<unsigned*>(a.dbg) + 3, 1u);
+                    if (a.skip_empty) atomicAdd(reinterpret_cast<unsigned*>(a.dbg) + 4, 1u);
+                }
+                empty = empty && a.skip_empty != 0;
             }
-            y_apply16<V, FC>(vacc, smem + LDSR_Y, wd, myr, lane_p);
+            if (empty) {
+                // The ring is shared: the wave still takes every chunk entry, barrier and refill piece of the rest of the
+                // segment where next_a would (skip_units), like a limb out of range in x_segment16.  What the alpha tile's
+                // pipe read ahead (three units, the next bias tile) lands first and is dropped: no register operands on the
+                // wait, the values are dead here and naming them would make hipcc copy registers still in flight.
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                PG_STAMP(6);
+                skip_units<TAV, HU16>(st, C_AV);
+                PG_STAMP(7);
+                PG_PREFETCH_Z(itn);
+                c0 = c1 = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+            } else {
+                f32x4 vacc[NTV16][2];
+                V fg[NTV16 / 2][2];
 #pragma unroll
-            for (int u = 0; u < NTV16 / 2; ++u)
+                for (int o = 1; o < NTV16 + 1; ++o) av_tile(o, vacc[o - 1][0], vacc[o - 1][1]);
+                PG_STAMP(6);
+                float wd[2][JG];
 #pragma unroll
-                for (int c = 0; c < 2; ++c) fg[u][c] = relu_pack16<V>(vacc[2 * u][c], vacc[2 * u + 1][c], true);
-        }
-        PG_STAMP(7);
-        // the next pass's depths: in flight through the rgb head and the pass boundary (unconditional: a
-        // conditional re-definition would keep registers live through the whole pass)
-        PG_PREFETCH_Z(itn);
-        f32x4 c0, c1;
-        {
-            APipe<V> pr;
-            BiasPipe bp(bbase, BS_RGB);
-            bp.fetch(0);
+                for (int jj = 0; jj < JG; ++jj) {
+                    float qx, qy, qz;
+                    q0(jj, qx, qy, qz);
+                    wd[0][jj] = cutoff_weight_fast(__builtin_amdgcn_sqrtf(qx * qx + qy * qy + qz * qz), tld, cutd[jj]);
+                    q1(jj, qx, qy, qz);
+                    wd[1][jj] = cutoff_weight_fast(__builtin_amdgcn_sqrtf(qx * qx + qy * qy + qz * qz), tld, cutd[jj]);
+                    // a limb left out of the pass has weights below 2^-24 in every point: exactly zero instead, so that what the
+                    // on-chip variant's Y image still holds for the limb from an earlier pass can never reach a result
+                    if (OC && ((gmask >> jj) & 1)) wd[0][jj] = wd[1][jj] = 0.0f;
+                }
+                y_apply16<V, FC>(vacc, smem + LDSR_Y, wd, myr, lane_p);
 #pragma unroll
-            for (int u = 0; u < pgp::R::U_RGB; ++u) {
-                const V av = next_a_cont<V, pgp::R::U_RGB, PG_PIPE_H, pgp::R::U_AV % UPC>(pr, st, u);
-                if (u == 0) c0 = c1 = bp.take();
-                c0 = Op16<V>::mfma(av, fg[u][0], c0);
-                c1 = Op16<V>::mfma(av, fg[u][1], c1);
+                for (int u = 0; u < NTV16 / 2; ++u)
+#pragma unroll
+                    for (int c = 0; c < 2; ++c) fg[u][c] = relu_pack16<V>(vacc[2 * u][c], vacc[2 * u + 1][c], true);
+                PG_STAMP(7);
+                // the next pass's depths: in flight through the rgb head and the pass boundary (defined on both
+                // branches: a conditional re-definition would keep registers live through the whole pass)
+                PG_PREFETCH_Z(itn);
+                APipe<V> pr;
+                BiasPipe bpr(bbase, BS_RGB);
+                bpr.fetch(0);
+#pragma unroll
+                for (int u = 0; u < pgp::R::U_RGB; ++u) {
+                    const V av = next_a_cont<V, pgp::R::U_RGB, PG_PIPE_H, pgp::R::U_AV % UPC>(pr, st, u);
+                    if (u == 0) c0 = c1 = bpr.take();
+                    c0 = Op16<V>::mfma(av, fg[u][0], c0);
+                    c1 = Op16<V>::mfma(av, fg[u][1], c1);
+                }
             }
         }
         if (g == 0) {       // rows 0..2 of the rgb tile and row 0 of the alpha tile live in lane group 0

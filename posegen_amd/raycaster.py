@@ -87,6 +87,7 @@ class HipRenderer:
         self._state: Dict[str, dict] = {}
         self._state_lazy: Dict[str, object] = {}      # state dicts to fetch from their owner on demand (load_network_device)
         self._chunk = cfg.chunk
+        self._wave_counts = None
 
     # -- lifetime ---------------------------------------------------------------------
     def close(self):
@@ -184,6 +185,22 @@ class HipRenderer:
     def set_far_skip(self, on=True):
         """Test / measurement aid (pg_set_far_skip): off = the fused kernels compute every limb for every point."""
         self._check(self.lib.pg_set_far_skip(self.handle, 1 if on else 0))
+
+    def set_empty_skip(self, on=True):
+        """pg_set_empty_skip: off = the 16x16x32 kernel runs the colour branch for every wave, also for those whose points
+        all have sigma <= 0 (tests, A/B; the maps are bitwise the same either way).  Default on."""
+        self._check(self.lib.pg_set_empty_skip(self.handle, 1 if on else 0))
+
+    def count_waves(self, on=True):
+        """Measurement aid (pg_debug_wave_counts): while on, the render calls' own launches of the on-chip 16x16x32 form (one
+        pose, no frame codes) count passes and empty / skipped waves; read_wave_counts() reads and clears."""
+        self._wave_counts = torch.zeros(16, device=self.device, dtype=torch.int32) if on else None
+        self._check(self.lib.pg_debug_wave_counts(self.handle, self._wave_counts.data_ptr() if on else None))
+
+    def read_wave_counts(self):
+        c = [int(v) for v in self._wave_counts.cpu()]
+        self._wave_counts.zero_()
+        return _wave_stats(c)
 
     def set_train_precision(self, precision="fp32"):
         """Arithmetic of the training step (pg_set_train_precision): "fp32" (the reference's, default) or "bf16" (bf16 tape
@@ -558,10 +575,7 @@ class HipRenderer:
         cnt = torch.zeros(64, device=self.device, dtype=torch.int32)
         self._check(self.lib.pg_stage_eval(self.handle, self._stream(), int(which), n, S, _ptr(rb), _ptr(zz),
                                            _ptr(sk), ps, _ptr(cam), _ptr(raw), cnt.data_ptr(), 97))
-        passes, per_pass, fine = (int(v) for v in cnt[:3].cpu())
-        per_fine = 48                                   # 8 waves / column tiles x 6 limbs per pass in both kernels
-        return {"passes": passes, "limbs_left_out_of_whole_passes_frac": per_pass / max(6 * passes, 1),
-                "limbs_left_out_frac": fine / max(per_fine * passes, 1)}
+        return _wave_stats([int(v) for v in cnt[:5].cpu()])
 
     def stage_composite(self, ray_batch, z, raw, n_importance=0):
         rb = _dev_f32(ray_batch, self.device)
@@ -578,6 +592,15 @@ class HipRenderer:
         if zf is not None:
             o["z_fine"] = zf
         return o
+
+
+def _wave_stats(c):
+    """the counters of pg_stage_eval's dbg_stage 97 as fractions; the empty-wave counts come from pg_eval16r.hip only"""
+    passes, per_pass, fine, empty, skipped = c[:5]
+    per_fine = 48                                   # 8 waves / column tiles x 6 limbs per pass in both kernels
+    return {"passes": passes, "limbs_left_out_of_whole_passes_frac": per_pass / max(6 * passes, 1),
+            "limbs_left_out_frac": fine / max(per_fine * passes, 1),
+            "empty_waves_frac": empty / max(8 * passes, 1), "skipped_waves_frac": skipped / max(8 * passes, 1)}
 
 
 def _same_state(a, b) -> bool:
