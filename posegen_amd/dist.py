@@ -19,8 +19,9 @@ from __future__ import annotations
 
 from typing import List, NamedTuple, Sequence
 
-import numpy as np
 import torch
+
+from .render import _pick, emit_frame, frame_background, frame_setup, frame_stacks, frames_to_host
 
 
 class Task(NamedTuple):
@@ -137,25 +138,11 @@ def render_frames_distributed(render_poses, hwf, chunk, render_kwargs, group=Non
     `stats` (dict): receives `host_pre_launch_ms` (call entry -> first render launch: the part no GPU overlaps)
     and `host_ms` (whole call, host side)."""
     import time
-    from .rays import BoxPixelIds, frame_boxes
-    from .render import _caster_device, _pick
     t_enter = time.perf_counter()
     world, rank, dist = _world(group)
-    H, W, focal = hwf
-    if not (isinstance(H, (int, np.integer)) and isinstance(W, (int, np.integer))):
-        raise ValueError("render_path_distributed needs one frame size (scalar H, W) for the gather")
-    H, W = int(H), int(W)
-    if render_factor:
-        H, W = H // render_factor, W // render_factor
-        focal = focal / render_factor if isinstance(focal, float) else focal.copy() / render_factor
-        if centers is not None:
-            centers = centers / render_factor if isinstance(focal, float) else centers.copy() / render_factor
-    if kp is None and cyls is None:
-        raise NotImplementedError("render_path needs kp or cyls (bounding-cylinder cull)")
-    r, dev = _caster_device(render_kwargs["ray_caster"])
-    cyls, bboxes, meta = frame_boxes(r, render_poses, H, W, focal, kps=kp, cylinder_params=cyls, ext_scale=ext_scale,
-                                     centers=centers)
-    valid_idxs = BoxPixelIds(bboxes, [m[1] for m in meta])
+    su = frame_setup(render_poses, hwf, render_kwargs, centers, kp, cyls, render_factor, ext_scale,
+                     need_scalar_hw="render_path_distributed needs one frame size (scalar H, W) for the gather")
+    r, dev, cyls, bboxes, meta, valid_idxs = su.r, su.dev, su.cyls, su.bboxes, su.meta, su.valid_idxs
     n_box = valid_idxs.counts()
     F = len(meta)
     tasks = plan_tasks(n_box, world, int(chunk))
@@ -205,7 +192,7 @@ def render_frames_distributed(render_poses, hwf, chunk, render_kwargs, group=Non
     for t in tasks:
         pieces_of[t.frame].append((t.r0, t.worker, offs[t.worker], t.r1 - t.r0))
         offs[t.worker] += t.r1 - t.r0
-    rgbs, disps, accs = [], [], []
+    frames = []
     for i in range(F):
         h, w, f, c2w_np, center = meta[i]
         rm, dm, am = [], [], []
@@ -213,28 +200,15 @@ def render_frames_distributed(render_poses, hwf, chunk, render_kwargs, group=Non
             blk = gathered[k, 5 * o:5 * (o + n)]
             rm.append(blk[:3 * n].view(n, 3)); dm.append(blk[3 * n:4 * n]); am.append(blk[4 * n:])
         cat = lambda xs, shape: (xs[0] if len(xs) == 1 else torch.cat(xs)) if xs else torch.zeros(shape, device=dev)
-        bg = None
-        if bg_imgs is not None and not white_bkgd:
-            import torch.nn.functional as Fn
-            bgi = torch.tensor(bg_imgs[bg_indices[i]] if bg_indices is not None else bg_imgs[0])
-            bg = Fn.interpolate(bgi.permute(2, 0, 1)[None].float(), size=(h, w), mode="bilinear",
-                                align_corners=False)[0].permute(1, 2, 0).reshape(h * w, 3).to(dev)
-        rgb, disp, acc = r.compose_frame(h, w, bboxes[i], cat(rm, (0, 3)), cat(dm, (0,)), cat(am, (0,)), bg=bg,
+        rgb, disp, acc = r.compose_frame(h, w, bboxes[i], cat(rm, (0, 3)), cat(dm, (0,)), cat(am, (0,)),
+                                         bg=frame_background(bg_imgs, bg_indices, i, h, w, white_bkgd, dev),
                                          base_bg=1.0 if white_bkgd else 0.0)
-        if frame_sink is not None:
-            frame_sink(i, rgb, torch.nan_to_num(disp, nan=0.0, posinf=float("inf"), neginf=float("-inf")), acc)   # run_nerf.py:142-143
-            continue
-        rgbs.append(rgb); disps.append(disp); accs.append(acc)
+        emit_frame(frame_sink, frames, i, rgb, disp, acc)
     if stats is not None:
         now = time.perf_counter()
         stats["host_pre_launch_ms"] = (t_first - t_enter) * 1e3
         stats["host_ms"] = (now - t_enter) * 1e3
-    if frame_sink is not None:
-        return None, None, None, valid_idxs, bboxes
-    e = lambda c: torch.zeros((0, H, W, c), device=dev)
-    rgbs, disps, accs = (torch.stack(rgbs), torch.stack(disps), torch.stack(accs)) if F else (e(3), e(1), e(1))
-    disps = torch.nan_to_num(disps, nan=0.0, posinf=float("inf"), neginf=float("-inf"))   # run_nerf.py:142-143
-    return rgbs, disps, accs, valid_idxs, bboxes
+    return frame_stacks(frame_sink, frames, su) + (valid_idxs, bboxes)
 
 
 def render_path_distributed(render_poses, hwf, chunk, render_kwargs, group=None, **kw):
@@ -243,21 +217,7 @@ def render_path_distributed(render_poses, hwf, chunk, render_kwargs, group=None,
     render.render_path; in a process without a process group it is the single-device render.  The composed
     frames go to the host through page-locked buffers on a copy stream while the next ones are composed
     (render.FrameDownloader), like the single-device render_path."""
-    from .render import FrameDownloader, _caster_device
     keep = ("centers", "kp", "skts", "cyls", "bg_imgs", "bg_indices", "cams", "render_factor", "white_bkgd", "ext_scale")
     args = {k: v for k, v in kw.items() if k in keep}
-    ret_acc = kw.get("ret_acc", True)
-    _, dev = _caster_device(render_kwargs["ray_caster"])
-    H, W = hwf[0], hwf[1]
-    scalar = isinstance(H, (int, np.integer)) and isinstance(W, (int, np.integer))
-    if len(render_poses) == 0 or torch.device(dev).type != "cuda" or not scalar:
-        rgbs, disps, accs, valid_idxs, bboxes = render_frames_distributed(render_poses, hwf, chunk, render_kwargs, group=group, **args)
-        packed = torch.cat([rgbs, disps, accs], -1).float().cpu().numpy()
-        return packed[..., 0:3], packed[..., 3:4], (packed[..., 4:5] if ret_acc else []), valid_idxs, bboxes
-    rf = kw.get("render_factor", 0)
-    H, W = (int(H) // rf, int(W) // rf) if rf else (int(H), int(W))
-    dl = FrameDownloader(len(render_poses), H, W, ret_acc, dev)
-    _, _, _, valid_idxs, bboxes = render_frames_distributed(render_poses, hwf, chunk, render_kwargs, group=group,
-                                                            frame_sink=dl.sink, **args)
-    res = dl.finish()
-    return res[0], res[1], (res[2] if ret_acc else []), valid_idxs, bboxes
+    driver = lambda sink: render_frames_distributed(render_poses, hwf, chunk, render_kwargs, group=group, frame_sink=sink, **args)
+    return frames_to_host(driver, render_kwargs, hwf, len(render_poses), kw.get("render_factor", 0), kw.get("ret_acc", True))

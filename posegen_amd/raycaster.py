@@ -7,20 +7,26 @@ core/trainer.py:74: same call signature, same returned dict keys
 (`_collect_outputs`, raycasters.py:711-724), same checkpoint key scheme
 (`state_dict` / `load_state_dict`, raycasters.py:752-788).
 
-Forward values only (no autograd graph).  Eval mode is the measured path; the training-mode
+Forward values only (no autograd graph): the training step with a gradient is `train.TrainableRayCaster`,
+which wraps a `HipRayCaster`.  Eval mode is the measured path; the training-mode
 arguments (perturb, raw_noise_std, ray_noise_std, pytest) are honoured with the random numbers
 drawn on the host side of the ABI (`training_draws`, pg_train_draws).
+
+Every ray-level call (render_rays, the training forward, stage_eval) is marshalled by `marshal_ray_call`; the
+reference's keywords the kernels do not honour are refused by `refuse_reference_kwargs`, for both casters.
 """
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Optional
+from contextlib import contextmanager
+from typing import Dict, NamedTuple, Optional
 
 import numpy as np
 import torch
 
 from . import _ffi
 from .config import PREC_BF16, PREC_BY_NAME, PREC_NAMES, RenderConfig
+from .rays import _focal_xy
 
 NET_TENSOR_ORDER = ([f"pts_linears.{l}.{k}" for l in range(8) for k in ("weight", "bias")]
                     + [f"{n}.{k}" for n in ("alpha_linear", "feature_linear", "views_linears.0", "rgb_linear")
@@ -47,6 +53,138 @@ def _dev_f32(t: torch.Tensor, device) -> torch.Tensor:
 
 def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _net_key(which: int) -> str:
+    """the reference checkpoint's key of net 0 (coarse) / 1 (fine)"""
+    return "network_fn_state_dict" if which == 0 else "network_fine_state_dict"
+
+
+def _resolve_sn(cfg: RenderConfig, n_samples, n_importance):
+    """(S, N) of a call: the configuration's counts unless the caller gives its own"""
+    return (cfg.n_samples if n_samples is None else int(n_samples),
+            cfg.n_importance if n_importance is None else int(n_importance))
+
+
+def _intrinsics(H, W, focal, center=None, f32_focal=False):
+    """(fx, fy, cx, cy): one focal length serves both axes, the principal point defaults to the frame's centre.
+    f32_focal: the focal lengths rounded through float32 (pose_boxes: nerf_c2w_to_extrinsic parity with the reference)."""
+    fx, fy = _focal_xy(focal)
+    if f32_focal:
+        fx, fy = float(np.float32(fx)), float(np.float32(fy))
+    cx, cy = (W * 0.5, H * 0.5) if center is None else (float(center[0]), float(center[1]))
+    return fx, fy, cx, cy
+
+
+def _per_ray(x: torch.Tensor, n: int, device, dims: int, stride: int, what: str):
+    """[1|n, ...] (or one un-batched item of `dims` - 1 dimensions) -> (contiguous device tensor, stride in floats: 0 = one
+    item for all rays).  `what`: the refusal's subject, e.g. "skts has {} poses"."""
+    if x.dim() == dims - 1:
+        x = x[None]
+    if x.shape[0] == 1 or x.stride(0) == 0:
+        return _dev_f32(x[:1], device), 0
+    if x.shape[0] != n:
+        raise ValueError(f"{what.format(x.shape[0])} for {n} rays")
+    return _dev_f32(x, device), stride
+
+
+class RayCall(NamedTuple):
+    """What the ABI needs for one ray-level call; the tensors live as long as this does."""
+    rb: torch.Tensor                    # [n,11] ray batch (zero-padded)
+    sk: torch.Tensor                    # pose(s) and their stride in floats
+    ps: int
+    cy: Optional[torch.Tensor]          # cylinder(s) and their stride
+    cs: int
+    cam: Optional[torch.Tensor]         # [n] frame-code index per ray
+    S: int
+    N: int
+    flags: int
+    draws: Optional[_ffi.PgTrainDraws]  # None: eval mode
+    keep: list                          # every tensor a pointer above refers to
+
+    @property
+    def n(self) -> int:
+        return self.rb.shape[0]
+
+
+def marshal_ray_call(cfg: RenderConfig, device, ray_batch, skts, cyls=None, cams=None, n_samples=None, n_importance=None,
+                     lindisp=False, draws=None) -> RayCall:
+    """The one place where a caller's ray-level arguments become ABI arguments.  `draws`: any of t_rand [n,S],
+    u_rand [n,N], noise0 [n,S], noise1 [n,S+N], ray_noise [n,S+N,3]; u_rand / noise1 are dropped when N = 0."""
+    S, N = _resolve_sn(cfg, n_samples, n_importance)
+    rb = _dev_f32(torch.as_tensor(ray_batch), device)
+    n = rb.shape[0]
+    if rb.dim() != 2 or rb.shape[1] < 8:
+        raise ValueError("ray_batch must be [n, >=8] (o, d, near, far [, viewdir])")
+    if rb.shape[1] != 11:
+        pad = torch.zeros(n, 11, device=device)
+        pad[:, :min(11, rb.shape[1])] = rb[:, :11]
+        rb = pad
+    skts = torch.as_tensor(skts).detach()
+    sk, ps = _per_ray(skts, n, device, 4, 24 * 16, "skts has {} poses")
+    cy, cs = (None, 0) if cyls is None else _per_ray(cyls, n, device, 2, 5, "cyls has {} rows")
+    cam = None
+    if cams is not None:
+        cam = _dev_f32(torch.as_tensor(cams).reshape(-1), device)
+        if cam.shape[0] == 1 and n > 1:
+            cam = cam.expand(n).contiguous()
+    keep = [rb, sk, cy, cam]
+    pd = None
+    if draws:
+        shapes = {"t_rand": (n, S), "u_rand": (n, N), "noise0": (n, S), "noise1": (n, S + N), "ray_noise": (n, S + N, 3)}
+        unknown = set(draws) - set(shapes)
+        if unknown:
+            raise ValueError(f"unknown draws {sorted(unknown)}; expected a subset of {sorted(shapes)}")
+        pd = _ffi.PgTrainDraws()
+        for k, shp in shapes.items():
+            t = draws.get(k)
+            if t is None or (N == 0 and k in ("u_rand", "noise1")):
+                continue
+            t = _dev_f32(t, device)
+            if tuple(t.shape) != shp:
+                raise ValueError(f"draws[{k!r}] must be {shp}, got {tuple(t.shape)}")
+            keep.append(t)
+            setattr(pd, k, t.data_ptr())
+    return RayCall(rb, sk, ps, cy, cs, cam, S, N, _ffi.PG_FLAG_LINDISP if lindisp else 0, pd, keep)
+
+
+def alloc_ray_outputs(n, S, N, device, want_alpha=True, extras=False):
+    """The result tensors of one ray-level call -> (maps (+ alphas) dict, extras dict, PgOutputs pointing at them)."""
+    new = lambda *s: torch.empty(*s, device=device, dtype=torch.float32)
+    SF = S + N
+    out = {"rgb_map": new(n, 3), "disp_map": new(n), "acc_map": new(n)}
+    if want_alpha:
+        out["alpha"] = new(n, SF)
+    if N > 0:
+        out.update({"rgb0": new(n, 3), "disp0": new(n), "acc0": new(n)})
+        if want_alpha:
+            out["alpha0"] = new(n, S)
+    ex = {}
+    if extras:
+        ex = {"near_far": new(n, 2), "z_coarse": new(n, S), "raw_coarse": new(n, S, 4), "weights0": new(n, S)}
+        if N > 0:
+            ex.update({"z_fine": new(n, SF), "raw_fine": new(n, SF, 4)})
+    po = _ffi.PgOutputs()
+    for k in ("rgb_map", "disp_map", "acc_map", "alpha", "rgb0", "disp0", "acc0", "alpha0"):
+        setattr(po, k, out[k].data_ptr() if k in out else None)
+    for k in ("near_far", "z_coarse", "z_fine", "raw_coarse", "raw_fine", "weights0"):
+        setattr(po, k, ex[k].data_ptr() if k in ex else None)
+    return out, ex, po
+
+
+@contextmanager
+def one_nanmean_group(renderer, n, grouped=False):
+    """One call = one nanmean group, like get_near_far_in_cylinder on the reference's ray_batch (ray_utils.py:292-344):
+    only batchify_rays / render_path split a frame into `chunk` groups (`grouped`: keep theirs).  The group size is a
+    property of THIS call: the renderer's own setting (what later direct render_rays / render_frame calls see) is put
+    back afterwards."""
+    keep = renderer._chunk
+    if not grouped:
+        renderer.set_chunk(max(int(n), 1))
+    try:
+        yield
+    finally:
+        renderer.set_chunk(keep)
 
 
 class HipRenderer:
@@ -122,7 +260,7 @@ class HipRenderer:
             codes = _np32(sd["framecodes.codes.weight"])
             self._check(self.lib.pg_set_framecodes(self.handle, which, codes.ctypes.data, codes.shape[0]))
         st = {k: torch.from_numpy(_np32(v).copy()) for k, v in sd.items()}
-        self._state["network_fn_state_dict" if which == 0 else "network_fine_state_dict"] = st
+        self._state[_net_key(which)] = st
         if self.cfg.single_net:     # network_fine is network: the reference's checkpoint holds both keys (raycasters.py:751-766)
             self._state["network_fine_state_dict"] = st
 
@@ -144,7 +282,7 @@ class HipRenderer:
                 raise ValueError("load_network_device: contiguous float32 device frame codes expected")
             cptr, ncodes = codes.data_ptr(), codes.shape[0]
         self._check(self.lib.pg_load_weights_device(self.handle, self._stream(), which, ptrs, len(ts), cptr, ncodes))
-        self._state_lazy["network_fn_state_dict" if which == 0 else "network_fine_state_dict"] = state_provider
+        self._state_lazy[_net_key(which)] = state_provider
 
     def _refresh_state(self):
         """the host-side state dicts brought up to date after device-side weight loads"""
@@ -245,22 +383,10 @@ class HipRenderer:
     # -- the hot path -----------------------------------------------------------------
     def _pose_args(self, skts: torch.Tensor, n: int):
         """[1|n,24,4,4] -> (contiguous device tensor, stride in floats)."""
-        if skts.dim() == 3:
-            skts = skts[None]
-        if skts.shape[0] == 1 or skts.stride(0) == 0:
-            return _dev_f32(skts[:1], self.device), 0
-        if skts.shape[0] != n:
-            raise ValueError(f"skts has {skts.shape[0]} poses for {n} rays")
-        return _dev_f32(skts, self.device), 24 * 16
+        return _per_ray(skts, n, self.device, 4, 24 * 16, "skts has {} poses")
 
     def _cyl_args(self, cyls: torch.Tensor, n: int):
-        if cyls.dim() == 1:
-            cyls = cyls[None]
-        if cyls.shape[0] == 1 or cyls.stride(0) == 0:
-            return _dev_f32(cyls[:1], self.device), 0
-        if cyls.shape[0] != n:
-            raise ValueError(f"cyls has {cyls.shape[0]} rows for {n} rays")
-        return _dev_f32(cyls, self.device), 5
+        return _per_ray(cyls, n, self.device, 2, 5, "cyls has {} rows")
 
     def render_rays(self, ray_batch: torch.Tensor, skts: torch.Tensor, cyls: torch.Tensor,
                     cams: Optional[torch.Tensor] = None, n_samples: Optional[int] = None,
@@ -270,66 +396,13 @@ class HipRenderer:
         """One `RayCaster.render_rays` call (core/raycasters.py:361-474).  `draws` = None: eval mode.
         Otherwise the random numbers of a training-mode call (pg_train_draws, posegen_hip.h): any of
         t_rand [n,S], u_rand [n,N], noise0 [n,S], noise1 [n,S+N], ray_noise [n,S+N,3]."""
-        cfg = self.cfg
-        S = cfg.n_samples if n_samples is None else int(n_samples)
-        N = cfg.n_importance if n_importance is None else int(n_importance)
-        rb = _dev_f32(ray_batch, self.device)
-        n = rb.shape[0]
-        if rb.dim() != 2 or rb.shape[1] < 8:
-            raise ValueError("ray_batch must be [n, >=8] (o, d, near, far [, viewdir])")
-        if rb.shape[1] != 11:
-            pad = torch.zeros(n, 11, device=self.device)
-            pad[:, :min(11, rb.shape[1])] = rb[:, :11]
-            rb = pad
-        sk, ps = self._pose_args(skts, n)
-        cy, cs = self._cyl_args(cyls, n)
-        cam = None
-        if cams is not None:
-            cam = _dev_f32(cams.reshape(-1), self.device)
-            if cam.shape[0] == 1 and n > 1:
-                cam = cam.expand(n).contiguous()
-        dev = self.device
-        new = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)
-        SF = S + N
-        out = {"rgb_map": new(n, 3), "disp_map": new(n), "acc_map": new(n)}
-        if want_alpha:
-            out["alpha"] = new(n, SF)
-        if N > 0:
-            out.update({"rgb0": new(n, 3), "disp0": new(n), "acc0": new(n)})
-            if want_alpha:
-                out["alpha0"] = new(n, S)
-        ex = {}
-        if extras:
-            ex = {"near_far": new(n, 2), "z_coarse": new(n, S), "raw_coarse": new(n, S, 4), "weights0": new(n, S)}
-            if N > 0:
-                ex.update({"z_fine": new(n, SF), "raw_fine": new(n, SF, 4)})
-        po = _ffi.PgOutputs()
-        for k in ("rgb_map", "disp_map", "acc_map", "alpha", "rgb0", "disp0", "acc0", "alpha0"):
-            setattr(po, k, out[k].data_ptr() if k in out else None)
-        for k in ("near_far", "z_coarse", "z_fine", "raw_coarse", "raw_fine", "weights0"):
-            setattr(po, k, ex[k].data_ptr() if k in ex else None)
-        flags = _ffi.PG_FLAG_LINDISP if lindisp else 0
-        if draws:
-            shapes = {"t_rand": (n, S), "u_rand": (n, N), "noise0": (n, S), "noise1": (n, SF), "ray_noise": (n, SF, 3)}
-            unknown = set(draws) - set(shapes)
-            if unknown:
-                raise ValueError(f"unknown draws {sorted(unknown)}; expected a subset of {sorted(shapes)}")
-            pd, keep = _ffi.PgTrainDraws(), []
-            for k, shp in shapes.items():
-                t = draws.get(k)
-                if t is None or (N == 0 and k in ("u_rand", "noise1")):
-                    continue
-                t = _dev_f32(t, dev)
-                if tuple(t.shape) != shp:
-                    raise ValueError(f"draws[{k!r}] must be {shp}, got {tuple(t.shape)}")
-                keep.append(t)
-                setattr(pd, k, t.data_ptr())
-            if n > 0:
-                self._check(self.lib.pg_render_rays_train(self.handle, self._stream(), n, _ptr(rb), _ptr(sk), ps, _ptr(cy),
-                                                          cs, _ptr(cam), S, N, flags, C.byref(pd), C.byref(po)))
-        elif n > 0:
-            self._check(self.lib.pg_render_rays(self.handle, self._stream(), n, _ptr(rb), _ptr(sk), ps, _ptr(cy), cs,
-                                                _ptr(cam), S, N, flags, C.byref(po)))
+        c = marshal_ray_call(self.cfg, self.device, ray_batch, skts, cyls, cams, n_samples, n_importance, lindisp, draws)
+        out, ex, po = alloc_ray_outputs(c.n, c.S, c.N, self.device, want_alpha, extras)
+        args = (self.handle, self._stream(), c.n, _ptr(c.rb), _ptr(c.sk), c.ps, _ptr(c.cy), c.cs, _ptr(c.cam), c.S, c.N, c.flags)
+        if c.n > 0 and c.draws is not None:
+            self._check(self.lib.pg_render_rays_train(*args, C.byref(c.draws), C.byref(po)))
+        elif c.n > 0:
+            self._check(self.lib.pg_render_rays(*args, C.byref(po)))
         if extras:
             out["extras"] = ex
         return out
@@ -341,39 +414,34 @@ class HipRenderer:
         """One frame entirely on the device (pg_render_frame): rays of the pixels in `box` =
         ((tl_x, tl_y), (br_x, br_y)), render, scatter over the background.  Returns device
         tensors rgb [H,W,3], disp [H,W,1], acc [H,W,1] (+ rgb8 uint8 [H,W,3])."""
-        cfg = self.cfg
-        S = cfg.n_samples if n_samples is None else int(n_samples)
-        N = cfg.n_importance if n_importance is None else int(n_importance)
-        f = np.asarray(focal.detach().cpu() if isinstance(focal, torch.Tensor) else focal, dtype=np.float64).reshape(-1)
-        fx, fy = (float(f[0]), float(f[0])) if f.size < 2 else (float(f[0]), float(f[1]))
-        cx, cy = (W * 0.5, H * 0.5) if center is None else (float(center[0]), float(center[1]))
-        c2w_h = np.ascontiguousarray(np.asarray(c2w.detach().cpu() if isinstance(c2w, torch.Tensor) else c2w,
-                                                dtype=np.float32)[:3, :4])
-        (tlx, tly), (brx, bry) = box
+        S, N = _resolve_sn(self.cfg, n_samples, n_importance)
+        c2w_h, intr, bx = self._frame_args(H, W, focal, c2w, box, center)
         sk, _ = self._pose_args(skts, 1)
         cy_t, _ = self._cyl_args(cyl, 1)
-        dev = self.device
-        rgb = torch.empty(H, W, 3, device=dev)
-        disp = torch.empty(H, W, 1, device=dev)
-        acc = torch.empty(H, W, 1, device=dev)
-        rgb8 = torch.empty(H, W, 3, device=dev, dtype=torch.uint8) if want_uint8 else None
-        bgt = None if bg is None else _dev_f32(bg.reshape(H * W, 3), dev)
+        rgb, disp, acc, rgb8, bgt = self._frame_outputs(H, W, bg, want_uint8)
         self._check(self.lib.pg_render_frame(
-            self.handle, self._stream(), int(H), int(W), c2w_h.ctypes.data_as(C.POINTER(C.c_float)),
-            (C.c_float * 4)(fx, fy, cx, cy), (C.c_int * 4)(int(tlx), int(tly), int(brx), int(bry)),
+            self.handle, self._stream(), int(H), int(W), c2w_h.ctypes.data_as(C.POINTER(C.c_float)), intr, bx,
             float(near), float(far), _ptr(sk), _ptr(cy_t), -1.0 if cam is None else float(cam), S, N,
             _ffi.PG_FLAG_LINDISP if lindisp else 0, _ptr(bgt), float(base_bg), _ptr(rgb), _ptr(disp), _ptr(acc),
             _ptr(rgb8)))
         return (rgb, disp, acc, rgb8) if want_uint8 else (rgb, disp, acc)
 
     def _frame_args(self, H, W, focal, c2w, box, center):
-        f = np.asarray(focal.detach().cpu() if isinstance(focal, torch.Tensor) else focal, dtype=np.float64).reshape(-1)
-        fx, fy = (float(f[0]), float(f[0])) if f.size < 2 else (float(f[0]), float(f[1]))
-        cx, cy = (W * 0.5, H * 0.5) if center is None else (float(center[0]), float(center[1]))
+        """-> (camera [3,4] float32 on the host, (fx, fy, cx, cy), (tl_x, tl_y, br_x, br_y)) as the ABI takes them"""
         c2w_h = np.ascontiguousarray(np.asarray(c2w.detach().cpu() if isinstance(c2w, torch.Tensor) else c2w,
                                                 dtype=np.float32)[:3, :4])
         (tlx, tly), (brx, bry) = box
-        return (c2w_h, (C.c_float * 4)(fx, fy, cx, cy), (C.c_int * 4)(int(tlx), int(tly), int(brx), int(bry)))
+        return (c2w_h, (C.c_float * 4)(*_intrinsics(H, W, focal, center)), (C.c_int * 4)(int(tlx), int(tly), int(brx), int(bry)))
+
+    def _frame_outputs(self, H, W, bg, want_uint8):
+        """The tensors of one composed frame -> (rgb [H,W,3], disp [H,W,1], acc [H,W,1], rgb8 uint8 [H,W,3] or None,
+        background [H*W,3] on the device or None)."""
+        dev = self.device
+        rgb = torch.empty(H, W, 3, device=dev)
+        disp = torch.empty(H, W, 1, device=dev)
+        acc = torch.empty(H, W, 1, device=dev)
+        rgb8 = torch.empty(H, W, 3, device=dev, dtype=torch.uint8) if want_uint8 else None
+        return rgb, disp, acc, rgb8, None if bg is None else _dev_f32(bg.reshape(H * W, 3), dev)
 
     def render_frame_range(self, H: int, W: int, focal, c2w, box, skts: torch.Tensor, cyl: torch.Tensor,
                            ray_begin: int, ray_end: int, center=None, cam: Optional[float] = None, near: float = 0.,
@@ -383,9 +451,7 @@ class HipRenderer:
         [5, n]: rows 0-2 hold rgb_map [n,3] (flat), row 3 disp_map, row 4 acc_map (pg_render_frame_range; the
         unit of work of the multi-process partition, dist.plan_tasks).  `ray_begin` must be 0 or a multiple
         of the nanmean group size, so the values are those of the whole frame."""
-        cfg = self.cfg
-        S = cfg.n_samples if n_samples is None else int(n_samples)
-        N = cfg.n_importance if n_importance is None else int(n_importance)
+        S, N = _resolve_sn(self.cfg, n_samples, n_importance)
         n = int(ray_end) - int(ray_begin)
         buf = torch.empty(5 * n, device=self.device) if out is None else out
         if buf.numel() != 5 * n or buf.dtype != torch.float32 or not buf.is_contiguous():
@@ -408,11 +474,7 @@ class HipRenderer:
         disp [H,W,1], acc [H,W,1] (+ rgb8)."""
         dev = self.device
         (tlx, tly), (brx, bry) = box
-        rgb = torch.empty(H, W, 3, device=dev)
-        disp = torch.empty(H, W, 1, device=dev)
-        acc = torch.empty(H, W, 1, device=dev)
-        rgb8 = torch.empty(H, W, 3, device=dev, dtype=torch.uint8) if want_uint8 else None
-        bgt = None if bg is None else _dev_f32(bg.reshape(H * W, 3), dev)
+        rgb, disp, acc, rgb8, bgt = self._frame_outputs(H, W, bg, want_uint8)
         rm, dm, am = (_dev_f32(rgb_map, dev), _dev_f32(disp_map, dev), _dev_f32(acc_map, dev))
         self._check(self.lib.pg_compose_frame(
             self.handle, self._stream(), int(H), int(W), (C.c_int * 4)(int(tlx), int(tly), int(brx), int(bry)),
@@ -430,17 +492,13 @@ class HipRenderer:
         """Frames on ALL devices of the handle (pg_render_frames), host in / host out: numpy arrays
         rgbs [F,H,W,3], disps [F,H,W,1], accs [F,H,W,1] (+ rgb8 uint8 [F,H,W,3]).  `boxes` = list of
         ((tl_x, tl_y), (br_x, br_y)); skts [F,24,4,4], cyls [F,5] (one pose per frame)."""
-        cfg = self.cfg
-        S = cfg.n_samples if n_samples is None else int(n_samples)
-        N = cfg.n_importance if n_importance is None else int(n_importance)
+        S, N = _resolve_sn(self.cfg, n_samples, n_importance)
         F = len(boxes)
         c2w_h = np.ascontiguousarray(np.stack([np.asarray(torch.as_tensor(c).detach().cpu(), dtype=np.float32)[:3, :4]
                                                for c in c2ws]))
         intr = np.zeros((F, 4), dtype=np.float32)
         for i in range(F):
-            f = np.asarray(torch.as_tensor(focals[i] if np.ndim(focals) > 0 else focals).detach().cpu(), dtype=np.float64).reshape(-1)
-            intr[i, 0], intr[i, 1] = (f[0], f[0]) if f.size < 2 else (f[0], f[1])
-            intr[i, 2], intr[i, 3] = (W * 0.5, H * 0.5) if centers is None else (float(centers[i][0]), float(centers[i][1]))
+            intr[i] = _intrinsics(H, W, focals[i] if np.ndim(focals) > 0 else focals, None if centers is None else centers[i])
         bx = np.ascontiguousarray(np.array([[b[0][0], b[0][1], b[1][0], b[1][1]] for b in boxes], dtype=np.int32))
         sk = _np32(skts).reshape(-1, 24, 4, 4)
         cy = _np32(cyls).reshape(-1, 5)
@@ -525,9 +583,8 @@ class HipRenderer:
             raise ValueError(f"{w2c.shape[0]} cameras for {F} poses")
         phi = np.linspace(0., 2 * np.pi, 50)
         ring = np.ascontiguousarray(np.stack([np.cos(phi), np.sin(phi)], -1))
-        f = np.asarray(torch.as_tensor(focal).detach().cpu(), dtype=np.float64).reshape(-1)
-        fx, fy = (float(np.float32(f[0])), float(np.float32(f[0]))) if f.size < 2 else (float(np.float32(f[0])), float(np.float32(f[1])))
-        offx, offy = (int(W * .5), int(H * .5)) if center is None else (int(center[0]), int(center[1]))
+        fx, fy, cx, cy = _intrinsics(H, W, focal, center, f32_focal=True)
+        offx, offy = int(cx), int(cy)                   # (the reference's integer principal point)
         ext = extend_mm * ext_scale
         d_w2c = torch.tensor(w2c, dtype=torch.float64, device=self.device)
         d_ring = torch.tensor(ring, dtype=torch.float64, device=self.device)
@@ -550,31 +607,25 @@ class HipRenderer:
                                                     _ptr(nf), _ptr(z)))
         return nf, z
 
-    def stage_eval(self, which, ray_batch, z, skts, cams=None, want_dbg=False, dbg_stage=0):
-        rb = _dev_f32(ray_batch, self.device)
+    def stage_eval(self, which, ray_batch, z, skts, cams=None, want_dbg=False, dbg_stage=0, dbg=None):
+        """Net `which` at the depths z [n,S] (pg_stage_eval) -> raw [n,S,4] (+ the activations of `dbg_stage` with want_dbg).
+        `dbg`: the caller's own buffer for a dbg_stage that writes something else (97: counters)."""
         zz = _dev_f32(z, self.device)
         n, S = zz.shape
-        sk, ps = self._pose_args(skts, n)
-        cam = None if cams is None else _dev_f32(cams.reshape(-1), self.device)
+        c = marshal_ray_call(self.cfg, self.device, ray_batch, skts, None, cams, n_samples=S, n_importance=0)
         raw = torch.empty(n, S, 4, device=self.device)
-        dbg = torch.zeros(n * S, 256, device=self.device) if want_dbg else None
-        self._check(self.lib.pg_stage_eval(self.handle, self._stream(), int(which), n, S, _ptr(rb), _ptr(zz),
-                                           _ptr(sk), ps, _ptr(cam), _ptr(raw), _ptr(dbg), int(dbg_stage)))
+        if want_dbg:
+            dbg = torch.zeros(n * S, 256, device=self.device)
+        self._check(self.lib.pg_stage_eval(self.handle, self._stream(), int(which), n, S, _ptr(c.rb), _ptr(zz),
+                                           _ptr(c.sk), c.ps, _ptr(c.cam), _ptr(raw), _ptr(dbg), int(dbg_stage)))
         return (raw, dbg) if want_dbg else raw
 
     def limb_skip_stats(self, which, ray_batch, z, skts, cams=None):
         """Measurement aid (pg_stage_eval, dbg_stage 97): what the limb masks of the fused kernel leave out on this launch --
         the kernel itself counts.  Returns the fraction of (pass, limb) pairs left out of whole passes and the fraction of
         (wave or column tile, limb) pairs left out at the finer level (which includes the former)."""
-        rb = _dev_f32(ray_batch, self.device)
-        zz = _dev_f32(z, self.device)
-        n, S = zz.shape
-        sk, ps = self._pose_args(skts, n)
-        cam = None if cams is None else _dev_f32(cams.reshape(-1), self.device)
-        raw = torch.empty(n, S, 4, device=self.device)
         cnt = torch.zeros(64, device=self.device, dtype=torch.int32)
-        self._check(self.lib.pg_stage_eval(self.handle, self._stream(), int(which), n, S, _ptr(rb), _ptr(zz),
-                                           _ptr(sk), ps, _ptr(cam), _ptr(raw), cnt.data_ptr(), 97))
+        self.stage_eval(which, ray_batch, z, skts, cams, dbg_stage=97, dbg=cnt)
         return _wave_stats([int(v) for v in cnt[:5].cpu()])
 
     def stage_composite(self, ray_batch, z, raw, n_importance=0):
@@ -603,11 +654,44 @@ def _wave_stats(c):
             "empty_waves_frac": empty / max(8 * passes, 1), "skipped_waves_frac": skipped / max(8 * passes, 1)}
 
 
-def _same_state(a, b) -> bool:
-    """two state dicts with the same keys and bitwise equal values"""
-    if set(a) != set(b):
-        return False
-    return all(np.array_equal(_np32(a[k]), _np32(b[k])) for k in a)
+def check_single_net_states(coarse, fine):
+    """A single-net caster has one net, which the reference saves under both keys (raycasters.py:751-766): a fine state
+    dict, where there is one, must hold the coarse one's keys and bitwise its values.  Anything else is not the reference's
+    checkpoint, and nobody guesses which of the two to render."""
+    if coarse is None or fine is None:
+        return
+    if set(coarse) != set(fine) or not all(np.array_equal(_np32(coarse[k]), _np32(fine[k])) for k in coarse):
+        raise ValueError("single_net: network_fine_state_dict differs from network_fn_state_dict "
+                         "(a single-net caster has one net; not guessing which one to render)")
+
+
+def refuse_reference_kwargs(who, check_preproc, skts, cyls, kw, own_fine=None):
+    """Refuse, don't render differently: a caller configured for anything the fused kernels do not compute.  `kw`: the
+    reference's keywords beyond the ones the casters act on, as `who`.forward got them; `own_fine`: the one `network_fine`
+    argument that is no request for another net (TrainableRayCaster's own).  retraw / verbose / ext_scale change nothing
+    the reference returns for these calls and are ignored."""
+    kw = dict(kw)
+    fwd_type = kw.pop("fwd_type", "")
+    if fwd_type:
+        raise NotImplementedError(f"fwd_type={fwd_type!r} is not on the HIP path of forward (HipRayCaster's call dispatches "
+                                  "'density' and 'mesh')")
+    if kw.pop("subject_idxs", None) is not None:
+        raise NotImplementedError("subject_idxs (multi-subject nets) are not supported")
+    if skts is None or cyls is None:
+        raise ValueError("skts and cyls are required (A-NeRF bone-relative rendering)")
+    nerf_type = kw.pop("nerf_type", "nerf")
+    if nerf_type != "nerf":
+        raise NotImplementedError(f"nerf_type={nerf_type!r}: only 'nerf' is on the HIP path")
+    if not kw.pop("use_viewdirs", True):
+        raise NotImplementedError("use_viewdirs=False: the HIP kernels always evaluate the view branch (nerf.py:112-121)")
+    fine = kw.pop("network_fine", None)
+    if fine is not None and fine is not own_fine:
+        raise NotImplementedError("network_fine: the caster renders with the nets it was loaded with (load_state_dict)")
+    check_preproc(kw.pop("preproc_kwargs", None))
+    for k in ("retraw", "verbose", "ext_scale"):
+        kw.pop(k, None)
+    if kw:
+        raise TypeError(f"{who}.forward: unexpected keyword arguments {sorted(kw)}")
 
 
 class HipRayCaster:
@@ -630,8 +714,8 @@ class HipRayCaster:
     @classmethod
     def from_weights(cls, cfg, w_coarse, w_fine, tau_v, tau_d, device="cuda:0", precision=PREC_BF16, devices=None):
         """`w_fine` may be None (coarse-only renders, or single_net: network_fine is network)."""
-        if cfg.single_net and w_fine is not None and not _same_state(w_coarse, w_fine):
-            raise ValueError("single_net: the fine weights differ from the coarse ones (the reference has one net)")
+        if cfg.single_net:
+            check_single_net_states(w_coarse, w_fine)
         rc = cls(cfg, device, precision, devices=devices)
         rc.renderer.load_network(0, w_coarse)
         if w_fine is not None and not cfg.single_net:
@@ -691,11 +775,8 @@ class HipRayCaster:
     def load_state_dict(self, ckpt, strict=True):
         r = self.renderer
         fine = ckpt.get("network_fine_state_dict")
-        if self.cfg.single_net and fine is not None and "network_fn_state_dict" in ckpt \
-                and not _same_state(ckpt["network_fn_state_dict"], fine):
-            # the reference saves the one module under both keys (raycasters.py:751-766): differing dicts are not its checkpoint
-            raise ValueError("single_net checkpoint: network_fine_state_dict differs from network_fn_state_dict "
-                             "(a single-net caster has one net; not guessing which one to render)")
+        if self.cfg.single_net:
+            check_single_net_states(ckpt.get("network_fn_state_dict"), fine)
         if "network_fn_state_dict" in ckpt:
             r.load_network(0, ckpt["network_fn_state_dict"])
         elif strict:
@@ -723,45 +804,23 @@ class HipRayCaster:
                 network_fine=None, raw_noise_std=0., ray_noise_std=0., verbose=False, ext_scale=0.001,
                 pytest=False, preproc_kwargs=None, nerf_type="nerf", fwd_type="", use_viewdirs=True,
                 want_alpha=True, extras=False, draws=None, **unused):
-        """`RayCaster.forward` (core/raycasters.py:349-474), forward values only (no autograd graph:
-        SURVEY.md 8 scopes the renderer, not NeRF training).  perturb / raw_noise_std /
+        """`RayCaster.forward` (core/raycasters.py:349-474), forward values only (no autograd graph: the training
+        step is train.TrainableRayCaster).  perturb / raw_noise_std /
         ray_noise_std behave as in render_kwargs_train (raycasters.py:156-165): the random numbers
         come from torch's generator on the caster's device, from numpy after np.random.seed(0) when
         pytest=True (the reference's deterministic test mode; it has no override for the position
         noise, which stays a torch draw), or from `draws` when the caller supplies them."""
-        if fwd_type:
-            raise NotImplementedError(f"fwd_type={fwd_type!r} is not on the HIP path ('density' and 'mesh' are)")
-        if subject_idxs is not None:
-            raise NotImplementedError("subject_idxs (multi-subject nets) are not supported")
-        if skts is None or cyls is None:
-            raise ValueError("skts and cyls are required (A-NeRF bone-relative rendering)")
-        # refuse, don't render differently: a caller configured for anything the fused kernels do not compute
-        if nerf_type != "nerf":
-            raise NotImplementedError(f"nerf_type={nerf_type!r}: only 'nerf' is on the HIP path")
-        if not use_viewdirs:
-            raise NotImplementedError("use_viewdirs=False: the HIP kernels always evaluate the view branch (nerf.py:112-121)")
-        if network_fine is not None:
-            raise NotImplementedError("network_fine: the caster renders with the nets it was loaded with (load_state_dict)")
-        if unused:
-            raise TypeError(f"HipRayCaster.forward: unexpected keyword arguments {sorted(unused)}")
-        self._check_preproc_kwargs(preproc_kwargs)
-        # One call = one nanmean group, like get_near_far_in_cylinder on the reference's ray_batch
-        # (ray_utils.py:292-344): only batchify_rays / render_path split a frame into `chunk` groups.
-        # The group size is a property of THIS call: the renderer's own setting (what later direct
-        # render_rays / render_frame calls see) is put back afterwards.
-        keep = self.renderer._chunk
-        if not getattr(self, "_grouped_call", False):
-            self.renderer.set_chunk(max(int(ray_batch.shape[0]), 1))
-        try:
+        refuse_reference_kwargs("HipRayCaster", self._check_preproc_kwargs, skts, cyls,
+                                dict(unused, fwd_type=fwd_type, subject_idxs=subject_idxs, nerf_type=nerf_type,
+                                     use_viewdirs=use_viewdirs, network_fine=network_fine, preproc_kwargs=preproc_kwargs))
+        with one_nanmean_group(self.renderer, ray_batch.shape[0], grouped=getattr(self, "_grouped_call", False)):
             if draws is None and (perturb or raw_noise_std or ray_noise_std):
-                S = self.cfg.n_samples if N_samples is None else int(N_samples)
+                S, _ = _resolve_sn(self.cfg, N_samples, None)
                 draws = self.training_draws(int(ray_batch.shape[0]), S, int(N_importance or 0), perturb, raw_noise_std,
                                             ray_noise_std, pytest=pytest)
             return self.renderer.render_rays(ray_batch, skts, cyls, cams=cams, n_samples=N_samples,
                                              n_importance=N_importance, lindisp=bool(lindisp),
                                              want_alpha=want_alpha, extras=extras, draws=draws)
-        finally:
-            self.renderer.set_chunk(keep)
 
     # the reference's preproc_kwargs (core/raycasters.py:140-152): the encoder objects and the density function
     # `create_raycaster` picked.  The kernels implement exactly one choice of each (SURVEY.md a-8..a-10, a-13).

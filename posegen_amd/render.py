@@ -9,10 +9,12 @@ pose of a frame is passed once.
 """
 from __future__ import annotations
 
+from collections import namedtuple
 from typing import Optional
 
 import numpy as np
 import torch
+import torch.nn.functional as F
 
 from .rays import BoxPixelIds, frame_boxes, get_rays, kp_to_boxes, kp_to_valid_rays
 
@@ -81,6 +83,98 @@ def _pick(x, i):
     return x[i % x.shape[0]:i % x.shape[0] + 1] if x.shape[0] > 1 else x
 
 
+def _scalar_hw(H, W) -> bool:
+    return isinstance(H, (int, np.integer)) and isinstance(W, (int, np.integer))
+
+
+# What the frame drivers share before their first launch (frame_setup): the renderer and its device; the frame size and the
+# centres after render_factor (H, W ints when there is one size: scalar_hw); cylinders [n_pose,5]; per frame the (tl, br)
+# box and (h, w, focal, c2w numpy, center); the BoxPixelIds (pixel ids built only if someone reads them).
+FrameSetup = namedtuple("FrameSetup", "r dev H W scalar_hw centers cyls bboxes meta valid_idxs")
+
+
+def frame_setup(render_poses, hwf, render_kwargs, centers=None, kp=None, cyls=None, render_factor=0, ext_scale=0.00035,
+                boxes=None, need_scalar_hw=None) -> FrameSetup:
+    """render_path's preamble (run_nerf.py:27-74) for every frame driver: the render_factor scaling, the refusal of a call
+    without kp and cyls, the cylinders and boxes -- from the device when the call allows it (rays.frame_boxes), or `boxes` =
+    a kp_to_boxes result of the caller's -- and the pixel ids.  `need_scalar_hw`: the refusal's text for a driver that
+    needs one frame size."""
+    H, W, focal = hwf
+    scalar = _scalar_hw(H, W)
+    if need_scalar_hw and not scalar:
+        raise ValueError(need_scalar_hw)
+    if scalar:
+        H, W = int(H), int(W)
+    if render_factor != 0:
+        H, W = H // render_factor, W // render_factor
+        focal = focal / render_factor if isinstance(focal, float) else focal.copy() / render_factor
+        if centers is not None:
+            centers = centers / render_factor if isinstance(focal, float) else centers.copy() / render_factor
+    if kp is None and cyls is None:
+        raise NotImplementedError("render_path needs kp or cyls (bounding-cylinder cull)")
+    r, dev = _caster_device(render_kwargs["ray_caster"])
+    if boxes is not None:
+        cyls, bboxes, grids = boxes
+        meta = [g[2:] for g in grids]
+    else:
+        cyls, bboxes, meta = frame_boxes(r, render_poses, H, W, focal, kps=kp, cylinder_params=cyls, ext_scale=ext_scale,
+                                         centers=centers)
+    return FrameSetup(r, dev, H, W, scalar, centers, cyls, bboxes, meta, BoxPixelIds(bboxes, [m[1] for m in meta]))
+
+
+def frame_background(bg_imgs, bg_indices, i, h, w, white_bkgd, dev=None):
+    """Frame i's background as [h*w,3]: image bg_indices[i] (the first one without indices) resized bilinearly to (h, w);
+    None when there are no images or the background is white."""
+    if bg_imgs is None or white_bkgd:
+        return None
+    bgi = torch.tensor(bg_imgs[bg_indices[i]] if bg_indices is not None else bg_imgs[0])
+    bg = F.interpolate(bgi.permute(2, 0, 1)[None].float(), size=(h, w), mode="bilinear",
+                       align_corners=False)[0].permute(1, 2, 0).reshape(h * w, 3)
+    return bg if dev is None else bg.to(dev)
+
+
+def _finite_disp(disp):
+    return torch.nan_to_num(disp, nan=0.0, posinf=float("inf"), neginf=float("-inf"))   # run_nerf.py:142-143
+
+
+def emit_frame(frame_sink, frames, k, rgb, disp, acc):
+    """the k-th finished frame: to the sink as soon as its kernels are enqueued, or kept for frame_stacks"""
+    if frame_sink is not None:
+        frame_sink(k, rgb, _finite_disp(disp), acc)
+    else:
+        frames.append((rgb, disp, acc))
+
+
+def frame_stacks(frame_sink, frames, su: FrameSetup):
+    """The drivers' tail: (rgbs [f,H,W,3], disps [f,H,W,1], accs [f,H,W,1]) of the frames kept by emit_frame -- empty
+    [0,H,W,C] stacks for no frames; None each when the frames went to a sink."""
+    if frame_sink is not None:
+        return None, None, None
+    if not frames:
+        if not su.scalar_hw:
+            raise ValueError("an empty frame share needs scalar H, W to shape its (empty) result")
+        e = lambda c: torch.zeros((0, su.H, su.W, c), device=su.dev)
+        return e(3), e(1), e(1)
+    rgbs, disps, accs = (torch.stack(x) for x in zip(*frames))
+    return rgbs, _finite_disp(disps), accs
+
+
+def frames_to_host(driver, render_kwargs, hwf, n_out, render_factor, ret_acc):
+    """Host delivery of `driver(frame_sink)` (a frame driver's result tuple) as run_nerf.render_path returns it: numpy
+    arrays.  On a GPU, with one frame size and at least one frame, the frames go through a FrameDownloader while the next
+    ones render; otherwise the stacks are copied at the end.  `accs` is [] without ret_acc."""
+    _, dev = _caster_device(render_kwargs["ray_caster"])
+    H, W = hwf[0], hwf[1]
+    if n_out == 0 or torch.device(dev).type != "cuda" or not _scalar_hw(H, W):
+        rgbs, disps, accs, valid_idxs, bboxes = driver(None)
+        return rgbs.cpu().numpy(), disps.cpu().numpy(), accs.cpu().numpy() if ret_acc else [], valid_idxs, bboxes
+    H, W = (int(H) // render_factor, int(W) // render_factor) if render_factor else (int(H), int(W))
+    dl = FrameDownloader(n_out, H, W, ret_acc, dev)
+    _, _, _, valid_idxs, bboxes = driver(dl.sink)
+    res = dl.finish()
+    return res[0], res[1], res[2] if ret_acc else [], valid_idxs, bboxes
+
+
 @torch.no_grad()
 def render_frames_device(render_poses, hwf, chunk, render_kwargs, centers=None, kp=None, skts=None, cyls=None,
                          bg_imgs=None, bg_indices=None, cams=None, render_factor=0, white_bkgd=False,
@@ -91,26 +185,12 @@ def render_frames_device(render_poses, hwf, chunk, render_kwargs, centers=None, 
     list returns empty [0,H,W,C] stacks); `boxes` = a kp_to_boxes result computed by the caller;
     `frame_sink(k, rgb, disp, acc)` is called with the k-th rendered frame's device tensors as soon as its kernels
     are enqueued (render_path starts the device-to-host copy there) -- the stacks are then not built (None)."""
-    H, W, focal = hwf
-    if render_factor != 0:
-        H, W = H // render_factor, W // render_factor
-        focal = focal / render_factor if isinstance(focal, float) else focal.copy() / render_factor
-        if centers is not None:
-            centers = centers / render_factor if isinstance(focal, float) else centers.copy() / render_factor
-    if kp is None and cyls is None:
-        raise NotImplementedError("render_path needs kp or cyls (bounding-cylinder cull)")
-    r, dev = _caster_device(render_kwargs["ray_caster"])
     # Boxes, rays, rendering and the scatter into the background frame on the device (pg_pose_boxes,
     # pg_render_frame): no per-frame meshgrid, no ray copies.
-    if boxes is not None:
-        cyls, bboxes, grids = boxes
-        meta = [g[2:] for g in grids]
-    else:                       # (boxes from the device when the call allows it; the pixel ids only if someone reads them)
-        cyls, bboxes, meta = frame_boxes(r, render_poses, H, W, focal, kps=kp, cylinder_params=cyls, ext_scale=ext_scale,
-                                         centers=centers)
-    valid_idxs = BoxPixelIds(bboxes, [m[1] for m in meta])
+    su = frame_setup(render_poses, hwf, render_kwargs, centers, kp, cyls, render_factor, ext_scale, boxes=boxes)
+    r, dev, cyls = su.r, su.dev, su.cyls
     ids = list(range(len(render_poses))) if frame_ids is None else list(frame_ids)
-    rgbs, disps, accs = [], [], []
+    frames = []
     kw = render_kwargs
     r.set_chunk(int(chunk))
     # poses and cylinders go to the device once: a per-frame host-to-device copy of 1.5 KB is a blocking call that
@@ -122,35 +202,15 @@ def render_frames_device(render_poses, hwf, chunk, render_kwargs, centers=None, 
     if cams is not None:        # frame-code indices on the host once (a per-frame float() of a device tensor would block)
         cams = torch.as_tensor(cams).detach().float().cpu()
     for k, i in enumerate(ids):
-        h, w, f, c2w_np, center = meta[i]
-        bg = None
-        if bg_imgs is not None and not white_bkgd:
-            import torch.nn.functional as F
-            bgi = torch.tensor(bg_imgs[bg_indices[i]] if bg_indices is not None else bg_imgs[0])
-            bg = F.interpolate(bgi.permute(2, 0, 1)[None].float(), size=(h, w), mode="bilinear",
-                               align_corners=False)[0].permute(1, 2, 0).reshape(h * w, 3).to(dev)
+        h, w, f, c2w_np, center = su.meta[i]
         cam = _pick(cams, i)
         rgb_img, disp_img, acc_img = r.render_frame(
-            h, w, f, c2w_np, bboxes[i], _pick(skts, i), _pick(cyls, i), center=center,
+            h, w, f, c2w_np, su.bboxes[i], _pick(skts, i), _pick(cyls, i), center=center,
             cam=None if cam is None else float(cam.reshape(-1)[0]),
             n_samples=kw.get("N_samples"), n_importance=kw.get("N_importance"), lindisp=bool(kw.get("lindisp", False)),
-            bg=bg, base_bg=1.0 if white_bkgd else 0.0)
-        if frame_sink is not None:
-            frame_sink(k, rgb_img, torch.nan_to_num(disp_img, nan=0.0, posinf=float("inf"), neginf=float("-inf")), acc_img)
-            continue
-        rgbs.append(rgb_img)
-        disps.append(disp_img)
-        accs.append(acc_img)
-    if frame_sink is not None:
-        return None, None, None, valid_idxs, bboxes
-    if not ids:
-        if not (isinstance(H, (int, np.integer)) and isinstance(W, (int, np.integer))):
-            raise ValueError("an empty frame share needs scalar H, W to shape its (empty) result")
-        e = lambda c: torch.zeros((0, int(H), int(W), c), device=dev)
-        return e(3), e(1), e(1), valid_idxs, bboxes
-    rgbs, disps, accs = torch.stack(rgbs), torch.stack(disps), torch.stack(accs)
-    disps = torch.nan_to_num(disps, nan=0.0, posinf=float("inf"), neginf=float("-inf"))   # run_nerf.py:142-143
-    return rgbs, disps, accs, valid_idxs, bboxes
+            bg=frame_background(bg_imgs, bg_indices, i, h, w, white_bkgd, dev), base_bg=1.0 if white_bkgd else 0.0)
+        emit_frame(frame_sink, frames, k, rgb_img, disp_img, acc_img)
+    return frame_stacks(frame_sink, frames, su) + (su.valid_idxs, su.bboxes)
 
 
 @torch.no_grad()
@@ -166,26 +226,14 @@ def render_path(render_poses, hwf, chunk, render_kwargs, centers=None, kp=None, 
     """
     r, _ = _caster_device(render_kwargs["ray_caster"])
     if getattr(r, "n_devices", 1) > 1 and frame_ids is None and (bg_imgs is None or white_bkgd or bg_indices is None):
-        return _render_path_multi(r, render_poses, hwf, chunk, render_kwargs, centers, kp, skts, cyls, bg_imgs, cams,
+        return _render_path_multi(render_poses, hwf, chunk, render_kwargs, centers, kp, skts, cyls, bg_imgs, cams,
                                   render_factor, white_bkgd, ret_acc, ext_scale)
-    H, W = hwf[0], hwf[1]
-    n_out = len(render_poses) if frame_ids is None else len(frame_ids)
-    _, dev = _caster_device(render_kwargs["ray_caster"])
-    if n_out == 0 or torch.device(dev).type != "cuda" or not (isinstance(H, (int, np.integer)) and isinstance(W, (int, np.integer))):
-        rgbs, disps, accs, valid_idxs, bboxes = render_frames_device(
-            render_poses, hwf, chunk, render_kwargs, centers=centers, kp=kp, skts=skts, cyls=cyls, bg_imgs=bg_imgs,
-            bg_indices=bg_indices, cams=cams, render_factor=render_factor, white_bkgd=white_bkgd, ext_scale=ext_scale,
-            frame_ids=frame_ids)
-        return (rgbs.cpu().numpy(), disps.cpu().numpy(), accs.cpu().numpy() if ret_acc else [], valid_idxs, bboxes)
-    if render_factor:
-        H, W = int(H) // render_factor, int(W) // render_factor
-    dl = FrameDownloader(n_out, int(H), int(W), ret_acc, dev)
-    _, _, _, valid_idxs, bboxes = render_frames_device(
+    driver = lambda sink: render_frames_device(
         render_poses, hwf, chunk, render_kwargs, centers=centers, kp=kp, skts=skts, cyls=cyls, bg_imgs=bg_imgs,
         bg_indices=bg_indices, cams=cams, render_factor=render_factor, white_bkgd=white_bkgd, ext_scale=ext_scale,
-        frame_ids=frame_ids, frame_sink=dl.sink)
-    res = dl.finish()
-    return (res[0], res[1], res[2] if ret_acc else [], valid_idxs, bboxes)
+        frame_ids=frame_ids, frame_sink=sink)
+    n_out = len(render_poses) if frame_ids is None else len(frame_ids)
+    return frames_to_host(driver, render_kwargs, hwf, n_out, render_factor, ret_acc)
 
 
 class FrameDownloader:
@@ -257,44 +305,29 @@ class FrameDownloader:
         return self.out
 
 
-def _render_path_multi(r, render_poses, hwf, chunk, render_kwargs, centers, kp, skts, cyls, bg_imgs, cams,
+def _render_path_multi(render_poses, hwf, chunk, render_kwargs, centers, kp, skts, cyls, bg_imgs, cams,
                        render_factor, white_bkgd, ret_acc, ext_scale):
     """render_path on a caster that owns several GPUs (HipRayCaster(devices=[...])): one pg_render_frames
     call, frames or ray chunks spread over the devices inside the library (no torch.distributed)."""
-    H, W, focal = hwf
-    if render_factor != 0:
-        H, W = H // render_factor, W // render_factor
-        focal = focal / render_factor if isinstance(focal, float) else focal.copy() / render_factor
-        if centers is not None:
-            centers = centers / render_factor if isinstance(focal, float) else centers.copy() / render_factor
-    if kp is None and cyls is None:
-        raise NotImplementedError("render_path needs kp or cyls (bounding-cylinder cull)")
-    if not (isinstance(H, (int, np.integer)) and isinstance(W, (int, np.integer))):
-        raise ValueError("multi-device render_path needs one frame size (scalar H, W)")
-    cyls, bboxes, meta = frame_boxes(r, render_poses, H, W, focal, kps=kp, cylinder_params=cyls, ext_scale=ext_scale,
-                                     centers=centers)
-    cyls = torch.as_tensor(cyls).detach().float().cpu()
-    valid_idxs = BoxPixelIds(bboxes, [m[1] for m in meta])
-    F = len(render_poses)
+    su = frame_setup(render_poses, hwf, render_kwargs, centers, kp, cyls, render_factor, ext_scale,
+                     need_scalar_hw="multi-device render_path needs one frame size (scalar H, W)")
+    r, H, W, meta = su.r, su.H, su.W, su.meta
+    cyls = torch.as_tensor(su.cyls).detach().float().cpu()
+    F_ = len(render_poses)
     n_pose = cyls.shape[0]
     sk = torch.as_tensor(skts).reshape(-1, 24, 4, 4)
-    sk = torch.stack([sk[i % sk.shape[0]] for i in range(F)])
-    cy = torch.stack([cyls[i % n_pose] for i in range(F)])
+    sk = torch.stack([sk[i % sk.shape[0]] for i in range(F_)])
+    cy = torch.stack([cyls[i % n_pose] for i in range(F_)])
     cm = None
     if cams is not None:
         ct = torch.as_tensor(cams).reshape(-1).float()
-        cm = torch.stack([ct[i % ct.shape[0]] for i in range(F)])
-    bg = None
-    if bg_imgs is not None and not white_bkgd:
-        import torch.nn.functional as Fn
-        bgi = torch.tensor(bg_imgs[0])
-        bg = Fn.interpolate(bgi.permute(2, 0, 1)[None].float(), size=(int(H), int(W)), mode="bilinear",
-                            align_corners=False)[0].permute(1, 2, 0).reshape(int(H) * int(W), 3)
+        cm = torch.stack([ct[i % ct.shape[0]] for i in range(F_)])
     r.set_chunk(int(chunk))
     kw = render_kwargs
-    focals = [m[2] for m in meta]
-    rgbs, disps, accs = r.render_frames(int(H), int(W), focals, [m[3] for m in meta], bboxes, sk, cy,
-                                        centers=None if centers is None else [m[4] for m in meta], cams=cm,
+    rgbs, disps, accs = r.render_frames(H, W, [m[2] for m in meta], [m[3] for m in meta], su.bboxes, sk, cy,
+                                        centers=None if su.centers is None else [m[4] for m in meta], cams=cm,
                                         n_samples=kw.get("N_samples"), n_importance=kw.get("N_importance"),
-                                        lindisp=bool(kw.get("lindisp", False)), bg=bg, base_bg=1.0 if white_bkgd else 0.0)
-    return rgbs, disps, accs if ret_acc else [], valid_idxs, bboxes
+                                        lindisp=bool(kw.get("lindisp", False)),
+                                        bg=frame_background(bg_imgs, None, 0, H, W, white_bkgd),    # (one background: render_path)
+                                        base_bg=1.0 if white_bkgd else 0.0)
+    return rgbs, disps, accs if ret_acc else [], su.valid_idxs, su.bboxes

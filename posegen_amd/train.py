@@ -16,7 +16,9 @@ from typing import Dict, Optional
 import torch
 
 from . import _ffi
-from .raycaster import NET_TENSOR_ORDER, HipRayCaster, _dev_f32, _ptr, make_training_draws
+from .raycaster import (NET_TENSOR_ORDER, HipRayCaster, _dev_f32, _ptr, _resolve_sn, alloc_ray_outputs,
+                        check_single_net_states, make_training_draws, marshal_ray_call, one_nanmean_group,
+                        refuse_reference_kwargs)
 
 
 class _RenderRaysFn(torch.autograd.Function):
@@ -30,13 +32,12 @@ class _RenderRaysFn(torch.autograd.Function):
     def forward(ctx, caster, call, skts, *params):
         r = caster.renderer
         lib, dev = r.lib, r.device
-        rb, sk, ps, cy, cs, cam, S, N, flags, draws = call
-        n = rb.shape[0]
+        n, S, N = call.n, call.S, call.N                 # (`call`: the RayCall of raycaster.marshal_ray_call)
         ctx.skts_shape, ctx.skts_dtype, ctx.skts_device = tuple(skts.shape), skts.dtype, skts.device
         nper = 24 + (1 if caster.cfg.framecode_ch > 0 else 0)
         single = bool(caster.cfg.single_net)             # one parameter set: network_fine is network
         nets = [params[:nper], params[nper:2 * nper]] if N > 0 and not single else [params[:nper]]
-        keep = [rb, sk, cy, cam]
+        keep = list(call.keep)
         structs = []
         for tens in nets:
             st = _ffi.PgNetParams()
@@ -51,27 +52,12 @@ class _RenderRaysFn(torch.autograd.Function):
                 keep.append(ext)
                 st.codes, st.n_codes = ext.data_ptr(), codes.shape[0]
             structs.append(st)
-        new = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)
-        out = {"rgb_map": new(n, 3), "disp_map": new(n), "acc_map": new(n)}
-        if N > 0:
-            out.update({"rgb0": new(n, 3), "disp0": new(n), "acc0": new(n)})
-        if single:                                       # what the reference's single-net call returns besides the maps
-            out["alpha"] = new(n, S + N)
-            if N > 0:
-                out["alpha0"] = new(n, S)
-        po = _ffi.PgOutputs()
-        for k, v in out.items():
-            setattr(po, k, v.data_ptr())
-        pd = None
-        if draws:
-            pd = _ffi.PgTrainDraws()
-            for k, t in draws.items():
-                t = _dev_f32(t, dev)
-                keep.append(t)
-                setattr(pd, k, t.data_ptr())
+        # the maps always; the alphas for a single-net caster, whose call in the reference returns them besides the maps
+        out, _, po = alloc_ray_outputs(n, S, N, dev, want_alpha=single)
         tape = C.c_int64(0)
-        r._check(lib.pg_train_forward(r.handle, r._stream(), n, _ptr(rb), _ptr(sk), ps, _ptr(cy), cs, _ptr(cam), S, N, flags,
-                                      None if pd is None else C.byref(pd), C.byref(structs[0]),
+        r._check(lib.pg_train_forward(r.handle, r._stream(), n, _ptr(call.rb), _ptr(call.sk), call.ps, _ptr(call.cy), call.cs,
+                                      _ptr(call.cam), S, N, call.flags,
+                                      None if call.draws is None else C.byref(call.draws), C.byref(structs[0]),
                                       C.byref(structs[1]) if len(structs) > 1 else None, C.byref(po), C.byref(tape)))
         ctx.caster, ctx.n_nets, ctx.nper, ctx.keep, ctx.tape_id = caster, len(nets), nper, keep, tape.value
         ctx.shapes = [tuple(p.shape) for p in params]
@@ -311,35 +297,18 @@ class TrainableRayCaster(torch.nn.Module):
                 r.load_network(which, self.net_state_dict(which))
         self._stale = False
 
-    def _check_unused(self, unused):
-        """The reference's keywords the kernels do not honour are refused, in training and in eval mode alike."""
-        if not unused:
-            return
-        unused = dict(unused)
-        self.caster._check_preproc_kwargs(unused.pop("preproc_kwargs", None))
-        if unused.pop("nerf_type", "nerf") != "nerf" or not unused.pop("use_viewdirs", True):
-            raise NotImplementedError("only nerf_type='nerf' with view directions is on the HIP path")
-        if unused.get("network_fine") is not None and unused["network_fine"] is not self.network_fine:
-            raise NotImplementedError("a network_fine argument other than this caster's own fine network")
-        for k in ("retraw", "verbose", "ext_scale", "network_fine"):
-            unused.pop(k, None)
-        if unused:
-            raise TypeError(f"TrainableRayCaster.forward: unexpected keyword arguments {sorted(unused)}")
-
     def forward(self, ray_batch, N_samples=None, kp_batch=None, skts=None, cyls=None, bones=None, cams=None,
                 subject_idxs=None, lindisp=False, perturb=0., N_importance=0, raw_noise_std=0., ray_noise_std=0.,
                 pytest=False, draws: Optional[Dict[str, torch.Tensor]] = None, **unused):
-        self._check_unused(unused)
+        # the reference's keywords the kernels do not honour are refused, in training and in eval mode alike
+        refuse_reference_kwargs("TrainableRayCaster", self.caster._check_preproc_kwargs, skts, cyls,
+                                dict(unused, subject_idxs=subject_idxs), own_fine=self.network_fine)
         if not (self.training and torch.is_grad_enabled()):
             if self._stale:                              # a backward pass has run since the last packing: render what was trained
                 self.sync_inference_weights()
             return self.caster(ray_batch, N_samples=N_samples, kp_batch=kp_batch, skts=skts, cyls=cyls, bones=bones, cams=cams,
                                subject_idxs=subject_idxs, lindisp=lindisp, perturb=perturb, N_importance=N_importance,
                                raw_noise_std=raw_noise_std, ray_noise_std=ray_noise_std, pytest=pytest, draws=draws)
-        if subject_idxs is not None:
-            raise NotImplementedError("subject_idxs (multi-subject nets) are not supported")
-        if skts is None or cyls is None:
-            raise ValueError("skts and cyls are required (A-NeRF bone-relative rendering)")
         # Without opt_pose the backward pass differentiates with respect to the networks' tensors only: a pose that wants a
         # gradient is refused rather than left without one.  With opt_pose (the reference's pose refinement, popt_layer,
         # trainer.py:286-313, 453-485) skts gets dL/dskts; kp_batch / bones are accepted and get none, as in the reference,
@@ -352,37 +321,17 @@ class TrainableRayCaster(torch.nn.Module):
                 raise NotImplementedError(f"{name} requires a gradient: {why}; pass a detached tensor")
         r = self.caster.renderer
         cfg = self.cfg
-        S = cfg.n_samples if N_samples is None else int(N_samples)
-        N = int(N_importance or 0)
+        S, N = _resolve_sn(cfg, N_samples, int(N_importance or 0))
         if N > 0 and self.network_fine is None:
             raise ValueError("N_importance > 0 needs the fine network")
-        rb = _dev_f32(ray_batch, r.device)
-        n = rb.shape[0]
-        if rb.shape[1] != 11:
-            pad = torch.zeros(n, 11, device=r.device)
-            pad[:, :min(11, rb.shape[1])] = rb[:, :11]
-            rb = pad
-        skts = torch.as_tensor(skts)
-        sk, ps = r._pose_args(skts.detach(), n)
-        cy, cs = r._cyl_args(cyls, n)
-        cam = None
-        if cams is not None:
-            cam = _dev_f32(torch.as_tensor(cams).reshape(-1), r.device)
-            if cam.shape[0] == 1 and n > 1:
-                cam = cam.expand(n).contiguous()
+        n = ray_batch.shape[0]
         if draws is None and (perturb or raw_noise_std or ray_noise_std):
             draws = make_training_draws(n, S, N, perturb, raw_noise_std, ray_noise_std, pytest=pytest,
                                         density_scale=cfg.density_scale, device=r.device)
-        if draws and N == 0:
-            draws = {k: v for k, v in draws.items() if k not in ("u_rand", "noise1")}
-        keep = r._chunk
-        r.set_chunk(max(n, 1))                          # one call = one nanmean group (ray_utils.py:292-344)
-        try:
-            flags = _ffi.PG_FLAG_LINDISP if lindisp else 0
-            rgb, acc, rgb0, acc0, disp, disp0, alpha, alpha0 = _RenderRaysFn.apply(self, (rb, sk, ps, cy, cs, cam, S, N, flags, draws or None), skts,
-                                                                    *self._flat())
-        finally:
-            r.set_chunk(keep)
+        skts = torch.as_tensor(skts)
+        call = marshal_ray_call(cfg, r.device, ray_batch, skts, cyls, cams, S, N, lindisp, draws)
+        with one_nanmean_group(r, n):
+            rgb, acc, rgb0, acc0, disp, disp0, alpha, alpha0 = _RenderRaysFn.apply(self, call, skts, *self._flat())
         out = {"rgb_map": rgb, "disp_map": disp, "acc_map": acc}
         if N > 0:
             out.update({"rgb0": rgb0, "disp0": disp0, "acc0": acc0})
@@ -414,10 +363,7 @@ class SingleNetTrainableRayCaster(TrainableRayCaster):
             raise ValueError("SingleNetTrainableRayCaster needs a single_net caster (two-net models: TrainableRayCaster)")
 
     def load_state_dict(self, ckpt, strict=True):
-        from .raycaster import _same_state
-        fine = ckpt.get("network_fine_state_dict")
-        if fine is not None and "network_fn_state_dict" in ckpt and not _same_state(ckpt["network_fn_state_dict"], fine):
-            raise ValueError("single_net checkpoint: network_fine_state_dict differs from network_fn_state_dict")
+        check_single_net_states(ckpt.get("network_fn_state_dict"), ckpt.get("network_fine_state_dict"))
         super().load_state_dict(ckpt, strict=strict)
 
 

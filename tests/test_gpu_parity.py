@@ -384,6 +384,58 @@ def test_training_mode_draws_change_the_image_and_eval_is_untouched(casters):
                       draws={"t_rand": dr["t_rand"][:, :-1]})
 
 
+def _seventy_rays(name, S=32, N=16):
+    """70 rays (ragged: no multiple of 64) of a fixture that holds 64: its rays and the first 6 once more; draws for S + N."""
+    from posegen_amd.raycaster import make_training_draws
+    g = load_golden(name)
+    rb, skts, cyl, cams = _inputs(g)
+    rb = torch.cat([rb, rb[:6]])
+    torch.manual_seed(11)
+    draws = make_training_draws(70, S, N, perturb=1., raw_noise_std=1., ray_noise_std=0.005)
+    assert set(draws) == {"t_rand", "u_rand", "noise0", "noise1", "ray_noise"}
+    return g, rb, skts, cyl, cams, draws
+
+
+def _same_maps(a, b):
+    assert set(a) == set(b) and {"rgb_map", "disp_map", "acc_map", "rgb0", "disp0", "acc0"} <= set(a)
+    for k in a:
+        assert torch.equal(a[k], b[k]), k
+
+
+def test_eight_column_ray_batch_is_the_zero_padded_one(casters):
+    """ray_batch[:, :8] (o, d, near, far) and the same rays zero-padded to [n,11] give bitwise the same maps: the eval call and
+    the training-mode call (explicit draws) -- one marshal pads for both.  70 rays, 32 + 16 samples, fp32."""
+    g, rb, skts, cyl, _, draws = _seventy_rays("rays_train")
+    c = casters(cfg_from_golden(g), int(g["seed_model"]), PREC_FP32)
+    rb8 = rb[:, :8].contiguous()
+    padded = torch.cat([rb8, torch.zeros(70, 3)], 1)
+    assert float(rb[:, 8:].abs().max()) > 0               # (the fixture's own columns 8..10 are not zero)
+    _same_maps(c.renderer.render_rays(rb8, skts, cyl, n_samples=32, n_importance=16),
+               c.renderer.render_rays(padded, skts, cyl, n_samples=32, n_importance=16))
+    c.train()
+    try:
+        kw = dict(N_samples=32, skts=skts, cyls=cyl, N_importance=16, draws=draws)
+        a, b = c(rb8, **kw), c(padded, **kw)
+        ev = c.renderer.render_rays(rb8, skts, cyl, n_samples=32, n_importance=16)
+    finally:
+        c.eval()
+    _same_maps(a, b)
+    assert not torch.equal(a["rgb_map"], ev["rgb_map"])   # (the draws were live)
+
+
+def test_one_frame_code_index_serves_all_rays(casters):
+    """`cams` of one element with n > 1 rays = the index expanded to [n] (h36m: frame codes), eval and training mode."""
+    g, rb, skts, cyl, cams, draws = _seventy_rays("rays_h36m")
+    c = casters(cfg_from_golden(g), int(g["seed_model"]), PREC_FP32)
+    one, every = cams[3:4].clone(), cams[3:4].expand(70).contiguous()
+    kw = dict(n_samples=32, n_importance=16)
+    _same_maps(c.renderer.render_rays(rb, skts, cyl, cams=one, **kw), c.renderer.render_rays(rb, skts, cyl, cams=every, **kw))
+    _same_maps(c.renderer.render_rays(rb, skts, cyl, cams=one, draws=draws, **kw),
+               c.renderer.render_rays(rb, skts, cyl, cams=every, draws=draws, **kw))
+    other = c.renderer.render_rays(rb, skts, cyl, cams=cams[3:4] + 1, **kw)
+    assert not torch.equal(other["rgb_map"], c.renderer.render_rays(rb, skts, cyl, cams=one, **kw)["rgb_map"])
+
+
 @pytest.mark.parametrize("name", ["rays_surreal", "rays_allhit", "rays_h36m"])
 @pytest.mark.parametrize("prec,quant", [(PREC_BF16, "bf16"), (PREC_FP16, "fp16")])
 def test_render_rays_fast_modes(casters, name, prec, quant):

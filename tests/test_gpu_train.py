@@ -246,6 +246,61 @@ def test_inputs_that_want_a_gradient_are_refused():
     m.renderer.close()
 
 
+def _seventy_rays(name, S=32, N=16):
+    """70 rays (ragged: no multiple of 64) of a fixture that holds 64: its rays and the first 6 once more; draws for S + N."""
+    from posegen_amd.raycaster import make_training_draws
+    g = load_golden(name)
+    rb = torch.tensor(g["ray_batch"])
+    rb = torch.cat([rb, rb[:6]])
+    torch.manual_seed(11)
+    draws = make_training_draws(70, S, N, perturb=1., raw_noise_std=1., ray_noise_std=0.005)
+    return g, rb, torch.tensor(g["skts"]), torch.tensor(g["cyl"]), draws
+
+
+def _same_maps(a, b):
+    assert set(a) == set(b) == {"rgb_map", "disp_map", "acc_map", "rgb0", "disp0", "acc0"}
+    for k in a:
+        assert torch.equal(a[k], b[k]), k
+
+
+def test_training_forward_marshals_like_render_rays():
+    """The training forward goes through the marshal of render_rays: ray_batch[:, :8] is the zero-padded [n,11] batch (bitwise
+    the same maps; 70 rays, 32 + 16 samples, explicit draws, fp32), and a wrongly shaped draw, an unknown draw and a ray batch
+    of 7 columns are refused with ValueError, as render_rays refuses them."""
+    g, rb, sk, cy, draws = _seventy_rays("rays_train")
+    cfg, m = _trainable(g)
+    m.train()
+    rb8 = rb[:, :8].contiguous()
+    padded = torch.cat([rb8, torch.zeros(70, 3)], 1)
+    kw = dict(N_samples=32, skts=sk, cyls=cy, N_importance=16)
+    a, b = m(rb8, draws=draws, **kw), m(padded, draws=draws, **kw)
+    assert a["rgb_map"].grad_fn is not None
+    _same_maps(a, b)
+    assert not torch.equal(a["rgb_map"], m(rb8, **kw)["rgb_map"])          # (the draws were live)
+    for bad in (dict(draws, t_rand=draws["t_rand"][:, :-1]), dict(draws, noise1=draws["noise0"]), dict(draws, v_rand=draws["u_rand"])):
+        with pytest.raises(ValueError):
+            m(rb8, draws=bad, **kw)
+        with pytest.raises(ValueError):
+            m.renderer.render_rays(rb8, sk, cy, n_samples=32, n_importance=16, draws=bad)
+    for call in (lambda: m(rb[:, :7], draws=draws, **kw), lambda: m.renderer.render_rays(rb[:, :7], sk, cy, n_samples=32, n_importance=16)):
+        with pytest.raises(ValueError):
+            call()
+    m.renderer.close()
+
+
+def test_training_forward_one_frame_code_index_serves_all_rays():
+    """`cams` of one element with n > 1 rays = the index expanded to [n], in the training forward (h36m: frame codes)."""
+    g, rb, sk, cy, draws = _seventy_rays("rays_h36m")
+    cfg, m = _trainable(g)
+    m.train()
+    cams = torch.tensor(g["cams"])
+    kw = dict(N_samples=32, skts=sk, cyls=cy, N_importance=16, draws=draws)
+    a = m(rb, cams=cams[3:4].clone(), **kw)
+    _same_maps(a, m(rb, cams=cams[3:4].expand(70).contiguous(), **kw))
+    assert not torch.equal(a["rgb_map"], m(rb, cams=cams[3:4] + 1, **kw)["rgb_map"])
+    m.renderer.close()
+
+
 @pytest.mark.parametrize("name", ["train_grads", "train_grads_h36m"])
 def test_bf16_training_mode_gradients_are_close_and_repeatable(name):
     """The 16-bit training mode (caster precision bf16: the tape -- embedding rows, activations, activation gradients --

@@ -228,6 +228,104 @@ def test_render_path_distributed_without_a_process_group_is_the_single_device_re
         assert np.array_equal(a, b)
 
 
+def _stub_with_background_and_cams():
+    """StubRenderer whose frames also depend on the frame-code index and the background, so that a driver which picks
+    another `cams` entry or another (or a differently resized) background image returns other frames."""
+    ns = {}
+    exec(_GLOO_RENDER_WORKER.split("dist.init_process_group")[0].replace("sys.path.insert(0, sys.argv[1])", ""), ns)
+    Base = ns["StubRenderer"]
+
+    class Stub(Base):
+        def render_frame_range(self, H, W, focal, c2w, box, skts, cyl, r0, r1, center=None, cam=None, **kw):
+            p = Base.render_frame_range(self, H, W, focal, c2w, box, skts, cyl, r0, r1)
+            p[4 * (r1 - r0):] += 0.0625 * (0. if cam is None else float(cam))
+            return p
+
+        def compose_frame(self, H, W, box, rgb_map, disp_map, acc_map, bg=None, base_bg=0., **kw):
+            rgb, disp, acc = Base.compose_frame(self, H, W, box, rgb_map, disp_map, acc_map, base_bg=base_bg)
+            if bg is not None:
+                assert bg.shape == (H * W, 3)
+                rgb = rgb + bg.view(H, W, 3) * (1 - acc)
+            return rgb, disp, acc
+
+        def render_frame(self, H, W, focal, c2w, box, skts, cyl, center=None, cam=None, bg=None, base_bg=0., **kw):
+            (tlx, tly), (brx, bry) = box
+            n = (bry - tly) * (brx - tlx)
+            p = self.render_frame_range(H, W, focal, c2w, box, skts, cyl, 0, n, center=center, cam=cam)
+            return self.compose_frame(H, W, box, p[:3 * n].view(n, 3), p[3 * n:4 * n], p[4 * n:], bg=bg, base_bg=base_bg)
+
+    class Caster:
+        renderer = Stub()
+        module = property(lambda self: self)
+    return Caster()
+
+
+@pytest.mark.parametrize("white_bkgd", [False, True])
+def test_the_three_frame_drivers_share_one_setup(white_bkgd):
+    """render_path, render_path_distributed (no process group) and render_frames_device return equal frames, valid_idxs and
+    boxes for a call that exercises the whole preamble: render_factor, own principal points, one background image per
+    frame picked by bg_indices, fewer frame codes than frames -- and equal empty [0,32,32,C] stacks for no frames."""
+    from posegen_amd import synthetic as syn
+    from posegen_amd.dist import render_frames_distributed, render_path_distributed
+    from posegen_amd.render import render_frames_device, render_path
+    H = W = 64
+    _, kps, skts = syn.make_pose(3, 3)
+    c2ws, focals = syn.make_camera(3, H, W)
+    rng = np.random.RandomState(5)
+    kw = dict(kp=torch.tensor(kps), skts=torch.tensor(skts), centers=np.array([[33., 31.], [30., 34.], [32., 32.]]),
+              bg_imgs=rng.rand(2, H, W, 3).astype(np.float32), bg_indices=[1, 0, 1], cams=torch.tensor([0., 1.]),
+              render_factor=2, white_bkgd=white_bkgd, ext_scale=0.001)
+    rk = {"ray_caster": _stub_with_background_and_cams(), "N_samples": 64, "N_importance": 16}
+    poses, hwf = torch.tensor(c2ws), (H, W, focals)
+    a = render_path(poses, hwf, 256, rk, ret_acc=True, **kw)
+    b = render_path_distributed(poses, hwf, 256, rk, ret_acc=True, **kw)
+    c = render_frames_device(poses, hwf, 256, rk, **kw)
+    assert a[0].shape == (3, 32, 32, 3) and a[1].shape == a[2].shape == (3, 32, 32, 1)
+    if not white_bkgd:                                  # the stub does read the background and the frame code
+        assert not np.array_equal(a[0], render_path(poses, hwf, 256, rk, **dict(kw, bg_indices=[0, 0, 0]))[0])
+        assert not np.array_equal(a[2], render_path(poses, hwf, 256, rk, ret_acc=True, **dict(kw, cams=None))[2])
+    for other in (b, c):
+        for x, y in zip(a[:3], other[:3]):
+            y = y.cpu().numpy() if torch.is_tensor(y) else y
+            assert x.shape == y.shape and x.dtype == y.dtype and np.array_equal(x, y)
+        assert len(other[3]) == 3 and all(np.array_equal(np.asarray(p), np.asarray(q)) for p, q in zip(a[3], other[3]))
+        assert np.array_equal(np.array(a[4]), np.array(other[4]))
+    # no frames: empty stacks of the scaled frame size from every driver
+    e_a = render_path(poses, hwf, 256, rk, ret_acc=True, frame_ids=[], **kw)
+    e_c = render_frames_device(poses, hwf, 256, rk, frame_ids=[], **kw)
+    e_b = render_path_distributed(poses[:0], hwf, 256, rk, ret_acc=True, **dict(kw, kp=kw["kp"][:0], skts=kw["skts"][:0]))
+    e_d = render_frames_distributed(poses[:0], hwf, 256, rk, **dict(kw, kp=kw["kp"][:0], skts=kw["skts"][:0]))
+    for e in (e_a, e_b, e_c, e_d):
+        assert [tuple(x.shape) for x in e[:3]] == [(0, 32, 32, 3), (0, 32, 32, 1), (0, 32, 32, 1)]
+
+
+def test_the_draw_rules_are_one_rule():
+    """make_training_draws makes no u_rand / noise1 without importance samples, and the marshal of a ray-level call
+    (raycaster.marshal_ray_call, what render_rays and the training forward both go through) drops them if a caller passes
+    them all the same, refuses unknown draws and wrong shapes, and refuses a ray batch of fewer than 8 columns."""
+    from posegen_amd import surreal_config
+    from posegen_amd.raycaster import make_training_draws, marshal_ray_call
+    assert set(make_training_draws(5, 32, 0, perturb=1, raw_noise_std=1)) == {"t_rand", "noise0"}
+    cfg = surreal_config()
+    n, S, N = 5, 32, 16
+    rb, skts, cyls = torch.rand(n, 8), torch.eye(4).expand(24, 4, 4), torch.rand(5)
+    call = lambda draws, N=N, rb=rb: marshal_ray_call(cfg, "cpu", rb, skts, cyls, None, S, N, False, draws)
+    d = make_training_draws(n, S, N, perturb=1, raw_noise_std=1, ray_noise_std=1)
+    c = call(d)
+    assert (c.rb.shape, c.ps, c.cs, c.S, c.N) == ((n, 11), 0, 0, S, N) and torch.equal(c.rb[:, :8], rb) and not c.rb[:, 8:].any()
+    assert all(getattr(c.draws, k) == d[k].data_ptr() for k in d) and call(None).draws is None
+    c0 = call({k: v for k, v in d.items() if k != "ray_noise"}, N=0)     # drawn for N = 16: u_rand / noise1 are not looked at with N = 0 ...
+    assert c0.draws.u_rand is None and c0.draws.noise1 is None and c0.draws.t_rand == d["t_rand"].data_ptr()
+    with pytest.raises(ValueError):                     # ... while ray_noise [n, S + 16, 3] has the wrong shape then
+        call({"ray_noise": d["ray_noise"]}, N=0)
+    with pytest.raises(ValueError):
+        call({"t_rand": torch.rand(n, S + 1)})
+    with pytest.raises(ValueError):
+        call({"t_rand": d["t_rand"], "v_rand": d["u_rand"]})
+    with pytest.raises(ValueError):
+        call(None, rb=torch.rand(n, 7))
+
+
 def _plan(n_rays, workers, chunk):
     import ctypes as C
     lib = _ffi.load_library()

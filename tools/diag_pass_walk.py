@@ -12,7 +12,7 @@ import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 from posegen_amd import surreal_config, synthetic as syn
-from posegen_amd.raycaster import HipRayCaster, _ptr
+from posegen_amd.raycaster import HipRayCaster
 from bench import full_frame_rays
 
 prec = sys.argv[1] if len(sys.argv) > 1 else "bf16"
@@ -29,12 +29,10 @@ MAXWG = 1024
 
 
 def stamps(which, zz):
-    n, S = zz.shape
-    sk, ps = r._pose_args(skts, n)
-    out = torch.empty(n, S, 4, device=dev)
+    S = zz.shape[1]
     for _ in range(2):          # (the second launch: clocks settled, weights in L2)
         dbg = torch.zeros(16 + 8 * MAXWG, device=dev, dtype=torch.int32)
-        r._check(r.lib.pg_stage_eval(r.handle, r._stream(), which, n, S, _ptr(rb), _ptr(zz), _ptr(sk), ps, None, _ptr(out), dbg.data_ptr(), 97))
+        r.stage_eval(which, rb, zz, skts, dbg_stage=97, dbg=dbg)
         torch.cuda.synchronize()
     d = dbg.cpu().numpy().view(np.uint32)
     rec = d[16:].reshape(MAXWG, 8)
