@@ -330,6 +330,45 @@ int pg_render_frames(pg_handle* h, int n_frames, int H, int W, const float* c2ws
                      const float* cams, int n_samples, int n_importance, int flags, const float* bg, float base_bg,
                      float* rgbs, float* disps, float* accs, uint8_t* rgb8);
 
+/* ---- the subject bank: S >= 1 complete models ("subjects": independent checkpoints of ONE architecture) behind one
+ * handle (frames drawn from >= 2 weight sets; the reference's subject_idxs).  A handle is created with one
+ * subject, and with one subject nothing differs from a handle without a bank.  Per subject: both nets (tensors, packed
+ * weight images, frame codes -- n_codes may differ between subjects) and the embedder state (cutoff_dist, tau) with a
+ * device copy of the cutoffs of its own.  Shared by the bank: pg_config's geometry (single_net, multires_views,
+ * framecode_ch, the density activation), precision, chunk, on-chip mode, the skip switches, every workspace.
+ * Training acts on the selected subject; the bank is not changed and no other subject selected while a training tape is
+ * outstanding (a pg_train_forward whose backward has not run). */
+#define PG_MAX_SUBJECTS 64
+
+/* 1 <= n <= PG_MAX_SUBJECTS subjects.  Growing keeps the loaded subjects (new ones are empty: no weights, the config's
+ * cutoff_dist, tau 20, embedder not set); shrinking frees the dropped subjects' device memory (waits for the device).
+ * PG_EINVAL: n out of range, the active subject would be dropped (select one that stays first), a tape outstanding. */
+int pg_set_subject_count(pg_handle* h, int n);
+int pg_subject_count(const pg_handle* h);
+
+/* Subject s becomes the active model: every entry point (pg_load_weights, pg_load_weights_device, pg_set_embedder,
+ * pg_set_framecodes, pg_render_rays*, pg_render_frame*, pg_query_density, pg_stage_*, the training entry points) then acts
+ * on it, on every device of the handle.  A swap of host-side pointers: no device allocation, no packing, no copy, no
+ * synchronisation -- safe between two launches enqueued on one stream (a launch has taken its subject's pointers when the
+ * call that enqueued it returns).  PG_EINVAL: s outside [0, count), a tape outstanding. */
+int pg_select_subject(pg_handle* h, int s);
+
+/* Which nets of subject s are loaded (bit 0: coarse, bit 1: fine), the device bytes its packed weight images hold, and how
+ * many images have been built for it so far (packed and uploaded by the first call that needed them, or re-formed on the
+ * device by pg_load_weights_device) -- on the handle's first device; any pointer may be NULL.  A render that alternates
+ * between subjects builds nothing once every subject has rendered in the precision. */
+int pg_subject_info(pg_handle* h, int s, int32_t* loaded_nets, int64_t* image_bytes, int64_t* image_builds);
+
+/* pg_render_frames with one subject per frame: subjects HOST [F] (NULL: every frame with the active subject, which is
+ * pg_render_frames).  The work plan is unchanged; every device selects the subject of the task it is about to enqueue, so
+ * the runs of a frame that is cut over several devices keep the frame's subject.  Every device holds every subject's
+ * weights (pg_load_weights replicates as it does for one model).  The active subject is the same before and after.
+ * PG_EINVAL: a subject outside [0, count); subjects given while a tape is outstanding. */
+int pg_render_frames_subjects(pg_handle* h, int n_frames, int H, int W, const float* c2ws, const float* intrinsics,
+                              const int* boxes, float near, float far, const float* skts, const float* cyls,
+                              const float* cams, int n_samples, int n_importance, int flags, const float* bg, float base_bg,
+                              float* rgbs, float* disps, float* accs, uint8_t* rgb8, const int32_t* subjects);
+
 /* Host-only: the work plan pg_render_frames uses (and posegen_amd.dist.plan_tasks restates for the one-process-
  * per-GPU path): tasks (frame, ray_begin, ray_end, worker, owner) for frames of n_rays[f] rays on n_workers
  * devices with nanmean groups of `chunk` rays; every ray of every frame is in exactly one task, every cut is a

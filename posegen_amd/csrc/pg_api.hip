@@ -408,6 +408,7 @@ int ensure_image(pg_handle* h, int which, int id) {
     if (const int rc = pack_image(h, which, tensors_of(ns, h->cfg), id, p)) return rc;     // (tensors_of folds feature_linear into the view layer: milliseconds of host work, once per load)
     if (const int rc = upload(h, p.data(), p.bytes(), reinterpret_cast<void**>(&s.d))) return rc;
     s.bytes = p.bytes();
+    ++ns.builds;
     return PG_OK;
 }
 
@@ -427,6 +428,20 @@ hipError_t release_images(NetState& ns, uint64_t keep, bool sync) {
         s = {};
     }
     return first;
+}
+
+// Everything a subject holds on the device (the caller has set the device); the subject is empty afterwards
+void release_subject(Subject& sub) {
+    for (NetState& ns : sub.net) {
+        (void)release_images(ns, 0, false);
+        if (ns.d_codes) (void)hipFree(ns.d_codes);
+        if (ns.d_src) (void)hipFree(ns.d_src);
+        for (int32_t* m : ns.d_map) if (m) (void)hipFree(m);
+        if (ns.d_vwide) (void)hipFree(ns.d_vwide);
+        ns = NetState();
+    }
+    if (sub.d_cut) (void)hipFree(sub.d_cut);
+    sub.d_cut = nullptr;
 }
 
 // The host copies of a net's tensors are brought up to date if the last weights came from the device
@@ -760,16 +775,10 @@ void pg_destroy(pg_handle* h) {
     pg_train_release(h);
     frames_cache_release(h);
     for (auto& pr : h->ev_aux) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
-    for (NetState& ns : h->net) {
-        (void)release_images(ns, 0, false);
-        if (ns.d_codes) (void)hipFree(ns.d_codes);
-        if (ns.d_src) (void)hipFree(ns.d_src);
-        for (int32_t* m : ns.d_map) if (m) (void)hipFree(m);
-        if (ns.d_vwide) (void)hipFree(ns.d_vwide);
-    }
+    release_subject(*h);
+    for (Subject& sub : h->bank.parked) release_subject(sub);
     for (auto& pr : h->ev_used) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
     for (auto& ev : h->ev_free) (void)hipEventDestroy(ev);
-    if (h->d_cut) (void)hipFree(h->d_cut);
     if (h->ws) (void)hipFree(h->ws);
     delete h;
 }
@@ -881,6 +890,7 @@ int pg_load_weights_device(pg_handle* h, void* stream, int which, const float* c
         case G_F32: pg_launch_gather32(ns.d_map[r.map], ns.d_src, reinterpret_cast<float*>(im.d), (long long)(im.bytes / 4), stream); break;
         case G_YCODE: pg_launch_ycode(ns.d_src + lay.off[20], vcols, ns.d_codes, ns.n_codes, reinterpret_cast<float*>(im.d), stream); break;
         }
+        ++ns.builds;
     }
     PG_HIP(h, hipGetLastError());
     // everything else: dropped (hipFree waits for the device: only forms the run has used beside the fast paths pay it)
@@ -922,6 +932,56 @@ int pg_set_framecodes(pg_handle* h, int which, const float* codes, int n_codes) 
     PG_HIP(h, hipMalloc(reinterpret_cast<void**>(&ns.d_codes), ns.codes_host.size() * sizeof(float)));
     PG_HIP(h, hipMemcpy(ns.d_codes, ns.codes_host.data(), ns.codes_host.size() * sizeof(float), hipMemcpyHostToDevice));
     PG_FORWARD(h, pg_set_framecodes(hh, which, codes, n_codes));
+    return PG_OK;
+}
+
+// ---- the subject bank (pg_bank.h) ---------------------------------------------------------------------------------
+int pg_subject_count(const pg_handle* h) { return h ? bank_count(h->bank) : 0; }
+
+int pg_set_subject_count(pg_handle* h, int n) {
+    if (!h) return pg_fail(nullptr, PG_EINVAL, "pg_set_subject_count: null handle");
+    if (n < 1 || n > PG_MAX_SUBJECTS) return pg_fail(h, PG_EINVAL, "pg_set_subject_count: 1..%d subjects, got %d", PG_MAX_SUBJECTS, n);
+    if (h->tape_out) return pg_fail(h, PG_EINVAL, "pg_set_subject_count: a training tape is outstanding (run its backward first)");
+    if (n <= h->bank.active)
+        return pg_fail(h, PG_EINVAL, "pg_set_subject_count: subject %d is selected and would be dropped (select one below %d first)", h->bank.active, n);
+    const int have = bank_count(h->bank);
+    if (n != have) {
+        PG_HIP(h, hipSetDevice(h->device));
+        if (n < have) PG_HIP(h, hipDeviceSynchronize());       // (launches in flight may still read the dropped subjects' images)
+        auto make = [&](Subject& sub) -> int {
+            for (float& c : sub.cut) c = h->cfg.cutoff_dist;
+            return hipMalloc(reinterpret_cast<void**>(&sub.d_cut), sizeof sub.cut) == hipSuccess ? PG_OK : PG_ENOMEM;
+        };
+        if (const int rc = bank_resize(*h, h->bank, n, make, release_subject)) return pg_fail(h, rc, "pg_set_subject_count: device allocation failed");
+    }
+    PG_FORWARD(h, pg_set_subject_count(hh, n));
+    return PG_OK;
+}
+
+int pg_select_subject(pg_handle* h, int s) {
+    if (!h) return pg_fail(nullptr, PG_EINVAL, "pg_select_subject: null handle");
+    if (s < 0 || s >= bank_count(h->bank)) return pg_fail(h, PG_EINVAL, "pg_select_subject: subject %d of %d", s, bank_count(h->bank));
+    if (h->tape_out) return pg_fail(h, PG_EINVAL, "pg_select_subject: a training tape is outstanding (run its backward first; training a bank is not built)");
+    bank_select(*h, h->bank, s);
+    PG_FORWARD(h, pg_select_subject(hh, s));
+    return PG_OK;
+}
+
+int pg_subject_info(pg_handle* h, int s, int32_t* loaded_nets, int64_t* image_bytes, int64_t* image_builds) {
+    if (!h) return pg_fail(nullptr, PG_EINVAL, "pg_subject_info: null handle");
+    if (s < 0 || s >= bank_count(h->bank)) return pg_fail(h, PG_EINVAL, "pg_subject_info: subject %d of %d", s, bank_count(h->bank));
+    const Subject& sub = s == h->bank.active ? static_cast<const Subject&>(*h) : h->bank.parked[s];
+    int32_t loaded = 0;
+    int64_t bytes = 0, builds = 0;
+    for (int w = 0; w < 2; ++w) {
+        const NetState& ns = sub.net[w];
+        if (ns.loaded) loaded |= 1 << w;
+        for (const NetState::Slot& im : ns.img) if (im.d) bytes += (int64_t)im.bytes;
+        builds += ns.builds;
+    }
+    if (loaded_nets) *loaded_nets = loaded;
+    if (image_bytes) *image_bytes = bytes;
+    if (image_builds) *image_builds = builds;
     return PG_OK;
 }
 
@@ -1853,10 +1913,25 @@ int pg_render_frames(pg_handle* h, int n_frames, int H, int W, const float* c2ws
                      float near, float far, const float* skts, const float* cyls, const float* cams, int n_samples,
                      int n_importance, int flags, const float* bg, float base_bg, float* rgbs, float* disps, float* accs,
                      uint8_t* rgb8) {
+    return pg_render_frames_subjects(h, n_frames, H, W, c2ws, intrinsics, boxes, near, far, skts, cyls, cams, n_samples, n_importance,
+                                     flags, bg, base_bg, rgbs, disps, accs, rgb8, nullptr);
+}
+
+int pg_render_frames_subjects(pg_handle* h, int n_frames, int H, int W, const float* c2ws, const float* intrinsics, const int* boxes,
+                              float near, float far, const float* skts, const float* cyls, const float* cams, int n_samples,
+                              int n_importance, int flags, const float* bg, float base_bg, float* rgbs, float* disps, float* accs,
+                              uint8_t* rgb8, const int32_t* subjects) {
     if (!h) return pg_fail(nullptr, PG_EINVAL, "null handle");
     if (n_frames < 0 || H <= 0 || W <= 0 || !c2ws || !intrinsics || !boxes || !skts || !cyls || (!rgbs && !rgb8))
         return pg_fail(h, PG_EINVAL, "pg_render_frames: null/negative argument");
     if (n_frames == 0) return PG_OK;
+    if (subjects) {
+        if (h->tape_out) return pg_fail(h, PG_EINVAL, "pg_render_frames_subjects: a training tape is outstanding (run its backward first)");
+        for (int f = 0; f < n_frames; ++f)
+            if (subjects[f] < 0 || subjects[f] >= bank_count(h->bank))
+                return pg_fail(h, PG_EINVAL, "pg_render_frames_subjects: frame %d names subject %d of %d", f, subjects[f], bank_count(h->bank));
+    }
+    const int active0 = h->bank.active;         // (every device's: pg_select_subject reaches them all)
     // Worker 0 runs on the primary handle's own stream over the primary's workspaces: everything the caller
     // queued on ITS stream (pg_render_rays / pg_render_frame are asynchronous and use the same buffers) must
     // have finished first.  The call is synchronous anyway.
@@ -1927,6 +2002,8 @@ int pg_render_frames(pg_handle* h, int n_frames, int H, int W, const float* c2ws
             const FrameTask& tk = tasks[t];
             if (tk.worker != k) continue;
             const int f = tk.frame;
+            // this device's own selection (each worker thread touches its own handle only): a pointer swap between two enqueues
+            if (subjects) bank_select(*hh, hh->bank, subjects[f]);
             if (whole(tk)) {
                 w.rc = frame_render_range(hh, st, geo[f], tk.r0, tk.r1, d_skts + (size_t)f * 384, d_cyls + (size_t)f * 5, n_samples, n_importance, flags, &maps_of[t]);
                 if (w.rc) return;
@@ -1988,6 +2065,8 @@ int pg_render_frames(pg_handle* h, int n_frames, int H, int W, const float* c2ws
     for (const Worker& w : ws) ok = ok && w.rc == PG_OK;
     if (ok && split) run(phase_b);
     run(finish);
+    if (subjects)
+        for (pg_handle* w : wk) bank_select(*w, w->bank, active0);
     int rc = PG_OK;
     for (Worker& w : ws) {
         if (w.rc != PG_OK) {        // nothing of a failed call may still be in flight when the caller's arrays go away

@@ -7,57 +7,18 @@
 #include <vector>
 
 #include "../../include/posegen_hip.h"
+#include "pg_bank.h"
 #include "pg_layout.h"
 
-// The packed weight images of one net.  pg_api.hip packs and uploads one on first use (ensure_image) and says which of them a
-// form of the fused kernel reads (FORMS).  The first four kinds exist per kernel arithmetic: id = kind + PG_PREC_*.
-enum Image : int {
-    IMG_NONE = -1,
-    IMG_DIRECT = 0,                                 // stream of the direct-view kernels: pg_eval16.hip (bf16 / fp16, shape A), pg_eval32.hip (the others, k-major shape B)
-    IMG_REC16 = IMG_DIRECT + PG_PREC_COUNT,         // 16x16x32 kernel with per-ray records (pg_eval16r.hip): stream
-    IMG_ONCHIP16 = IMG_REC16 + PG_PREC_COUNT,       // ... its on-chip variant (no per-ray records): stream
-    IMG_VY16 = IMG_ONCHIP16 + PG_PREC_COUNT,        // Y-stage weights of the per-ray record kernel (pg_rayrec.hip)
-    IMG_PER_PREC_END = IMG_VY16 + PG_PREC_COUNT,
-    IMG_COMP_DIRECT = IMG_PER_PREC_END,             // compensated-fp16 kernel (pg_evalc.hip), direct view layer: stream (shape C)
-    IMG_COMP_REC,                                   // ... record variant (REC): stream,
-    IMG_VYC,                                        // ... and the fp32 Y-stage weights of its record kernel
-    IMG_COMP_ONCHIP,                                // ... on-chip form of the record variant (OC): stream
-    IMG_C2,                                         // compensated-fp16 kernel with the out tiles over the waves (pg_evalc2.hip): weights (pg_program.h T)
-    IMG_YCODE,                                      // on-chip 16x16x32 variant with frame codes: Yc[n_codes + 1][128] = W_view[:, 904:920] codes[c]
-    IMG_BIAS16,                                     // 16-row bias table (the 16x16x32 kernel, pg_evalc2.hip)
-    IMG_BIAS,                                       // 32-row bias table (every other kernel)
-    IMG_COUNT
-};
-enum SrcMap : int { MAP_NONE = -1, MAP_ONCHIP16 = 0 /* one map for bf16 and fp16 */, MAP_C2, MAP_BIAS16, MAP_COUNT };
-
-struct NetState {
-    bool loaded = false;
-    std::vector<std::vector<float>> host;      // 24 tensors, reference order (see header)
-    std::vector<float> codes_host;             // [n_codes+1,16]
-    mutable std::vector<float> fold_w, fold_b; // W_view[:, :256] W_feature and its bias (NetTensors::fold), formed once per pg_load_weights
-    int n_codes = 0;
-    struct Slot { uint8_t* d = nullptr; size_t bytes = 0; } img[IMG_COUNT];
-    float* d_codes = nullptr;
-    // pg_load_weights_device: the net's tensors as one flat device vector (NetTensors::layout; + the folded view layer), the
-    // source maps of the images that are re-formed by a gather, and whether `host` lags the device copy
-    float* d_src = nullptr;
-    int32_t* d_map[MAP_COUNT] = {};
-    float* d_vwide = nullptr;      // multires_views = 0: the caller's view weight widened to the 4-band layout (pg_launch_widen_views)
-    bool host_stale = false;
-};
-
-
-struct pg_handle {
+// The handle is its active subject (pg_bank.h): net, cut, tau, emb_set and d_cut below are that model's; the other subjects of the
+// bank wait in `bank` and are swapped in by pg_select_subject.
+struct pg_handle : Subject {
     pg_config cfg;
     int device = 0;
     int n_cu = 256;
     int clock_khz = 0;
     char err[512] = "";
-    NetState net[2];
-    float cut[48];
-    float tau[2] = {20.f, 20.f};
-    bool emb_set[2] = {false, false};
-    float* d_cut = nullptr;
+    Bank bank;                       // pg_set_subject_count / pg_select_subject
     uint8_t* ws = nullptr;
     size_t ws_bytes = 0;
     uint8_t* fws = nullptr;          // frame front/back end: ray_batch, cams, rgb/disp/acc maps of the box
@@ -87,6 +48,7 @@ struct pg_handle {
     double aux_ms = 0.0;
     int64_t prof_points = 0;
     void* train = nullptr;           // the training tape (pg_train.hip): activations of the last pg_train_forward
+    bool tape_out = false;           // a pg_train_forward whose backward has not run yet: the bank stays as it is until then
     // pg_render_frames: per-device buffers kept between calls (frames of H x W pixels, background, pinned staging)
     struct FramesCache {
         size_t hw = 0;               // pixels the frame buffers were sized for

@@ -2028,6 +2028,7 @@ void pg_train_release(pg_handle* h) {
     if (t->pbuf) (void)hipFree(t->pbuf);
     delete t;
     h->train = nullptr;
+    h->tape_out = false;
 }
 
 int pg_train_forward(pg_handle* h, void* stream, int64_t n, const float* ray_batch, const float* skts, int64_t pose_stride,
@@ -2059,7 +2060,9 @@ int pg_train_forward(pg_handle* h, void* stream, int64_t n, const float* ray_bat
     Tape& t = *tape_of(h);
     PG_TRY(tape_begin(a, t));
     // one net, S + N rows per ray on one tape pass (`fine` is not read: network_fine is network), or two
-    return single ? forward_single(a, t, *coarse) : forward_two_nets(a, t, *coarse, fine);
+    const int rc = single ? forward_single(a, t, *coarse) : forward_two_nets(a, t, *coarse, fine);
+    h->tape_out = rc == PG_OK;      // the tape reads this subject's embedder state until its backward: the bank stays put (pg_select_subject)
+    return rc;
 }
 
 // the backward of both entries; d_skts null: no pose gradient (the kernels of pg_train_backward, nothing else)
@@ -2134,6 +2137,7 @@ static int train_backward(pg_handle* h, void* stream, int64_t tape_id, const flo
         hipLaunchKernelGGL(reduce_parts_kernel, dim3((unsigned)((J * 16 + 255) / 256)), dim3(256), 0, s, per_ray, (int)t.n, 1, J * 16, d_skts, (long long)(J * 16));
         PG_LAUNCH_CHECK(h, "pose gradient reduction");
     }
+    h->tape_out = false;
     return PG_OK;
 }
 

@@ -21,7 +21,7 @@ from typing import List, NamedTuple, Sequence
 
 import torch
 
-from .render import _pick, emit_frame, frame_background, frame_setup, frame_stacks, frames_to_host
+from .render import _pick, emit_frame, frame_background, frame_setup, frame_stacks, frame_subjects_of, frames_to_host
 
 
 class Task(NamedTuple):
@@ -121,7 +121,7 @@ def _world(group):
 @torch.no_grad()
 def render_frames_distributed(render_poses, hwf, chunk, render_kwargs, group=None, centers=None, kp=None, skts=None,
                               cyls=None, bg_imgs=None, bg_indices=None, cams=None, render_factor=0, white_bkgd=False,
-                              ext_scale=0.00035, frame_sink=None, stats=None):
+                              ext_scale=0.00035, frame_sink=None, stats=None, subject_idxs=None):
     """The frames of `render_path` rendered by all ranks of the group and assembled on EVERY rank, left on
     the device: (rgbs [F,H,W,3], disps [F,H,W,1], accs [F,H,W,1], valid_idxs, bboxes).
 
@@ -135,6 +135,9 @@ def render_frames_distributed(render_poses, hwf, chunk, render_kwargs, group=Non
     caller reads them, poses and cylinders are uploaded once, and nothing between the first and the last launch
     waits for the device.  `frame_sink(i, rgb, disp, acc)`: called with each composed frame instead of stacking
     them (render_path_distributed starts the device-to-host copy there; the three stacks are then None).
+    `subject_idxs`: one subject of the caster's bank per frame ([F], [n_pose] by i % n_pose, or a scalar): every task of the
+    plan carries its frame's subject to the rank that renders it (every rank holds the whole bank), so the runs of a cut
+    frame keep the frame's subject.
     `stats` (dict): receives `host_pre_launch_ms` (call entry -> first render launch: the part no GPU overlaps)
     and `host_ms` (whole call, host side)."""
     import time
@@ -145,6 +148,7 @@ def render_frames_distributed(render_poses, hwf, chunk, render_kwargs, group=Non
     r, dev, cyls, bboxes, meta, valid_idxs = su.r, su.dev, su.cyls, su.bboxes, su.meta, su.valid_idxs
     n_box = valid_idxs.counts()
     F = len(meta)
+    subj = frame_subjects_of(r, subject_idxs, F)     # (checked before anything is launched)
     tasks = plan_tasks(n_box, world, int(chunk))
     per_rank = [sum(t.r1 - t.r0 for t in tasks if t.worker == k) for k in range(world)]
     L = max(max(per_rank), 1)                       # rays per rank in the gathered buffer (padded to the largest share)
@@ -162,10 +166,13 @@ def render_frames_distributed(render_poses, hwf, chunk, render_kwargs, group=Non
     local = torch.zeros(5 * L, device=dev)
     off = 0
     t_first = None
+    prev = r.selected_subject if subj is not None else None
     for t in tasks:
         if t.worker != rank or t.r1 == t.r0:
             continue
         i = t.frame
+        if subj is not None:
+            r.select_subject(subj[i])
         h, w, f, c2w_np, center = meta[i]
         n = t.r1 - t.r0
         dst = local[5 * off:5 * (off + n)]
@@ -178,6 +185,8 @@ def render_frames_distributed(render_poses, hwf, chunk, render_kwargs, group=Non
         if piece.data_ptr() != dst.data_ptr():       # (a renderer that does not write in place)
             dst.copy_(piece.reshape(-1))
         off += n
+    if prev is not None:
+        r.select_subject(prev)
     if t_first is None:
         t_first = time.perf_counter()
     if dist is not None:                            # also at world size 1: the collective is the path being run
@@ -217,7 +226,8 @@ def render_path_distributed(render_poses, hwf, chunk, render_kwargs, group=None,
     render.render_path; in a process without a process group it is the single-device render.  The composed
     frames go to the host through page-locked buffers on a copy stream while the next ones are composed
     (render.FrameDownloader), like the single-device render_path."""
-    keep = ("centers", "kp", "skts", "cyls", "bg_imgs", "bg_indices", "cams", "render_factor", "white_bkgd", "ext_scale")
+    keep = ("centers", "kp", "skts", "cyls", "bg_imgs", "bg_indices", "cams", "render_factor", "white_bkgd", "ext_scale",
+            "subject_idxs")
     args = {k: v for k, v in kw.items() if k in keep}
     driver = lambda sink: render_frames_distributed(render_poses, hwf, chunk, render_kwargs, group=group, frame_sink=sink, **args)
     return frames_to_host(driver, render_kwargs, hwf, len(render_poses), kw.get("render_factor", 0), kw.get("ret_acc", True))

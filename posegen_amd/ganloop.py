@@ -53,24 +53,34 @@ def resize_antialiased(img: torch.Tensor, size: Tuple[int, int]) -> torch.Tensor
 def render_for_regressor(caster, bones: torch.Tensor, rest_pose, c2w, H: int, W: int, focal: float,
                          ext_scale: float = 0.001, crop: Tuple[int, int] = (100, 412), out_res: int = 224,
                          white_bkgd: bool = True, chunk: int = 4096, n_samples: Optional[int] = None,
-                         n_importance: Optional[int] = None, return_frames: bool = False):
+                         n_importance: Optional[int] = None, return_frames: bool = False, subject_idxs=None):
     """bones [F,24,3] axis-angle on the device -> regressor input [F,3,out_res,out_res] on the device
     (+ the uint8 frames [F,H,W,3] if `return_frames`).  One camera `c2w` [4,4] for all frames, like the
-    fixed extrinsic of the loop (run_gan.py:2023-2028)."""
+    fixed extrinsic of the loop (run_gan.py:2023-2028).  `subject_idxs`: one subject of the caster's bank per pose
+    ([F], or fewer indexed i % n, or a scalar): several A-NeRF characters in one call."""
+    from .render import frame_subjects_of
     r = caster.renderer
     dev = r.device
+    subj = frame_subjects_of(r, subject_idxs, bones.shape[0])       # (checked before anything is launched)
     kps, skts = r.pose_kinematics(bones, rest_pose)
     cyls, boxes = r.pose_boxes(kps, c2w, H, W, focal, ext_scale)
     boxes_h = boxes.cpu().numpy()                           # 16 B per frame: the only host round trip
     r.set_chunk(int(chunk))
     c2w_np = np.asarray(torch.as_tensor(c2w).detach().cpu(), dtype=np.float32)
     frames = torch.empty(bones.shape[0], H, W, 3, device=dev, dtype=torch.uint8)
-    for i in range(bones.shape[0]):
-        b = boxes_h[i]
-        _, _, _, rgb8 = r.render_frame(H, W, focal, c2w_np, ((int(b[0]), int(b[1])), (int(b[2]), int(b[3]))), skts[i:i + 1],
-                                       cyls[i:i + 1], n_samples=n_samples, n_importance=n_importance,
-                                       base_bg=1.0 if white_bkgd else 0.0, want_uint8=True)
-        frames[i] = rgb8
+    prev = r.selected_subject if subj is not None else None
+    try:
+        for i in range(bones.shape[0]):
+            b = boxes_h[i]
+            if subj is not None:
+                r.select_subject(subj[i])
+            _, _, _, rgb8 = r.render_frame(H, W, focal, c2w_np, ((int(b[0]), int(b[1])), (int(b[2]), int(b[3]))), skts[i:i + 1],
+                                           cyls[i:i + 1], n_samples=n_samples, n_importance=n_importance,
+                                           base_bg=1.0 if white_bkgd else 0.0, want_uint8=True)
+            frames[i] = rgb8
+    finally:
+        if prev is not None:
+            r.select_subject(prev)
     img = frames[:, crop[0]:crop[1], crop[0]:crop[1], :].permute(0, 3, 1, 2).float() / 255.0
     mean = torch.tensor(IMG_NORM_MEAN, device=dev).view(1, 3, 1, 1)
     std = torch.tensor(IMG_NORM_STD, device=dev).view(1, 3, 1, 1)

@@ -88,6 +88,61 @@ def _per_ray(x: torch.Tensor, n: int, device, dims: int, stride: int, what: str)
     return _dev_f32(x, device), stride
 
 
+MIXED_SUBJECTS = ("subject_idxs holds more than one subject in one ray call: per-ray mixing of subjects is not built (it would "
+                  "split the call's nanmean groups); render each subject's rays in a call of their own, or render whole frames "
+                  "with one subject per frame (render_path)")
+
+
+def _subject_values(x, what="subject_idxs") -> np.ndarray:
+    """int64 array of the subject indices in `x` (int, sequence, numpy array or tensor); anything that is not a whole number
+    is a ValueError."""
+    if isinstance(x, torch.Tensor):
+        x = x.detach().cpu().numpy()
+    if isinstance(x, (list, tuple)) and any(isinstance(v, (bool, np.bool_)) for v in x):
+        raise ValueError(f"{what} must hold integer subject indices, not booleans")
+    a = np.asarray(x)
+    if a.dtype == np.bool_ or not (np.issubdtype(a.dtype, np.integer) or np.issubdtype(a.dtype, np.floating)):
+        raise ValueError(f"{what} must hold integer subject indices, not {a.dtype}")
+    if np.issubdtype(a.dtype, np.floating):
+        if not np.all(np.isfinite(a)) or np.any(a != np.floor(a)):
+            raise ValueError(f"{what} must hold integer subject indices, got non-integer values")
+    return a.astype(np.int64).reshape(-1)
+
+
+def _check_subject_range(a: np.ndarray, n_subjects: int, what="subject_idxs"):
+    if a.size and (a.min() < 0 or a.max() >= n_subjects):
+        bad = int(a.min()) if a.min() < 0 else int(a.max())
+        raise ValueError(f"{what}: subject {bad} is outside [0, {n_subjects}) (the caster holds {n_subjects} subject"
+                         f"{'s' if n_subjects != 1 else ''})")
+
+
+def call_subject(subject_idxs, n_subjects: int, what="subject_idxs") -> Optional[int]:
+    """The ONE subject of a ray-level call: None (the selected subject), an int, or an array / tensor whose entries are all
+    equal -- what the reference's per-ray expansion of a frame's subject produces.  Mixed values are refused (MIXED_SUBJECTS),
+    values outside [0, n_subjects) are a ValueError; both before anything is launched."""
+    if subject_idxs is None:
+        return None
+    a = _subject_values(subject_idxs, what)
+    if a.size == 0:
+        return None
+    if np.any(a != a[0]):
+        raise NotImplementedError(MIXED_SUBJECTS)
+    _check_subject_range(a[:1], n_subjects, what)
+    return int(a[0])
+
+
+def frame_subjects(subject_idxs, n_frames: int, n_subjects: int, what="subject_idxs") -> Optional[list]:
+    """One subject per frame for the frame drivers: None, a scalar, [F], or [n_pose] indexed i % n_pose like every other
+    per-pose argument.  Values outside [0, n_subjects) are a ValueError before anything is launched."""
+    if subject_idxs is None:
+        return None
+    a = _subject_values(subject_idxs, what)
+    if a.size == 0:
+        raise ValueError(f"{what} is empty")
+    _check_subject_range(a, n_subjects, what)
+    return [int(a[i % a.size]) for i in range(n_frames)]
+
+
 class RayCall(NamedTuple):
     """What the ABI needs for one ray-level call; the tensors live as long as this does."""
     rb: torch.Tensor                    # [n,11] ray batch (zero-padded)
@@ -222,8 +277,10 @@ class HipRenderer:
         rc = self.lib.pg_create(C.byref(pc), len(dev_ids), ids, C.byref(h))
         _ffi.check(self.lib, None, rc)
         self.handle = h
-        self._state: Dict[str, dict] = {}
-        self._state_lazy: Dict[str, object] = {}      # state dicts to fetch from their owner on demand (load_network_device)
+        # host-side bookkeeping PER SUBJECT: the state dicts kept for checkpoints, and those to fetch from their owner on demand
+        # (load_network_device).  `_state` / `_state_lazy` are the selected subject's.
+        self._subjects = [{"state": {}, "lazy": {}}]
+        self._subject = 0
         self._chunk = cfg.chunk
         self._wave_counts = None
 
@@ -241,6 +298,61 @@ class HipRenderer:
 
     def _check(self, rc):
         _ffi.check(self.lib, self.handle, rc)
+
+    # -- the subject bank (pg_set_subject_count / pg_select_subject) -----------------
+    @property
+    def _state(self) -> Dict[str, dict]:
+        return self._subjects[self._subject]["state"]
+
+    @property
+    def _state_lazy(self) -> Dict[str, object]:
+        return self._subjects[self._subject]["lazy"]
+
+    @property
+    def n_subjects(self) -> int:
+        return len(self._subjects)
+
+    @property
+    def selected_subject(self) -> int:
+        return self._subject
+
+    def set_subject_count(self, n: int):
+        """n >= 1 complete models behind this handle.  Growing keeps the loaded subjects, shrinking frees the dropped ones
+        (the selected subject must be one that stays)."""
+        n = int(n)
+        if n != len(self._subjects):
+            self._check(self.lib.pg_set_subject_count(self.handle, n))
+            del self._subjects[n:]
+            while len(self._subjects) < n:
+                self._subjects.append({"state": {}, "lazy": {}})
+
+    def select_subject(self, s: int):
+        """Every later call -- loads, embedder state, renders, density queries, state_dict -- acts on subject s.  A swap of
+        host pointers in the library: nothing is packed, copied or waited for."""
+        s = int(s)
+        if not 0 <= s < len(self._subjects):
+            raise ValueError(f"subject {s} is outside [0, {len(self._subjects)})")
+        if s != self._subject:
+            self._check(self.lib.pg_select_subject(self.handle, s))
+            self._subject = s
+
+    @contextmanager
+    def subject(self, s: Optional[int]):
+        """`with r.subject(s):` selects subject s and puts the previous selection back (None: leaves it alone)."""
+        prev = self._subject
+        if s is not None:
+            self.select_subject(s)
+        try:
+            yield self
+        finally:
+            if s is not None:
+                self.select_subject(prev)
+
+    def subject_info(self, s: Optional[int] = None):
+        """pg_subject_info: which nets of subject s are loaded, the device bytes of its packed images, images built so far."""
+        ln, by, bu = C.c_int32(), C.c_int64(), C.c_int64()
+        self._check(self.lib.pg_subject_info(self.handle, self._subject if s is None else int(s), C.byref(ln), C.byref(by), C.byref(bu)))
+        return {"loaded_nets": [w for w in (0, 1) if ln.value >> w & 1], "image_bytes": by.value, "image_builds": bu.value}
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -488,12 +600,15 @@ class HipRenderer:
     def render_frames(self, H: int, W: int, focals, c2ws, boxes, skts, cyls, centers=None, cams=None,
                       near: float = 0., far: float = 1., n_samples: Optional[int] = None,
                       n_importance: Optional[int] = None, lindisp: bool = False, bg=None, base_bg: float = 0.,
-                      want_uint8: bool = False):
+                      want_uint8: bool = False, subjects=None):
         """Frames on ALL devices of the handle (pg_render_frames), host in / host out: numpy arrays
         rgbs [F,H,W,3], disps [F,H,W,1], accs [F,H,W,1] (+ rgb8 uint8 [F,H,W,3]).  `boxes` = list of
-        ((tl_x, tl_y), (br_x, br_y)); skts [F,24,4,4], cyls [F,5] (one pose per frame)."""
+        ((tl_x, tl_y), (br_x, br_y)); skts [F,24,4,4], cyls [F,5] (one pose per frame); `subjects`: one subject per frame
+        (pg_render_frames_subjects; None: the selected subject for all)."""
         S, N = _resolve_sn(self.cfg, n_samples, n_importance)
         F = len(boxes)
+        subj = frame_subjects(subjects, F, self.n_subjects, "subjects")
+        sj = None if subj is None else np.ascontiguousarray(np.asarray(subj, dtype=np.int32))
         c2w_h = np.ascontiguousarray(np.stack([np.asarray(torch.as_tensor(c).detach().cpu(), dtype=np.float32)[:3, :4]
                                                for c in c2ws]))
         intr = np.zeros((F, 4), dtype=np.float32)
@@ -518,9 +633,12 @@ class HipRenderer:
         rgbs, disps, accs = new(3, torch.float32), new(1, torch.float32), new(1, torch.float32)
         rgb8 = new(3, torch.uint8) if want_uint8 else None
         hp = lambda a: None if a is None else C.c_void_p(a.ctypes.data)
-        self._check(self.lib.pg_render_frames(
-            self.handle, F, int(H), int(W), hp(c2w_h), hp(intr), hp(bx), float(near), float(far), hp(sk), hp(cy), hp(cm),
-            S, N, _ffi.PG_FLAG_LINDISP if lindisp else 0, hp(bgh), float(base_bg), hp(rgbs), hp(disps), hp(accs), hp(rgb8)))
+        args = (self.handle, F, int(H), int(W), hp(c2w_h), hp(intr), hp(bx), float(near), float(far), hp(sk), hp(cy), hp(cm),
+                S, N, _ffi.PG_FLAG_LINDISP if lindisp else 0, hp(bgh), float(base_bg), hp(rgbs), hp(disps), hp(accs), hp(rgb8))
+        if sj is None:
+            self._check(self.lib.pg_render_frames(*args))
+        else:
+            self._check(self.lib.pg_render_frames_subjects(*args, hp(sj)))
         return (rgbs, disps, accs, rgb8) if want_uint8 else (rgbs, disps, accs)
 
     def query_density(self, pts: torch.Tensor, skts: torch.Tensor, which: Optional[int] = None) -> torch.Tensor:
@@ -675,8 +793,9 @@ def refuse_reference_kwargs(who, check_preproc, skts, cyls, kw, own_fine=None):
     if fwd_type:
         raise NotImplementedError(f"fwd_type={fwd_type!r} is not on the HIP path of forward (HipRayCaster's call dispatches "
                                   "'density' and 'mesh')")
-    if kw.pop("subject_idxs", None) is not None:
-        raise NotImplementedError("subject_idxs (multi-subject nets) are not supported")
+    if kw.pop("subject_idxs", None) is not None:       # (HipRayCaster resolves its own before it comes here: call_subject)
+        raise NotImplementedError(f"{who}: subject_idxs in training mode is not built (training a subject bank is out of scope; "
+                                  "eval-mode calls render the subject through the HipRayCaster)")
     if skts is None or cyls is None:
         raise ValueError("skts and cyls are required (A-NeRF bone-relative rendering)")
     nerf_type = kw.pop("nerf_type", "nerf")
@@ -724,22 +843,69 @@ class HipRayCaster:
         rc.renderer.set_embedder(1, tau_d)
         return rc
 
+    @classmethod
+    def from_subjects(cls, cfg, models, device="cuda:0", precision=PREC_BF16, devices=None):
+        """A bank of len(models) subjects of one architecture: `models` = [(w_coarse, w_fine, tau_v, tau_d), ...], each as
+        from_weights takes them.  Subject 0 is selected."""
+        models = list(models)
+        if not models:
+            raise ValueError("from_subjects: at least one (w_coarse, w_fine, tau_v, tau_d)")
+        if cfg.single_net:
+            for wc, wf, _, _ in models:
+                check_single_net_states(wc, wf)
+        rc = cls(cfg, device, precision, devices=devices)
+        r = rc.renderer
+        r.set_subject_count(len(models))
+        for s, (wc, wf, tau_v, tau_d) in enumerate(models):
+            with r.subject(s):
+                r.load_network(0, wc)
+                if wf is not None and not cfg.single_net:
+                    r.load_network(1, wf)
+                r.set_embedder(0, tau_v)
+                r.set_embedder(1, tau_d)
+        return rc
+
+    # ---- the subject bank -------------------------------------------------------------
+    @property
+    def n_subjects(self) -> int:
+        return self.renderer.n_subjects
+
+    def set_subject_count(self, n: int):
+        self.renderer.set_subject_count(n)
+
+    def select_subject(self, s: int):
+        self.renderer.select_subject(s)
+
+    def subject(self, s):
+        """context manager: subject s selected inside, the previous selection restored afterwards"""
+        return self.renderer.subject(s)
+
+    def load_subject(self, s: int, ckpt, strict=True):
+        """load_state_dict (the reference's checkpoint layout) applied to subject s; the selection is left as it was"""
+        with self.renderer.subject(int(s)):
+            self.load_state_dict(ckpt, strict=strict)
+
+    def _call_subject(self, subject_idxs) -> Optional[int]:
+        return call_subject(subject_idxs, self.renderer.n_subjects)
+
     # ---- density queries (core/raycasters.py:579-646) ----------------------------------------
     def render_pts_density(self, pts, kps, skts, bones=None, render_kwargs=None, subject_idxs=None,
                            netchunk=1024 * 64, network=None, color=False, v=None):
         """Raw density [..., 1] at points `pts` [n,1,3] (or [n,3]) for one pose; fine net unless
         `network` is 0/1.  `kps`, `bones`, `netchunk` are accepted for call compatibility."""
-        if color or v is not None or subject_idxs is not None:
-            raise NotImplementedError("render_pts_density: color / precomputed v / subject_idxs are not supported")
+        if color or v is not None:
+            raise NotImplementedError("render_pts_density: color / precomputed v are not supported")
         which = network if network in (0, 1) else None
-        return self.renderer.query_density(torch.as_tensor(pts), skts, which)
+        with self.renderer.subject(self._call_subject(subject_idxs)):
+            return self.renderer.query_density(torch.as_tensor(pts), skts, which)
 
     def render_mesh_density(self, kps, skts, bones=None, subject_idxs=None, radius=1.0, res=64,
                             render_kwargs=None, netchunk=1024 * 64, v=None):
         """Raw density on the (res+1)^3 grid around the root joint, as the reference lays it out."""
-        if v is not None or subject_idxs is not None:
-            raise NotImplementedError("render_mesh_density: precomputed v / subject_idxs are not supported")
-        return self.renderer.mesh_density(kps, skts, radius=radius, res=res)
+        if v is not None:
+            raise NotImplementedError("render_mesh_density: precomputed v is not supported")
+        with self.renderer.subject(self._call_subject(subject_idxs)):
+            return self.renderer.mesh_density(kps, skts, radius=radius, res=res)
 
     # ---- nn.Module-like surface the reference touches -------------------------------
     @property
@@ -811,9 +977,10 @@ class HipRayCaster:
         pytest=True (the reference's deterministic test mode; it has no override for the position
         noise, which stays a torch draw), or from `draws` when the caller supplies them."""
         refuse_reference_kwargs("HipRayCaster", self._check_preproc_kwargs, skts, cyls,
-                                dict(unused, fwd_type=fwd_type, subject_idxs=subject_idxs, nerf_type=nerf_type,
+                                dict(unused, fwd_type=fwd_type, nerf_type=nerf_type,
                                      use_viewdirs=use_viewdirs, network_fine=network_fine, preproc_kwargs=preproc_kwargs))
-        with one_nanmean_group(self.renderer, ray_batch.shape[0], grouped=getattr(self, "_grouped_call", False)):
+        # one subject per ray call (an int, or the reference's per-ray expansion of it); checked before anything is launched
+        with self.renderer.subject(self._call_subject(subject_idxs)), one_nanmean_group(self.renderer, ray_batch.shape[0], grouped=getattr(self, "_grouped_call", False)):
             if draws is None and (perturb or raw_noise_std or ray_noise_std):
                 S, _ = _resolve_sn(self.cfg, N_samples, None)
                 draws = self.training_draws(int(ray_batch.shape[0]), S, int(N_importance or 0), perturb, raw_noise_std,
@@ -893,9 +1060,14 @@ def make_training_draws(n, S, N, perturb=0., raw_noise_std=0., ray_noise_std=0.,
 def create_raycaster(cfg: RenderConfig, ckpt=None, device="cuda:0", precision=PREC_BF16, devices=None):
     """Counterpart of `create_raycaster` (core/raycasters.py:17-184) for rendering:
     returns `render_kwargs_test` with the HIP caster under 'ray_caster'.  `devices` = the GPUs the
-    reference would hand to nn.DataParallel (raycasters.py:157)."""
+    reference would hand to nn.DataParallel (raycasters.py:157).  `ckpt`: one checkpoint, or a list of them: a bank with
+    one subject per checkpoint (render_path's subject_idxs picks per frame)."""
     caster = HipRayCaster(cfg, device, precision, devices=devices)
-    if ckpt is not None:
+    if isinstance(ckpt, (list, tuple)):
+        caster.set_subject_count(len(ckpt))
+        for s, c in enumerate(ckpt):
+            caster.load_subject(s, c)
+    elif ckpt is not None:
         caster.load_state_dict(ckpt)
     caster.eval()
     return {"ray_caster": caster, "perturb": False, "N_importance": cfg.n_importance,
@@ -920,9 +1092,10 @@ def find_checkpoint(basedir: str, expname: str, ft_path: Optional[str] = None, n
 _RAYCASTER_CACHE: Dict[tuple, dict] = {}
 
 
-def load_raycaster(ckpt_path: str, cfg: RenderConfig, device="cuda:0", precision=PREC_BF16, devices=None):
+def load_raycaster(ckpt_path, cfg: RenderConfig, device="cuda:0", precision=PREC_BF16, devices=None):
     """`create_raycaster` on an A-NeRF checkpoint file (`.tar`, the reference's five state dicts,
-    core/raycasters.py:752-766), memoised on (path, mtime, size, config, device, precision).
+    core/raycasters.py:752-766), memoised on (path, mtime, size, config, device, precision).  A list of paths gives ONE
+    memoised bank with a subject per file, in the list's order.
 
     The reference's `run_render` reloads and re-wraps the checkpoint on every call of the GAN
     loop (run_gan.py:135-165, 2290-2330); here a repeated call returns the caster whose packed
@@ -930,12 +1103,14 @@ def load_raycaster(ckpt_path: str, cfg: RenderConfig, device="cuda:0", precision
     import os
     if isinstance(precision, str):
         precision = PREC_BY_NAME[precision]
-    st = os.stat(ckpt_path)
-    key = (os.path.abspath(ckpt_path), st.st_mtime_ns, st.st_size, repr(cfg), str(device), int(precision),
-           None if devices is None else tuple(devices))
+    many = isinstance(ckpt_path, (list, tuple))
+    paths = [os.fspath(p) for p in ckpt_path] if many else [ckpt_path]
+    stamp = lambda p, st: (os.path.abspath(p), st.st_mtime_ns, st.st_size)
+    files = tuple(stamp(p, os.stat(p)) for p in paths)
+    key = (files if many else files[0]) + (repr(cfg), str(device), int(precision), None if devices is None else tuple(devices))
     kw = _RAYCASTER_CACHE.get(key)
     if kw is None:
-        ckpt = torch.load(ckpt_path, map_location="cpu", weights_only=False)
-        kw = create_raycaster(cfg, ckpt, device=device, precision=precision, devices=devices)
+        ckpts = [torch.load(p, map_location="cpu", weights_only=False) for p in paths]
+        kw = create_raycaster(cfg, ckpts if many else ckpts[0], device=device, precision=precision, devices=devices)
         _RAYCASTER_CACHE[key] = kw
     return dict(kw)

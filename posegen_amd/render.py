@@ -133,6 +133,13 @@ def frame_background(bg_imgs, bg_indices, i, h, w, white_bkgd, dev=None):
     return bg if dev is None else bg.to(dev)
 
 
+def frame_subjects_of(r, subject_idxs, n_frames):
+    """One subject per frame (None: the selected subject for all) for renderer `r`: a scalar, [F], or [n_pose] indexed
+    i % n_pose like every other per-pose argument; checked against the renderer's bank before anything is launched."""
+    from .raycaster import frame_subjects
+    return frame_subjects(subject_idxs, n_frames, getattr(r, "n_subjects", 1))
+
+
 def _finite_disp(disp):
     return torch.nan_to_num(disp, nan=0.0, posinf=float("inf"), neginf=float("-inf"))   # run_nerf.py:142-143
 
@@ -178,18 +185,22 @@ def frames_to_host(driver, render_kwargs, hwf, n_out, render_factor, ret_acc):
 @torch.no_grad()
 def render_frames_device(render_poses, hwf, chunk, render_kwargs, centers=None, kp=None, skts=None, cyls=None,
                          bg_imgs=None, bg_indices=None, cams=None, render_factor=0, white_bkgd=False,
-                         ext_scale=0.00035, frame_ids: Optional[list] = None, boxes=None, frame_sink=None):
+                         ext_scale=0.00035, frame_ids: Optional[list] = None, boxes=None, frame_sink=None,
+                         subject_idxs=None):
     """The frame loop of `render_path` with its results left on the device:
     (rgbs [f,H,W,3], disps [f,H,W,1], accs [f,H,W,1] device tensors, valid_idxs, bboxes).
     `frame_ids` restricts rendering to a subset of the frames (multi-GPU partition; an empty
     list returns empty [0,H,W,C] stacks); `boxes` = a kp_to_boxes result computed by the caller;
     `frame_sink(k, rgb, disp, acc)` is called with the k-th rendered frame's device tensors as soon as its kernels
-    are enqueued (render_path starts the device-to-host copy there) -- the stacks are then not built (None)."""
+    are enqueued (render_path starts the device-to-host copy there) -- the stacks are then not built (None).
+    `subject_idxs`: one subject of the caster's bank per frame ([F], [n_pose] by i % n_pose, or a scalar), selected before
+    that frame's launches; the caster's selection is the same before and after."""
     # Boxes, rays, rendering and the scatter into the background frame on the device (pg_pose_boxes,
     # pg_render_frame): no per-frame meshgrid, no ray copies.
     su = frame_setup(render_poses, hwf, render_kwargs, centers, kp, cyls, render_factor, ext_scale, boxes=boxes)
     r, dev, cyls = su.r, su.dev, su.cyls
     ids = list(range(len(render_poses))) if frame_ids is None else list(frame_ids)
+    subj = frame_subjects_of(r, subject_idxs, len(render_poses))
     frames = []
     kw = render_kwargs
     r.set_chunk(int(chunk))
@@ -201,15 +212,22 @@ def render_frames_device(render_poses, hwf, chunk, render_kwargs, centers=None, 
         cyls = torch.as_tensor(cyls).to(dev, dtype=torch.float32)
     if cams is not None:        # frame-code indices on the host once (a per-frame float() of a device tensor would block)
         cams = torch.as_tensor(cams).detach().float().cpu()
-    for k, i in enumerate(ids):
-        h, w, f, c2w_np, center = su.meta[i]
-        cam = _pick(cams, i)
-        rgb_img, disp_img, acc_img = r.render_frame(
-            h, w, f, c2w_np, su.bboxes[i], _pick(skts, i), _pick(cyls, i), center=center,
-            cam=None if cam is None else float(cam.reshape(-1)[0]),
-            n_samples=kw.get("N_samples"), n_importance=kw.get("N_importance"), lindisp=bool(kw.get("lindisp", False)),
-            bg=frame_background(bg_imgs, bg_indices, i, h, w, white_bkgd, dev), base_bg=1.0 if white_bkgd else 0.0)
-        emit_frame(frame_sink, frames, k, rgb_img, disp_img, acc_img)
+    prev = r.selected_subject if subj is not None else None
+    try:
+        for k, i in enumerate(ids):
+            h, w, f, c2w_np, center = su.meta[i]
+            cam = _pick(cams, i)
+            if subj is not None:
+                r.select_subject(subj[i])       # (a pointer swap: nothing waits between this frame's launches and the last one's)
+            rgb_img, disp_img, acc_img = r.render_frame(
+                h, w, f, c2w_np, su.bboxes[i], _pick(skts, i), _pick(cyls, i), center=center,
+                cam=None if cam is None else float(cam.reshape(-1)[0]),
+                n_samples=kw.get("N_samples"), n_importance=kw.get("N_importance"), lindisp=bool(kw.get("lindisp", False)),
+                bg=frame_background(bg_imgs, bg_indices, i, h, w, white_bkgd, dev), base_bg=1.0 if white_bkgd else 0.0)
+            emit_frame(frame_sink, frames, k, rgb_img, disp_img, acc_img)
+    finally:
+        if prev is not None:
+            r.select_subject(prev)
     return frame_stacks(frame_sink, frames, su) + (su.valid_idxs, su.bboxes)
 
 
@@ -223,15 +241,17 @@ def render_path(render_poses, hwf, chunk, render_kwargs, centers=None, kp=None, 
 
     `frame_ids` (extension) restricts rendering to a subset of frames (multi-GPU
     partition); the returned arrays then hold those frames in the given order.
+    `subject_idxs`: one subject of the caster's bank per frame -- [F], [n_pose] indexed i % n_pose, or a scalar; every frame
+    is rendered with the model it names (None: the selected subject).
     """
     r, _ = _caster_device(render_kwargs["ray_caster"])
     if getattr(r, "n_devices", 1) > 1 and frame_ids is None and (bg_imgs is None or white_bkgd or bg_indices is None):
         return _render_path_multi(render_poses, hwf, chunk, render_kwargs, centers, kp, skts, cyls, bg_imgs, cams,
-                                  render_factor, white_bkgd, ret_acc, ext_scale)
+                                  render_factor, white_bkgd, ret_acc, ext_scale, subject_idxs=subject_idxs)
     driver = lambda sink: render_frames_device(
         render_poses, hwf, chunk, render_kwargs, centers=centers, kp=kp, skts=skts, cyls=cyls, bg_imgs=bg_imgs,
         bg_indices=bg_indices, cams=cams, render_factor=render_factor, white_bkgd=white_bkgd, ext_scale=ext_scale,
-        frame_ids=frame_ids, frame_sink=sink)
+        frame_ids=frame_ids, frame_sink=sink, subject_idxs=subject_idxs)
     n_out = len(render_poses) if frame_ids is None else len(frame_ids)
     return frames_to_host(driver, render_kwargs, hwf, n_out, render_factor, ret_acc)
 
@@ -306,7 +326,7 @@ class FrameDownloader:
 
 
 def _render_path_multi(render_poses, hwf, chunk, render_kwargs, centers, kp, skts, cyls, bg_imgs, cams,
-                       render_factor, white_bkgd, ret_acc, ext_scale):
+                       render_factor, white_bkgd, ret_acc, ext_scale, subject_idxs=None):
     """render_path on a caster that owns several GPUs (HipRayCaster(devices=[...])): one pg_render_frames
     call, frames or ray chunks spread over the devices inside the library (no torch.distributed)."""
     su = frame_setup(render_poses, hwf, render_kwargs, centers, kp, cyls, render_factor, ext_scale,
@@ -322,6 +342,7 @@ def _render_path_multi(render_poses, hwf, chunk, render_kwargs, centers, kp, skt
     if cams is not None:
         ct = torch.as_tensor(cams).reshape(-1).float()
         cm = torch.stack([ct[i % ct.shape[0]] for i in range(F_)])
+    subj = frame_subjects_of(r, subject_idxs, F_)
     r.set_chunk(int(chunk))
     kw = render_kwargs
     rgbs, disps, accs = r.render_frames(H, W, [m[2] for m in meta], [m[3] for m in meta], su.bboxes, sk, cy,
@@ -329,5 +350,5 @@ def _render_path_multi(render_poses, hwf, chunk, render_kwargs, centers, kp, skt
                                         n_samples=kw.get("N_samples"), n_importance=kw.get("N_importance"),
                                         lindisp=bool(kw.get("lindisp", False)),
                                         bg=frame_background(bg_imgs, None, 0, H, W, white_bkgd),    # (one background: render_path)
-                                        base_bg=1.0 if white_bkgd else 0.0)
+                                        base_bg=1.0 if white_bkgd else 0.0, **({} if subj is None else {"subjects": subj}))
     return rgbs, disps, accs if ret_acc else [], su.valid_idxs, su.bboxes

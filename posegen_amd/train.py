@@ -185,6 +185,9 @@ class TrainableRayCaster(torch.nn.Module):
         if train_precision not in ("fp32", "bf16"):
             raise ValueError(f"train_precision must be 'fp32' or 'bf16', not {train_precision!r}")
         self._check_model(caster.cfg)
+        if getattr(caster, "n_subjects", 1) > 1:
+            raise NotImplementedError(f"{type(self).__name__}: training a subject bank is not built (the caster holds "
+                                      f"{caster.n_subjects} subjects; train each subject's model in a caster of its own)")
         self.caster = caster
         self.train_precision = train_precision
         self.opt_pose = bool(opt_pose)
@@ -300,10 +303,12 @@ class TrainableRayCaster(torch.nn.Module):
     def forward(self, ray_batch, N_samples=None, kp_batch=None, skts=None, cyls=None, bones=None, cams=None,
                 subject_idxs=None, lindisp=False, perturb=0., N_importance=0, raw_noise_std=0., ray_noise_std=0.,
                 pytest=False, draws: Optional[Dict[str, torch.Tensor]] = None, **unused):
-        # the reference's keywords the kernels do not honour are refused, in training and in eval mode alike
+        # the reference's keywords the kernels do not honour are refused, in training and in eval mode alike; subject_idxs in
+        # training mode only (an eval-mode call hands it to the caster, which checks it against its one subject)
+        training = self.training and torch.is_grad_enabled()
         refuse_reference_kwargs("TrainableRayCaster", self.caster._check_preproc_kwargs, skts, cyls,
-                                dict(unused, subject_idxs=subject_idxs), own_fine=self.network_fine)
-        if not (self.training and torch.is_grad_enabled()):
+                                dict(unused, subject_idxs=subject_idxs if training else None), own_fine=self.network_fine)
+        if not training:
             if self._stale:                              # a backward pass has run since the last packing: render what was trained
                 self.sync_inference_weights()
             return self.caster(ray_batch, N_samples=N_samples, kp_batch=kp_batch, skts=skts, cyls=cyls, bones=bones, cams=cams,
