@@ -438,6 +438,37 @@ int pg_stage_eval(pg_handle* h, void* stream, int which_net, int64_t n, int n_sa
 int pg_query_density(pg_handle* h, void* stream, int which_net, int64_t n_points, const float* pts,
                      const float* skts, float* raw);
 
+/* Mesh extraction (the reference's run_render.render_mesh): the density grid and marching cubes on the
+ * device.
+ *
+ * pg_grid_density: raw density (alpha_linear output, no activation) of net `which_net` for one pose on the (res+1)^3 grid
+ * root + (t[a], t[b], t[c]), t = linspace(-radius, radius, res+1) formed in double and rounded to float like numpy's, the
+ * sums in float like the reference's `grid + kps[0,0]`.  sigma [R,R,R] device, c fastest: the layout of
+ * RayCaster.render_mesh_density (core/raycasters.py:579-596) after its transpose.  root HOST [3], skts device [24,4,4].
+ * A grid row is a ray of res+1 samples, so the call runs the fused kernel forms of a render call; rows shorter than the
+ * form's minimum of samples per ray, or longer than 256, run as explicit points formed on the device (the forms of
+ * pg_query_density).  The grid goes in slabs of slab_rays rows (0: chosen so that a slab's raw output stays within
+ * 256 MiB), rounded down to a multiple of 256 / gcd(res+1, 256) rows (at least one such multiple) so that every slab starts
+ * on a pass boundary of the kernels: the values do not depend on the slab size.  Refusals as pg_query_density; res outside [1, 1023] or a radius that
+ * is not positive and finite is PG_EINVAL. */
+int pg_grid_density(pg_handle* h, void* stream, int which_net, int res, double radius, const float* root,
+                    const float* skts, int64_t slab_rays, float* sigma);
+
+/* Marching cubes on a device float grid [nx,ny,nz] (nz fastest, every dimension >= 2, at most 4e8 points); needs no loaded
+ * weights.  With f = max(grid, clamp) (clamp = 0: the reference's np.maximum(raw, 0); -INFINITY: the grid as it is), a point
+ * is inside when f > threshold.  One vertex per grid edge whose ends differ: on the edge from point i to i + 1 along axis a,
+ * coordinate i + (threshold - fa) / (fb - fa) on that axis (float), the integer indices on the other two -- index
+ * coordinates.  Vertices are ordered by the linear index of the edge's lower point, then by axis; triangles by cell, then by
+ * the case table's order (posegen_amd/mesh.py, compiled in); they index the vertices, which neighbouring cells share.
+ * Normals point away from the inside.  Two calls on the same grid give the same bytes.
+ * pg_mesh_count synchronises the stream, returns the two counts (0, 0 when nothing crosses: no error) and keeps its flags
+ * and scans in the handle; pg_mesh_emit writes vertices [nv,3] and triangles [nt,3] (device) from them and is PG_ESTATE
+ * unless shape, threshold, clamp and both counts are those of the last pg_mesh_count.  The grid must not change in between. */
+int pg_mesh_count(pg_handle* h, void* stream, const float* grid, int nx, int ny, int nz, float threshold, float clamp,
+                  int64_t* n_vertices, int64_t* n_triangles);
+int pg_mesh_emit(pg_handle* h, void* stream, const float* grid, int nx, int ny, int nz, float threshold, float clamp,
+                 float* vertices, int32_t* triangles, int64_t n_vertices, int64_t n_triangles);
+
 /* raw2outputs (nerf.py:150-205) and, if n_importance > 0, isample_from_lineseg
  * (ray_utils.py:157-201, 255-289): wave-per-ray prefix-product compositing.  The pdf follows the
  * handle: is_only weights 0.5 (max(w_l, w_k) + max(w_k, w_u)) + 0.01 with single_net. */

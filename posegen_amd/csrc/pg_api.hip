@@ -2,6 +2,7 @@
 // packing / upload, workspace, and the launch sequence of one render_rays call.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -37,6 +38,9 @@ int pg_launch_sample_coarse(const float* rays, const float* cyls, long long cyl_
 long long pg_sample_coarse_scratch(long long n, int chunk);
 int pg_launch_gather_noise(const float* src, long long n, int stride, int S, const int* order, float* dst, void* stream);
 int pg_launch_mfma_rate(int f16, int lds_fed, int blocks, int iters, float* sink, void* stream);
+int pg_launch_grid_rays(const float* root3, const float* t, int R, long long row0, long long rows, float* rays, float* z, void* stream);
+int pg_launch_grid_points(const float* root3, const float* t, int R, long long p0, long long n, float* pts, void* stream);
+int pg_launch_gather_sigma(const float* raw, long long n, float* sigma, void* stream);
 int pg_launch_composite_iso(const float* rays, const float* z, const float* raw, long long n, int S, float density_scale,
                             float rgb_eps, int density_act, float act_shift, float* rgb, float* disp, float* acc, float* alpha,
                             float* weights, int n_imp, float* z_fine, const float* noise, const float* u_rand, int* order,
@@ -773,6 +777,7 @@ void pg_destroy(pg_handle* h) {
     if (h->rec) (void)hipFree(h->rec);
     if (h->sc_part) (void)hipFree(h->sc_part);
     pg_train_release(h);
+    pg_mesh_release(h);
     frames_cache_release(h);
     for (auto& pr : h->ev_aux) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
     release_subject(*h);
@@ -1329,6 +1334,69 @@ int pg_query_density(pg_handle* h, void* stream, int which, int64_t n_points, co
     PG_HIP(h, hipMemsetAsync(h->ws, 0, 64, static_cast<hipStream_t>(stream)));
     return launch_eval(h, stream, which, 1, (int)n_points, reinterpret_cast<const float*>(h->ws), nullptr, skts, 0,
                        nullptr, raw, nullptr, 0, pts);
+}
+
+// The density grid of mesh extraction.  A grid row is a ray (pg_mesh.hip), so launch_eval picks the forms of a render call: the
+// 16x16x32 kernel on chip or with records and pg_evalc2.hip from their sample minimum up, with limb masks.  Rows shorter than the picked
+// form's minimum of samples per ray (or longer than the 256 samples the forms are measured and tested at) go as explicit points made on
+// the device: the direct forms, as pg_query_density runs them.
+int pg_grid_density(pg_handle* h, void* stream, int which, int res, double radius, const float* root, const float* skts,
+                    int64_t slab_rays, float* sigma) {
+    int rc = check_ready(h, which == 1);
+    if (rc) return rc;
+    if (which < 0 || which > 1) return pg_fail(h, PG_EINVAL, "pg_grid_density: which_net must be 0 or 1");
+    if (which == 1 && h->cfg.single_net) return pg_fail(h, PG_EINVAL, "pg_grid_density: a single_net handle has one net (which_net 0)");
+    if (!root || !skts || !sigma || slab_rays < 0) return pg_fail(h, PG_EINVAL, "pg_grid_density: null/negative argument");
+    if (res < 1 || res > 1023) return pg_fail(h, PG_EINVAL, "pg_grid_density: res must be in [1, 1023], got %d", res);
+    if (!(radius > 0.0) || !std::isfinite(radius)) return pg_fail(h, PG_EINVAL, "pg_grid_density: radius must be positive and finite");
+    PG_HIP(h, hipSetDevice(h->device));
+    const int R = res + 1;
+    const long long rows_all = (long long)R * R;
+    // t = np.linspace(-radius, radius, R).astype(float32): i * step + start in double, the last element the stop itself
+    h->grid_t.resize(R);
+    const double step = (radius - -radius) / res;
+    for (int i = 0; i < R; ++i) { volatile double m = (double)i * step; h->grid_t[i] = (float)(m + -radius); }
+    h->grid_t[R - 1] = (float)radius;
+    const int prec = pass_precision(h->cfg.precision, false);
+    const Form form = pick_form(CallFacts{prec, R, 0, h->cfg.framecode_ch > 0, false, false, false, 0, h->onchip_mode}, switches());
+    const bool ray_form = R >= FORMS[form].points_per_pass() / (MAXR - 1) && R <= 256;
+    // a slab's raw (16 B per point) stays within 256 MiB unless the caller sizes the slabs
+    long long slab = slab_rays > 0 ? (long long)slab_rays : std::max(1ll, (256ll << 20) / (16ll * R));
+    // Every slab starts on a pass boundary of every form (256 points): the limb masks are taken per pass and per wave, so only then
+    // does a point share its pass with the same points as in one launch over the whole grid, and the slab size changes no value.
+    long long align = 256;
+    for (long long a = R, b = 256; b;) { const long long r = a % b; a = b; b = r; if (!b) align = 256 / a; }
+    slab = std::max(align, slab / align * align);
+    slab = std::min(slab, rows_all);
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t b_t = al((size_t)R * 4), b_head = ray_form ? al((size_t)slab * 11 * 4) : 256;
+    const size_t b_in = ray_form ? al((size_t)slab * R * 4) : al((size_t)slab * R * 12), b_raw = al((size_t)slab * R * 16);
+    rc = ensure_ws(h, b_t + b_head + b_in + b_raw);
+    if (rc) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    float* d_t = reinterpret_cast<float*>(h->ws);
+    float* d_head = reinterpret_cast<float*>(h->ws + b_t);              // the slab's rays, or the one pseudo ray of the point form
+    float* d_in = reinterpret_cast<float*>(h->ws + b_t + b_head);       // z [rows,R], or pts [rows R,3]
+    float* d_raw = reinterpret_cast<float*>(h->ws + b_t + b_head + b_in);
+    PG_HIP(h, hipMemcpyAsync(d_t, h->grid_t.data(), (size_t)R * 4, hipMemcpyHostToDevice, st));
+    if (!ray_form) PG_HIP(h, hipMemsetAsync(d_head, 0, 64, st));
+    for (long long r0 = 0; r0 < rows_all; r0 += slab) {
+        const long long rows = std::min(slab, rows_all - r0);
+        int e;
+        if (ray_form) {
+            e = pg_launch_grid_rays(root, d_t, R, r0, rows, d_head, d_in, stream);
+            if (e) return pg_fail(h, PG_EHIP, "grid setup kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+            rc = launch_eval(h, stream, which, rows, R, d_head, d_in, skts, 0, nullptr, d_raw, nullptr);
+        } else {
+            e = pg_launch_grid_points(root, d_t, R, r0 * R, rows * R, d_in, stream);
+            if (e) return pg_fail(h, PG_EHIP, "grid setup kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+            rc = launch_eval(h, stream, which, 1, (int)(rows * R), d_head, nullptr, skts, 0, nullptr, d_raw, nullptr, 0, d_in);
+        }
+        if (rc) return rc;
+        e = pg_launch_gather_sigma(d_raw, rows * R, sigma + r0 * R, stream);
+        if (e) return pg_fail(h, PG_EHIP, "density gather kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    }
+    return PG_OK;
 }
 
 int pg_stage_composite(pg_handle* h, void* stream, int64_t n, int n_samples, const float* ray_batch, const float* z,

@@ -666,6 +666,42 @@ class HipRenderer:
         d = self.query_density(pts, skts, which)
         return d.reshape(*sh[:-1]).transpose(1, 0)
 
+    def _density_net(self, which: Optional[int]) -> int:
+        """the net a density query means: the fine net if loaded, like the reference; net 0 with single_net"""
+        if which is None:
+            which = 1 if "network_fine_state_dict" in self._state and not self.cfg.single_net else 0
+        return int(which)
+
+    def grid_density(self, kps: torch.Tensor, skts: torch.Tensor, radius: float = 1.8, res: int = 255,
+                     which: Optional[int] = None, slab_rays: int = 0) -> torch.Tensor:
+        """mesh_density's grid, formed and evaluated on the device (pg_grid_density): raw density at root + (t[a], t[b], t[c]),
+        t = linspace(-radius, radius, res + 1), as a device tensor [R,R,R].  A grid row runs as a ray, through the kernel forms
+        of a render call; nothing but the root joint and the pose crosses the bus.  `slab_rays`: rows per launch (0: the
+        library sizes the slabs); the values do not depend on it."""
+        R = int(res) + 1
+        root = _np32(torch.as_tensor(kps).reshape(-1, 24, 3)[0, 0])
+        sk, _ = self._pose_args(torch.as_tensor(skts).detach(), 1)
+        sigma = torch.empty(R, R, R, device=self.device) if res >= 1 else None
+        self._check(self.lib.pg_grid_density(self.handle, self._stream(), self._density_net(which), int(res), float(radius),
+                                             root.ctypes.data_as(C.POINTER(C.c_float)), _ptr(sk), int(slab_rays), _ptr(sigma)))
+        return sigma
+
+    def marching_cubes(self, grid: torch.Tensor, threshold: float, clamp: float = 0.0):
+        """Marching cubes on a device grid [Nx,Ny,Nz] (pg_mesh_count + pg_mesh_emit): inside is max(grid, clamp) > threshold
+        (clamp = 0: the reference's np.maximum(raw, 0); -inf: the grid as it is).  Returns device tensors (vertices float32
+        [nv,3] in index coordinates, triangles int32 [nt,3]); shared vertices, normals away from the inside."""
+        g = _dev_f32(torch.as_tensor(grid), self.device)
+        if g.dim() != 3:
+            raise ValueError(f"marching_cubes: a 3-D grid expected, got {tuple(g.shape)}")
+        nv, nt = C.c_int64(), C.c_int64()
+        args = (self.handle, self._stream(), _ptr(g), *(int(n) for n in g.shape), float(threshold), float(clamp))
+        self._check(self.lib.pg_mesh_count(*args, C.byref(nv), C.byref(nt)))
+        verts = torch.empty(nv.value, 3, device=self.device)
+        tris = torch.empty(nt.value, 3, device=self.device, dtype=torch.int32)
+        self._check(self.lib.pg_mesh_emit(*args, _ptr(verts) if nv.value else None, _ptr(tris) if nt.value else None,
+                                          nv.value, nt.value))
+        return verts, tris
+
     def pose_kinematics(self, bones: torch.Tensor, rest_pose, parents=None, want_l2ws: bool = False):
         """bones [F,24,3] axis-angle (any device/dtype) -> device kps [F,24,3] f32, skts [F,24,4,4] f32
         (+ l2ws f64), computed on the device in float64 (pg_pose_kinematics; the host equivalent is
@@ -906,6 +942,15 @@ class HipRayCaster:
             raise NotImplementedError("render_mesh_density: precomputed v is not supported")
         with self.renderer.subject(self._call_subject(subject_idxs)):
             return self.renderer.mesh_density(kps, skts, radius=radius, res=res)
+
+    def extract_mesh(self, kps, skts, bones=None, subject_idxs=None, radius=1.8, res=255, threshold=10., which=None):
+        """The mesh of one pose as the reference's render_mesh builds it (run_render.py:976-991), on the device: density grid,
+        relu, marching cubes at `threshold`.  Returns device tensors (vertices / res - .5 float32 [nv,3], triangles int32
+        [nt,3]).  `bones` is accepted for call compatibility."""
+        with self.renderer.subject(self._call_subject(subject_idxs)):
+            grid = self.renderer.grid_density(kps, skts, radius=radius, res=res, which=which)
+            verts, tris = self.renderer.marching_cubes(grid, threshold, clamp=0.0)
+        return verts / res - .5, tris
 
     # ---- nn.Module-like surface the reference touches -------------------------------
     @property
