@@ -18,71 +18,8 @@
 #include "../../include/posegen_hip.h"
 #include "pg_device.h"
 #include "pg_handle.h"
+#include "pg_launch.h"
 #include "pg_pack.h"
-
-extern "C" {
-int pg_launch_eval16(const pgd::EvalArgs* a, int fp16, int framecode, int grid, void* stream);
-int pg_launch_eval16r(const pgd::EvalArgs* a, int fp16, int framecode, int onchip, int grid, void* stream);
-int pg_launch_ray_records(const pgd::RecArgs* a, int fp16, int framecode, int n_cu, void* stream);
-int pg_eval16_points_per_pass(void);
-int pg_eval16_wgs_per_cu(void);
-int pg_launch_eval32(const pgd::EvalArgs* a, int precision, int framecode, int grid, void* stream);
-int pg_eval32_points_per_pass(void);
-int pg_launch_evalc(const pgd::EvalArgs* a, int framecode, int rec, int grid, void* stream);
-int pg_launch_ray_records_c(const pgd::RecArgs* a, int framecode, int n_cu, void* stream);
-int pg_evalc_points_per_pass(void);
-int pg_launch_evalc2(const pgd::EvalArgs* a, int framecode, int grid, void* stream);
-int pg_evalc2_points_per_pass(void);
-int pg_launch_sample_coarse(const float* rays, const float* cyls, long long cyl_stride, long long n, int chunk,
-                            int S, int lindisp, float* near_far, float* z, const float* t_rand, double* scratch, void* stream);
-long long pg_sample_coarse_scratch(long long n, int chunk);
-int pg_launch_gather_noise(const float* src, long long n, int stride, int S, const int* order, float* dst, void* stream);
-int pg_launch_mfma_rate(int f16, int lds_fed, int blocks, int iters, float* sink, void* stream);
-int pg_launch_grid_rays(const float* root3, const float* t, int R, long long row0, long long rows, float* rays, float* z, void* stream);
-int pg_launch_grid_points(const float* root3, const float* t, int R, long long p0, long long n, float* pts, void* stream);
-int pg_launch_gather_sigma(const float* raw, long long n, float* sigma, void* stream);
-int pg_launch_composite_iso(const float* rays, const float* z, const float* raw, long long n, int S, float density_scale,
-                            float rgb_eps, int density_act, float act_shift, float* rgb, float* disp, float* acc, float* alpha,
-                            float* weights, int n_imp, float* z_fine, const float* noise, const float* u_rand, int* order,
-                            float* z_new, int ld_new, void* stream);
-int pg_launch_composite_merged(const float* rays, const float* z_fine, const float* raw_c, const float* raw_new, int ld_new, const int* order,
-                               long long n, int S0, int N, float density_scale, float rgb_eps, int density_act, float act_shift,
-                               float* rgb, float* disp, float* acc, float* alpha, const float* noise, float* raw_out, void* stream);
-int pg_launch_composite(const float* rays, const float* z, const float* raw, long long n, int S,
-                        float density_scale, float rgb_eps, int density_act, float act_shift, float* rgb, float* disp, float* acc,
-                        float* alpha, float* weights, int n_imp, float* z_fine, const float* noise, const float* u_rand, int* order,
-                        void* stream);
-int pg_composite_max_samples(void);
-int pg_composite_max_importance(void);
-}
-namespace pgk {
-struct FrameGeom {
-    int H, W, tlx, tly, bw, bh;
-    float fx, fy, cx, cy;
-    float R[9], t[3];
-    float near, far, cam;
-};
-}
-extern "C" {
-int pg_launch_frame_rays(const pgk::FrameGeom* g, long long i0, long long n, float* rays, float* cams, void* stream);
-int pg_launch_pose_kinematics(const double* offs72, const int* parents24, const double* bones, long long n,
-                              float* kps, float* skts, double* l2ws, void* stream);
-int pg_launch_pose_boxes(const float* kps, long long n, const double* w2c, long long w2c_stride, const double* ring,
-                         float ext_r, float ext_top, float ext_bot, double fx, double fy, int H, int W, int offx, int offy,
-                         float* cyls, int* boxes, void* stream);
-int pg_launch_frame_compose(const pgk::FrameGeom* g, const float* rgb_map, const float* disp_map, const float* acc_map,
-                            const float* bg, float base_bg, float* rgb, float* disp, float* acc, uint8_t* rgb8,
-                            void* stream);
-// pg_repack.hip: packed images re-formed on the device (pg_load_weights_device)
-void pg_launch_collect(const float* const* tensors, const long long* off25, float* dst, void* stream);
-void pg_launch_fold(float* src, long long off_view_w, int vcols, long long off_view_b, long long off_feat_w, long long off_feat_b,
-                    long long off_fw, long long off_fb, void* stream);
-void pg_launch_gather16(const int32_t* map, const float* src, uint16_t* out, long long n, int is_bf, void* stream);
-void pg_launch_gather32(const int32_t* map, const float* src, float* out, long long n, void* stream);
-void pg_launch_codes(const float* codes, int n_codes, float* out, void* stream);
-void pg_launch_ycode(const float* view_w, int vcols, const float* codes, int n_codes, float* yc, void* stream);
-void pg_launch_widen_views(const float* src, int framecode_ch, float* dst, void* stream);
-}
 
 namespace {
 
@@ -103,6 +40,15 @@ int pg_fail(pg_handle* h, int code, const char* fmt, ...) {
     std::snprintf(g_last_error, sizeof g_last_error, "%s", buf);
     if (h) std::snprintf(h->err, sizeof h->err, "%s", buf);
     return code;
+}
+
+int pg_grow(pg_handle* h, uint8_t*& buf, size_t& bytes, size_t need, const char* what) {
+    if (need <= bytes) return PG_OK;
+    if (buf) { PG_HIP(h, hipDeviceSynchronize()); PG_HIP(h, hipFree(buf)); buf = nullptr; bytes = 0; }
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&buf), need);
+    if (e != hipSuccess) return pg_fail(h, PG_ENOMEM, "%s of %zu bytes failed: %s", what, need, hipGetErrorString(e));
+    bytes = need;
+    return PG_OK;
 }
 
 namespace {
@@ -314,13 +260,8 @@ int ensure_rec(pg_handle* h, int64_t n, int y_bytes) {
     const size_t need = (size_t)(n + REC_PAD_RAYS) * ((size_t)y_bytes + REC_AB_BYTES);
     if (need <= h->rec_bytes) return PG_OK;
     PG_HIP(h, hipSetDevice(h->device));
-    if (h->rec) { PG_HIP(h, hipDeviceSynchronize()); PG_HIP(h, hipFree(h->rec)); h->rec = nullptr; h->rec_bytes = 0; }
-    const size_t want = need + need / 16;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&h->rec), want);
-    if (e != hipSuccess) return pg_fail(h, PG_ENOMEM, "ray record buffer of %zu bytes failed: %s", want, hipGetErrorString(e));
-    h->rec_bytes = want;
     h->rec_pad_n = -1;
-    return PG_OK;
+    return pg_grow(h, h->rec, h->rec_bytes, need + need / 16, "ray record buffer");
 }
 
 // ---- the packed weight images of a net (NetState::img) ------------------------------------------------------------
@@ -407,10 +348,10 @@ int ensure_image(pg_handle* h, int which, int id) {
     if (!ns.loaded) return pg_fail(h, PG_ESTATE, "weights of net %d not loaded", which);
     NetState::Slot& s = ns.img[id];
     if (s.d) return PG_OK;
-    if (const int rr_ = refresh_host(h, which)) return rr_;     // (the last weights may have come from the device)
+    PG_TRY(refresh_host(h, which));     // (the last weights may have come from the device)
     Packed p;
-    if (const int rc = pack_image(h, which, tensors_of(ns, h->cfg), id, p)) return rc;     // (tensors_of folds feature_linear into the view layer: milliseconds of host work, once per load)
-    if (const int rc = upload(h, p.data(), p.bytes(), reinterpret_cast<void**>(&s.d))) return rc;
+    PG_TRY(pack_image(h, which, tensors_of(ns, h->cfg), id, p));     // (tensors_of folds feature_linear into the view layer: milliseconds of host work, once per load)
+    PG_TRY(upload(h, p.data(), p.bytes(), reinterpret_cast<void**>(&s.d)));
     s.bytes = p.bytes();
     ++ns.builds;
     return PG_OK;
@@ -474,7 +415,7 @@ int ensure_form_images(pg_handle* h, int which, Form f, int prec, bool with_code
     const FormInfo& fi = FORMS[f];
     for (const int image : {fi.stream, fi.wy, fi.bias}) {
         if (image == IMG_NONE || (image == IMG_YCODE && !with_codes)) continue;
-        if (const int rc = ensure_image(h, which, image_of(image, prec))) return rc;
+        PG_TRY(ensure_image(h, which, image_of(image, prec)));
     }
     return PG_OK;
 }
@@ -506,12 +447,7 @@ constexpr Reformed REFORMED[] = {
 int ensure_ws(pg_handle* h, size_t bytes) {
     if (bytes <= h->ws_bytes) return PG_OK;
     PG_HIP(h, hipSetDevice(h->device));
-    if (h->ws) { PG_HIP(h, hipDeviceSynchronize()); PG_HIP(h, hipFree(h->ws)); h->ws = nullptr; h->ws_bytes = 0; }
-    const size_t want = bytes + bytes / 8;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&h->ws), want);
-    if (e != hipSuccess) return pg_fail(h, PG_ENOMEM, "workspace allocation of %zu bytes failed: %s", want, hipGetErrorString(e));
-    h->ws_bytes = want;
-    return PG_OK;
+    return pg_grow(h, h->ws, h->ws_bytes, bytes + bytes / 8, "workspace allocation");
 }
 
 int check_ready(pg_handle* h, bool need_fine) {
@@ -531,24 +467,62 @@ bool skip_empty_ok(const pg_handle* h, bool colour_free) {
     return colour_free && h->empty_skip && h->cfg.density_act == PG_ACT_RELU && h->cfg.density_scale > 0.0f;
 }
 
-int launch_eval_one(pg_handle* h, void* stream, int which, long long n, int S, const float* rays, const float* z,
-                    const float* skts, long long pose_stride, const float* cams, float* raw, float* dbg, int dbg_stage,
-                    const float* points, const float* pnoise, bool guide_pass, bool colour_free) {
-    const int prec = pass_precision(h->cfg.precision, guide_pass);
+// One launch of a net on n rays x S samples: what a caller of launch_eval fills in, by name (the arrays as pg_stage_eval takes them)
+struct EvalCall {
+    int which = 0;
+    long long n = 0;
+    int S = 0;
+    const float *rays = nullptr, *z = nullptr, *skts = nullptr, *cams = nullptr;
+    long long pose_stride = 0;
+    float *raw = nullptr, *dbg = nullptr;
+    int dbg_stage = 0;
+    const float *points = nullptr, *pnoise = nullptr;       // [n S,3] explicit points instead of rays + z; [n,S,3] position noise
+    bool guide_pass = false, colour_free = false;           // pass_precision; skip_empty_ok
+    EvalCall slice(long long r0, long long m) const {       // rays [r0, r0 + m) of a call from rays (no points, no debug tap)
+        EvalCall c = *this;
+        c.n = m;
+        c.rays += r0 * 11; c.z += r0 * S; c.skts += r0 * pose_stride; c.raw += r0 * S * 4;
+        if (cams) c.cams += r0;
+        if (pnoise) c.pnoise += r0 * S * 3;
+        return c;
+    }
+};
+
+// The launch of `what` between two events of the handle's pool while it profiles; the pair is filed into `list` (ev_used / ev_aux)
+// unless the launch failed: a failed launch is not a sample.
+template <typename F>
+int timed_launch(pg_handle* h, void* stream, std::vector<std::pair<hipEvent_t, hipEvent_t>>& list, const char* what, F launch) {
+    if (!h->profiling) { PG_TRY_LAUNCH(h, what, launch()); return PG_OK; }
+    hipEvent_t ev[2];
+    for (hipEvent_t& e : ev) {
+        if (h->ev_free.empty()) PG_HIP(h, hipEventCreate(&e));
+        else { e = h->ev_free.back(); h->ev_free.pop_back(); }
+    }
+    PG_HIP(h, hipEventRecord(ev[0], static_cast<hipStream_t>(stream)));
+    const int err = launch();
+    PG_HIP(h, hipEventRecord(ev[1], static_cast<hipStream_t>(stream)));
+    if (err) { h->ev_free.push_back(ev[0]); h->ev_free.push_back(ev[1]); }
+    else list.emplace_back(ev[0], ev[1]);
+    PG_TRY_LAUNCH(h, what, err);
+    return PG_OK;
+}
+
+int launch_eval_one(pg_handle* h, void* stream, EvalCall c) {
+    const long long n = c.n;
+    const int prec = pass_precision(h->cfg.precision, c.guide_pass);
     const bool fc = h->cfg.framecode_ch > 0;
-    Form form = pick_form(CallFacts{prec, S, pose_stride, fc, points != nullptr, pnoise != nullptr, dbg != nullptr, dbg_stage, h->onchip_mode}, switches());
+    Form form = pick_form(CallFacts{prec, c.S, c.pose_stride, fc, c.points != nullptr, c.pnoise != nullptr, c.dbg != nullptr, c.dbg_stage, h->onchip_mode}, switches());
     // pg_debug_wave_counts: a launch of the on-chip form that the counting instantiation covers (one pose, no frame codes) adds
     // its counters to the caller's words -- what a render call's own launches did, not a stage call beside it
-    if (!dbg && h->wave_counts && form == F_ONCHIP16 && pose_stride == 0 && !fc) { dbg = reinterpret_cast<float*>(h->wave_counts); dbg_stage = 97; }
+    if (!c.dbg && h->wave_counts && form == F_ONCHIP16 && c.pose_stride == 0 && !fc) { c.dbg = reinterpret_cast<float*>(h->wave_counts); c.dbg_stage = 97; }
     const FormInfo& fi = FORMS[form];
     const int y_bytes = fi.rec_y_bytes;
-    int rc = ensure_form_images(h, which, form, prec, fc);
-    if (rc) return rc;
-    if (y_bytes && (rc = ensure_rec(h, n, y_bytes))) return rc;
-    NetState& ns = h->net[which];
-    if (fc && !ns.d_codes) return pg_fail(h, PG_ESTATE, "frame codes of net %d not set (pg_set_framecodes)", which);
+    PG_TRY(ensure_form_images(h, c.which, form, prec, fc));
+    if (y_bytes) PG_TRY(ensure_rec(h, n, y_bytes));
+    NetState& ns = h->net[c.which];
+    if (fc && !ns.d_codes) return pg_fail(h, PG_ESTATE, "frame codes of net %d not set (pg_set_framecodes)", c.which);
     pgd::EvalArgs a{};
-    a.rays = rays; a.z = z; a.pts = points; a.pnoise = pnoise; a.skts = skts; a.cams = cams;
+    a.rays = c.rays; a.z = c.z; a.pts = c.points; a.pnoise = c.pnoise; a.skts = c.skts; a.cams = c.cams;
     a.codes = fc ? ns.d_codes : nullptr;
     a.wstream = ns.img[image_of(fi.stream, prec)].d;
     a.wy = fi.wy == IMG_NONE || (fi.wy == IMG_YCODE && !fc) ? nullptr : ns.img[image_of(fi.wy, prec)].d;
@@ -569,20 +543,20 @@ int launch_eval_one(pg_handle* h, void* stream, int which, long long n, int S, c
         }
     }
     a.cutoff = h->d_cut;
-    a.raw = raw; a.dbg = dbg;
-    a.pose_stride = pose_stride;
-    a.n_points = n * S;
+    a.raw = c.raw; a.dbg = c.dbg;
+    a.pose_stride = c.pose_stride;
+    a.n_points = n * c.S;
     a.n_rays = (int)n;
-    a.S = S;
+    a.S = c.S;
     a.n_codes = ns.n_codes;
     a.tau_v = h->tau[0];
     a.tau_d = h->tau[1];
-    a.dbg_stage = dbg_stage;
+    a.dbg_stage = c.dbg_stage;
     a.far_skip = h->far_skip ? 1 : 0;
-    a.skip_empty = skip_empty_ok(h, colour_free) ? 1 : 0;
+    a.skip_empty = skip_empty_ok(h, c.colour_free) ? 1 : 0;
     const int pts = fi.points_per_pass();
-    if (!points && S < pts / (MAXR - 1))      // explicit points are one pseudo ray: a pass touches one slot
-        return pg_fail(h, PG_EINVAL, "N_samples=%d too small: the fused kernel needs >= %d samples per ray", S, pts / (MAXR - 1));
+    if (!c.points && c.S < pts / (MAXR - 1))      // explicit points are one pseudo ray: a pass touches one slot
+        return pg_fail(h, PG_EINVAL, "N_samples=%d too small: the fused kernel needs >= %d samples per ray", c.S, pts / (MAXR - 1));
     const long long iters = (a.n_points + pts - 1) / pts;
     a.n_iters = (int)iters;
     // POSEGEN_MAX_WG (measurement aid): fewer persistent workgroups than CUs, to see how much of a pass's time
@@ -592,73 +566,80 @@ int launch_eval_one(pg_handle* h, void* stream, int which, long long n, int S, c
     if (wg_cap > 0 && wg_cap < max_wg) max_wg = wg_cap;
     const int grid = (int)(iters < max_wg ? iters : max_wg);
     a.walk_rho = switches().pass_walk % grid;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    auto get = [&](hipEvent_t& ev) {
-        if (!h->ev_free.empty()) { ev = h->ev_free.back(); h->ev_free.pop_back(); return hipSuccess; }
-        return hipEventCreate(&ev);
-    };
     if (y_bytes) {          // what depends on the ray only, once per ray, in front of the fused kernel (pg_rayrec.hip)
         pgd::RecArgs ra{};
-        ra.rays = rays; ra.skts = skts; ra.cams = cams; ra.codes = a.codes; ra.wy = a.wy;
+        ra.rays = c.rays; ra.skts = c.skts; ra.cams = c.cams; ra.codes = a.codes; ra.wy = a.wy;
         ra.rec_ab = const_cast<float*>(a.rec_ab); ra.rec_y = const_cast<uint8_t*>(a.rec_y);
-        ra.pose_stride = pose_stride; ra.n_rays = (int)n; ra.n_codes = ns.n_codes;
-        ra.z = z; ra.S = S;
-        hipEvent_t x0 = nullptr, x1 = nullptr;
-        if (h->profiling) { PG_HIP(h, get(x0)); PG_HIP(h, get(x1)); PG_HIP(h, hipEventRecord(x0, static_cast<hipStream_t>(stream))); }
-        const int er = form == F_COMP_REC ? pg_launch_ray_records_c(&ra, fc, h->n_cu, stream) : pg_launch_ray_records(&ra, prec == PG_PREC_FP16, fc, h->n_cu, stream);
-        if (h->profiling) {
-            PG_HIP(h, hipEventRecord(x1, static_cast<hipStream_t>(stream)));
-            if (er) { h->ev_free.push_back(x0); h->ev_free.push_back(x1); }      // a failed launch is not a sample
-            else h->ev_aux.emplace_back(x0, x1);
+        ra.pose_stride = c.pose_stride; ra.n_rays = (int)n; ra.n_codes = ns.n_codes;
+        ra.z = c.z; ra.S = c.S;
+        PG_TRY(timed_launch(h, stream, h->ev_aux, "ray record kernel", [&] {
+            return form == F_COMP_REC ? pg_launch_ray_records_c(&ra, fc, h->n_cu, stream) : pg_launch_ray_records(&ra, prec == PG_PREC_FP16, fc, h->n_cu, stream);
+        }));
+    }
+    const int f16 = prec == PG_PREC_FP16;
+    PG_TRY(timed_launch(h, stream, h->ev_used, "fused embed+MLP kernel", [&] {
+        switch (form) {
+        case F_DIRECT16:    return pg_launch_eval16(&a, f16, fc, grid, stream);
+        case F_REC16:       return pg_launch_eval16r(&a, f16, fc, 0, grid, stream);
+        case F_ONCHIP16:    return pg_launch_eval16r(&a, f16, fc, 1, grid, stream);
+        case F_C2:          return pg_launch_evalc2(&a, fc, grid, stream);
+        case F_COMP_DIRECT: return pg_launch_evalc(&a, fc, 0, grid, stream);
+        case F_COMP_REC:    return pg_launch_evalc(&a, fc, 1, grid, stream);
+        case F_COMP_ONCHIP: return pg_launch_evalc(&a, fc, 2, grid, stream);
+        default:            return pg_launch_eval32(&a, prec, fc, grid, stream);
         }
-        if (er) return pg_fail(h, PG_EHIP, "ray record kernel launch failed: %s", hipGetErrorString((hipError_t)er));
-    }
-    if (h->profiling) {
-        PG_HIP(h, get(e0));
-        PG_HIP(h, get(e1));
-        PG_HIP(h, hipEventRecord(e0, static_cast<hipStream_t>(stream)));
-    }
-    int e = 0;
-    switch (form) {
-    case F_DIRECT16:    e = pg_launch_eval16(&a, prec == PG_PREC_FP16, fc, grid, stream); break;
-    case F_REC16:       e = pg_launch_eval16r(&a, prec == PG_PREC_FP16, fc, 0, grid, stream); break;
-    case F_ONCHIP16:    e = pg_launch_eval16r(&a, prec == PG_PREC_FP16, fc, 1, grid, stream); break;
-    case F_C2:          e = pg_launch_evalc2(&a, fc, grid, stream); break;
-    case F_COMP_DIRECT: e = pg_launch_evalc(&a, fc, 0, grid, stream); break;
-    case F_COMP_REC:    e = pg_launch_evalc(&a, fc, 1, grid, stream); break;
-    case F_COMP_ONCHIP: e = pg_launch_evalc(&a, fc, 2, grid, stream); break;
-    default:            e = pg_launch_eval32(&a, prec, fc, grid, stream); break;
-    }
-    if (h->profiling) {
-        PG_HIP(h, hipEventRecord(e1, static_cast<hipStream_t>(stream)));
-        h->ev_used.emplace_back(e0, e1);
-        h->prof_points += a.n_points;
-    }
-    if (e) return pg_fail(h, PG_EHIP, "fused embed+MLP kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    }));
+    if (h->profiling) h->prof_points += a.n_points;
     return PG_OK;
 }
 
 // One net on n rays x S samples.  Calls with more than REC_BATCH_RAYS rays run as consecutive launches over ray
 // ranges (rays are independent): the per-ray records (8.75 / 16.75 KiB per ray) then need 4.6 / 9 GB at most instead
 // of growing with the call (a 2048 x 2048 frame would ask for 72 GB).  POSEGEN_REC_BATCH overrides the size (tests).
-int launch_eval(pg_handle* h, void* stream, int which, long long n, int S, const float* rays, const float* z,
-                const float* skts, long long pose_stride, const float* cams, float* raw, float* dbg, int dbg_stage = 0,
-                const float* points = nullptr, const float* pnoise = nullptr, bool guide_pass = false, bool colour_free = false) {
+int launch_eval(pg_handle* h, void* stream, const EvalCall& c) {
     long long batch = 1ll << 19;
     if (const char* e = std::getenv("POSEGEN_REC_BATCH")) { const long long v = std::atoll(e); if (v >= 64) batch = v; }
-    if (points || dbg || n <= batch)
-        return launch_eval_one(h, stream, which, n, S, rays, z, skts, pose_stride, cams, raw, dbg, dbg_stage, points, pnoise, guide_pass, colour_free);
-    for (long long r0 = 0; r0 < n; r0 += batch) {
-        const long long m = std::min(batch, n - r0);
-        const int rc = launch_eval_one(h, stream, which, m, S, rays + r0 * 11, z + r0 * S, skts + r0 * pose_stride, pose_stride,
-                                       cams ? cams + r0 : nullptr, raw + r0 * S * 4, nullptr, 0, nullptr,
-                                       pnoise ? pnoise + r0 * S * 3 : nullptr, guide_pass, colour_free);
-        if (rc) return rc;
-    }
+    if (c.points || c.dbg || c.n <= batch) return launch_eval_one(h, stream, c);
+    for (long long r0 = 0; r0 < c.n; r0 += batch) PG_TRY(launch_eval_one(h, stream, c.slice(r0, std::min(batch, c.n - r0))));
+    return PG_OK;
+}
+
+// ---- argument rules that several entry points share ----
+// the net a stage call names (`fn`: the entry point, for the message): ready, 0 or 1, and 0 on a single_net handle
+int check_net(pg_handle* h, int which, const char* fn) {
+    PG_TRY(check_ready(h, which == 1));
+    if (which < 0 || which > 1) return pg_fail(h, PG_EINVAL, "%s: which_net must be 0 or 1", fn);
+    if (which == 1 && h->cfg.single_net) return pg_fail(h, PG_EINVAL, "%s: a single_net handle has one net (which_net 0)", fn);
+    return PG_OK;
+}
+// (`prefix`: "name: " or nothing, as the entry point has always worded it)
+int check_samples(pg_handle* h, int S, int N, const char* prefix) {
+    if (S < 2 || S > pg_composite_max_samples()) return pg_fail(h, PG_EINVAL, "%sN_samples %d outside [2,%d]", prefix, S, pg_composite_max_samples());
+    if (N < 0 || N == 1 || N > pg_composite_max_importance())
+        return pg_fail(h, PG_EINVAL, "%sN_importance %d outside {0, 2..%d}", prefix, N, pg_composite_max_importance());
+    return PG_OK;
+}
+
+// the workspace of a call, carved by `carve` (pg_handle.h Carver): sized, grown if need be, then handed out
+template <typename F> int carve_ws(pg_handle* h, F carve) {
+    Carver sizes;
+    carve(sizes);
+    PG_TRY(ensure_ws(h, sizes.off));
+    Carver c{h->ws};
+    carve(c);
     return PG_OK;
 }
 
 }  // namespace
+
+int pg_check_pose_stride(pg_handle* h, long long v, bool stage) {
+    if (v == 0 || v == 384) return PG_OK;
+    return pg_fail(h, PG_EINVAL, stage ? "pose_stride must be 0 or 384" : "pose_stride must be 0 (shared) or 384 (per ray)");
+}
+int pg_check_cyl_stride(pg_handle* h, long long v, bool stage) {
+    if (v == 0 || v == 5) return PG_OK;
+    return pg_fail(h, PG_EINVAL, stage ? "cyl_stride must be 0 or 5" : "cyl_stride must be 0 (shared) or 5 (per ray)");
+}
 
 int pg_sc_scratch(pg_handle* h, long long n, int chunk, double** out) {
     *out = nullptr;
@@ -1239,8 +1220,7 @@ int pg_device_info(const pg_handle* h, int32_t* n_cu, int32_t* clock_khz) {
 int pg_calibrate_mfma(pg_handle* h, int f16, int lds_fed, double min_ms, double* tflops, double* ms_out) {
     if (!h || !tflops) return pg_fail(h, PG_EINVAL, "pg_calibrate_mfma: null argument");
     PG_HIP(h, hipSetDevice(h->device));
-    int rc = ensure_ws(h, 256);
-    if (rc) return rc;
+    PG_TRY(ensure_ws(h, 256));
     hipEvent_t e0, e1;
     PG_HIP(h, hipEventCreate(&e0));
     PG_HIP(h, hipEventCreate(&e1));
@@ -1291,49 +1271,44 @@ int pg_stage_sample_coarse(pg_handle* h, void* stream, int64_t n, const float* r
     if (!h) return pg_fail(nullptr, PG_EINVAL, "null handle");
     if (n < 0 || !ray_batch || !cyls || !near_far || !z) return pg_fail(h, PG_EINVAL, "pg_stage_sample_coarse: null/negative argument");
     if (n_samples < 2) return pg_fail(h, PG_EINVAL, "pg_stage_sample_coarse: N_samples must be >= 2");
-    if (cyl_stride != 0 && cyl_stride != 5) return pg_fail(h, PG_EINVAL, "cyl_stride must be 0 or 5");
+    PG_TRY(pg_check_cyl_stride(h, cyl_stride, true));
     PG_HIP(h, hipSetDevice(h->device));
     double* scs = nullptr;
-    if (int rc = pg_sc_scratch(h, n, h->cfg.chunk, &scs)) return rc;
-    int e = pg_launch_sample_coarse(ray_batch, cyls, cyl_stride, n, h->cfg.chunk, n_samples,
-                                    (flags & PG_FLAG_LINDISP) ? 1 : 0, near_far, z, nullptr, scs, stream);
-    if (e) return pg_fail(h, PG_EHIP, "sample_coarse launch failed: %s", hipGetErrorString((hipError_t)e));
+    PG_TRY(pg_sc_scratch(h, n, h->cfg.chunk, &scs));
+    PG_TRY_LAUNCH(h, "sample_coarse", pg_launch_sample_coarse(ray_batch, cyls, cyl_stride, n, h->cfg.chunk, n_samples,
+                                                              (flags & PG_FLAG_LINDISP) ? 1 : 0, near_far, z, nullptr, scs, stream));
     return PG_OK;
 }
 
 int pg_stage_eval(pg_handle* h, void* stream, int which, int64_t n, int n_samples, const float* ray_batch,
                   const float* z, const float* skts, int64_t pose_stride, const float* cams, float* raw, float* dbg,
                   int dbg_stage) {
-    int rc = check_ready(h, which == 1);
-    if (rc) return rc;
-    if (which < 0 || which > 1) return pg_fail(h, PG_EINVAL, "pg_stage_eval: which_net must be 0 or 1");
-    if (which == 1 && h->cfg.single_net) return pg_fail(h, PG_EINVAL, "pg_stage_eval: a single_net handle has one net (which_net 0)");
+    PG_TRY(check_net(h, which, "pg_stage_eval"));
     if (n < 0 || !ray_batch || !z || !skts || !raw) return pg_fail(h, PG_EINVAL, "pg_stage_eval: null/negative argument");
-    if (pose_stride != 0 && pose_stride != 384) return pg_fail(h, PG_EINVAL, "pose_stride must be 0 or 384");
+    PG_TRY(pg_check_pose_stride(h, pose_stride, true));
     if (n == 0) return PG_OK;
     PG_HIP(h, hipSetDevice(h->device));
-    // (a counting call, stage 97, runs as a render call's launch would: empty waves leave their colours out of `raw`)
-    return launch_eval(h, stream, which, n, n_samples, ray_batch, z, skts, pose_stride, cams, raw, dbg, dbg_stage, nullptr, nullptr, false,
-                       dbg && dbg_stage == 97);
+    EvalCall c;
+    c.which = which; c.n = n; c.S = n_samples; c.rays = ray_batch; c.z = z; c.skts = skts; c.pose_stride = pose_stride; c.cams = cams;
+    c.raw = raw; c.dbg = dbg; c.dbg_stage = dbg_stage;
+    c.colour_free = dbg && dbg_stage == 97;     // (a counting call runs as a render call's launch would: empty waves leave their colours out of `raw`)
+    return launch_eval(h, stream, c);
 }
 
 int pg_query_density(pg_handle* h, void* stream, int which, int64_t n_points, const float* pts, const float* skts,
                      float* raw) {
-    int rc = check_ready(h, which == 1);
-    if (rc) return rc;
-    if (which < 0 || which > 1) return pg_fail(h, PG_EINVAL, "pg_query_density: which_net must be 0 or 1");
-    if (which == 1 && h->cfg.single_net) return pg_fail(h, PG_EINVAL, "pg_query_density: a single_net handle has one net (which_net 0)");
+    PG_TRY(check_net(h, which, "pg_query_density"));
     if (n_points < 0 || !pts || !skts || !raw) return pg_fail(h, PG_EINVAL, "pg_query_density: null/negative argument");
     if (n_points > 0x7fffffffLL) return pg_fail(h, PG_EINVAL, "pg_query_density: at most 2^31-1 points per call");
     if (n_points == 0) return PG_OK;
     PG_HIP(h, hipSetDevice(h->device));
     // one pseudo ray (o = d = 0) that owns all points: the kernels take the pose and the view table
     // from the ray slot, the position from `pts`
-    rc = ensure_ws(h, 256);
-    if (rc) return rc;
+    PG_TRY(ensure_ws(h, 256));
     PG_HIP(h, hipMemsetAsync(h->ws, 0, 64, static_cast<hipStream_t>(stream)));
-    return launch_eval(h, stream, which, 1, (int)n_points, reinterpret_cast<const float*>(h->ws), nullptr, skts, 0,
-                       nullptr, raw, nullptr, 0, pts);
+    EvalCall c;
+    c.which = which; c.n = 1; c.S = (int)n_points; c.rays = reinterpret_cast<const float*>(h->ws); c.skts = skts; c.raw = raw; c.points = pts;
+    return launch_eval(h, stream, c);
 }
 
 // The density grid of mesh extraction.  A grid row is a ray (pg_mesh.hip), so launch_eval picks the forms of a render call: the
@@ -1342,10 +1317,7 @@ int pg_query_density(pg_handle* h, void* stream, int which, int64_t n_points, co
 // the device: the direct forms, as pg_query_density runs them.
 int pg_grid_density(pg_handle* h, void* stream, int which, int res, double radius, const float* root, const float* skts,
                     int64_t slab_rays, float* sigma) {
-    int rc = check_ready(h, which == 1);
-    if (rc) return rc;
-    if (which < 0 || which > 1) return pg_fail(h, PG_EINVAL, "pg_grid_density: which_net must be 0 or 1");
-    if (which == 1 && h->cfg.single_net) return pg_fail(h, PG_EINVAL, "pg_grid_density: a single_net handle has one net (which_net 0)");
+    PG_TRY(check_net(h, which, "pg_grid_density"));
     if (!root || !skts || !sigma || slab_rays < 0) return pg_fail(h, PG_EINVAL, "pg_grid_density: null/negative argument");
     if (res < 1 || res > 1023) return pg_fail(h, PG_EINVAL, "pg_grid_density: res must be in [1, 1023], got %d", res);
     if (!(radius > 0.0) || !std::isfinite(radius)) return pg_fail(h, PG_EINVAL, "pg_grid_density: radius must be positive and finite");
@@ -1368,33 +1340,29 @@ int pg_grid_density(pg_handle* h, void* stream, int which, int res, double radiu
     for (long long a = R, b = 256; b;) { const long long r = a % b; a = b; b = r; if (!b) align = 256 / a; }
     slab = std::max(align, slab / align * align);
     slab = std::min(slab, rows_all);
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t b_t = al((size_t)R * 4), b_head = ray_form ? al((size_t)slab * 11 * 4) : 256;
-    const size_t b_in = ray_form ? al((size_t)slab * R * 4) : al((size_t)slab * R * 12), b_raw = al((size_t)slab * R * 16);
-    rc = ensure_ws(h, b_t + b_head + b_in + b_raw);
-    if (rc) return rc;
+    float *d_t, *d_head, *d_in, *d_raw;
+    PG_TRY(carve_ws(h, [&](Carver& c) {
+        d_t = c.take<float>(R);
+        d_head = c.take<float>(ray_form ? (size_t)slab * 11 : 64);                      // the slab's rays, or the one pseudo ray of the point form
+        d_in = c.take<float>(ray_form ? (size_t)slab * R : (size_t)slab * R * 3);       // z [rows,R], or pts [rows R,3]
+        d_raw = c.take<float>((size_t)slab * R * 4);
+    }));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    float* d_t = reinterpret_cast<float*>(h->ws);
-    float* d_head = reinterpret_cast<float*>(h->ws + b_t);              // the slab's rays, or the one pseudo ray of the point form
-    float* d_in = reinterpret_cast<float*>(h->ws + b_t + b_head);       // z [rows,R], or pts [rows R,3]
-    float* d_raw = reinterpret_cast<float*>(h->ws + b_t + b_head + b_in);
     PG_HIP(h, hipMemcpyAsync(d_t, h->grid_t.data(), (size_t)R * 4, hipMemcpyHostToDevice, st));
     if (!ray_form) PG_HIP(h, hipMemsetAsync(d_head, 0, 64, st));
+    EvalCall ev;
+    ev.which = which; ev.rays = d_head; ev.skts = skts; ev.raw = d_raw;
     for (long long r0 = 0; r0 < rows_all; r0 += slab) {
         const long long rows = std::min(slab, rows_all - r0);
-        int e;
         if (ray_form) {
-            e = pg_launch_grid_rays(root, d_t, R, r0, rows, d_head, d_in, stream);
-            if (e) return pg_fail(h, PG_EHIP, "grid setup kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-            rc = launch_eval(h, stream, which, rows, R, d_head, d_in, skts, 0, nullptr, d_raw, nullptr);
+            PG_TRY_LAUNCH(h, "grid setup kernel", pg_launch_grid_rays(root, d_t, R, r0, rows, d_head, d_in, stream));
+            ev.n = rows; ev.S = R; ev.z = d_in;
         } else {
-            e = pg_launch_grid_points(root, d_t, R, r0 * R, rows * R, d_in, stream);
-            if (e) return pg_fail(h, PG_EHIP, "grid setup kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-            rc = launch_eval(h, stream, which, 1, (int)(rows * R), d_head, nullptr, skts, 0, nullptr, d_raw, nullptr, 0, d_in);
+            PG_TRY_LAUNCH(h, "grid setup kernel", pg_launch_grid_points(root, d_t, R, r0 * R, rows * R, d_in, stream));
+            ev.n = 1; ev.S = (int)(rows * R); ev.points = d_in;
         }
-        if (rc) return rc;
-        e = pg_launch_gather_sigma(d_raw, rows * R, sigma + r0 * R, stream);
-        if (e) return pg_fail(h, PG_EHIP, "density gather kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+        PG_TRY(launch_eval(h, stream, ev));
+        PG_TRY_LAUNCH(h, "density gather kernel", pg_launch_gather_sigma(d_raw, rows * R, sigma + r0 * R, stream));
     }
     return PG_OK;
 }
@@ -1404,197 +1372,176 @@ int pg_stage_composite(pg_handle* h, void* stream, int64_t n, int n_samples, con
                        int n_importance, float* z_fine) {
     if (!h) return pg_fail(nullptr, PG_EINVAL, "null handle");
     if (n < 0 || !ray_batch || !z || !raw) return pg_fail(h, PG_EINVAL, "pg_stage_composite: null/negative argument");
-    if (n_samples < 2 || n_samples > pg_composite_max_samples()) return pg_fail(h, PG_EINVAL, "pg_stage_composite: N_samples %d outside [2,%d]", n_samples, pg_composite_max_samples());
-    if (n_importance < 0 || n_importance > pg_composite_max_importance() || n_importance == 1)
-        return pg_fail(h, PG_EINVAL, "pg_stage_composite: N_importance %d outside {0, 2..%d}", n_importance, pg_composite_max_importance());
+    PG_TRY(check_samples(h, n_samples, n_importance, "pg_stage_composite: "));
     if (n_importance > 0 && n_samples < 3) return pg_fail(h, PG_EINVAL, "importance sampling needs N_samples >= 3");
     PG_HIP(h, hipSetDevice(h->device));
-    int e = h->cfg.single_net
-        ? pg_launch_composite_iso(ray_batch, z, raw, n, n_samples, h->cfg.density_scale, h->cfg.rgb_eps, h->cfg.density_act, h->cfg.softplus_shift,
-                                  rgb, disp, acc, alpha, weights, n_importance, z_fine, nullptr, nullptr, nullptr, nullptr, 0, stream)
-        : pg_launch_composite(ray_batch, z, raw, n, n_samples, h->cfg.density_scale, h->cfg.rgb_eps, h->cfg.density_act, h->cfg.softplus_shift, rgb, disp, acc,
-                              alpha, weights, n_importance, z_fine, nullptr, nullptr, nullptr, stream);
-    if (e) return pg_fail(h, PG_EHIP, "composite launch failed: %s", hipGetErrorString((hipError_t)e));
+    pgk::Composite c{ray_batch, z, raw, n, n_samples, pgk::density_of(h->cfg), {rgb, disp, acc, alpha}};
+    c.weights = weights; c.n_imp = n_importance; c.z_fine = z_fine;
+    PG_TRY_LAUNCH(h, "composite", h->cfg.single_net ? pg_launch_composite_iso(&c, stream) : pg_launch_composite(&c, stream));
     return PG_OK;
 }
 
 namespace {
-int render_rays_impl(pg_handle* h, void* stream, int64_t n, const float* ray_batch, const float* skts,
-                     int64_t pose_stride, const float* cyls, int64_t cyl_stride, const float* cams, int n_samples,
-                     int n_importance, int flags, const pg_train_draws* dr, const pg_outputs* out);
+
+// one ray-level render call: the arguments of pg_render_rays / pg_render_rays_train
+struct RayCall {
+    int64_t n;
+    const float *rays, *skts;
+    int64_t pose_stride;
+    const float* cyls;
+    int64_t cyl_stride;
+    const float* cams;
+    int S, N, flags;
+    const pg_train_draws* dr;       // null: eval mode
+    const pg_outputs* out;
+    bool rnoise() const { return dr && dr->ray_noise; }
+    EvalCall eval(int which, int S_, const float* z, const float* pn, float* raw) const {   // a net on S_ samples per ray at the depths z
+        EvalCall c;
+        c.which = which; c.n = n; c.S = S_; c.rays = rays; c.z = z; c.skts = skts; c.pose_stride = pose_stride; c.cams = cams; c.raw = raw; c.pnoise = pn;
+        return c;
+    }
+};
+
+// The workspace of a render call, in the order it has always been carved (null: the call has no such buffer).  NP: the points per
+// ray of single_net's second pass (0: the two-net pipeline)
+struct RayBufs {
+    float *nf, *zc, *rawc, *w0;     // near/far [n,2]; the coarse points' depths [n,S] and raw [n,S,4]; weights0 where the caller takes none
+    float *zf, *rawf;               // merged depths [n,S+N]; two nets: the fine net's raw [n,S+N,4]
+    int* order;                     // sort permutation of the merged depths [n,S+N]
+    float *zn, *rawn;               // single_net: the new points' depths [n,NP] and raw [n,NP,4]
+    float* pn;                      // position noise [.,3] of the pass being evaluated
+    int carve(pg_handle* h, const RayCall& r, int NP) {
+        const size_t n = (size_t)r.n, S = r.S, SF = r.S + r.N;
+        const bool hier = r.N > 0, single = NP > 0;
+        return carve_ws(h, [&](Carver& c) {
+            nf = c.take<float>(n * 2);
+            zc = c.take<float>(n * S);
+            rawc = c.take<float>(n * S * 4);
+            w0 = c.take<float>(n * S);
+            zf = c.take<float>(n * SF, hier);
+            rawf = c.take<float>(n * SF * 4, hier && !single);
+            order = c.take<int>(n * SF, single || (hier && r.rnoise()));
+            zn = c.take<float>(n * NP, single);
+            rawn = c.take<float>(n * NP * 4, single);
+            pn = c.take<float>(n * (single ? std::max<size_t>(S, NP) : SF) * 3, r.rnoise());
+        });
+    }
+};
+
+// What both pipelines start with: near/far and the coarse depths -- with perturb the stratified jitter from the caller's draws
+// (ray_utils.py:229-246) --, the position noise of the coarse points (rows [:S] of every ray's draws), net 0 on them, and their
+// composite, which places the N importance depths: merged into b.zf and, single_net (NP > 0: the is_only pdf), in sample order
+// into b.zn as well.  colour_free: skip_empty_ok.
+int coarse_front(pg_handle* h, void* stream, const RayCall& r, const RayBufs& b, int NP, bool colour_free) {
+    const pg_train_draws* dr = r.dr;
+    const bool hier = r.N > 0, single = NP > 0;
+    double* scs = nullptr;
+    PG_TRY(pg_sc_scratch(h, r.n, h->cfg.chunk, &scs));
+    PG_TRY_LAUNCH(h, "coarse sampling", pg_launch_sample_coarse(r.rays, r.cyls, r.cyl_stride, r.n, h->cfg.chunk, r.S, (r.flags & PG_FLAG_LINDISP) ? 1 : 0,
+                                                                 b.nf, b.zc, dr ? dr->t_rand : nullptr, scs, stream));
+    if (r.rnoise()) PG_TRY_LAUNCH(h, "noise gather", pg_launch_gather_noise(dr->ray_noise, r.n, r.S + r.N, r.S, nullptr, b.pn, stream));
+    EvalCall ec = r.eval(0, r.S, b.zc, b.pn, b.rawc);
+    ec.guide_pass = hier && !single;        // (single_net's coarse raw enters the fine maps: PG_PREC_FP16M runs it in fp16c)
+    ec.colour_free = colour_free;
+    PG_TRY(launch_eval(h, stream, ec));
+    pgk::Composite cc{r.rays, b.zc, b.rawc, r.n, r.S, pgk::density_of(h->cfg), hier ? pgk::coarse_maps(*r.out) : pgk::final_maps(*r.out)};
+    cc.noise = dr ? dr->noise0 : nullptr; cc.weights = r.out->weights0 ? r.out->weights0 : b.w0;
+    cc.n_imp = r.N; cc.z_fine = b.zf; cc.u_rand = dr ? dr->u_rand : nullptr; cc.order = b.order; cc.z_new = b.zn; cc.ld_new = NP;
+    PG_TRY_LAUNCH(h, "composite", single ? pg_launch_composite_iso(&cc, stream) : pg_launch_composite(&cc, stream));
+    return PG_OK;
 }
+
+// and what both end with: the optional intermediates the caller asked for (raw_fine: null when a kernel has written it already)
+int copy_intermediates(pg_handle* h, void* stream, const RayCall& r, const RayBufs& b, const float* raw_fine) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const pg_outputs* out = r.out;
+    const size_t Pc = (size_t)r.n * r.S, Pf = (size_t)r.n * (r.S + r.N);
+    if (out->near_far) PG_HIP(h, hipMemcpyAsync(out->near_far, b.nf, (size_t)r.n * 8, hipMemcpyDeviceToDevice, s));
+    if (out->z_coarse) PG_HIP(h, hipMemcpyAsync(out->z_coarse, b.zc, Pc * 4, hipMemcpyDeviceToDevice, s));
+    if (out->raw_coarse) PG_HIP(h, hipMemcpyAsync(out->raw_coarse, b.rawc, Pc * 16, hipMemcpyDeviceToDevice, s));
+    if (r.N > 0 && out->z_fine) PG_HIP(h, hipMemcpyAsync(out->z_fine, b.zf, Pf * 4, hipMemcpyDeviceToDevice, s));
+    if (raw_fine && out->raw_fine) PG_HIP(h, hipMemcpyAsync(out->raw_fine, raw_fine, Pf * 16, hipMemcpyDeviceToDevice, s));
+    return PG_OK;
+}
+
+// single_net (core/raycasters.py:446-469): one net evaluates the S coarse points, then only the N new points drawn from the
+// is_only pdf (sample_pts_is, is_only=True); the fine maps composite the S + N raw merged in depth order.  Arguments are
+// checked by render_rays_impl.  S + N evaluations per ray instead of S + (S + N).
+int render_rays_single(pg_handle* h, void* stream, const RayCall& r) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t n = (size_t)r.n;
+    const int S = r.S, N = r.N, SF = S + N;
+    const pg_train_draws* dr = r.dr;
+    const pg_outputs* out = r.out;
+    // the new points are one pass of NP >= N points per ray: the direct 16-bit kernel needs points_per_pass / (MAXR - 1)
+    // per ray (32); the columns behind N repeat the last new depth and are not read back
+    const int prec = h->cfg.precision == PG_PREC_FP16M ? PG_PREC_FP16C : h->cfg.precision;
+    const int NP = is_shape_a(prec) ? std::max(N, pg_eval16_points_per_pass() / (MAXR - 1)) : N;
+    RayBufs b{};
+    PG_TRY(b.carve(h, r, NP));
+    // (the coarse raw is composited twice, by the coarse maps and merged into the fine ones: neither may draw density noise)
+    PG_TRY(coarse_front(h, stream, r, b, NP, !out->raw_coarse && !out->raw_fine && !(dr && (dr->noise0 || dr->noise1))));
+    if (r.rnoise()) {   // the new points' noise: rows [S:] in z_samples order (sample_pts_is, raycasters.py:665-674)
+        int e = NP == N ? pg_launch_gather_noise(dr->ray_noise + (size_t)S * 3, r.n, SF, N, nullptr, b.pn, stream)
+                        : (int)hipMemsetAsync(b.pn, 0, n * NP * 12, s);
+        if (!e && NP != N)      // rows of NP: the N draws, then zeros for the padding points
+            e = (int)hipMemcpy2DAsync(b.pn, (size_t)NP * 12, dr->ray_noise + (size_t)S * 3, (size_t)SF * 12, (size_t)N * 12, n,
+                                      hipMemcpyDeviceToDevice, s);
+        if (e) return pg_fail(h, PG_EHIP, "noise gather failed: %s", hipGetErrorString((hipError_t)e));
+    }
+    EvalCall en = r.eval(0, NP, b.zn, b.pn, b.rawn);
+    en.colour_free = !out->raw_fine && !(dr && dr->noise1);
+    PG_TRY(launch_eval(h, stream, en));
+    pgk::Composite cm{r.rays, b.zf, b.rawc, r.n, SF, pgk::density_of(h->cfg), pgk::final_maps(*out)};
+    cm.noise = dr ? dr->noise1 : nullptr; cm.n_imp = N; cm.order = b.order; cm.raw_new = b.rawn; cm.ld_new = NP; cm.raw_out = out->raw_fine;
+    PG_TRY_LAUNCH(h, "composite", pg_launch_composite_merged(&cm, stream));
+    return copy_intermediates(h, stream, r, b, nullptr);
+}
+
+int render_rays_impl(pg_handle* h, void* stream, const RayCall& r) {
+    PG_TRY(check_ready(h, r.N > 0));
+    if (r.n < 0 || !r.rays || !r.skts || !r.cyls || !r.out) return pg_fail(h, PG_EINVAL, "pg_render_rays: null/negative argument");
+    PG_TRY(pg_check_pose_stride(h, r.pose_stride, false));
+    PG_TRY(pg_check_cyl_stride(h, r.cyl_stride, false));
+    PG_TRY(check_samples(h, r.S, r.N, ""));
+    if (r.N > 0 && r.S + r.N > pg_composite_max_samples())
+        return pg_fail(h, PG_EINVAL, "N_samples + N_importance exceeds %d", pg_composite_max_samples());
+    if (r.n == 0) return PG_OK;
+    PG_HIP(h, hipSetDevice(h->device));
+    if (h->cfg.single_net && r.N > 0) return render_rays_single(h, stream, r);
+    const int SF = r.S + r.N;
+    const pg_train_draws* dr = r.dr;
+    const pg_outputs* out = r.out;
+    RayBufs b{};
+    PG_TRY(b.carve(h, r, 0));
+    // what the empty-wave skip needs to know (skip_empty_ok): the launch's raw goes to one composite, without density noise, and to nobody else
+    PG_TRY(coarse_front(h, stream, r, b, 0, !out->raw_coarse && !(dr && dr->noise0)));
+    if (r.N > 0) {
+        // every fine point keeps the noise of the stage it came from, in sorted order (raycasters.py:666-686)
+        if (r.rnoise()) PG_TRY_LAUNCH(h, "noise gather", pg_launch_gather_noise(dr->ray_noise, r.n, SF, SF, b.order, b.pn, stream));
+        EvalCall ef = r.eval(1, SF, b.zf, b.pn, b.rawf);
+        ef.colour_free = !out->raw_fine && !(dr && dr->noise1);
+        PG_TRY(launch_eval(h, stream, ef));
+        pgk::Composite cf{r.rays, b.zf, b.rawf, r.n, SF, pgk::density_of(h->cfg), pgk::final_maps(*out)};
+        cf.noise = dr ? dr->noise1 : nullptr;
+        PG_TRY_LAUNCH(h, "composite", pg_launch_composite(&cf, stream));
+    }
+    return copy_intermediates(h, stream, r, b, b.rawf);
+}
+}  // namespace
 
 int pg_render_rays(pg_handle* h, void* stream, int64_t n, const float* ray_batch, const float* skts,
                    int64_t pose_stride, const float* cyls, int64_t cyl_stride, const float* cams, int n_samples,
                    int n_importance, int flags, const pg_outputs* out) {
-    return render_rays_impl(h, stream, n, ray_batch, skts, pose_stride, cyls, cyl_stride, cams, n_samples, n_importance,
-                            flags, nullptr, out);
+    return render_rays_impl(h, stream, RayCall{n, ray_batch, skts, pose_stride, cyls, cyl_stride, cams, n_samples, n_importance, flags, nullptr, out});
 }
 
 int pg_render_rays_train(pg_handle* h, void* stream, int64_t n, const float* ray_batch, const float* skts,
                          int64_t pose_stride, const float* cyls, int64_t cyl_stride, const float* cams, int n_samples,
                          int n_importance, int flags, const pg_train_draws* draws, const pg_outputs* out) {
     if (!draws) return pg_fail(h, PG_EINVAL, "pg_render_rays_train: null draws (use pg_render_rays for eval mode)");
-    return render_rays_impl(h, stream, n, ray_batch, skts, pose_stride, cyls, cyl_stride, cams, n_samples, n_importance,
-                            flags, draws, out);
+    return render_rays_impl(h, stream, RayCall{n, ray_batch, skts, pose_stride, cyls, cyl_stride, cams, n_samples, n_importance, flags, draws, out});
 }
-
-namespace {
-// single_net (core/raycasters.py:446-469): one net evaluates the S coarse points, then only the N new points drawn from the
-// is_only pdf (sample_pts_is, is_only=True); the fine maps composite the S + N raw merged in depth order.  Arguments are
-// checked by render_rays_impl.  S + N evaluations per ray instead of S + (S + N).
-int render_rays_single(pg_handle* h, void* stream, int64_t n, const float* ray_batch, const float* skts, int64_t pose_stride,
-                       const float* cyls, int64_t cyl_stride, const float* cams, int S, int N, int flags,
-                       const pg_train_draws* dr, const pg_outputs* out) {
-    PG_HIP(h, hipSetDevice(h->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int SF = S + N;
-    // the new points are one pass of NP >= N points per ray: the direct 16-bit kernel needs points_per_pass / (MAXR - 1)
-    // per ray (32); the columns behind N repeat the last new depth and are not read back
-    const int prec = h->cfg.precision == PG_PREC_FP16M ? PG_PREC_FP16C : h->cfg.precision;
-    const int NP = is_shape_a(prec) ? std::max(N, pg_eval16_points_per_pass() / (MAXR - 1)) : N;
-    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-    const bool rnoise = dr && dr->ray_noise;
-    const size_t b_nf = al((size_t)n * 2 * 4), b_zc = al((size_t)n * S * 4), b_rc = al((size_t)n * S * 16),
-                 b_w0 = al((size_t)n * S * 4), b_zf = al((size_t)n * SF * 4), b_ord = al((size_t)n * SF * 4),
-                 b_zn = al((size_t)n * NP * 4), b_rn = al((size_t)n * NP * 16),
-                 b_pn = rnoise ? al((size_t)n * std::max(S, NP) * 12) : 0;
-    int rc = ensure_ws(h, b_nf + b_zc + b_rc + b_w0 + b_zf + b_ord + b_zn + b_rn + b_pn);
-    if (rc) return rc;
-    uint8_t* p = h->ws;
-    float* nf = reinterpret_cast<float*>(p); p += b_nf;
-    float* zc = reinterpret_cast<float*>(p); p += b_zc;
-    float* rawc = reinterpret_cast<float*>(p); p += b_rc;
-    float* w0 = reinterpret_cast<float*>(p); p += b_w0;
-    float* zf = reinterpret_cast<float*>(p); p += b_zf;
-    int* order = reinterpret_cast<int*>(p); p += b_ord;
-    float* zn = reinterpret_cast<float*>(p); p += b_zn;
-    float* rawn = reinterpret_cast<float*>(p); p += b_rn;
-    float* pn = b_pn ? reinterpret_cast<float*>(p) : nullptr;
-    {
-        double* scs = nullptr;
-        if (int rc2 = pg_sc_scratch(h, n, h->cfg.chunk, &scs)) return rc2;
-        int e0 = pg_launch_sample_coarse(ray_batch, cyls, cyl_stride, n, h->cfg.chunk, S, (flags & PG_FLAG_LINDISP) ? 1 : 0, nf, zc,
-                                         dr ? dr->t_rand : nullptr, scs, stream);
-        if (e0) return pg_fail(h, PG_EHIP, "coarse sampling launch failed: %s", hipGetErrorString((hipError_t)e0));
-    }
-    if (rnoise) {       // position noise of the coarse points: rows [:S] of every ray's draws
-        int e0 = pg_launch_gather_noise(dr->ray_noise, n, SF, S, nullptr, pn, stream);
-        if (e0) return pg_fail(h, PG_EHIP, "noise gather launch failed: %s", hipGetErrorString((hipError_t)e0));
-    }
-    // the coarse raw enters the fine maps: not a guide pass (PG_PREC_FP16M runs fp16c)
-    // (the coarse raw is composited twice, by the coarse maps and merged into the fine ones: neither may draw density noise)
-    const bool free_c = !out->raw_coarse && !out->raw_fine && !(dr && (dr->noise0 || dr->noise1));
-    const bool free_n = !out->raw_fine && !(dr && dr->noise1);
-    rc = launch_eval(h, stream, 0, n, S, ray_batch, zc, skts, pose_stride, cams, rawc, nullptr, 0, nullptr, rnoise ? pn : nullptr, false, free_c);
-    if (rc) return rc;
-    int e = pg_launch_composite_iso(ray_batch, zc, rawc, n, S, h->cfg.density_scale, h->cfg.rgb_eps, h->cfg.density_act,
-                                    h->cfg.softplus_shift, out->rgb0, out->disp0, out->acc0, out->alpha0,
-                                    out->weights0 ? out->weights0 : w0, N, zf, dr ? dr->noise0 : nullptr, dr ? dr->u_rand : nullptr,
-                                    order, zn, NP, stream);
-    if (e) return pg_fail(h, PG_EHIP, "composite launch failed: %s", hipGetErrorString((hipError_t)e));
-    if (rnoise) {       // the new points' noise: rows [S:] in z_samples order (sample_pts_is, raycasters.py:665-674)
-        e = NP == N ? pg_launch_gather_noise(dr->ray_noise + (size_t)S * 3, n, SF, N, nullptr, pn, stream)
-                    : (int)hipMemsetAsync(pn, 0, (size_t)n * NP * 12, s);
-        if (!e && NP != N)      // rows of NP: the N draws, then zeros for the padding points
-            e = (int)hipMemcpy2DAsync(pn, (size_t)NP * 12, dr->ray_noise + (size_t)S * 3, (size_t)SF * 12, (size_t)N * 12, (size_t)n,
-                                      hipMemcpyDeviceToDevice, s);
-        if (e) return pg_fail(h, PG_EHIP, "noise gather failed: %s", hipGetErrorString((hipError_t)e));
-    }
-    rc = launch_eval(h, stream, 0, n, NP, ray_batch, zn, skts, pose_stride, cams, rawn, nullptr, 0, nullptr, rnoise ? pn : nullptr, false, free_n);
-    if (rc) return rc;
-    e = pg_launch_composite_merged(ray_batch, zf, rawc, rawn, NP, order, n, S, N, h->cfg.density_scale, h->cfg.rgb_eps, h->cfg.density_act,
-                                   h->cfg.softplus_shift, out->rgb_map, out->disp_map, out->acc_map, out->alpha,
-                                   dr ? dr->noise1 : nullptr, out->raw_fine, stream);
-    if (e) return pg_fail(h, PG_EHIP, "composite launch failed: %s", hipGetErrorString((hipError_t)e));
-    if (out->near_far) PG_HIP(h, hipMemcpyAsync(out->near_far, nf, (size_t)n * 8, hipMemcpyDeviceToDevice, s));
-    if (out->z_coarse) PG_HIP(h, hipMemcpyAsync(out->z_coarse, zc, (size_t)n * S * 4, hipMemcpyDeviceToDevice, s));
-    if (out->raw_coarse) PG_HIP(h, hipMemcpyAsync(out->raw_coarse, rawc, (size_t)n * S * 16, hipMemcpyDeviceToDevice, s));
-    if (out->z_fine) PG_HIP(h, hipMemcpyAsync(out->z_fine, zf, (size_t)n * SF * 4, hipMemcpyDeviceToDevice, s));
-    return PG_OK;
-}
-
-int render_rays_impl(pg_handle* h, void* stream, int64_t n, const float* ray_batch, const float* skts,
-                     int64_t pose_stride, const float* cyls, int64_t cyl_stride, const float* cams, int n_samples,
-                     int n_importance, int flags, const pg_train_draws* dr, const pg_outputs* out) {
-    int rc = check_ready(h, n_importance > 0);
-    if (rc) return rc;
-    if (n < 0 || !ray_batch || !skts || !cyls || !out) return pg_fail(h, PG_EINVAL, "pg_render_rays: null/negative argument");
-    if (pose_stride != 0 && pose_stride != 384) return pg_fail(h, PG_EINVAL, "pose_stride must be 0 (shared) or 384 (per ray)");
-    if (cyl_stride != 0 && cyl_stride != 5) return pg_fail(h, PG_EINVAL, "cyl_stride must be 0 (shared) or 5 (per ray)");
-    if (n_samples < 2 || n_samples > pg_composite_max_samples()) return pg_fail(h, PG_EINVAL, "N_samples %d outside [2,%d]", n_samples, pg_composite_max_samples());
-    if (n_importance < 0 || n_importance == 1 || n_importance > pg_composite_max_importance())
-        return pg_fail(h, PG_EINVAL, "N_importance %d outside {0, 2..%d}", n_importance, pg_composite_max_importance());
-    if (n_importance > 0 && n_samples + n_importance > pg_composite_max_samples())
-        return pg_fail(h, PG_EINVAL, "N_samples + N_importance exceeds %d", pg_composite_max_samples());
-    if (n == 0) return PG_OK;
-    if (h->cfg.single_net && n_importance > 0)
-        return render_rays_single(h, stream, n, ray_batch, skts, pose_stride, cyls, cyl_stride, cams, n_samples, n_importance, flags, dr, out);
-    PG_HIP(h, hipSetDevice(h->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int S = n_samples, SF = n_samples + n_importance;
-    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-    const size_t b_nf = al((size_t)n * 2 * 4), b_zc = al((size_t)n * S * 4), b_rc = al((size_t)n * S * 16),
-                 b_w0 = al((size_t)n * S * 4), b_zf = al((size_t)n * SF * 4), b_rf = al((size_t)n * SF * 16);
-    const bool hier = n_importance > 0;
-    const bool rnoise = dr && dr->ray_noise;
-    const size_t b_ord = rnoise && hier ? al((size_t)n * SF * 4) : 0, b_pn = rnoise ? al((size_t)n * SF * 12) : 0;
-    rc = ensure_ws(h, b_nf + b_zc + b_rc + b_w0 + (hier ? b_zf + b_rf : 0) + b_ord + b_pn);
-    if (rc) return rc;
-    uint8_t* p = h->ws;
-    float* nf = reinterpret_cast<float*>(p); p += b_nf;
-    float* zc = reinterpret_cast<float*>(p); p += b_zc;
-    float* rawc = reinterpret_cast<float*>(p); p += b_rc;
-    float* w0 = reinterpret_cast<float*>(p); p += b_w0;
-    float* zf = reinterpret_cast<float*>(p); p += hier ? b_zf : 0;
-    float* rawf = reinterpret_cast<float*>(p); p += hier ? b_rf : 0;
-    int* order = b_ord ? reinterpret_cast<int*>(p) : nullptr; p += b_ord;
-    float* pn = b_pn ? reinterpret_cast<float*>(p) : nullptr;
-
-    // near/far + coarse depths; with perturb the stratified jitter from the caller's draws (ray_utils.py:229-246)
-    {
-        double* scs = nullptr;
-        if (int rc = pg_sc_scratch(h, n, h->cfg.chunk, &scs)) return rc;
-        int e0 = pg_launch_sample_coarse(ray_batch, cyls, cyl_stride, n, h->cfg.chunk, S, (flags & PG_FLAG_LINDISP) ? 1 : 0, nf, zc,
-                                         dr ? dr->t_rand : nullptr, scs, stream);
-        if (e0) return pg_fail(h, PG_EHIP, "coarse sampling launch failed: %s", hipGetErrorString((hipError_t)e0));
-    }
-    if (rnoise) {       // position noise of the coarse points: rows [:S] of every ray's draws
-        int e0 = pg_launch_gather_noise(dr->ray_noise, n, SF, S, nullptr, pn, stream);
-        if (e0) return pg_fail(h, PG_EHIP, "noise gather launch failed: %s", hipGetErrorString((hipError_t)e0));
-    }
-    // what the empty-wave skip needs to know (skip_empty_ok): the launch's raw goes to one composite, without density noise, and to nobody else
-    const bool free_c = !out->raw_coarse && !(dr && dr->noise0);
-    const bool free_f = !out->raw_fine && !(dr && dr->noise1);
-    rc = launch_eval(h, stream, 0, n, S, ray_batch, zc, skts, pose_stride, cams, rawc, nullptr, 0, nullptr, rnoise ? pn : nullptr, hier, free_c);
-    if (rc) return rc;
-    int e = pg_launch_composite(ray_batch, zc, rawc, n, S, h->cfg.density_scale, h->cfg.rgb_eps, h->cfg.density_act, h->cfg.softplus_shift,
-                                hier ? out->rgb0 : out->rgb_map, hier ? out->disp0 : out->disp_map,
-                                hier ? out->acc0 : out->acc_map, hier ? out->alpha0 : out->alpha,
-                                out->weights0 ? out->weights0 : w0, n_importance, hier ? zf : nullptr,
-                                dr ? dr->noise0 : nullptr, dr ? dr->u_rand : nullptr, order, stream);
-    if (e) return pg_fail(h, PG_EHIP, "composite launch failed: %s", hipGetErrorString((hipError_t)e));
-    if (hier) {
-        if (rnoise) {   // every fine point keeps the noise of the stage it came from, in sorted order (raycasters.py:666-686)
-            e = pg_launch_gather_noise(dr->ray_noise, n, SF, SF, order, pn, stream);
-            if (e) return pg_fail(h, PG_EHIP, "noise gather launch failed: %s", hipGetErrorString((hipError_t)e));
-        }
-        rc = launch_eval(h, stream, 1, n, SF, ray_batch, zf, skts, pose_stride, cams, rawf, nullptr, 0, nullptr, rnoise ? pn : nullptr, false, free_f);
-        if (rc) return rc;
-        e = pg_launch_composite(ray_batch, zf, rawf, n, SF, h->cfg.density_scale, h->cfg.rgb_eps, h->cfg.density_act, h->cfg.softplus_shift, out->rgb_map,
-                                out->disp_map, out->acc_map, out->alpha, nullptr, 0, nullptr, dr ? dr->noise1 : nullptr,
-                                nullptr, nullptr, stream);
-        if (e) return pg_fail(h, PG_EHIP, "composite launch failed: %s", hipGetErrorString((hipError_t)e));
-    }
-    // optional intermediates
-    if (out->near_far) PG_HIP(h, hipMemcpyAsync(out->near_far, nf, (size_t)n * 8, hipMemcpyDeviceToDevice, s));
-    if (out->z_coarse) PG_HIP(h, hipMemcpyAsync(out->z_coarse, zc, (size_t)n * S * 4, hipMemcpyDeviceToDevice, s));
-    if (out->raw_coarse) PG_HIP(h, hipMemcpyAsync(out->raw_coarse, rawc, (size_t)n * S * 16, hipMemcpyDeviceToDevice, s));
-    if (hier && out->z_fine) PG_HIP(h, hipMemcpyAsync(out->z_fine, zf, (size_t)n * SF * 4, hipMemcpyDeviceToDevice, s));
-    if (hier && out->raw_fine) PG_HIP(h, hipMemcpyAsync(out->raw_fine, rawf, (size_t)n * SF * 16, hipMemcpyDeviceToDevice, s));
-    return PG_OK;
-}
-}  // namespace
 
 int pg_pose_kinematics(pg_handle* h, void* stream, int64_t n_poses, const double* bones, const double* bone_offsets,
                        const int32_t* parents, float* kps, float* skts, double* l2ws) {
@@ -1606,8 +1553,7 @@ int pg_pose_kinematics(pg_handle* h, void* stream, int64_t n_poses, const double
         if (parents[j] < 0 || parents[j] > j || (j > 0 && parents[j] == j))
             return pg_fail(h, PG_EINVAL, "pg_pose_kinematics: joint %d must come after its parent (%d)", j, parents[j]);
     PG_HIP(h, hipSetDevice(h->device));
-    int e = pg_launch_pose_kinematics(rest_pose, parents, bones, n_poses, kps, skts, l2ws, stream);
-    if (e) return pg_fail(h, PG_EHIP, "pose kinematics kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    PG_TRY_LAUNCH(h, "pose kinematics kernel", pg_launch_pose_kinematics(rest_pose, parents, bones, n_poses, kps, skts, l2ws, stream));
     return PG_OK;
 }
 
@@ -1670,22 +1616,19 @@ int frame_render_range(pg_handle* h, void* stream, const pgk::FrameGeom& g, int6
     float *rays, *cams;
     pg_outputs out{};
     FrameMaps own{};
-    int rc = frame_ws(h, ext ? 0 : n, r1 - r0, &rays, &cams, &own, &out);
-    if (rc) return rc;
+    PG_TRY(frame_ws(h, ext ? 0 : n, r1 - r0, &rays, &cams, &own, &out));
     if (maps) *maps = ext ? *ext : own;
     if (r1 == r0) return PG_OK;
     if (ext) { out.rgb_map = ext->rgb_map; out.disp_map = ext->disp_map; out.acc_map = ext->acc_map; }
     else { out.rgb_map = own.rgb_map + r0 * 3; out.disp_map = own.disp_map + r0; out.acc_map = own.acc_map + r0; }
     const bool fc = h->cfg.framecode_ch > 0;
-    int e = pg_launch_frame_rays(&g, r0, r1 - r0, rays, fc ? cams : nullptr, stream);
-    if (e) return pg_fail(h, PG_EHIP, "frame ray kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    PG_TRY_LAUNCH(h, "frame ray kernel", pg_launch_frame_rays(&g, r0, r1 - r0, rays, fc ? cams : nullptr, stream));
     return pg_render_rays(h, stream, r1 - r0, rays, skts, 0, cyl, 0, fc ? cams : nullptr, n_samples, n_importance, flags, &out);
 }
 
 int frame_compose(pg_handle* h, void* stream, const pgk::FrameGeom& g, const FrameMaps& maps, const float* bg, float base_bg,
                   float* rgb, float* disp, float* acc, uint8_t* rgb8) {
-    int e = pg_launch_frame_compose(&g, maps.rgb_map, maps.disp_map, maps.acc_map, bg, base_bg, rgb, disp, acc, rgb8, stream);
-    if (e) return pg_fail(h, PG_EHIP, "frame compose kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    PG_TRY_LAUNCH(h, "frame compose kernel", pg_launch_frame_compose(&g, maps.rgb_map, maps.disp_map, maps.acc_map, bg, base_bg, rgb, disp, acc, rgb8, stream));
     return PG_OK;
 }
 
@@ -1698,11 +1641,9 @@ int pg_render_frame(pg_handle* h, void* stream, int H, int W, const float* c2w, 
     if (!h) return pg_fail(nullptr, PG_EINVAL, "null handle");
     if (!skts || !cyl || !rgb) return pg_fail(h, PG_EINVAL, "pg_render_frame: null argument");
     pgk::FrameGeom g{};
-    int rc = frame_geom(h, H, W, c2w, intrinsics, box, near, far, cam, &g);
-    if (rc) return rc;
+    PG_TRY(frame_geom(h, H, W, c2w, intrinsics, box, near, far, cam, &g));
     FrameMaps maps{};
-    rc = frame_render_range(h, stream, g, 0, (int64_t)g.bw * g.bh, skts, cyl, n_samples, n_importance, flags, &maps);
-    if (rc) return rc;
+    PG_TRY(frame_render_range(h, stream, g, 0, (int64_t)g.bw * g.bh, skts, cyl, n_samples, n_importance, flags, &maps));
     return frame_compose(h, stream, g, maps, bg, base_bg, rgb, disp, acc, rgb8);
 }
 
@@ -1713,8 +1654,7 @@ int pg_render_frame_range(pg_handle* h, void* stream, int H, int W, const float*
     if (!h) return pg_fail(nullptr, PG_EINVAL, "null handle");
     if (!skts || !cyl || !rgb_map || !disp_map || !acc_map) return pg_fail(h, PG_EINVAL, "pg_render_frame_range: null argument");
     pgk::FrameGeom g{};
-    int rc = frame_geom(h, H, W, c2w, intrinsics, box, near, far, cam, &g);
-    if (rc) return rc;
+    PG_TRY(frame_geom(h, H, W, c2w, intrinsics, box, near, far, cam, &g));
     const FrameMaps ext{rgb_map, disp_map, acc_map};
     return frame_render_range(h, stream, g, ray_begin, ray_end, skts, cyl, n_samples, n_importance, flags, nullptr, &ext);
 }
@@ -1725,8 +1665,7 @@ int pg_compose_frame(pg_handle* h, void* stream, int H, int W, const int* box, c
     if (H <= 0 || W <= 0 || !box || !rgb) return pg_fail(h, PG_EINVAL, "pg_compose_frame: null/non-positive argument");
     pgk::FrameGeom g{};
     const float c2w[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0}, intr[4] = {1.f, 1.f, 0.f, 0.f};
-    int rc = frame_geom(h, H, W, c2w, intr, box, 0.f, 1.f, -1.f, &g);
-    if (rc) return rc;
+    PG_TRY(frame_geom(h, H, W, c2w, intr, box, 0.f, 1.f, -1.f, &g));
     if ((int64_t)g.bw * g.bh > 0 && (!rgb_map || !disp_map || !acc_map)) return pg_fail(h, PG_EINVAL, "pg_compose_frame: null map of a non-empty box");
     PG_HIP(h, hipSetDevice(h->device));
     const FrameMaps maps{const_cast<float*>(rgb_map), const_cast<float*>(disp_map), const_cast<float*>(acc_map)};
@@ -1741,9 +1680,8 @@ int pg_pose_boxes(pg_handle* h, void* stream, int64_t n_poses, const float* kps,
         return pg_fail(h, PG_EINVAL, "pg_pose_boxes: null/negative argument");
     if (w2c_stride != 0 && w2c_stride != 16) return pg_fail(h, PG_EINVAL, "pg_pose_boxes: w2c_stride must be 0 (one camera) or 16");
     PG_HIP(h, hipSetDevice(h->device));
-    int e = pg_launch_pose_boxes(kps, n_poses, w2c, w2c_stride, ring, (float)extension, (float)top_extension, (float)bot_extension,
-                                 fx, fy, H, W, off_x, off_y, cyls, boxes, stream);
-    if (e) return pg_fail(h, PG_EHIP, "pose box kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    PG_TRY_LAUNCH(h, "pose box kernel", pg_launch_pose_boxes(kps, n_poses, w2c, w2c_stride, ring, (float)extension, (float)top_extension,
+                                                             (float)bot_extension, fx, fy, H, W, off_x, off_y, cyls, boxes, stream));
     return PG_OK;
 }
 
@@ -1945,15 +1883,14 @@ struct FrameOut {
     int put(int f, const pgk::FrameGeom& g, const FrameMaps& maps) {
         auto& c = h->fc;
         const int b = k++ % NBUF;
-        if (staged) { const int rc = drain(b); if (rc) return rc; }
+        if (staged) PG_TRY(drain(b));
         PG_HIP(h, hipStreamWaitEvent(st, c.copied[b], 0));          // buffer b's previous copy-out (no-op before the first)
         uint8_t* base = reinterpret_cast<uint8_t*>(c.d_frame[b]);
         float* d_rgb = reinterpret_cast<float*>(base);
         float* d_disp = reinterpret_cast<float*>(base + hw * 12);
         float* d_acc = reinterpret_cast<float*>(base + hw * 16);
         uint8_t* d_u8 = rgb8 ? base + hw * 20 : nullptr;
-        int rc = frame_compose(h, st, g, maps, d_bg, base_bg, d_rgb, d_disp, d_acc, d_u8);
-        if (rc) return rc;
+        PG_TRY(frame_compose(h, st, g, maps, d_bg, base_bg, d_rgb, d_disp, d_acc, d_u8));
         PG_HIP(h, hipEventRecord(c.composed[b], st));
         PG_HIP(h, hipStreamWaitEvent(c.copy_stream, c.composed[b], 0));
         uint8_t* sp = staged ? stage(b) : nullptr;
@@ -1967,7 +1904,7 @@ struct FrameOut {
     }
     int finish() {
         if (staged)
-            for (int b = 0; b < NBUF; ++b) { const int rc = drain(b); if (rc) return rc; }
+            for (int b = 0; b < NBUF; ++b) PG_TRY(drain(b));
         PG_HIP(h, hipStreamSynchronize(h->fc.copy_stream));
         return PG_OK;
     }
@@ -2013,8 +1950,7 @@ int pg_render_frames_subjects(pg_handle* h, int n_frames, int H, int W, const fl
     std::vector<pgk::FrameGeom> geo(n_frames);
     std::vector<int64_t> nr(n_frames);
     for (int f = 0; f < n_frames; ++f) {
-        const int rc = frame_geom(h, H, W, c2ws + 12 * f, intrinsics + 4 * f, boxes + 4 * f, near, far, cams ? cams[f] : -1.0f, &geo[f]);
-        if (rc) return rc;
+        PG_TRY(frame_geom(h, H, W, c2ws + 12 * f, intrinsics + 4 * f, boxes + 4 * f, near, far, cams ? cams[f] : -1.0f, &geo[f]));
         nr[f] = (int64_t)geo[f].bw * geo[f].bh;
     }
     std::vector<FrameTask> tasks;

@@ -16,6 +16,7 @@
 // This is the 16-bit kernel for rays with < 64 samples, explicit points (density queries) and position
 // noise; rays with >= 64 samples run pg_eval16r.hip (16x16x32 MFMAs, per-ray records).
 #include "pg_eval16_common.h"
+#include "pg_launch.h"
 
 namespace pgd {
 __device__ __forceinline__ int h_abl(int lane) { return lane >> 5; }

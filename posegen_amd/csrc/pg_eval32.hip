@@ -12,6 +12,7 @@
 // values, or 8 split values, per lane) is multiplied into all out tiles, so split
 // operands are converted once per unit.
 #include "pg_device.h"
+#include "pg_launch.h"
 
 namespace pgd {
 using namespace pgp::B;

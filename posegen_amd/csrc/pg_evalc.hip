@@ -35,6 +35,7 @@
 #include <type_traits>
 
 #include "pg_comp.h"
+#include "pg_launch.h"
 
 // cache policy of the per-ray record fetches (streamed once; must not evict the weight stream from L2)
 #ifndef PG_REC_POLICY

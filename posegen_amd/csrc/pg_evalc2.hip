@@ -27,6 +27,7 @@
 #include <type_traits>
 
 #include "pg_comp.h"
+#include "pg_launch.h"
 
 namespace pgd {
 namespace c2 {

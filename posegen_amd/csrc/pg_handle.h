@@ -75,9 +75,28 @@ extern "C" void pg_train_release(pg_handle* h);
 extern "C" void pg_mesh_release(pg_handle* h);
 // scratch of pg_launch_sample_coarse for n rays in chunks of `chunk` (null when the one-launch form runs)
 int pg_sc_scratch(pg_handle* h, long long n, int chunk, double** out);
+// the pose / cylinder stride of a ray-level call (`stage`: the stage entry points' shorter wording)
+int pg_check_pose_stride(pg_handle* h, long long v, bool stage);
+int pg_check_cyl_stride(pg_handle* h, long long v, bool stage);
 
 // records the message (handle and thread-local "last error") and returns `code`
 int pg_fail(pg_handle* h, int code, const char* fmt, ...);
+// a device buffer that only ever grows (the old contents are void; what read them has to finish before they go)
+int pg_grow(pg_handle* h, uint8_t*& buf, size_t& bytes, size_t need, const char* what);
+
+// A buffer carved into arrays, each on a 256-byte boundary.  The list of take<T>(count) calls runs twice: over a Carver without a
+// base, which only adds the sizes up (the pointers come out null), then over the allocation -- an array cannot be carved without
+// being counted.
+struct Carver {
+    uint8_t* base = nullptr;
+    size_t off = 0;
+    template <typename T> T* take(size_t count, bool wanted = true) {
+        if (!wanted) return nullptr;
+        T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+        off += (count * sizeof(T) + 255) & ~size_t(255);
+        return p;
+    }
+};
 
 #define PG_HIP(h, call)                                                                      \
     do {                                                                                     \
@@ -85,3 +104,10 @@ int pg_fail(pg_handle* h, int code, const char* fmt, ...);
         if (e_ != hipSuccess)                                                                \
             return pg_fail(h, PG_EHIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
+
+// a step that fails: PG_TRY hands the callee's code up (the callee has recorded its message), PG_TRY_LAUNCH records a launcher's
+// hipError_t; PG_LAUNCH_CHECK is the latter behind a hipLaunchKernelGGL
+#define PG_TRY(call) do { const int rc_ = (call); if (rc_) return rc_; } while (0)
+#define PG_TRY_LAUNCH(h, what, call)                                                                                            \
+    do { const int e_ = (int)(call); if (e_) return pg_fail(h, PG_EHIP, "%s launch failed: %s", what, hipGetErrorString((hipError_t)e_)); } while (0)
+#define PG_LAUNCH_CHECK(h, what) PG_TRY_LAUNCH(h, what, hipGetLastError())

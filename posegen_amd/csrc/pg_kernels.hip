@@ -8,6 +8,8 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "pg_launch.h"
+
 namespace pgk {
 
 // ------------------------------------------------------------------------------------
@@ -530,14 +532,7 @@ __global__ __launch_bounds__(256) void gather_noise_kernel(const float* __restri
 
 namespace pgk {
 
-// ---- frame front / back end ---------------------------------------
-struct FrameGeom {
-    int H, W, tlx, tly, bw, bh;        // box = pixels [tly, tly+bh) x [tlx, tlx+bw)
-    float fx, fy, cx, cy;
-    float R[9], t[3];                   // c2w[:3,:3] row-major, c2w[:3,3]
-    float near, far, cam;
-};
-
+// ---- frame front / back end (FrameGeom: pg_launch.h) ----------------
 // ray_batch rows of the box's pixels (get_rays + the bbox gather of kp_to_valid_rays,
 // core/utils/ray_utils.py:6-28, 83-136, and the packing of trainer.py:118-137), in the
 // reference's row-major pixel order.  Plain fp32 ops in the reference's order, no FMA.
@@ -771,51 +766,31 @@ extern "C" int pg_launch_sample_coarse(const float* rays, const float* cyls, lon
     return (int)hipGetLastError();
 }
 
-extern "C" int pg_launch_composite(const float* rays, const float* z, const float* raw, long long n, int S,
-                                   float density_scale, float rgb_eps, int density_act, float act_shift, float* rgb, float* disp,
-                                   float* acc, float* alpha, float* weights, int n_imp, float* z_fine, const float* noise,
-                                   const float* u_rand, int* order, void* stream) {
-    if (n <= 0) return 0;
-    long long blocks = (n + pgk::CP_WAVES - 1) / pgk::CP_WAVES;
+// one composite_kernel<MODE> launch of the descriptor `c` (pg_launch.h).  CP_MERGE samples nothing and writes no weights: the
+// kernel's importance arguments stay empty there, and c.n_imp / c.order describe the merge (`mg`) instead
+template <int MODE>
+static int launch_composite(const pgk::Composite& c, const pgk::CompMerge& mg, void* stream) {
+    if (c.n <= 0) return 0;
+    constexpr bool SAMPLES = MODE != pgk::CP_MERGE;
+    long long blocks = (c.n + pgk::CP_WAVES - 1) / pgk::CP_WAVES;
     if (blocks > 16384) blocks = 16384;         // a wave takes several rays (measured flat from 4 k to 32 k blocks, -0.05 ms per frame against one ray per wave)
-    hipLaunchKernelGGL(pgk::composite_kernel<pgk::CP_PLAIN>, dim3((unsigned)blocks), dim3(pgk::CP_WAVES * 64), 0,
-                       static_cast<hipStream_t>(stream), rays, z, reinterpret_cast<const float4*>(raw), n, S,
-                       density_scale, rgb_eps, density_act, act_shift, rgb, disp, acc, alpha, weights, n_imp, z_fine, noise, u_rand, order,
-                       nullptr, pgk::CompMerge{});
+    hipLaunchKernelGGL(pgk::composite_kernel<MODE>, dim3((unsigned)blocks), dim3(pgk::CP_WAVES * 64), 0,
+                       static_cast<hipStream_t>(stream), c.rays, c.z, reinterpret_cast<const float4*>(c.raw), c.n, c.S,
+                       c.den.scale, c.den.rgb_eps, c.den.act, c.den.shift, c.out.rgb, c.out.disp, c.out.acc, c.out.alpha,
+                       SAMPLES ? c.weights : nullptr, SAMPLES ? c.n_imp : 0, SAMPLES ? c.z_fine : nullptr, c.noise,
+                       SAMPLES ? c.u_rand : nullptr, SAMPLES ? c.order : nullptr, MODE == pgk::CP_ISO ? c.z_new : nullptr, mg);
     return (int)hipGetLastError();
 }
 
-// single_net, coarse pass: pg_launch_composite with the is_only pdf; z_new [n, ld_new] (may be null) receives the new depths
-// in sample order (columns n_imp.. repeat the last one)
-extern "C" int pg_launch_composite_iso(const float* rays, const float* z, const float* raw, long long n, int S,
-                                       float density_scale, float rgb_eps, int density_act, float act_shift, float* rgb, float* disp,
-                                       float* acc, float* alpha, float* weights, int n_imp, float* z_fine, const float* noise,
-                                       const float* u_rand, int* order, float* z_new, int ld_new, void* stream) {
-    if (n <= 0) return 0;
-    long long blocks = (n + pgk::CP_WAVES - 1) / pgk::CP_WAVES;
-    if (blocks > 16384) blocks = 16384;
-    hipLaunchKernelGGL(pgk::composite_kernel<pgk::CP_ISO>, dim3((unsigned)blocks), dim3(pgk::CP_WAVES * 64), 0,
-                       static_cast<hipStream_t>(stream), rays, z, reinterpret_cast<const float4*>(raw), n, S,
-                       density_scale, rgb_eps, density_act, act_shift, rgb, disp, acc, alpha, weights, n_imp, z_fine, noise, u_rand, order,
-                       z_new, pgk::CompMerge{nullptr, nullptr, nullptr, 0, n_imp, ld_new < n_imp ? n_imp : ld_new});
-    return (int)hipGetLastError();
+extern "C" int pg_launch_composite(const pgk::Composite* c, void* stream) {
+    return launch_composite<pgk::CP_PLAIN>(*c, pgk::CompMerge{}, stream);
 }
-
-// single_net, fine pass over z_fine [n, S0 + N]: raw of sample s = raw_c[order < S0] or raw_new[order - S0] (order: the rank
-// map of pg_launch_composite_iso; raw_new [n, ld_new, 4]); raw_out [n, S0 + N, 4] (may be null) receives the merged raw
-extern "C" int pg_launch_composite_merged(const float* rays, const float* z_fine, const float* raw_c, const float* raw_new, int ld_new,
-                                          const int* order, long long n, int S0, int N, float density_scale, float rgb_eps,
-                                          int density_act, float act_shift, float* rgb, float* disp, float* acc, float* alpha,
-                                          const float* noise, float* raw_out, void* stream) {
-    if (n <= 0) return 0;
-    long long blocks = (n + pgk::CP_WAVES - 1) / pgk::CP_WAVES;
-    if (blocks > 16384) blocks = 16384;
-    const pgk::CompMerge mg{reinterpret_cast<const float4*>(raw_new), order, reinterpret_cast<float4*>(raw_out), S0, N, ld_new};
-    hipLaunchKernelGGL(pgk::composite_kernel<pgk::CP_MERGE>, dim3((unsigned)blocks), dim3(pgk::CP_WAVES * 64), 0,
-                       static_cast<hipStream_t>(stream), rays, z_fine, reinterpret_cast<const float4*>(raw_c), n, S0 + N,
-                       density_scale, rgb_eps, density_act, act_shift, rgb, disp, acc, alpha, nullptr, 0, nullptr, noise, nullptr,
-                       nullptr, nullptr, mg);
-    return (int)hipGetLastError();
+extern "C" int pg_launch_composite_iso(const pgk::Composite* c, void* stream) {
+    return launch_composite<pgk::CP_ISO>(*c, pgk::CompMerge{nullptr, nullptr, nullptr, 0, c->n_imp, c->ld_new < c->n_imp ? c->n_imp : c->ld_new}, stream);
+}
+extern "C" int pg_launch_composite_merged(const pgk::Composite* c, void* stream) {
+    return launch_composite<pgk::CP_MERGE>(*c, pgk::CompMerge{reinterpret_cast<const float4*>(c->raw_new), c->order, reinterpret_cast<float4*>(c->raw_out),
+                                                              c->S - c->n_imp, c->n_imp, c->ld_new}, stream);
 }
 
 // ------------------------------------------------------------------------------------

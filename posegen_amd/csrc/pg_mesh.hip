@@ -13,6 +13,7 @@
 #include <stdint.h>
 
 #include "pg_handle.h"
+#include "pg_launch.h"
 #include "pg_mesh_table.inc"        // generated from posegen_amd/mesh.py by the Makefile: PG_MC_MAX_TRI, PG_MC_TRI_TABLE, PG_MC_N_TRI
 
 namespace pgm {

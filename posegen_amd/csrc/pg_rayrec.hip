@@ -14,6 +14,7 @@
 // Workgroup = 8 waves; wave w owns out tile w&3 (32 of the 128 view channels) and the joints of half w>>2, and
 // keeps its Y-stage weights (pack_vy: 24 or 26 B fragments) in registers for the whole launch.
 #include "pg_device.h"
+#include "pg_launch.h"
 
 namespace pgd {
 

@@ -14,6 +14,7 @@
 #include <cstdint>
 
 #include "pg_layout.h"
+#include "pg_launch.h"
 #include "pg_pack.h"
 
 namespace pgr {

@@ -33,25 +33,7 @@
 #include <vector>
 
 #include "pg_handle.h"
-
-extern "C" {
-int pg_launch_sample_coarse(const float* rays, const float* cyls, long long cyl_stride, long long n, int chunk,
-                            int S, int lindisp, float* near_far, float* z, const float* t_rand, double* scratch, void* stream);
-int pg_launch_gather_noise(const float* src, long long n, int stride, int S, const int* order, float* dst, void* stream);
-int pg_launch_composite(const float* rays, const float* z, const float* raw, long long n, int S,
-                        float density_scale, float rgb_eps, int density_act, float act_shift, float* rgb, float* disp, float* acc,
-                        float* alpha, float* weights, int n_imp, float* z_fine, const float* noise, const float* u_rand, int* order,
-                        void* stream);
-int pg_launch_composite_iso(const float* rays, const float* z, const float* raw, long long n, int S, float density_scale, float rgb_eps,
-                            int density_act, float act_shift, float* rgb, float* disp, float* acc, float* alpha, float* weights, int n_imp,
-                            float* z_fine, const float* noise, const float* u_rand, int* order, float* z_new, int ld_new, void* stream);
-int pg_launch_composite_merged(const float* rays, const float* z_fine, const float* raw_c, const float* raw_new, int ld_new, const int* order,
-                               long long n, int S0, int N, float density_scale, float rgb_eps, int density_act, float act_shift, float* rgb,
-                               float* disp, float* acc, float* alpha, const float* noise, float* raw_out, void* stream);
-void pg_launch_widen_views(const float* src, int framecode_ch, float* dst, void* stream);
-int pg_composite_max_samples(void);
-int pg_composite_max_importance(void);
-}
+#include "pg_launch.h"
 
 namespace pgt {
 using namespace pgl;
@@ -1324,13 +1306,6 @@ inline Tape* tape_of(pg_handle* h) {
     return static_cast<Tape*>(h->train);
 }
 
-// a step that fails: PG_TRY hands the callee's code up (the callee has recorded its message), PG_TRY_LAUNCH records a launcher's
-// hipError_t; PG_LAUNCH_CHECK is the latter behind a hipLaunchKernelGGL
-#define PG_TRY(call) do { const int rc_ = (call); if (rc_) return rc_; } while (0)
-#define PG_TRY_LAUNCH(h, what, call)                                                                                            \
-    do { const int e_ = (int)(call); if (e_) return pg_fail(h, PG_EHIP, "%s launch failed: %s", what, hipGetErrorString((hipError_t)e_)); } while (0)
-#define PG_LAUNCH_CHECK(h, what) PG_TRY_LAUNCH(h, what, hipGetLastError())
-
 // C += row (x) col in fp32, row[m ld] a column of another array (gemm(): persistent layer kernel only)
 struct Rank1 { const float* row; long long ld; const float* col; };
 // C[M,N] = A B (+ bias, relu, accumulate) with element strides (sam, sak: A's row and k strides; sbk, sbn: B's); a_kcont / b_kcont:
@@ -1781,13 +1756,9 @@ inline WMat wmat(int i, int fc) {
 // THE layout of the tape: sets every pointer of `t` into the buffer at `base` and returns the bytes used.  Run with a null base
 // first (the byte count; the pointers come out null), then with the allocation -- an array cannot be carved without being counted
 size_t plan_tape(Tape& t, const TapeShape& sh, uint8_t* base) {
-    // every array starts on a 256-byte boundary (the GEMMs pick kernels by the alignment of these pointers)
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        float* r = base ? reinterpret_cast<float*>(base + off) : nullptr;
-        off += (bytes + 255) & ~size_t(255);
-        return r;
-    };
+    // every array starts on a 256-byte boundary (Carver; the GEMMs pick kernels by the alignment of these pointers)
+    Carver c{base};
+    auto take = [&](size_t bytes) { return reinterpret_cast<float*>(c.take<uint8_t>(bytes)); };
     auto take_weights = [&](int k, bool on) {       // net k's bf16 weight copies (on = false: none, the pointers are null)
         for (int i = 0; i < 24; ++i) {
             const WMat m = wmat(i, sh.fc);
@@ -1834,16 +1805,7 @@ size_t plan_tape(Tape& t, const TapeShape& sh, uint8_t* base) {
     t.gwide = (sh.single && sh.views0) ? take(vwide) : nullptr;
     for (int k = 0; k < 2; ++k) take_weights(k, sh.bf16 && t.pass[k].P > 0);
     t.part = take(PART_FLOATS * 4); t.rs_part = take(RS_FLOATS * 4); t.ray_g = take(n * FC_CH * 4);
-    return off;
-}
-// a device buffer that only ever grows (the old contents are void; what read them has to finish before they go)
-int grow(pg_handle* h, uint8_t*& buf, size_t& bytes, size_t need, const char* what) {
-    if (need <= bytes) return PG_OK;
-    if (buf) { PG_HIP(h, hipDeviceSynchronize()); PG_HIP(h, hipFree(buf)); buf = nullptr; bytes = 0; }
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&buf), need);
-    if (e != hipSuccess) return pg_fail(h, PG_ENOMEM, "%s of %zu bytes failed: %s", what, need, hipGetErrorString(e));
-    bytes = need;
-    return PG_OK;
+    return c.off;
 }
 // the start of a forward: the old tape is void from here on, the new one is laid out (the buffer only ever grows) and described
 int tape_begin(const Step& a, Tape& t) {
@@ -1853,7 +1815,7 @@ int tape_begin(const Step& a, Tape& t) {
     const bool single = h->cfg.single_net != 0;
     const TapeShape sh{a.n, a.S, a.N, single, h->train_precision == PG_PREC_BF16, h->cfg.framecode_ch > 0, h->cfg.multires_views == 0};
     // (the counting run leaves every pointer of the tape null; should the allocation fail they stay so, behind valid = false)
-    PG_TRY(grow(h, t.buf, t.bytes, plan_tape(t, sh, nullptr), "training tape"));
+    PG_TRY(pg_grow(h, t.buf, t.bytes, plan_tape(t, sh, nullptr), "training tape"));
     if (plan_tape(t, sh, t.buf) > t.bytes) return pg_fail(h, PG_ESTATE, "training tape: the layout ends outside the allocation");
     if (!a.cams) t.cams = nullptr;
     t.n = a.n; t.S = a.S; t.N = a.N; t.fc = sh.fc; t.bf16 = sh.bf16;     // (16-bit mode: the tape's activations and their gradients are bf16 arrays)
@@ -1944,13 +1906,11 @@ int forward_two_nets(const Step& a, Tape& t, const pg_net_params& coarse, const 
     if (hier) t.params[1] = *fine;
     Pass pc;
     PG_TRY(coarse_stage(a, t, pc));
-    const float ds = h->cfg.density_scale, eps = h->cfg.rgb_eps, shift = h->cfg.softplus_shift;
-    const int act = h->cfg.density_act;
     Pass& pf = t.pass[1];
-    PG_TRY_LAUNCH(h, "composite", pg_launch_composite(t.rays, pc.z, pc.raw, a.n, a.S, ds, eps, act, shift, hier ? out->rgb0 : out->rgb_map,
-                                                      hier ? out->disp0 : out->disp_map, hier ? out->acc0 : out->acc_map, hier ? out->alpha0 : out->alpha,
-                                                      out->weights0 ? out->weights0 : t.w0, a.N, hier ? pf.z : nullptr, pc.noise,
-                                                      dr ? dr->u_rand : nullptr, (t.rnoise && hier) ? t.order : nullptr, a.s));
+    pgk::Composite cc{t.rays, pc.z, pc.raw, a.n, a.S, pgk::density_of(h->cfg), hier ? pgk::coarse_maps(*out) : pgk::final_maps(*out)};
+    cc.noise = pc.noise; cc.weights = out->weights0 ? out->weights0 : t.w0;
+    cc.n_imp = a.N; cc.z_fine = hier ? pf.z : nullptr; cc.u_rand = dr ? dr->u_rand : nullptr; cc.order = (t.rnoise && hier) ? t.order : nullptr;
+    PG_TRY_LAUNCH(h, "composite", pg_launch_composite(&cc, a.s));
     if (hier) {
         if (dr && dr->noise1) PG_HIP(h, hipMemcpyAsync(pf.noise, dr->noise1, (size_t)pf.P * 4, hipMemcpyDeviceToDevice, a.s));
         else pf.noise = nullptr;
@@ -1958,8 +1918,9 @@ int forward_two_nets(const Step& a, Tape& t, const pg_net_params& coarse, const 
         if (t.rnoise) PG_TRY_LAUNCH(h, "noise gather", pg_launch_gather_noise(dr->ray_noise, a.n, SF, SF, t.order, pf.pn, a.s));
         PG_TRY(launch_embed(h, a.s, t, pf, fine->codes, fine->n_codes));
         PG_TRY(mlp_forward(h, a.s, t, 1, pf, *fine, t.fc));
-        PG_TRY_LAUNCH(h, "composite", pg_launch_composite(t.rays, pf.z, pf.raw, a.n, SF, ds, eps, act, shift, out->rgb_map, out->disp_map, out->acc_map,
-                                                          out->alpha, nullptr, 0, nullptr, pf.noise, nullptr, nullptr, a.s));
+        pgk::Composite cf{t.rays, pf.z, pf.raw, a.n, SF, cc.den, pgk::final_maps(*out)};
+        cf.noise = pf.noise;
+        PG_TRY_LAUNCH(h, "composite", pg_launch_composite(&cf, a.s));
     }
     return finish_step(a, t, pc, hier ? pf.z : nullptr, hier ? pf.raw : nullptr);
 }
@@ -1986,25 +1947,24 @@ int forward_single(const Step& a, Tape& t, const pg_net_params& net) {
     Pass pc;
     PG_TRY(coarse_stage(a, t, pc));
     const Pass& p = t.pass[0];
-    const float ds = h->cfg.density_scale, eps = h->cfg.rgb_eps, shift = h->cfg.softplus_shift;
-    const int act = h->cfg.density_act;
-    float* w0 = out->weights0 ? out->weights0 : t.w0;
+    pgk::Composite cc{t.rays, pc.z, pc.raw, a.n, S, pgk::density_of(h->cfg), hier ? pgk::coarse_maps(*out) : pgk::final_maps(*out)};
+    cc.noise = p.noise; cc.weights = out->weights0 ? out->weights0 : t.w0;
     if (!hier) {
-        PG_TRY_LAUNCH(h, "composite", pg_launch_composite(t.rays, pc.z, pc.raw, a.n, S, ds, eps, act, shift, out->rgb_map, out->disp_map, out->acc_map,
-                                                          out->alpha, w0, 0, nullptr, p.noise, nullptr, nullptr, a.s));
+        PG_TRY_LAUNCH(h, "composite", pg_launch_composite(&cc, a.s));
         return finish_step(a, t, pc, nullptr, nullptr);
     }
     Pass pn = sub_pass(p, p.P1, a.n * N, N, t.es());
-    PG_TRY_LAUNCH(h, "composite", pg_launch_composite_iso(t.rays, pc.z, pc.raw, a.n, S, ds, eps, act, shift, out->rgb0, out->disp0, out->acc0, out->alpha0,
-                                                          w0, N, t.zf, p.noise, dr ? dr->u_rand : nullptr, t.order, pn.z, N, a.s));
+    cc.n_imp = N; cc.z_fine = t.zf; cc.u_rand = dr ? dr->u_rand : nullptr; cc.order = t.order; cc.z_new = pn.z; cc.ld_new = N;
+    PG_TRY_LAUNCH(h, "composite", pg_launch_composite_iso(&cc, a.s));
     // the new points' noise: rows [S:] in z_samples order (sample_pts_is, raycasters.py:665-674)
     if (t.rnoise) PG_TRY_LAUNCH(h, "noise gather", pg_launch_gather_noise(dr->ray_noise + (size_t)S * 3, a.n, SF, N, nullptr, pn.pn, a.s));
     PG_TRY(launch_embed(h, a.s, t, pn, net.codes, net.n_codes));
     PG_TRY(mlp_forward(h, a.s, t, 0, pn, t.params[0], t.fc));
     if (dr && dr->noise1) PG_HIP(h, hipMemcpyAsync(t.noise1, dr->noise1, (size_t)a.n * SF * 4, hipMemcpyDeviceToDevice, a.s));
     else t.noise1 = nullptr;
-    PG_TRY_LAUNCH(h, "composite", pg_launch_composite_merged(t.rays, t.zf, pc.raw, pn.raw, N, t.order, a.n, S, N, ds, eps, act, shift, out->rgb_map,
-                                                             out->disp_map, out->acc_map, out->alpha, t.noise1, out->raw_fine, a.s));
+    pgk::Composite cm{t.rays, t.zf, pc.raw, a.n, SF, cc.den, pgk::final_maps(*out)};
+    cm.noise = t.noise1; cm.n_imp = N; cm.order = t.order; cm.raw_new = pn.raw; cm.ld_new = N; cm.raw_out = out->raw_fine;
+    PG_TRY_LAUNCH(h, "composite", pg_launch_composite_merged(&cm, a.s));
     return finish_step(a, t, pc, t.zf, nullptr);
 }
 
@@ -2043,8 +2003,8 @@ int pg_train_forward(pg_handle* h, void* stream, int64_t n, const float* ray_bat
     if (!single && h->cfg.multires_views != pgl::LD)
         return pg_fail(h, PG_EINVAL, "pg_train_forward: two nets with multires_views = 0 are not trained on this path (no shipped config; the "
                                      "0-band view embedding trains with single_net, and such two-net models render only)");
-    if (pose_stride != 0 && pose_stride != 384) return pg_fail(h, PG_EINVAL, "pose_stride must be 0 (shared) or 384 (per ray)");
-    if (cyl_stride != 0 && cyl_stride != 5) return pg_fail(h, PG_EINVAL, "cyl_stride must be 0 (shared) or 5 (per ray)");
+    PG_TRY(pg_check_pose_stride(h, pose_stride, false));
+    PG_TRY(pg_check_cyl_stride(h, cyl_stride, false));
     const int S = n_samples, N = n_importance, SF = S + N;
     if (S < 2 || SF > pg_composite_max_samples() || N < 0 || N == 1 || N > pg_composite_max_importance())
         return pg_fail(h, PG_EINVAL, "pg_train_forward: N_samples %d / N_importance %d outside the supported range", S, N);
@@ -2082,11 +2042,12 @@ static int train_backward(pg_handle* h, void* stream, int64_t tape_id, const flo
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bool pose = d_skts != nullptr;
     float *dX = nullptr, *per_ray = nullptr;
+    const pgk::Density den = pgk::density_of(h->cfg);
     if (pose) {
         const long long Pm = std::max(t.pass[0].P, t.pass[1].P);
         const size_t dx_bytes = ((size_t)Pm * DXW * 4 + 255) & ~size_t(255);
         const size_t need = dx_bytes + (d_pose_stride == 0 ? (size_t)t.n * J * 16 * 4 : 0);
-        PG_TRY(grow(h, t.pbuf, t.pbytes, need, "pose gradient workspace"));
+        PG_TRY(pg_grow(h, t.pbuf, t.pbytes, need, "pose gradient workspace"));
         dX = reinterpret_cast<float*>(t.pbuf);
         per_ray = d_pose_stride == 0 ? reinterpret_cast<float*>(t.pbuf + dx_bytes) : d_skts;
     }
@@ -2096,7 +2057,7 @@ static int train_backward(pg_handle* h, void* stream, int64_t tape_id, const flo
         const Pass& p = t.pass[0];
         if (t.views0 && !coarse->w[20]) return pg_fail(h, PG_EINVAL, "pg_train_backward: gradient tensor 20 is null");
         PG_HIP(h, hipMemsetAsync(t.d_raw, 0, (size_t)p.P * 16, s));
-        const CBwd cb{h->cfg.density_scale, h->cfg.rgb_eps, h->cfg.softplus_shift, h->cfg.density_act};
+        const CBwd cb{den.scale, den.rgb_eps, den.shift, den.act};
         const bool hier = t.N > 0;
         hipLaunchKernelGGL(merged_composite_bwd_kernel, dim3((unsigned)((t.n + 63) / 64)), dim3(64), 0, s, t.rays, p.z, t.zf, p.raw, p.noise,
                            t.noise1, t.order, (long long)t.n, t.S, t.N, cb, hier ? d_rgb_map : nullptr, hier ? d_acc_map : nullptr,
@@ -2118,7 +2079,7 @@ static int train_backward(pg_handle* h, void* stream, int64_t tape_id, const flo
         auto run = [&](int k, const float* d_rgb, const float* d_acc, const pg_net_grads& g) -> int {
             const Pass& p = t.pass[k];
             hipLaunchKernelGGL(composite_bwd_kernel, dim3((unsigned)((t.n + 63) / 64)), dim3(64), 0, s, t.rays, p.z, p.raw, p.noise, (long long)t.n, p.S,
-                               h->cfg.density_scale, h->cfg.rgb_eps, h->cfg.density_act, h->cfg.softplus_shift, d_rgb, d_acc, t.d_raw);
+                               den.scale, den.rgb_eps, den.act, den.shift, d_rgb, d_acc, t.d_raw);
             PG_LAUNCH_CHECK(h, "composite backward");
             PG_TRY(mlp_backward(h, s, t, k, p, t.params[k], g, dX));
             // this pass's share of every ray's 4 x 4s: the fine pass writes them, the coarse pass adds its own

@@ -505,6 +505,29 @@ def test_sample_counts_beyond_the_kernel_limits_are_refused(casters):
     assert torch.isfinite(ok["rgb_map"]).all()
 
 
+def test_strides_other_than_the_two_layouts_are_refused_at_the_abi(casters):
+    """pose_stride is 0 or 384 and cyl_stride 0 or 5 at every ray-level entry point: anything else -- a negative one too, which
+    would index in front of the caller's arrays -- is PG_EINVAL before anything is launched."""
+    import ctypes as C
+    from posegen_amd import _ffi
+    g = load_golden("rays_surreal")
+    cfg = cfg_from_golden(g)
+    r = casters(cfg, int(g["seed_model"]), PREC_FP32).renderer
+    rb, skts, cyl = (t.to(DEV).float().contiguous() for t in _inputs(g)[:3])
+    n, S = 8, 64
+    buf = torch.zeros(n * S * 4, device=DEV)
+    p = lambda t: C.c_void_p(t.data_ptr())
+    out = _ffi.PgOutputs()
+    for bad in (-1, 1, 16, 385):
+        assert r.lib.pg_render_rays(r.handle, r._stream(), n, p(rb), p(skts), bad, p(cyl), 0, None, S, 16, 0, C.byref(out)) == _ffi.PG_EINVAL
+        assert r.lib.pg_render_rays(r.handle, r._stream(), n, p(rb), p(skts), 0, p(cyl), bad, None, S, 16, 0, C.byref(out)) == _ffi.PG_EINVAL
+        assert r.lib.pg_stage_eval(r.handle, r._stream(), 0, n, S, p(rb), p(buf), p(skts), bad, None, p(buf), None, 0) == _ffi.PG_EINVAL
+        assert r.lib.pg_stage_sample_coarse(r.handle, r._stream(), n, p(rb), p(cyl), bad, S, 0, p(buf), p(buf)) == _ffi.PG_EINVAL
+    torch.cuda.synchronize()
+    ok = r.render_rays(rb[:n], skts, cyl, n_samples=S, n_importance=16)     # the handle survives the refusals
+    assert torch.isfinite(ok["rgb_map"]).all()
+
+
 def test_render_rays_chunk_boundary_and_ragged_sizes(casters):
     """n not a multiple of the 256-point pass, several nanmean groups, n = 1."""
     g = load_golden("rays_surreal")
