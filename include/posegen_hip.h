@@ -276,6 +276,42 @@ int pg_train_backward_pose(pg_handle* h, void* stream, int64_t tape_id, const fl
                            const float* d_rgb0, const float* d_acc0, const pg_net_grads* coarse, const pg_net_grads* fine,
                            float* d_skts, int64_t d_pose_stride);
 
+/* ---- the pose layer of pose refinement: PoseOptLayer.calculate_kinematic (core/pose_opt.py:372-445) for the configuration
+ * the shipped configs train with -- SMPL skeleton, use_rot6d, no cache.  Per unique pose u < n_poses: 6-D parameters -> rotation
+ * (rot6d_to_rotmat, core/utils/skeleton_utils.py:507-523), the kinematic chain over the rest pose's offsets (pose_opt.py:399-414,
+ * the levels of unrolled_kinematic_chain, pose_opt.py:482-521), + pelvis on every joint's translation (pose_opt.py:423-432),
+ * skts = torch.inverse(l2ws) (pose_opt.py:435), kps = l2ws[..., :3, -1] (pose_opt.py:443); then the gather by inverse_idxs
+ * (pose_opt.py:438-441): every output is written PER RAY through the ray -> pose map.
+ *   bones     device [n_poses,24,rot_dim] f32, rot_dim = 6: a joint's 6 numbers viewed as [3,2], columns a1, a2
+ *   pelvis    device [n_poses,3] f32
+ *   rest_pose device f32: [24,3] shared by all poses (rest_stride 0) or [n_poses,24,3] (rest_stride 72)
+ *   parents   HOST [24]: the joint tree, parent < child (parents[0] is not read beyond that check: joint 0 is the root)
+ *   ray_pose  HOST [n_rays] int32: the pose of every ray (inverse_idxs); NULL: n_rays == n_poses and ray u is pose u
+ *   rots [n_rays,24,3,3], l2ws [n_rays,24,4,4], skts [n_rays,24,4,4], kps [n_rays,24,3]: device f32 outputs, any may be NULL
+ * float64 arithmetic inside, outputs rounded once.  The index arrays are HOST pointers so that they are checked before anything
+ * is launched; they are copied into a buffer of the handle.  PG_EINVAL, nothing launched: rot_dim != 6, rest_stride other than
+ * 0 / 72, a joint that does not come after its parent, a ray_pose entry outside [0, n_poses), NULL ray_pose with n_rays != n_poses.
+ * Asynchronous on `stream`. */
+int pg_poseopt_forward(pg_handle* h, void* stream, int64_t n_poses, int rot_dim, const float* bones, const float* pelvis,
+                       const float* rest_pose, int64_t rest_stride, const int32_t* parents, int64_t n_rays, const int32_t* ray_pose,
+                       float* rots, float* l2ws, float* skts, float* kps);
+
+/* The transpose of pg_poseopt_forward: what loss.backward() does between the per-ray kps / skts / l2ws / rots and the parameters
+ * (the autograd graph of core/pose_opt.py:387-443; the pose optimiser's step follows, core/trainer.py:453-485).  Stateless: the
+ * forward of every pose is formed again from the parameters.  The per-ray cotangents d_rots / d_l2ws / d_skts / d_kps (device f32,
+ * shapes of the forward's outputs, any may be NULL = zero) of a pose's rays are summed in ASCENDING RAY ORDER without atomics --
+ * the reference's backward of skts[inverse_idxs] is an atomic scatter-add in no fixed order on a GPU -- then carried through the
+ * inverse (dL2W = -S^T dS S^T, S = skt), the pelvis shift, the chain (children before parents), the cross product and the two
+ * normalisations (below F.normalize's eps 1e-12: its derivative 1 / eps).  Outputs, device f32, OVERWRITTEN: d_bones
+ * [n_poses,24,6], d_pelvis [n_poses,3].  Bitwise repeatable.
+ *   seg_start HOST [n_poses + 1], seg_rays HOST [n_rays]: the rays of pose u are seg_rays[seg_start[u] .. seg_start[u + 1])
+ * PG_EINVAL, nothing launched: the refusals of pg_poseopt_forward; seg_start not monotone from 0 to n_rays; seg_rays not a
+ * permutation of 0 .. n_rays - 1, or not ascending inside a segment.  Asynchronous on `stream`. */
+int pg_poseopt_backward(pg_handle* h, void* stream, int64_t n_poses, int rot_dim, const float* bones, const float* pelvis,
+                        const float* rest_pose, int64_t rest_stride, const int32_t* parents, int64_t n_rays, const int32_t* seg_start,
+                        const int32_t* seg_rays, const float* d_rots, const float* d_l2ws, const float* d_skts, const float* d_kps,
+                        float* d_bones, float* d_pelvis);
+
 /* One frame with its front and back end on the device.  Replaces, per
  * frame: get_rays + the bounding-box gather of kp_to_valid_rays (core/utils/ray_utils.py:6-28,
  * 83-136), render()'s ray_batch packing (core/trainer.py:118-137), RayCaster.forward on the

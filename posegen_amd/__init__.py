@@ -14,6 +14,7 @@ __all__ = ["RenderConfig", "surreal_config", "surreal_single_config", "h36m_conf
 __version__ = "0.1.0"
 
 _TRAIN_NAMES = ("make_trainable", "TrainableRayCaster", "SingleNetTrainableRayCaster")
+_POSEOPT_NAMES = ("HipPoseOptLayer",)
 
 
 def __getattr__(name):
@@ -21,4 +22,7 @@ def __getattr__(name):
     if name in _TRAIN_NAMES:
         from . import train
         return getattr(train, name)
+    if name in _POSEOPT_NAMES:                 # the pose layer of pose refinement (imports torch as well)
+        from . import poseopt
+        return getattr(poseopt, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

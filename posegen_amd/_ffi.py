@@ -128,6 +128,10 @@ PROTOTYPES = {
     "pg_train_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _FP, _FP, _FP, _FP, C.POINTER(PgNetGrads), C.POINTER(PgNetGrads)]),
     "pg_train_backward_pose": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _FP, _FP, _FP, _FP, C.POINTER(PgNetGrads),
                                          C.POINTER(PgNetGrads), _FP, C.c_int64]),
+    "pg_poseopt_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, _FP, _FP, _FP, C.c_int64, C.POINTER(C.c_int32), C.c_int64,
+                                     C.POINTER(C.c_int32), _FP, _FP, _FP, _FP]),
+    "pg_poseopt_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, _FP, _FP, _FP, C.c_int64, C.POINTER(C.c_int32), C.c_int64,
+                                      C.POINTER(C.c_int32), C.POINTER(C.c_int32), _FP, _FP, _FP, _FP, _FP, _FP]),
     "pg_set_subject_count": (C.c_int, [C.c_void_p, C.c_int]),
     "pg_subject_count": (C.c_int, [C.c_void_p]),
     "pg_select_subject": (C.c_int, [C.c_void_p, C.c_int]),

@@ -759,6 +759,7 @@ void pg_destroy(pg_handle* h) {
     if (h->sc_part) (void)hipFree(h->sc_part);
     pg_train_release(h);
     pg_mesh_release(h);
+    pg_poseopt_release(h);
     frames_cache_release(h);
     for (auto& pr : h->ev_aux) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
     release_subject(*h);

@@ -49,6 +49,7 @@ struct pg_handle : Subject {
     int64_t prof_points = 0;
     void* train = nullptr;           // the training tape (pg_train.hip): activations of the last pg_train_forward
     void* mesh = nullptr;            // marching-cubes state of the last pg_mesh_count (pg_mesh.hip): flags, cases, scans
+    void* poseopt = nullptr;         // the pose layer's index buffer (pg_poseopt.hip): joint tree and ray segments of the last call
     std::vector<float> grid_t;       // pg_grid_density: the host copy of the axis table t[R] while its upload is in flight
     bool tape_out = false;           // a pg_train_forward whose backward has not run yet: the bank stays as it is until then
     // pg_render_frames: per-device buffers kept between calls (frames of H x W pixels, background, pinned staging)
@@ -73,6 +74,7 @@ struct pg_handle : Subject {
 
 extern "C" void pg_train_release(pg_handle* h);
 extern "C" void pg_mesh_release(pg_handle* h);
+extern "C" void pg_poseopt_release(pg_handle* h);
 // scratch of pg_launch_sample_coarse for n rays in chunks of `chunk` (null when the one-launch form runs)
 int pg_sc_scratch(pg_handle* h, long long n, int chunk, double** out);
 // the pose / cylinder stride of a ray-level call (`stage`: the stage entry points' shorter wording)
