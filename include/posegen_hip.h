@@ -513,6 +513,52 @@ int pg_stage_composite(pg_handle* h, void* stream, int64_t n, int n_samples,
                        float* rgb, float* disp, float* acc, float* alpha, float* weights,
                        int n_importance, float* z_fine /*[n,S+N] or NULL*/);
 
+/* The sampling, compositing and composite-backward kernels on the caller's own buffers, with everything the render and training
+ * calls can hand them (tests/test_gpu_composite_stages.py).  All check their host arguments before any launch and return
+ * PG_EINVAL on: a null required pointer, n < 0, N_samples outside [2,256] (the sampler, which has no upper limit: below 2), N_importance outside {0, 2..64}, N_samples +
+ * N_importance > 256, importance samples with N_samples < 3, ld_new < N_importance.  None needs loaded weights.
+ *
+ * pg_stage_sample_coarse_draws: pg_stage_sample_coarse with the stratified draws t_rand [n,S] (or NULL: the same call).  Chunks of
+ * more than 256 rays run as two launches, partial nanmean sums then depths; PG_FLAG_STAGE_ONE_LAUNCH in `flags` (this entry point
+ * only) runs the one-launch form at any chunk, so that the two can be compared on the same groups.
+ *
+ * pg_stage_composite_form: one composite launch in the form the caller names (not the handle's single_net).
+ *   PG_COMP_PLAIN / PG_COMP_IS_ONLY: z [n,S], raw [n,S,4]; noise [n,S] and u_rand [n,N] or NULL; rgb / disp / acc / alpha /
+ *     weights as pg_stage_composite; with N_importance > 0: z_fine [n,S+N] (required) and order [n,S+N] int32 (or NULL), the
+ *     stable sort permutation of cat(z, new depths).  IS_ONLY draws from the is_only pdf and also stores the new depths in
+ *     sample order in z_new [n,ld_new] (or NULL), columns N.. repeating the last one.  raw_new / raw_out are not read.
+ *   PG_COMP_MERGED: the fine pass of the single-net pair.  z [n,S+N] the merged depths, raw [n,S,4] the coarse points' raw,
+ *     raw_new [n,ld_new,4] the new points', order [n,S+N] (required, an INPUT: out-of-range entries are clamped), noise
+ *     [n,S+N] or NULL; raw_out [n,S+N,4] (or NULL) receives the raw gathered by order.  u_rand, weights, z_fine, z_new are
+ *     not read.
+ *
+ * pg_stage_composite_bwd: d_raw [n,S,4] of one composite from d_rgb [n,3] and d_acc [n] (either may be NULL: zero), the
+ * backward of raw2outputs as pg_train_backward runs it per net.
+ *
+ * pg_stage_merged_composite_bwd: the backward of the single-net pair.  raw / d_raw [n S + n N, 4]: the coarse points' rows
+ * ray-major, then the N new points of every ray; z_coarse [n,S], z_fine / order / noise1 [n,S+N], noise0 [n,S]; d_rgb / d_acc
+ * of the fine maps, d_rgb0 / d_acc0 of the coarse maps, any NULL.  With N_importance = 0 the one composite is the coarse one
+ * (z_fine, order, d_rgb, d_acc are not read).  d_raw is zeroed by the call, then every ray's thread adds the fine and the
+ * coarse share in that order: two calls give the same bytes.  raw and d_raw must be 16-byte aligned.  The transmittances
+ * [S+N][n] are kept in the handle's workspace. */
+#define PG_FLAG_STAGE_ONE_LAUNCH 256
+#define PG_COMP_PLAIN 0
+#define PG_COMP_IS_ONLY 1
+#define PG_COMP_MERGED 2
+int pg_stage_sample_coarse_draws(pg_handle* h, void* stream, int64_t n, const float* ray_batch, const float* cyls,
+                                 int64_t cyl_stride, int n_samples, int flags, const float* t_rand,
+                                 float* near_far /*[n,2]*/, float* z /*[n,S]*/);
+int pg_stage_composite_form(pg_handle* h, void* stream, int form, int64_t n, int n_samples, int n_importance,
+                            const float* ray_batch, const float* z, const float* raw, const float* noise, const float* u_rand,
+                            float* rgb, float* disp, float* acc, float* alpha, float* weights, float* z_fine, int32_t* order,
+                            float* z_new, int ld_new, const float* raw_new, float* raw_out);
+int pg_stage_composite_bwd(pg_handle* h, void* stream, int64_t n, int n_samples, const float* ray_batch, const float* z,
+                           const float* raw, const float* noise, const float* d_rgb, const float* d_acc, float* d_raw);
+int pg_stage_merged_composite_bwd(pg_handle* h, void* stream, int64_t n, int n_samples, int n_importance, const float* ray_batch,
+                                  const float* z_coarse, const float* z_fine, const float* raw, const float* noise0,
+                                  const float* noise1, const int32_t* order, const float* d_rgb, const float* d_acc,
+                                  const float* d_rgb0, const float* d_acc0, float* d_raw);
+
 /* Test / measurement aid: on = 0 makes the fused 16-bit and compensated kernels compute every limb of the density input
  * for every point instead of leaving out the limbs a wave / a pass is out of cutoff range of (a joint farther than
  * cutoff_dist + 24 / (tau log2 e) has a cutoff weight 1 - sigmoid(tau (v - c)) below 2^-24, cutoff_embedder.py:139-146:

@@ -17,7 +17,9 @@ LIB_PATH = os.path.join(_HERE, "_lib", "libposegen_hip.so")
 
 PG_OK, PG_EINVAL, PG_ENOMEM, PG_EHIP, PG_ESTATE = 0, -1, -2, -3, -4
 PG_FLAG_LINDISP = 1
+PG_FLAG_STAGE_ONE_LAUNCH = 256
 PG_ACT_RELU, PG_ACT_SOFTPLUS = 0, 1
+PG_COMP_PLAIN, PG_COMP_IS_ONLY, PG_COMP_MERGED = 0, 1, 2
 PG_ABI_VERSION = 11
 
 
@@ -91,6 +93,13 @@ PROTOTYPES = {
                                 C.c_int64, _FP, _FP, _FP, C.c_int]),
     "pg_stage_composite": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, _FP, _FP, _FP, _FP, _FP, _FP,
                                      _FP, _FP, C.c_int, _FP]),
+    "pg_stage_sample_coarse_draws": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _FP, _FP, C.c_int64, C.c_int,
+                                               C.c_int, _FP, _FP, _FP]),
+    "pg_stage_composite_form": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, _FP, _FP, _FP, _FP, _FP,
+                                          _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, C.c_int, _FP, _FP]),
+    "pg_stage_composite_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, _FP, _FP, _FP, _FP, _FP, _FP, _FP]),
+    "pg_stage_merged_composite_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, _FP, _FP, _FP, _FP, _FP,
+                                                _FP, _FP, _FP, _FP, _FP, _FP, _FP]),
     "pg_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "pg_profile_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "pg_profile_read_aux": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_double)]),

@@ -1382,6 +1382,56 @@ int pg_stage_composite(pg_handle* h, void* stream, int64_t n, int n_samples, con
     return PG_OK;
 }
 
+int pg_stage_sample_coarse_draws(pg_handle* h, void* stream, int64_t n, const float* ray_batch, const float* cyls,
+                                 int64_t cyl_stride, int n_samples, int flags, const float* t_rand, float* near_far, float* z) {
+    if (!h) return pg_fail(nullptr, PG_EINVAL, "null handle");
+    if (n < 0 || !ray_batch || !cyls || !near_far || !z) return pg_fail(h, PG_EINVAL, "pg_stage_sample_coarse_draws: null/negative argument");
+    if (n_samples < 2) return pg_fail(h, PG_EINVAL, "pg_stage_sample_coarse_draws: N_samples must be >= 2");
+    PG_TRY(pg_check_cyl_stride(h, cyl_stride, true));
+    PG_HIP(h, hipSetDevice(h->device));
+    double* scs = nullptr;      // (without scratch the launcher runs the one-launch form at any chunk)
+    if (!(flags & PG_FLAG_STAGE_ONE_LAUNCH)) PG_TRY(pg_sc_scratch(h, n, h->cfg.chunk, &scs));
+    PG_TRY_LAUNCH(h, "sample_coarse", pg_launch_sample_coarse(ray_batch, cyls, cyl_stride, n, h->cfg.chunk, n_samples,
+                                                              (flags & PG_FLAG_LINDISP) ? 1 : 0, near_far, z, t_rand, scs, stream));
+    return PG_OK;
+}
+
+int pg_stage_composite_form(pg_handle* h, void* stream, int form, int64_t n, int n_samples, int n_importance, const float* ray_batch,
+                            const float* z, const float* raw, const float* noise, const float* u_rand, float* rgb, float* disp,
+                            float* acc, float* alpha, float* weights, float* z_fine, int32_t* order, float* z_new, int ld_new,
+                            const float* raw_new, float* raw_out) {
+    const char* fn = "pg_stage_composite_form";
+    if (!h) return pg_fail(nullptr, PG_EINVAL, "null handle");
+    if (form != PG_COMP_PLAIN && form != PG_COMP_IS_ONLY && form != PG_COMP_MERGED) return pg_fail(h, PG_EINVAL, "%s: form %d is none of PG_COMP_*", fn, form);
+    if (n < 0 || !ray_batch || !z || !raw) return pg_fail(h, PG_EINVAL, "%s: null/negative argument", fn);
+    const int S = n_samples, N = n_importance;
+    PG_TRY(check_samples(h, S, N, "pg_stage_composite_form: "));
+    if (S + N > pg_composite_max_samples()) return pg_fail(h, PG_EINVAL, "%s: N_samples + N_importance exceeds %d", fn, pg_composite_max_samples());
+    if (N > 0 && S < 3) return pg_fail(h, PG_EINVAL, "%s: importance sampling needs N_samples >= 3", fn);
+    const bool merged = form == PG_COMP_MERGED;
+    if (merged) {
+        if (N < 2) return pg_fail(h, PG_EINVAL, "%s: the merged form needs N_importance >= 2", fn);
+        if (!raw_new || !order) return pg_fail(h, PG_EINVAL, "%s: the merged form needs raw_new and order", fn);
+        if (ld_new < N) return pg_fail(h, PG_EINVAL, "%s: ld_new %d < N_importance %d", fn, ld_new, N);
+    } else {
+        if (N > 0 && !z_fine) return pg_fail(h, PG_EINVAL, "%s: importance sampling needs z_fine", fn);
+        if (form == PG_COMP_IS_ONLY && z_new && ld_new < N) return pg_fail(h, PG_EINVAL, "%s: ld_new %d < N_importance %d", fn, ld_new, N);
+    }
+    PG_HIP(h, hipSetDevice(h->device));
+    // (the merged form composites the S + N sorted depths `z`; its launcher takes the total as S and the new ones as n_imp)
+    pgk::Composite c{ray_batch, z, raw, n, merged ? S + N : S, pgk::density_of(h->cfg), {rgb, disp, acc, alpha}};
+    c.noise = noise; c.n_imp = N; c.order = order;
+    if (merged) {
+        c.raw_new = raw_new; c.ld_new = ld_new; c.raw_out = raw_out;
+        PG_TRY_LAUNCH(h, "composite", pg_launch_composite_merged(&c, stream));
+        return PG_OK;
+    }
+    c.weights = weights; c.z_fine = z_fine; c.u_rand = u_rand;
+    if (form == PG_COMP_IS_ONLY) { c.z_new = z_new; c.ld_new = ld_new; }
+    PG_TRY_LAUNCH(h, "composite", form == PG_COMP_IS_ONLY ? pg_launch_composite_iso(&c, stream) : pg_launch_composite(&c, stream));
+    return PG_OK;
+}
+
 namespace {
 
 // one ray-level render call: the arguments of pg_render_rays / pg_render_rays_train

@@ -267,27 +267,30 @@ constexpr int CP_MAXI = 64;         // importance samples per ray
         __builtin_amdgcn_wave_barrier();                             \
     } while (0)
 
-__device__ __forceinline__ float wave_excl_scan_mul(float x, int lane) {
+// The transmittance is a product of up to 256 factors just below 1 and the cdf a sum of up to 254 terms: carried in float32 (6 scan
+// levels + the in-lane steps, every one rounding at an ulp of 1) the far samples' weights drift by ~1e-6 relative and sum w by up to
+// 7 ulp from 1 at S >= 129.  Both scans and the running values therefore go in double; their inputs and results are float32.
+__device__ __forceinline__ double wave_excl_scan_mul(double x, int lane) {
     // inclusive Hillis-Steele product, then shift by one lane
-    float incl = x;
+    double incl = x;
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) {
-        const float t = __shfl_up(incl, off);
+        const double t = __shfl_up(incl, off);
         if (lane >= off) incl *= t;
     }
-    const float prev = __shfl_up(incl, 1);
-    return lane == 0 ? 1.0f : prev;
+    const double prev = __shfl_up(incl, 1);
+    return lane == 0 ? 1.0 : prev;
 }
-__device__ __forceinline__ float wave_incl_scan_add(float x, int lane) {
-    float incl = x;
+__device__ __forceinline__ double wave_incl_scan_add(double x, int lane) {
+    double incl = x;
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) {
-        const float t = __shfl_up(incl, off);
+        const double t = __shfl_up(incl, off);
         if (lane >= off) incl += t;
     }
     return incl;
 }
-__device__ __forceinline__ float wave_sum(float x) {
+template <typename V> __device__ __forceinline__ V wave_sum(V x) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
     return x;
@@ -336,11 +339,12 @@ __device__ __forceinline__ void composite_ray(
     const float4* rr = raw + ray * S;
 
     float a_[CP_MAXE], z_[CP_MAXE], cr[CP_MAXE], cg[CP_MAXE], cb[CP_MAXE];
-    float lane_prod = 1.0f;
+    double f_[CP_MAXE];         // the transmittance factor 1 - alpha + 1e-10 of a sample
+    double lane_prod = 1.0;
 #pragma unroll
     for (int e = 0; e < CP_MAXE; ++e) {
         const int s = lane * E + e;
-        a_[e] = 0.0f; z_[e] = 0.0f; cr[e] = cg[e] = cb[e] = 0.0f;
+        a_[e] = 0.0f; z_[e] = 0.0f; cr[e] = cg[e] = cb[e] = 0.0f; f_[e] = 1.0;
         if (e < E && s < S) {
             float4 q;
             if (MODE == CP_MERGE) {
@@ -356,32 +360,38 @@ __device__ __forceinline__ void composite_ray(
             const float delta = (s + 1 < S ? zr[s + 1] - zs : 1e10f) * dnorm;
             // raw2alpha(raw / B + noise): `noise` [n,S] is the caller's draw (training, nerf.py:175-186), else 0
             const float sig = density_act(q.w / density_scale + (noise ? noise[ray * S + s] : 0.0f), act, act_shift);
-            a_[e] = 1.0f - expf(-sig * delta);
+            // exp in double: alpha = 1 - e cancels (e within an ulp of 1 leaves alpha ~ 0.002 with 5 digits), and a product of 256
+            // expf results, none correctly rounded, moves the far transmittance by ~1e-6; alpha and the factor come from the one value
+            const double ed = exp(-(double)(sig * delta));
+            a_[e] = (float)(1.0 - ed);
+            f_[e] = ed + 1e-10;
             z_[e] = zs;
             const float k = 1.0f + 2.0f * rgb_eps;
             cr[e] = (1.0f / (1.0f + expf(-q.x))) * k - rgb_eps;
             cg[e] = (1.0f / (1.0f + expf(-q.y))) * k - rgb_eps;
             cb[e] = (1.0f / (1.0f + expf(-q.z))) * k - rgb_eps;
-            lane_prod *= (1.0f - a_[e] + 1e-10f);
+            lane_prod *= f_[e];
         }
     }
-    float T = wave_excl_scan_mul(lane_prod, lane);
-    float sr = 0, sg = 0, sb = 0, sd = 0, sw = 0;
+    double T = wave_excl_scan_mul(lane_prod, lane);
+    float sr = 0, sg = 0, sb = 0, sd = 0;
+    double swd = 0;             // sum w in double: acc = min(sum w, 1) and the backward's `sum w < 1` gate (pg_train.hip) see one value
 #pragma unroll
     for (int e = 0; e < CP_MAXE; ++e) {
         const int s = lane * E + e;
         if (e < E && s < S) {
-            const float w = a_[e] * T;
-            T *= (1.0f - a_[e] + 1e-10f);
+            const float w = a_[e] * (float)T;
+            T *= f_[e];
             sr += w * cr[e]; sg += w * cg[e]; sb += w * cb[e];
-            sd += w * z_[e]; sw += w;
+            sd += w * z_[e]; swd += (double)w;
             if (alpha_out) alpha_out[ray * S + s] = a_[e];
             if (w_out) w_out[ray * S + s] = w;
             sh_w[wave][s] = w;
             sh_z[wave][s] = z_[e];
         }
     }
-    sr = wave_sum(sr); sg = wave_sum(sg); sb = wave_sum(sb); sd = wave_sum(sd); sw = wave_sum(sw);
+    sr = wave_sum(sr); sg = wave_sum(sg); sb = wave_sum(sb); sd = wave_sum(sd);
+    const float sw = (float)wave_sum(swd);
     if (lane == 0) {
         if (rgb_out) { rgb_out[ray * 3 + 0] = sr; rgb_out[ray * 3 + 1] = sg; rgb_out[ray * 3 + 2] = sb; }
         if (disp_out) {
@@ -415,15 +425,15 @@ __device__ __forceinline__ void composite_ray(
     }
     const float total = wave_sum(part);
     // cdf[0] = 0, cdf[i+1] = cumsum(pdf)[i]
-    float lane_sum = 0.0f;
+    double lane_sum = 0.0;
 #pragma unroll
-    for (int e = 0; e < CP_MAXE; ++e) { pw[e] = pw[e] / total; lane_sum += pw[e]; }
-    float run = wave_incl_scan_add(lane_sum, lane) - lane_sum;
+    for (int e = 0; e < CP_MAXE; ++e) { pw[e] = pw[e] / total; lane_sum += (double)pw[e]; }
+    double run = wave_incl_scan_add(lane_sum, lane) - lane_sum;
     if (lane == 0) sh_cdf[wave][0] = 0.0f;
 #pragma unroll
     for (int e = 0; e < CP_MAXE; ++e) {
         const int i = lane * E + e;
-        if (e < E && i < NB) { run += pw[e]; sh_cdf[wave][i + 1] = run; }
+        if (e < E && i < NB) { run += (double)pw[e]; sh_cdf[wave][i + 1] = (float)run; }
     }
     PG_WAVE_SYNC();
     const int NC = NB + 1;

@@ -1090,37 +1090,41 @@ __global__ __launch_bounds__(64) void composite_bwd_kernel(const float* __restri
     float* dr = d_raw + r * S * 4;
     const float gr = d_rgb ? d_rgb[r * 3] : 0.0f, gg = d_rgb ? d_rgb[r * 3 + 1] : 0.0f, gb = d_rgb ? d_rgb[r * 3 + 2] : 0.0f;
     // pass 1: sum of the weights (for the min(.., 1) of acc_map)
-    float T = 1.0f, wsum = 0.0f;
+    // (the running transmittance, exp and sum w in double, as the forward takes them -- composite_ray, pg_kernels.hip: a float32
+    // product of 256 factors drifts by ~1e-6, and the gate below is to see the sum w whose min(.., 1) the forward returned)
+    double T = 1.0, wsum_d = 0.0;
     for (int i = 0; i < S; ++i) {
         const float delta = (i + 1 < S ? zr[i + 1] - zr[i] : 1e10f) * dn;
         const float s = actf(rw[i * 4 + 3] / density_scale + (nz ? nz[i] : 0.0f));
-        const float a = 1.0f - expf(-s * delta);
-        wsum += a * T;
-        T *= 1.0f - a + 1e-10f;
+        const double ed = exp(-(double)(s * delta));        // (exp in double, as the forward takes it)
+        wsum_d += (double)((float)(1.0 - ed) * (float)T);
+        T *= ed + 1e-10;
     }
+    const float wsum = (float)wsum_d;
     const float ga = (d_acc && wsum < 1.0f) ? d_acc[r] : 0.0f;
     // pass 2, back to front: T_i by division is unstable, so the transmittances are recomputed front to back in
     // chunks ... S <= 256: keep them in a small local array instead
     float Tl[256];
-    T = 1.0f;
+    T = 1.0;
     for (int i = 0; i < S; ++i) {
-        Tl[i] = T;
+        Tl[i] = (float)T;
         const float delta = (i + 1 < S ? zr[i + 1] - zr[i] : 1e10f) * dn;
         const float s = actf(rw[i * 4 + 3] / density_scale + (nz ? nz[i] : 0.0f));
-        T *= 1.0f - (1.0f - expf(-s * delta)) + 1e-10f;
+        T *= exp(-(double)(s * delta)) + 1e-10;
     }
     float suffix = 0.0f;        // sum_{k>i} g_k w_k
     for (int i = S - 1; i >= 0; --i) {
         const float delta = (i + 1 < S ? zr[i + 1] - zr[i] : 1e10f) * dn;
         const float pre = rw[i * 4 + 3] / density_scale + (nz ? nz[i] : 0.0f);
         const float s = actf(pre);
-        const float e = expf(-s * delta);
-        const float a = 1.0f - e;
+        const double ed = exp(-(double)(s * delta));
+        const float e = (float)ed;
+        const float a = (float)(1.0 - ed);
         const float w = a * Tl[i];
         const float sr = 1.0f / (1.0f + expf(-rw[i * 4])), sg = 1.0f / (1.0f + expf(-rw[i * 4 + 1])), sb = 1.0f / (1.0f + expf(-rw[i * 4 + 2]));
         const float k = 1.0f + 2.0f * rgb_eps;
         const float g = gr * (sr * k - rgb_eps) + gg * (sg * k - rgb_eps) + gb * (sb * k - rgb_eps) + ga;
-        const float dA = g * Tl[i] - suffix / (1.0f - a + 1e-10f);
+        const float dA = g * Tl[i] - suffix / (float)(ed + 1e-10);
         dr[i * 4] = gr * w * k * sr * (1.0f - sr);
         dr[i * 4 + 1] = gg * w * k * sg * (1.0f - sg);
         dr[i * 4 + 2] = gb * w * k * sb * (1.0f - sb);
@@ -1153,15 +1157,16 @@ __device__ __forceinline__ void composite_bwd_ray(const float* __restrict__ zr, 
         return o < S0 ? row0 + o : new0 + (o - S0);
     };
     // front to back: the transmittances and the sum of the weights (for the min(.., 1) of acc_map)
-    float T = 1.0f, wsum = 0.0f;
+    double T = 1.0, wsum_d = 0.0;
     for (int i = 0; i < S; ++i) {
         const float delta = (i + 1 < S ? zr[i + 1] - zr[i] : 1e10f) * dn;
         const float s = actf(raw[row(i) * 4 + 3] / c.density_scale + (nz ? nz[i] : 0.0f));
-        const float a = 1.0f - expf(-s * delta);
-        Tb[i * ts] = T;
-        wsum += a * T;
-        T *= 1.0f - a + 1e-10f;
+        const double ed = exp(-(double)(s * delta));
+        Tb[i * ts] = (float)T;
+        wsum_d += (double)((float)(1.0 - ed) * (float)T);
+        T *= ed + 1e-10;
     }
+    const float wsum = (float)wsum_d;
     const float ga = (has_acc && wsum < 1.0f) ? d_acc : 0.0f;
     float suffix = 0.0f;        // sum_{k>i} g_k w_k
     for (int i = S - 1; i >= 0; --i) {
@@ -1171,13 +1176,14 @@ __device__ __forceinline__ void composite_bwd_ray(const float* __restrict__ zr, 
         const float4 q = *reinterpret_cast<const float4*>(raw + rw);
         const float pre = q.w / c.density_scale + (nz ? nz[i] : 0.0f);
         const float s = actf(pre);
-        const float e = expf(-s * delta);
-        const float a = 1.0f - e;
+        const double ed = exp(-(double)(s * delta));
+        const float e = (float)ed;
+        const float a = (float)(1.0 - ed);
         const float w = a * Ti;
         const float sr = 1.0f / (1.0f + expf(-q.x)), sg = 1.0f / (1.0f + expf(-q.y)), sb = 1.0f / (1.0f + expf(-q.z));
         const float k = 1.0f + 2.0f * c.rgb_eps;
         const float g = gr * (sr * k - c.rgb_eps) + gg * (sg * k - c.rgb_eps) + gb * (sb * k - c.rgb_eps) + ga;
-        const float dA = g * Ti - suffix / (1.0f - a + 1e-10f);
+        const float dA = g * Ti - suffix / (float)(ed + 1e-10);
         const float da = dact(pre);
         float4 d = make_float4(gr * w * k * sr * (1.0f - sr), gg * w * k * sg * (1.0f - sg), gb * w * k * sb * (1.0f - sb),
                                da > 0.0f ? dA * delta * e * da / c.density_scale : 0.0f);
@@ -2117,6 +2123,51 @@ int pg_train_backward_pose(pg_handle* h, void* stream, int64_t tape_id, const fl
     if (!d_skts || reinterpret_cast<uintptr_t>(d_skts) % 16 != 0)
         return pg_fail(h, PG_EINVAL, "pg_train_backward_pose: d_skts must be a non-null, 16-byte aligned device array");
     return train_backward(h, stream, tape_id, d_rgb_map, d_acc_map, d_rgb0, d_acc0, coarse, fine, d_skts, d_pose_stride);
+}
+
+// ---- stage entry points: the two composite backward kernels on the caller's buffers, launched as train_backward launches them ----
+int pg_stage_composite_bwd(pg_handle* h, void* stream, int64_t n, int n_samples, const float* ray_batch, const float* z,
+                           const float* raw, const float* noise, const float* d_rgb, const float* d_acc, float* d_raw) {
+    using namespace pgt;
+    if (!h) return pg_fail(nullptr, PG_EINVAL, "null handle");
+    if (n < 0 || !ray_batch || !z || !raw || !d_raw) return pg_fail(h, PG_EINVAL, "pg_stage_composite_bwd: null/negative argument");
+    if (n_samples < 2 || n_samples > pg_composite_max_samples())
+        return pg_fail(h, PG_EINVAL, "pg_stage_composite_bwd: N_samples %d outside [2,%d]", n_samples, pg_composite_max_samples());
+    if (n == 0) return PG_OK;
+    PG_HIP(h, hipSetDevice(h->device));
+    const pgk::Density den = pgk::density_of(h->cfg);
+    hipLaunchKernelGGL(composite_bwd_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, static_cast<hipStream_t>(stream), ray_batch, z, raw, noise,
+                       (long long)n, n_samples, den.scale, den.rgb_eps, den.act, den.shift, d_rgb, d_acc, d_raw);
+    PG_LAUNCH_CHECK(h, "composite backward");
+    return PG_OK;
+}
+
+int pg_stage_merged_composite_bwd(pg_handle* h, void* stream, int64_t n, int n_samples, int n_importance, const float* ray_batch,
+                                  const float* z_coarse, const float* z_fine, const float* raw, const float* noise0, const float* noise1,
+                                  const int32_t* order, const float* d_rgb, const float* d_acc, const float* d_rgb0, const float* d_acc0,
+                                  float* d_raw) {
+    using namespace pgt;
+    const char* fn = "pg_stage_merged_composite_bwd";
+    if (!h) return pg_fail(nullptr, PG_EINVAL, "null handle");
+    const int S = n_samples, N = n_importance;
+    if (n < 0 || !ray_batch || !z_coarse || !raw || !d_raw) return pg_fail(h, PG_EINVAL, "%s: null/negative argument", fn);
+    if (S < 2 || S + N > pg_composite_max_samples() || N < 0 || N == 1 || N > pg_composite_max_importance())
+        return pg_fail(h, PG_EINVAL, "%s: N_samples %d / N_importance %d outside the supported range", fn, S, N);
+    if (N > 0 && S < 3) return pg_fail(h, PG_EINVAL, "%s: importance sampling needs N_samples >= 3", fn);
+    if (N > 0 && (!z_fine || !order)) return pg_fail(h, PG_EINVAL, "%s: importance samples need z_fine and order", fn);
+    if (reinterpret_cast<uintptr_t>(raw) % 16 != 0 || reinterpret_cast<uintptr_t>(d_raw) % 16 != 0)
+        return pg_fail(h, PG_EINVAL, "%s: raw and d_raw must be 16-byte aligned", fn);
+    if (n == 0) return PG_OK;
+    PG_HIP(h, hipSetDevice(h->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    PG_TRY(pg_grow(h, h->ws, h->ws_bytes, (size_t)(S + N) * (size_t)n * sizeof(float), "workspace allocation"));   // Tbuf [S + N][n]
+    PG_HIP(h, hipMemsetAsync(d_raw, 0, (size_t)n * (S + N) * 16, s));
+    const pgk::Density den = pgk::density_of(h->cfg);
+    const CBwd cb{den.scale, den.rgb_eps, den.shift, den.act};
+    hipLaunchKernelGGL(merged_composite_bwd_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, ray_batch, z_coarse, z_fine, raw, noise0, noise1,
+                       order, (long long)n, S, N, cb, d_rgb, d_acc, d_rgb0, d_acc0, d_raw, reinterpret_cast<float*>(h->ws));
+    PG_LAUNCH_CHECK(h, "merged composite backward");
+    return PG_OK;
 }
 
 }  // extern "C"

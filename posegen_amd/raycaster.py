@@ -798,6 +798,85 @@ class HipRenderer:
             o["z_fine"] = zf
         return o
 
+    def stage_sample_coarse_draws(self, ray_batch, cyls, n_samples, lindisp=False, t_rand=None, one_launch=False):
+        """stage_sample_coarse with the stratified draws t_rand [n,S] (pg_stage_sample_coarse_draws); `one_launch`: the one-launch
+        form of the kernel also for chunks of more than 256 rays."""
+        rb = _dev_f32(ray_batch, self.device)
+        n = rb.shape[0]
+        cy, cs = self._cyl_args(cyls, n)
+        tr = None if t_rand is None else _dev_f32(t_rand, self.device)
+        nf = torch.empty(n, 2, device=self.device)
+        z = torch.empty(n, n_samples, device=self.device)
+        self._check(self.lib.pg_stage_sample_coarse_draws(self.handle, self._stream(), n, _ptr(rb), _ptr(cy), cs, int(n_samples),
+                                                          (_ffi.PG_FLAG_LINDISP if lindisp else 0) | (_ffi.PG_FLAG_STAGE_ONE_LAUNCH if one_launch else 0),
+                                                          _ptr(tr), _ptr(nf), _ptr(z)))
+        return nf, z
+
+    def stage_composite_form(self, form, ray_batch, z, raw, n_importance=0, noise=None, u_rand=None, ld_new=None, fill=None):
+        """One composite launch in the named form, "plain" or "is_only" (pg_stage_composite_form): the maps, alpha, weights and, with
+        n_importance > 0, z_fine, order and (is_only) z_new [n,ld_new].  `fill`: the outputs start as this value, not uninitialised."""
+        rb, zz, rw = (_dev_f32(t, self.device) for t in (ray_batch, z, raw))
+        n, S = zz.shape
+        N = int(n_importance)
+        nz = None if noise is None else _dev_f32(noise, self.device)
+        ur = None if u_rand is None else _dev_f32(u_rand, self.device)
+        new = lambda *s, dtype=torch.float32: (torch.empty(*s, device=self.device, dtype=dtype) if fill is None
+                                               else torch.full(s, fill, device=self.device, dtype=dtype))
+        o = {"rgb_map": new(n, 3), "disp_map": new(n), "acc_map": new(n), "alpha": new(n, S), "weights": new(n, S)}
+        iso = {"plain": False, "is_only": True}[form]
+        ld = N if ld_new is None else int(ld_new)
+        if N > 0:
+            o["z_fine"], o["order"] = new(n, S + N), new(n, S + N, dtype=torch.int32)
+            if iso:
+                o["z_new"] = new(n, ld)
+        self._check(self.lib.pg_stage_composite_form(
+            self.handle, self._stream(), _ffi.PG_COMP_IS_ONLY if iso else _ffi.PG_COMP_PLAIN, n, S, N, _ptr(rb), _ptr(zz), _ptr(rw),
+            _ptr(nz), _ptr(ur), _ptr(o["rgb_map"]), _ptr(o["disp_map"]), _ptr(o["acc_map"]), _ptr(o["alpha"]), _ptr(o["weights"]),
+            _ptr(o.get("z_fine")), _ptr(o.get("order")), _ptr(o.get("z_new")), ld, None, None))
+        return o
+
+    def stage_composite_merged(self, ray_batch, z_fine, raw, raw_new, order, noise=None, fill=None):
+        """The fine pass of the single-net pair (pg_stage_composite_form, merged): z_fine [n,S+N], coarse raw [n,S,4], raw_new
+        [n,ld_new,4], order [n,S+N] int32 -> the maps, alpha and raw_out [n,S+N,4]."""
+        rb, zf, rw, rn = (_dev_f32(t, self.device) for t in (ray_batch, z_fine, raw, raw_new))
+        od = order.to(device=self.device, dtype=torch.int32).contiguous()
+        n, S, ld = rw.shape[0], rw.shape[1], rn.shape[1]
+        N = zf.shape[1] - S
+        nz = None if noise is None else _dev_f32(noise, self.device)
+        new = lambda *s: (torch.empty(*s, device=self.device) if fill is None else torch.full(s, fill, device=self.device))
+        o = {"rgb_map": new(n, 3), "disp_map": new(n), "acc_map": new(n), "alpha": new(n, S + N), "raw_out": new(n, S + N, 4)}
+        self._check(self.lib.pg_stage_composite_form(
+            self.handle, self._stream(), _ffi.PG_COMP_MERGED, n, S, N, _ptr(rb), _ptr(zf), _ptr(rw), _ptr(nz), None, _ptr(o["rgb_map"]),
+            _ptr(o["disp_map"]), _ptr(o["acc_map"]), _ptr(o["alpha"]), None, None, _ptr(od), None, ld, _ptr(rn), _ptr(o["raw_out"])))
+        return o
+
+    def stage_composite_bwd(self, ray_batch, z, raw, noise=None, d_rgb=None, d_acc=None):
+        """d_raw [n,S,4] of one composite from the cotangents of its rgb and acc maps (pg_stage_composite_bwd)."""
+        opt = lambda t: None if t is None else _dev_f32(t, self.device)
+        rb, zz, rw = (_dev_f32(t, self.device) for t in (ray_batch, z, raw))
+        nz, gr, ga = opt(noise), opt(d_rgb), opt(d_acc)
+        n, S = zz.shape
+        d_raw = torch.empty(n, S, 4, device=self.device)
+        self._check(self.lib.pg_stage_composite_bwd(self.handle, self._stream(), n, S, _ptr(rb), _ptr(zz), _ptr(rw), _ptr(nz), _ptr(gr),
+                                                    _ptr(ga), _ptr(d_raw)))
+        return d_raw
+
+    def stage_merged_composite_bwd(self, ray_batch, z, z_fine, raw, order, noise0=None, noise1=None, d_rgb=None, d_acc=None,
+                                   d_rgb0=None, d_acc0=None):
+        """d_raw [n S + n N, 4] of the single-net pair (pg_stage_merged_composite_bwd): raw holds the coarse rows [n S, 4], then the
+        new points' [n N, 4]."""
+        opt = lambda t: None if t is None else _dev_f32(t, self.device)
+        rb, zz, zf, rw = (_dev_f32(t, self.device) for t in (ray_batch, z, z_fine, raw))
+        od = order.to(device=self.device, dtype=torch.int32).contiguous()
+        n, S = zz.shape
+        N = zf.shape[1] - S
+        keep = [opt(t) for t in (noise0, noise1, d_rgb, d_acc, d_rgb0, d_acc0)]
+        d_raw = torch.empty(n * (S + N), 4, device=self.device)
+        self._check(self.lib.pg_stage_merged_composite_bwd(self.handle, self._stream(), n, S, N, _ptr(rb), _ptr(zz), _ptr(zf), _ptr(rw),
+                                                           _ptr(keep[0]), _ptr(keep[1]), _ptr(od), *[_ptr(t) for t in keep[2:]],
+                                                           _ptr(d_raw)))
+        return d_raw
+
 
 def _wave_stats(c):
     """the counters of pg_stage_eval's dbg_stage 97 as fractions; the empty-wave counts come from pg_eval16r.hip only"""
