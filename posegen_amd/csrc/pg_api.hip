@@ -194,7 +194,8 @@ Form pick_form(const CallFacts& c, const Switches& sw) {
         // the 16-bit precisions factorise the view layer over rays when a pass cannot touch more than MAXR_F rays (pg_layout.h)
         if (!(from_rays && sw.view_fact && c.S >= FACT_MIN_S)) return F_DIRECT16;
         const bool by_mode = c.onchip_mode == PG_ONCHIP_ALWAYS || (c.onchip_mode == PG_ONCHIP_AUTO && c.S <= ONCHIP_MAX_S);
-        const bool dbg_ok = !c.dbg || (c.dbg_stage == 97 && c.pose_stride == 0 && !c.fc);     // (97: the on-chip variant's limb-mask counters)
+        // (97: the on-chip variant's limb-mask counters; 99: the stamps of a PG_STAMPS build, whichever form the mode picks)
+        const bool dbg_ok = !c.dbg || c.dbg_stage == 99 || (c.dbg_stage == 97 && c.pose_stride == 0 && !c.fc);
         return by_mode && dbg_ok ? F_ONCHIP16 : F_REC16;
     }
     // PG_PREC_FP16C runs in its dedicated kernels when a ray has >= COMP_MIN_S samples (then a 128-point pass touches

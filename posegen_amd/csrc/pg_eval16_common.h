@@ -379,7 +379,9 @@ __device__ __forceinline__ void dump_frags(const EvalArgs& a, int stage, long lo
 
 
 #if defined(PG_STAMPS)
-#define PG_STAMP(k) do { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); stamps[k] = t_; } while (0)
+// (the scheduling barriers keep register-only work -- a ReLU + pack, conversions -- on its own side of the stamp: the asm's
+// memory clobber orders loads and stores only)
+#define PG_STAMP(k) do { unsigned long long t_; __builtin_amdgcn_sched_barrier(0); asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); __builtin_amdgcn_sched_barrier(0); stamps[k] = t_; } while (0)
 #else
 #define PG_STAMP(k) do {} while (0)
 #endif

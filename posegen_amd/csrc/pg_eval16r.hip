@@ -193,12 +193,45 @@ __device__ __forceinline__ void y_code16(const float* yc, uint8_t* ylds, int nrm
     }
 }
 
+// What of a B value depends on the lane alone: value i of lane group g is row k = 8 g + i of the 32 (27 used), component
+// c = k / 9, row r9 = k % 9 of the component's nine (e, sin e, cos e, .., sin 8 e, cos 8 e).  Byte g of y_lane_tab(i): bits 1-2
+// the octave f of the row (the angle is e 2^f), bit 0 the quarter-turn phase of a cosine row.  (Row 0 and the rows k >= 27 take
+// octave 0: their sine is dropped.)
+constexpr unsigned y_lane_tab(int i) {
+    unsigned w = 0u;
+    for (int g = 0; g < 4; ++g) {
+        const int k = 8 * g + i, c = (k >= 9) + (k >= 18), r9 = k - 9 * c;
+        const bool row = r9 >= 1 && k < 27;
+        w |= (unsigned)(row ? (((r9 - 1) >> 1) << 1) | ((r9 - 1) & 1) : 0) << (8 * g);
+    }
+    return w;
+}
+
+// The lane's constants are formed once per pass, in front of the limb loop (layer 0's accumulators have just died: registers are
+// free here), from the per-pass copy of the lane index, so that they are not carried through the pass; the limb body is
+// branch-free: the chunk's A fragments are read together, the MFMAs go back to back into accumulators of their own, and the
+// conversions and 16-bit stores of all tiles follow.  Value of row k, exactly: 0 for k >= 27, e_c 2 pi for r9 = 0, else
+// v_sin(fma(e_c, 2^f, phase)) with e_c in revolutions.
 template <typename V, typename ST>
 __device__ __forceinline__ void y_segment16(ST& st, int gmask, const uint8_t* ab, uint8_t* ylds, int nrm1, int wave, int lane) {
     using E = typename Op<V>::E;
+    constexpr int NQ = NTV16 / 2;          // out tiles per wave: waves w and w + 4 share a joint group
+    if ((~gmask & ((1 << JG) - 1)) == 0) return;            // no limb in range of the pass: no chunk of this segment is in its sequence
     const int g = lane >> 4, col = lane & 15;
-    const int gj = wave & 3, t0 = 4 * (wave >> 2);
+    const int gj = wave & 3, t0 = NQ * (wave >> 2);
     const uint8_t* row = ab + min(col, nrm1) * REC_AB_BYTES + (JG * gj) * 32 + 16;         // b rows of this wave's joint slots
+    uint8_t* ydst = ylds + col * REC_Y_BYTES + t0 * 1024 + (gj * 16 + 4 * g) * 16;
+    float fac[8], ph[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const unsigned t = y_lane_tab(i) >> (8 * g);
+        fac[i] = __builtin_bit_cast(float, 0x3f800000u + ((t & 6u) << 22));
+        ph[i] = (t & 1u) ? 0.25f : 0.0f;
+    }
+    // components: values 2.. of the lane group are of component min(g, 2), value 0 of component max(g - 1, 0), value 1 of the
+    // former in group 1 and of the latter in group 2 (the same in groups 0 and 3); row 0 of a component is value g of groups
+    // 0..2; k >= 27 is values 3.. of group 3
+    const bool g0 = g == 0, g1 = g == 1, g2 = g == 2, g3 = g == 3;
 #pragma clang loop unroll(full)
     for (int jj = 0; jj < JG; ++jj) {
         if ((gmask >> jj) & 1) continue;
@@ -206,30 +239,32 @@ __device__ __forceinline__ void y_segment16(ST& st, int gmask, const uint8_t* ab
 #pragma unroll
         for (int i = 0; i < ST::PER; ++i) st.piece(i);
         const float4 b = *reinterpret_cast<const float4*>(row + jj * 32);
+        V av[NQ];
+#pragma unroll
+        for (int q = 0; q < NQ; ++q)
+            av[q] = __builtin_bit_cast(V, *reinterpret_cast<const uint4*>(st.at(0, (gj * NTV16 + t0 + q) * UNIT_BYTES)));
+        __builtin_amdgcn_sched_barrier(0);      // all of the chunk's reads are out before the first wait: the row's, then one counted wait per fragment
         const float inv = __builtin_amdgcn_rsqf(fmaxf(b.x * b.x + b.y * b.y + b.z * b.z, 1e-24f)) * 0.15915494309189535f;
         const float rx = b.x * inv, ry = b.y * inv, rz = b.z * inv;       // e in revolutions
+        const float ehi = g0 ? rx : (g1 ? ry : rz), elo = g2 ? ry : (g3 ? rz : rx);
         float tv[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-            const int k = 8 * g + i;                    // 0 .. 31 (27 used): component c = k / 9, row r9 = k % 9
-            const int c = (k >= 9) + (k >= 18), r9 = k - 9 * c;
-            const float ec = c == 0 ? rx : (c == 1 ? ry : rz);
-            const int f = (r9 - 1) >> 1;
-            const float ang = ec * (float)(1 << (f < 0 ? 0 : f)) + (((r9 - 1) & 1) ? 0.25f : 0.0f);
-            const float sv = __builtin_amdgcn_sinf(ang);
-            tv[i] = k >= 27 ? 0.0f : (r9 == 0 ? ec * 6.283185307179586f : sv);
+            const float ec = i == 0 ? elo : (i == 1 ? (g1 ? ehi : elo) : ehi);
+            const float sv = __builtin_amdgcn_sinf(fmaf(ec, fac[i], ph[i]));
+            const bool row0 = i == 0 ? g0 : (i == 1 ? g1 : (i == 2 && g2));
+            tv[i] = (i >= 3 && g3) ? 0.0f : (row0 ? ec * 6.283185307179586f : sv);
         }
         const V bf = Op<V>::cvt(tv);
+        f32x4 c4[NQ];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int t = t0 + q;
-            const V av = __builtin_bit_cast(V, *reinterpret_cast<const uint4*>(st.at(0, (gj * NTV16 + t) * UNIT_BYTES)));
-            f32x4 c4 = {0.0f, 0.0f, 0.0f, 0.0f};
-            c4 = Op16<V>::mfma(av, bf, c4);
-            if (col <= nrm1) {
-                E* dst = reinterpret_cast<E*>(ylds + col * REC_Y_BYTES + t * 1024 + (gj * 16 + 4 * g) * 16 + 2 * jj);
+        for (int q = 0; q < NQ; ++q) c4[q] = Op16<V>::mfma(av[q], bf, f32x4{0.0f, 0.0f, 0.0f, 0.0f});
+        if (col <= nrm1) {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) dst[r * 8] = (E)c4[r];
+            for (int q = 0; q < NQ; ++q) {
+                E* dst = reinterpret_cast<E*>(ydst + q * 1024 + 2 * jj);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) dst[r * 8] = (E)c4[q][r];
             }
         }
     }
@@ -572,6 +607,7 @@ __global__ __launch_bounds__(NTHR, 2) void eval16r_kernel(const EvalArgs a) {
 #pragma unroll
                 for (int c = 0; c < 2; ++c) fa[u][c] = relu_pack16<V>(acc[2 * u][c], acc[2 * u + 1][c], true);
         }
+        PG_STAMP(11);
         if constexpr (OC) {
             // the view layer's direction part of this pass's rays, for the limbs in range
             y_segment16<V>(st, gmask, smem + LDSR_AB + abuf * LDS_AB_BYTES, smem + LDSR_Y, nrm1, wave, lane_p);
@@ -742,10 +778,14 @@ __global__ __launch_bounds__(NTHR, 2) void eval16r_kernel(const EvalArgs a) {
         gmask = gmask_n;
         PG_STAMP(8);
 #if defined(PG_STAMPS)
-        if (a.dbg && a.dbg_stage == 99 && lane == 0 && it < 64) {
-            for (int k = 0; k < 9; ++k) reinterpret_cast<unsigned long long*>(a.dbg)[((long long)it * NWAVE + wave) * 16 + k] = stamps[k];
-            reinterpret_cast<unsigned long long*>(a.dbg)[((long long)it * NWAVE + wave) * 16 + 9] = st.t_vm;
-            reinterpret_cast<unsigned long long*>(a.dbg)[((long long)it * NWAVE + wave) * 16 + 10] = st.t_bar;
+        {   // kept: the stamps of 1024 passes spread evenly over the launch (tools/diag_stamps.py)
+            const int every = max(1, a.n_iters / 1024), slot = it / every;
+            if (a.dbg && a.dbg_stage == 99 && lane == 0 && slot * every == it && slot < 1024) {
+                unsigned long long* rec = reinterpret_cast<unsigned long long*>(a.dbg) + ((long long)slot * NWAVE + wave) * 16;
+                for (int k = 0; k < 9; ++k) rec[k] = stamps[k];
+                rec[9] = st.t_vm; rec[10] = st.t_bar;
+                rec[11] = stamps[11];           // in front of y_segment16
+            }
             st.t_vm = 0; st.t_bar = 0;
         }
 #endif
