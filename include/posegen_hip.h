@@ -505,6 +505,63 @@ int pg_mesh_count(pg_handle* h, void* stream, const float* grid, int nx, int ny,
 int pg_mesh_emit(pg_handle* h, void* stream, const float* grid, int nx, int ny, int nz, float threshold, float clamp,
                  float* vertices, int32_t* triangles, int64_t n_vertices, int64_t n_triangles);
 
+/* ---- training batches from an image bank on the device: what BaseH5Dataset.__getitem__ + RayImageSampler + ray_collate_fn
+ * (core/dataset.py:57-105, 277-364, 756-802; core/load_data.py:71-84) produce per step on the host.  The dataset's pixels
+ * stay on the device as the uint8 they are stored as; none of the four entry points needs loaded weights, none uses atomics,
+ * and two calls on the same inputs give the same bytes.  All are asynchronous on `stream` and check their host arguments
+ * before anything is launched: PG_EINVAL, nothing launched and no output written, on a NULL required pointer, F or P not
+ * positive (P above 2^31 - 2), k outside [1, 1024], an image / camera row outside its array, a background index outside the bank.
+ *
+ * The pixel index (once per bank) replaces the per-item `np.where(sampling_mask > 0)` (dataset.py:285-287).
+ *   sampling_masks  device uint8 [F,P], P = H W; a pixel is valid when its byte is > 0
+ * pg_pixel_index_count writes counts (device int64 [F]) and keeps the per-tile prefixes in the handle;
+ * pg_pixel_index_emit, given start (device int64 [F + 1], the exclusive scan of counts with the total as last entry) and
+ * total, writes ids (device int32 [total]): image f's valid flat pixel ids, ascending, at ids[start[f] .. start[f + 1]).
+ * It is PG_ESTATE unless masks, F and P are those of the last pg_pixel_index_count on this handle; the masks must not change
+ * in between (a store never leaves image f's range if they do). */
+int pg_pixel_index_count(pg_handle* h, void* stream, const uint8_t* sampling_masks, int64_t F, int64_t P, int64_t* counts);
+int pg_pixel_index_emit(pg_handle* h, void* stream, const uint8_t* sampling_masks, int64_t F, int64_t P, const int64_t* start,
+                        int64_t total, int32_t* ids);
+
+/* np.sort(np.random.choice(valid_idxs, k, replace=False)) of dataset.py:287-290, 321 for every image of a batch: a uniformly
+ * random k-subset of the image's valid pixels, ascending.  The random numbers are the caller's, as everywhere in this ABI:
+ * draws, device float64 [n_img,k] in [0, 1).  Per image with m valid pixels, Floyd's algorithm in the order of the draws:
+ * for j = m - k .. m - 1 with u = draws[a, j - (m - k)], t = min((int64) floor(u (j + 1)), j); the rank inserted is j if t is
+ * already chosen, else t.  The chosen ranks are sorted and pixel_idxs[a, :] (device int32 [n_img,k]) = ids[start[img] + rank].
+ *   ids, start  device: the pixel index;  counts HOST int64 [F]: its counts;  img_rows HOST int32 [n_img]: the batch's
+ *   images in the given order (the same image twice is two independent rows of draws), copied into a buffer of the handle.
+ * PG_EINVAL also when k > counts[img] for an image of the batch. */
+int pg_batch_sample_pixels(pg_handle* h, void* stream, const int32_t* ids, const int64_t* start, const int64_t* counts, int64_t F,
+                           const int32_t* img_rows, int64_t n_img, int k, const double* draws, int32_t* pixel_idxs);
+
+/* The bank a batch is gathered from.  Pixel arrays are device uint8, camera arrays device float32; bkgd_idxs is a HOST array. */
+typedef struct pg_image_bank {
+    const uint8_t* imgs;        /* [F,P,3] */
+    const uint8_t* masks;       /* [F,P] (the reference's [F,P,1]) */
+    const uint8_t* bkgds;       /* [n_bkgd,P,3] or NULL: no backgrounds */
+    const int32_t* bkgd_idxs;   /* HOST [F]: the background of every image (required with bkgds) */
+    const float* c2ws;          /* [n_cam,3,4] row-major: c2w[:3,:4] */
+    const float* focals;        /* [n_cam,2]: (fx, fy) */
+    const float* centers;       /* [n_cam,2]: (cx, cy), or NULL: the frame's centre (W 0.5, H 0.5) */
+    int64_t F, P, n_bkgd, n_cam;
+    int32_t H, W;               /* H W = P */
+    int32_t mask_img;           /* target = target fg + (1 - fg) bg (dataset.py:272-273); ignored without backgrounds */
+} pg_image_bank;
+
+/* get_img_data + get_rays (dataset.py:259-275, 142-162, 346-364) and render()'s ray packing (core/trainer.py:118-137) for the
+ * n = n_img k rays of a batch: ray r = a k + b is pixel p = pixel_idxs[r] (row = p / W, col = p % W) of image img_rows[a] seen
+ * by camera cam_rows[a] (NULL: the image rows).  Device float32 outputs:
+ *   target_s [n,3] = imgs[img, p] / 255 (IEEE division; with mask_img: target fg + (1 - fg) bg, each operation rounded)
+ *   fgs [n,1] = masks[img, p];  bgs [n,3] = bkgds[bkgd_idxs[img], p] / 255 (NULL without backgrounds)
+ *   rays_o [n,3] = c2w[:3,3];  rays_d [n,3]: with x = (col - W 0.5) / fx, y = (-(row - H 0.5)) / fy (centers: x = (col - cx) / fx,
+ *   y = (-row + cy) / fy) and z = -1, rays_d[c] = (x R[c,0] + y R[c,1]) + z R[c,2], R = c2w[:3,:3] -- float32, in this order,
+ *   nothing contracted (an identity R gives the reference's shortcut bit for bit)
+ *   ray_batch [n,11] = (o, d, near 0, far 1, d / |d|)
+ * img_rows / cam_rows are HOST int32 [n_img], copied into a buffer of the handle together with the images' background rows.
+ * A pixel id outside [0, P) (the ids are device data) reads nothing: that ray's pixel values and direction are NaN. */
+int pg_batch_gather(pg_handle* h, void* stream, const pg_image_bank* bank, const int32_t* img_rows, const int32_t* cam_rows, int64_t n_img,
+                    int k, const int32_t* pixel_idxs, float* target_s, float* fgs, float* bgs, float* rays_o, float* rays_d, float* ray_batch);
+
 /* raw2outputs (nerf.py:150-205) and, if n_importance > 0, isample_from_lineseg
  * (ray_utils.py:157-201, 255-289): wave-per-ray prefix-product compositing.  The pdf follows the
  * handle: is_only weights 0.5 (max(w_l, w_k) + max(w_k, w_u)) + 0.01 with single_net. */

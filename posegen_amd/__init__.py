@@ -15,6 +15,7 @@ __version__ = "0.1.0"
 
 _TRAIN_NAMES = ("make_trainable", "TrainableRayCaster", "SingleNetTrainableRayCaster")
 _POSEOPT_NAMES = ("HipPoseOptLayer",)
+_BATCH_NAMES = ("DeviceImageBank", "ImageBatchSampler", "RayBatchSource")
 
 
 def __getattr__(name):
@@ -25,4 +26,7 @@ def __getattr__(name):
     if name in _POSEOPT_NAMES:                 # the pose layer of pose refinement (imports torch as well)
         from . import poseopt
         return getattr(poseopt, name)
+    if name in _BATCH_NAMES:                   # training batches on the device (imports torch as well)
+        from . import batches
+        return getattr(batches, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

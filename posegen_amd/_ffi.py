@@ -59,6 +59,13 @@ class PgNetGrads(C.Structure):
     _fields_ = [("w", _FP * 24), ("codes", _FP)]
 
 
+class PgImageBank(C.Structure):
+    """pg_image_bank: the device arrays a training batch is gathered from (bkgd_idxs: host)."""
+    _fields_ = [("imgs", C.c_void_p), ("masks", C.c_void_p), ("bkgds", C.c_void_p), ("bkgd_idxs", C.POINTER(C.c_int32)),
+                ("c2ws", _FP), ("focals", _FP), ("centers", _FP), ("F", C.c_int64), ("P", C.c_int64), ("n_bkgd", C.c_int64),
+                ("n_cam", C.c_int64), ("H", C.c_int32), ("W", C.c_int32), ("mask_img", C.c_int32)]
+
+
 class PgOutputs(C.Structure):
     _fields_ = [(k, _FP) for k in ("rgb_map", "disp_map", "acc_map", "alpha", "rgb0", "disp0", "acc0",
                                    "alpha0", "near_far", "z_coarse", "z_fine", "raw_coarse", "raw_fine",
@@ -154,6 +161,12 @@ PROTOTYPES = {
                                 C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "pg_mesh_emit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p,
                                C.c_void_p, C.c_int64, C.c_int64]),
+    "pg_pixel_index_count": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    "pg_pixel_index_emit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    "pg_batch_sample_pixels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int64,
+                                         C.POINTER(C.c_int32), C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
+    "pg_batch_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(PgImageBank), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int64,
+                                  C.c_int, C.c_void_p, _FP, _FP, _FP, _FP, _FP, _FP]),
     "pg_plan_frames": (C.c_int, [C.c_int, C.POINTER(C.c_int64), C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int,
                                  C.POINTER(C.c_int)]),
 }

@@ -50,6 +50,7 @@ struct pg_handle : Subject {
     void* train = nullptr;           // the training tape (pg_train.hip): activations of the last pg_train_forward
     void* mesh = nullptr;            // marching-cubes state of the last pg_mesh_count (pg_mesh.hip): flags, cases, scans
     void* poseopt = nullptr;         // the pose layer's index buffer (pg_poseopt.hip): joint tree and ray segments of the last call
+    void* batch = nullptr;           // training batches (pg_api.hip): tile offsets of the last pg_pixel_index_count, the row-upload ring
     std::vector<float> grid_t;       // pg_grid_density: the host copy of the axis table t[R] while its upload is in flight
     bool tape_out = false;           // a pg_train_forward whose backward has not run yet: the bank stays as it is until then
     // pg_render_frames: per-device buffers kept between calls (frames of H x W pixels, background, pinned staging)

@@ -51,6 +51,19 @@ struct Composite {
     float* raw_out = nullptr;
 };
 
+// One gather launch of a training batch (batch_gather_kernel, pg_batch.hip: passed by value as a kernel argument)
+struct BatchGather {
+    const uint8_t *imgs, *masks, *bkgds;    // [F,P,3], [F,P], [n_bkgd,P,3] (may be null)
+    const float *c2ws, *focals, *centers;   // [n_cam,3,4], [n_cam,2] = (fx, fy), [n_cam,2] = (cx, cy) (may be null)
+    long long P;
+    int H, W, mask_img;
+    const int* rows;                        // [3,n_img]: image row, camera row, background row of every batch image
+    long long n_img;
+    int k;
+    const int* pix;                         // [n_img k] flat pixel ids
+    float *target, *fgs, *bgs, *rays_o, *rays_d, *ray_batch;       // [n,3], [n], [n,3] (may be null), [n,3], [n,3], [n,11]
+};
+
 }  // namespace pgk
 
 extern "C" {
@@ -90,6 +103,15 @@ int pg_launch_pose_boxes(const float* kps, long long n, const double* w2c, long 
 int pg_launch_grid_rays(const float* root3, const float* t, int R, long long row0, long long rows, float* rays, float* z, void* stream);
 int pg_launch_grid_points(const float* root3, const float* t, int R, long long p0, long long n, float* pts, void* stream);
 int pg_launch_gather_sigma(const float* raw, long long n, float* sigma, void* stream);
+// ---- pg_batch.hip: training batches from an image bank on the device ----
+int pg_batch_tile_pixels(void);
+int pg_batch_max_pixels(void);
+// tile_cnt [F ceil(P / tile)]: the tiles' counts, left as each image's exclusive prefix; counts [F]
+int pg_launch_pixel_count(const uint8_t* masks, long long F, long long P, int* tile_cnt, long long* counts, void* stream);
+int pg_launch_pixel_emit(const uint8_t* masks, long long F, long long P, const int* tile_off, const long long* start, int* ids, void* stream);
+int pg_launch_sample_pixels(const int* ids, const long long* start, const int* img_rows, long long n_img, int k, const double* draws, int* pix,
+                            void* stream);
+int pg_launch_batch_gather(const pgk::BatchGather* g, void* stream);
 // ---- pg_repack.hip: packed images re-formed on the device (pg_load_weights_device) ----
 void pg_launch_collect(const float* const* tensors, const long long* off25, float* dst, void* stream);
 void pg_launch_fold(float* src, long long off_view_w, int vcols, long long off_view_b, long long off_feat_w, long long off_feat_b,
