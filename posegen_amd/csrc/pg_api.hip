@@ -9,8 +9,6 @@
 #include <chrono>
 #include <cstring>
 #include <algorithm>
-#include <mutex>
-#include <thread>
 #include <new>
 #include <utility>
 #include <vector>
@@ -27,9 +25,6 @@ using namespace pgl;
 
 thread_local char g_last_error[512] = "";      // pg_last_error(NULL): per host thread
 
-void frames_cache_release(pg_handle* h);       // per-device buffers of pg_render_frames (defined beside it)
-void batch_release(pg_handle* h);              // pixel-index state and row-upload ring of the training batches (defined beside them)
-
 }  // namespace
 
 int pg_fail(pg_handle* h, int code, const char* fmt, ...) {
@@ -43,12 +38,23 @@ int pg_fail(pg_handle* h, int code, const char* fmt, ...) {
     return code;
 }
 
-int pg_grow(pg_handle* h, uint8_t*& buf, size_t& bytes, size_t need, const char* what) {
-    if (need <= bytes) return PG_OK;
-    if (buf) { PG_HIP(h, hipDeviceSynchronize()); PG_HIP(h, hipFree(buf)); buf = nullptr; bytes = 0; }
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&buf), need);
-    if (e != hipSuccess) return pg_fail(h, PG_ENOMEM, "%s of %zu bytes failed: %s", what, need, hipGetErrorString(e));
-    bytes = need;
+int pg_grow(pg_handle* h, DevBuf& b, size_t need, const char* what, size_t alloc) {
+    if (need <= b.bytes) return PG_OK;
+    if (b.p) { PG_HIP(h, hipDeviceSynchronize()); PG_HIP(h, hipFree(b.p)); b = DevBuf(); }
+    if (alloc < need) alloc = need;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&b.p), alloc);
+    if (e != hipSuccess) { b = DevBuf(); return pg_fail(h, PG_ENOMEM, "%s of %zu bytes failed: %s", what, alloc, hipGetErrorString(e)); }
+    b.bytes = alloc;
+    return PG_OK;
+}
+
+int pg_grow_pinned(pg_handle* h, PinBuf& b, size_t need, const char* what, size_t alloc) {
+    if (need <= b.bytes) return PG_OK;
+    if (b.p) { PG_HIP(h, hipHostFree(b.p)); b = PinBuf(); }
+    if (alloc < need) alloc = need;
+    hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&b.p), alloc, hipHostMallocDefault);
+    if (e != hipSuccess) { b = PinBuf(); return pg_fail(h, PG_ENOMEM, "%s of %zu pinned bytes failed: %s", what, alloc, hipGetErrorString(e)); }
+    b.bytes = alloc;
     return PG_OK;
 }
 
@@ -260,10 +266,10 @@ constexpr int image_of(int image, int prec) { return image >= 0 && image < IMG_P
 
 int ensure_rec(pg_handle* h, int64_t n, int y_bytes) {
     const size_t need = (size_t)(n + REC_PAD_RAYS) * ((size_t)y_bytes + REC_AB_BYTES);
-    if (need <= h->rec_bytes) return PG_OK;
+    if (need <= h->rec.bytes) return PG_OK;
     PG_HIP(h, hipSetDevice(h->device));
     h->rec_pad_n = -1;
-    return pg_grow(h, h->rec, h->rec_bytes, need + need / 16, "ray record buffer");
+    return pg_grow(h, h->rec, need, "ray record buffer", need + need / 16);
 }
 
 // ---- the packed weight images of a net (NetState::img) ------------------------------------------------------------
@@ -447,9 +453,9 @@ constexpr Reformed REFORMED[] = {
 };
 
 int ensure_ws(pg_handle* h, size_t bytes) {
-    if (bytes <= h->ws_bytes) return PG_OK;
+    if (bytes <= h->ws.bytes) return PG_OK;
     PG_HIP(h, hipSetDevice(h->device));
-    return pg_grow(h, h->ws, h->ws_bytes, bytes + bytes / 8, "workspace allocation");
+    return pg_grow(h, h->ws, bytes, "workspace allocation", bytes + bytes / 8);
 }
 
 int check_ready(pg_handle* h, bool need_fine) {
@@ -530,16 +536,16 @@ int launch_eval_one(pg_handle* h, void* stream, EvalCall c) {
     a.wy = fi.wy == IMG_NONE || (fi.wy == IMG_YCODE && !fc) ? nullptr : ns.img[image_of(fi.wy, prec)].d;
     a.bias = reinterpret_cast<const float*>(ns.img[fi.bias].d);
     if (y_bytes) {
-        a.rec_y = h->rec;
-        a.rec_ab = reinterpret_cast<const float*>(h->rec + (size_t)(n + REC_PAD_RAYS) * y_bytes);
+        a.rec_y = h->rec.p;
+        a.rec_ab = reinterpret_cast<const float*>(h->rec.p + (size_t)(n + REC_PAD_RAYS) * y_bytes);
         // the padding rays behind the last record are fetched by the last passes (their values are multiplied by
         // zero weights at most): keep them finite whatever the buffer held before.  The record kernels write rays
         // < n only, so the padding of an (n, record size) pair stays zero until another pair moves it.
         // (every writer of h->rec -- the two record kernels -- stores rays < n only; anything else that is ever handed the
         // buffer must reset rec_pad_n to -1, as ensure_rec does)
         if (h->rec_pad_n != n || h->rec_pad_y != y_bytes || h->rec_pad_stream != stream) {
-            PG_HIP(h, hipMemsetAsync(h->rec + (size_t)n * y_bytes, 0, (size_t)REC_PAD_RAYS * y_bytes, static_cast<hipStream_t>(stream)));
-            PG_HIP(h, hipMemsetAsync(h->rec + (size_t)(n + REC_PAD_RAYS) * y_bytes + (size_t)n * REC_AB_BYTES, 0,
+            PG_HIP(h, hipMemsetAsync(h->rec.p + (size_t)n * y_bytes, 0, (size_t)REC_PAD_RAYS * y_bytes, static_cast<hipStream_t>(stream)));
+            PG_HIP(h, hipMemsetAsync(h->rec.p + (size_t)(n + REC_PAD_RAYS) * y_bytes + (size_t)n * REC_AB_BYTES, 0,
                                      (size_t)REC_PAD_RAYS * REC_AB_BYTES, static_cast<hipStream_t>(stream)));
             h->rec_pad_n = n; h->rec_pad_y = y_bytes; h->rec_pad_stream = stream;
         }
@@ -627,7 +633,7 @@ template <typename F> int carve_ws(pg_handle* h, F carve) {
     Carver sizes;
     carve(sizes);
     PG_TRY(ensure_ws(h, sizes.off));
-    Carver c{h->ws};
+    Carver c{h->ws.p};
     carve(c);
     return PG_OK;
 }
@@ -647,15 +653,12 @@ int pg_sc_scratch(pg_handle* h, long long n, int chunk, double** out) {
     *out = nullptr;
     const long long need = pg_sample_coarse_scratch(n, chunk);
     if (need <= 0) return PG_OK;
-    if ((size_t)need > h->sc_part_cap) {
+    const size_t bytes = (size_t)need * sizeof(double);
+    if (bytes > h->sc_part.bytes) {
         PG_HIP(h, hipSetDevice(h->device));
-        if (h->sc_part) { PG_HIP(h, hipDeviceSynchronize()); PG_HIP(h, hipFree(h->sc_part)); h->sc_part = nullptr; h->sc_part_cap = 0; }
-        const size_t want = (size_t)need * 2;
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&h->sc_part), want * sizeof(double));
-        if (e != hipSuccess) return pg_fail(h, PG_ENOMEM, "coarse sampler scratch of %zu doubles failed: %s", want, hipGetErrorString(e));
-        h->sc_part_cap = want;
+        PG_TRY(pg_grow(h, h->sc_part, bytes, "coarse sampler scratch", 2 * bytes));
     }
-    *out = h->sc_part;
+    *out = h->sc_part.as<double>();
     return PG_OK;
 }
 
@@ -705,10 +708,9 @@ int pg_create(const pg_config* cfg, int n_devices, const int* device_ids, pg_han
         delete h;
         return pg_fail(nullptr, PG_ENOMEM, "pg_create: device allocation failed");
     }
-    if (hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&h->d_pose), (24 * 16 + 8) * sizeof(float)) != hipSuccess) {
+    if (hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking) != hipSuccess) {
         pg_destroy(h);
-        return pg_fail(nullptr, PG_ENOMEM, "pg_create: stream / pose buffer creation failed");
+        return pg_fail(nullptr, PG_ENOMEM, "pg_create: stream creation failed");
     }
     // further devices: one sub-handle each (the same device may be listed twice: two workers on one GPU)
     for (int i = 1; i < n_devices; ++i) {
@@ -755,21 +757,18 @@ void pg_destroy(pg_handle* h) {
     (void)hipSetDevice(h->device);
     (void)hipDeviceSynchronize();
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
-    if (h->d_pose) (void)hipFree(h->d_pose);
-    if (h->fws) (void)hipFree(h->fws);
-    if (h->rec) (void)hipFree(h->rec);
-    if (h->sc_part) (void)hipFree(h->sc_part);
+    for (DevBuf* b : {&h->fws, &h->rec, &h->sc_part}) pg_release(*b);
     pg_train_release(h);
     pg_mesh_release(h);
     pg_poseopt_release(h);
-    batch_release(h);
-    frames_cache_release(h);
+    pg_batch_release(h);
+    pg_frames_release(h);
     for (auto& pr : h->ev_aux) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
     release_subject(*h);
     for (Subject& sub : h->bank.parked) release_subject(sub);
     for (auto& pr : h->ev_used) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
     for (auto& ev : h->ev_free) (void)hipEventDestroy(ev);
-    if (h->ws) (void)hipFree(h->ws);
+    pg_release(h->ws);
     delete h;
 }
 
@@ -1239,7 +1238,7 @@ int pg_calibrate_mfma(pg_handle* h, int f16, int lds_fed, double min_ms, double*
     hipError_t herr = hipSuccess;
     for (int round = 0; round < 6; ++round) {           // grow until one launch lasts min_ms: the clock settles in ms
         (void)hipEventRecord(e0, s);
-        err = pg_launch_mfma_rate(f16, lds_fed, blocks, iters, reinterpret_cast<float*>(h->ws), s);
+        err = pg_launch_mfma_rate(f16, lds_fed, blocks, iters, h->ws.as<float>(), s);
         (void)hipEventRecord(e1, s);
         if (err) break;
         herr = hipEventSynchronize(e1);
@@ -1309,9 +1308,9 @@ int pg_query_density(pg_handle* h, void* stream, int which, int64_t n_points, co
     // one pseudo ray (o = d = 0) that owns all points: the kernels take the pose and the view table
     // from the ray slot, the position from `pts`
     PG_TRY(ensure_ws(h, 256));
-    PG_HIP(h, hipMemsetAsync(h->ws, 0, 64, static_cast<hipStream_t>(stream)));
+    PG_HIP(h, hipMemsetAsync(h->ws.p, 0, 64, static_cast<hipStream_t>(stream)));
     EvalCall c;
-    c.which = which; c.n = 1; c.S = (int)n_points; c.rays = reinterpret_cast<const float*>(h->ws); c.skts = skts; c.raw = raw; c.points = pts;
+    c.which = which; c.n = 1; c.S = (int)n_points; c.rays = h->ws.as<const float>(); c.skts = skts; c.raw = raw; c.points = pts;
     return launch_eval(h, stream, c);
 }
 
@@ -1611,121 +1610,6 @@ int pg_pose_kinematics(pg_handle* h, void* stream, int64_t n_poses, const double
     return PG_OK;
 }
 
-// ---- frame front / back end: helpers shared by pg_render_frame (one device) and pg_render_frames ----
-namespace {
-
-struct FrameMaps { float *rgb_map, *disp_map, *acc_map; };      // [n_box,3], [n_box], [n_box]: the whole box
-
-int frame_geom(pg_handle* h, int H, int W, const float* c2w, const float* intrinsics, const int* box, float near,
-               float far, float cam, pgk::FrameGeom* g) {
-    if (H <= 0 || W <= 0 || !c2w || !intrinsics || !box) return pg_fail(h, PG_EINVAL, "frame: null/non-positive argument");
-    g->H = H; g->W = W;
-    g->tlx = box[0] < 0 ? 0 : box[0]; g->tly = box[1] < 0 ? 0 : box[1];
-    const int brx = box[2] > W ? W : box[2], bry = box[3] > H ? H : box[3];
-    g->bw = brx > g->tlx ? brx - g->tlx : 0; g->bh = bry > g->tly ? bry - g->tly : 0;
-    g->fx = intrinsics[0]; g->fy = intrinsics[1]; g->cx = intrinsics[2]; g->cy = intrinsics[3];
-    for (int r = 0; r < 3; ++r) {
-        for (int c = 0; c < 3; ++c) g->R[3 * r + c] = c2w[4 * r + c];
-        g->t[r] = c2w[4 * r + 3];
-    }
-    g->near = near; g->far = far; g->cam = cam;
-    return PG_OK;
-}
-
-// Frame workspace of `h`: ray_batch rows and cams of a range of n_range rays, the maps of a WHOLE box of
-// n rays (n = 0: none -- the range's maps live in a buffer of the caller), coarse-pass scratch of the range.
-int frame_ws(pg_handle* h, int64_t n, int64_t n_range, float** rays, float** cams, FrameMaps* maps, pg_outputs* scratch) {
-    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-    const size_t b_rays = al((size_t)n_range * 44), b_cam = al((size_t)n_range * 4);
-    const size_t b_rgb = al((size_t)n * 12), b_1 = al((size_t)n * 4), r_rgb = al((size_t)n_range * 12), r_1 = al((size_t)n_range * 4);
-    const size_t need = b_rays + b_cam + b_rgb + 2 * b_1 + r_rgb + 2 * r_1;
-    if (need > h->fws_bytes) {
-        if (h->fws) { PG_HIP(h, hipDeviceSynchronize()); PG_HIP(h, hipFree(h->fws)); h->fws = nullptr; h->fws_bytes = 0; }
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&h->fws), need + need / 8);
-        if (e != hipSuccess) return pg_fail(h, PG_ENOMEM, "frame workspace allocation of %zu bytes failed", need);
-        h->fws_bytes = need + need / 8;
-    }
-    uint8_t* p = h->fws;
-    *rays = reinterpret_cast<float*>(p); p += b_rays;
-    *cams = reinterpret_cast<float*>(p); p += b_cam;
-    maps->rgb_map = reinterpret_cast<float*>(p); p += b_rgb;
-    maps->disp_map = reinterpret_cast<float*>(p); p += b_1;
-    maps->acc_map = reinterpret_cast<float*>(p); p += b_1;
-    scratch->rgb0 = reinterpret_cast<float*>(p); p += r_rgb;
-    scratch->disp0 = reinterpret_cast<float*>(p); p += r_1;
-    scratch->acc0 = reinterpret_cast<float*>(p);
-    return PG_OK;
-}
-
-// rays [r0, r1) of the box (row-major ray list of kp_to_valid_rays).  r0 must be a multiple of the nanmean
-// group size (`chunk`) unless it is 0, so that the groups are those of the whole frame.  ext == nullptr:
-// the maps of the whole box are carved from the frame workspace and the range is written at its offset
-// (returned in *maps); otherwise the range's maps go to ext (rgb [r1-r0,3], disp, acc [r1-r0]).
-int frame_render_range(pg_handle* h, void* stream, const pgk::FrameGeom& g, int64_t r0, int64_t r1, const float* skts,
-                       const float* cyl, int n_samples, int n_importance, int flags, FrameMaps* maps, const FrameMaps* ext = nullptr) {
-    const int64_t n = (int64_t)g.bw * g.bh;
-    if (r0 < 0 || r1 > n || r0 > r1) return pg_fail(h, PG_EINVAL, "frame range [%lld, %lld) outside the box of %lld rays", (long long)r0, (long long)r1, (long long)n);
-    if (r0 % h->cfg.chunk != 0) return pg_fail(h, PG_EINVAL, "frame range must start on a nanmean group boundary (chunk %d)", h->cfg.chunk);
-    PG_HIP(h, hipSetDevice(h->device));
-    float *rays, *cams;
-    pg_outputs out{};
-    FrameMaps own{};
-    PG_TRY(frame_ws(h, ext ? 0 : n, r1 - r0, &rays, &cams, &own, &out));
-    if (maps) *maps = ext ? *ext : own;
-    if (r1 == r0) return PG_OK;
-    if (ext) { out.rgb_map = ext->rgb_map; out.disp_map = ext->disp_map; out.acc_map = ext->acc_map; }
-    else { out.rgb_map = own.rgb_map + r0 * 3; out.disp_map = own.disp_map + r0; out.acc_map = own.acc_map + r0; }
-    const bool fc = h->cfg.framecode_ch > 0;
-    PG_TRY_LAUNCH(h, "frame ray kernel", pg_launch_frame_rays(&g, r0, r1 - r0, rays, fc ? cams : nullptr, stream));
-    return pg_render_rays(h, stream, r1 - r0, rays, skts, 0, cyl, 0, fc ? cams : nullptr, n_samples, n_importance, flags, &out);
-}
-
-int frame_compose(pg_handle* h, void* stream, const pgk::FrameGeom& g, const FrameMaps& maps, const float* bg, float base_bg,
-                  float* rgb, float* disp, float* acc, uint8_t* rgb8) {
-    PG_TRY_LAUNCH(h, "frame compose kernel", pg_launch_frame_compose(&g, maps.rgb_map, maps.disp_map, maps.acc_map, bg, base_bg, rgb, disp, acc, rgb8, stream));
-    return PG_OK;
-}
-
-}  // namespace
-
-int pg_render_frame(pg_handle* h, void* stream, int H, int W, const float* c2w, const float* intrinsics,
-                    const int* box, float near, float far, const float* skts, const float* cyl, float cam,
-                    int n_samples, int n_importance, int flags, const float* bg, float base_bg,
-                    float* rgb, float* disp, float* acc, uint8_t* rgb8) {
-    if (!h) return pg_fail(nullptr, PG_EINVAL, "null handle");
-    if (!skts || !cyl || !rgb) return pg_fail(h, PG_EINVAL, "pg_render_frame: null argument");
-    pgk::FrameGeom g{};
-    PG_TRY(frame_geom(h, H, W, c2w, intrinsics, box, near, far, cam, &g));
-    FrameMaps maps{};
-    PG_TRY(frame_render_range(h, stream, g, 0, (int64_t)g.bw * g.bh, skts, cyl, n_samples, n_importance, flags, &maps));
-    return frame_compose(h, stream, g, maps, bg, base_bg, rgb, disp, acc, rgb8);
-}
-
-int pg_render_frame_range(pg_handle* h, void* stream, int H, int W, const float* c2w, const float* intrinsics,
-                          const int* box, float near, float far, const float* skts, const float* cyl, float cam,
-                          int n_samples, int n_importance, int flags, int64_t ray_begin, int64_t ray_end,
-                          float* rgb_map, float* disp_map, float* acc_map) {
-    if (!h) return pg_fail(nullptr, PG_EINVAL, "null handle");
-    if (!skts || !cyl || !rgb_map || !disp_map || !acc_map) return pg_fail(h, PG_EINVAL, "pg_render_frame_range: null argument");
-    pgk::FrameGeom g{};
-    PG_TRY(frame_geom(h, H, W, c2w, intrinsics, box, near, far, cam, &g));
-    const FrameMaps ext{rgb_map, disp_map, acc_map};
-    return frame_render_range(h, stream, g, ray_begin, ray_end, skts, cyl, n_samples, n_importance, flags, nullptr, &ext);
-}
-
-int pg_compose_frame(pg_handle* h, void* stream, int H, int W, const int* box, const float* rgb_map, const float* disp_map,
-                     const float* acc_map, const float* bg, float base_bg, float* rgb, float* disp, float* acc, uint8_t* rgb8) {
-    if (!h) return pg_fail(nullptr, PG_EINVAL, "null handle");
-    if (H <= 0 || W <= 0 || !box || !rgb) return pg_fail(h, PG_EINVAL, "pg_compose_frame: null/non-positive argument");
-    pgk::FrameGeom g{};
-    const float c2w[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0}, intr[4] = {1.f, 1.f, 0.f, 0.f};
-    PG_TRY(frame_geom(h, H, W, c2w, intr, box, 0.f, 1.f, -1.f, &g));
-    if ((int64_t)g.bw * g.bh > 0 && (!rgb_map || !disp_map || !acc_map)) return pg_fail(h, PG_EINVAL, "pg_compose_frame: null map of a non-empty box");
-    PG_HIP(h, hipSetDevice(h->device));
-    const FrameMaps maps{const_cast<float*>(rgb_map), const_cast<float*>(disp_map), const_cast<float*>(acc_map)};
-    return frame_compose(h, stream, g, maps, bg, base_bg, rgb, disp, acc, rgb8);
-}
-
 int pg_pose_boxes(pg_handle* h, void* stream, int64_t n_poses, const float* kps, const double* w2c, int64_t w2c_stride,
                   const double* ring, double extension, double top_extension, double bot_extension, double fx, double fy,
                   int H, int W, int off_x, int off_y, float* cyls, int32_t* boxes) {
@@ -1740,572 +1624,5 @@ int pg_pose_boxes(pg_handle* h, void* stream, int64_t n_poses, const float* kps,
 }
 
 int pg_device_count(const pg_handle* h) { return h ? 1 + (int)h->peers.size() : 0; }
-
-// ---- in-process multi-device frame rendering -------------------------------------------------------
-namespace {
-
-struct FrameTask { int frame; int64_t r0, r1; int worker; int owner; };
-
-// Work plan of a frame batch on G workers (the call pattern of run_gan.py:2042-2047 is
-// 20 frames per call: whole frames alone would leave 3:2 loads on 8 GPUs).  The unit of work is a nanmean
-// group (`chunk` consecutive rays of a frame's box).  Frames go to workers whole, largest first, to the
-// least loaded worker, as long as they fit under the per-worker target (total rays / G, 2 % slack); the
-// frames that do not fit (the tail of a batch with F mod G != 0, or every frame when F < G) are cut into
-// contiguous runs of whole groups that fill the least loaded workers up to the target.  Every cut falls
-// on a multiple of `chunk`, so every group is rendered exactly as on one device.  A cut frame is composed
-// by its owner (the worker of its first run).  Deterministic; dist.plan_tasks is the same algorithm.
-void plan_frames(const std::vector<int64_t>& n_rays, int G, int chunk, std::vector<FrameTask>* tasks) {
-    const int F = (int)n_rays.size();
-    tasks->clear();
-    if (F == 0) return;
-    std::vector<int> order(F);
-    for (int f = 0; f < F; ++f) order[f] = f;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return n_rays[a] > n_rays[b]; });
-    int64_t total = 0;
-    for (int64_t n : n_rays) total += n > 0 ? n : 0;
-    const int64_t target = (total + G - 1) / G;
-    std::vector<int64_t> load(G, 0);
-    auto least = [&] {
-        int w = 0;
-        for (int k = 1; k < G; ++k) if (load[k] < load[w]) w = k;
-        return w;
-    };
-    std::vector<int> tail;
-    for (int f : order) {
-        const int w = least();
-        if (n_rays[f] <= chunk || load[w] + n_rays[f] <= target + target / 50) {
-            load[w] += n_rays[f] > 0 ? n_rays[f] : 0;
-            tasks->push_back({f, 0, n_rays[f] > 0 ? n_rays[f] : 0, w, w});
-        } else {
-            tail.push_back(f);
-        }
-    }
-    for (int f : tail) {
-        const int64_t groups = (n_rays[f] + chunk - 1) / chunk;
-        int64_t g = 0;
-        int owner = -1;
-        while (g < groups) {
-            const int w = least();
-            const int64_t cap = target - load[w];
-            int64_t take = cap > 0 ? (cap + chunk / 2) / chunk : 0;     // nearest whole number of groups
-            if (take < 1) take = 1;
-            if (take > groups - g) take = groups - g;
-            const int64_t rest = groups - g - take;
-            if (rest > 0 && rest * chunk <= std::max<int64_t>(chunk, target / 32)) take += rest;   // no sliver of a run for yet another worker
-            const int64_t r0 = g * chunk, r1 = std::min((g + take) * chunk, n_rays[f]);
-            if (owner < 0) owner = w;
-            if (!tasks->empty() && tasks->back().frame == f && tasks->back().worker == w && tasks->back().r1 == r0) tasks->back().r1 = r1;
-            else tasks->push_back({f, r0, r1, w, owner});
-            load[w] += r1 - r0;
-            g += take;
-        }
-    }
-}
-
-}  // namespace
-
-int pg_plan_frames(int n_frames, const int64_t* n_rays, int n_workers, int chunk, int32_t* out_tasks /*[cap,5]*/, int cap, int* n_tasks) {
-    if (n_frames < 0 || !n_rays || n_workers < 1 || chunk < 1 || !n_tasks) return pg_fail(nullptr, PG_EINVAL, "pg_plan_frames: bad argument");
-    std::vector<FrameTask> t;
-    plan_frames(std::vector<int64_t>(n_rays, n_rays + n_frames), n_workers, chunk, &t);
-    *n_tasks = (int)t.size();
-    if (out_tasks) {
-        if ((int)t.size() > cap) return pg_fail(nullptr, PG_EINVAL, "pg_plan_frames: %zu tasks exceed the capacity %d", t.size(), cap);
-        for (size_t i = 0; i < t.size(); ++i) {
-            out_tasks[5 * i] = t[i].frame; out_tasks[5 * i + 1] = (int32_t)t[i].r0; out_tasks[5 * i + 2] = (int32_t)t[i].r1;
-            out_tasks[5 * i + 3] = t[i].worker; out_tasks[5 * i + 4] = t[i].owner;
-        }
-    }
-    return PG_OK;
-}
-
-// ---- pg_render_frames: per-device resources kept on the handle between calls -----------------------------------
-}  // extern "C"
-
-namespace {
-
-constexpr int NBUF = pg_handle::FramesCache::NBUF;
-
-void frames_cache_release(pg_handle* h) {
-    auto& c = h->fc;
-    (void)hipSetDevice(h->device);
-    for (int b = 0; b < NBUF; ++b) {
-        if (c.d_frame[b]) (void)hipFree(c.d_frame[b]);
-        if (c.copied[b]) (void)hipEventDestroy(c.copied[b]);
-        if (c.composed[b]) (void)hipEventDestroy(c.composed[b]);
-        c.d_frame[b] = nullptr; c.copied[b] = nullptr; c.composed[b] = nullptr;
-    }
-    if (c.copy_stream) (void)hipStreamDestroy(c.copy_stream);
-    if (c.d_bg) (void)hipFree(c.d_bg);
-    if (c.d_poses) (void)hipFree(c.d_poses);
-    if (c.d_part) (void)hipFree(c.d_part);
-    if (c.h_stage) (void)hipHostFree(c.h_stage);
-    c = pg_handle::FramesCache();
-}
-
-// bytes of one frame buffer: rgb [hw,3] | disp [hw] | acc [hw] floats, then the uint8 frame
-size_t frame_bytes(size_t hw) { return hw * 20 + ((hw * 3 + 255) & ~size_t(255)); }
-
-// grow-only: nothing is allocated or freed by a call whose sizes an earlier call has seen
-int frames_cache_ensure(pg_handle* h, size_t hw, int n_frames, size_t part_rays, const float* bg_host, bool staged) {
-    auto& c = h->fc;
-    PG_HIP(h, hipSetDevice(h->device));
-    if (!c.copy_stream) PG_HIP(h, hipStreamCreateWithFlags(&c.copy_stream, hipStreamNonBlocking));
-    for (int b = 0; b < NBUF; ++b) {
-        if (!c.copied[b]) PG_HIP(h, hipEventCreateWithFlags(&c.copied[b], hipEventDisableTiming));
-        if (!c.composed[b]) PG_HIP(h, hipEventCreateWithFlags(&c.composed[b], hipEventDisableTiming));
-    }
-    if (hw > c.hw) {
-        PG_HIP(h, hipDeviceSynchronize());
-        for (int b = 0; b < NBUF; ++b) {
-            if (c.d_frame[b]) { PG_HIP(h, hipFree(c.d_frame[b])); c.d_frame[b] = nullptr; }
-            hipError_t e = hipMalloc(reinterpret_cast<void**>(&c.d_frame[b]), frame_bytes(hw));
-            if (e != hipSuccess) { c.hw = 0; return pg_fail(h, PG_ENOMEM, "frame buffer of %zu bytes failed: %s", frame_bytes(hw), hipGetErrorString(e)); }
-        }
-        c.hw = hw;
-    }
-    if (bg_host) {
-        if (hw > c.bg_hw) {
-            PG_HIP(h, hipDeviceSynchronize());
-            if (c.d_bg) { PG_HIP(h, hipFree(c.d_bg)); c.d_bg = nullptr; c.bg_hw = 0; }
-            PG_HIP(h, hipMalloc(reinterpret_cast<void**>(&c.d_bg), hw * 12));
-            c.bg_hw = hw;
-        }
-        PG_HIP(h, hipMemcpy(c.d_bg, bg_host, hw * 12, hipMemcpyHostToDevice));
-    }
-    if ((size_t)n_frames > c.poses_cap) {
-        PG_HIP(h, hipDeviceSynchronize());
-        if (c.d_poses) { PG_HIP(h, hipFree(c.d_poses)); c.d_poses = nullptr; c.poses_cap = 0; }
-        const size_t cap = (size_t)n_frames + (size_t)n_frames / 2 + 8;
-        PG_HIP(h, hipMalloc(reinterpret_cast<void**>(&c.d_poses), cap * (384 + 8) * sizeof(float)));
-        c.poses_cap = cap;
-    }
-    if (part_rays > c.part_cap) {
-        PG_HIP(h, hipDeviceSynchronize());
-        if (c.d_part) { PG_HIP(h, hipFree(c.d_part)); c.d_part = nullptr; c.part_cap = 0; }
-        const size_t cap = part_rays + part_rays / 4;
-        PG_HIP(h, hipMalloc(reinterpret_cast<void**>(&c.d_part), cap * 20));
-        c.part_cap = cap;
-    }
-    if (staged && NBUF * frame_bytes(hw) > c.stage_bytes) {
-        PG_HIP(h, hipDeviceSynchronize());
-        if (c.h_stage) { PG_HIP(h, hipHostFree(c.h_stage)); c.h_stage = nullptr; c.stage_bytes = 0; }
-        PG_HIP(h, hipHostMalloc(&c.h_stage, NBUF * frame_bytes(hw), hipHostMallocDefault));
-        c.stage_bytes = NBUF * frame_bytes(hw);
-    }
-    return PG_OK;
-}
-
-// page-locked host memory (hipHostMalloc / hipHostRegister, e.g. a torch tensor with pin_memory=True)?
-bool host_pinned(const void* p) {
-    if (!p) return true;
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return a.type == hipMemoryTypeHost;
-}
-
-// Output pipeline of one worker: frame k of the worker composes into device buffer k % NBUF on the render stream
-// while frame k - 1 is copied to the host on the copy stream; nothing blocks the host thread before the call's end
-// (results in pageable memory go through pinned staging and are moved by the worker thread one frame later).
-struct FrameOut {
-    pg_handle* h;
-    hipStream_t st;
-    size_t hw;
-    float* rgbs; float* disps; float* accs; uint8_t* rgb8;
-    bool staged;
-    const float* d_bg;
-    float base_bg;
-    int k = 0;
-    int pend[NBUF];
-    FrameOut(pg_handle* h_, hipStream_t st_, size_t hw_, float* r, float* d, float* a, uint8_t* u8, bool stg, const float* bg, float bb)
-        : h(h_), st(st_), hw(hw_), rgbs(r), disps(d), accs(a), rgb8(u8), staged(stg), d_bg(bg), base_bg(bb) {
-        for (int b = 0; b < NBUF; ++b) pend[b] = -1;
-    }
-    uint8_t* stage(int b) const { return static_cast<uint8_t*>(h->fc.h_stage) + (size_t)b * frame_bytes(hw); }
-    int drain(int b) {              // the staged frame of buffer b -> the caller's (pageable) arrays
-        const int f = pend[b];
-        if (f < 0) return PG_OK;
-        PG_HIP(h, hipEventSynchronize(h->fc.copied[b]));
-        const uint8_t* sp = stage(b);
-        if (rgbs) std::memcpy(rgbs + (size_t)f * hw * 3, sp, hw * 12);
-        if (disps) std::memcpy(disps + (size_t)f * hw, sp + hw * 12, hw * 4);
-        if (accs) std::memcpy(accs + (size_t)f * hw, sp + hw * 16, hw * 4);
-        if (rgb8) std::memcpy(rgb8 + (size_t)f * hw * 3, sp + hw * 20, hw * 3);
-        pend[b] = -1;
-        return PG_OK;
-    }
-    int put(int f, const pgk::FrameGeom& g, const FrameMaps& maps) {
-        auto& c = h->fc;
-        const int b = k++ % NBUF;
-        if (staged) PG_TRY(drain(b));
-        PG_HIP(h, hipStreamWaitEvent(st, c.copied[b], 0));          // buffer b's previous copy-out (no-op before the first)
-        uint8_t* base = reinterpret_cast<uint8_t*>(c.d_frame[b]);
-        float* d_rgb = reinterpret_cast<float*>(base);
-        float* d_disp = reinterpret_cast<float*>(base + hw * 12);
-        float* d_acc = reinterpret_cast<float*>(base + hw * 16);
-        uint8_t* d_u8 = rgb8 ? base + hw * 20 : nullptr;
-        PG_TRY(frame_compose(h, st, g, maps, d_bg, base_bg, d_rgb, d_disp, d_acc, d_u8));
-        PG_HIP(h, hipEventRecord(c.composed[b], st));
-        PG_HIP(h, hipStreamWaitEvent(c.copy_stream, c.composed[b], 0));
-        uint8_t* sp = staged ? stage(b) : nullptr;
-        if (rgbs) PG_HIP(h, hipMemcpyAsync(staged ? (void*)sp : (void*)(rgbs + (size_t)f * hw * 3), d_rgb, hw * 12, hipMemcpyDeviceToHost, c.copy_stream));
-        if (disps) PG_HIP(h, hipMemcpyAsync(staged ? (void*)(sp + hw * 12) : (void*)(disps + (size_t)f * hw), d_disp, hw * 4, hipMemcpyDeviceToHost, c.copy_stream));
-        if (accs) PG_HIP(h, hipMemcpyAsync(staged ? (void*)(sp + hw * 16) : (void*)(accs + (size_t)f * hw), d_acc, hw * 4, hipMemcpyDeviceToHost, c.copy_stream));
-        if (rgb8) PG_HIP(h, hipMemcpyAsync(staged ? (void*)(sp + hw * 20) : (void*)(rgb8 + (size_t)f * hw * 3), d_u8, hw * 3, hipMemcpyDeviceToHost, c.copy_stream));
-        PG_HIP(h, hipEventRecord(c.copied[b], c.copy_stream));
-        if (staged) pend[b] = f;
-        return PG_OK;
-    }
-    int finish() {
-        if (staged)
-            for (int b = 0; b < NBUF; ++b) PG_TRY(drain(b));
-        PG_HIP(h, hipStreamSynchronize(h->fc.copy_stream));
-        return PG_OK;
-    }
-};
-
-}  // namespace
-
-extern "C" {
-
-int pg_render_frames(pg_handle* h, int n_frames, int H, int W, const float* c2ws, const float* intrinsics, const int* boxes,
-                     float near, float far, const float* skts, const float* cyls, const float* cams, int n_samples,
-                     int n_importance, int flags, const float* bg, float base_bg, float* rgbs, float* disps, float* accs,
-                     uint8_t* rgb8) {
-    return pg_render_frames_subjects(h, n_frames, H, W, c2ws, intrinsics, boxes, near, far, skts, cyls, cams, n_samples, n_importance,
-                                     flags, bg, base_bg, rgbs, disps, accs, rgb8, nullptr);
-}
-
-int pg_render_frames_subjects(pg_handle* h, int n_frames, int H, int W, const float* c2ws, const float* intrinsics, const int* boxes,
-                              float near, float far, const float* skts, const float* cyls, const float* cams, int n_samples,
-                              int n_importance, int flags, const float* bg, float base_bg, float* rgbs, float* disps, float* accs,
-                              uint8_t* rgb8, const int32_t* subjects) {
-    if (!h) return pg_fail(nullptr, PG_EINVAL, "null handle");
-    if (n_frames < 0 || H <= 0 || W <= 0 || !c2ws || !intrinsics || !boxes || !skts || !cyls || (!rgbs && !rgb8))
-        return pg_fail(h, PG_EINVAL, "pg_render_frames: null/negative argument");
-    if (n_frames == 0) return PG_OK;
-    if (subjects) {
-        if (h->tape_out) return pg_fail(h, PG_EINVAL, "pg_render_frames_subjects: a training tape is outstanding (run its backward first)");
-        for (int f = 0; f < n_frames; ++f)
-            if (subjects[f] < 0 || subjects[f] >= bank_count(h->bank))
-                return pg_fail(h, PG_EINVAL, "pg_render_frames_subjects: frame %d names subject %d of %d", f, subjects[f], bank_count(h->bank));
-    }
-    const int active0 = h->bank.active;         // (every device's: pg_select_subject reaches them all)
-    // Worker 0 runs on the primary handle's own stream over the primary's workspaces: everything the caller
-    // queued on ITS stream (pg_render_rays / pg_render_frame are asynchronous and use the same buffers) must
-    // have finished first.  The call is synchronous anyway.
-    PG_HIP(h, hipSetDevice(h->device));
-    PG_HIP(h, hipDeviceSynchronize());
-    std::vector<pg_handle*> wk;
-    wk.push_back(h);
-    for (pg_handle* s : h->peers) wk.push_back(s);
-    const int G = (int)wk.size();
-    const size_t hw = (size_t)H * W;
-    std::vector<pgk::FrameGeom> geo(n_frames);
-    std::vector<int64_t> nr(n_frames);
-    for (int f = 0; f < n_frames; ++f) {
-        PG_TRY(frame_geom(h, H, W, c2ws + 12 * f, intrinsics + 4 * f, boxes + 4 * f, near, far, cams ? cams[f] : -1.0f, &geo[f]));
-        nr[f] = (int64_t)geo[f].bw * geo[f].bh;
-    }
-    std::vector<FrameTask> tasks;
-    plan_frames(nr, G, h->cfg.chunk, &tasks);
-    auto whole = [&](const FrameTask& tk) { return tk.r0 == 0 && tk.r1 == nr[tk.frame]; };
-    // Everything a worker needs is set up BEFORE its first launch and kept on its handle between calls (no allocation
-    // in a call whose sizes have been seen): the poses of all frames (one upload), two frame buffers in rotation, the
-    // background, one buffer for the packed maps of the cut-frame ranges it renders, pinned staging when the
-    // caller's result arrays are pageable.
-    const bool staged = !(host_pinned(rgbs) && host_pinned(disps) && host_pinned(accs) && host_pinned(rgb8));
-    std::vector<size_t> part_off(tasks.size(), 0), part_rays(G, 0);
-    std::vector<char> composes(G, 0);
-    for (size_t t = 0; t < tasks.size(); ++t) {
-        const FrameTask& tk = tasks[t];
-        if (whole(tk)) { composes[tk.worker] = 1; continue; }
-        composes[tk.owner] = 1;
-        part_off[t] = part_rays[tk.worker];
-        part_rays[tk.worker] += (size_t)(tk.r1 - tk.r0);
-    }
-    for (int k = 0; k < G; ++k) {
-        const int rc = frames_cache_ensure(wk[k], composes[k] ? hw : 0, n_frames, part_rays[k], composes[k] ? bg : nullptr, staged && composes[k]);
-        if (rc) { (void)hipSetDevice(h->device); return wk[k] == h ? rc : pg_fail(h, rc, "device %d: %s", wk[k]->device, wk[k]->err); }
-    }
-    struct Worker { pg_handle* h; int rc = PG_OK; };
-    std::vector<Worker> ws(G);
-    for (int k = 0; k < G; ++k) ws[k].h = wk[k];
-    std::vector<FrameMaps> maps_of(tasks.size());
-    std::vector<FrameOut> outs;
-    outs.reserve(G);
-    for (int k = 0; k < G; ++k)
-        outs.emplace_back(wk[k], wk[k]->own_stream, hw, rgbs, disps, accs, rgb8, staged, bg ? wk[k]->fc.d_bg : nullptr, base_bg);
-
-    auto checker = [&](Worker& w) {
-        return [&w](hipError_t e, const char* what) {
-            if (e != hipSuccess && w.rc == PG_OK) w.rc = pg_fail(w.h, PG_EHIP, "%s failed on device %d: %s", what, w.h->device, hipGetErrorString(e));
-            return e == hipSuccess;
-        };
-    };
-    // phase A: every worker renders its tasks; whole frames are composed and handed to the output pipeline at once,
-    // the runs of cut frames stay in the worker's range buffer for the owner
-    auto phase_a = [&](int k) {
-        Worker& w = ws[k];
-        pg_handle* hh = w.h;
-        auto check = checker(w);
-        if (!check(hipSetDevice(hh->device), "hipSetDevice")) return;
-        hipStream_t st = hh->own_stream;
-        float* d_skts = hh->fc.d_poses;
-        float* d_cyls = hh->fc.d_poses + (size_t)n_frames * 384;
-        // (pageable sources: the runtime stages them before the calls return; the kernels are ordered behind on `st`)
-        if (!check(hipMemcpyAsync(d_skts, skts, (size_t)n_frames * 384 * sizeof(float), hipMemcpyHostToDevice, st), "pose upload")) return;
-        if (!check(hipMemcpyAsync(d_cyls, cyls, (size_t)n_frames * 5 * sizeof(float), hipMemcpyHostToDevice, st), "cylinder upload")) return;
-        for (size_t t = 0; t < tasks.size() && w.rc == PG_OK; ++t) {
-            const FrameTask& tk = tasks[t];
-            if (tk.worker != k) continue;
-            const int f = tk.frame;
-            // this device's own selection (each worker thread touches its own handle only): a pointer swap between two enqueues
-            if (subjects) bank_select(*hh, hh->bank, subjects[f]);
-            if (whole(tk)) {
-                w.rc = frame_render_range(hh, st, geo[f], tk.r0, tk.r1, d_skts + (size_t)f * 384, d_cyls + (size_t)f * 5, n_samples, n_importance, flags, &maps_of[t]);
-                if (w.rc) return;
-                w.rc = outs[k].put(f, geo[f], maps_of[t]);
-            } else {
-                const size_t n = (size_t)(tk.r1 - tk.r0);
-                if (n == 0) continue;
-                float* part = hh->fc.d_part + part_off[t] * 5;
-                const FrameMaps ext{part, part + n * 3, part + n * 4};
-                w.rc = frame_render_range(hh, st, geo[f], tk.r0, tk.r1, d_skts + (size_t)f * 384, d_cyls + (size_t)f * 5, n_samples, n_importance, flags, &maps_of[t], &ext);
-            }
-        }
-        if (w.rc == PG_OK) check(hipStreamSynchronize(st), "hipStreamSynchronize");      // phase B reads other workers' range buffers
-    };
-    // phase B: the owner of a cut frame gathers all its runs (device to device), composes, copies out
-    auto phase_b = [&](int k) {
-        Worker& w = ws[k];
-        pg_handle* hh = w.h;
-        auto check = checker(w);
-        if (!check(hipSetDevice(hh->device), "hipSetDevice")) return;
-        hipStream_t st = hh->own_stream;
-        for (int f = 0; f < n_frames && w.rc == PG_OK; ++f) {
-            bool mine = false;
-            for (const FrameTask& tk : tasks) mine = mine || (tk.frame == f && tk.owner == k && !whole(tk));
-            if (!mine) continue;
-            float *rays, *cams_d;
-            FrameMaps box{};
-            pg_outputs scratch{};
-            w.rc = frame_ws(hh, nr[f], 0, &rays, &cams_d, &box, &scratch);     // phase A is over: the workspace is free
-            if (w.rc) return;
-            for (size_t u = 0; u < tasks.size(); ++u) {
-                const FrameTask& pt = tasks[u];
-                if (pt.frame != f || pt.r1 == pt.r0) continue;
-                const int src_dev = wk[pt.worker]->device;
-                const size_t n = (size_t)(pt.r1 - pt.r0);
-                if (!check(hipMemcpyPeerAsync(box.rgb_map + pt.r0 * 3, hh->device, maps_of[u].rgb_map, src_dev, n * 12, st), "peer copy") ||
-                    !check(hipMemcpyPeerAsync(box.disp_map + pt.r0, hh->device, maps_of[u].disp_map, src_dev, n * 4, st), "peer copy") ||
-                    !check(hipMemcpyPeerAsync(box.acc_map + pt.r0, hh->device, maps_of[u].acc_map, src_dev, n * 4, st), "peer copy")) return;
-            }
-            w.rc = outs[k].put(f, geo[f], box);
-        }
-    };
-    auto finish = [&](int k) {
-        Worker& w = ws[k];
-        if (w.rc != PG_OK || !composes[k]) return;
-        if (!checker(w)(hipSetDevice(w.h->device), "hipSetDevice")) return;
-        w.rc = outs[k].finish();
-    };
-    auto run = [&](auto&& fn) {
-        std::vector<std::thread> th;
-        for (int k = 1; k < G; ++k) th.emplace_back(fn, k);
-        fn(0);
-        for (auto& t : th) t.join();
-    };
-    run(phase_a);
-    bool split = false;
-    for (const FrameTask& tk : tasks) split = split || !whole(tk);
-    bool ok = true;
-    for (const Worker& w : ws) ok = ok && w.rc == PG_OK;
-    if (ok && split) run(phase_b);
-    run(finish);
-    if (subjects)
-        for (pg_handle* w : wk) bank_select(*w, w->bank, active0);
-    int rc = PG_OK;
-    for (Worker& w : ws) {
-        if (w.rc != PG_OK) {        // nothing of a failed call may still be in flight when the caller's arrays go away
-            (void)hipSetDevice(w.h->device);
-            (void)hipDeviceSynchronize();
-            if (rc == PG_OK) rc = (w.h == h) ? w.rc : pg_fail(h, w.rc, "device %d: %s", w.h->device, w.h->err);
-        }
-    }
-    (void)hipSetDevice(h->device);
-    return rc;
-}
-
-}  // extern "C"
-
-// ---- training batches from an image bank on the device (pg_batch.hip) ----------------------------------------------
-namespace {
-
-// what the four entry points keep in the handle: the tile offsets of the last pg_pixel_index_count (and what they were counted on),
-// and a ring of pinned host / device buffer pairs for a call's image rows.  A slot is reused only after the copy out of its host
-// buffer has finished (its event), so a call neither waits for the stream nor overwrites rows still in flight.
-struct BatchState {
-    uint8_t* tiles = nullptr;
-    size_t tiles_bytes = 0;
-    const void* masks = nullptr;
-    int64_t F = 0, P = 0;
-    static constexpr int SLOTS = 8;
-    struct Slot {
-        int32_t* host = nullptr;
-        size_t cap = 0;              // ... words
-        uint8_t* dev = nullptr;
-        size_t dev_bytes = 0;
-        hipEvent_t done = nullptr;
-    } slot[SLOTS];
-    unsigned next = 0;
-};
-
-BatchState* batch_state(pg_handle* h) {
-    if (!h->batch) h->batch = new BatchState();
-    return static_cast<BatchState*>(h->batch);
-}
-
-void batch_release(pg_handle* h) {
-    if (!h->batch) return;
-    auto* s = static_cast<BatchState*>(h->batch);
-    if (s->tiles) (void)hipFree(s->tiles);
-    for (auto& sl : s->slot) {
-        if (sl.done) (void)hipEventDestroy(sl.done);
-        if (sl.host) (void)hipHostFree(sl.host);
-        if (sl.dev) (void)hipFree(sl.dev);
-    }
-    delete s;
-    h->batch = nullptr;
-}
-
-// `words` (checked by the caller) -> the next slot's device buffer, on stream st
-int batch_upload(pg_handle* h, const std::vector<int32_t>& words, hipStream_t st, const int** dev) {
-    BatchState* s = batch_state(h);
-    BatchState::Slot& sl = s->slot[s->next++ % BatchState::SLOTS];
-    if (!sl.done) PG_HIP(h, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
-    else PG_HIP(h, hipEventSynchronize(sl.done));
-    if (words.size() > sl.cap) {
-        if (sl.host) { PG_HIP(h, hipHostFree(sl.host)); sl.host = nullptr; sl.cap = 0; }
-        const size_t cap = words.size() + words.size() / 2 + 64;
-        PG_HIP(h, hipHostMalloc(reinterpret_cast<void**>(&sl.host), cap * sizeof(int32_t), hipHostMallocDefault));
-        sl.cap = cap;
-    }
-    PG_TRY(pg_grow(h, sl.dev, sl.dev_bytes, sl.cap * sizeof(int32_t), "batch row buffer"));
-    std::memcpy(sl.host, words.data(), words.size() * sizeof(int32_t));
-    PG_HIP(h, hipMemcpyAsync(sl.dev, sl.host, words.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    PG_HIP(h, hipEventRecord(sl.done, st));
-    *dev = reinterpret_cast<const int*>(sl.dev);
-    return PG_OK;
-}
-
-int check_index_args(pg_handle* h, const char* who, const void* masks, int64_t F, int64_t P) {
-    if (!masks) return pg_fail(h, PG_EINVAL, "%s: sampling_masks is null", who);
-    if (F <= 0 || P <= 0) return pg_fail(h, PG_EINVAL, "%s: F (%lld) and P (%lld) must be positive", who, (long long)F, (long long)P);
-    if (P > 0x7ffffffell) return pg_fail(h, PG_EINVAL, "%s: at most 2^31 - 2 pixels per image (the ids are int32)", who);
-    const int64_t ntiles = (P + pg_batch_tile_pixels() - 1) / pg_batch_tile_pixels();
-    if (F > (int64_t)(0x7fffffffffffll / ntiles)) return pg_fail(h, PG_EINVAL, "%s: F * P is too large", who);
-    return PG_OK;
-}
-
-int check_rows(pg_handle* h, const char* who, const char* what, const int32_t* rows, int64_t n, int64_t bound) {
-    for (int64_t a = 0; a < n; ++a)
-        if (rows[a] < 0 || rows[a] >= bound)
-            return pg_fail(h, PG_EINVAL, "%s: %s[%lld] = %d is outside [0, %lld)", who, what, (long long)a, rows[a], (long long)bound);
-    return PG_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int pg_pixel_index_count(pg_handle* h, void* stream, const uint8_t* sampling_masks, int64_t F, int64_t P, int64_t* counts) {
-    if (!h) return pg_fail(nullptr, PG_EINVAL, "null handle");
-    PG_TRY(check_index_args(h, "pg_pixel_index_count", sampling_masks, F, P));
-    if (!counts) return pg_fail(h, PG_EINVAL, "pg_pixel_index_count: counts is null");
-    BatchState* s = batch_state(h);
-    s->masks = nullptr;
-    const int64_t ntiles = (P + pg_batch_tile_pixels() - 1) / pg_batch_tile_pixels();
-    PG_HIP(h, hipSetDevice(h->device));
-    PG_TRY(pg_grow(h, s->tiles, s->tiles_bytes, (size_t)(F * ntiles) * sizeof(int), "pixel index tile counts"));
-    PG_TRY_LAUNCH(h, "pixel count kernels",
-                  pg_launch_pixel_count(sampling_masks, F, P, reinterpret_cast<int*>(s->tiles), reinterpret_cast<long long*>(counts), stream));
-    s->masks = sampling_masks; s->F = F; s->P = P;
-    return PG_OK;
-}
-
-int pg_pixel_index_emit(pg_handle* h, void* stream, const uint8_t* sampling_masks, int64_t F, int64_t P, const int64_t* start,
-                        int64_t total, int32_t* ids) {
-    if (!h) return pg_fail(nullptr, PG_EINVAL, "null handle");
-    PG_TRY(check_index_args(h, "pg_pixel_index_emit", sampling_masks, F, P));
-    if (!start || total < 0 || (total > 0 && !ids)) return pg_fail(h, PG_EINVAL, "pg_pixel_index_emit: null start / ids or negative total");
-    BatchState* s = batch_state(h);
-    if (s->masks != sampling_masks || s->F != F || s->P != P)
-        return pg_fail(h, PG_ESTATE, "pg_pixel_index_emit: masks, F and P are not those of the last pg_pixel_index_count");
-    if (total == 0) return PG_OK;
-    PG_HIP(h, hipSetDevice(h->device));
-    PG_TRY_LAUNCH(h, "pixel emit kernel", pg_launch_pixel_emit(sampling_masks, F, P, reinterpret_cast<const int*>(s->tiles),
-                                                               reinterpret_cast<const long long*>(start), ids, stream));
-    return PG_OK;
-}
-
-int pg_batch_sample_pixels(pg_handle* h, void* stream, const int32_t* ids, const int64_t* start, const int64_t* counts, int64_t F,
-                           const int32_t* img_rows, int64_t n_img, int k, const double* draws, int32_t* pixel_idxs) {
-    const char* who = "pg_batch_sample_pixels";
-    if (!h) return pg_fail(nullptr, PG_EINVAL, "null handle");
-    if (!ids || !start || !counts || !img_rows || !draws || !pixel_idxs) return pg_fail(h, PG_EINVAL, "%s: null argument", who);
-    if (F <= 0) return pg_fail(h, PG_EINVAL, "%s: F (%lld) must be positive", who, (long long)F);
-    if (k < 1 || k > pg_batch_max_pixels()) return pg_fail(h, PG_EINVAL, "%s: k = %d is outside [1, %d]", who, k, pg_batch_max_pixels());
-    if (n_img < 0 || n_img > 0x7ffffffell / k) return pg_fail(h, PG_EINVAL, "%s: n_img (%lld) negative or n_img * k above 2^31 - 2", who, (long long)n_img);
-    PG_TRY(check_rows(h, who, "img_rows", img_rows, n_img, F));
-    for (int64_t a = 0; a < n_img; ++a)
-        if (k > counts[img_rows[a]])
-            return pg_fail(h, PG_EINVAL, "%s: image %d has %lld valid pixels, fewer than k = %d", who, img_rows[a], (long long)counts[img_rows[a]], k);
-    if (n_img == 0) return PG_OK;
-    PG_HIP(h, hipSetDevice(h->device));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int* d_rows = nullptr;
-    PG_TRY(batch_upload(h, std::vector<int32_t>(img_rows, img_rows + n_img), st, &d_rows));
-    PG_TRY_LAUNCH(h, "pixel sampler kernel",
-                  pg_launch_sample_pixels(ids, reinterpret_cast<const long long*>(start), d_rows, n_img, k, draws, pixel_idxs, stream));
-    return PG_OK;
-}
-
-int pg_batch_gather(pg_handle* h, void* stream, const pg_image_bank* bank, const int32_t* img_rows, const int32_t* cam_rows, int64_t n_img,
-                    int k, const int32_t* pixel_idxs, float* target_s, float* fgs, float* bgs, float* rays_o, float* rays_d, float* ray_batch) {
-    const char* who = "pg_batch_gather";
-    if (!h) return pg_fail(nullptr, PG_EINVAL, "null handle");
-    if (!bank || !img_rows || !pixel_idxs || !target_s || !fgs || !rays_o || !rays_d || !ray_batch) return pg_fail(h, PG_EINVAL, "%s: null argument", who);
-    if (!bank->imgs || !bank->masks || !bank->c2ws || !bank->focals) return pg_fail(h, PG_EINVAL, "%s: the bank's imgs / masks / c2ws / focals are required", who);
-    if (bank->F <= 0 || bank->P <= 0 || bank->n_cam <= 0) return pg_fail(h, PG_EINVAL, "%s: F, P and n_cam must be positive", who);
-    if (bank->H <= 0 || bank->W <= 0 || (int64_t)bank->H * bank->W != bank->P || bank->P > 0x7ffffffell)
-        return pg_fail(h, PG_EINVAL, "%s: H x W = %d x %d is not P = %lld", who, bank->H, bank->W, (long long)bank->P);
-    if (bank->bkgds && (!bank->bkgd_idxs || bank->n_bkgd <= 0)) return pg_fail(h, PG_EINVAL, "%s: backgrounds without bkgd_idxs / n_bkgd", who);
-    if (bgs && !bank->bkgds) return pg_fail(h, PG_EINVAL, "%s: bgs asked for from a bank without backgrounds", who);
-    if (k < 1 || k > pg_batch_max_pixels()) return pg_fail(h, PG_EINVAL, "%s: k = %d is outside [1, %d]", who, k, pg_batch_max_pixels());
-    if (n_img < 0 || n_img > 0x7ffffffell / k) return pg_fail(h, PG_EINVAL, "%s: n_img (%lld) negative or n_img * k above 2^31 - 2", who, (long long)n_img);
-    PG_TRY(check_rows(h, who, "img_rows", img_rows, n_img, bank->F));
-    PG_TRY(check_rows(h, who, "cam_rows", cam_rows ? cam_rows : img_rows, n_img, bank->n_cam));
-    std::vector<int32_t> rows((size_t)n_img * 3, 0);
-    for (int64_t a = 0; a < n_img; ++a) {
-        rows[a] = img_rows[a];
-        rows[n_img + a] = (cam_rows ? cam_rows : img_rows)[a];
-        if (bank->bkgds) {
-            const int32_t b = bank->bkgd_idxs[img_rows[a]];
-            if (b < 0 || b >= bank->n_bkgd)
-                return pg_fail(h, PG_EINVAL, "%s: bkgd_idxs[%d] = %d is outside [0, %lld)", who, img_rows[a], b, (long long)bank->n_bkgd);
-            rows[2 * n_img + a] = b;
-        }
-    }
-    if (n_img == 0) return PG_OK;
-    PG_HIP(h, hipSetDevice(h->device));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int* d_rows = nullptr;
-    PG_TRY(batch_upload(h, rows, st, &d_rows));
-    pgk::BatchGather g{bank->imgs, bank->masks, bank->bkgds, bank->c2ws, bank->focals, bank->centers, bank->P, bank->H, bank->W,
-                       bank->bkgds ? bank->mask_img : 0, d_rows, n_img, k, pixel_idxs, target_s, fgs, bgs, rays_o, rays_d, ray_batch};
-    PG_TRY_LAUNCH(h, "batch gather kernel", pg_launch_batch_gather(&g, stream));
-    return PG_OK;
-}
 
 }  // extern "C"

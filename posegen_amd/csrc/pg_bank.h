@@ -1,6 +1,6 @@
 // pg_bank.h -- the subject bank of a renderer handle: S >= 1 complete models ("subjects": independent checkpoints of one
 // architecture) behind one pg_handle.  Host-only and free of HIP calls, so that the swap logic compiles into a plain C++ program
-// (tests/host/subject_bank_main.cpp, built with the address and undefined-behaviour sanitisers); device memory is allocated and
+// (tools/sanitize/subject_bank_asan.cpp, built with the address and undefined-behaviour sanitisers); device memory is allocated and
 // released through the caller's functors.
 //
 // What a subject owns is `Subject`: both nets' NetState (host tensors, folded view layer, every packed image, source maps, frame

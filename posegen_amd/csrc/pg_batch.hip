@@ -11,6 +11,9 @@
 #include <math.h>
 #include <stdint.h>
 
+#include <cstring>
+
+#include "pg_handle.h"
 #include "pg_launch.h"
 
 namespace pgb {
@@ -260,6 +263,170 @@ int pg_launch_batch_gather(const pgk::BatchGather* g, void* stream) {
     hipLaunchKernelGGL(pgb::batch_gather_kernel, dim3((unsigned)((n + pgb::THREADS - 1) / pgb::THREADS)), dim3(pgb::THREADS), 0,
                        static_cast<hipStream_t>(stream), *g);
     return (int)hipGetLastError();
+}
+
+}  // extern "C"
+
+// ---- the host side: the four entry points of the C ABI and what they keep in the handle ---------------------------------------------
+namespace {
+
+// what the four entry points keep in the handle: the tile offsets of the last pg_pixel_index_count (and what they were counted on),
+// and a ring of pinned host / device buffer pairs for a call's image rows.  A slot is reused only after the copy out of its host
+// buffer has finished (its event), so a call neither waits for the stream nor overwrites rows still in flight.
+struct BatchState {
+    DevBuf tiles;
+    const void* masks = nullptr;
+    int64_t F = 0, P = 0;
+    static constexpr int SLOTS = 8;
+    struct Slot {
+        PinBuf host;
+        DevBuf dev;
+        hipEvent_t done = nullptr;
+    } slot[SLOTS];
+    unsigned next = 0;
+};
+
+BatchState* batch_state(pg_handle* h) {
+    if (!h->batch) h->batch = new BatchState();
+    return static_cast<BatchState*>(h->batch);
+}
+
+// `words` (checked by the caller) -> the next slot's device buffer, on stream st
+int batch_upload(pg_handle* h, const std::vector<int32_t>& words, hipStream_t st, const int** dev) {
+    BatchState* s = batch_state(h);
+    BatchState::Slot& sl = s->slot[s->next++ % BatchState::SLOTS];
+    if (!sl.done) PG_HIP(h, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
+    else PG_HIP(h, hipEventSynchronize(sl.done));
+    const size_t bytes = words.size() * sizeof(int32_t);
+    PG_TRY(pg_grow_pinned(h, sl.host, bytes, "batch row staging", (words.size() + words.size() / 2 + 64) * sizeof(int32_t)));
+    PG_TRY(pg_grow(h, sl.dev, sl.host.bytes, "batch row buffer"));
+    std::memcpy(sl.host.p, words.data(), bytes);
+    PG_HIP(h, hipMemcpyAsync(sl.dev.p, sl.host.p, bytes, hipMemcpyHostToDevice, st));
+    PG_HIP(h, hipEventRecord(sl.done, st));
+    *dev = sl.dev.as<const int>();
+    return PG_OK;
+}
+
+int check_index_args(pg_handle* h, const char* who, const void* masks, int64_t F, int64_t P) {
+    if (!masks) return pg_fail(h, PG_EINVAL, "%s: sampling_masks is null", who);
+    if (F <= 0 || P <= 0) return pg_fail(h, PG_EINVAL, "%s: F (%lld) and P (%lld) must be positive", who, (long long)F, (long long)P);
+    if (P > 0x7ffffffell) return pg_fail(h, PG_EINVAL, "%s: at most 2^31 - 2 pixels per image (the ids are int32)", who);
+    const int64_t ntiles = (P + pg_batch_tile_pixels() - 1) / pg_batch_tile_pixels();
+    if (F > (int64_t)(0x7fffffffffffll / ntiles)) return pg_fail(h, PG_EINVAL, "%s: F * P is too large", who);
+    return PG_OK;
+}
+
+int check_rows(pg_handle* h, const char* who, const char* what, const int32_t* rows, int64_t n, int64_t bound) {
+    for (int64_t a = 0; a < n; ++a)
+        if (rows[a] < 0 || rows[a] >= bound)
+            return pg_fail(h, PG_EINVAL, "%s: %s[%lld] = %d is outside [0, %lld)", who, what, (long long)a, rows[a], (long long)bound);
+    return PG_OK;
+}
+
+}  // namespace
+
+void pg_batch_release(pg_handle* h) {
+    if (!h || !h->batch) return;
+    auto* s = static_cast<BatchState*>(h->batch);
+    pg_release(s->tiles);
+    for (auto& sl : s->slot) {
+        if (sl.done) (void)hipEventDestroy(sl.done);
+        pg_release(sl.host);
+        pg_release(sl.dev);
+    }
+    delete s;
+    h->batch = nullptr;
+}
+
+extern "C" {
+
+int pg_pixel_index_count(pg_handle* h, void* stream, const uint8_t* sampling_masks, int64_t F, int64_t P, int64_t* counts) {
+    if (!h) return pg_fail(nullptr, PG_EINVAL, "null handle");
+    PG_TRY(check_index_args(h, "pg_pixel_index_count", sampling_masks, F, P));
+    if (!counts) return pg_fail(h, PG_EINVAL, "pg_pixel_index_count: counts is null");
+    BatchState* s = batch_state(h);
+    s->masks = nullptr;
+    const int64_t ntiles = (P + pg_batch_tile_pixels() - 1) / pg_batch_tile_pixels();
+    PG_HIP(h, hipSetDevice(h->device));
+    PG_TRY(pg_grow(h, s->tiles, (size_t)(F * ntiles) * sizeof(int), "pixel index tile counts"));
+    PG_TRY_LAUNCH(h, "pixel count kernels",
+                  pg_launch_pixel_count(sampling_masks, F, P, s->tiles.as<int>(), reinterpret_cast<long long*>(counts), stream));
+    s->masks = sampling_masks; s->F = F; s->P = P;
+    return PG_OK;
+}
+
+int pg_pixel_index_emit(pg_handle* h, void* stream, const uint8_t* sampling_masks, int64_t F, int64_t P, const int64_t* start,
+                        int64_t total, int32_t* ids) {
+    if (!h) return pg_fail(nullptr, PG_EINVAL, "null handle");
+    PG_TRY(check_index_args(h, "pg_pixel_index_emit", sampling_masks, F, P));
+    if (!start || total < 0 || (total > 0 && !ids)) return pg_fail(h, PG_EINVAL, "pg_pixel_index_emit: null start / ids or negative total");
+    BatchState* s = batch_state(h);
+    if (s->masks != sampling_masks || s->F != F || s->P != P)
+        return pg_fail(h, PG_ESTATE, "pg_pixel_index_emit: masks, F and P are not those of the last pg_pixel_index_count");
+    if (total == 0) return PG_OK;
+    PG_HIP(h, hipSetDevice(h->device));
+    PG_TRY_LAUNCH(h, "pixel emit kernel", pg_launch_pixel_emit(sampling_masks, F, P, s->tiles.as<const int>(),
+                                                               reinterpret_cast<const long long*>(start), ids, stream));
+    return PG_OK;
+}
+
+int pg_batch_sample_pixels(pg_handle* h, void* stream, const int32_t* ids, const int64_t* start, const int64_t* counts, int64_t F,
+                           const int32_t* img_rows, int64_t n_img, int k, const double* draws, int32_t* pixel_idxs) {
+    const char* who = "pg_batch_sample_pixels";
+    if (!h) return pg_fail(nullptr, PG_EINVAL, "null handle");
+    if (!ids || !start || !counts || !img_rows || !draws || !pixel_idxs) return pg_fail(h, PG_EINVAL, "%s: null argument", who);
+    if (F <= 0) return pg_fail(h, PG_EINVAL, "%s: F (%lld) must be positive", who, (long long)F);
+    if (k < 1 || k > pg_batch_max_pixels()) return pg_fail(h, PG_EINVAL, "%s: k = %d is outside [1, %d]", who, k, pg_batch_max_pixels());
+    if (n_img < 0 || n_img > 0x7ffffffell / k) return pg_fail(h, PG_EINVAL, "%s: n_img (%lld) negative or n_img * k above 2^31 - 2", who, (long long)n_img);
+    PG_TRY(check_rows(h, who, "img_rows", img_rows, n_img, F));
+    for (int64_t a = 0; a < n_img; ++a)
+        if (k > counts[img_rows[a]])
+            return pg_fail(h, PG_EINVAL, "%s: image %d has %lld valid pixels, fewer than k = %d", who, img_rows[a], (long long)counts[img_rows[a]], k);
+    if (n_img == 0) return PG_OK;
+    PG_HIP(h, hipSetDevice(h->device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int* d_rows = nullptr;
+    PG_TRY(batch_upload(h, std::vector<int32_t>(img_rows, img_rows + n_img), st, &d_rows));
+    PG_TRY_LAUNCH(h, "pixel sampler kernel",
+                  pg_launch_sample_pixels(ids, reinterpret_cast<const long long*>(start), d_rows, n_img, k, draws, pixel_idxs, stream));
+    return PG_OK;
+}
+
+int pg_batch_gather(pg_handle* h, void* stream, const pg_image_bank* bank, const int32_t* img_rows, const int32_t* cam_rows, int64_t n_img,
+                    int k, const int32_t* pixel_idxs, float* target_s, float* fgs, float* bgs, float* rays_o, float* rays_d, float* ray_batch) {
+    const char* who = "pg_batch_gather";
+    if (!h) return pg_fail(nullptr, PG_EINVAL, "null handle");
+    if (!bank || !img_rows || !pixel_idxs || !target_s || !fgs || !rays_o || !rays_d || !ray_batch) return pg_fail(h, PG_EINVAL, "%s: null argument", who);
+    if (!bank->imgs || !bank->masks || !bank->c2ws || !bank->focals) return pg_fail(h, PG_EINVAL, "%s: the bank's imgs / masks / c2ws / focals are required", who);
+    if (bank->F <= 0 || bank->P <= 0 || bank->n_cam <= 0) return pg_fail(h, PG_EINVAL, "%s: F, P and n_cam must be positive", who);
+    if (bank->H <= 0 || bank->W <= 0 || (int64_t)bank->H * bank->W != bank->P || bank->P > 0x7ffffffell)
+        return pg_fail(h, PG_EINVAL, "%s: H x W = %d x %d is not P = %lld", who, bank->H, bank->W, (long long)bank->P);
+    if (bank->bkgds && (!bank->bkgd_idxs || bank->n_bkgd <= 0)) return pg_fail(h, PG_EINVAL, "%s: backgrounds without bkgd_idxs / n_bkgd", who);
+    if (bgs && !bank->bkgds) return pg_fail(h, PG_EINVAL, "%s: bgs asked for from a bank without backgrounds", who);
+    if (k < 1 || k > pg_batch_max_pixels()) return pg_fail(h, PG_EINVAL, "%s: k = %d is outside [1, %d]", who, k, pg_batch_max_pixels());
+    if (n_img < 0 || n_img > 0x7ffffffell / k) return pg_fail(h, PG_EINVAL, "%s: n_img (%lld) negative or n_img * k above 2^31 - 2", who, (long long)n_img);
+    PG_TRY(check_rows(h, who, "img_rows", img_rows, n_img, bank->F));
+    PG_TRY(check_rows(h, who, "cam_rows", cam_rows ? cam_rows : img_rows, n_img, bank->n_cam));
+    std::vector<int32_t> rows((size_t)n_img * 3, 0);
+    for (int64_t a = 0; a < n_img; ++a) {
+        rows[a] = img_rows[a];
+        rows[n_img + a] = (cam_rows ? cam_rows : img_rows)[a];
+        if (bank->bkgds) {
+            const int32_t b = bank->bkgd_idxs[img_rows[a]];
+            if (b < 0 || b >= bank->n_bkgd)
+                return pg_fail(h, PG_EINVAL, "%s: bkgd_idxs[%d] = %d is outside [0, %lld)", who, img_rows[a], b, (long long)bank->n_bkgd);
+            rows[2 * n_img + a] = b;
+        }
+    }
+    if (n_img == 0) return PG_OK;
+    PG_HIP(h, hipSetDevice(h->device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int* d_rows = nullptr;
+    PG_TRY(batch_upload(h, rows, st, &d_rows));
+    pgk::BatchGather g{bank->imgs, bank->masks, bank->bkgds, bank->c2ws, bank->focals, bank->centers, bank->P, bank->H, bank->W,
+                       bank->bkgds ? bank->mask_img : 0, d_rows, n_img, k, pixel_idxs, target_s, fgs, bgs, rays_o, rays_d, ray_batch};
+    PG_TRY_LAUNCH(h, "batch gather kernel", pg_launch_batch_gather(&g, stream));
+    return PG_OK;
 }
 
 }  // extern "C"

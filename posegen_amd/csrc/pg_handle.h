@@ -1,5 +1,6 @@
-// pg_handle.h -- the renderer handle behind the C ABI (include/posegen_hip.h), shared by the translation units
-// that implement its entry points (pg_api.hip: rendering; pg_train.hip: the training step).
+// pg_handle.h -- the renderer handle behind the C ABI (include/posegen_hip.h), shared by the translation units that implement
+// its entry points: pg_api.hip (handle, weights, ray-level rendering), pg_frames.hip (frames), pg_train.hip (the training step),
+// pg_mesh.hip, pg_poseopt.hip, pg_batch.hip.  Each of the last five keeps its own state behind a void* of the handle.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,6 +11,20 @@
 #include "pg_bank.h"
 #include "pg_layout.h"
 
+// A buffer that only ever grows (pg_grow / pg_grow_pinned below): on the device, or page-locked on the host (two types: neither
+// is ever freed as the other).
+template <bool PINNED> struct Buf {
+    uint8_t* p = nullptr;
+    size_t bytes = 0;
+    template <typename T = uint8_t> T* as() const { return reinterpret_cast<T*>(p); }
+};
+using DevBuf = Buf<false>;
+using PinBuf = Buf<true>;
+template <bool PINNED> void pg_release(Buf<PINNED>& b) {
+    if (b.p) (void)(PINNED ? hipHostFree(b.p) : hipFree(b.p));
+    b = Buf<PINNED>();
+}
+
 // The handle is its active subject (pg_bank.h): net, cut, tau, emb_set and d_cut below are that model's; the other subjects of the
 // bank wait in `bank` and are swapped in by pg_select_subject.
 struct pg_handle : Subject {
@@ -19,22 +34,17 @@ struct pg_handle : Subject {
     int clock_khz = 0;
     char err[512] = "";
     Bank bank;                       // pg_set_subject_count / pg_select_subject
-    uint8_t* ws = nullptr;
-    size_t ws_bytes = 0;
-    uint8_t* fws = nullptr;          // frame front/back end: ray_batch, cams, rgb/disp/acc maps of the box
-    size_t fws_bytes = 0;
-    double* sc_part = nullptr;       // partial nanmean sums of the two-launch coarse sampler (pg_kernels.hip)
-    size_t sc_part_cap = 0;          // ... doubles
-    uint8_t* rec = nullptr;          // per-ray records of the factorised 16-bit path: Y [n + pad, 8 KiB] then (a, b) [n + pad, 768 B]
-    size_t rec_bytes = 0;
+    DevBuf ws;                       // a ray-level call's workspace (pg_api.hip carve_ws)
+    DevBuf fws;                      // frame front/back end: ray_batch, cams, rgb/disp/acc maps of the box (pg_frames.hip frame_ws)
+    DevBuf sc_part;                  // partial nanmean sums (doubles) of the two-launch coarse sampler (pg_kernels.hip)
+    DevBuf rec;                      // per-ray records of the factorised 16-bit path: Y [n + pad, 8 KiB] then (a, b) [n + pad, 768 B]
     long long rec_pad_n = -1;        // (n, Y bytes per ray) whose padding records are currently zero (-1: none)
     int rec_pad_y = 0;
     void* rec_pad_stream = nullptr;  // the stream that memset was issued on: a call on another stream zeroes again (no ordering between streams)
     // in-process multi-device rendering (pg_render_frames): the primary handle owns one sub-handle per
-    // further device; every handle has a stream and a small pose buffer of its own for that path
+    // further device; every handle has a stream of its own for that path
     std::vector<pg_handle*> peers;
     hipStream_t own_stream = nullptr;
-    float* d_pose = nullptr;         // [24*16 + 5 + pad] skts + cyl of the frame being rendered
     bool far_skip = true;            // pg_set_far_skip (test / measurement aid)
     bool empty_skip = true;          // pg_set_empty_skip: waves whose points are all empty leave the colour branch out (pg_eval16r.hip)
     uint32_t* wave_counts = nullptr; // pg_debug_wave_counts: device words the counting instantiation of render launches adds to
@@ -50,32 +60,17 @@ struct pg_handle : Subject {
     void* train = nullptr;           // the training tape (pg_train.hip): activations of the last pg_train_forward
     void* mesh = nullptr;            // marching-cubes state of the last pg_mesh_count (pg_mesh.hip): flags, cases, scans
     void* poseopt = nullptr;         // the pose layer's index buffer (pg_poseopt.hip): joint tree and ray segments of the last call
-    void* batch = nullptr;           // training batches (pg_api.hip): tile offsets of the last pg_pixel_index_count, the row-upload ring
+    void* batch = nullptr;           // training batches (pg_batch.hip): tile offsets of the last pg_pixel_index_count, the row-upload ring
+    void* frames = nullptr;          // pg_render_frames (pg_frames.hip): per-device buffers, copy stream and events kept between calls
     std::vector<float> grid_t;       // pg_grid_density: the host copy of the axis table t[R] while its upload is in flight
     bool tape_out = false;           // a pg_train_forward whose backward has not run yet: the bank stays as it is until then
-    // pg_render_frames: per-device buffers kept between calls (frames of H x W pixels, background, pinned staging)
-    struct FramesCache {
-        size_t hw = 0;               // pixels the frame buffers were sized for
-        bool has_u8 = false;
-        static constexpr int NBUF = 2;               // frame buffers in rotation: frame k+1 composes while frame k copies out
-        float* d_frame[NBUF] = {};                   // rgb [hw,3] | disp [hw] | acc [hw] (| rgb8 [hw,3] bytes behind)
-        hipEvent_t composed[NBUF] = {};              // buffer b holds a finished frame (render stream)
-        hipEvent_t copied[NBUF] = {};                // the device-to-host copy out of buffer b has finished (copy stream)
-        hipStream_t copy_stream = nullptr;
-        float* d_bg = nullptr;                       // background [hw,3] (uploaded per call when given)
-        size_t bg_hw = 0;
-        float* d_poses = nullptr;                    // skts + cyls of all frames of the call: [F, 384 + 8]
-        size_t poses_cap = 0;                        // ... frames
-        float* d_part = nullptr;                     // packed maps (20 B per ray) of the ray ranges of cut frames this device renders
-        size_t part_cap = 0;                         // ... rays
-        void* h_stage = nullptr;                     // pinned host staging of NBUF frames (results that land in pageable memory)
-        size_t stage_bytes = 0;
-    } fc;
 };
 
 extern "C" void pg_train_release(pg_handle* h);
 extern "C" void pg_mesh_release(pg_handle* h);
 extern "C" void pg_poseopt_release(pg_handle* h);
+void pg_batch_release(pg_handle* h);
+void pg_frames_release(pg_handle* h);
 // scratch of pg_launch_sample_coarse for n rays in chunks of `chunk` (null when the one-launch form runs)
 int pg_sc_scratch(pg_handle* h, long long n, int chunk, double** out);
 // the pose / cylinder stride of a ray-level call (`stage`: the stage entry points' shorter wording)
@@ -84,8 +79,12 @@ int pg_check_cyl_stride(pg_handle* h, long long v, bool stage);
 
 // records the message (handle and thread-local "last error") and returns `code`
 int pg_fail(pg_handle* h, int code, const char* fmt, ...);
-// a device buffer that only ever grows (the old contents are void; what read them has to finish before they go)
-int pg_grow(pg_handle* h, uint8_t*& buf, size_t& bytes, size_t need, const char* what);
+// `need` bytes in a buffer that only ever grows, on the current device: one that is too small is freed (after a
+// hipDeviceSynchronize: what read it has to finish first; its contents are void) and allocated again with `alloc` bytes (0: need).
+// A failing allocation leaves the buffer empty.  The pinned twin frees without the synchronise: its owner knows when the copies
+// out of it have finished.
+int pg_grow(pg_handle* h, DevBuf& b, size_t need, const char* what, size_t alloc = 0);
+int pg_grow_pinned(pg_handle* h, PinBuf& b, size_t need, const char* what, size_t alloc = 0);
 
 // A buffer carved into arrays, each on a 256-byte boundary.  The list of take<T>(count) calls runs twice: over a Carver without a
 // base, which only adds the sizes up (the pointers come out null), then over the allocation -- an array cannot be carved without

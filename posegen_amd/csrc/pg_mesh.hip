@@ -170,25 +170,24 @@ unsigned blocks_for(long long n) {
 
 // what pg_mesh_count leaves in the handle for pg_mesh_emit
 struct MeshState {
+    DevBuf arrays;                      // the six arrays below (carve)
     unsigned char* flags = nullptr;     // [N]
     unsigned char* cases = nullptr;     // [N]
     int* ecnt = nullptr;                // [N + 1] each: counts and their exclusive scans
     int* tcnt = nullptr;
     int* eoff = nullptr;
     int* toff = nullptr;
-    long long cap = 0;                  // points the arrays hold
-    void* tmp = nullptr;                // hipcub's scratch
-    size_t tmp_bytes = 0;
+    DevBuf tmp;                         // hipcub's scratch
     bool valid = false;                 // the scans are those of (dims, thr, clamp)
     Dims dims{0, 0, 0};
     float thr = 0.0f, clamp = 0.0f;
     long long nv = 0, nt = 0;
 };
 
-void release(MeshState* s) {
-    for (void* p : {(void*)s->flags, (void*)s->cases, (void*)s->ecnt, (void*)s->tcnt, (void*)s->eoff, (void*)s->toff, s->tmp})
-        if (p) (void)hipFree(p);
-    *s = MeshState{};
+void carve(MeshState* s, Carver& c, size_t N) {
+    s->flags = c.take<unsigned char>(N);
+    s->cases = c.take<unsigned char>(N);
+    for (int** p : {&s->ecnt, &s->tcnt, &s->eoff, &s->toff}) *p = c.take<int>(N + 1);
 }
 
 bool same_float(float a, float b) { return a == b || (a != a && b != b); }
@@ -220,7 +219,8 @@ int pg_launch_gather_sigma(const float* raw, long long n, float* sigma, void* st
 void pg_mesh_release(pg_handle* h) {
     if (!h || !h->mesh) return;
     auto* s = static_cast<pgm::MeshState*>(h->mesh);
-    pgm::release(s);
+    pg_release(s->arrays);
+    pg_release(s->tmp);
     delete s;
     h->mesh = nullptr;
 }
@@ -240,31 +240,20 @@ int pg_mesh_count(pg_handle* h, void* stream, const float* grid, int nx, int ny,
     auto* s = static_cast<MeshState*>(h->mesh);
     s->valid = false;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (N > s->cap) {
-        PG_HIP(h, hipDeviceSynchronize());
-        release(s);
-        const size_t n1 = (size_t)N + 1;
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&s->flags), (size_t)N);
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->cases), (size_t)N);
-        for (int** p : {&s->ecnt, &s->tcnt, &s->eoff, &s->toff})
-            if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(p), n1 * sizeof(int));
-        if (e != hipSuccess) { release(s); return pg_fail(h, PG_ENOMEM, "marching cubes scratch for %lld points failed: %s", N, hipGetErrorString(e)); }
-        s->cap = N;
-    }
+    Carver sizes;
+    carve(s, sizes, (size_t)N);
+    PG_TRY(pg_grow(h, s->arrays, sizes.off, "marching cubes scratch"));
+    Carver c{s->arrays.p};
+    carve(s, c, (size_t)N);
     size_t need = 0;
     PG_HIP(h, hipcub::DeviceScan::ExclusiveSum(nullptr, need, s->ecnt, s->eoff, (int)(N + 1), st));
-    if (need > s->tmp_bytes) {
-        if (s->tmp) { PG_HIP(h, hipDeviceSynchronize()); PG_HIP(h, hipFree(s->tmp)); s->tmp = nullptr; s->tmp_bytes = 0; }
-        hipError_t e = hipMalloc(&s->tmp, need);
-        if (e != hipSuccess) return pg_fail(h, PG_ENOMEM, "scan scratch of %zu bytes failed: %s", need, hipGetErrorString(e));
-        s->tmp_bytes = need;
-    }
+    PG_TRY(pg_grow(h, s->tmp, need, "scan scratch"));
     hipLaunchKernelGGL(mc_count_kernel, dim3(blocks_for(N + 1)), dim3(THREADS), 0, st, grid, d, threshold, clamp, s->flags, s->cases, s->ecnt, s->tcnt);
     PG_HIP(h, hipGetLastError());
-    size_t tb = s->tmp_bytes;
-    PG_HIP(h, hipcub::DeviceScan::ExclusiveSum(s->tmp, tb, s->ecnt, s->eoff, (int)(N + 1), st));
-    tb = s->tmp_bytes;
-    PG_HIP(h, hipcub::DeviceScan::ExclusiveSum(s->tmp, tb, s->tcnt, s->toff, (int)(N + 1), st));
+    size_t tb = s->tmp.bytes;
+    PG_HIP(h, hipcub::DeviceScan::ExclusiveSum(s->tmp.p, tb, s->ecnt, s->eoff, (int)(N + 1), st));
+    tb = s->tmp.bytes;
+    PG_HIP(h, hipcub::DeviceScan::ExclusiveSum(s->tmp.p, tb, s->tcnt, s->toff, (int)(N + 1), st));
     int tot[2] = {0, 0};
     PG_HIP(h, hipMemcpyAsync(&tot[0], s->eoff + N, sizeof(int), hipMemcpyDeviceToHost, st));
     PG_HIP(h, hipMemcpyAsync(&tot[1], s->toff + N, sizeof(int), hipMemcpyDeviceToHost, st));

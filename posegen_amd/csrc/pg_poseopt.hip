@@ -245,8 +245,7 @@ __global__ __launch_bounds__(THREADS) void poseopt_bwd_kernel(const float* __res
 // what the two entry points keep in the handle: the device copy of the joint tree and of the ray segments, and the host copy the
 // upload reads while it is in flight
 struct State {
-    uint8_t* d_idx = nullptr;
-    size_t d_bytes = 0;
+    DevBuf d_idx;
     std::vector<int32_t> host;
 };
 
@@ -280,8 +279,8 @@ int check_common(pg_handle* h, const char* who, int64_t n_poses, int rot_dim, co
 
 int upload(pg_handle* h, State* s, hipStream_t st) {
     const size_t bytes = s->host.size() * sizeof(int32_t);
-    PG_TRY(pg_grow(h, s->d_idx, s->d_bytes, bytes + bytes / 8, "pose layer index buffer"));
-    PG_HIP(h, hipMemcpyAsync(s->d_idx, s->host.data(), bytes, hipMemcpyHostToDevice, st));
+    PG_TRY(pg_grow(h, s->d_idx, bytes + bytes / 8, "pose layer index buffer"));
+    PG_HIP(h, hipMemcpyAsync(s->d_idx.p, s->host.data(), bytes, hipMemcpyHostToDevice, st));
     return PG_OK;
 }
 
@@ -292,7 +291,7 @@ extern "C" {
 void pg_poseopt_release(pg_handle* h) {
     if (!h || !h->poseopt) return;
     auto* s = static_cast<pgp::State*>(h->poseopt);
-    if (s->d_idx) (void)hipFree(s->d_idx);
+    pg_release(s->d_idx);
     delete s;
     h->poseopt = nullptr;
 }
@@ -326,7 +325,7 @@ int pg_poseopt_forward(pg_handle* h, void* stream, int64_t n_poses, int rot_dim,
     PG_HIP(h, hipSetDevice(h->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     PG_TRY(upload(h, s, st));
-    const int* d = reinterpret_cast<const int*>(s->d_idx);
+    const int* d = s->d_idx.as<const int>();
     hipLaunchKernelGGL(poseopt_fwd_kernel, dim3((unsigned)U), dim3(THREADS), 0, st, bones, pelvis, rest_pose, (int)rest_stride, d, max_depth,
                        ray_pose ? d + TREE_WORDS : nullptr, ray_pose ? d + TREE_WORDS + U + 1 : nullptr, rots, l2ws, skts, kps);
     PG_LAUNCH_CHECK(h, "pose layer forward kernel");
@@ -368,7 +367,7 @@ int pg_poseopt_backward(pg_handle* h, void* stream, int64_t n_poses, int rot_dim
     PG_HIP(h, hipSetDevice(h->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     PG_TRY(upload(h, s, st));
-    const int* d = reinterpret_cast<const int*>(s->d_idx);
+    const int* d = s->d_idx.as<const int>();
     hipLaunchKernelGGL(poseopt_bwd_kernel, dim3((unsigned)U), dim3(THREADS), 0, st, bones, pelvis, rest_pose, (int)rest_stride, d, max_depth,
                        d + TREE_WORDS, d + TREE_WORDS + U + 1, d_rots, d_l2ws, d_skts, d_kps, d_bones, d_pelvis);
     PG_LAUNCH_CHECK(h, "pose layer backward kernel");

@@ -1256,8 +1256,7 @@ struct Pass {               // one network evaluation kept for the backward pass
 };
 
 struct Tape {
-    uint8_t* buf = nullptr;
-    size_t bytes = 0;
+    DevBuf buf;
     bool valid = false;
     int64_t generation = 0;     // id of the forward pass the tape holds (pg_train_forward returns it, pg_train_backward checks it)
     long long n = 0;
@@ -1281,8 +1280,7 @@ struct Tape {
     float tau[2] = {0.f, 0.f};
     // the pose gradient's workspace, allocated by the first pg_train_backward_pose (a step without one never touches it):
     // dX [P, DXW] fp32 of one pass, then the per-ray 4 x 4s [n, 384] when the caller asks for their sum
-    uint8_t* pbuf = nullptr;
-    size_t pbytes = 0;
+    DevBuf pbuf;
     // single_net (one net, pass[0] holds the S coarse + N new rows of every ray): the merged depths, the rank map, noise1 by merged
     // position, the transmittances of the composite backward; multires_views = 0: the view weight widened for this step and the
     // gradient in that layout (narrow_views_kernel takes it back)
@@ -1821,8 +1819,8 @@ int tape_begin(const Step& a, Tape& t) {
     const bool single = h->cfg.single_net != 0;
     const TapeShape sh{a.n, a.S, a.N, single, h->train_precision == PG_PREC_BF16, h->cfg.framecode_ch > 0, h->cfg.multires_views == 0};
     // (the counting run leaves every pointer of the tape null; should the allocation fail they stay so, behind valid = false)
-    PG_TRY(pg_grow(h, t.buf, t.bytes, plan_tape(t, sh, nullptr), "training tape"));
-    if (plan_tape(t, sh, t.buf) > t.bytes) return pg_fail(h, PG_ESTATE, "training tape: the layout ends outside the allocation");
+    PG_TRY(pg_grow(h, t.buf, plan_tape(t, sh, nullptr), "training tape"));
+    if (plan_tape(t, sh, t.buf.p) > t.buf.bytes) return pg_fail(h, PG_ESTATE, "training tape: the layout ends outside the allocation");
     if (!a.cams) t.cams = nullptr;
     t.n = a.n; t.S = a.S; t.N = a.N; t.fc = sh.fc; t.bf16 = sh.bf16;     // (16-bit mode: the tape's activations and their gradients are bf16 arrays)
     t.single = single; t.views0 = sh.views0; t.has_fine = !single && a.N > 0;
@@ -1990,8 +1988,8 @@ extern "C" {
 void pg_train_release(pg_handle* h) {
     if (!h || !h->train) return;
     pgt::Tape* t = static_cast<pgt::Tape*>(h->train);
-    if (t->buf) (void)hipFree(t->buf);
-    if (t->pbuf) (void)hipFree(t->pbuf);
+    pg_release(t->buf);
+    pg_release(t->pbuf);
     delete t;
     h->train = nullptr;
     h->tape_out = false;
@@ -2053,9 +2051,9 @@ static int train_backward(pg_handle* h, void* stream, int64_t tape_id, const flo
         const long long Pm = std::max(t.pass[0].P, t.pass[1].P);
         const size_t dx_bytes = ((size_t)Pm * DXW * 4 + 255) & ~size_t(255);
         const size_t need = dx_bytes + (d_pose_stride == 0 ? (size_t)t.n * J * 16 * 4 : 0);
-        PG_TRY(pg_grow(h, t.pbuf, t.pbytes, need, "pose gradient workspace"));
-        dX = reinterpret_cast<float*>(t.pbuf);
-        per_ray = d_pose_stride == 0 ? reinterpret_cast<float*>(t.pbuf + dx_bytes) : d_skts;
+        PG_TRY(pg_grow(h, t.pbuf, need, "pose gradient workspace"));
+        dX = t.pbuf.as<float>();
+        per_ray = d_pose_stride == 0 ? reinterpret_cast<float*>(t.pbuf.p + dx_bytes) : d_skts;
     }
     if (t.single) {
         // d_raw of the P rows: zeroed, then per ray the fine (merged) composite's share of every row it reads and the coarse
@@ -2160,12 +2158,12 @@ int pg_stage_merged_composite_bwd(pg_handle* h, void* stream, int64_t n, int n_s
     if (n == 0) return PG_OK;
     PG_HIP(h, hipSetDevice(h->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    PG_TRY(pg_grow(h, h->ws, h->ws_bytes, (size_t)(S + N) * (size_t)n * sizeof(float), "workspace allocation"));   // Tbuf [S + N][n]
+    PG_TRY(pg_grow(h, h->ws, (size_t)(S + N) * (size_t)n * sizeof(float), "workspace allocation"));   // Tbuf [S + N][n]
     PG_HIP(h, hipMemsetAsync(d_raw, 0, (size_t)n * (S + N) * 16, s));
     const pgk::Density den = pgk::density_of(h->cfg);
     const CBwd cb{den.scale, den.rgb_eps, den.shift, den.act};
     hipLaunchKernelGGL(merged_composite_bwd_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, ray_batch, z_coarse, z_fine, raw, noise0, noise1,
-                       order, (long long)n, S, N, cb, d_rgb, d_acc, d_rgb0, d_acc0, d_raw, reinterpret_cast<float*>(h->ws));
+                       order, (long long)n, S, N, cb, d_rgb, d_acc, d_rgb0, d_acc0, d_raw, h->ws.as<float>());
     PG_LAUNCH_CHECK(h, "merged composite backward");
     return PG_OK;
 }

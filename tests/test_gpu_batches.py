@@ -227,6 +227,29 @@ def test_gather_without_backgrounds_at_the_frame_corners_and_through_item_maps(r
     assert batch["temp_val"].dtype == torch.float32 and np.array_equal(batch["temp_val"].cpu().numpy(), want_tv)
 
 
+def test_the_row_ring_wraps_and_regrows_under_consecutive_gathers(golden):
+    """Ten pg_batch_gather calls in a row on a fresh renderer, nothing waited for in between: more than the ring's 8 slots, so
+    calls 8 and 9 reuse the slots of calls 0 and 1.  n_img = 40 first meets an empty slot (call 2), then the slot call 0 sized
+    for n_img = 2 (call 8: 120 words against the 73 it holds), which is freed and allocated again."""
+    from posegen_amd import RayBatchSource, surreal_config
+    from posegen_amd.raycaster import HipRenderer
+    bank = golden_bank(golden, "centers")
+    F, P = bank["imgs"].shape[0], bank["imgs"].shape[1]
+    r = HipRenderer(surreal_config(), device=DEV)
+    try:
+        src = RayBatchSource(_device_bank(r, bank), 5, 1)
+        rng = np.random.default_rng(8)
+        calls = []
+        for n_img in (2, 2, 40, 2, 2, 2, 2, 2, 40, 2):
+            items, pix = rng.integers(0, F, n_img), rng.integers(0, P, (n_img, 5))
+            calls.append((items, pix, src.gather(items, pix)))
+        assert len(calls) > 8
+        for items, pix, batch in calls:
+            assert_batch_equals_restatement(batch, ref.gather(bank, items, pix))
+    finally:
+        r.close()
+
+
 def test_sampled_batches_equal_the_restatement_at_the_same_draws(renderer, golden):
     from posegen_amd import RayBatchSource
     bank = golden_bank(golden, "plain")

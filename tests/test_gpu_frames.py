@@ -347,6 +347,62 @@ def test_in_process_multi_device_frames_are_bitwise_those_of_one_device(n_frames
     assert np.array_equal(np.array(one[4]), np.array(multi[4]))
 
 
+def test_frame_buffers_regrow_on_a_live_handle_with_pinned_and_pageable_results():
+    """Three pg_render_frames calls on ONE two-worker handle (chunk 1024), each against a fresh single-device caster through
+    HipRenderer.render_frames, every array bitwise:
+      1. one 48 x 48 frame with rgb8, pageable results: a cut frame (phase B), pinned staging and its drain;
+      2. three 96 x 96 frames over a [hw,3] background, pinned results: two whole frames and a cut one; every frame
+         buffer, the pose, range and background buffers and the frame workspace of call 1 are too small and grow;
+      3. one 48 x 48 frame, pageable results, in the buffers call 2 left behind."""
+    import ctypes as C
+    from posegen_amd import _ffi, surreal_config
+    from posegen_amd.raycaster import HipRayCaster, _intrinsics
+    from posegen_amd.render import frame_setup
+    cfg = surreal_config()
+    model = syn.make_model(cfg, 0)
+    ndev = torch.cuda.device_count()
+    chunk = 1024
+    multi = HipRayCaster.from_weights(cfg, *model, device=DEV, precision="fp32", devices=list(range(ndev)) if ndev >= 2 else [0, 0])
+    multi.renderer.set_chunk(chunk)
+    S, N = cfg.n_samples, cfg.n_importance
+    hp = lambda a: None if a is None else C.c_void_p(a.ctypes.data)
+    try:
+        for n_frames, H, want_u8, with_bg, pinned in ((1, 48, True, False, False), (3, 96, False, True, True), (1, 48, False, False, False)):
+            W = H
+            _, kps, skts = syn.make_pose(n_frames, 5)
+            c2ws, focals = syn.make_camera(n_frames, H, W)
+            bg = torch.rand(H * W, 3, generator=torch.Generator().manual_seed(n_frames)) if with_bg else None
+            one = HipRayCaster.from_weights(cfg, *model, device=DEV, precision="fp32")
+            try:
+                one.renderer.set_chunk(chunk)
+                su = frame_setup(torch.tensor(c2ws), (H, W, focals), {"ray_caster": one}, kp=torch.tensor(kps), ext_scale=cfg.ext_scale)
+                for tl, br in su.bboxes:        # (inside the frame already) more than two nanmean groups each
+                    assert (int(br[0]) - int(tl[0])) * (int(br[1]) - int(tl[1])) > 2 * chunk
+                cyls = torch.as_tensor(su.cyls).detach().float().cpu()
+                want = one.renderer.render_frames(H, W, focals, c2ws, su.bboxes, skts, cyls, bg=bg, base_bg=1.0, want_uint8=want_u8)
+            finally:
+                one.renderer.close()
+            new = lambda c, dt: torch.empty((n_frames, H, W, c), dtype=dt, pin_memory=pinned).numpy()
+            got = [new(3, torch.float32), new(1, torch.float32), new(1, torch.float32)] + ([new(3, torch.uint8)] if want_u8 else [])
+            for a in got:
+                a.fill(7)
+            c2w_h = np.ascontiguousarray(np.asarray(c2ws, dtype=np.float32)[:, :3, :4])
+            intr = np.ascontiguousarray(np.stack([_intrinsics(H, W, f) for f in focals]).astype(np.float32))
+            bx = np.ascontiguousarray(np.array([[b[0][0], b[0][1], b[1][0], b[1][1]] for b in su.bboxes], dtype=np.int32))
+            sk = np.ascontiguousarray(skts, dtype=np.float32)
+            cy = np.ascontiguousarray(cyls.numpy(), dtype=np.float32)
+            bgh = None if bg is None else np.ascontiguousarray(bg.numpy(), dtype=np.float32)
+            r = multi.renderer
+            r._check(r.lib.pg_render_frames(r.handle, n_frames, H, W, hp(c2w_h), hp(intr), hp(bx), 0.0, 1.0, hp(sk), hp(cy), None, S, N, 0,
+                                            hp(bgh), 1.0, hp(got[0]), hp(got[1]), hp(got[2]), hp(got[3]) if want_u8 else None))
+            assert len(got) == len(want)
+            for a, b in zip(got, want):
+                assert a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a, b)
+            assert float(want[2].max()) > 0.5 and (want[0] != 1.0).any()      # a body was rendered
+    finally:
+        multi.renderer.close()
+
+
 def test_pose_boxes_on_device_equal_the_reference_boxes():
     """pg_pose_boxes: bounding cylinder (float32) and projected integer box (float64) of device key points --
     bit-for-bit the cylinders and boxes the reference computed for the golden fixture, and those of the host

@@ -377,6 +377,27 @@ def test_frame_plan_covers_every_ray_once_on_group_boundaries():
     assert all(x[1] == 0 and x[2] == 5000 for x in t) and sorted(x[3] for x in t) == list(range(8))
 
 
+def test_frame_plan_partition_and_layout_are_clean_under_address_and_ub_sanitizers(tmp_path):
+    """pg_frames_plan.h (what pg_render_frames decides before its first launch) as a stand-alone program with its own main:
+    F in 0..7 frames on 1..8 workers at chunk 1, 64 and 1024, ray counts of 0, below chunk and off its multiples.  Every frame
+    covered once and in order, cuts on multiples of chunk, the owner the worker of the first run, the runs of a worker's range
+    buffer disjoint and inside it, the four regions of a frame buffer disjoint, float-aligned and adding up to its bytes."""
+    clang = "/opt/rocm/lib/llvm/bin/clang++"
+    if not os.path.exists(clang):
+        pytest.skip("ROCm clang++ not found")
+    exe = str(tmp_path / "frames_plan_asan")
+    csrc = os.path.join(REPO, "posegen_amd", "csrc")
+    build = subprocess.run([clang, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                            "-fno-omit-frame-pointer", "-I", csrc, os.path.join(REPO, "tools", "sanitize", "frames_plan_asan.cpp"),
+                            "-o", exe], capture_output=True, text=True)
+    if build.returncode != 0 and "sanitizer" in build.stderr.lower() and "cannot find" in build.stderr.lower():
+        pytest.skip("sanitizer runtime not installed")
+    assert build.returncode == 0, build.stderr[-2000:]
+    run = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert run.returncode == 0, (run.stdout[-1500:], run.stderr[-3000:])
+    assert "1152 frame plans clean under ASan/UBSan" in run.stdout
+
+
 def test_bench_launches_itself_for_n_gpus_dry_run():
     """`python bench.py --gpus 2` with no rendezvous in the environment starts its own two
     ranks (as a child process) and relays rank 0's single JSON line; --dry-run swaps the renderer
