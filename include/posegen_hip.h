@@ -654,7 +654,7 @@ int pg_load_weights_device(pg_handle* h, void* stream, int which_net, const floa
  *   PG_ONCHIP_ALWAYS  (2): on chip whatever the sample count (no record workspace, a quarter of the HBM traffic at
  *                          128 + 16 samples, 2 % slower there).
  * The environment variable POSEGEN_ONCHIP = 0 / 1 / 2 sets the initial mode of handles created by the process.  The
- * compensated kernel's older form (pg_evalc.hip, POSEGEN_EVALC2=0) follows modes 0 / non-0. */
+ * compensated mode (PG_PREC_FP16C) has no per-ray records: the setting does not reach it. */
 #define PG_ONCHIP_RECORDS 0
 #define PG_ONCHIP_AUTO 1
 #define PG_ONCHIP_ALWAYS 2
@@ -681,9 +681,9 @@ int pg_profile_read_aux(pg_handle* h, int64_t* n_launches, double* total_ms);
  * pg_load_weights) into the weight stream and bias table the kernels consume, for tests
  * of the packing / stream-program logic.  stream_out may be NULL to query the size.
  * view_fact != 0 selects the stream of the factorised view layer the 16-bit kernels use
- * when a ray has >= 64 samples; view_fact == 2: the record variant of the compensated kernel;
- * view_fact == 3: the on-chip variant of the 16x16x32 kernel or of the compensated kernel's record form (no per-ray records: one pose,
- * no frame codes); view_fact == 4 with PG_PREC_FP16C: the weight image of pg_evalc2.hip (pg_program.h T; bias_out: the 16-row table). */
+ * when a ray has >= 64 samples; view_fact == 3: the on-chip variant of the 16x16x32 kernel (no per-ray records);
+ * view_fact == 4 with PG_PREC_FP16C: the weight image of pg_evalc2.hip (pg_program.h T; bias_out: the 16-row table).
+ * PG_PREC_FP16C packs 0 (the k-major stream of pg_eval32.hip) and 4 only: 1, 2 and 3 return PG_EINVAL. */
 int pg_debug_pack(const float* const* tensors, const int64_t* shapes, int n_tensors,
                   int framecode_ch, int precision, int view_fact, uint8_t* stream_out, int64_t stream_cap,
                   int64_t* stream_bytes, float* bias_out /* 82*32 floats or NULL */,

@@ -131,10 +131,7 @@ enum Form {
     F_REC16,            // pg_eval16r.hip: bf16 / fp16, 16x16x32 MFMAs, the view layer factorised over per-ray records (pg_rayrec.hip)
     F_ONCHIP16,         // ... its on-chip variant: no per-ray records
     F_C2,               // pg_evalc2.hip: compensated fp16, the out tiles split over the waves
-    F_COMP_DIRECT,      // pg_evalc.hip: compensated fp16, direct view layer
-    F_COMP_REC,         // ... record variant (per-ray records of ray_records_c_kernel)
-    F_COMP_ONCHIP,      // ... on-chip form of the record variant (one pose per launch, no frame codes)
-    F_KMAJOR,           // pg_eval32.hip, k-major: fp32, the split-operand precisions, and PG_PREC_FP16C where pg_evalc*.hip do not run
+    F_KMAJOR,           // pg_eval32.hip, k-major: fp32, the split-operand precisions, and PG_PREC_FP16C where pg_evalc2.hip does not run
     F_COUNT
 };
 
@@ -145,9 +142,7 @@ enum Form {
 constexpr int PASS_WALK_RHO = 99;
 struct Switches {
     bool view_fact = true;          // POSEGEN_VIEW_FACT=0: the direct 32x32x16 kernel (pg_eval16.hip) for every 16-bit call
-    bool comp_kernel = true;        // POSEGEN_COMP_KERNEL=0: PG_PREC_FP16C in the k-major kernel of pg_eval32.hip, same arithmetic
-    bool comp_rec = true;           // POSEGEN_COMP_REC=0: the direct form of pg_evalc.hip whatever the sample count
-    bool evalc2 = true;             // POSEGEN_EVALC2=0: keeps fp16c calls on pg_evalc.hip (and the record / on-chip forms' tests)
+    bool comp_kernel = true;        // POSEGEN_COMP_KERNEL=0: PG_PREC_FP16C in the k-major kernel of pg_eval32.hip instead of pg_evalc2.hip, same arithmetic
     int onchip = PG_ONCHIP_AUTO;    // POSEGEN_ONCHIP = 0 / 1 / 2: the pg_set_onchip mode a new handle starts in
     bool empty_skip = true;         // POSEGEN_EMPTY_SKIP=0: the pg_set_empty_skip setting a new handle starts in (A/B on one library)
     int pass_walk = PASS_WALK_RHO;  // POSEGEN_PASS_WALK=0: the static pass walk of the kernels with limb masks (pg_device.h PassWalk); n > 0: rotation n
@@ -158,8 +153,6 @@ const Switches& switches() {
         Switches s;
         s.view_fact = !off("POSEGEN_VIEW_FACT");
         s.comp_kernel = !off("POSEGEN_COMP_KERNEL");
-        s.comp_rec = !off("POSEGEN_COMP_REC");
-        s.evalc2 = !off("POSEGEN_EVALC2");
         s.empty_skip = !off("POSEGEN_EMPTY_SKIP");
         const char* e = std::getenv("POSEGEN_ONCHIP");
         s.onchip = e && e[0] == '0' ? PG_ONCHIP_RECORDS : e && e[0] == '2' ? PG_ONCHIP_ALWAYS : PG_ONCHIP_AUTO;
@@ -184,8 +177,7 @@ struct CallFacts {
 // rgb0/acc0): plain fp16 there, compensated fp16 wherever the pass produces the returned maps
 int pass_precision(int mode, bool guide_pass) { return mode == PG_PREC_FP16M ? (guide_pass ? PG_PREC_FP16 : PG_PREC_FP16C) : mode; }
 
-// The on-chip variants run for rays of at most ONCHIP_MAX_S samples.  The 16x16x32 kernel's on-chip variant takes per-ray poses and
-// frame codes too; pg_evalc.hip's on-chip form needs one pose per launch and no frame codes and has no sample-count rule.
+// The on-chip variant of the 16x16x32 kernel runs for rays of at most ONCHIP_MAX_S samples, per-ray poses and frame codes included.
 // The on-chip variant forms a ray's rows in every pass the ray has points in, the record variant once
 // per ray in a kernel in front: measured on one box (profiles/r5_ab_onchip_by_samples.txt, bf16 512 x 512 frames) the two
 // tie at 64 + 16 samples (31.7 / 31.8 ms), on-chip wins at 96 + 16 (43.3 / 43.6) and records win from 128 + 16 on (59.3 /
@@ -205,16 +197,12 @@ Form pick_form(const CallFacts& c, const Switches& sw) {
         const bool dbg_ok = !c.dbg || c.dbg_stage == 99 || (c.dbg_stage == 97 && c.pose_stride == 0 && !c.fc);
         return by_mode && dbg_ok ? F_ONCHIP16 : F_REC16;
     }
-    // PG_PREC_FP16C runs in its dedicated kernels when a ray has >= COMP_MIN_S samples (then a 128-point pass touches
-    // <= MAXR_C rays) and the points come from rays; otherwise in the k-major kernel of pg_eval32.hip, same arithmetic
-    if (!(c.prec == PG_PREC_FP16C && from_rays && sw.comp_kernel && c.S >= COMP_MIN_S)) return F_KMAJOR;
-    // >= pgp::T::MIN_S samples per ray: out tiles over the waves (pg_evalc2.hip), whatever the pose stride, with or without frame codes
-    if (sw.evalc2 && c.S >= pgp::T::MIN_S && (!c.dbg || c.dbg_stage == 99 || c.dbg_stage == 97)) return F_C2;
-    // pg_evalc.hip: its record variant when a ray has >= FACT_MIN_S samples, that variant's on-chip form where it applies
-    if (!(sw.comp_rec && c.S >= FACT_MIN_S)) return F_COMP_DIRECT;
-    const bool plain = c.onchip_mode != PG_ONCHIP_RECORDS && !c.fc && c.pose_stride == 0;
-    const bool dbg_ok = !c.dbg || c.dbg_stage == 98 || c.dbg_stage == 99;                     // (98 / 99: diagnosis builds' dumps)
-    return plain && dbg_ok ? F_COMP_ONCHIP : F_COMP_REC;
+    // PG_PREC_FP16C runs in pg_evalc2.hip (out tiles over the waves) when the points come from rays of >= pgp::T::MIN_S samples (then a
+    // 128-point pass touches <= pgp::T::MAXR rays), whatever the pose stride, with or without frame codes; that kernel has no activation
+    // tap (97: its limb-mask counters; 99: the stamps of a PG_STAMPS build).  Every other call, of this precision too, runs in the
+    // k-major kernel of pg_eval32.hip, same arithmetic
+    const bool c2 = c.prec == PG_PREC_FP16C && sw.comp_kernel && from_rays && c.S >= pgp::T::MIN_S && (!c.dbg || c.dbg_stage == 97 || c.dbg_stage == 99);
+    return c2 ? F_C2 : F_KMAJOR;
 }
 
 // the usual call of a precision: rays with >= 64 samples, one pose per launch, no points, no noise, no debug.  Its form is what
@@ -250,12 +238,6 @@ constexpr FormInfo FORMS[F_COUNT] = {
     /* F_C2 (no stream: the whole image) */
                         {IMG_C2, IMG_NONE, IMG_BIAS16, 0, pg_evalc2_points_per_pass, one_wg_per_cu,
                          [](int) -> int64_t { return pgp::T::TOTAL; }, PG_MFMA(pgp::T::MFMA16_PER_PASS / 2 / (pgp::T::PTS / 32))},
-    /* F_COMP_DIRECT */ {IMG_COMP_DIRECT, IMG_NONE, IMG_BIAS, 0, pg_evalc_points_per_pass, one_wg_per_cu,
-                         PG_CHUNKS(pgp::C::NCHUNK), PG_MFMA(pgp::C::MFMA_PER_GROUP(fc))},
-    /* F_COMP_REC    */ {IMG_COMP_REC, IMG_VYC, IMG_BIAS, RECC_Y_BYTES, pg_evalc_points_per_pass, one_wg_per_cu,
-                         PG_CHUNKS(pgp::C::NCHUNK_R), PG_MFMA(pgp::C::MFMA_PER_GROUP_R)},
-    /* F_COMP_ONCHIP */ {IMG_COMP_ONCHIP, IMG_NONE, IMG_BIAS, 0, pg_evalc_points_per_pass, one_wg_per_cu,
-                         PG_CHUNKS(pgp::C::NCHUNK_OC), PG_MFMA(pgp::C::MFMA_PER_GROUP_R)},
     /* F_KMAJOR      */ {IMG_DIRECT, IMG_NONE, IMG_BIAS, 0, pg_eval32_points_per_pass, one_wg_per_cu,
                          [](int prec) -> int64_t { return (int64_t)(prec == PG_PREC_FP32 ? pgp::B::NCHUNK : pgp::B::NCHUNK_FOLD) * CHUNK_BYTES; },
                          PG_MFMA(prec == PG_PREC_FP32 ? mfma_direct(fc) * 8 : (mfma_direct(fc) - NT * pgp::A::HU) * (prec == PG_PREC_FP16C ? 2 : 3))},
@@ -288,10 +270,7 @@ int pack_image(pg_handle* h, int which, const pgpack::NetTensors& t, int id, Pac
     int rc = 0;
     switch (id < IMG_PER_PREC_END ? id - prec : id) {
     case IMG_DIRECT:
-        if ((rc = pgpack::pack_stream(t, prec, fc, false, p.b))) return pg_fail(h, PG_EINVAL, "weight stream packing failed (%d) for precision %d", rc, prec);
-        break;
-    case IMG_COMP_DIRECT:
-        if ((rc = pgpack::pack_stream(t, prec, fc, true, p.b))) return pg_fail(h, PG_EINVAL, "weight stream packing failed (%d) for precision %d", rc, prec);
+        if ((rc = pgpack::pack_stream(t, prec, fc, p.b))) return pg_fail(h, PG_EINVAL, "weight stream packing failed (%d) for precision %d", rc, prec);
         break;
     case IMG_REC16:
         if ((rc = pgpack::pack_stream_r(t, prec, p.b))) return pg_fail(h, PG_EINVAL, "16x16x32 weight stream packing failed (%d) for precision %d", rc, prec);
@@ -301,13 +280,6 @@ int pack_image(pg_handle* h, int which, const pgpack::NetTensors& t, int id, Pac
         break;
     case IMG_VY16:
         if (pgpack::pack_vy(t, prec, fc, p.b) != 0) return pg_fail(h, PG_EINVAL, "Y-stage weight packing failed for precision %d", prec);
-        break;
-    case IMG_COMP_REC:
-        if ((rc = pgpack::pack_stream(t, prec, fc, true, p.b, nullptr, true))) return pg_fail(h, PG_EINVAL, "compensated-fp16 record-variant stream packing failed (%d)", rc);
-        break;
-    case IMG_VYC: pgpack::pack_vyc(t, fc, p.f); break;
-    case IMG_COMP_ONCHIP:
-        if ((rc = pgpack::pack_stream(t, prec, false, true, p.b, nullptr, true, true))) return pg_fail(h, PG_EINVAL, "compensated-fp16 on-chip stream packing failed (%d)", rc);
         break;
     case IMG_C2:
         if ((rc = pgpack::pack_c2(t, fc, p.b, src))) return pg_fail(h, PG_EINVAL, "compensated-fp16 tile-split weight packing failed (%d)", rc);
@@ -539,9 +511,9 @@ int launch_eval_one(pg_handle* h, void* stream, EvalCall c) {
         a.rec_y = h->rec.p;
         a.rec_ab = reinterpret_cast<const float*>(h->rec.p + (size_t)(n + REC_PAD_RAYS) * y_bytes);
         // the padding rays behind the last record are fetched by the last passes (their values are multiplied by
-        // zero weights at most): keep them finite whatever the buffer held before.  The record kernels write rays
+        // zero weights at most): keep them finite whatever the buffer held before.  The record kernel writes rays
         // < n only, so the padding of an (n, record size) pair stays zero until another pair moves it.
-        // (every writer of h->rec -- the two record kernels -- stores rays < n only; anything else that is ever handed the
+        // (every writer of h->rec -- the record kernel -- stores rays < n only; anything else that is ever handed the
         // buffer must reset rec_pad_n to -1, as ensure_rec does)
         if (h->rec_pad_n != n || h->rec_pad_y != y_bytes || h->rec_pad_stream != stream) {
             PG_HIP(h, hipMemsetAsync(h->rec.p + (size_t)n * y_bytes, 0, (size_t)REC_PAD_RAYS * y_bytes, static_cast<hipStream_t>(stream)));
@@ -581,7 +553,7 @@ int launch_eval_one(pg_handle* h, void* stream, EvalCall c) {
         ra.pose_stride = c.pose_stride; ra.n_rays = (int)n; ra.n_codes = ns.n_codes;
         ra.z = c.z; ra.S = c.S;
         PG_TRY(timed_launch(h, stream, h->ev_aux, "ray record kernel", [&] {
-            return form == F_COMP_REC ? pg_launch_ray_records_c(&ra, fc, h->n_cu, stream) : pg_launch_ray_records(&ra, prec == PG_PREC_FP16, fc, h->n_cu, stream);
+            return pg_launch_ray_records(&ra, prec == PG_PREC_FP16, fc, h->n_cu, stream);
         }));
     }
     const int f16 = prec == PG_PREC_FP16;
@@ -591,9 +563,6 @@ int launch_eval_one(pg_handle* h, void* stream, EvalCall c) {
         case F_REC16:       return pg_launch_eval16r(&a, f16, fc, 0, grid, stream);
         case F_ONCHIP16:    return pg_launch_eval16r(&a, f16, fc, 1, grid, stream);
         case F_C2:          return pg_launch_evalc2(&a, fc, grid, stream);
-        case F_COMP_DIRECT: return pg_launch_evalc(&a, fc, 0, grid, stream);
-        case F_COMP_REC:    return pg_launch_evalc(&a, fc, 1, grid, stream);
-        case F_COMP_ONCHIP: return pg_launch_evalc(&a, fc, 2, grid, stream);
         default:            return pg_launch_eval32(&a, prec, fc, grid, stream);
         }
     }));
@@ -1095,12 +1064,13 @@ int pg_debug_pack(const float* const* tensors, const int64_t* shapes, int n_tens
     cfg.framecode_ch = framecode_ch;
     std::vector<uint8_t> packed;
     const bool rprog = view_fact != 0 && is_shape_a(precision);       // the 16x16x32 program of pg_eval16r.hip
-    const bool crec = view_fact >= 2 && precision == PG_PREC_FP16C;     // record variant of pg_evalc.hip (3: its on-chip form)
     const bool c2 = view_fact == 4 && precision == PG_PREC_FP16C;       // the weight image of pg_evalc2.hip (pg_program.h T)
+    if (view_fact != 0 && !rprog && !c2)
+        return pg_fail(nullptr, PG_EINVAL, precision == PG_PREC_FP16C ? "pg_debug_pack: PG_PREC_FP16C packs view_fact 0 (the k-major stream of pg_eval32.hip) or 4 (the image of pg_evalc2.hip), not %d"
+                                                                      : "pg_debug_pack: this precision packs view_fact 0 (its k-major stream) only, not %d", view_fact);
     const int rc = c2 ? pgpack::pack_c2(tensors_of(ns, cfg), framecode_ch > 0, packed)
                  : rprog ? pgpack::pack_stream_r(tensors_of(ns, cfg), precision, packed, view_fact == 3)
-                         : pgpack::pack_stream(tensors_of(ns, cfg), precision, framecode_ch > 0, view_fact != 0, packed, nullptr, crec,
-                                               crec && view_fact == 3);
+                         : pgpack::pack_stream(tensors_of(ns, cfg), precision, framecode_ch > 0, packed);
     if (rc != 0) return pg_fail(nullptr, PG_EINVAL, "pg_debug_pack: packing failed (%d)", rc);
     if (stream_bytes) *stream_bytes = (int64_t)packed.size();
     if (chunk_bytes) *chunk_bytes = CHUNK_BYTES;
@@ -1198,13 +1168,8 @@ int pg_debug_pack_vy(const float* const* tensors, const int64_t* shapes, int n_t
     pg_config cfg{};
     cfg.framecode_ch = framecode_ch;
     std::vector<uint8_t> vy;
-    if (precision == PG_PREC_FP16C) {       // the fp32 Y-stage weights of ray_records_c_kernel
-        std::vector<float> f;
-        pgpack::pack_vyc(tensors_of(ns, cfg), framecode_ch > 0, f);
-        vy.resize(f.size() * sizeof(float));
-        std::memcpy(vy.data(), f.data(), vy.size());
-    } else if (pgpack::pack_vy(tensors_of(ns, cfg), precision, framecode_ch > 0, vy) != 0)
-        return pg_fail(nullptr, PG_EINVAL, "pg_debug_pack_vy: 16-bit and compensated-fp16 precisions only");
+    if (pgpack::pack_vy(tensors_of(ns, cfg), precision, framecode_ch > 0, vy) != 0)
+        return pg_fail(nullptr, PG_EINVAL, "pg_debug_pack_vy: 16-bit precisions only");
     if (out_bytes) *out_bytes = (int64_t)vy.size();
     if (out) {
         if ((int64_t)vy.size() > cap) return pg_fail(nullptr, PG_EINVAL, "pg_debug_pack_vy: buffer too small");

@@ -27,11 +27,7 @@ enum Image : int {
     IMG_ONCHIP16 = IMG_REC16 + PG_PREC_COUNT,       // ... its on-chip variant (no per-ray records): stream
     IMG_VY16 = IMG_ONCHIP16 + PG_PREC_COUNT,        // Y-stage weights of the per-ray record kernel (pg_rayrec.hip)
     IMG_PER_PREC_END = IMG_VY16 + PG_PREC_COUNT,
-    IMG_COMP_DIRECT = IMG_PER_PREC_END,             // compensated-fp16 kernel (pg_evalc.hip), direct view layer: stream (shape C)
-    IMG_COMP_REC,                                   // ... record variant (REC): stream,
-    IMG_VYC,                                        // ... and the fp32 Y-stage weights of its record kernel
-    IMG_COMP_ONCHIP,                                // ... on-chip form of the record variant (OC): stream
-    IMG_C2,                                         // compensated-fp16 kernel with the out tiles over the waves (pg_evalc2.hip): weights (pg_program.h T)
+    IMG_C2 = IMG_PER_PREC_END,                      // compensated-fp16 kernel with the out tiles over the waves (pg_evalc2.hip): weights (pg_program.h T)
     IMG_YCODE,                                      // on-chip 16x16x32 variant with frame codes: Yc[n_codes + 1][128] = W_view[:, 904:920] codes[c]
     IMG_BIAS16,                                     // 16-row bias table (the 16x16x32 kernel, pg_evalc2.hip)
     IMG_BIAS,                                       // 32-row bias table (every other kernel)

@@ -1,5 +1,4 @@
-// pg_comp.h -- the compensated-fp16 arithmetic (PG_PREC_FP16C) shared by the kernels that compute in it
-// (pg_evalc.hip: points over waves, activations in registers; pg_evalc2.hip: out tiles over waves, activations in LDS):
+// pg_comp.h -- the compensated-fp16 arithmetic (PG_PREC_FP16C) of pg_evalc2.hip (out tiles over waves, activations in LDS):
 // the fp16 pair of a value, a B-operand fragment pair, and the embedding values of one joint.
 #pragma once
 #include "pg_eval16_common.h"
@@ -13,47 +12,26 @@ using VC = f16x8;
 // is formed by v_cvt_pk_f16_f32 from the fp32 value and the residual's copy by v_fma_mixlo_f16
 // from the exact product that produced the value -- two roundings that disagree on ties, after
 // which the compensation has the wrong sign (an error of a full fp16 ulp).
-// step A: two values -> their (optionally ReLU'd) fp32 values and the packed x1 pair
-template <bool RELU>
-__device__ __forceinline__ void conv_a(float a, float b, float& ra, float& rb, unsigned& h) {
-    if (RELU) {
-        asm("v_max_f32 %0, 0, %3\n\tv_max_f32 %1, 0, %4\n\tv_cvt_pk_f16_f32 %2, %0, %1"
-            : "=&v"(ra), "=&v"(rb), "=&v"(h) : "v"(a), "v"(b));
-    } else {
-        ra = a; rb = b;
-        asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(h) : "v"(a), "v"(b));
-    }
+// step A: two values -> the packed x1 pair
+__device__ __forceinline__ void conv_a(float a, float b, unsigned& h) {
+    asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(h) : "v"(a), "v"(b));
 }
 // step B: d = x - x1 (exact), t = S d + x1, x2 pair = f16(t).  v_fma_mix_f32 reads the fp16 halves of
 // `h` directly.  The trailing s_nop 1 provides the wait states a VALU write needs before an MFMA may
 // read the register (hipcc pads nothing for inline asm).
-template <bool NOP = true>
 __device__ __forceinline__ unsigned conv_b(float ra, float rb, unsigned h, float s) {
     unsigned x2;
     float da, db;
-    if (NOP)
-        asm("v_fma_mix_f32 %1, %3, -1.0, %4 op_sel_hi:[1,0,0]\n\t"
-            "v_fma_mix_f32 %2, %3, -1.0, %5 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
-            "v_fma_mix_f32 %1, %1, %6, %3 op_sel_hi:[0,0,1]\n\t"
-            "v_fma_mix_f32 %2, %2, %6, %3 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
-            "v_cvt_pk_f16_f32 %0, %1, %2\n\ts_nop 1"
-            : "=&v"(x2), "=&v"(da), "=&v"(db) : "v"(h), "v"(ra), "v"(rb), "s"(s));
-    else        // the fragment is consumed a whole unit row later: no wait states needed
-        asm("v_fma_mix_f32 %1, %3, -1.0, %4 op_sel_hi:[1,0,0]\n\t"
-            "v_fma_mix_f32 %2, %3, -1.0, %5 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
-            "v_fma_mix_f32 %1, %1, %6, %3 op_sel_hi:[0,0,1]\n\t"
-            "v_fma_mix_f32 %2, %2, %6, %3 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
-            "v_cvt_pk_f16_f32 %0, %1, %2"
-            : "=&v"(x2), "=&v"(da), "=&v"(db) : "v"(h), "v"(ra), "v"(rb), "s"(s));
+    asm("v_fma_mix_f32 %1, %3, -1.0, %4 op_sel_hi:[1,0,0]\n\t"
+        "v_fma_mix_f32 %2, %3, -1.0, %5 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
+        "v_fma_mix_f32 %1, %1, %6, %3 op_sel_hi:[0,0,1]\n\t"
+        "v_fma_mix_f32 %2, %2, %6, %3 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
+        "v_cvt_pk_f16_f32 %0, %1, %2\n\ts_nop 1"
+        : "=&v"(x2), "=&v"(da), "=&v"(db) : "v"(h), "v"(ra), "v"(rb), "s"(s));
     return x2;
 }
 
 struct FragC { unsigned x1[4], x2[4]; };       // one input unit: 8 values per lane as the two MFMA B operands
-
-__device__ __forceinline__ VC frag_v(const unsigned* p) {
-    const u32x4 v = {p[0], p[1], p[2], p[3]};
-    return __builtin_bit_cast(VC, v);
-}
 
 // the 18 density-input values of one joint (joint_values_q of pg_device.h) for the compensated mode:
 // hardware transcendentals, but every octave's sin/cos straight from v_sin/v_cos (revolutions, exact
@@ -77,11 +55,10 @@ __device__ __forceinline__ void joint_values_c(float qx, float qy, float qz, flo
 
 __device__ __forceinline__ FragC frag_of(const float* x, float s129) {
     FragC f;
-    float ra, rb;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        conv_a<false>(x[2 * j], x[2 * j + 1], ra, rb, f.x1[j]);
-        f.x2[j] = conv_b(ra, rb, f.x1[j], s129);
+        conv_a(x[2 * j], x[2 * j + 1], f.x1[j]);
+        f.x2[j] = conv_b(x[2 * j], x[2 * j + 1], f.x1[j], s129);
     }
     return f;
 }

@@ -38,7 +38,7 @@ struct EvalArgs {
     int n_iters;              // workgroup passes = ceil(n_points / points per pass)
     float tau_v, tau_d;
     int dbg_stage;            // which activation `dbg` receives (see pg_stage_eval)
-    int far_skip;             // 1: limbs out of cutoff range are skipped (pg_eval16r.hip, pg_evalc.hip REC); 0: every limb computed
+    int far_skip;             // 1: limbs out of cutoff range are skipped (pg_eval16r.hip, pg_evalc2.hip); 0: every limb computed
     int skip_empty;           // 1: a wave whose points all have sigma <= 0 leaves the colour branch out (pg_eval16r.hip); set only where the caller composites with the ReLU density, no density noise, and hands no raw out
     int walk_rho;             // PassWalk: rotation of the pass walk per round, < grid (0: the static walk); kernels with limb masks only
 };
@@ -60,7 +60,7 @@ struct RecArgs {
 };
 
 // The passes of one workgroup of a persistent grid of G workgroups, for the kernels whose passes cost what their data
-// asks for (limb masks: pg_eval16r.hip, pg_evalc.hip, pg_evalc2.hip).  Round k of the grid is the passes k G .. k G + G - 1;
+// asks for (limb masks: pg_eval16r.hip, pg_evalc2.hip).  Round k of the grid is the passes k G .. k G + G - 1;
 // in round k workgroup b takes pass k G + ((b + k rho) mod G).  rho = 0 is the static walk `it = b + k G`: with rays in
 // row-major frame order and a row a whole number of passes that divides G (or a multiple of it), a workgroup then stays on
 // one column strip of the frame for the whole launch, and the strips that cross the body cost more than the others.  With
@@ -107,7 +107,7 @@ struct PassWalk {
     __host__ __device__ __forceinline__ void advance() { it = itn; c = cn; p0 = p0n; r0 = r0n; off0 = off0n; }
 };
 
-// slot -> joint tables of pg_layout.h (PERM16, PERMC) as a device lookup at a run-time index: 24 x 5 bits in two constants
+// slot -> joint table of pg_layout.h (PERM16) as a device lookup at a run-time index: 24 x 5 bits in two constants
 template <const int (&P)[24]>
 __device__ __forceinline__ int perm_dev(int s) {
     constexpr unsigned long long lo = [] { unsigned long long v = 0; for (int i = 0; i < 12; ++i) v |= (unsigned long long)P[i] << (5 * i); return v; }();
@@ -115,7 +115,6 @@ __device__ __forceinline__ int perm_dev(int s) {
     return (int)(((s < 12 ? lo : hi) >> (5 * (s < 12 ? s : s - 12))) & 31);
 }
 __device__ __forceinline__ int slot_joint_dev(int s) { return perm_dev<PERM16>(s); }
-__device__ __forceinline__ int slotc_joint_dev(int s) { return perm_dev<PERMC>(s); }
 
 // The opt-in to > 64 KiB of dynamic LDS is per (kernel, device): set once per device, from any host
 // thread (pg_render_frames drives one thread per device).

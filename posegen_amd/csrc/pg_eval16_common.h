@@ -395,7 +395,7 @@ __device__ __forceinline__ void dma_dwords(const void* base, uint32_t lane_off, 
     asm volatile("s_nop 4\n\ts_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2" :: "s"(lds_dst), "v"(lane_off), "s"(base) : "memory");
 }
 
-// One (ray, joint slot) record row of the on-chip variants (pg_eval16r.hip OC, pg_evalc.hip OC) -- what pg_rayrec.hip writes to HBM for the record variant:
+// One (ray, joint slot) record row of the on-chip variants (pg_eval16r.hip OC, pg_evalc2.hip) -- what pg_rayrec.hip writes to HBM for the record variant:
 // a = R_j o + t_j, b = R_j d (encoders.py:8-37) and, in a.w, the squared distance of the ray's sampled segment
 // [z0, z1] from the joint (pass_far_mask).  sk = the joint's three bone rows (R | t), ray = (o, d).
 __device__ __forceinline__ void ab_row(const float* sk, const float* ray, float z0, float z1, float4* dst) {

@@ -2,13 +2,13 @@
 // OUT TILES of every layer are split over the waves and the activations live in LDS.  Shape T of pg_program.h.
 //
 // Replaces RayCaster.encode_inputs + run_network + NeRF.forward for one net (reference core/raycasters.py:476-577,
-// core/networks/nerf.py:90-148, core/encoders.py, core/cutoff_embedder.py) on n*S points p = o + d*z, like pg_evalc.hip,
-// with the same arithmetic: every product W x = (S-1) w1 x1 + w2 x2 as two fp16 MFMAs into one fp32 accumulator
+// core/networks/nerf.py:90-148, core/encoders.py, core/cutoff_embedder.py) on n*S points p = o + d*z, in compensated
+// arithmetic: every product W x = (S-1) w1 x1 + w2 x2 as two fp16 MFMAs into one fp32 accumulator
 // (pg_comp.h), hardware sin / cos per octave, Y / S split like a weight.
 //
-// Why a second form.  pg_evalc.hip gives a wave 32 points and all out channels: two accumulator sets of 128 registers,
-// hence ONE wave per SIMD, and every MFMA needs its own 1-KiB weight fragment from the LDS ring -- its matrix pipe is
-// busy half the time (profiles/r4_fp16c_*).  Here a workgroup of 8 waves (two per SIMD) carries 128 points through the
+// Why a second form.  The first one (retired: DESIGN.md 2.2) gave a wave 32 points and all out channels: two accumulator
+// sets of 128 registers, hence ONE wave per SIMD, and every MFMA needed its own 1-KiB weight fragment from the LDS ring --
+// its matrix pipe was busy half the time (profiles/r4_fp16c_*).  Here a workgroup of 8 waves (two per SIMD) carries 128 points through the
 // net together:
 //   * wave w owns out channels 32 w .. 32 w + 31 of every layer (two 16-row tiles of v_mfma_f32_16x16x32_f16) for ALL
 //     128 points (8 column tiles): 64 accumulator registers, one set;
@@ -211,7 +211,7 @@ __device__ __forceinline__ void settle(f32x4 (&acc)[2][TT::NCT]) {
     }
 }
 // one value pair -> its ReLU'd fp16 pair, pinned (asm volatile) between the hand-issued reads of the MFMA steps: the
-// instructions of conv_a<true> + conv_b (pg_comp.h)
+// instructions of conv_a + conv_b (pg_comp.h) behind a v_max_f32
 // Every register the block WRITES is a "+v" operand that lives through the whole run of MFMA steps (CState): a fresh
 // temporary could be given a register that an MFMA of the step before has just written (hipcc renames the accumulators
 // freely), and a VALU write to it inside the same 7 slots is the same hazard (tools/audit_asm_hazards.py).

@@ -67,18 +67,15 @@ struct BatchGather {
 }  // namespace pgk
 
 extern "C" {
-// ---- the fused eval kernels and the per-ray record kernels in front of them (pg_eval*.hip, pg_rayrec.hip) ----
+// ---- the fused eval kernels and the per-ray record kernel in front of them (pg_eval*.hip, pg_rayrec.hip) ----
 int pg_launch_eval16(const pgd::EvalArgs* a, int fp16, int framecode, int grid, void* stream);
 int pg_launch_eval16r(const pgd::EvalArgs* a, int fp16, int framecode, int onchip, int grid, void* stream);
 int pg_launch_eval32(const pgd::EvalArgs* a, int precision, int framecode, int grid, void* stream);
-int pg_launch_evalc(const pgd::EvalArgs* a, int framecode, int rec, int grid, void* stream);
 int pg_launch_evalc2(const pgd::EvalArgs* a, int framecode, int grid, void* stream);
 int pg_launch_ray_records(const pgd::RecArgs* a, int fp16, int framecode, int n_cu, void* stream);
-int pg_launch_ray_records_c(const pgd::RecArgs* a, int framecode, int n_cu, void* stream);
 int pg_eval16_points_per_pass(void);
 int pg_eval16_wgs_per_cu(void);
 int pg_eval32_points_per_pass(void);
-int pg_evalc_points_per_pass(void);
 int pg_evalc2_points_per_pass(void);
 // ---- pg_kernels.hip: sampling, compositing, poses, frames, calibration ----
 int pg_launch_sample_coarse(const float* rays, const float* cyls, long long cyl_stride, long long n, int chunk, int S, int lindisp, float* near_far,

@@ -128,17 +128,6 @@ PG_HD constexpr int vy_slot(int w, int e, bool fc) {
     return e < JH ? JH * (w >> 2) + e : ((fc && (w >> 2) == 0 && e == JH) ? JC : -1);
 }
 
-// ---- per-ray LDS slot of the compensated-fp16 kernel (pg_evalc.hip), floats -----------------
-// AB: per joint a = R_j o + t_j and b = R_j d (8 floats, 2 pads): q = a + z b; DTAB: the view table
-// of the classic slot (2 halves x DSEQ); CODE: the ray's frame code
-constexpr int SLOTC_AB = 0;                       // 24 x 8
-constexpr int SLOTC_DTAB = J * 8;                 // 192
-constexpr int SLOTC_CODE = SLOTC_DTAB + 2 * DSEQ; // 848
-constexpr int SLOTC_FLOATS = SLOTC_CODE + FC_CH;  // 864, multiple of 4
-constexpr int MAXR_C = 5;                         // rays overlapped by a 128-point pass when S >= 32
-constexpr int COMP_MIN_S = 32;
-static_assert(SLOTC_FLOATS % 4 == 0 && SLOTC_DTAB % 4 == 0 && SLOTC_CODE % 4 == 0, "LDS alignment");
-
 // ---- "small tile" layout of pg_eval16r.hip (v_mfma_f32_16x16x32, factorised view layer) ----
 // A = weights 16 out channels x 32 k, B = activations 32 k x 16 points, C = 16 x 16: lane
 // (g = lane>>4, col = lane&15) holds rows 4g..4g+3.  A wave still owns 32 points = two column
@@ -203,53 +192,6 @@ constexpr int REC_PAD_RAYS = 8;
 constexpr int REC_TILE_RAYS = 32;                 // rays per MFMA tile of the record kernel (rows of a 32x32x16 MFMA)
 constexpr int LDS_AB_BYTES = 4096;                // one AB buffer in LDS: MAXR_F x 768 = 3840 -> 4 DMA pieces of 1 KiB
 static_assert(MAXR_F * REC_AB_BYTES <= LDS_AB_BYTES && LDS_AB_BYTES / REC_AB_BYTES + 1 <= REC_PAD_RAYS, "AB fetch stays inside the padded array");
-
-// ---- per-ray records of the compensated-fp16 kernel (pg_rayrec.hip writes, pg_evalc.hip reads; >= 64 samples per ray) ----
-// Same idea for PG_PREC_FP16C: (a, b) as above, and the view layer's direction part as A operands of the
-// compensated product (S-1) y1 w1 + y2 w2 (y = Y / S split like a weight, w = the point's cutoff weights split
-// like an activation):
-//   Yc[ray][out tile32 t][k-unit u][plane][lane (h, row)] x 16 B = the 8 joint slots (vyc_slot_joint) of
-//       plane 0: (S-1) f16(y),  plane 1: f16(y1 + S (y - y1)),  y = Y[ray][j][32 t + row] / S,  Y in fp32
-// A 128-point pass touches <= MAXR_CR rays.  The fp32 Y-stage weights are [joint 0..24][VYC_K][128 out] floats.
-constexpr int RECC_Y_BYTES = (VW / 32) * 2 * 2 * 1024;    // 16384
-constexpr int MAXR_CR = 3;
-constexpr int LDS_ABC_BYTES = 3072;               // one AB buffer in LDS: MAXR_CR x 768 = 2304 -> 3 DMA pieces of 1 KiB
-constexpr int VYC_K = 28;                         // 27 view values per joint (16 of the frame code), padded
-constexpr int VYC_FLOATS = (J + 1) * VYC_K * VW;
-// SLOT (slotc_joint below; JC = the frame code) whose weight is value e of k-unit u in lane half h of the second-stage
-// B operand (-1 = zero)
-PG_HD constexpr int vyc_slot(int u, int h, int e, bool fc) {
-    if (u == 0) return JH * h + e;
-    if (e < JH - 8) return JH * h + 8 + e;
-    return (fc && h == 0 && e == JH - 8) ? JC : -1;
-}
-// ---- density input of the compensated kernel's RECORD variant (pg_evalc.hip REC): like the 16x16x32 kernel's X16
-// sequence, with the TWO lane halves' joints of a unit forming one limb segment, so that a wave (and a pass) can leave
-// out the units of a joint pair that is out of cutoff range (pg_eval16r.hip explains the test).  Slot s = 12 h + jj of
-// lane half h holds joint PERMC[s]; per slot two units of cutoff-weighted values (one chunk of 16 unit pairs per joint
-// pair), then six units of directions (two slots each).  The (a, b) records, the cutoff tables and the Y records of
-// this variant are in slot order too.
-constexpr int PERMC[24] = {1, 7, 2, 8, 16, 20, 17, 21, 0, 6, 12, 13,   4, 10, 5, 11, 18, 22, 19, 23, 3, 9, 15, 14};
-PG_HD constexpr int slotc_joint(int s) { return PERMC[s]; }
-constexpr int XVC = 2 * JH;             // 24 units of cutoff-weighted values
-constexpr int XUC = XVC + JH / 2;       // + 6 units of directions = 30
-PG_HD constexpr int xseqc_channel(int i, int h) {
-    int u = i / 8, e = i % 8;
-    if (u < XVC) {
-        int q = 8 * (u % 2) + e;
-        if (q >= ROWS_V) return -1;
-        return q * J + slotc_joint(JH * h + u / 2);
-    }
-    if (e >= 6) return -1;
-    return CH_V + 3 * slotc_joint(JH * h + 2 * (u - XVC) + e / 3) + e % 3;
-}
-static_assert(MAXR_CR * REC_AB_BYTES <= LDS_ABC_BYTES && LDS_ABC_BYTES / REC_AB_BYTES + 1 <= REC_PAD_RAYS && MAXR_CR <= REC_PAD_RAYS,
-              "record fetches stay inside the padded arrays");
-// compacted bias table of the record variant of pg_evalc.hip: L0..L7 (64 tiles), alpha, folded view (4), rgb
-constexpr int BTC_ALPHA = 64;
-constexpr int BTC_VIEWF = 65;
-constexpr int BTC_RGB = 69;
-constexpr int BTC_COUNT = 70;
 
 // bias tiles: L0..L7 (8 each), feature (8), alpha (1), view (4), rgb (1), folded view (4)
 constexpr int BT_LAYER0 = 0;

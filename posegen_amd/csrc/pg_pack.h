@@ -9,7 +9,7 @@
 
 namespace pgpack {
 
-enum { SHAPE_A = 0, SHAPE_B = 1, SHAPE_C = 2 };
+enum { SHAPE_A = 0, SHAPE_B = 1 };
 
 // Borrowed host pointers to one net's tensors (reference checkpoint layout).
 struct NetTensors {
@@ -38,15 +38,10 @@ struct NetTensors {
 // one entry of a source map: (flat offset << 2) | kind, or -1 (a zero of the layout)
 enum { SRC_PLAIN = 0, SRC_COMP0 = 1, SRC_COMP1 = 2 };
 
-// Packs the weight stream for `precision`; returns 0, or <0 on an internal layout error.
-// `fact`: for PG_PREC_FP16C, the program of the dedicated kernel pg_evalc.hip (pg_program.h C); the 16-bit
-// precisions' second program (rays with >= 64 samples, pg_eval16r.hip) is pack_stream_r.
-// `rec` (with fact, PG_PREC_FP16C only): the record variant of that kernel -- no view-direction segment, the view
-// directions arrive as per-ray Y records (pack_vyc, pg_rayrec.hip).
-// `onchip` (with rec, no frame codes): the variant without per-ray records (pg_evalc.hip OC): + one chunk per joint pair of the
-// view layer's direction weights behind layer 0 (pg_program.h C::C_YC).
-int pack_stream(const NetTensors& t, int precision, bool framecode, bool fact, std::vector<uint8_t>& out,
-                std::vector<int>* seg_chunk_base = nullptr, bool rec = false, bool onchip = false);
+// Packs the weight stream for `precision` (shape A for the 16-bit precisions, shape B for the others; the 16-bit
+// precisions' second program -- rays with >= 64 samples, pg_eval16r.hip -- is pack_stream_r); returns 0, or <0 on an
+// internal layout error.
+int pack_stream(const NetTensors& t, int precision, bool framecode, std::vector<uint8_t>& out);
 void pack_bias(const NetTensors& t, std::vector<float>& out);
 // stream and bias table of the 16x16x32 kernel (pg_program.h R, pg_layout.h "small tile")
 // `onchip`: the variant without per-ray records (pg_eval16r.hip OC): + one chunk per limb of the view layer's direction
@@ -59,8 +54,5 @@ int pack_c2(const NetTensors& t, bool framecode, std::vector<uint8_t>& out, std:
 // Y-stage weights of the record kernel (pg_rayrec.hip): [wave 8][unit n][64 lanes x 16 B]; unit n of
 // wave w = (joint slot16_joint(vy_slot(w, n/2)), k-unit n%2) of out tile w&3 as an MFMA B operand.
 int pack_vy(const NetTensors& t, int precision, bool framecode, std::vector<uint8_t>& out);
-// fp32 Y-stage weights of the compensated-fp16 record kernel: [joint 0..24][VYC_K][128 out channels],
-// W_vd[o, (j, k)] for value k = c * 9 + row of joint j (vd_channel), joint 24 = the frame code
-void pack_vyc(const NetTensors& t, bool framecode, std::vector<float>& out);
 
 }  // namespace pgpack

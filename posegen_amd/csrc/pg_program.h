@@ -14,7 +14,7 @@
 namespace pgp {
 using namespace pgl;
 
-enum Seq { SEQ_X = 0, SEQ_H = 1, SEQ_D = 2, SEQ_CODE = 3, SEQ_XC = 4 /* record variant of the compensated kernel */ };
+enum Seq { SEQ_X = 0, SEQ_H = 1, SEQ_D = 2, SEQ_CODE = 3 };
 enum Mat { MAT_L0 = 0, /* .. MAT_L7 = 7 */ MAT_FEAT = 8, MAT_ALPHA = 9, MAT_VIEW = 10, MAT_RGB = 11,
            MAT_FEAT_ALPHA = 12 /* tiles 0..7 feature_linear, tile 8 row 0 alpha_linear */,
            MAT_ALPHA_VIEWF = 13 /* tile 0 row 0 alpha_linear, tiles 1..4 W_view[:, :256] W_feature */,
@@ -103,40 +103,6 @@ constexpr int NCHUNK = C_RGB + 1;
 constexpr int NCHUNK_FOLD = NCHUNK - CH_HID;
 static_assert(cdiv(DSEQ * NTV, VPC) == CH_VD, "view segment must take the same chunks with and without frame code");
 }  // namespace B
-
-// ---------------- shape C: compensated fp16 (pg_evalc.hip), k-major everywhere ----------------
-// A unit pair = 2 KiB: plane (S-1) w1 then plane w2 (pg_pack.cpp); one pair per (sequence unit, out tile).
-// [L0x][L1..L4][L5h][L5x][L6][L7][alpha | folded view trunk: 5 tiles][view directions (+code)][rgb]
-namespace C {
-constexpr int PPC = CHUNK_BYTES / 2048;       // unit pairs per chunk
-constexpr int XU = XSEQ / 8;                  // 27
-constexpr int HU = HSEQ / 8;                  // 16
-constexpr int DU = DSEQ / 8;                  // 41
-constexpr int CH_L0X = cdiv(XU * NT, PPC);    // 14
-constexpr int CH_HID = cdiv(HU * NT, PPC);    // 8
-constexpr int CH_AV = cdiv(HU * (NTV + 1), PPC);        // 5
-constexpr int CH_VD = cdiv((DU + 1) * NTV, PPC);        // 11
-constexpr int NCHUNK = 2 * CH_L0X + 7 * CH_HID + CH_AV + CH_VD + 1;
-static_assert(cdiv(DU * NTV, PPC) == CH_VD, "view segment must take the same chunks with and without frame code");
-constexpr int MFMA_PER_GROUP(bool fc) {
-    return 2 * (2 * XU * NT + 7 * HU * NT + HU * (NTV + 1) + (DU + (fc ? 1 : 0)) * NTV + HU / 2);
-}
-// record variant (>= 64 samples per ray): no view-direction segment, its second stage is 2 k-units x NTV tiles per ray;
-// the density input in the XC sequence (pg_layout.h): one chunk per joint pair (12), then the directions (3 chunks)
-constexpr int CH_L0XR = cdiv(XUC * NT, PPC);            // 15
-constexpr int NCHUNK_R = 2 * CH_L0XR + 7 * CH_HID + CH_AV + 1;
-constexpr int C_L5XR = CH_L0XR + 5 * CH_HID;            // 55: first chunk of the skip layer's x part
-constexpr int NPAIRJ = JH;                              // joint-pair chunks at the head of both x segments
-static_assert(2 * NT == PPC, "a joint pair's two unit rows are exactly one chunk");
-constexpr int MFMA_PER_GROUP_R = 2 * (2 * XUC * NT + 7 * HU * NT + HU * (NTV + 1) + HU / 2) + 2 * 2 * NTV;
-// on-chip variant (pg_evalc.hip OC: one pose per launch, no frame codes): no per-ray records; + one chunk per joint pair of the
-// view layer's direction weights right behind layer 0: unit pairs [k-unit u of 8 view values (4)][out tile o (NTV)], lane
-// (h, col) = out channel 32 o + col, values 8 u + e of joint slot 12 h + p (vd_channel order, 27 used)
-constexpr int C_YC = CH_L0XR;                           // 15
-constexpr int NCHUNK_OC = NCHUNK_R + NPAIRJ;            // 104
-constexpr int C_L5XR_OC = C_L5XR + NPAIRJ;              // 67
-static_assert(4 * NTV == PPC, "a joint pair's direction weights (4 k-units x 4 out tiles) are exactly one chunk");
-}  // namespace C
 
 // ---------------- shape T: compensated fp16 with the OUT TILES split over the waves (pg_evalc2.hip) ----------------
 // No stream and no ring: a workgroup of NW = 8 waves (two per SIMD) carries PTS = 128 points through the net together,

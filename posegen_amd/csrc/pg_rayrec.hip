@@ -1,5 +1,5 @@
-// pg_rayrec.hip -- per-ray records of the factorised view layer: ray_records_kernel for the 16-bit path (pg_eval16r.hip),
-// ray_records_c_kernel for the compensated-fp16 path (pg_evalc.hip, record variant) -- pg_layout.h "per-ray records".
+// pg_rayrec.hip -- per-ray records of the factorised view layer: ray_records_kernel for the 16-bit path (pg_eval16r.hip) --
+// pg_layout.h "per-ray records".
 //
 // The 648-wide view-direction input of a point is w_j(point) * T[ray][j][k] (core/encoders.py:25-37, 172-193;
 // core/cutoff_embedder.py:111-174 with dist_inputs=True): 27 values per joint that depend on the RAY only, times
@@ -168,152 +168,6 @@ __global__ __launch_bounds__(REC_THREADS, 2) void ray_records_kernel(const RecAr
     }
 }
 
-// ---- records of the compensated-fp16 kernel (pg_layout.h "per-ray records of the compensated-fp16 kernel") ----
-// Y in fp32 (its error must stay below the 2^-17 of the compensated products that consume it, so no 16-bit MFMA
-// here): v_mfma_f32_32x32x2_f32 with 32 rays as rows (A = the ray's view table T from LDS, one float per lane),
-// the out channels as columns (B = the fp32 weights [joint][k][out] straight from L2, one coalesced float per lane)
-// and K = 28 = 14 steps per joint.  Wave w owns out tile w and runs the two lane halves of the second stage's A
-// operand (vyc_slot_joint) one after the other; a k-unit's eight joints at a time, then per ray of the C layout the
-// eight values are split like a weight, y = Y / S -> ((S-1) f16(y), f16(y1 + S (y - y1))), one 16-byte fragment per plane.
-// The view table uses accurate sincosf for the base angle like the direct form of pg_evalc.hip (per ray, its cost
-// is nothing).
-constexpr int RECC_THREADS = 256;            // one wave per SIMD: the 128 accumulators of a k-unit need the 512-register budget
-constexpr int RECC_RAYS = 32;
-constexpr int RECC_TSTRIDE = (J + 1) * VYC_K + 1;        // floats per ray in LDS (701, odd: the 32 rays of an A read hit 32 banks)
-constexpr int RECC_LDS = RECC_RAYS * RECC_TSTRIDE * 4;
-
-// One k-unit of the second stage's A operand for this wave's out tile and lane half: the joints of its NJ <= 8 slots
-// (slot e < NJ: joint jbase + e, or JC for the LAST slot when `code`), all accumulators live, so that a ray's eight
-// values leave as ONE 16-byte fragment per plane (32 lanes x 16 B contiguous per store; half fragments of 8 bytes
-// ran the 4.3 GB of a 512 x 512 launch at 1.8 TB/s).
-template <int NJ, bool CODE>
-__device__ __forceinline__ void recc_unit(const RecArgs& a, const float* wy, const float* trow, int ray0, int hl, int jbase, uint8_t* dst0) {
-    f32x16 acc[NJ];
-#pragma unroll
-    for (int e = 0; e < NJ; ++e)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[e][r] = 0.0f;
-#pragma unroll
-    for (int kk = 0; kk < VYC_K / 2; ++kk) {
-        if (kk % 2 == 0) asm volatile("" ::: "memory");         // operands of two steps in flight, not of all fourteen
-#pragma unroll
-        for (int e = 0; e < NJ; ++e) {
-            const int j = (CODE && e == NJ - 1) ? JC : jbase + e;
-            const float av = trow[j * VYC_K + 2 * kk];
-            const float bv = wy[(j * VYC_K + 2 * kk) * VW];
-            acc[e] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[e], 0, 0, 0);
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int ray = ray0 + rho(r, hl);
-        unsigned p0[4], p1[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            unsigned short b0[2], b1[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const int e = 2 * q + i;
-                float v = e < NJ ? acc[e < NJ ? e : 0][r] * (1.0f / (float)COMP_S) : 0.0f;
-                asm volatile("" : "+v"(v));     // one rounded value for both halves (no fused convert of the product)
-                const _Float16 y1 = (_Float16)v;
-                const float y1f = (float)y1;
-                const _Float16 y2 = (_Float16)fmaf((float)COMP_S, v - y1f, y1f);
-                const _Float16 ym = (_Float16)((float)(COMP_S - 1) * y1f);
-                __builtin_memcpy(&b0[i], &ym, 2);
-                __builtin_memcpy(&b1[i], &y2, 2);
-            }
-            p0[q] = (unsigned)b0[0] | ((unsigned)b0[1] << 16);
-            p1[q] = (unsigned)b1[0] | ((unsigned)b1[1] << 16);
-        }
-        if (ray < a.n_rays) {
-            uint8_t* dst = dst0 + (size_t)rho(r, hl) * RECC_Y_BYTES;
-            *reinterpret_cast<uint4*>(dst) = make_uint4(p0[0], p0[1], p0[2], p0[3]);
-            *reinterpret_cast<uint4*>(dst + 1024) = make_uint4(p1[0], p1[1], p1[2], p1[3]);
-        }
-    }
-}
-
-template <bool FC>
-__global__ __launch_bounds__(RECC_THREADS, 1) void ray_records_c_kernel(const RecArgs a) {
-    constexpr int NJ = J + (FC ? 1 : 0);
-    extern __shared__ __attribute__((aligned(16))) float tl[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int t = wave, hl = lane >> 5, col = lane & 31;
-    const float* wy = reinterpret_cast<const float*>(a.wy) + hl * VW + 32 * t + col;       // row k = 2 kk + hl, column 32 t + col
-    const float* trow = tl + col * RECC_TSTRIDE + hl;                                       // ray `col` of the tile, value 2 kk + hl
-    const int n_tiles = (a.n_rays + RECC_RAYS - 1) / RECC_RAYS;
-    for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const int r0 = tile * RECC_RAYS;
-        __syncthreads();                        // the previous tile's table has been read
-        for (int idx = tid; idx < RECC_RAYS * NJ; idx += RECC_THREADS) {
-            const int rr = idx / NJ, j = idx - rr * NJ;
-            const bool live = r0 + rr < a.n_rays;
-            const long long ray = live ? r0 + rr : a.n_rays - 1;
-            float* tv = tl + rr * RECC_TSTRIDE + j * VYC_K;
-            if (j < J) {        // (j = joint SLOT of the compensated kernel's record variant: joint slotc_joint(j), pg_layout.h)
-                const float4* sk = reinterpret_cast<const float4*>(a.skts + ray * a.pose_stride + slotc_joint_dev(j) * 16);
-                const float4 ra = sk[0], rb = sk[1], rc = sk[2];
-                const float* ry = a.rays + ray * 11;
-                const float ox = ry[0], oy = ry[1], oz = ry[2], dx = ry[3], dy = ry[4], dz = ry[5];
-                float e[3];
-                e[0] = fmaf(ra.z, dz, fmaf(ra.y, dy, ra.x * dx));
-                e[1] = fmaf(rb.z, dz, fmaf(rb.y, dy, rb.x * dx));
-                e[2] = fmaf(rc.z, dz, fmaf(rc.y, dy, rc.x * dx));
-                if (live) {
-                    float4* ab = reinterpret_cast<float4*>(a.rec_ab + ray * (REC_AB_BYTES / 4) + j * 8);
-                    const float ax = fmaf(ra.z, oz, fmaf(ra.y, oy, fmaf(ra.x, ox, ra.w))),
-                                ay = fmaf(rb.z, oz, fmaf(rb.y, oy, fmaf(rb.x, ox, rb.w))),
-                                az = fmaf(rc.z, oz, fmaf(rc.y, oy, fmaf(rc.x, ox, rc.w)));
-                    ab[0] = make_float4(ax, ay, az, segment_dist2(a, ray, ax, ay, az, e[0], e[1], e[2]));
-                    ab[1] = make_float4(e[0], e[1], e[2], 0.0f);
-                }
-                const float den = fmaxf(sqrtf(e[0] * e[0] + e[1] * e[1] + e[2] * e[2]), 1e-12f);
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const float ev = e[c] / den;
-                    float sn, co;
-                    sincosf(ev, &sn, &co);
-                    tv[c * ROWS_D] = ev;
-#pragma unroll
-                    for (int f = 0; f < LD; ++f) {
-                        tv[c * ROWS_D + 1 + 2 * f] = sn;
-                        tv[c * ROWS_D + 2 + 2 * f] = co;
-                        const float s2 = 2.0f * sn * co;
-                        co = (co - sn) * (co + sn);
-                        sn = s2;
-                    }
-                }
-                tv[27] = 0.0f;
-            } else {
-                const float cam = a.cams ? a.cams[ray] : -1.0f;
-                const int ci = cam < 0.0f ? a.n_codes : min((int)cam, a.n_codes - 1);
-#pragma unroll
-                for (int k = 0; k < VYC_K; ++k) tv[k] = k < FC_CH ? a.codes[ci * FC_CH + k] : 0.0f;
-            }
-        }
-        __syncthreads();
-#pragma unroll 1
-        for (int kh = 0; kh < 2; ++kh) {
-            uint8_t* d0 = a.rec_y + (size_t)r0 * RECC_Y_BYTES + (t * 4) * 1024 + (kh * 32 + col) * 16;
-            recc_unit<8, false>(a, wy, trow, r0, hl, JH * kh, d0);                            // k-unit 0: joints 12 kh + 0..7
-            if (FC && kh == 0) recc_unit<JH - 8 + 1, true>(a, wy, trow, r0, hl, JH * kh + 8, d0 + 2048);   // k-unit 1: joints 12 kh + 8..11
-            else recc_unit<JH - 8, false>(a, wy, trow, r0, hl, JH * kh + 8, d0 + 2048);        // (+ the frame code in half 0), zeros
-        }
-    }
-}
-
-template <bool FC>
-static hipError_t launch_records_c(const RecArgs& a, int n_cu, hipStream_t stream) {
-    auto k = ray_records_c_kernel<FC>;
-    static std::atomic<unsigned long long> attr_done{0};       // per device (pg_device.h)
-    const hipError_t e = ensure_lds_attr(reinterpret_cast<const void*>(k), RECC_LDS, attr_done);
-    if (e != hipSuccess) return e;
-    const int n_tiles = (a.n_rays + RECC_RAYS - 1) / RECC_RAYS;
-    hipLaunchKernelGGL(k, dim3(n_tiles < n_cu ? n_tiles : n_cu), dim3(RECC_THREADS), RECC_LDS, stream, a);
-    return hipGetLastError();
-}
-
 template <typename V, bool FC>
 static hipError_t launch_records(const RecArgs& a, int n_cu, hipStream_t stream) {
     const int n_tiles = (a.n_rays + REC_TILE_RAYS - 1) / REC_TILE_RAYS;
@@ -323,13 +177,6 @@ static hipError_t launch_records(const RecArgs& a, int n_cu, hipStream_t stream)
 }
 
 }  // namespace pgd
-
-extern "C" int pg_launch_ray_records_c(const pgd::RecArgs* a, int framecode, int n_cu, void* stream) {
-    using namespace pgd;
-    if (a->n_rays <= 0) return 0;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    return (int)(framecode ? launch_records_c<true>(*a, n_cu, s) : launch_records_c<false>(*a, n_cu, s));
-}
 
 extern "C" int pg_launch_ray_records(const pgd::RecArgs* a, int fp16, int framecode, int n_cu, void* stream) {
     using namespace pgd;

@@ -1,5 +1,5 @@
 """Child process of test_other_kernel_forms_vs_reference_golden: the environment switches that select a kernel form
-(POSEGEN_ONCHIP, POSEGEN_EVALC2) are read once per process, so every form renders the golden ray sets in a process of
+(POSEGEN_ONCHIP) are read once per process, so every form renders the golden ray sets in a process of
 its own and reports its errors against the reference's vectors as one JSON line."""
 import json
 import os

@@ -50,7 +50,7 @@ def main():
         d["raw"] = digest(res["extras"]["raw_coarse"])
         d["finite"] = bool(torch.isfinite(res["rgb_map"]).all())
         d["acc_max"] = float(res["acc_map"].max())
-        default_form = "POSEGEN_ONCHIP" not in os.environ and "POSEGEN_EVALC2" not in os.environ     # (the forms that count)
+        default_form = "POSEGEN_ONCHIP" not in os.environ     # (the forms that count)
         if default_form and conf == "surreal" and pose == "one" and n <= (1 << 19) and (prec == "fp16c" or S <= 112):
             # the kernel's own count of the passes it ran: the CNT instantiation of the on-chip 16x16x32 kernel (256 points per
             # pass; up to 112 samples per ray), pg_evalc2.hip's counters (128 points per pass)

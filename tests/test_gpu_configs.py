@@ -242,8 +242,8 @@ def test_seeded_parity_sweep():
 
 @pytest.mark.parametrize("prec,bound", [("bf16", 2e-2), ("fp16", 1e-2), ("fp16c", 1e-3)])
 def test_record_kernels_on_odd_ray_and_sample_counts(prec, bound):
-    """The 16x16x32 kernel (bf16 / fp16) and the record variant of the compensated kernel, each in its on-chip form (one pose per
-    call) and its record form (the pose given per ray), against the fp32 kernel (direct view layer, no records) on shapes that stress their pass bookkeeping: ray counts that leave the last
+    """The 16x16x32 kernel (bf16 / fp16: its on-chip form or, above 112 samples per ray, its record form) and the compensated kernel
+    (pg_evalc2.hip, record-free), each with one pose per call and with the pose given per ray, against the fp32 kernel (direct view layer, no records) on shapes that stress their pass bookkeeping: ray counts that leave the last
     pass and the last record tile ragged (1 ray ... 4097 rays), sample counts that make passes straddle 2 to 5 rays at
     every offset (64 ... 200 samples), with and without importance samples.  fp32 is pinned to the reference by
     test_gpu_parity.py; the bounds are what the modes' operand precision gives on random-weight nets with importance sampling

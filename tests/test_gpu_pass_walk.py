@@ -2,7 +2,7 @@
 
 Which workgroup runs a pass must not show in any output byte: the rotated walk (the default) and the static walk
 (POSEGEN_PASS_WALK=0) render bitwise equal raw, rgb_map, disp_map and acc_map, in every kernel that uses the walk
-(pg_eval16r.hip record and on-chip forms, with frame codes and with a pose per ray; pg_evalc2.hip; pg_evalc.hip) -- a child
+(pg_eval16r.hip record and on-chip forms, with frame codes and with a pose per ray; pg_evalc2.hip) -- a child
 process per (case, walk), since the switches are read once per process (tests/diag/pass_walk_cases.py).  And every pass runs
 exactly once: the kernels' own pass counters on the GPU, and the walk itself on the host (pg_debug_pass_walk: the two-step
 update of (first point, ray, sample) against the integer division, for every pass of a 2^19-ray call).
@@ -41,16 +41,14 @@ CASES = {
     "framecodes_bf16": ("h36m:bf16:one:4099:64,128", {}),
     "framecodes_fp16c": ("h36m:fp16c:one:4099:64,128", {}),
     "above_one_launch_bf16": (f"surreal:bf16:one:{BIG}:64", {}),
-    # the other forms that walk: the 16x16x32 kernel with per-ray records, pg_evalc.hip on chip and with records
+    # the other form that walks: the 16x16x32 kernel with per-ray records
     "records_bf16": ("surreal:bf16:one:4099:64,144", {"POSEGEN_ONCHIP": "0"}),
-    "evalc_onchip": ("surreal:fp16c:one:4099:64,144", {"POSEGEN_EVALC2": "0"}),
-    "evalc_records": ("surreal:fp16c:one:4099:64,144", {"POSEGEN_EVALC2": "0", "POSEGEN_ONCHIP": "0"}),
 }
 TWICE = ("bf16", "fp16c", "framecodes_bf16")        # the default walk twice: the same bytes
 
 
 def _child(case, env):
-    e = {k: v for k, v in os.environ.items() if k not in ("POSEGEN_PASS_WALK", "POSEGEN_MAX_WG", "POSEGEN_ONCHIP", "POSEGEN_EVALC2")}
+    e = {k: v for k, v in os.environ.items() if k not in ("POSEGEN_PASS_WALK", "POSEGEN_MAX_WG", "POSEGEN_ONCHIP")}
     e.update(env)
     run = subprocess.run([sys.executable, os.path.join(REPO, "tests", "diag", "pass_walk_cases.py"), case],
                          capture_output=True, text=True, timeout=300, env=e, cwd=REPO)

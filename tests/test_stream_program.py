@@ -64,7 +64,7 @@ def pack(weights, cfg, prec, fact=False):
     rc = lib.pg_debug_pack(ptrs, shp, 24, cfg.framecode_ch, prec, int(fact), buf.ctypes.data, size.value, C.byref(size),
                            bias.ctypes.data, C.byref(chunk))
     assert rc == 0, lib.pg_last_error(None)
-    if (fact and fact not in (3, 4) and prec != PREC_FP16C) or fact == 2:      # Y-stage weights (the compensated kernel: record variant only)
+    if fact and fact not in (3, 4) and prec != PREC_FP16C:      # Y-stage weights of the record kernel (16-bit precisions)
         n = C.c_int64()
         rc = lib.pg_debug_pack_vy(ptrs, shp, 24, cfg.framecode_ch, prec, None, 0, C.byref(n))
         assert rc == 0, lib.pg_last_error(None)
@@ -121,33 +121,11 @@ def vd_channel(j, k):
 
 
 PERM16 = [1, 2, 16, 17, 0, 12, 4, 5, 18, 19, 3, 13, 7, 8, 20, 21, 6, 14, 10, 11, 22, 23, 9, 15]     # pg_layout.h: slot -> joint
-PERMC = [1, 7, 2, 8, 16, 20, 17, 21, 0, 6, 12, 13, 4, 10, 5, 11, 18, 22, 19, 23, 3, 9, 15, 14]       # ... of the compensated record variant
-XVC, XUC = 24, 30
-
-
-def xseqc_channel(i, h):
-    """pg_layout.h xseqc_channel: units 2 jj, 2 jj + 1 = the 15 cutoff-weighted values of joint slot jj of lane half h
-    (+ a pad), units 24 + p = the directions of slots 2 p, 2 p + 1 (+ two pads)"""
-    u, e = divmod(i, 8)
-    if u < XVC:
-        q = 8 * (u % 2) + e
-        return q * J + PERMC[JH * h + u // 2] if q < 15 else -1
-    if e >= 6:
-        return -1
-    return 360 + 3 * PERMC[JH * h + 2 * (u - XVC) + e // 3] + e % 3
 
 
 def vy_joint(w, e, fc):
     """joint the Y-stage wave w handles as its e-th: the joint of SLOT 12 (w >> 2) + e (pg_layout.h vy_slot / slot16_joint)"""
     return PERM16[JH * (w >> 2) + e] if e < JH else (J if fc and (w >> 2) == 0 and e == JH else -1)
-
-
-def vy_slot_joint(u, h, e, fc):
-    if u == 0:
-        return JH * h + e
-    if e < 4:
-        return JH * h + 8 + e
-    return J if fc and h == 0 and e == 4 else -1
 
 
 def y_stage(vy, tray, fc, prec):
@@ -173,9 +151,8 @@ def y_stage(vy, tray, fc, prec):
     return q16(y, prec)
 
 
-def emulate(stream, bias, chunk_bytes, prec, x, cfg, fact=None):
-    """x: [32 pts, 1080(+code16)] oracle input rows -> raw [32, 4] through the packed stream.
-    fact = (tray [25,32], wpt [32,24], vy): the factorised view layer with x[:,432:1080] = wpt (x) tray."""
+def emulate(stream, bias, chunk_bytes, prec, x, cfg):
+    """x: [32 pts, 1080(+code16)] oracle input rows -> raw [32, 4] through the packed stream."""
     wv = Wave(stream, chunk_bytes, prec)
     shape_a = prec in (PREC_BF16, PREC_FP16)
     ue = wv.ue
@@ -238,23 +215,10 @@ def emulate(stream, bias, chunk_bytes, prec, x, cfg, fact=None):
         sigma = segment(1, True, [(hv, HSEQ)], BT_ALPHA)[0][0]
         fv, _ = hidden_vals(feat, relu=False)
         vt = segment(NTV, km, [(fv, HSEQ)], BT_VIEW)
-    if fact is not None:
-        yq = y_stage(fact[2], fact[0], bool(cfg.framecode_ch), prec)
-        wq = q16(fact[1].astype(np.float32), prec)                  # [pt, 24]
-        for u in range(2):
-            for h in range(2):
-                for e in range(8):
-                    j = vy_slot_joint(u, h, e, bool(cfg.framecode_ch))
-                    if j < 0:
-                        continue
-                    wj = wq[:, j] if j < J else np.ones(32, dtype=np.float32)
-                    for o in range(NTV):
-                        vt[o] += np.outer(yq[j, 32 * o:32 * o + 32], wj)
-    else:
-        ins = [(seq_vals(dseq_channel, DSEQ, x[:, 432:1080]), DSEQ)]
-        if cfg.framecode_ch:
-            ins.append((seq_vals(lambda i, h: 8 * h + i, 8, x[:, 1080:1096]), 8))
-        vt = segment(NTV, True, ins, 0, acc=vt)
+    ins = [(seq_vals(dseq_channel, DSEQ, x[:, 432:1080]), DSEQ)]
+    if cfg.framecode_ch:
+        ins.append((seq_vals(lambda i, h: 8 * h + i, 8, x[:, 1080:1096]), 8))
+    vt = segment(NTV, True, ins, 0, acc=vt)
     gv, _ = hidden_vals(vt)
     rgb = segment(1, km, [(gv, VW // 2)], BT_RGB)[0]
     return np.stack([rgb[0], rgb[1], rgb[2], sigma], -1), wv.chunk + 1
@@ -368,176 +332,6 @@ def emulate_r(stream, bias16, chunk_bytes, prec, x, cfg, fact):
     return np.stack([rgb[0], rgb[1], rgb[2], sigma], -1), state["chunk"] + 1
 
 
-def emulate_c(stream, bias, chunk_bytes, x, cfg, rec=None):
-    """The compensated-fp16 program (pg_program.h C, pg_evalc.hip): every segment k-major, every
-    (input unit, out tile) a PAIR of 1-KiB units -- plane 0 = (S-1) f16(W/S) against x1 = f16(x),
-    plane 1 = f16(w1 + S (W/S - w1)) against x2 = f16(x1 + S (x - x1)) -- into one accumulator."""
-    S = 129.0
-    wv = Wave(stream, chunk_bytes, PREC_FP16)          # both planes are fp16 fragments
-
-    def h16(v):
-        return v.astype(np.float16).astype(np.float32)
-
-    def pair_vals(fn, n, src):
-        v = np.zeros((2, n, 32), dtype=np.float32)
-        for h in range(2):
-            for i in range(n):
-                ch = fn(i, h)
-                if ch >= 0:
-                    v[h, i] = src[:, ch]
-        x1 = h16(v)
-        x2 = h16(x1 + np.float32(S) * (v - x1))
-        return x1, x2
-
-    def bias_tile(t):
-        b = bias[t * 32:(t + 1) * 32].reshape(2, 16)
-        out = np.zeros((32, 1), dtype=np.float32)
-        for h in range(2):
-            for r in range(16):
-                out[rho(r, h), 0] = b[h, r]
-        return np.repeat(out, 32, axis=1)
-
-    def segment(no, inputs, acc):
-        wv_units = [(p1, p2, u) for (p1, p2), n in inputs for u in range(n // 8)]
-        for P in range(len(wv_units) * no):
-            ui, o = P // no, P % no
-            p1, p2, u = wv_units[ui]
-            wv.mma(acc, 2 * P, o, p1, u)
-            wv.mma(acc, 2 * P + 1, o, p2, u)
-        return acc
-
-    def hidden(tiles, relu=True):
-        act = np.concatenate(tiles, 0)
-        if relu:
-            act = np.maximum(act, 0)
-        return pair_vals(hseq_channel, len(tiles) * 16, act.T)
-
-    tiles_of = lambda t0, n: [bias_tile(t0 + o) for o in range(n)]
-    # record variant: the XC sequence (one chunk per joint pair, then the directions; joint slots PERMC) -- pg_layout.h
-    xfn, xn = (xseqc_channel, XUC * 8) if rec is not None else (xseq_channel, XSEQ)
-    xs = pair_vals(xfn, xn, x[:, :432])
-    tiles = segment(NT, [(xs, xn)], tiles_of(0, NT))
-    y_onchip = None
-    if rec is not None and rec[2] is None:
-        # on-chip form (pg_evalc.hip y_segment_c): twelve joint-pair chunks of direction weights behind layer 0, unit pairs
-        # [k-unit u of 8 view values][out tile o], lane (h, col) = out channel 32 o + col, values 8 u + e of joint slot
-        # 12 h + p; the ray's view values split like an activation
-        t32 = rec[0].astype(np.float32)
-        t1 = h16(t32)
-        t2 = h16(t1 + np.float32(S) * (t32 - t1))
-        y_onchip = np.zeros((J + 1, VW), dtype=np.float32)
-        for pj in range(JH):
-            for u in range(4):
-                for o in range(NTV):
-                    P = (pj * 4 + u) * NTV + o
-                    a0, a1 = wv.unit(2 * P), wv.unit(2 * P + 1)     # [col, h, e]
-                    for h in range(2):
-                        j = PERMC[JH * h + pj]
-                        y_onchip[j, 32 * o:32 * o + 32] += a0[:, h, :] @ t1[j, 8 * u:8 * u + 8] + a1[:, h, :] @ t2[j, 8 * u:8 * u + 8]
-    for l in range(1, 5):
-        tiles = segment(NT, [(hidden(tiles), HSEQ)], tiles_of(l * NT, NT))
-    tiles = segment(NT, [(hidden(tiles), HSEQ)], tiles_of(5 * NT, NT))
-    tiles = segment(NT, [(xs, xn)], tiles)
-    for l in (6, 7):
-        tiles = segment(NT, [(hidden(tiles), HSEQ)], tiles_of(l * NT, NT))
-    av = segment(NTV + 1, [(hidden(tiles), HSEQ)], [bias_tile(BT_ALPHA)] + tiles_of(BT_VIEWF, NTV))
-    sigma = av[0][0]
-    if rec is None:
-        ins = [(pair_vals(dseq_channel, DSEQ, x[:, 432:1080]), DSEQ)]
-        if cfg.framecode_ch:
-            ins.append((pair_vals(lambda i, h: 8 * h + i, 8, x[:, 1080:1096]), 8))
-        vt = segment(NTV, ins, av[1:])
-    else:
-        # record variant (pg_rayrec.hip ray_records_c_kernel + the second stage of pg_evalc.hip): Y in fp32 from the
-        # [joint][28][128] weights, split like a weight; the point's 24 cutoff weights (+ 1 for the frame code) split
-        # like an activation; slots per vyc_slot_joint
-        tray, wpt, vyc = rec
-        fc = bool(cfg.framecode_ch)
-        y = np.zeros((J + 1, VW), dtype=np.float32)
-        if y_onchip is not None:
-            y = y_onchip
-        else:
-            wy = vyc.view(np.float32).reshape(J + 1, 28, VW)
-        for sl in range(J + (1 if fc else 0) if y_onchip is None else 0):       # weight blocks are in SLOT order (pack_vyc), y by joint
-            j = PERMC[sl] if sl < J else J
-            acc = np.zeros(VW, dtype=np.float32)
-            for k in range(28):
-                acc = np.float32(wy[sl, k] * np.float32(tray[j, k]) + acc) if k < 27 or j == J else acc
-            y[j] = acc
-        ys = (y * np.float32(1.0 / S)).astype(np.float32)
-        y1 = h16(ys)
-        p0 = h16(np.float32(S - 1) * y1)
-        p1 = h16(y1 + np.float32(S) * (ys - y1))
-        vt = av[1:]
-        for u in range(2):
-            a0 = np.zeros((VW, 2, 8), dtype=np.float32)            # [out, h, e]
-            a1 = np.zeros((VW, 2, 8), dtype=np.float32)
-            wv_ = np.zeros((2, 8, 32), dtype=np.float32)           # [h, e, pt]
-            for h in range(2):
-                for e in range(8):
-                    sl = vy_slot_joint(u, h, e, fc)               # a SLOT of the record variant
-                    if sl < 0:
-                        continue
-                    j = PERMC[sl] if sl < J else J
-                    a0[:, h, e], a1[:, h, e] = p0[j], p1[j]
-                    wv_[h, e] = wpt[:, j] if j < J else 1.0
-            x1 = h16(wv_)
-            x2 = h16(x1 + np.float32(S) * (wv_ - x1))
-            for o in range(NTV):
-                vt[o] += np.einsum("rhe,hep->rp", a0[32 * o:32 * o + 32], x1) + np.einsum("rhe,hep->rp", a1[32 * o:32 * o + 32], x2)
-    rgb = segment(1, [(hidden(vt), VW // 2)], [bias_tile(BT_RGB)])[0]
-    return np.stack([rgb[0], rgb[1], rgb[2], sigma], -1), wv.chunk + 1
-
-
-@pytest.mark.parametrize("fc", [False, True])
-@pytest.mark.parametrize("rec", [False, True, 3])
-def test_packed_compensated_stream_reproduces_mlp(fc, rec):
-    """The fp16c stream as the kernel consumes it (pairs of planes, k-major, every segment on a chunk
-    boundary) against the fp32 oracle: the compensation itself is what is tested -- plain fp16 is at
-    4e-3 on this input (test below), the pair must be 40x closer."""
-    try:
-        _ffi.load_library()
-    except _ffi.HipLibraryError as e:
-        pytest.skip(str(e))
-    if rec == 3 and fc:
-        pytest.skip("the on-chip form has no frame-code pseudo joint")
-    cfg = h36m_config() if fc else surreal_config()
-    w = syn.make_weights(cfg, 3)
-    stream, bias, chunk_bytes, vyc = pack(w, cfg, PREC_FP16C, 3 if rec == 3 else 2 if rec else True)
-    rng = np.random.RandomState(0)
-    x = rng.uniform(-1, 1, size=(32, 1080)).astype(np.float32)
-    x[:, :360] *= rng.uniform(0, 1, size=(32, 1)).astype(np.float32)
-    rec_in = None
-    if rec:       # one ray: view inputs = per-point joint weight x per-ray value (the record variant, S >= 64)
-        tray = np.zeros((J + 1, 32), dtype=np.float32)
-        tray[:J, :27] = rng.uniform(-1, 1, size=(J, 27))
-        wpt = rng.uniform(0, 1, size=(32, J)).astype(np.float32)
-        for j in range(J):
-            for k in range(27):
-                x[:, 432 + vd_channel(j, k)] = wpt[:, j] * tray[j, k]
-        rec_in = (tray, wpt, vyc)
-    ocfg = oracle_cfg(cfg, 79.6, 79.6)
-    tw = {k: torch.tensor(v) for k, v in w.items()}
-    if fc:
-        idx = rng.randint(0, cfg.n_framecodes, size=(32, 1)).astype(np.float32)
-        if rec:
-            idx[:] = idx[0]                                            # one ray, one frame code
-            rec_in[0][J, :16] = w["framecodes.codes.weight"][int(idx[0, 0])]
-        ref = orc.mlp_forward(torch.tensor(np.concatenate([x, idx], 1)), tw, ocfg).numpy()
-        x_em = np.concatenate([x, w["framecodes.codes.weight"][idx[:, 0].astype(int)]], 1)
-    else:
-        ref = orc.mlp_forward(torch.tensor(x), tw, ocfg).numpy()
-        x_em = x
-    raw, n_chunks = emulate_c(stream, bias, chunk_bytes, x_em, cfg, rec_in)
-    assert n_chunks * chunk_bytes == stream.size, "kernel program and packer disagree on the chunk count"
-    err = float(np.abs(raw - ref).max())
-    print(f"fp16c stream emulation vs fp32 oracle: {err:.2e} (|ref| max {np.abs(ref).max():.2f})")
-    assert err <= 1e-4 * max(1.0, float(np.abs(ref).max()) / 10)
-    ocfg.quant = "fp16c"
-    emu = orc.mlp_forward(torch.tensor(np.concatenate([x, idx], 1) if fc else x), tw, ocfg).numpy()
-    assert float(np.abs(raw - emu).max()) <= 1e-4 * max(1.0, float(np.abs(ref).max()) / 10)
-
-
 @pytest.mark.parametrize("prec,quant,tol", [(PREC_FP32, None, 2e-4), (PREC_BF16, "bf16", 2e-2), (PREC_FP16, "fp16", 4e-3)])
 @pytest.mark.parametrize("fc", [False, True])
 @pytest.mark.parametrize("fact", [False, True, 3])
@@ -581,7 +375,7 @@ def test_packed_stream_reproduces_mlp(prec, quant, tol, fc, fact):
     if fact:        # 16-bit precisions, rays with >= 64 samples: the 16x16x32 kernel with per-ray records
         raw, n_chunks = emulate_r(stream, bias, chunk_bytes, prec, x_em, cfg, fact_in)
     else:
-        raw, n_chunks = emulate(stream, bias, chunk_bytes, prec, x_em, cfg, None)
+        raw, n_chunks = emulate(stream, bias, chunk_bytes, prec, x_em, cfg)
     assert n_chunks * chunk_bytes == stream.size, "kernel program and packer disagree on the chunk count"
     np.testing.assert_allclose(raw, ref, rtol=0, atol=tol * max(1.0, float(np.abs(ref).max()) / 10))
 
@@ -727,6 +521,34 @@ def test_tile_split_weight_image_reproduces_mlp(fc):
     err = float(np.abs(raw - ref).max())
     print(f"pg_evalc2 weight image emulation vs fp32 oracle: {err:.2e} (|ref| max {np.abs(ref).max():.2f})")
     assert err <= 1e-4 * max(1.0, float(np.abs(ref).max()) / 10)
+
+
+def test_debug_pack_takes_fp16c_as_the_k_major_stream_or_the_tile_split_image_only():
+    """PG_PREC_FP16C has two weight forms: view_fact 0 (the k-major stream of pg_eval32.hip) and 4 (pg_evalc2.hip's image).
+    1, 2 and 3 -- programs of a kernel that no longer exists -- are refused with a message naming the two, and so is the
+    Y-stage packer for this precision."""
+    try:
+        lib = _ffi.load_library()
+    except _ffi.HipLibraryError as e:
+        pytest.skip(str(e))
+    cfg = surreal_config()
+    w = syn.make_weights(cfg, 3)
+    arrs = [np.ascontiguousarray(w[k], dtype=np.float32) for k in NET_TENSOR_ORDER]
+    ptrs = (C.c_void_p * 24)(*[a.ctypes.data for a in arrs])
+    shp = (C.c_int64 * 48)()
+    for i, a in enumerate(arrs):
+        shp[2 * i], shp[2 * i + 1] = a.shape[0], (a.shape[1] if a.ndim == 2 else 1)
+    size, chunk = C.c_int64(), C.c_int32()
+    for fact in (1, 2, 3):
+        rc = lib.pg_debug_pack(ptrs, shp, 24, cfg.framecode_ch, PREC_FP16C, fact, None, 0, C.byref(size), None, C.byref(chunk))
+        msg = lib.pg_last_error(None).decode()
+        assert rc == _ffi.PG_EINVAL, (fact, rc)
+        assert "view_fact 0" in msg and "or 4" in msg and f"not {fact}" in msg, msg
+    stream, _, chunk_bytes, vy = pack(w, cfg, PREC_FP16C, 0)
+    assert vy is None and stream.size > 0 and stream.size % chunk_bytes == 0
+    img, _, _, _ = pack(w, cfg, PREC_FP16C, 4)
+    assert img.size == T_TOTAL
+    assert lib.pg_debug_pack_vy(ptrs, shp, 24, cfg.framecode_ch, PREC_FP16C, None, 0, C.byref(size)) == _ffi.PG_EINVAL
 
 
 # ---- source maps (pg_load_weights_device re-forms a packed image by a gather from the flat parameter vector) ----

@@ -4,8 +4,7 @@ only when a dump is asked for) may spill.   usage: audit_asm_scratch.py file.s [
 import re, sys
 
 # position of the TAPS flag among the bool template arguments (Lb0E / Lb1E in the mangled name); None = no debug form
-TAPS_BOOL = {"eval16r_kernel": 1, "eval16_kernel": 1, "evalc_kernel": 1, "eval32_kernel": None,
-             "ray_records_kernel": None, "ray_records_c_kernel": None}
+TAPS_BOOL = {"eval16r_kernel": 1, "eval16_kernel": 1, "eval32_kernel": None, "ray_records_kernel": None}
 
 
 def main(path, only=None):

@@ -1,8 +1,7 @@
-"""pg_evalc2.hip (compensated fp16, out tiles over the waves) against the oracle, the fp32 kernel and pg_evalc.hip:
+"""pg_evalc2.hip (compensated fp16, out tiles over the waves) against the oracle and the fp32 kernel:
 raw values of the coarse net on the golden ray sets (shared / per-ray poses, frame codes, odd sample counts), then
 the launch time on the 512 x 512 benchmark frame.   usage: diag_evalc2.py [check|time]"""
 import os
-import subprocess
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -96,17 +95,12 @@ def time_one():
             r.stage_eval(0, rb, z, skts)
         n, ms, pts = r.profile_read()
         tot += ms / n
-        print(f"  EVALC2={os.environ.get('POSEGEN_EVALC2', '1')} S={S}: eval {ms / n:.3f} ms, {pts * cfg.flops_per_point() / (ms * 1e-3) / 2.5e15:.3f} of peak", flush=True)
-    print(f"  EVALC2={os.environ.get('POSEGEN_EVALC2', '1')} coarse+fine {tot:.3f} ms", flush=True)
+        print(f"  S={S}: eval {ms / n:.3f} ms, {pts * cfg.flops_per_point() / (ms * 1e-3) / 2.5e15:.3f} of peak", flush=True)
+    print(f"  coarse+fine {tot:.3f} ms", flush=True)
 
 
 if __name__ == "__main__":
     mode = sys.argv[1] if len(sys.argv) > 1 else "check"
     if mode == "check":
         sys.exit(check())
-    if mode == "time1":
-        time_one()
-    else:
-        for rnd in range(2):
-            for v in ("1", "0"):
-                subprocess.run([sys.executable, __file__, "time1"], env=dict(os.environ, POSEGEN_EVALC2=v))
+    time_one()

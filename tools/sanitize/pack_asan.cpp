@@ -29,14 +29,12 @@ int main() {
         t.view_w = mk((size_t)128 * view_in); t.view_b = mk(128);
         t.rgb_w = mk(3 * 128); t.rgb_b = mk(3);
         t.fold();
-        for (int prec = 0; prec < PG_PREC_COUNT; ++prec)
-            for (int fact = 0; fact < 2; ++fact) {
-                std::vector<uint8_t> out;
-                std::vector<int> base;
-                const int rc = pack_stream(t, prec, fc != 0, fact != 0, out, &base);
-                std::printf("fc=%d prec=%d fact=%d: rc=%d, %zu bytes, %zu segments\n", fc, prec, fact, rc, out.size(), base.size());
-                if (rc != 0 && !(fact && prec != PG_PREC_FP16C)) ++fails;       // only fp16c has a second program here
-            }
+        for (int prec = 0; prec < PG_PREC_COUNT; ++prec) {
+            std::vector<uint8_t> out;
+            const int rc = pack_stream(t, prec, fc != 0, out);
+            std::printf("fc=%d prec=%d: rc=%d, %zu bytes\n", fc, prec, rc, out.size());
+            if (rc != 0) ++fails;
+        }
         for (int prec : {PG_PREC_BF16, PG_PREC_FP16}) {
             std::vector<uint8_t> s, vy;
             std::vector<float> b;
@@ -45,12 +43,10 @@ int main() {
             if (pack_vy(t, prec, fc != 0, vy) != 0) ++fails;
             std::printf("fc=%d prec=%d: small-tile stream %zu bytes, vy %zu bytes\n", fc, prec, s.size(), vy.size());
         }
-        {   // record variant of the compensated-fp16 kernel: stream without the view-direction segment + fp32 Y-stage weights
-            std::vector<uint8_t> s;
-            std::vector<float> vyc;
-            if (pack_stream(t, PG_PREC_FP16C, fc != 0, true, s, nullptr, true) != 0) ++fails;
-            pack_vyc(t, fc != 0, vyc);
-            std::printf("fc=%d fp16c record variant: stream %zu bytes, vyc %zu floats\n", fc, s.size(), vyc.size());
+        {   // the weight image of the out-tile-split compensated-fp16 kernel
+            std::vector<uint8_t> img;
+            if (pack_c2(t, fc != 0, img) != 0) ++fails;
+            std::printf("fc=%d fp16c tile-split image: %zu bytes\n", fc, img.size());
         }
         std::vector<float> bias;
         pack_bias(t, bias);
