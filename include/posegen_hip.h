@@ -562,6 +562,36 @@ typedef struct pg_image_bank {
 int pg_batch_gather(pg_handle* h, void* stream, const pg_image_bank* bank, const int32_t* img_rows, const int32_t* cam_rows, int64_t n_img,
                     int k, const int32_t* pixel_idxs, float* target_s, float* fgs, float* bgs, float* rays_o, float* rays_d, float* ray_batch);
 
+/* ---- scoring a rendered frame against its ground truth: the sums behind the PSNR, the SSIM and their foreground-masked variants of
+ * the reference's two evaluate_metric functions (run_render.py:888-974 -- in the frame's 2-D box, :910-961;
+ * core/utils/evaluation_helpers.py:257-385 -- whole frames, box = the frame), with the SSIM map of the vendored
+ * pytorch_msssim.ssim (pytorch-msssim/pytorch_msssim/__init__.py:7-59).  The frame and the bank's bytes stay on the device, no map
+ * is written, and a frame's scores are eight doubles.  Asynchronous on `stream`; needs no loaded weights; no atomics: two calls on
+ * the same inputs give the same bytes.
+ *   bank     imgs, masks (NULL: no foreground, the masked sums are 0), F, P, H, W; with PG_METRICS_BG also bkgds, bkgd_idxs, n_bkgd
+ *   img_row  the ground-truth image, in [0, F)
+ *   box      HOST int32 (x0, y0, x1, y1): top-left inclusive, bottom-right exclusive, as render_path's bboxes; h = y1 - y0, w = x1 - x0
+ *   rgb      device float32 [H,W,3]: the rendered frame, H W = the bank's
+ *   flags    PG_METRICS_BG: gt = mask ? img : bkgds[bkgd_idxs[img_row]] (run_render.py:935-937; masks are binary, so a selection)
+ *   sums     device float64 [8] = (n, se, n_fg, se_fg, n_map, ssim, n_fg_map, ssim_fg):
+ *     gt = byte / 255 rounded to float32; m = 1 where the mask byte is > 0, else 0
+ *     n = 3 h w;  se = sum (gt - rgb)^2 over box and channels;  n_fg = 3 sum m;  se_fg = sum m (gt - rgb)^2
+ *     map = ssim_map of pytorch_msssim.ssim(rgb, gt): 11 x 11 Gaussian (sigma 1.5, the float32 taps of gaussian(), the window their
+ *     outer product), valid convolution -- (h - 10) x (w - 10) per channel -- of x, y, x^2, y^2, xy; L = 1, C1 = 1e-4, C2 = 9e-4
+ *     n_map = 3 (h - 10)(w - 10);  ssim = sum map
+ *     masked SSIM -- THIS PROJECT'S definition (the reference multiplies a per-image mean by a full-size mask and cannot run): a map
+ *     value is weighted by the mask at its window's centre pixel, m_c(i, j) = m(y0 + 5 + i, x0 + 5 + j);
+ *     n_fg_map = 3 sum m_c;  ssim_fg = sum m_c map
+ *   Every sum and the map's arithmetic is float64 on the float32 frame and the bytes.  A box with h < 11 or w < 11 has no map (the
+ *   reference's SSIM raises): n_map = ssim = n_fg_map = ssim_fg = 0, the first four sums are filled.
+ * The host arguments are checked before anything is launched.  PG_EINVAL, nothing launched and nothing written: a NULL pointer, a
+ * box that is empty or reaches outside the frame, img_row outside [0, F), H W != P, unknown flags, PG_METRICS_BG without bkgds /
+ * bkgd_idxs / masks or with a background index outside the bank.  The tiles' partial sums live in a buffer of the handle: calls
+ * enqueued on different streams must be ordered by the caller. */
+#define PG_METRICS_BG 1
+int pg_frame_metrics(pg_handle* h, void* stream, const pg_image_bank* bank, int32_t img_row, const int32_t box[4], const float* rgb,
+                     int flags, double* sums);
+
 /* raw2outputs (nerf.py:150-205) and, if n_importance > 0, isample_from_lineseg
  * (ray_utils.py:157-201, 255-289): wave-per-ray prefix-product compositing.  The pdf follows the
  * handle: is_only weights 0.5 (max(w_l, w_k) + max(w_k, w_u)) + 0.01 with single_net. */

@@ -16,6 +16,7 @@ __version__ = "0.1.0"
 _TRAIN_NAMES = ("make_trainable", "TrainableRayCaster", "SingleNetTrainableRayCaster")
 _POSEOPT_NAMES = ("HipPoseOptLayer",)
 _BATCH_NAMES = ("DeviceImageBank", "ImageBatchSampler", "RayBatchSource")
+_EVALUATE_NAMES = ("FrameScorer", "evaluate_frames", "evaluate_metric")
 
 
 def __getattr__(name):
@@ -29,4 +30,7 @@ def __getattr__(name):
     if name in _BATCH_NAMES:                   # training batches on the device (imports torch as well)
         from . import batches
         return getattr(batches, name)
+    if name in _EVALUATE_NAMES:                # frame scores on the device (imports torch as well)
+        from . import evaluate
+        return getattr(evaluate, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -21,6 +21,7 @@ PG_FLAG_STAGE_ONE_LAUNCH = 256
 PG_ACT_RELU, PG_ACT_SOFTPLUS = 0, 1
 PG_COMP_PLAIN, PG_COMP_IS_ONLY, PG_COMP_MERGED = 0, 1, 2
 PG_ABI_VERSION = 11
+PG_METRICS_BG = 1
 
 
 class HipLibraryError(RuntimeError):
@@ -167,6 +168,8 @@ PROTOTYPES = {
                                          C.POINTER(C.c_int32), C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
     "pg_batch_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(PgImageBank), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int64,
                                   C.c_int, C.c_void_p, _FP, _FP, _FP, _FP, _FP, _FP]),
+    "pg_frame_metrics": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(PgImageBank), C.c_int32, C.POINTER(C.c_int32), _FP, C.c_int,
+                                   C.c_void_p]),
     "pg_plan_frames": (C.c_int, [C.c_int, C.POINTER(C.c_int64), C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int,
                                  C.POINTER(C.c_int)]),
 }

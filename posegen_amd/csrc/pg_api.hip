@@ -731,6 +731,7 @@ void pg_destroy(pg_handle* h) {
     pg_mesh_release(h);
     pg_poseopt_release(h);
     pg_batch_release(h);
+    pg_metrics_release(h);
     pg_frames_release(h);
     for (auto& pr : h->ev_aux) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
     release_subject(*h);

@@ -1,0 +1,60 @@
+// pg_metrics_plan.h -- the box and tile arithmetic of pg_frame_metrics (pg_metrics.hip): the check of a box against
+// its frame, the grid of tiles over the box, what a tile stages, which pixels' squared errors and which map pixels it owns, and
+// where its partial sums go.  Host-only and free of HIP calls, like pg_frames_plan.h, so that it compiles into a plain C++ program
+// (tools/sanitize/metrics_plan_asan.cpp, built with the address and undefined-behaviour sanitisers); the kernel runs the same
+// functions on the device.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+
+#if defined(__HIPCC__)
+#define PG_METRICS_HD __host__ __device__
+#else
+#define PG_METRICS_HD
+#endif
+
+namespace pgsp {
+
+constexpr int WIN = 11;                  // the Gaussian window of pytorch_msssim (window_size = 11, valid convolution)
+constexpr int HALO = WIN - 1;
+constexpr int TILE = 32;                 // map pixels of a tile along each axis
+constexpr int STAGE = TILE + HALO;       // box pixels a tile stages along each axis
+constexpr int SUMS = 8;                  // (n, se, n_fg, se_fg, n_map, ssim, n_fg_map, ssim_fg)
+// The float32 taps of pytorch_msssim's gaussian(11, 1.5), bit for bit (tests/golden/frame_metrics.npz holds what that function
+// returns; tests/test_frame_metrics_ref.py compares).  The 2-D window is their outer product, formed in double.
+constexpr float TAPS[WIN] = {0x1.0d956cp-10f, 0x1.f1fe02p-8f, 0x1.26eb18p-5f, 0x1.bff0fep-4f, 0x1.b43c3ep-3f, 0x1.10656p-2f,
+                             0x1.b43c3ep-3f, 0x1.bff0fep-4f, 0x1.26eb18p-5f, 0x1.f1fe02p-8f, 0x1.0d956cp-10f};
+
+// A box (x0, y0, x1, y1), top-left inclusive and bottom-right exclusive, inside an H x W frame and not empty
+PG_METRICS_HD inline bool box_ok(const int32_t box[4], int H, int W) {
+    return box[0] >= 0 && box[1] >= 0 && box[0] < box[2] && box[1] < box[3] && box[2] <= W && box[3] <= H;
+}
+
+// Tiles along an axis of `len` box pixels: the map has len - HALO pixels there, TILE per tile; a box below the window has no map
+// and one tile, which still owns the box's squared errors.
+PG_METRICS_HD inline int tiles_along(int len) { return len > HALO ? (len - HALO + TILE - 1) / TILE : 1; }
+
+struct Span {
+    int s0, sn;      // staged box pixels [s0, s0 + sn), sn <= STAGE
+    int own;         // the first `own` of them are this tile's for the squared error: every box pixel belongs to one tile
+    int map;         // map pixels s0 .. s0 + map (<= TILE): map pixel i has its window over staged pixels [i, i + WIN)
+};
+
+// Tile t of tiles_along(len) along one axis (box-relative pixels)
+PG_METRICS_HD inline Span tile_span(int len, int t) {
+    const int nt = tiles_along(len);
+    Span s;
+    s.s0 = t * TILE;
+    s.sn = len - s.s0 < STAGE ? len - s.s0 : STAGE;
+    s.own = t == nt - 1 ? len - s.s0 : TILE;
+    const int mlen = len > HALO ? len - HALO : 0;
+    s.map = mlen - s.s0 < TILE ? mlen - s.s0 : TILE;
+    if (s.map < 0) s.map = 0;
+    return s;
+}
+
+// Partial sums of tile (tx, ty): SUMS doubles at this offset of the slot buffer
+PG_METRICS_HD inline size_t slot_offset(int ntx, int tx, int ty) { return ((size_t)ty * ntx + tx) * SUMS; }
+inline size_t slot_bytes(int w, int h) { return (size_t)tiles_along(w) * tiles_along(h) * SUMS * sizeof(double); }
+
+}  // namespace pgsp

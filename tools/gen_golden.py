@@ -685,6 +685,58 @@ def gen_frame(out, name, cfg, H, chunk, seed_model=0, seed_pose=1, n_frames=2):
     print(f"[{name}] frames={n_frames} valid={[len(v) for v in vids]} acc max={accs.max():.3f}")
 
 
+def gen_frame_metrics(out):
+    """Frame scores (posegen_amd/evaluate.py, pg_frame_metrics): tiny uint8 ground-truth images, masks and a background, float32
+    "rendered" frames (ground truth plus seeded noise, with a region that is constant white in both), boxes, and for every box
+    of at least 11 x 11 the value of the vendored `pytorch_msssim.SSIM(size_average=False)` on the cropped pair formed by the
+    lines of run_render.py:912, 935-937, 944-951 -- float32, one value per image (what `box_ssim.mean()` would be, if :952 could
+    run) -- with the float32 taps of that package's `gaussian(11, 1.5)`.  Two frame sizes: 36 x 48, and 50 x 37 (odd width)."""
+    import torch
+    from pytorch_msssim import SSIM, gaussian
+    rng = np.random.RandomState(20)
+    d = {"taps": gaussian(11, 1.5).numpy()}
+    ssim_eval = SSIM(size_average=False)
+    sets = {"a": (2, 36, 48, [(0, 0, 48, 36), (3, 5, 14, 16), (10, 4, 22, 17), (0, 0, 11, 36), (37, 25, 48, 36), (0, 20, 30, 36),
+                              (20, 0, 48, 14), (5, 2, 48, 36), (4, 3, 46, 35), (1, 1, 47, 12)]),
+            "b": (1, 50, 37, [(0, 0, 37, 50), (1, 1, 36, 49), (20, 30, 37, 50), (0, 0, 12, 11), (3, 0, 37, 43)])}
+    cases = []
+    for tag, (F, H, W, boxes) in sets.items():
+        yy, xx = np.mgrid[0:H, 0:W]
+        imgs = np.empty((F, H, W, 3), dtype=np.uint8)
+        masks = np.empty((F, H, W), dtype=np.uint8)
+        rgbs = np.empty((F, H, W, 3), dtype=np.float32)
+        for f in range(F):
+            smooth = 127 + 90 * np.stack([np.sin(xx / (5. + c + f) + yy / 9.) * np.cos(yy / (4. + f) - c) for c in range(3)], -1)
+            imgs[f] = np.clip(smooth + rng.randint(-20, 21, size=(H, W, 3)), 0, 255).astype(np.uint8)
+            masks[f] = ((xx - W * (0.45 + 0.1 * f)) ** 2 / (0.3 * W) ** 2 + (yy - H * 0.55) ** 2 / (0.35 * H) ** 2 < 1).astype(np.uint8)
+            white = (yy < H // 3) & (xx >= W - W // 3 - 13)              # > 11 x 11: windows that see nothing but white
+            imgs[f][white] = 255
+            rgbs[f] = np.clip(imgs[f] / 255. + rng.normal(0, 0.06, size=(H, W, 3)), 0, 1).astype(np.float32)
+            rgbs[f][white] = 1.0
+        bkgd = rng.randint(0, 256, size=(1, H, W, 3)).astype(np.uint8)
+        d.update({f"imgs_{tag}": imgs, f"masks_{tag}": masks, f"bkgds_{tag}": bkgd, f"rgbs_{tag}": rgbs,
+                  f"boxes_{tag}": np.asarray(boxes, dtype=np.int32)})
+        vals = np.full((F, len(boxes), 2), np.nan, dtype=np.float32)
+        for f in range(F):
+            for b, (x0, y0, x1, y1) in enumerate(boxes):
+                for use_bg in (0, 1):
+                    gt_img = imgs[f] / 255.
+                    gt_mask = masks[f][:, :, None]
+                    if use_bg:
+                        gt_img = gt_img * gt_mask + (1. - gt_mask) * (bkgd[0] / 255.)
+                    gt_cropped = gt_img[y0:y1, x0:x1].astype(np.float32)
+                    rgb_cropped = rgbs[f][y0:y1, x0:x1]
+                    rgb_tensor = torch.tensor(rgb_cropped[None]).permute(0, 3, 1, 2)
+                    gt_tensor = torch.tensor(gt_cropped[None]).permute(0, 3, 1, 2)
+                    v = ssim_eval(rgb_tensor, gt_tensor)
+                    assert v.shape == (1,) and v.dtype == torch.float32
+                    vals[f, b, use_bg] = v.numpy()[0]
+                    cases.append(float(v))
+        d[f"ssim_{tag}"] = vals              # [frame, box, use_bg]
+    np.savez_compressed(os.path.join(out, "frame_metrics.npz"), **d)
+    print(f"[frame_metrics] {len(cases)} reference SSIM values in [{min(cases):.4f}, {max(cases):.4f}]")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ref", default="/root/reference")
@@ -769,6 +821,9 @@ def main():
         gen_train_grads_pose(a.out, "train_grads_single_pose",
                              surreal_config(single_net=True, multires_views=0, n_samples=96, n_importance=48),
                              n_rays=48, H=128, n_poses=2, seed_pose=20, model_keys=True)
+    # frame scores: the vendored pytorch_msssim on cropped pairs (consumes no torch RNG state)
+    if want("frame_metrics"):
+        gen_frame_metrics(a.out)
 
 
 if __name__ == "__main__":
