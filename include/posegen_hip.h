@@ -592,6 +592,28 @@ int pg_batch_gather(pg_handle* h, void* stream, const pg_image_bank* bank, const
 int pg_frame_metrics(pg_handle* h, void* stream, const pg_image_bank* bank, int32_t img_row, const int32_t box[4], const float* rgb,
                      int flags, double* sums);
 
+/* The trainer's validation scoring (run_nerf.py:586-589 -> evaluation_helpers.py:257-385 with eval_both and render_factor): the
+ * frame is given at the size it was rendered at, rgb_h x rgb_w <= H x W, and scored as its bilinear upsampling U to H x W; beside
+ * the eight sums over `box` (pg_frame_metrics with the frame = U) come four over a second rectangle `valid` of the frame -- the
+ * frame's 2-D box at the bank's resolution, whose pixels the reference's valid_masks mark.
+ *   rgb      device float32 [rgb_h,rgb_w,3], 1 <= rgb_h <= H, 1 <= rgb_w <= W
+ *   U        F.interpolate(mode='bilinear', align_corners=False) with the index arithmetic in double.  Per axis, n_in -> n_out, pixel d:
+ *              src = max((n_in / n_out) (d + 0.5) - 0.5, 0);  i0 = min((int)src, n_in - 1);  i1 = i0 + (i0 < n_in - 1);
+ *              l1 = src - i0;  l0 = 1 - l1
+ *            U[y,x,c] = float32( ly0 (lx0 a + lx1 b) + ly1 (lx0 c + lx1 d) ) with the texels a (y0,x0), b (y0,x1), c (y1,x0),
+ *            d (y1,x1) widened to double, every product and sum rounded on its own.  rgb_h = H and rgb_w = W: U = rgb bit for bit.
+ *   valid    HOST int32 (vx0, vy0, vx1, vy1) or NULL; x0 <= x1, y0 <= y1 (it may be empty), inside the frame; it may reach outside
+ *            `box` or miss it
+ *   sums     device float64 [12]: [0..7] as pg_frame_metrics, then (n_valid, se_valid, n_valid_map, ssim_valid), all 0 for NULL:
+ *     n_valid = 3 |box n valid|;  se_valid = sum (gt - U)^2 over those pixels
+ *     n_valid_map = 3 x the map pixels of `box` whose window-centre pixel lies in `valid`;  ssim_valid = sum map over those
+ * Asynchronous on `stream`, no loaded weights, no atomics, the slot buffer and the ordering rule of pg_frame_metrics.  PG_EINVAL,
+ * nothing launched and nothing written: everything pg_frame_metrics refuses, rgb_h / rgb_w outside [1, H] / [1, W], a malformed
+ * valid. */
+int pg_frame_metrics_val(pg_handle* h, void* stream, const pg_image_bank* bank, int32_t img_row, const int32_t box[4],
+                         const float* rgb, int32_t rgb_h, int32_t rgb_w, const int32_t valid[4] /* or NULL */,
+                         int flags, double* sums /* device float64 [12] */);
+
 /* raw2outputs (nerf.py:150-205) and, if n_importance > 0, isample_from_lineseg
  * (ray_utils.py:157-201, 255-289): wave-per-ray prefix-product compositing.  The pdf follows the
  * handle: is_only weights 0.5 (max(w_l, w_k) + max(w_k, w_u)) + 0.01 with single_net. */

@@ -16,7 +16,8 @@ __version__ = "0.1.0"
 _TRAIN_NAMES = ("make_trainable", "TrainableRayCaster", "SingleNetTrainableRayCaster")
 _POSEOPT_NAMES = ("HipPoseOptLayer",)
 _BATCH_NAMES = ("DeviceImageBank", "ImageBatchSampler", "RayBatchSource")
-_EVALUATE_NAMES = ("FrameScorer", "evaluate_frames", "evaluate_metric")
+_EVALUATE_NAMES = ("FrameScorer", "evaluate_frames", "evaluate_metric", "ValidationScorer", "evaluate_validation", "evaluate_testset",
+                   "validation_scores")
 
 
 def __getattr__(name):

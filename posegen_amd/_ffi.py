@@ -170,6 +170,8 @@ PROTOTYPES = {
                                   C.c_int, C.c_void_p, _FP, _FP, _FP, _FP, _FP, _FP]),
     "pg_frame_metrics": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(PgImageBank), C.c_int32, C.POINTER(C.c_int32), _FP, C.c_int,
                                    C.c_void_p]),
+    "pg_frame_metrics_val": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(PgImageBank), C.c_int32, C.POINTER(C.c_int32), _FP, C.c_int32,
+                                       C.c_int32, C.POINTER(C.c_int32), C.c_int, C.c_void_p]),
     "pg_plan_frames": (C.c_int, [C.c_int, C.POINTER(C.c_int64), C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int,
                                  C.POINTER(C.c_int)]),
 }

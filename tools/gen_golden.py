@@ -737,6 +737,57 @@ def gen_frame_metrics(out):
     print(f"[frame_metrics] {len(cases)} reference SSIM values in [{min(cases):.4f}, {max(cases):.4f}]")
 
 
+def gen_frame_metrics_val(out):
+    """Validation scores (posegen_amd/evaluate.py, pg_frame_metrics_val): the frames of frame_metrics.npz area-averaged (numpy, this
+    repository's tests/metrics_val_ref.area_average) to H // rf x W // rf for rf = 2, 3 -- 36 x 48 -> 18 x 24, 12 x 16 and
+    50 x 37 -> 25 x 18, 16 x 12, where the size ratios are not integers -- and for every frame, with and without backgrounds, what
+    the lines of evaluation_helpers.py:307-344 give on the whole frame: F.interpolate(bilinear, align_corners=False) in float32,
+    the vendored `SSIM(size_average=False)`, and the literal PSNR lines -- all pixels (:348), foreground (:325-327) and under a
+    valid rectangle (:336-338).  Only arrays are stored."""
+    import torch
+    import torch.nn.functional as F
+    from pytorch_msssim import SSIM
+    from tests.metrics_val_ref import area_average
+    g = np.load(os.path.join(out, "frame_metrics.npz"))
+    ssim_eval = SSIM(size_average=False)
+    d, n = {}, 0
+    valid = {"a": (9, 4, 41, 33), "b": (0, 7, 30, 50)}
+    for tag in "ab":
+        imgs, masks, bkgd, rgbs = g[f"imgs_{tag}"], g[f"masks_{tag}"], g[f"bkgds_{tag}"][0], g[f"rgbs_{tag}"]
+        nf, H, W = masks.shape
+        vx0, vy0, vx1, vy1 = valid[tag]
+        valid_mask = np.zeros((H, W, 1), dtype=np.float32)
+        valid_mask[vy0:vy1, vx0:vx1] = 1
+        d[f"valid_{tag}"] = np.asarray(valid[tag], dtype=np.int32)
+        for rf in (2, 3):
+            lo = np.stack([area_average(rgbs[f], rf) for f in range(nf)])
+            ssim = np.empty((nf, 2), dtype=np.float32)
+            psnr = np.empty((nf, 2, 3), dtype=np.float64)
+            for f in range(nf):
+                for use_bg in (0, 1):
+                    gt_img = imgs[f] / 255.
+                    gt_mask = masks[f][:, :, None].astype(np.float32)
+                    if use_bg:
+                        gt_img = gt_img * gt_mask + (1. - gt_mask) * (bkgd / 255.)
+                    gt_imgs = gt_img.astype(np.float32)[None]
+                    th_rgbs = torch.tensor(lo[f:f + 1]).permute(0, 3, 1, 2)
+                    th_rgbs = F.interpolate(th_rgbs, size=gt_imgs.shape[1:3], mode='bilinear', align_corners=False).cpu()
+                    up = th_rgbs.permute(0, 2, 3, 1).numpy()
+                    th_gt = torch.tensor(gt_imgs).permute(0, 3, 1, 2).cpu()
+                    v = ssim_eval(th_rgbs, th_gt)
+                    assert v.shape == (1,) and v.dtype == torch.float32 and up.dtype == np.float32
+                    ssim[f, use_bg] = v.numpy()[0]
+                    sqr_diff = np.square(gt_imgs - up)
+                    psnr[f, use_bg, 0] = (-10. * np.log10(np.mean(sqr_diff.reshape(1, -1), axis=-1)))[0]
+                    for j, m in ((1, gt_mask[None]), (2, valid_mask[None])):
+                        denom = np.maximum(m.reshape(1, -1).sum(-1) * 3., 1.)
+                        psnr[f, use_bg, j] = (-10. * np.log10((sqr_diff * m[..., :1]).reshape(1, -1).sum(-1) / denom))[0]
+                    n += 1
+            d[f"lo_{tag}_rf{rf}"], d[f"ssim_{tag}_rf{rf}"], d[f"psnr_{tag}_rf{rf}"] = lo, ssim, psnr
+    np.savez_compressed(os.path.join(out, "frame_metrics_val.npz"), **d)
+    print(f"[frame_metrics_val] {n} cases")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ref", default="/root/reference")
@@ -824,6 +875,9 @@ def main():
     # frame scores: the vendored pytorch_msssim on cropped pairs (consumes no torch RNG state)
     if want("frame_metrics"):
         gen_frame_metrics(a.out)
+    # validation scores: the same frames at H // rf x W // rf, torch's float32 upsampling (reads frame_metrics.npz; no RNG state)
+    if want("frame_metrics_val"):
+        gen_frame_metrics_val(a.out)
 
 
 if __name__ == "__main__":
