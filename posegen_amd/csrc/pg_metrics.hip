@@ -190,7 +190,7 @@ __global__ __launch_bounds__(THREADS) void frame_metrics_kernel(Args a) {
             for (int q = 0; q < NR; ++q) s[q] += red[w][q];
             c[0] += redi[w][0]; c[1] += redi[w][1];
         }
-        double* o = a.slots + (VALID ? slot_offset_val(a.ntx, tx, ty) : slot_offset(a.ntx, tx, ty));
+        double* o = a.slots + slot_offset(a.ntx, tx, ty, VALID ? SUMS_VAL : SUMS);
         o[0] = 3.0 * xs.own * ys.own; o[1] = s[0]; o[2] = (double)c[0]; o[3] = s[1];     // (n_fg: a lane per channel has counted 3 m)
         o[4] = 3.0 * xs.map * ys.map; o[5] = s[2]; o[6] = (double)c[1]; o[7] = s[3];
         if constexpr (VALID) {
@@ -284,7 +284,7 @@ int frame_metrics(pg_handle* h, const char* who, bool wide, void* stream, const 
     const int ntx = pgsp::tiles_along(w), nty = pgsp::tiles_along(hh);
     const bool up = wide && (rgb_h != bank->H || rgb_w != bank->W), val = wide && valid;
     PG_HIP(h, hipSetDevice(h->device));
-    PG_TRY(pg_grow(h, s->slots, val ? pgsp::slot_bytes_val(w, hh) : pgsp::slot_bytes(w, hh), "frame metrics tile sums"));
+    PG_TRY(pg_grow(h, s->slots, pgsp::slot_bytes(w, hh, val ? pgsp::SUMS_VAL : pgsp::SUMS), "frame metrics tile sums"));
     pgs::Args a{rgb, bank->imgs + (size_t)img_row * bank->P * 3, bank->masks ? bank->masks + (size_t)img_row * bank->P : nullptr, bg,
                 bank->W, box[0], box[1], w, hh, ntx, {}, s->slots.as<double>(), bank->H, up ? rgb_h : bank->H, up ? rgb_w : bank->W,
                 val ? valid[0] - box[0] : 0, val ? valid[1] - box[1] : 0, val ? valid[2] - box[0] : 0, val ? valid[3] - box[1] : 0};

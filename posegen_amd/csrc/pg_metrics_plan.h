@@ -1,8 +1,9 @@
 // pg_metrics_plan.h -- the box and tile arithmetic of pg_frame_metrics and pg_frame_metrics_val (pg_metrics.hip, DESIGN.md 2.8,
 // 2.8b): the check of a box against its frame, the grid of tiles over the box, what a tile stages, which pixels' squared errors
-// and which map pixels it owns, where its partial sums go, and the per-axis taps and the blend of the bilinear resampling.  Host-only and free of HIP calls, like pg_frames_plan.h, so that it compiles into a plain C++ program
-// (tools/sanitize/metrics_plan_asan.cpp, metrics_resample_asan.cpp, built with the address and undefined-behaviour sanitisers); the kernel runs the same
-// functions on the device.
+// and which map pixels it owns, where its partial sums go, and the per-axis taps and the blend of the bilinear resampling.
+// Free of HIP calls, like pg_frames_plan.h, so that it compiles into plain C++ programs (tools/sanitize/metrics_plan_asan.cpp and
+// metrics_resample_asan.cpp, built with the address and undefined-behaviour sanitisers); the kernel runs the same functions on
+// the device.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -54,12 +55,9 @@ PG_METRICS_HD inline Span tile_span(int len, int t) {
     return s;
 }
 
-// Partial sums of tile (tx, ty): SUMS doubles at this offset of the slot buffer
-PG_METRICS_HD inline size_t slot_offset(int ntx, int tx, int ty) { return ((size_t)ty * ntx + tx) * SUMS; }
-inline size_t slot_bytes(int w, int h) { return (size_t)tiles_along(w) * tiles_along(h) * SUMS * sizeof(double); }
-// ... and of a tile of pg_frame_metrics_val with a valid rectangle: SUMS_VAL doubles
-PG_METRICS_HD inline size_t slot_offset_val(int ntx, int tx, int ty) { return ((size_t)ty * ntx + tx) * SUMS_VAL; }
-inline size_t slot_bytes_val(int w, int h) { return (size_t)tiles_along(w) * tiles_along(h) * SUMS_VAL * sizeof(double); }
+// Partial sums of tile (tx, ty): n doubles at this offset of the slot buffer, n = SUMS, or SUMS_VAL with a valid rectangle
+PG_METRICS_HD inline size_t slot_offset(int ntx, int tx, int ty, int n) { return ((size_t)ty * ntx + tx) * n; }
+inline size_t slot_bytes(int w, int h, int n) { return (size_t)tiles_along(w) * tiles_along(h) * n * sizeof(double); }
 
 // ---- pg_frame_metrics_val: the valid rectangle and the bilinear resampling of a low-resolution frame ----------------
 // A valid rectangle (vx0, vy0, vx1, vy1) inside an H x W frame; it may be empty (x0 == x1 or y0 == y1), unlike a box

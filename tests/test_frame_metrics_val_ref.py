@@ -1,4 +1,4 @@
-"""Validation scores without a GPU: the float64 restatement of pg_frame_metrics_val (tests/metrics_val_ref.py) -- its upsampling
+"""Validation scores without a GPU: the float64 restatement of pg_frame_metrics_val (tests/metrics_ref.py) -- its upsampling
 against torch's float64 F.interpolate and its own edge cases, its scores against the reference's values on torch's float32
 upsampling (tests/golden/frame_metrics_val.npz) -- the mapping of evaluation_helpers.py:296-385 on hand-written sums, the refusals
 of posegen_amd.evaluate's validation names, the header and the binding, and the resampling tables and 12-wide slots under the
@@ -15,7 +15,6 @@ import torch.nn.functional as F
 
 from posegen_amd import _ffi, evaluate as ev
 from tests import metrics_ref as ref
-from tests import metrics_val_ref as vref
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # |restatement - reference float32 SSIM| over the fixture's 12 whole-frame cases, measured on the CPU: worst 5.294e-6 (50 x 37 from
@@ -55,32 +54,32 @@ def torch64(lo, H, W):
 def test_upsampling_to_the_same_size_is_the_frame_bit_for_bit():
     lo = np.random.RandomState(0).rand(37, 50, 3).astype(np.float32)
     lo[3, 4] = [0.0, 1.0, 1e-40]                                        # a zero, a one and a subnormal
-    assert vref.up(lo, 37, 50).tobytes() == lo.tobytes()
-    i0, i1, l1 = vref.axis_taps(37, 37)
+    assert ref.up(lo, 37, 50).tobytes() == lo.tobytes()
+    i0, i1, l1 = ref.axis_taps(37, 37)
     assert np.array_equal(i0, np.arange(37)) and np.all(l1 == 0)
 
 
 def test_one_texel_along_an_axis_and_the_clamped_borders():
     rng = np.random.RandomState(1)
     row = rng.rand(1, 9, 3).astype(np.float32)                          # h_lo = 1: every output row is the row upsampled along x
-    U = vref.up(row, 7, 20)
+    U = ref.up(row, 7, 20)
     assert all(U[y].tobytes() == U[0].tobytes() for y in range(7))
     col = rng.rand(9, 1, 3).astype(np.float32)                          # w_lo = 1: constant rows
-    U = vref.up(col, 20, 7)
+    U = ref.up(col, 20, 7)
     assert all(U[:, x].tobytes() == U[:, 0].tobytes() for x in range(7))
-    assert vref.up(row, 1, 9).tobytes() == row.tobytes()
+    assert ref.up(row, 1, 9).tobytes() == row.tobytes()
     one = rng.rand(1, 1, 3).astype(np.float32)
-    assert np.all(vref.up(one, 5, 6) == one[0, 0])
+    assert np.all(ref.up(one, 5, 6) == one[0, 0])
     # the first and last output rows / columns take the clamped texels: src < 0 -> texel 0 alone; the last texel blends with itself
     lo = rng.rand(18, 25, 3).astype(np.float32)
-    U = vref.up(lo, 37, 50)
+    U = ref.up(lo, 37, 50)
     for n_in, n_out in ((18, 37), (25, 50), (12, 37), (1, 4096), (500, 1000)):
-        i0, i1, l1 = vref.axis_taps(n_in, n_out)
+        i0, i1, l1 = ref.axis_taps(n_in, n_out)
         assert i0[0] == 0 and l1[0] == 0 and i0[-1] == n_in - 1 and i1[-1] == n_in - 1
         assert i0.min() >= 0 and i1.max() <= n_in - 1 and np.all(np.diff(i0) >= 0) and np.all((l1 >= 0) & (l1 <= 1))
     assert U[0, 0].tobytes() == lo[0, 0].tobytes() and U[-1, -1].tobytes() == lo[-1, -1].tobytes()
     assert U[0, -1].tobytes() == lo[0, -1].tobytes() and U[-1, 0].tobytes() == lo[-1, 0].tobytes()
-    assert np.array_equal(U[0], vref.up(lo[:1], 1, 50)[0]) and np.array_equal(U[:, -1:], vref.up(lo[:, -1:], 37, 1))
+    assert np.array_equal(U[0], ref.up(lo[:1], 1, 50)[0]) and np.array_equal(U[:, -1:], ref.up(lo[:, -1:], 37, 1))
 
 
 def test_the_restatement_is_torch_float64_interpolate_within_one_float32_rounding():
@@ -92,7 +91,7 @@ def test_the_restatement_is_torch_float64_interpolate_within_one_float32_roundin
     for (h, w), (H, W) in (((18, 25), (37, 50)), ((12, 16), (37, 50)), ((18, 24), (36, 48)), ((37, 50), (75, 101)), ((25, 33), (75, 101)),
                            ((75, 50), (75, 101)), ((1, 101), (75, 101)), ((75, 1), (75, 101)), ((167, 167), (501, 501))):
         lo = rng.rand(h, w, 3).astype(np.float32)
-        dev = np.abs(vref.up(lo, H, W).astype(np.float64) - torch64(lo, H, W)).max()
+        dev = np.abs(ref.up(lo, H, W).astype(np.float64) - torch64(lo, H, W)).max()
         print(f"{h} x {w} -> {H} x {W}: worst |up - torch float64| {dev:.3e}")
         worst = max(worst, dev)
         assert dev <= 2.0 ** -25 + 16 * 2.0 ** -53
@@ -107,7 +106,7 @@ def test_restatement_scores_equal_the_reference_on_torch_float32_upsampling(gold
     for tag, rf, f, use_bg, img, mask, bk, lo, valid, want, psnr in golden_val_cases(golden):
         H, W = mask.shape
         assert lo.shape == (H // rf, W // rf, 3) and np.isfinite(want)
-        s = vref.frame_sums_val(img, mask, bk, lo, (0, 0, W, H), golden["taps"], bool(use_bg), valid)
+        s = ref.frame_sums_val(img, mask, bk, lo, (0, 0, W, H), golden["taps"], bool(use_bg), valid)
         assert s[4] == 3 * (W - 10) * (H - 10) and s[0] == 3 * H * W
         assert s[8] == 3 * (valid[2] - valid[0]) * (valid[3] - valid[1]) and s[2] == 3 * int((mask > 0).sum())
         dev = abs(s[5] / s[4] - want)
@@ -128,19 +127,19 @@ def test_valid_sums_of_the_restatement(golden):
     img, mask, bk, lo = g["imgs_a"][0], g["masks_a"][0], g["bkgds_a"][0], g["lo_a_rf2"][0]
     H, W = mask.shape
     box = (3, 4, 40, 33)
-    s = vref.frame_sums_val(img, mask, bk, lo, box, g["taps"], False, box)           # valid = the box: the box's own sums
+    s = ref.frame_sums_val(img, mask, bk, lo, box, g["taps"], False, box)           # valid = the box: the box's own sums
     assert s[8] == s[0] and s[9] == s[1]
     inner = (box[0] + 5, box[1] + 5, box[2] - 5, box[3] - 5)                          # ... and the map's pixels are its inner centres
-    s = vref.frame_sums_val(img, mask, bk, lo, box, g["taps"], False, inner)
+    s = ref.frame_sums_val(img, mask, bk, lo, box, g["taps"], False, inner)
     assert s[10] == s[4] and s[11] == s[5]
-    s = vref.frame_sums_val(img, mask, bk, lo, box, g["taps"], False, (41, 0, 48, 36))             # beside the box
+    s = ref.frame_sums_val(img, mask, bk, lo, box, g["taps"], False, (41, 0, 48, 36))             # beside the box
     assert np.all(s[8:] == 0) and s[0] > 0
-    s = vref.frame_sums_val(img, mask, bk, lo, box, g["taps"], False, (20, 17, 21, 18))            # one pixel: its three map values
-    U = vref.up(lo, H, W)
+    s = ref.frame_sums_val(img, mask, bk, lo, box, g["taps"], False, (20, 17, 21, 18))            # one pixel: its three map values
+    U = ref.up(lo, H, W)
     x = U[4:33, 3:40].astype(np.float64)
     y = ref.ground_truth(img, mask, bk, False)[4:33, 3:40].astype(np.float64)
     assert s[8] == 3 and s[10] == 3 and abs(s[11] - ref.ssim_map(x, y, g["taps"])[17 - 4 - 5, 20 - 3 - 5].sum()) < 1e-12
-    assert np.all(vref.frame_sums_val(img, mask, bk, lo, box, g["taps"])[8:] == 0)                 # no valid rectangle
+    assert np.all(ref.frame_sums_val(img, mask, bk, lo, box, g["taps"])[8:] == 0)                 # no valid rectangle
 
 
 def test_scores_from_sums_follow_the_validation_mapping():
@@ -171,6 +170,54 @@ def test_scores_from_sums_follow_the_validation_mapping():
     assert ev.validation_scores(np.zeros((0, 12)))["psnr"] is None
     with pytest.raises(ValueError, match="eval_both needs masks"):
         ev.validation_scores(sums, use_masks=False, eval_both=True)
+
+
+def test_eight_sums_take_the_same_mapping_as_evaluate_metric_had():
+    """`validation_scores` on FrameScorer's eight sums, which is what `evaluate_metric` returns: hand-written rows against
+    evaluation_helpers.py:296-364 written out per frame here, with masks and without.  The one place where that function's own
+    mapping differed -- no inf -> 0 on the unmasked SSIM mean -- cannot show: a frame below the window has n_map = ssim = 0, which
+    is NaN with and without it."""
+    #                 n     se  n_fg se_fg n_map ssim n_fg_map ssim_fg
+    rows = {"normal": [300., 3., 30., 0.6, 150., 120., 12., 9.],
+            "no mask pixel": [300., 6., 0., 0.0, 150., 100., 0., 0.],
+            "perfect": [300., 0., 30., 0.0, 150., 150., 12., 12.],
+            "below the window": [90., 1.8, 30., 0.9, 0., 0., 0., 0.]}
+    nan, inf = float("nan"), float("inf")
+
+    def reference(sums, masks):
+        psnr = lambda mse: -10. * np.log10(mse) if mse > 0 else inf
+        zero_inf = lambda v: 0. if v == inf else v
+        if masks:
+            kept = [r for r in sums if r[2] > 0]                                        # :296-305
+            fg_psnr = [zero_inf(psnr(r[3] / max(r[2], 1.))) for r in kept]              # :325-328
+            fg_ssim = [zero_inf(r[7] / max(r[6], 1.)) for r in kept]                    # :331-332, this project's masked SSIM
+            fg_psnr, fg_ssim = (np.mean(v) if kept else None for v in (fg_psnr, fg_ssim))
+            return {"psnr": fg_psnr, "ssim": fg_ssim, "psnr_fg": fg_psnr, "ssim_fg": fg_ssim}        # :361-364
+        test_psnr = [zero_inf(psnr(r[1] / r[0])) for r in sums]                         # :348-349
+        test_ssim = [r[5] / r[4] if r[4] > 0 else nan for r in sums]                    # :352-353: the mean of a map without pixels
+        return {"psnr": np.mean(test_psnr) if sums else None, "ssim": np.mean(test_ssim) if sums else None, "psnr_fg": None, "ssim_fg": None}
+
+    for names in (list(rows), ["normal", "no mask pixel", "perfect"], ["below the window"], ["no mask pixel"], []):
+        sums = [rows[k] for k in names]
+        for masks in (True, False):
+            got = ev.validation_scores(np.asarray(sums, np.float64).reshape(-1, 8), use_masks=masks, eval_both=False)
+            want = reference(sums, masks)
+            print(names, "masks" if masks else "no masks", got, want)
+            assert list(got) == ["psnr", "ssim", "psnr_fg", "ssim_fg"]
+            for key in got:
+                if want[key] is None:
+                    assert got[key] is None, (names, masks, key)
+                elif np.isnan(want[key]):
+                    assert np.isnan(got[key]), (names, masks, key)
+                else:
+                    assert np.isclose(got[key], want[key], rtol=1e-14, atol=0), (names, masks, key, got[key], want[key])
+    whole = ev.validation_scores(np.asarray([rows["normal"], rows["perfect"]]), use_masks=False)
+    assert np.isclose(whole["psnr"], 10.0, rtol=1e-14) and np.isclose(whole["ssim"], 0.9, rtol=1e-14)       # (20 + 0) / 2, (0.8 + 1) / 2
+    assert np.isnan(ev.validation_scores(np.asarray([rows["normal"], rows["below the window"]]), use_masks=False)["ssim"])
+    with pytest.raises(ValueError, match="eval_both"):
+        ev.validation_scores(np.asarray([rows["normal"]]), eval_both=True)
+    with pytest.raises(ValueError, match="validation_scores"):
+        ev.validation_scores(np.zeros((2, 9)))
 
 
 def _fake_bank(device="cuda:0", HW=(36, 48), masks=True, bkgds=False):
@@ -238,7 +285,7 @@ def test_header_binding_and_package_export_the_entry_point():
     assert re.search(r"constexpr int SUMS = 8;", plan) and re.search(r"constexpr int SUMS_VAL = 12;", plan)
     lib = _ffi.load_library()
     assert hasattr(lib, "pg_frame_metrics_val") and len(_ffi.PROTOTYPES["pg_frame_metrics_val"][1]) == 11
-    assert len(ev.SUMS_VAL) == 12 and ev.SUMS_VAL == vref.SUMS and ev.SUMS_VAL[:8] == ev.SUMS
+    assert len(ev.SUMS_VAL) == 12 and ev.SUMS_VAL == ref.SUMS_VAL and ev.SUMS == ref.SUMS and ev.SUMS_VAL[:8] == ev.SUMS
     assert posegen_amd.ValidationScorer is ev.ValidationScorer and posegen_amd.evaluate_validation is ev.evaluate_validation
     assert posegen_amd.evaluate_testset is ev.evaluate_testset
     # a null handle is refused before anything else
@@ -246,7 +293,7 @@ def test_header_binding_and_package_export_the_entry_point():
 
 
 def test_resampling_tables_and_wide_slots_are_clean_under_address_and_ub_sanitizers(tmp_path):
-    """pg_metrics_plan.h's resample_tap / resample_blend / overlap / slot_offset_val as a stand-alone program with its own main:
+    """pg_metrics_plan.h's resample_tap / resample_blend / overlap / slot_offset at SUMS_VAL as a stand-alone program with its own main:
     every n_in <= n_out <= 130 plus 500 -> 1000 and 1 -> 4096 -- every tile's table entries name texels of the low-resolution
     axis, weights in [0, 1], i0 never runs backwards -- and every 12-wide slot inside its buffer and written once, the counts from
     the spans equal to the pixels counted one by one."""

@@ -4,7 +4,6 @@ the reference's values (tests/golden/frame_metrics.npz) within the bound of test
 
 The 1e-9: kernel and restatement add at most 2e5 double terms of magnitude <= 1 in different orders (<= 2e5 x 1.1e-16 relative),
 the window sums a few ulps more.  Frames are at most 320 x 200; a tile is 32 x 32 map pixels (42 x 42 box pixels)."""
-import ctypes as C
 import os
 import types
 
@@ -14,58 +13,19 @@ import torch
 
 from posegen_amd import _ffi, evaluate as ev
 from tests import metrics_ref as ref
+from tests.frame_metrics_gpu import DEV, abi_sums, assert_sums, make_bank, renderer, synthetic_frames  # noqa: F401 (renderer: a fixture)
 from tests.test_frame_metrics_ref import F32_EPS, PSNR_ULPS, SSIM_BOUND, golden_cases
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EINVAL = -1
 TILE = 32
 H, W = 200, 320
-COUNTS, REALS = (0, 2, 4, 6), (1, 3, 5, 7)
-
-
-@pytest.fixture(scope="module")
-def renderer():
-    from posegen_amd import surreal_config
-    from posegen_amd.raycaster import HipRenderer
-    r = HipRenderer(surreal_config(), device=DEV)          # no weights loaded: the entry point needs none
-    yield r
-    r.close()
 
 
 @pytest.fixture(scope="module")
 def golden():
     return dict(np.load(os.path.join(REPO, "tests", "golden", "frame_metrics.npz")))
-
-
-def make_bank(renderer, imgs, masks, bkgds=None):
-    """a DeviceImageBank of imgs [F,H,W,3], masks [F,H,W] and backgrounds [n,H,W,3] (all images use background 0)"""
-    from posegen_amd.batches import DeviceImageBank
-    F, h, w = masks.shape
-    c2ws = np.tile(np.eye(4, dtype=np.float32)[None], (F, 1, 1))
-    return DeviceImageBank(renderer, imgs.reshape(F, h * w, 3), masks.reshape(F, h * w, 1), masks.reshape(F, h * w, 1), c2ws,
-                           np.full(F, 100.0, np.float32), (h, w), bkgds=None if bkgds is None else bkgds.reshape(len(bkgds), h * w, 3),
-                           bkgd_idxs=None if bkgds is None else np.zeros(F, np.int32))
-
-
-def synthetic_frames(h, w, F, seed):
-    """uint8 images, elliptic masks, one background and float32 'rendered' frames: ground truth plus noise, a region that is
-    constant white in both (rows < h/3, the right third and 13 columns: windows that see nothing else)"""
-    rng = np.random.RandomState(seed)
-    yy, xx = np.mgrid[0:h, 0:w]
-    imgs = np.empty((F, h, w, 3), np.uint8)
-    masks = np.empty((F, h, w), np.uint8)
-    rgbs = np.empty((F, h, w, 3), np.float32)
-    white = (yy < h // 3) & (xx >= w - w // 3 - 13)
-    for f in range(F):
-        smooth = 127 + 90 * np.stack([np.sin(xx / (7. + c + f) + yy / 11.) * np.cos(yy / (5. + f) - c) for c in range(3)], -1)
-        imgs[f] = np.clip(smooth + rng.randint(-20, 21, size=(h, w, 3)), 0, 255).astype(np.uint8)
-        masks[f] = ((xx - w * (0.45 + 0.1 * f)) ** 2 / (0.3 * w) ** 2 + (yy - h * 0.55) ** 2 / (0.35 * h) ** 2 < 1).astype(np.uint8)
-        imgs[f][white] = 255
-        rgbs[f] = np.clip(imgs[f] / 255. + rng.normal(0, 0.06, size=(h, w, 3)), 0, 1).astype(np.float32)
-        rgbs[f][white] = 1.0
-    return imgs, masks, rng.randint(0, 256, size=(1, h, w, 3)).astype(np.uint8), rgbs, white
 
 
 @pytest.fixture(scope="module")
@@ -75,23 +35,6 @@ def scene(renderer):
     bank = make_bank(renderer, imgs, masks, bkgds)
     return types.SimpleNamespace(imgs=imgs, masks=masks, bkgds=bkgds, rgbs=rgbs, white=white, bank=bank, dev_rgbs=torch.from_numpy(rgbs).to(DEV),
                     taps=ref.header_taps())
-
-
-def abi_sums(r, bank_struct, img_row, box, rgb_dev, flags, out=None):
-    """pg_frame_metrics through the C ABI -> (return code, float64 [8] from the device)"""
-    out = torch.full((8,), -7.0, dtype=torch.float64, device=DEV) if out is None else out
-    rc = r.lib.pg_frame_metrics(r.handle, r._stream(), C.byref(bank_struct), int(img_row), (C.c_int32 * 4)(*(int(v) for v in box)),
-                                C.c_void_p(rgb_dev.data_ptr()), int(flags), C.c_void_p(out.data_ptr()))
-    torch.cuda.synchronize()
-    return rc, out.cpu().numpy()
-
-
-def assert_sums(got, want, what=""):
-    print(what, "got", got, "want", want)
-    for i in COUNTS:
-        assert got[i] == want[i], (what, ref.SUMS[i], got[i], want[i])
-    for i in REALS:
-        assert abs(got[i] - want[i]) <= 1e-9 * max(1.0, abs(want[i])), (what, ref.SUMS[i], got[i], want[i], got[i] - want[i])
 
 
 BOXES = {
@@ -118,7 +61,7 @@ def test_sums_equal_the_restatement(renderer, scene, name, flags):
     rc, got = abi_sums(renderer, scene.bank.struct, f, box, scene.dev_rgbs[f], flags)
     assert rc == 0, renderer.lib.pg_last_error(renderer.handle)
     want = ref.frame_sums(scene.imgs[f], scene.masks[f], scene.bkgds[0], scene.rgbs[f], box, scene.taps, bool(flags))
-    assert_sums(got, want, name)
+    assert_sums(got, want, ref.SUMS, name)
     if "below" in name:
         assert np.all(got[4:] == 0) and got[0] == 3 * (box[2] - box[0]) * (box[3] - box[1]) and got[1] > 0
 
@@ -133,7 +76,7 @@ def test_a_frame_with_an_odd_width(renderer, golden):
             rc, got = abi_sums(renderer, bank.struct, 0, box, rgb, flags)
             assert rc == 0
             assert_sums(got, ref.frame_sums(g["imgs_b"][0], g["masks_b"][0], g["bkgds_b"][0], g["rgbs_b"][0], box, g["taps"], bool(flags)),
-                        f"box {tuple(box)} flags {flags}")
+                        ref.SUMS, f"box {tuple(box)} flags {flags}")
 
 
 def test_masks_empty_full_and_one_pixel_on_a_tile_seam(renderer, scene):
@@ -155,7 +98,7 @@ def test_masks_empty_full_and_one_pixel_on_a_tile_seam(renderer, scene):
             rc, got = abi_sums(renderer, bank.struct, f, box, scene.dev_rgbs[0], flags)
             assert rc == 0
             want = ref.frame_sums(imgs[f], masks[f], scene.bkgds[0], scene.rgbs[0], box, scene.taps, bool(flags))
-            assert_sums(got, want, f"{what} flags {flags}")
+            assert_sums(got, want, ref.SUMS, f"{what} flags {flags}")
             if what == "empty":
                 assert got[2] == 0 and got[3] == 0 and got[6] == 0 and got[7] == 0
             if what == "all ones":
@@ -188,14 +131,14 @@ def test_two_calls_give_identical_bytes_and_a_row_leaves_its_neighbour_alone(ren
     sc.score(2, scene.dev_rgbs[0], 0, box)                      # grows the tensor past its capacity of 2
     s = sc.sums()
     assert s.shape == (3, 8) and s[0].tobytes() == first[0].tobytes() == s[2].tobytes()
-    assert_sums(s[1], ref.frame_sums(scene.imgs[1], scene.masks[1], scene.bkgds[0], scene.rgbs[1], (0, 0, W, H), scene.taps, True), "row 1")
+    assert_sums(s[1], ref.frame_sums(scene.imgs[1], scene.masks[1], scene.bkgds[0], scene.rgbs[1], (0, 0, W, H), scene.taps, True), ref.SUMS, "row 1")
     rc, again = abi_sums(renderer, scene.bank.struct, 0, (11, 13, 142, 110), scene.dev_rgbs[0], _ffi.PG_METRICS_BG)
     assert rc == 0 and again.tobytes() == first[0].tobytes()
     # without masks the kernel is told there is no foreground
     nm = ev.FrameScorer(scene.bank, use_masks=False, background=False)
     nm.score(0, scene.dev_rgbs[0], 0, box)
     want = ref.frame_sums(scene.imgs[0], None, None, scene.rgbs[0], (11, 13, 142, 110), scene.taps, False)
-    assert_sums(nm.sums()[0], want, "no masks")
+    assert_sums(nm.sums()[0], want, ref.SUMS, "no masks")
 
 
 def test_bad_arguments_are_einval_and_leave_the_output_untouched(renderer, scene):

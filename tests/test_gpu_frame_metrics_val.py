@@ -1,12 +1,11 @@
 """pg_frame_metrics_val on the GPU, through the C ABI and through ValidationScorer / evaluate_validation / evaluate_testset: a frame
 of the bank's size gives pg_frame_metrics' bytes; a low-resolution frame gives, bit for bit, what pg_frame_metrics gives on the
-restatement's upsampled frame (tests/metrics_val_ref.py); all twelve sums against the float64 restatement -- the counts exactly, the
+restatement's upsampled frame (tests/metrics_ref.py); all twelve sums against the float64 restatement -- the counts exactly, the
 real sums within 1e-9 max(1, |sum|) -- and the mapped scores against the reference's values on torch's float32 upsampling
 (tests/golden/frame_metrics_val.npz) within the bounds of tests/test_frame_metrics_val_ref.py.
 
 The 1e-9 is tests/test_gpu_frame_metrics.py's, for its reason: kernel and restatement add at most 2.3e4 double terms of magnitude
 <= 1 in different orders.  The bank is two 75 x 101 images: three tiles of 32 x 32 map pixels along each axis, the last ones ragged."""
-import ctypes as C
 import os
 import types
 
@@ -16,17 +15,14 @@ import torch
 
 from posegen_amd import _ffi, evaluate as ev
 from tests import metrics_ref as ref
-from tests import metrics_val_ref as vref
+from tests.frame_metrics_gpu import DEV, abi_sums, abi_val, assert_sums, make_bank, renderer, synthetic_frames  # noqa: F401 (renderer: a fixture)
 from tests.test_frame_metrics_val_ref import F32_EPS, PSNR_ULPS, SSIM_VAL_BOUND, golden_val_cases
-from tests.test_gpu_frame_metrics import make_bank, synthetic_frames
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EINVAL = -1
 TILE = 32
 H, W = 75, 101
-COUNTS, REALS = (0, 2, 4, 6, 8, 10), (1, 3, 5, 7, 9, 11)
 LO_SHAPES = [(37, 50), (25, 33), (75, 50), (1, 101), (75, 1)]        # rf 2 with both ratios non-integer, rf 3, one axis only, one row, one column
 
 BOXES = {
@@ -56,15 +52,6 @@ VALIDS = {
 
 
 @pytest.fixture(scope="module")
-def renderer():
-    from posegen_amd import surreal_config
-    from posegen_amd.raycaster import HipRenderer
-    r = HipRenderer(surreal_config(), device=DEV)          # no weights loaded: the entry point needs none
-    yield r
-    r.close()
-
-
-@pytest.fixture(scope="module")
 def golden():
     g = dict(np.load(os.path.join(REPO, "tests", "golden", "frame_metrics.npz")))
     g.update(np.load(os.path.join(REPO, "tests", "golden", "frame_metrics_val.npz")))
@@ -78,44 +65,14 @@ def scene(renderer):
     upsampling of each on the host and on the device, and the taps"""
     imgs, masks, bkgds, rgbs, _ = synthetic_frames(H, W, 2, 41)
     rng = np.random.RandomState(43)
-    lo = {(37, 50): vref.area_average(rgbs[0], 2), (25, 33): vref.area_average(rgbs[0], 3)}
+    lo = {(37, 50): ref.area_average(rgbs[0], 2), (25, 33): ref.area_average(rgbs[0], 3)}
     for shape in LO_SHAPES:
         lo.setdefault(shape, rng.rand(*shape, 3).astype(np.float32))
     assert all(lo[s].shape == s + (3,) for s in LO_SHAPES)
-    U = {s: vref.up(lo[s], H, W) for s in LO_SHAPES}
+    U = {s: ref.up(lo[s], H, W) for s in LO_SHAPES}
     return types.SimpleNamespace(imgs=imgs, masks=masks, bkgds=bkgds, rgbs=rgbs, bank=make_bank(renderer, imgs, masks, bkgds),
                                  dev_rgbs=torch.from_numpy(rgbs).to(DEV), lo=lo, U=U, dev_lo={s: torch.from_numpy(v).to(DEV) for s, v in lo.items()},
                                  dev_U={s: torch.from_numpy(v).to(DEV) for s, v in U.items()}, taps=ref.header_taps())
-
-
-def abi_sums(r, bank_struct, img_row, box, rgb_dev, flags):
-    """pg_frame_metrics through the C ABI -> (return code, float64 [8] from the device)"""
-    out = torch.full((8,), -7.0, dtype=torch.float64, device=DEV)
-    rc = r.lib.pg_frame_metrics(r.handle, r._stream(), C.byref(bank_struct), int(img_row), (C.c_int32 * 4)(*(int(v) for v in box)),
-                                C.c_void_p(rgb_dev.data_ptr()), int(flags), C.c_void_p(out.data_ptr()))
-    torch.cuda.synchronize()
-    return rc, out.cpu().numpy()
-
-
-def abi_val(r, bank_struct, img_row, box, rgb_dev, valid, flags, hw=None):
-    """pg_frame_metrics_val through the C ABI -> (return code, float64 [12] from the device, with a guard entry behind them)"""
-    out = torch.full((13,), -7.0, dtype=torch.float64, device=DEV)
-    h, w = rgb_dev.shape[:2] if hw is None else hw
-    rc = r.lib.pg_frame_metrics_val(r.handle, r._stream(), C.byref(bank_struct), int(img_row), (C.c_int32 * 4)(*(int(v) for v in box)),
-                                    C.c_void_p(rgb_dev.data_ptr()), int(h), int(w),
-                                    None if valid is None else (C.c_int32 * 4)(*(int(v) for v in valid)), int(flags), C.c_void_p(out.data_ptr()))
-    torch.cuda.synchronize()
-    out = out.cpu().numpy()
-    assert out[12] == -7.0                                  # nothing behind the twelve is written
-    return rc, out[:12]
-
-
-def assert_sums(got, want, what=""):
-    print(what, "got", got, "want", want)
-    for i in COUNTS:
-        assert got[i] == want[i], (what, vref.SUMS[i], got[i], want[i])
-    for i in REALS:
-        assert abs(got[i] - want[i]) <= 1e-9 * max(1.0, abs(want[i])), (what, vref.SUMS[i], got[i], want[i], got[i] - want[i])
 
 
 @pytest.mark.parametrize("name", list(BOXES))
@@ -156,8 +113,8 @@ def test_all_twelve_sums_equal_the_restatement(renderer, scene, shape, box):
         for flags in (0, _ffi.PG_METRICS_BG):
             rc, got = abi_val(renderer, scene.bank.struct, 0, box, dev_lo, valid, flags)
             assert rc == 0, renderer.lib.pg_last_error(renderer.handle)
-            want = vref.frame_sums_val(scene.imgs[0], scene.masks[0], scene.bkgds[0], lo, box, scene.taps, bool(flags), valid)
-            assert_sums(got, want, f"{shape} box {box} valid {what} flags {flags}")
+            want = ref.frame_sums_val(scene.imgs[0], scene.masks[0], scene.bkgds[0], lo, box, scene.taps, bool(flags), valid)
+            assert_sums(got, want, ref.SUMS_VAL, f"{shape} box {box} valid {what} flags {flags}")
             if what in ("disjoint from it", "empty") and box == BOX3:
                 assert np.all(got[8:] == 0)
             if what == "equal to it" and box == BOX3:
@@ -191,7 +148,7 @@ def test_mapped_scores_equal_the_reference_values(renderer, golden):
     assert len(cases) == 12
     # evaluate_validation on set a at rf 2: the means of the per-frame values, the valid pair in front with eval_both
     lo, valid = g["lo_a_rf2"], [g["valid_a"]] * 2
-    s = np.stack([vref.frame_sums_val(g["imgs_a"][f], g["masks_a"][f], g["bkgds_a"][0], lo[f], (0, 0, 48, 36), g["taps"], True, valid[f]) for f in range(2)])
+    s = np.stack([ref.frame_sums_val(g["imgs_a"][f], g["masks_a"][f], g["bkgds_a"][0], lo[f], (0, 0, 48, 36), g["taps"], True, valid[f]) for f in range(2)])
     both = ev.evaluate_validation(lo, banks["a"], [0, 1], valid_boxes=valid, eval_both=True, background=True)
     assert abs(both["psnr"] - np.mean(-10 * np.log10(s[:, 9] / s[:, 8]))) <= 1e-9 and abs(both["ssim"] - np.mean(s[:, 11] / s[:, 10])) <= 1e-9
     assert abs(both["psnr_fg"] - np.mean(-10 * np.log10(s[:, 3] / s[:, 2]))) <= 1e-9 and abs(both["ssim_fg"] - np.mean(s[:, 7] / s[:, 6])) <= 1e-9
@@ -199,7 +156,7 @@ def test_mapped_scores_equal_the_reference_values(renderer, golden):
     fg = ev.evaluate_validation(torch.from_numpy(lo).to(DEV), banks["a"], [0, 1], background=True)
     assert fg["psnr"] == fg["psnr_fg"] == both["psnr_fg"] and fg["ssim"] == fg["ssim_fg"] == both["ssim_fg"]
     whole = ev.evaluate_validation(lo, banks["a"], [0, 1], use_masks=False)
-    s = np.stack([vref.frame_sums_val(g["imgs_a"][f], None, None, lo[f], (0, 0, 48, 36), g["taps"]) for f in range(2)])
+    s = np.stack([ref.frame_sums_val(g["imgs_a"][f], None, None, lo[f], (0, 0, 48, 36), g["taps"]) for f in range(2)])
     assert abs(whole["psnr"] - np.mean(-10 * np.log10(s[:, 1] / s[:, 0]))) <= 1e-9 and abs(whole["ssim"] - np.mean(s[:, 5] / s[:, 4])) <= 1e-9
     assert whole["psnr_fg"] is None
     assert abs(whole["ssim"] - np.mean(g["ssim_a_rf2"][:, 0])) <= SSIM_VAL_BOUND
@@ -214,15 +171,15 @@ def test_two_calls_give_identical_bytes_and_a_row_leaves_its_neighbour_alone(ren
     sc.score(2, lo, 0, valid, box=BOX3)                         # grows the tensor past its capacity of 2
     s = sc.sums()
     assert s.shape == (3, 12) and s[0].tobytes() == first[0].tobytes() == s[2].tobytes()
-    assert_sums(s[1], vref.frame_sums_val(scene.imgs[1], scene.masks[1], scene.bkgds[0], scene.lo[(25, 33)], (0, 0, W, H), scene.taps, True), "row 1")
+    assert_sums(s[1], ref.frame_sums_val(scene.imgs[1], scene.masks[1], scene.bkgds[0], scene.lo[(25, 33)], (0, 0, W, H), scene.taps, True), ref.SUMS_VAL, "row 1")
     assert np.all(s[1, 8:] == 0)
     rc, again = abi_val(renderer, scene.bank.struct, 0, BOX3, lo, (30, 25, 60, 50), _ffi.PG_METRICS_BG)
     assert rc == 0 and again.tobytes() == first[0].tobytes()
     # without masks the kernel is told there is no foreground
     nm = ev.ValidationScorer(scene.bank, use_masks=False, background=False)
     nm.score(0, lo, 0, valid, box=BOX3)
-    want = vref.frame_sums_val(scene.imgs[0], None, None, scene.lo[(37, 50)], BOX3, scene.taps, False, (30, 25, 60, 50))
-    assert_sums(nm.sums()[0], want, "no masks")
+    want = ref.frame_sums_val(scene.imgs[0], None, None, scene.lo[(37, 50)], BOX3, scene.taps, False, (30, 25, 60, 50))
+    assert_sums(nm.sums()[0], want, ref.SUMS_VAL, "no masks")
 
 
 def test_bad_arguments_are_einval_and_leave_the_output_untouched(renderer, scene):

@@ -739,7 +739,7 @@ def gen_frame_metrics(out):
 
 def gen_frame_metrics_val(out):
     """Validation scores (posegen_amd/evaluate.py, pg_frame_metrics_val): the frames of frame_metrics.npz area-averaged (numpy, this
-    repository's tests/metrics_val_ref.area_average) to H // rf x W // rf for rf = 2, 3 -- 36 x 48 -> 18 x 24, 12 x 16 and
+    repository's tests/metrics_ref.area_average) to H // rf x W // rf for rf = 2, 3 -- 36 x 48 -> 18 x 24, 12 x 16 and
     50 x 37 -> 25 x 18, 16 x 12, where the size ratios are not integers -- and for every frame, with and without backgrounds, what
     the lines of evaluation_helpers.py:307-344 give on the whole frame: F.interpolate(bilinear, align_corners=False) in float32,
     the vendored `SSIM(size_average=False)`, and the literal PSNR lines -- all pixels (:348), foreground (:325-327) and under a
@@ -747,7 +747,7 @@ def gen_frame_metrics_val(out):
     import torch
     import torch.nn.functional as F
     from pytorch_msssim import SSIM
-    from tests.metrics_val_ref import area_average
+    from tests.metrics_ref import area_average
     g = np.load(os.path.join(out, "frame_metrics.npz"))
     ssim_eval = SSIM(size_average=False)
     d, n = {}, 0

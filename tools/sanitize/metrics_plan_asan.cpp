@@ -21,7 +21,7 @@ void check_box(int w, int h) {
     const int mw = w > HALO ? w - HALO : 0, mh = h > HALO ? h - HALO : 0;
     const bool has_map = mw > 0 && mh > 0;
     std::vector<char> owned((size_t)w * h, 0), mapped((size_t)mw * mh, 0);
-    std::vector<char> slots(slot_bytes(w, h), 0);
+    std::vector<char> slots(slot_bytes(w, h, SUMS), 0);
     CHECK(slots.size() == (size_t)ntx * nty * SUMS * sizeof(double));
     for (int ty = 0; ty < nty; ++ty)
         for (int tx = 0; tx < ntx; ++tx) {
@@ -44,7 +44,7 @@ void check_box(int w, int h) {
                         CHECK(stage.data()[(size_t)(i + WIN / 2) * xs.sn + j + WIN / 2] == 1);
                     }
             }
-            const size_t off = slot_offset(ntx, tx, ty) * sizeof(double);
+            const size_t off = slot_offset(ntx, tx, ty, SUMS) * sizeof(double);
             for (size_t b = 0; b < SUMS * sizeof(double); ++b) CHECK(slots.data()[off + b]++ == 0);
         }
     for (char c : owned) CHECK(c == 1);

@@ -1,5 +1,5 @@
 // What pg_frame_metrics_val adds to a tile (posegen_amd/csrc/pg_metrics_plan.h: resample_tap, resample_blend, overlap, valid_ok,
-// slot_offset_val, slot_bytes_val) on the CPU under ASan + UBSan.  A tile's tap tables, the low-resolution axis and the slot buffer
+// slot_offset and slot_bytes at SUMS_VAL) on the CPU under ASan + UBSan.  A tile's tap tables, the low-resolution axis and the slot buffer
 // are vectors of this program: a tap that names a texel outside the low-resolution frame, a table entry past the staged rows, or a
 // 12-wide slot outside its buffer shows as a heap overflow; a weight outside [0, 1], a tap that runs backwards, a count that differs
 // from the pixels counted one by one, or a slot written twice as a failed check.
@@ -54,13 +54,13 @@ void check_axis(int n_in, int n_out) {
 // the counts from the spans equal the pixels counted one by one
 void check_slots(int w, int h, int vx0, int vy0, int vx1, int vy1) {
     const int ntx = tiles_along(w), nty = tiles_along(h);
-    std::vector<char> slots(slot_bytes_val(w, h), 0);
+    std::vector<char> slots(slot_bytes(w, h, SUMS_VAL), 0);
     CHECK(slots.size() == (size_t)ntx * nty * SUMS_VAL * sizeof(double));
     long n_valid = 0, n_valid_map = 0;
     for (int ty = 0; ty < nty; ++ty)
         for (int tx = 0; tx < ntx; ++tx) {
             const Span xs = tile_span(w, tx), ys = tile_span(h, ty);
-            const size_t off = slot_offset_val(ntx, tx, ty) * sizeof(double);
+            const size_t off = slot_offset(ntx, tx, ty, SUMS_VAL) * sizeof(double);
             for (size_t b = 0; b < SUMS_VAL * sizeof(double); ++b) CHECK(slots.data()[off + b]++ == 0);
             n_valid += (long)overlap(xs.s0, xs.s0 + xs.own, vx0, vx1) * overlap(ys.s0, ys.s0 + ys.own, vy0, vy1);
             if (xs.map > 0 && ys.map > 0)
