@@ -113,7 +113,8 @@ typedef struct pg_outputs {
     float* disp0;     /* [n]                                                          */
     float* acc0;      /* [n]                                                          */
     float* alpha0;    /* [n, N_samples]                                               */
-    /* optional intermediates (tests / debugging), reference names in comments */
+    /* optional intermediates (tests / debugging; pg_render_scene's lists), reference names in comments.  A z_* / raw_* array on a
+     * 256-byte boundary is the pass's own buffer (written in place), any other is filled by a copy at the end of the call. */
     float* near_far;  /* [n,2]  get_near_far_in_cylinder                              */
     float* z_coarse;  /* [n, N_samples]                 sample_from_lineseg           */
     float* z_fine;    /* [n, N_samples+N_importance]    isample_from_lineseg (sorted) */
@@ -667,6 +668,49 @@ int pg_stage_merged_composite_bwd(pg_handle* h, void* stream, int64_t n, int n_s
                                   const float* z_coarse, const float* z_fine, const float* raw, const float* noise0,
                                   const float* noise1, const int32_t* order, const float* d_rgb, const float* d_acc,
                                   const float* d_rgb0, const float* d_acc0, float* d_raw);
+
+/* ---- several posed people in one frame, in front of and behind each other (the reference has no counterpart: its
+ * frames hold one character).  A scene is one camera and 1 <= P <= PG_SCENE_MAX_PEOPLE people; person p is a subject of the bank,
+ * a pose (skts, cyl: device), a 2-D box and a frame-code index (HOST data; cam < 0: the mean code).
+ *   1. Person p is rendered over ITS OWN box exactly as pg_render_frame renders it -- the same rays, `chunk`-ray nanmean groups,
+ *      kernel forms and precision -- with its subject selected before the launches; the selection is the same before and after
+ *      the call.  Kept per ray: the depths z_p [S_f] and the raw_p [S_f,4] the person's final maps are composited from,
+ *      S_f = N_samples + N_importance (single_net: the merged raw).
+ *   2. Per sample, on the person's own list: delta_i = (z_{i+1} - z_i) |d|, the last 1e10 |d|; sigma = act(raw.w / density_scale);
+ *      alpha_i = 1 - exp(-sigma delta_i); c_i = sigmoid(raw.xyz) (1 + 2 rgb_eps) - rgb_eps (raw2outputs, nerf.py:150-205).
+ *   3. Per pixel the lists of the people whose clipped box holds it are merged by depth: (q,k) precedes (p,i) if z_qk < z_pi, or
+ *      z_qk == z_pi and (q,k) < (p,i).  In merged order T = prod_earlier (1 - alpha + 1e-10), w = alpha T, rgb_map = sum w c,
+ *      depth = sum w z, Wt = sum w, acc_map = min(Wt, 1), disp_map = 1 / max(1e-10, depth / (Wt + 1e-10)) (0 where |Wt| <= 1e-8),
+ *      person_acc[p] = min(sum_{i in p} w, 1): how much of person p is visible there.
+ *   4. A pixel inside no box has all-zero maps; the frame is composed as pg_render_frame composes it (rgb = rgb_map + (1 - acc) bg,
+ *      NaN disparity -> 0, optional uint8 frame).
+ * One person gives the one-person frame; people with disjoint boxes give each box its one-person frame.
+ *   person_acc device [P,H W] or NULL (0 outside a person's box); lists HOST array of 2 P device pointers or NULL (tests):
+ *   lists[2 p] receives z_p [n_p,S_f], lists[2 p + 1] raw_p [n_p,S_f,4], n_p = the pixels of the clipped box, row-major; either may
+ *   be NULL.  The other arguments are pg_render_frame's.
+ * Asynchronous on `stream`; no atomics: two calls give the same bytes.  The lists live in a grow-only buffer of the handle
+ * (20 B per sample).  PG_EINVAL with nothing launched: P outside [1, PG_SCENE_MAX_PEOPLE], a subject outside the bank,
+ * N_samples + N_importance > 256, a training tape outstanding, a handle on several devices. */
+#define PG_SCENE_MAX_PEOPLE 8
+typedef struct pg_scene_person {
+    int32_t subject;        /* in [0, pg_subject_count) */
+    int32_t box[4];         /* (tl_x, tl_y, br_x, br_y), clipped to the frame */
+    const float* skts;      /* device [24,4,4] */
+    const float* cyl;       /* device [5] */
+    float cam;              /* frame-code index (negative: the mean code) */
+} pg_scene_person;
+int pg_render_scene(pg_handle* h, void* stream, int H, int W, const float* c2w, const float* intrinsics, float near, float far,
+                    int n_people, const pg_scene_person* people, int n_samples, int n_importance, int flags, const float* bg,
+                    float base_bg, float* rgb, float* disp, float* acc, uint8_t* rgb8, float* person_acc, float* const* lists);
+
+/* Step 3 above on the caller's own buffers (tests/test_gpu_scene_stages.py): z / raw HOST arrays of P device pointers, list p of
+ * n_rows[p] (HOST) rows [.,S] / [.,S,4] (raw 16-byte aligned); rows device int32 [P,n_pix]: the row of pixel i in list p, anything
+ * outside [0, n_rows[p]) = person p does not cover it; dirs device [n_pix,3]: the pixels' ray directions.  rgb [n_pix,3], disp,
+ * acc [n_pix], person_acc [P,n_pix] or NULL.  The density line follows the handle's config; no loaded weights needed.  PG_EINVAL,
+ * nothing launched: a null pointer, P outside [1, PG_SCENE_MAX_PEOPLE], S outside [1, 256]. */
+int pg_stage_scene_composite(pg_handle* h, void* stream, int64_t n_pix, int n_people, int n_samples, const float* const* z,
+                             const float* const* raw, const int64_t* n_rows, const int32_t* rows, const float* dirs, float* rgb,
+                             float* disp, float* acc, float* person_acc);
 
 /* Test / measurement aid: on = 0 makes the fused 16-bit and compensated kernels compute every limb of the density input
  * for every point instead of leaving out the limbs a wave / a pass is out of cutoff range of (a joint farther than

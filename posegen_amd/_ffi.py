@@ -67,6 +67,14 @@ class PgImageBank(C.Structure):
                 ("n_cam", C.c_int64), ("H", C.c_int32), ("W", C.c_int32), ("mask_img", C.c_int32)]
 
 
+PG_SCENE_MAX_PEOPLE = 8
+
+
+class PgScenePerson(C.Structure):
+    """pg_scene_person: one person of a pg_render_scene call (skts, cyl: device pointers; the rest host data)."""
+    _fields_ = [("subject", C.c_int32), ("box", C.c_int32 * 4), ("skts", _FP), ("cyl", _FP), ("cam", C.c_float)]
+
+
 class PgOutputs(C.Structure):
     _fields_ = [(k, _FP) for k in ("rgb_map", "disp_map", "acc_map", "alpha", "rgb0", "disp0", "acc0",
                                    "alpha0", "near_far", "z_coarse", "z_fine", "raw_coarse", "raw_fine",
@@ -174,6 +182,11 @@ PROTOTYPES = {
                                        C.c_int32, C.POINTER(C.c_int32), C.c_int, C.c_void_p]),
     "pg_plan_frames": (C.c_int, [C.c_int, C.POINTER(C.c_int64), C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int,
                                  C.POINTER(C.c_int)]),
+    "pg_render_scene": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float,
+                                  C.c_float, C.c_int, C.POINTER(PgScenePerson), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "pg_stage_scene_composite": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_void_p),
+                                           C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_void_p, _FP, _FP, _FP, _FP, _FP]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -733,6 +733,7 @@ void pg_destroy(pg_handle* h) {
     pg_batch_release(h);
     pg_metrics_release(h);
     pg_frames_release(h);
+    pg_scene_release(h);
     for (auto& pr : h->ev_aux) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
     release_subject(*h);
     for (Subject& sub : h->bank.parked) release_subject(sub);
@@ -1429,16 +1430,21 @@ struct RayBufs {
     int* order;                     // sort permutation of the merged depths [n,S+N]
     float *zn, *rawn;               // single_net: the new points' depths [n,NP] and raw [n,NP,4]
     float* pn;                      // position noise [.,3] of the pass being evaluated
+    // A caller that takes the depths and the raw a pass works on (pg_outputs' z_coarse / raw_coarse / z_fine / raw_fine: tests, and
+    // pg_render_scene, whose lists they are) gets them written in place, if its array is aligned like the workspace's (256 B): it
+    // stands where the workspace's would.  Any other is filled by a copy at the end (copy_intermediates).
     int carve(pg_handle* h, const RayCall& r, int NP) {
         const size_t n = (size_t)r.n, S = r.S, SF = r.S + r.N;
         const bool hier = r.N > 0, single = NP > 0;
+        const pg_outputs* o = r.out;
+        auto in_place = [](float* p) { return p && reinterpret_cast<uintptr_t>(p) % 256 == 0; };
         return carve_ws(h, [&](Carver& c) {
             nf = c.take<float>(n * 2);
-            zc = c.take<float>(n * S);
-            rawc = c.take<float>(n * S * 4);
+            zc = in_place(o->z_coarse) ? o->z_coarse : c.take<float>(n * S);
+            rawc = in_place(o->raw_coarse) ? o->raw_coarse : c.take<float>(n * S * 4);
             w0 = c.take<float>(n * S);
-            zf = c.take<float>(n * SF, hier);
-            rawf = c.take<float>(n * SF * 4, hier && !single);
+            zf = hier && in_place(o->z_fine) ? o->z_fine : c.take<float>(n * SF, hier);
+            rawf = hier && !single && in_place(o->raw_fine) ? o->raw_fine : c.take<float>(n * SF * 4, hier && !single);
             order = c.take<int>(n * SF, single || (hier && r.rnoise()));
             zn = c.take<float>(n * NP, single);
             rawn = c.take<float>(n * NP * 4, single);
@@ -1476,10 +1482,11 @@ int copy_intermediates(pg_handle* h, void* stream, const RayCall& r, const RayBu
     const pg_outputs* out = r.out;
     const size_t Pc = (size_t)r.n * r.S, Pf = (size_t)r.n * (r.S + r.N);
     if (out->near_far) PG_HIP(h, hipMemcpyAsync(out->near_far, b.nf, (size_t)r.n * 8, hipMemcpyDeviceToDevice, s));
-    if (out->z_coarse) PG_HIP(h, hipMemcpyAsync(out->z_coarse, b.zc, Pc * 4, hipMemcpyDeviceToDevice, s));
-    if (out->raw_coarse) PG_HIP(h, hipMemcpyAsync(out->raw_coarse, b.rawc, Pc * 16, hipMemcpyDeviceToDevice, s));
-    if (r.N > 0 && out->z_fine) PG_HIP(h, hipMemcpyAsync(out->z_fine, b.zf, Pf * 4, hipMemcpyDeviceToDevice, s));
-    if (raw_fine && out->raw_fine) PG_HIP(h, hipMemcpyAsync(out->raw_fine, raw_fine, Pf * 16, hipMemcpyDeviceToDevice, s));
+    // (the depths and the raw were written in place, RayBufs::carve; single_net's merged raw is gathered into raw_fine by its composite)
+    if (out->z_coarse && out->z_coarse != b.zc) PG_HIP(h, hipMemcpyAsync(out->z_coarse, b.zc, Pc * 4, hipMemcpyDeviceToDevice, s));
+    if (out->raw_coarse && out->raw_coarse != b.rawc) PG_HIP(h, hipMemcpyAsync(out->raw_coarse, b.rawc, Pc * 16, hipMemcpyDeviceToDevice, s));
+    if (r.N > 0 && out->z_fine && out->z_fine != b.zf) PG_HIP(h, hipMemcpyAsync(out->z_fine, b.zf, Pf * 4, hipMemcpyDeviceToDevice, s));
+    if (raw_fine && out->raw_fine && out->raw_fine != raw_fine) PG_HIP(h, hipMemcpyAsync(out->raw_fine, raw_fine, Pf * 16, hipMemcpyDeviceToDevice, s));
     return PG_OK;
 }
 

@@ -7,15 +7,12 @@
 #include <cstring>
 #include <thread>
 
+#include "pg_frames.h"
 #include "pg_frames_plan.h"
 #include "pg_handle.h"
 #include "pg_launch.h"
 
-// ---- frame front / back end: helpers shared by pg_render_frame (one device) and pg_render_frames ----
-namespace {
-
-struct FrameMaps { float *rgb_map, *disp_map, *acc_map; };      // [n_box,3], [n_box], [n_box]: the whole box
-
+// ---- frame front / back end: helpers shared by pg_render_frame (one device), pg_render_frames and pg_render_scene (pg_frames.h) ----
 int frame_geom(pg_handle* h, int H, int W, const float* c2w, const float* intrinsics, const int* box, float near,
                float far, float cam, pgk::FrameGeom* g) {
     if (H <= 0 || W <= 0 || !c2w || !intrinsics || !box) return pg_fail(h, PG_EINVAL, "frame: null/non-positive argument");
@@ -31,6 +28,8 @@ int frame_geom(pg_handle* h, int H, int W, const float* c2w, const float* intrin
     g->near = near; g->far = far; g->cam = cam;
     return PG_OK;
 }
+
+namespace {
 
 // Frame workspace of `h`: ray_batch rows and cams of a range of n_range rays, the maps of a WHOLE box of
 // n rays (n = 0: none -- the range's maps live in a buffer of the caller), coarse-pass scratch of the range.
@@ -53,12 +52,11 @@ int frame_ws(pg_handle* h, int64_t n, int64_t n_range, float** rays, float** cam
     return PG_OK;
 }
 
-// rays [r0, r1) of the box (row-major ray list of kp_to_valid_rays).  r0 must be a multiple of the nanmean
-// group size (`chunk`) unless it is 0, so that the groups are those of the whole frame.  ext == nullptr:
-// the maps of the whole box are carved from the frame workspace and the range is written at its offset
-// (returned in *maps); otherwise the range's maps go to ext (rgb [r1-r0,3], disp, acc [r1-r0]).
+}  // namespace
+
 int frame_render_range(pg_handle* h, void* stream, const pgk::FrameGeom& g, int64_t r0, int64_t r1, const float* skts,
-                       const float* cyl, int n_samples, int n_importance, int flags, FrameMaps* maps, const FrameMaps* ext = nullptr) {
+                       const float* cyl, int n_samples, int n_importance, int flags, FrameMaps* maps, const FrameMaps* ext,
+                       const FrameLists* lists) {
     const int64_t n = (int64_t)g.bw * g.bh;
     if (r0 < 0 || r1 > n || r0 > r1) return pg_fail(h, PG_EINVAL, "frame range [%lld, %lld) outside the box of %lld rays", (long long)r0, (long long)r1, (long long)n);
     if (r0 % h->cfg.chunk != 0) return pg_fail(h, PG_EINVAL, "frame range must start on a nanmean group boundary (chunk %d)", h->cfg.chunk);
@@ -71,6 +69,8 @@ int frame_render_range(pg_handle* h, void* stream, const pgk::FrameGeom& g, int6
     if (r1 == r0) return PG_OK;
     if (ext) { out.rgb_map = ext->rgb_map; out.disp_map = ext->disp_map; out.acc_map = ext->acc_map; }
     else { out.rgb_map = own.rgb_map + r0 * 3; out.disp_map = own.disp_map + r0; out.acc_map = own.acc_map + r0; }
+    if (lists && n_importance > 0) { out.z_fine = lists->z; out.raw_fine = lists->raw; }
+    else if (lists) { out.z_coarse = lists->z; out.raw_coarse = lists->raw; }
     const bool fc = h->cfg.framecode_ch > 0;
     PG_TRY_LAUNCH(h, "frame ray kernel", pg_launch_frame_rays(&g, r0, r1 - r0, rays, fc ? cams : nullptr, stream));
     return pg_render_rays(h, stream, r1 - r0, rays, skts, 0, cyl, 0, fc ? cams : nullptr, n_samples, n_importance, flags, &out);
@@ -81,6 +81,8 @@ int frame_compose(pg_handle* h, void* stream, const pgk::FrameGeom& g, const Fra
     PG_TRY_LAUNCH(h, "frame compose kernel", pg_launch_frame_compose(&g, maps.rgb_map, maps.disp_map, maps.acc_map, bg, base_bg, rgb, disp, acc, rgb8, stream));
     return PG_OK;
 }
+
+namespace {
 
 // ---- pg_render_frames: per-device resources kept on the handle between calls -----------------------------------
 constexpr int NBUF = 2;                 // frame buffers in rotation: frame k+1 composes while frame k copies out

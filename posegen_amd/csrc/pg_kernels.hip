@@ -8,6 +8,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "pg_frame_dir.h"
 #include "pg_launch.h"
 
 namespace pgk {
@@ -552,13 +553,8 @@ __global__ __launch_bounds__(256) void frame_rays_kernel(const FrameGeom g, long
     for (long long k = blockIdx.x * (long long)blockDim.x + threadIdx.x; k < n; k += (long long)gridDim.x * blockDim.x) {
         const long long i = i0 + k;
         const int r = g.tly + (int)(i / g.bw), c = g.tlx + (int)(i % g.bw);
-        const float dx = __fdiv_rn(__fsub_rn((float)c, g.cx), g.fx);
-        const float dy = -__fdiv_rn(__fsub_rn((float)r, g.cy), g.fy);
-        const float dz = -1.0f;
         float d[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-            d[k] = __fadd_rn(__fadd_rn(__fmul_rn(dx, g.R[3 * k]), __fmul_rn(dy, g.R[3 * k + 1])), __fmul_rn(dz, g.R[3 * k + 2]));
+        frame_ray_dir(g, r, c, d);
         const float inv = 1.0f / sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
         float* o = rays + k * 11;
         o[0] = g.t[0]; o[1] = g.t[1]; o[2] = g.t[2];

@@ -593,6 +593,11 @@ class HipRenderer:
             _ptr(rm), _ptr(dm), _ptr(am), _ptr(bgt), float(base_bg), _ptr(rgb), _ptr(disp), _ptr(acc), _ptr(rgb8)))
         return (rgb, disp, acc, rgb8) if want_uint8 else (rgb, disp, acc)
 
+    def render_scene(self, H: int, W: int, focal, c2w, people, **kw):
+        """Several people of the bank in ONE frame with mutual occlusion (pg_render_scene): posegen_amd.scene.render_scene."""
+        from .scene import render_scene
+        return render_scene(self, H, W, focal, c2w, people, **kw)
+
     @property
     def n_devices(self) -> int:
         return len(self.devices)
