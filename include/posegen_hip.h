@@ -715,7 +715,8 @@ int pg_stage_scene_composite(pg_handle* h, void* stream, int64_t n_pix, int n_pe
 /* Test / measurement aid: on = 0 makes the fused 16-bit and compensated kernels compute every limb of the density input
  * for every point instead of leaving out the limbs a wave / a pass is out of cutoff range of (a joint farther than
  * cutoff_dist + 24 / (tau log2 e) has a cutoff weight 1 - sigmoid(tau (v - c)) below 2^-24, cutoff_embedder.py:139-146:
- * DESIGN.md 2.1).  Default on.  The two settings agree to ~1e-7 per skipped product. */
+ * DESIGN.md 2.1; an embedder with tau <= 0 has no such radius: nothing is left out).  Default on.  The two settings agree to
+ * ~1e-7 per skipped product. */
 int pg_set_far_skip(pg_handle* h, int on);
 
 /* The fused 16x16x32 kernel (pg_eval16r.hip; bf16 / fp16 renders of rays with >= 64 samples) leaves the colour branch --

@@ -83,6 +83,9 @@ class OracleConfig:
     skips: Tuple[int, ...] = (4,)
     framecode_ch: int = 0        # 16 with opt_framecode (h36m)
     cutoff_dist: float = 0.5     # cutoff_mm(500) * ext_scale(0.001)
+    # the CutoffEmbedder.cutoff_dist Parameter[24] of embed_fn / embeddirs_fn when they are not uniform (None: cutoff_dist)
+    cutoff_v: Optional[Sequence[float]] = None
+    cutoff_d: Optional[Sequence[float]] = None
     tau_v: float = 20.0          # CutoffEmbedder.tau of embed_fn
     tau_d: float = 20.0          # CutoffEmbedder.tau of embeddirs_fn
     density_scale: float = 1.0
@@ -329,13 +332,15 @@ def coarse_z(near, far, n_samples: int, lindisp: bool = False, t_rand=None):
 # ----------------------------------------------------------------------------
 # a-8 .. a-10: bone-relative transform + cutoff positional embedding
 # ----------------------------------------------------------------------------
-def _cutoff_embed(x, dists, n_freq: int, tau: float, cutoff: float, per_joint: int):
+def _cutoff_embed(x, dists, n_freq: int, tau: float, cutoff, per_joint: int):
     """CutoffEmbedder with include_input & cutoff_inputs (cutoff_embedder.py:111-174).
 
     x [..., J*per_joint]; dists [..., J].  Output channel = row*(J*per_joint)+i
     with rows (x, sin 2^0 x, cos 2^0 x, ...), every row times
-    w = 1 - sigmoid(tau (dist - cutoff)) of the owning joint.
+    w = 1 - sigmoid(tau (dist - cutoff)) of the owning joint; cutoff a scalar or one value per joint [J].
     """
+    if torch.is_tensor(cutoff) and per_joint > 1:       # cutoff_embedder.py:143
+        cutoff = cutoff[:, None].expand(-1, per_joint).flatten()
     freqs = 2. ** torch.linspace(0., n_freq - 1, steps=n_freq)
     if per_joint > 1:
         dists = dists[..., None].expand(*dists.shape, per_joint).flatten(start_dim=-2)
@@ -361,8 +366,9 @@ def embed_points(pts, rays_d, skts, cfg: OracleConfig, cams=None):
     v = torch.norm(q, dim=-1, p=2)                                  # [n,s,J]
     r = F.normalize(q, dim=-1, p=2).flatten(start_dim=2)            # [n,s,3J]
     e = F.normalize(dl, dim=-1, p=2).flatten(start_dim=2).expand(n, s, -1)
-    xv = _cutoff_embed(v, v, cfg.multires, cfg.tau_v, cfg.cutoff_dist, 1)
-    xd = _cutoff_embed(e, v, cfg.multires_views, cfg.tau_d, cfg.cutoff_dist, 3)
+    cut = lambda c: cfg.cutoff_dist if c is None else torch.as_tensor(np.asarray(c)).to(pts.dtype)
+    xv = _cutoff_embed(v, v, cfg.multires, cfg.tau_v, cut(cfg.cutoff_v), 1)
+    xd = _cutoff_embed(e, v, cfg.multires_views, cfg.tau_d, cut(cfg.cutoff_d), 3)
     parts = [xv, r, xd]
     if cams is not None:
         parts.append(cams.view(-1, 1, 1).to(pts.dtype).expand(n, s, 1))

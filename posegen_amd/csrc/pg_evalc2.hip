@@ -364,7 +364,8 @@ __global__ __launch_bounds__(NTHR2, 2) void evalc2_kernel(const EvalArgs a) {
     if (tid < 48) cut[tid] = -a.cutoff[(tid < J ? 0 : J) + slot_joint_dev(tid < J ? tid : tid - J)] * (tid < J ? tlv : tld);
     else if (tid < 72) {
         const int jt = slot_joint_dev(tid - 48);
-        const float far = fmaxf(a.cutoff[jt] + 24.0f / tlv, a.cutoff[J + jt] + 24.0f / tld);
+        // (tau <= 0: the cutoff weight does not fall with distance, so no radius bounds it -- nothing is masked)
+        const float far = fmaxf(tlv > 0.0f ? a.cutoff[jt] + 24.0f / tlv : __builtin_inff(), tld > 0.0f ? a.cutoff[J + jt] + 24.0f / tld : __builtin_inff());
         cut[tid] = far * far;
     }
     for (int i = tid; i < (TT::SMALL_ALPHA + TT::SMALL_RGB) / 16; i += NTHR2)

@@ -658,6 +658,60 @@ def gen_train_grads_pose(out, name, cfg, *, n_rays, H, n_poses, seed_model=0, se
     print(f"[{name}] rays={n} poses={n_poses} loss={float(loss.detach()):.6f} max |dL/dskts| {float(np.abs(d['dskts']).max()):.3e}")
 
 
+def gen_eval_edges(out, name="eval_edges", seed_model=0, seed_pose=21, n_samples=33):
+    """The embed + MLP stage alone with NON-UNIFORM cutoffs: the reference's own embedders (encode_inputs) and both of its
+    networks (run_network) on rays aimed at joints, `cutoff_dist` drawn per joint in [0.3, 0.7] independently for embed_fn and
+    embeddirs_fn, tau_v != tau_d.  Arrays only: the inputs and raw of both nets (9 x 33 points)."""
+    import torch
+    from posegen_amd import synthetic as syn
+    from posegen_amd.config import surreal_config
+    cfg = surreal_config(n_samples=n_samples, n_importance=16)      # (N_importance > 0: the caster builds the fine net)
+    with tempfile.TemporaryDirectory() as wd:
+        caster, kw, (wc, wf, _, _) = _build_reference_caster(cfg, seed_model, wd)
+    rng = np.random.RandomState(2101)
+    cut_v = rng.uniform(0.3, 0.7, 24).astype(np.float32)
+    cut_d = rng.uniform(0.3, 0.7, 24).astype(np.float32)
+    tau_v, tau_d = 20.0, 79.6
+    with torch.no_grad():
+        caster.embed_fn.cutoff_dist.copy_(torch.tensor(cut_v))
+        caster.embeddirs_fn.cutoff_dist.copy_(torch.tensor(cut_d))
+    caster.embed_fn.tau = torch.tensor(tau_v)
+    caster.embeddirs_fn.tau = torch.tensor(tau_d)
+    bones, kps, skts = syn.make_pose(1, seed_pose)
+    c2ws, _ = syn.make_camera(1, 64, 64)
+    cam = c2ws[0, :3, 3].astype(np.float64)
+    joints = np.array([0, 3, 4, 7, 12, 15, 18, 20, 23])
+    aim = kps[0, joints].astype(np.float64) + rng.uniform(-0.08, 0.08, (len(joints), 3))
+    dist = np.linalg.norm(aim - cam, axis=-1, keepdims=True)
+    d_np = ((aim - cam) / dist * rng.uniform(0.8, 1.25, (len(joints), 1))).astype(np.float32)    # (rays are not unit length)
+    n = len(joints)
+    o = torch.tensor(np.repeat(cam[None].astype(np.float32), n, 0))
+    d = torch.tensor(d_np)
+    mid = torch.tensor((dist[:, 0] / np.linalg.norm(d_np.astype(np.float64), axis=-1)).astype(np.float32))[:, None]
+    z = mid + torch.linspace(-0.9, 0.9, n_samples)[None, :] * torch.tensor(rng.uniform(0.7, 1.0, (n, 1)).astype(np.float32))
+    pts = o[:, None, :] + d[:, None, :] * z[..., None]
+    kp_b = torch.tensor(kps).expand(n, -1, -1)
+    skt_b = torch.tensor(skts).expand(n, -1, -1, -1)
+    bones_b = torch.tensor(bones).expand(n, -1, -1)
+    pk = kw["preproc_kwargs"]
+    jc = caster.get_subject_joint_coords(None, pts.device)
+    raws = {}
+    with torch.no_grad():
+        for tag, net in (("coarse", caster.network), ("fine", caster.network_fine)):
+            enc = caster.encode_inputs(pts, [o[:, None, :], d[:, None, :]], kp_b, skt_b, bones_b, cam_idxs=None,
+                                       subject_idxs=None, joint_coords=jc, network=net, **pk)
+            raws[tag] = caster.run_network(enc, net).numpy()
+    vd = d / torch.norm(d, dim=-1, keepdim=True)
+    ones = torch.ones(n, 1)
+    batch = torch.cat([o, d, 0. * ones, 1. * ones, vd], -1)
+    np.savez_compressed(os.path.join(out, f"{name}.npz"), ray_batch=batch.numpy(), z=z.numpy(), skts=skts, kps=kps,
+                        cutoff_v=cut_v, cutoff_d=cut_d, tau_v=tau_v, tau_d=tau_d, seed_model=seed_model,
+                        n_samples=n_samples, n_importance=0, digest_coarse=_weights_digest(wc), digest_fine=_weights_digest(wf),
+                        raw_coarse=raws["coarse"].reshape(n, n_samples, 4), raw_fine=raws["fine"].reshape(n, n_samples, 4))
+    sig = raws["coarse"].reshape(-1, 4)[:, 3]
+    print(f"[{name}] {n} rays x {n_samples}: sigma_raw in [{sig.min():.2f}, {sig.max():.2f}], {(sig > 0).mean():.2f} of the points occupied")
+
+
 def gen_frame(out, name, cfg, H, chunk, seed_model=0, seed_pose=1, n_frames=2):
     """a-1/a-3: whole frames through the reference's render_path (bbox cull,
     chunk loop with a chunk boundary inside the frame, white background)."""
@@ -872,6 +926,9 @@ def main():
         gen_train_grads_pose(a.out, "train_grads_single_pose",
                              surreal_config(single_net=True, multires_views=0, n_samples=96, n_importance=48),
                              n_rays=48, H=128, n_poses=2, seed_pose=20, model_keys=True)
+    # per-joint cutoffs, different for the two embedders, tau_v != tau_d: embed + MLP of both nets (consumes no torch RNG state)
+    if want("eval_edges"):
+        gen_eval_edges(a.out)
     # frame scores: the vendored pytorch_msssim on cropped pairs (consumes no torch RNG state)
     if want("frame_metrics"):
         gen_frame_metrics(a.out)
