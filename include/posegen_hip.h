@@ -712,6 +712,39 @@ int pg_stage_scene_composite(pg_handle* h, void* stream, int64_t n_pix, int n_pe
                              const float* const* raw, const int64_t* n_rows, const int32_t* rows, const float* dirs, float* rgb,
                              float* disp, float* acc, float* person_acc);
 
+/* ---- 3-D poses scored against their ground truth on the device (posegen_amd/pose_eval.py) -----------------------
+ * What the reference computes per pose on the host: Criterion_MPJPE, Criterion3DPose_leastQuaresScaled and
+ * Criterion3DPose_ProcrustesCorrected over `procrustes` (core/utils/evaluation_helpers.py:387-522), compute_similarity_transform and
+ * reconstruction_error (run_gan.py:1380-1456), and the PCK / AUC shares of evaluate_pampjpe_from_smpl_params (:595-601).
+ *
+ * p, g: rows `joints` of pred, gt after row `root` of each was subtracted from it (root = -1: nothing subtracted).  All arithmetic
+ * is float64 on the float32 inputs.  Per pose:
+ *   raw     = mean_j |p_j - g_j|
+ *   Z       = p aligned to g by `align`:  NONE      Z = p
+ *                                          SCALE     Z = s p, s = <p,g> / <p,p> (no mean removed)
+ *                                          BEST      Z = normX (sum s) Y0 T + muX with X = g, Y = p, X0 Y0 the centred sets scaled to
+ *                                                    unit Frobenius norm, A = X0^T Y0 = U diag(s) V^T, T = V U^T (reflections allowed)
+ *                                          ROTATION  as BEST, but where det T < 0 the smallest singular direction and its singular
+ *                                                    value change sign: det T = +1
+ *   aligned = mean_j |Z_j - g_j|,  d = sum |Z_j - g_j|^2 / sum |g_j - mean g|^2,  scale = the factor applied to p (1 for NONE)
+ * per_pose [B,4] = raw, aligned, d, scale; aligned [B,J,3] = Z; joint_err [B,J] = |Z_j - g_j| (each may be NULL).
+ * summary [4 + 2 T] = B, mean raw, mean aligned, mean d, then for each of the T thresholds (HOST doubles, in the inputs' unit) the
+ * share of the B J joint distances STRICTLY below it: T shares of |p_j - g_j|, then T shares of |Z_j - g_j|.
+ * A pose whose p or g has no spread (J = 1, all joints equal) has NaN aligned, d and scale under BEST and ROTATION (0 / 0) and a
+ * valid raw; a pose with a non-finite coordinate among its selected joints or its root is NaN in every output, that pose only;
+ * the means propagate NaN; a NaN distance is below no threshold.
+ * Asynchronous on `stream`; no atomics, every sum in a fixed order: two calls give the same bytes, and a pose's own numbers do not
+ * depend on B or on its place in the batch.  The singular value decomposition runs a fixed number of Jacobi sweeps.
+ * PG_EINVAL, nothing launched and nothing written: pred, gt or summary NULL; B < 1; J outside [1, 64] (joints = NULL: J = J_in);
+ * a joint or root index outside J_in; an unknown mode; T outside [0, 64]. */
+#define PG_POSE_ALIGN_NONE     0  /* plain MPJPE */
+#define PG_POSE_ALIGN_SCALE    1  /* Criterion3DPose_leastQuaresScaled */
+#define PG_POSE_ALIGN_BEST     2  /* evaluation_helpers.procrustes, scaling=True, reflection='best' */
+#define PG_POSE_ALIGN_ROTATION 3  /* run_gan.compute_similarity_transform: det(R) = +1 */
+int pg_pose_scores(pg_handle* h, void* stream, int64_t B, int J_in, const float* pred, const float* gt, const int32_t* joints, int J,
+                   int root, int align, const double* thresholds, int T, double* per_pose, float* aligned, float* joint_err,
+                   double* summary);
+
 /* Test / measurement aid: on = 0 makes the fused 16-bit and compensated kernels compute every limb of the density input
  * for every point instead of leaving out the limbs a wave / a pass is out of cutoff range of (a joint farther than
  * cutoff_dist + 24 / (tau log2 e) has a cutoff weight 1 - sigmoid(tau (v - c)) below 2^-24, cutoff_embedder.py:139-146:

@@ -18,6 +18,7 @@ _POSEOPT_NAMES = ("HipPoseOptLayer",)
 _BATCH_NAMES = ("DeviceImageBank", "ImageBatchSampler", "RayBatchSource")
 _EVALUATE_NAMES = ("FrameScorer", "evaluate_frames", "evaluate_metric", "ValidationScorer", "evaluate_validation", "evaluate_testset",
                    "validation_scores")
+_POSE_EVAL_NAMES = ("PoseScorer", "pa_mpjpe", "n_mpjpe", "reconstruction_error", "refinement_scores")
 _SCENE_NAMES = ("ScenePerson", "render_scene", "render_scenes", "place_people")
 
 
@@ -35,6 +36,9 @@ def __getattr__(name):
     if name in _EVALUATE_NAMES:                # frame scores on the device (imports torch as well)
         from . import evaluate
         return getattr(evaluate, name)
+    if name in _POSE_EVAL_NAMES:               # pose scores on the device (imports torch as well)
+        from . import pose_eval
+        return getattr(pose_eval, name)
     if name in _SCENE_NAMES:                   # several people in one frame (imports torch as well)
         from . import scene
         return getattr(scene, name)

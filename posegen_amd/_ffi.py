@@ -22,6 +22,7 @@ PG_ACT_RELU, PG_ACT_SOFTPLUS = 0, 1
 PG_COMP_PLAIN, PG_COMP_IS_ONLY, PG_COMP_MERGED = 0, 1, 2
 PG_ABI_VERSION = 11
 PG_METRICS_BG = 1
+PG_POSE_ALIGN_NONE, PG_POSE_ALIGN_SCALE, PG_POSE_ALIGN_BEST, PG_POSE_ALIGN_ROTATION = 0, 1, 2, 3
 
 
 class HipLibraryError(RuntimeError):
@@ -180,6 +181,8 @@ PROTOTYPES = {
                                    C.c_void_p]),
     "pg_frame_metrics_val": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(PgImageBank), C.c_int32, C.POINTER(C.c_int32), _FP, C.c_int32,
                                        C.c_int32, C.POINTER(C.c_int32), C.c_int, C.c_void_p]),
+    "pg_pose_scores": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, _FP, _FP, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int,
+                                 C.POINTER(C.c_double), C.c_int, C.c_void_p, _FP, _FP, C.c_void_p]),
     "pg_plan_frames": (C.c_int, [C.c_int, C.POINTER(C.c_int64), C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int,
                                  C.POINTER(C.c_int)]),
     "pg_render_scene": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float,

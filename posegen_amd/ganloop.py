@@ -86,3 +86,15 @@ def render_for_regressor(caster, bones: torch.Tensor, rest_pose, c2w, H: int, W:
     std = torch.tensor(IMG_NORM_STD, device=dev).view(1, 3, 1, 1)
     img = resize_antialiased((img - mean) / std, (out_res, out_res))
     return (img, frames) if return_frames else img
+
+
+@torch.no_grad()
+def regressor_feedback(pred_kps: torch.Tensor, gt_kps: torch.Tensor, scorer=None) -> torch.Tensor:
+    """The number the loop feeds back from the regressor (run_gan.py:2085-2091): both [F,24,3] pose sets centred on joint 0, the
+    14 joints of run_gan.py:2087, `spin_loss = 1 - mpjpe(pose, pose_gt)` -- as a float64 device scalar from `pg_pose_scores`
+    (pose_eval.PoseScorer), with no synchronisation and no copy to the host.  `scorer`: a `PoseScorer` (e.g. of the caster's
+    renderer); None = the module's own on the key points' device."""
+    from . import pose_eval
+    sc = pose_eval._scorer_for(scorer, pred_kps, gt_kps)
+    out = sc.enqueue(pred_kps, gt_kps, joints=pose_eval.GAN_LOOP_JOINTS, root=0, align="none")
+    return 1.0 - out["summary"][1]

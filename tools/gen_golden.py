@@ -842,6 +842,92 @@ def gen_frame_metrics_val(out):
     print(f"[frame_metrics_val] {n} cases")
 
 
+def _reference_definitions(path, names):
+    """The top-level functions and classes `names` of the reference file `path`, compiled from its syntax tree into a namespace
+    that holds numpy and torch only: the file itself is never imported (run_gan.py parses argv and loads model files when it is)."""
+    import ast
+    import torch
+    with open(path) as f:
+        tree = ast.parse(f.read(), filename=path)
+    body = [n for n in tree.body if isinstance(n, (ast.FunctionDef, ast.ClassDef)) and n.name in names]
+    missing = set(names) - {n.name for n in body}
+    if missing:
+        sys.exit(f"gen_golden: {path} does not define {sorted(missing)}")
+    ns = {"np": np, "torch": torch}
+    exec(compile(ast.Module(body=body, type_ignores=[]), path, "exec"), ns)
+    return ns
+
+
+POSE_SCORE_SETS = {"j14": [1, 2, 4, 5, 7, 8, 12, 15, 16, 17, 18, 19, 20, 21], "j17": list(range(17)), "j24": list(range(24)),
+                   "mirror": [1, 2, 4, 5, 7, 8, 12, 15, 16, 17, 18, 19, 20, 21]}
+POSE_SCORE_MIN_RATIO = 1e-2
+
+
+def gen_pose_scores(out, ref_root):
+    """Pose scores (posegen_amd/pose_eval.py, pg_pose_scores): seeded body-like poses -- synthetic.make_pose key points in metres
+    (a 1.7 m body), a subset of the 24 joints as ground truth, the prediction = ground truth + 3 cm joint noise under a random
+    similarity transform (scale 0.7 .. 1.4, any rotation, a shift of up to 1 m) -- 32 poses each of 14, 17 and 24 joints, and 8
+    14-joint poses whose prediction is mirrored as well, so that the reference's own det < 0 branch runs.  A pose whose normalised
+    cross-covariance has s3 / s1 < 1e-2 (mirrored: or (s2 - s3) / s1 < 1e-2) is drawn again, so every stored pose is compared.
+    Stored: the float32 inputs and, on them, what the reference returns: `procrustes` (d, Z, scale) as
+    Criterion3DPose_ProcrustesCorrected calls it and that criterion's distances, Criterion_MPJPE, Criterion3DPose_leastQuaresScaled
+    (evaluation_helpers.py:387-522), compute_similarity_transform and reconstruction_error(reduction=None) (run_gan.py:1380-1456).
+    Only arrays are stored."""
+    import torch
+    from posegen_amd import synthetic as syn
+    from tests import pose_scores_ref as ref
+    eh = _reference_definitions(os.path.join(ref_root, "core", "utils", "evaluation_helpers.py"),
+                                ["procrustes", "Criterion_MPJPE", "Criterion3DPose_ProcrustesCorrected", "Criterion3DPose_leastQuaresScaled"])
+    rg = _reference_definitions(os.path.join(ref_root, "run_gan.py"),
+                                ["compute_similarity_transform", "compute_similarity_transform_batch", "reconstruction_error"])
+    rng = np.random.RandomState(20240607)
+    _, kps, _ = syn.make_pose(256, seed=31, sigma=0.35)
+    kps = kps.astype(np.float64)
+    height = (kps[..., 1].max(1) - kps[..., 1].min(1)).mean()
+    kps *= 1.7 / max(height, 1e-9)                                  # metres
+    d, next_pose, redrawn = {}, 0, 0
+    for tag, joints in POSE_SCORE_SETS.items():
+        n = 8 if tag == "mirror" else 32
+        preds, gts = [], []
+        while len(preds) < n:
+            gt = kps[next_pose % len(kps)][joints] + rng.normal(0, 0.5, 3)
+            next_pose += 1
+            q, _ = np.linalg.qr(rng.normal(size=(3, 3)))
+            q *= np.sign(np.linalg.det(q))                          # a rotation
+            if tag == "mirror":
+                q = q @ np.diag([-1.0, 1.0, 1.0])
+            pred = rng.uniform(0.7, 1.4) * (gt + rng.normal(0, 0.03, gt.shape)) @ q.T + rng.uniform(-1, 1, 3)
+            pred, gt = pred.astype(np.float32), gt.astype(np.float32)
+            r3, gap = ref.conditioning(pred[None], gt[None])
+            if r3[0] < POSE_SCORE_MIN_RATIO or (tag == "mirror" and gap[0] < POSE_SCORE_MIN_RATIO):
+                redrawn += 1
+                continue
+            preds.append(pred)
+            gts.append(gt)
+        pred, gt = np.stack(preds), np.stack(gts)
+        tp, tg = torch.tensor(pred), torch.tensor(gt)
+        mpjpe = eh["Criterion_MPJPE"](reduction=None)
+        pa_dist, pa_kps = eh["Criterion3DPose_ProcrustesCorrected"](mpjpe)(tp, tg)
+        n_dist, n_kps = eh["Criterion3DPose_leastQuaresScaled"](mpjpe)(tp, tg)
+        proc = [eh["procrustes"](gt[i].copy(), pred[i].copy()) for i in range(n)]
+        assert all(np.array_equal(proc[i][1], pa_kps[i].numpy()) for i in range(n))
+        d[f"pred_{tag}"], d[f"gt_{tag}"] = pred, gt
+        d[f"mpjpe_dist_{tag}"] = mpjpe(tp, tg).numpy()
+        d[f"mpjpe_mean_{tag}"] = eh["Criterion_MPJPE"](reduction="mean")(tp, tg).numpy()
+        d[f"pa_dist_{tag}"], d[f"pa_kps_{tag}"] = pa_dist.numpy(), pa_kps.numpy()
+        d[f"pa_d_{tag}"] = np.asarray([p[0] for p in proc])
+        d[f"pa_scale_{tag}"] = np.asarray([p[2]["scale"] for p in proc])
+        d[f"pa_det_{tag}"] = np.asarray([np.linalg.det(p[2]["rotation"].astype(np.float64)) for p in proc])
+        d[f"n_dist_{tag}"], d[f"n_kps_{tag}"] = n_dist.numpy(), n_kps.numpy()
+        d[f"cst_kps_{tag}"] = np.stack([rg["compute_similarity_transform"](pred[i], gt[i]) for i in range(n)])
+        d[f"re_{tag}"] = np.asarray(rg["reconstruction_error"](pred, gt, reduction=None))
+        if tag == "mirror":
+            assert np.all(d[f"pa_det_{tag}"] < 0), "the mirrored poses did not take the reference's reflection branch"
+    path = os.path.join(out, "pose_scores.npz")
+    np.savez_compressed(path, **d)
+    print(f"[pose_scores] {sum(len(d[f'pred_{t}']) for t in POSE_SCORE_SETS)} poses, {redrawn} drawn again, {os.path.getsize(path)} bytes")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ref", default="/root/reference")
@@ -935,6 +1021,9 @@ def main():
     # validation scores: the same frames at H // rf x W // rf, torch's float32 upsampling (reads frame_metrics.npz; no RNG state)
     if want("frame_metrics_val"):
         gen_frame_metrics_val(a.out)
+    # pose scores: the reference's Procrustes / MPJPE functions on seeded poses (consumes no torch RNG state)
+    if want("pose_scores"):
+        gen_pose_scores(a.out, a.ref)
 
 
 if __name__ == "__main__":
