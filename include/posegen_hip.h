@@ -745,6 +745,56 @@ int pg_pose_scores(pg_handle* h, void* stream, int64_t B, int J_in, const float*
                    int root, int align, const double* thresholds, int T, double* per_pose, float* aligned, float* joint_err,
                    double* summary);
 
+/* ---- the SMPL body on the device (posegen_amd/smpl.py) -------------------------------------------------------------
+ * The model as the library reads it: device arrays built once per model by the caller (posegen_amd.smpl.BodyModel).  blend and skin
+ * hold the model's float32 values unchanged; rest_joints is J_regressor applied to each of the first 1 + NB blend rows in float64
+ * (the rest joints are linear in beta: J = rest_joints[0] + sum_l beta_l rest_joints[1 + l], exactly). */
+typedef struct pg_body_model {
+    int32_t V, NB;              /* vertices >= 1; shape coefficients, 1..16 */
+    const float*  blend;        /* [1+NB+207, 3V]: row 0 v_template, rows 1..NB shapedirs[:,:,l] flattened (v,xyz), then the 207 rows of posedirs as stored */
+    const float*  skin;         /* [V,24] lbs_weights, treated as DENSE */
+    const double* rest_joints;  /* [1+NB,24,3] */
+    int32_t parents[24];        /* parents[0] = -1, parent < child */
+} pg_body_model;
+
+/* smplx.lbs.lbs(betas, pose, v_template, shapedirs, posedirs, J_regressor, parents, lbs_weights, pose2rot = !pose_is_rotmat)
+ * (smplx/smplx/lbs.py:152-248) followed by vertices2joints(regress, verts) (:251-268): what SMPL.forward and
+ * `J_regressor @ vertices` compute in evaluate.test (run_gan.py:1584-1634) and SMPLEvalHelper + vertices2joints in
+ * evaluate_pampjpe_from_smpl_params (core/utils/evaluation_helpers.py:542-612).
+ *   betas     device [B,NB] (betas_stride = NB), or one row for every pose (betas_stride = 0)
+ *   pose      device [B,24,3] axis-angle, or [B,24,3,3] rotation matrices with pose_is_rotmat
+ *   regress   device [K,V], K in 0..64 (NULL with K = 0)
+ *   verts [B,V,3], joints [B,24,3] (J_transformed), regressed [B,K,3]: device float32, each may be NULL, not all three
+ * Axis-angle follows batch_rodrigues as written (:295-329): angle = |r + 1e-8|, rot_dir = r / angle, R = I + sin K + (1 - cos) K K.
+ * Rodrigues, the rest joints, the chain and the relative transforms A_j (batch_rigid_transform, :345-401) are float64 on the float32
+ * inputs and rounded once; blend (v_template + shapedirs beta + posedirs (R - I), one GEMM on v_mfma_f32_16x16x4_f32), skinning
+ * (T = sum_j skin[v,j] A_j, T [v_posed; 1]) and regression are float32 products; the regression adds 4 vertices in float32 and
+ * everything above that in float64.  Vertices and per-vertex transforms reach memory only where `verts` is given.
+ * Asynchronous on `stream`; no atomics, every sum in a fixed order: two calls give the same bytes, and a pose's outputs are the same
+ * bytes whatever B is and wherever the pose sits in the batch (the vertex range is cut by V alone).  A pose with a non-finite input
+ * is non-finite in its own outputs only.
+ * Workspace: the handle's grow-only buffer, at most 48 MiB plus the carving's alignment: a long batch is walked in slices of at most
+ * 4096 poses inside the call (fewer where K times the vertex chunks, at most 256, makes a pose's partial sums large).
+ * PG_EINVAL, nothing launched and nothing written: m, betas or pose NULL; all three outputs NULL; B < 1; NB outside [1, 16]; V < 1 or
+ * (1 + NB + 207) 3 V >= 2^31; a NULL model array; K outside [0, 64]; K > 0 with regress NULL; regressed with K = 0; betas_stride
+ * neither NB nor 0; parents not ordered parent before child from parents[0] = -1. */
+int pg_smpl_forward(pg_handle* h, void* stream, const pg_body_model* m, int64_t B, const float* betas, int64_t betas_stride,
+                    const float* pose, int pose_is_rotmat, const float* regress, int K, float* verts, float* joints, float* regressed);
+
+/* Mesh errors per pose: per_pose[b] = mean_v |a[b,v] - b[b,v]|, the `ume` / `pme` lines of evaluate.test (run_gan.py:1630-1631).
+ *   a, b device [B,V,3] float32; per_pose device [B] float64; summary device [2] float64 = B, the mean of per_pose (may be NULL)
+ * float64 arithmetic, ordered sums, no atomics; a non-finite coordinate makes its own pose NaN and the mean with it.
+ * PG_EINVAL: a, b or per_pose NULL; B < 1; V < 1. */
+int pg_vertex_errors(pg_handle* h, void* stream, int64_t B, int V, const float* a, const float* b, double* per_pose, double* summary);
+
+/* pg_pose_kinematics with the rotations given: get_smpl_l2ws_torch(pose, axis_to_matrix=False) (core/utils/skeleton_utils.py:379-463),
+ * which the GAN loop applies to the regressor's rotation matrices (run_gan.py:2080-2091).
+ *   rotmats   device [n_poses,24,3,3] float32
+ *   bone_offsets, parents, kps, skts, l2ws: as pg_pose_kinematics (HOST offsets and joint tree; device outputs, any may be NULL)
+ * float64 arithmetic on the float32 matrices; float32 outputs are rounded once. */
+int pg_pose_kinematics_rot(pg_handle* h, void* stream, int64_t n_poses, const float* rotmats, const double* bone_offsets,
+                           const int32_t* parents, float* kps, float* skts, double* l2ws);
+
 /* Test / measurement aid: on = 0 makes the fused 16-bit and compensated kernels compute every limb of the density input
  * for every point instead of leaving out the limbs a wave / a pass is out of cutoff range of (a joint farther than
  * cutoff_dist + 24 / (tau log2 e) has a cutoff weight 1 - sigmoid(tau (v - c)) below 2^-24, cutoff_embedder.py:139-146:

@@ -18,7 +18,9 @@ _POSEOPT_NAMES = ("HipPoseOptLayer",)
 _BATCH_NAMES = ("DeviceImageBank", "ImageBatchSampler", "RayBatchSource")
 _EVALUATE_NAMES = ("FrameScorer", "evaluate_frames", "evaluate_metric", "ValidationScorer", "evaluate_validation", "evaluate_testset",
                    "validation_scores")
-_POSE_EVAL_NAMES = ("PoseScorer", "pa_mpjpe", "n_mpjpe", "reconstruction_error", "refinement_scores")
+_POSE_EVAL_NAMES = ("PoseScorer", "pa_mpjpe", "n_mpjpe", "reconstruction_error", "refinement_scores", "evaluate_smpl_predictions",
+                    "pampjpe_from_smpl_params")
+_SMPL_NAMES = ("BodyModel", "vertex_errors")
 _SCENE_NAMES = ("ScenePerson", "render_scene", "render_scenes", "place_people")
 
 
@@ -39,7 +41,10 @@ def __getattr__(name):
     if name in _POSE_EVAL_NAMES:               # pose scores on the device (imports torch as well)
         from . import pose_eval
         return getattr(pose_eval, name)
-    if name in _SCENE_NAMES:                   # several people in one frame (imports torch as well)
+    if name in _SMPL_NAMES:                    # the SMPL body on the device (imports torch as well)
+        from . import smpl
+        return getattr(smpl, name)
+    if name in _SCENE_NAMES:                  # several people in one frame (imports torch as well)
         from . import scene
         return getattr(scene, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

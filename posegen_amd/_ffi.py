@@ -76,6 +76,12 @@ class PgScenePerson(C.Structure):
     _fields_ = [("subject", C.c_int32), ("box", C.c_int32 * 4), ("skts", _FP), ("cyl", _FP), ("cam", C.c_float)]
 
 
+class PgBodyModel(C.Structure):
+    """pg_body_model: the device arrays of one SMPL body (blend, skin, rest_joints) and its joint tree."""
+    _fields_ = [("V", C.c_int32), ("NB", C.c_int32), ("blend", _FP), ("skin", _FP), ("rest_joints", C.c_void_p),
+                ("parents", C.c_int32 * 24)]
+
+
 class PgOutputs(C.Structure):
     _fields_ = [(k, _FP) for k in ("rgb_map", "disp_map", "acc_map", "alpha", "rgb0", "disp0", "acc0",
                                    "alpha0", "near_far", "z_coarse", "z_fine", "raw_coarse", "raw_fine",
@@ -183,6 +189,11 @@ PROTOTYPES = {
                                        C.c_int32, C.POINTER(C.c_int32), C.c_int, C.c_void_p]),
     "pg_pose_scores": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, _FP, _FP, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int,
                                  C.POINTER(C.c_double), C.c_int, C.c_void_p, _FP, _FP, C.c_void_p]),
+    "pg_smpl_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(PgBodyModel), C.c_int64, _FP, C.c_int64, _FP, C.c_int, _FP, C.c_int,
+                                  _FP, _FP, _FP]),
+    "pg_vertex_errors": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, _FP, _FP, C.c_void_p, C.c_void_p]),
+    "pg_pose_kinematics_rot": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _FP, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_void_p,
+                                         C.c_void_p, C.c_void_p]),
     "pg_plan_frames": (C.c_int, [C.c_int, C.POINTER(C.c_int64), C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int,
                                  C.POINTER(C.c_int)]),
     "pg_render_scene": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float,

@@ -1,0 +1,573 @@
+// pg_smpl.hip -- the SMPL body on the device: smplx.lbs.lbs (smplx/smplx/lbs.py:152-248) with the joint regressors
+// applied to its vertices (vertices2joints, :251-268), the mesh errors of run_gan.py:1630-1631 and the rotation-matrix form of the
+// kinematic chain (get_smpl_l2ws_torch(axis_to_matrix=False), core/utils/skeleton_utils.py:379-463).
+//   smpl_pre_kernel    : one wave per pose, lane j owns joint j.  Rodrigues as batch_rodrigues writes it (or the matrix as given), the
+//                        rest joints from rest_joints and beta, the chain and the relative transforms A_j in float64; the pose's
+//                        feature row f = [1, beta, (R_j - I), 0 ..] and A go to the workspace as float32, rounded once.
+//   smpl_body_kernel   : a workgroup owns 32 poses and walks 64-vertex tiles.  Blend is a GEMM on v_mfma_f32_16x16x4_f32: A = the
+//                        poses' feature rows (LDS), B = 192 columns of `blend` (each wave 48, read once per 32 poses), the result
+//                        goes through LDS to the skinning lanes: T = sum_j skin[v,j] A_j is a second MFMA over the 24 joints (rows:
+//                        4 poses x one row of T, columns: the wave's 16 vertices), so a lane receives a row of T for its (pose,
+//                        vertex) and applies it.  The vertex goes to `verts` (if asked) and back into LDS, where the regressors
+//                        meet it in a third MFMA (A = regress rows, B = 64 vertices x 96 (pose, xyz) columns).  One MFMA adds 4
+//                        vertices in float32; everything above that is added in double, in tile order, per vertex chunk.
+//   smpl_regress_sum   : the chunks' doubles added in chunk order, rounded to float32 once.
+//   vertex_err_kernel, vertex_err_mean, kin_rot_kernel: one wave per pose, float64.
+// The vertex range is cut into 64-vertex tiles and min(tiles, 256) chunks (chunk c owns tiles c, c + chunks, ..): a function of V
+// only.  A pose is a row of the first two MFMAs and three columns of the third, so its bytes do not depend on the batch around it.
+// No atomics, no loop that depends on a value of the data.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "pg_handle.h"
+
+namespace pgsm {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int THREADS = 256;
+constexpr int WAVES = THREADS / 64;
+constexpr int NJ = 24;
+constexpr int POSE_ROWS = 207;               // 23 joints x 9
+constexpr int MAX_NB = 16, MAX_K = 64;
+constexpr int PT = 32;                       // poses per workgroup: two MFMA row tiles
+constexpr int VT = 64;                       // vertices per tile: each wave 16 vertices = 48 columns = three MFMA column tiles
+constexpr int KP_MAX = 224;                  // 1 + 16 + 207
+constexpr int LDF = KP_MAX + 4;              // row stride of the feature tile: lanes (l & 15, l >> 4) fall on 64 different banks
+constexpr int LDV = 3 * VT + 4;              // row stride of the vertex tile
+constexpr int MAX_CHUNKS = 256;
+constexpr size_t WS_TARGET = (size_t)48 << 20;
+
+__device__ __forceinline__ double wave_all_sum(double v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+    return v;
+}
+
+// The lane's joint-to-parent transform G (rows of a 3 x 4) becomes joint-to-world: every lane leaves its own in the wave's LDS
+// rows, then walks up its ancestors, `depth` steps for every lane (a lane that has reached the root keeps what it has).
+__device__ __forceinline__ void chain_to_world(double (*srel)[12], const int* spar, int j, bool jl, int depth, double G[12]) {
+    if (jl) {
+#pragma unroll
+        for (int e = 0; e < 12; ++e) srel[j][e] = G[e];
+    }
+    __syncthreads();
+    int p = spar[j];
+    for (int s = 0; s < depth; ++s) {
+        if (p >= 0) {
+            double P[12], N[12];
+#pragma unroll
+            for (int e = 0; e < 12; ++e) P[e] = srel[p][e];
+#pragma unroll
+            for (int r = 0; r < 3; ++r)
+#pragma unroll
+                for (int c = 0; c < 4; ++c)
+                    N[4 * r + c] = P[4 * r] * G[c] + P[4 * r + 1] * G[4 + c] + P[4 * r + 2] * G[8 + c] + (c == 3 ? P[4 * r + 3] : 0.0);
+#pragma unroll
+            for (int e = 0; e < 12; ++e) G[e] = N[e];
+            p = spar[p];
+        }
+    }
+}
+
+struct PreArgs {
+    const float* betas;
+    long long betas_stride;
+    const float* pose;
+    const double* rest;          // [1 + NB, 24, 3]
+    float* feat;                 // [n, KP] or null
+    float* A;                    // [n, 24, 12] or null
+    float* joints;               // [n, 24, 3] or null
+    long long n;
+    int is_rotmat, NB, K, KP, depth;
+    int parent[NJ];
+};
+
+__global__ __launch_bounds__(THREADS) void smpl_pre_kernel(PreArgs a) {
+    __shared__ double srel[WAVES][NJ][12];
+    __shared__ int spar[NJ];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (threadIdx.x < NJ) spar[threadIdx.x] = a.parent[threadIdx.x];
+    long long pose = (long long)blockIdx.x * WAVES + w;
+    const bool live = pose < a.n;                       // the whole wave
+    if (!live) pose = a.n - 1;                          // computes a pose again and writes nothing
+    const bool jl = lane < NJ;
+    const int j = jl ? lane : 0;
+    const int par = a.parent[j];
+    const float* bp = a.betas + pose * a.betas_stride;
+
+    // the rest joint of the lane and of its parent: linear in beta
+    double Jr[3], Jp[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        Jr[c] = a.rest[j * 3 + c];
+        Jp[c] = par >= 0 ? a.rest[par * 3 + c] : 0.0;
+    }
+    for (int l = 0; l < a.NB; ++l) {
+        const double b = (double)bp[l];
+        const double* rl = a.rest + (size_t)(1 + l) * NJ * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            Jr[c] += b * rl[j * 3 + c];
+            if (par >= 0) Jp[c] += b * rl[par * 3 + c];
+        }
+    }
+
+    double R[9];
+    if (a.is_rotmat) {
+        const float* rp = a.pose + ((size_t)pose * NJ + j) * 9;
+#pragma unroll
+        for (int e = 0; e < 9; ++e) R[e] = (double)rp[e];
+    } else {
+        // batch_rodrigues (lbs.py:295-329) as written: angle = |r + 1e-8|, rot_dir = r / angle, R = I + sin K + (1 - cos) K K
+        const float* rp = a.pose + ((size_t)pose * NJ + j) * 3;
+        const double r0 = (double)rp[0], r1 = (double)rp[1], r2 = (double)rp[2];
+        const double e0 = r0 + 1e-8, e1 = r1 + 1e-8, e2 = r2 + 1e-8;
+        const double angle = sqrt(e0 * e0 + e1 * e1 + e2 * e2);
+        const double x = r0 / angle, y = r1 / angle, z = r2 / angle;
+        const double sn = sin(angle), oc = 1.0 - cos(angle);
+        const double Km[9] = {0.0, -z, y, z, 0.0, -x, -y, x, 0.0};
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const double kk = Km[3 * r] * Km[c] + Km[3 * r + 1] * Km[3 + c] + Km[3 * r + 2] * Km[6 + c];
+                R[3 * r + c] = (r == c ? 1.0 : 0.0) + sn * Km[3 * r + c] + oc * kk;
+            }
+    }
+
+    // the feature row of the blend GEMM
+    if (a.feat && live) {
+        float* f = a.feat + (size_t)pose * a.KP;
+        if (jl && j >= 1) {
+#pragma unroll
+            for (int e = 0; e < 9; ++e) f[1 + a.NB + (j - 1) * 9 + e] = (float)(R[e] - ((e & 3) == 0 ? 1.0 : 0.0));
+        }
+        if (lane == 0) f[0] = 1.f;
+        if (lane >= 24 && lane < 24 + a.NB) f[1 + lane - 24] = bp[lane - 24];
+        if (lane >= 48 && a.K + (lane - 48) < a.KP) f[a.K + (lane - 48)] = 0.f;
+    }
+
+    double G[12];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) G[4 * r + c] = R[3 * r + c];
+        G[4 * r + 3] = Jr[r] - Jp[r];
+    }
+    chain_to_world(srel[w], spar, j, jl, a.depth, G);
+
+    if (live && jl) {
+        if (a.joints) {
+            float* o = a.joints + ((size_t)pose * NJ + j) * 3;
+            o[0] = (float)G[3]; o[1] = (float)G[7]; o[2] = (float)G[11];
+        }
+        if (a.A) {
+            // rel_transforms = transforms - pad(transforms @ [J; 0]) (lbs.py:396-399): [G_R | G_t - G_R J]
+            float* o = a.A + ((size_t)pose * NJ + j) * 12;
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) o[4 * r + c] = (float)G[4 * r + c];
+                o[4 * r + 3] = (float)(G[4 * r + 3] - (G[4 * r] * Jr[0] + G[4 * r + 1] * Jr[1] + G[4 * r + 2] * Jr[2]));
+            }
+        }
+    }
+}
+
+struct BodyArgs {
+    const float* blend;          // [K, 3V]
+    const float* skin;           // [V, 24]
+    const float* regress;        // [KR, V]
+    const float* feat;           // [n, KP]
+    const float* A;              // [n, 24, 12]
+    float* verts;                // [n, V, 3] or null
+    double* part;                // [chunks, n, KR, 3]
+    long long n;
+    int V, K, KP, KR, chunks, tiles;
+};
+
+__global__ __launch_bounds__(THREADS) void smpl_body_kernel(BodyArgs a) {
+    __shared__ float sf[PT * LDF];
+    __shared__ float sv[PT * LDV];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l15 = lane & 15, l4 = lane >> 4;
+    const long long pose0 = (long long)blockIdx.y * PT;
+    const int V = a.V, KP = a.KP;
+    const size_t ncol = (size_t)3 * V;
+
+    // the feature rows: eight loads in flight per thread (a load per trip would pay the memory latency every trip)
+    for (int i0 = tid; i0 < PT * KP; i0 += THREADS * 8) {
+        float fv[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int i = i0 + u * THREADS, row = i / KP;
+            fv[u] = (i < PT * KP && pose0 + row < a.n) ? a.feat[(size_t)pose0 * KP + i] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int i = i0 + u * THREADS, row = i / KP;
+            if (i < PT * KP) sf[row * LDF + (i - row * KP)] = fv[u];
+        }
+    }
+    __syncthreads();
+
+    const int MT = (a.KR + 15) >> 4, P = 6 * MT;         // regressor row tiles; (row tile, column tile) products of the workgroup
+    double racc[6][4];
+#pragma unroll
+    for (int q = 0; q < 6; ++q)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) racc[q][r] = 0.0;
+
+    for (int tile = blockIdx.x; tile < a.tiles; tile += a.chunks) {
+        const int v0 = tile * VT;
+        // ---- blend: v_posed[32 poses, the wave's 48 columns] ----
+        f32x4 acc[2][3];
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+            for (int t = 0; t < 3; ++t) acc[m][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+        const size_t c0 = (size_t)3 * v0 + w * 48 + l15;
+        // eight k steps at a time: their 24 B fragments are loaded together, then the 48 MFMAs run (rows past K, and features past
+        // KP, are zero: the steps a short last group adds change nothing)
+        for (int k0 = 0; k0 < KP; k0 += 32) {
+            float b[8][3];
+#pragma unroll
+            for (int s = 0; s < 8; ++s) {
+                const int kk = k0 + 4 * s + l4;
+#pragma unroll
+                for (int t = 0; t < 3; ++t) {
+                    const size_t col = c0 + t * 16;
+                    b[s][t] = (kk < a.K && col < ncol) ? a.blend[(size_t)kk * ncol + col] : 0.f;
+                }
+            }
+#pragma unroll
+            for (int s = 0; s < 8; ++s) {
+                const int kk = k0 + 4 * s + l4;
+                const float a0 = kk < KP ? sf[l15 * LDF + kk] : 0.f, a1 = kk < KP ? sf[(16 + l15) * LDF + kk] : 0.f;
+#pragma unroll
+                for (int t = 0; t < 3; ++t) {
+                    acc[0][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b[s][t], acc[0][t], 0, 0, 0);
+                    acc[1][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b[s][t], acc[1][t], 0, 0, 0);
+                }
+            }
+        }
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+            for (int t = 0; t < 3; ++t)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) sv[(m * 16 + l4 * 4 + r) * LDV + w * 48 + t * 16 + l15] = acc[m][t][r];
+        __syncthreads();
+
+        // ---- skinning: T = sum_j skin[v,j] A_j as an MFMA over the 24 joints.  Rows: 4 poses x the 4 entries of row c of T;
+        //      columns: the wave's own 16 vertices.  A lane receives row c of T for its (pose, vertex), three times: T [v; 1] ----
+        const int v = v0 + w * 16 + l15;
+        const bool vlive = v < V;
+        float sk[NJ / 4];
+#pragma unroll
+        for (int ks = 0; ks < NJ / 4; ++ks) sk[ks] = vlive ? a.skin[(size_t)v * NJ + 4 * ks + l4] : 0.f;
+        for (int pb = 0; pb < PT / 4; ++pb) {
+            const long long apose = pose0 + 4 * pb + (l15 >> 2);         // the pose of the lane's A row; its entry: l15 & 3
+            const bool alive = apose < a.n;
+            const float* Ar = a.A + (size_t)(alive ? apose : 0) * (NJ * 12) + 12 * l4 + (l15 & 3);     // + 48 ks + 4 c
+            const int row = 4 * pb + l4;                                 // the pose of the lane's results
+            const long long pose = pose0 + row;
+            float* pv = sv + row * LDV + 3 * (w * 16 + l15);
+            const float x = pv[0], y = pv[1], z = pv[2];
+            float o[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                f32x4 T = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int ks = 0; ks < NJ / 4; ++ks)
+                    T = __builtin_amdgcn_mfma_f32_16x16x4f32(alive ? Ar[48 * ks + 4 * c] : 0.f, sk[ks], T, 0, 0, 0);
+                o[c] = vlive ? fmaf(T[0], x, fmaf(T[1], y, fmaf(T[2], z, T[3]))) : 0.f;
+            }
+            if (a.verts && vlive && pose < a.n) {
+                float* ov = a.verts + ((size_t)pose * V + v) * 3;
+                ov[0] = o[0]; ov[1] = o[1]; ov[2] = o[2];
+            }
+            pv[0] = o[0]; pv[1] = o[1]; pv[2] = o[2];
+        }
+
+        // ---- regression: regress[KR, 64 vertices] x verts[64 vertices, 32 poses x 3] ----
+        if (a.KR > 0) {
+            __syncthreads();
+#pragma unroll
+            for (int q = 0; q < 6; ++q) {
+                const int p = w + WAVES * q;
+                if (p < P) {                             // the whole wave
+                    const int mt = p / 6, nt = p - mt * 6;
+                    const int krow = mt * 16 + l15, jj = nt * 16 + l15;
+                    const int jb = jj / 3, jc = jj - jb * 3;
+                    const bool klive = krow < a.KR;
+                    const float* rrow = a.regress + (size_t)(klive ? krow : 0) * V;
+                    float ra[VT / 4];                    // the product's 16 regressor fragments, loaded together
+#pragma unroll
+                    for (int s = 0; s < VT / 4; ++s) ra[s] = (klive && v0 + 4 * s + l4 < V) ? rrow[v0 + 4 * s + l4] : 0.f;
+#pragma unroll
+                    for (int s4 = 0; s4 < VT / 4; ++s4) {
+                        const int kk = 4 * s4 + l4;
+                        const float rb = sv[jb * LDV + 3 * kk + jc];
+                        const f32x4 d = __builtin_amdgcn_mfma_f32_16x16x4f32(ra[s4], rb, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) racc[q][r] += (double)d[r];
+                    }
+                }
+            }
+        }
+        __syncthreads();
+    }
+
+    if (a.KR > 0) {
+#pragma unroll
+        for (int q = 0; q < 6; ++q) {
+            const int p = w + WAVES * q;
+            if (p < P) {
+                const int mt = p / 6, nt = p - mt * 6;
+                const int jj = nt * 16 + l15;
+                const int jb = jj / 3, jc = jj - jb * 3;
+                const long long pose = pose0 + jb;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int k = mt * 16 + l4 * 4 + r;
+                    if (k < a.KR && pose < a.n) a.part[(((size_t)blockIdx.x * a.n + pose) * a.KR + k) * 3 + jc] = racc[q][r];
+                }
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(THREADS) void smpl_regress_sum(const double* __restrict__ part, long long per_chunk, int chunks,
+                                                            float* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * THREADS + threadIdx.x;
+    if (i >= per_chunk) return;
+    double s = 0.0;
+    for (int c = 0; c < chunks; ++c) s += part[(size_t)c * per_chunk + i];
+    out[i] = (float)s;
+}
+
+// per_pose[b] = mean_v |a_v - b_v| (run_gan.py:1630-1631): lane l adds vertices l, l + 64, .. in that order, then the butterfly
+__global__ __launch_bounds__(THREADS) void vertex_err_kernel(const float* __restrict__ a, const float* __restrict__ b, long long B, int V,
+                                                             double* __restrict__ per_pose) {
+    const int lane = threadIdx.x & 63;
+    const long long pose = (long long)blockIdx.x * WAVES + (threadIdx.x >> 6);
+    if (pose >= B) return;                               // the whole wave
+    const float* pa = a + (size_t)pose * V * 3;
+    const float* pb = b + (size_t)pose * V * 3;
+    double s = 0.0;
+    for (int v = lane; v < V; v += 64) {
+        const double dx = (double)pa[3 * (size_t)v] - (double)pb[3 * (size_t)v], dy = (double)pa[3 * (size_t)v + 1] - (double)pb[3 * (size_t)v + 1],
+                     dz = (double)pa[3 * (size_t)v + 2] - (double)pb[3 * (size_t)v + 2];
+        s += sqrt(dx * dx + dy * dy + dz * dz);
+    }
+    s = wave_all_sum(s);
+    if (lane == 0) per_pose[pose] = s / (double)V;
+}
+
+// summary = B, the mean of per_pose: thread t adds poses t, t + 256, .. in that order, the four waves' sums are added in wave order
+__global__ __launch_bounds__(THREADS) void vertex_err_mean(const double* __restrict__ per_pose, long long B, double* __restrict__ summary) {
+    __shared__ double sw[WAVES];
+    double s = 0.0;
+    for (long long i = threadIdx.x; i < B; i += THREADS) s += per_pose[i];
+    s = wave_all_sum(s);
+    if ((threadIdx.x & 63) == 0) sw[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        summary[0] = (double)B;
+        summary[1] = (((sw[0] + sw[1]) + sw[2]) + sw[3]) / (double)B;
+    }
+}
+
+struct KinConst { double offs[NJ * 3]; int parent[NJ]; int depth; };
+
+// get_smpl_l2ws_torch(axis_to_matrix=False): l2w_j = l2w_parent [R_j | rest_j - rest_parent], float64 on the float32 matrices
+__global__ __launch_bounds__(THREADS) void kin_rot_kernel(const KinConst kc, const float* __restrict__ rot, long long n, float* __restrict__ kps,
+                                                          float* __restrict__ skts, double* __restrict__ l2ws) {
+    __shared__ double srel[WAVES][NJ][12];
+    __shared__ int spar[NJ];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (threadIdx.x < NJ) spar[threadIdx.x] = kc.parent[threadIdx.x];
+    long long pose = (long long)blockIdx.x * WAVES + w;
+    const bool live = pose < n;
+    if (!live) pose = n - 1;
+    const bool jl = lane < NJ;
+    const int j = jl ? lane : 0;
+    const float* rp = rot + ((size_t)pose * NJ + j) * 9;
+    double G[12];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) G[4 * r + c] = (double)rp[3 * r + c];
+        G[4 * r + 3] = kc.offs[3 * j + r];
+    }
+    chain_to_world(srel[w], spar, j, jl, kc.depth, G);
+    if (!live || !jl) return;
+    const size_t at = (size_t)pose * NJ + j;
+    if (kps) { kps[at * 3] = (float)G[3]; kps[at * 3 + 1] = (float)G[7]; kps[at * 3 + 2] = (float)G[11]; }
+    if (l2ws) {
+        double* o = l2ws + at * 16;
+#pragma unroll
+        for (int e = 0; e < 12; ++e) o[e] = G[e];
+        o[12] = 0.0; o[13] = 0.0; o[14] = 0.0; o[15] = 1.0;
+    }
+    if (skts) {
+        float* o = skts + at * 16;
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            o[4 * r] = (float)G[r]; o[4 * r + 1] = (float)G[4 + r]; o[4 * r + 2] = (float)G[8 + r];
+            o[4 * r + 3] = (float)(-(G[r] * G[3] + G[4 + r] * G[7] + G[8 + r] * G[11]));
+        }
+        o[12] = 0.f; o[13] = 0.f; o[14] = 0.f; o[15] = 1.f;
+    }
+}
+
+}  // namespace pgsm
+
+// ---- the host side --------------------------------------------------------------------------------------------------------------------
+namespace {
+
+struct SmplState {
+    DevBuf ws;
+};
+
+// the deepest joint's distance from the root, or -1 for a tree that is not ordered parent before child
+int tree_depth(const int32_t* parents) {
+    if (parents[0] != -1) return -1;
+    int depth[pgsm::NJ] = {0}, deepest = 0;
+    for (int j = 1; j < pgsm::NJ; ++j) {
+        if (parents[j] < 0 || parents[j] >= j) return -1;
+        depth[j] = depth[parents[j]] + 1;
+        if (depth[j] > deepest) deepest = depth[j];
+    }
+    return deepest;
+}
+
+}  // namespace
+
+void pg_smpl_release(pg_handle* h) {
+    if (!h || !h->smpl) return;
+    auto* s = static_cast<SmplState*>(h->smpl);
+    pg_release(s->ws);
+    delete s;
+    h->smpl = nullptr;
+}
+
+extern "C" int pg_smpl_forward(pg_handle* h, void* stream, const pg_body_model* m, int64_t B, const float* betas, int64_t betas_stride,
+                               const float* pose, int pose_is_rotmat, const float* regress, int K, float* verts, float* joints,
+                               float* regressed) {
+    const char* who = "pg_smpl_forward";
+    if (!h) return pg_fail(nullptr, PG_EINVAL, "null handle");
+    if (!m || !betas || !pose) return pg_fail(h, PG_EINVAL, "%s: model, betas and pose are required", who);
+    if (!verts && !joints && !regressed) return pg_fail(h, PG_EINVAL, "%s: no output asked for", who);
+    if (B < 1) return pg_fail(h, PG_EINVAL, "%s: B = %lld", who, (long long)B);
+    if (m->NB < 1 || m->NB > pgsm::MAX_NB) return pg_fail(h, PG_EINVAL, "%s: NB = %d is outside [1, %d]", who, m->NB, pgsm::MAX_NB);
+    const int rows = 1 + m->NB + pgsm::POSE_ROWS;
+    if (m->V < 1 || (long long)rows * 3 * (long long)m->V >= (1ll << 31))
+        return pg_fail(h, PG_EINVAL, "%s: V = %d (at least 1, and %d blend rows of 3 V below 2^31 elements)", who, m->V, rows);
+    if (!m->blend || !m->skin || !m->rest_joints) return pg_fail(h, PG_EINVAL, "%s: the model has a NULL array", who);
+    if (K < 0 || K > pgsm::MAX_K) return pg_fail(h, PG_EINVAL, "%s: K = %d is outside [0, %d]", who, K, pgsm::MAX_K);
+    if (K > 0 && !regress) return pg_fail(h, PG_EINVAL, "%s: K = %d without regress", who, K);
+    if (regressed && K == 0) return pg_fail(h, PG_EINVAL, "%s: regressed asked for with K = 0", who);
+    if (betas_stride != 0 && betas_stride != m->NB)
+        return pg_fail(h, PG_EINVAL, "%s: betas_stride = %lld (NB = %d, or 0 for one row)", who, (long long)betas_stride, m->NB);
+    const int depth = tree_depth(m->parents);
+    if (depth < 0) return pg_fail(h, PG_EINVAL, "%s: parents[0] must be -1 and every joint must come after its parent", who);
+
+    const int V = m->V, KP = (rows + 3) & ~3;
+    const int KR = regressed ? K : 0;
+    const bool body = verts || regressed;
+    const int tiles = (V + pgsm::VT - 1) / pgsm::VT;
+    const int chunks = tiles < pgsm::MAX_CHUNKS ? tiles : pgsm::MAX_CHUNKS;
+    // the poses of one slice: what keeps the workspace at WS_TARGET, in whole pose tiles, at least one
+    const size_t per_pose = body ? ((size_t)KP + pgsm::NJ * 12) * sizeof(float) + (size_t)chunks * KR * 3 * sizeof(double) : 0;
+    long long S = body ? (long long)(pgsm::WS_TARGET / per_pose) / pgsm::PT * pgsm::PT : B;
+    if (S < pgsm::PT) S = pgsm::PT;
+    if (S > 4096 && body) S = 4096;
+    if (S > B) S = B;
+
+    PG_HIP(h, hipSetDevice(h->device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    float *d_feat = nullptr, *d_A = nullptr;
+    double* d_part = nullptr;
+    if (body) {
+        if (!h->smpl) h->smpl = new SmplState();
+        auto* s = static_cast<SmplState*>(h->smpl);
+        auto carve = [&](Carver& c) {
+            d_part = c.take<double>((size_t)chunks * S * KR * 3, KR > 0);
+            d_feat = c.take<float>((size_t)S * KP);
+            d_A = c.take<float>((size_t)S * pgsm::NJ * 12);
+        };
+        Carver count, real;
+        carve(count);
+        PG_TRY(pg_grow(h, s->ws, count.off, "body model workspace"));
+        real.base = s->ws.p;
+        carve(real);
+    }
+
+    for (long long b0 = 0; b0 < B; b0 += S) {
+        const long long n = B - b0 < S ? B - b0 : S;
+        pgsm::PreArgs pa{};
+        pa.betas = betas + b0 * betas_stride; pa.betas_stride = betas_stride;
+        pa.pose = pose + (size_t)b0 * pgsm::NJ * (pose_is_rotmat ? 9 : 3);
+        pa.rest = m->rest_joints; pa.feat = d_feat; pa.A = d_A;
+        pa.joints = joints ? joints + (size_t)b0 * pgsm::NJ * 3 : nullptr;
+        pa.n = n; pa.is_rotmat = pose_is_rotmat ? 1 : 0; pa.NB = m->NB; pa.K = rows; pa.KP = KP; pa.depth = depth;
+        for (int j = 0; j < pgsm::NJ; ++j) pa.parent[j] = m->parents[j];
+        hipLaunchKernelGGL(pgsm::smpl_pre_kernel, dim3((unsigned)((n + pgsm::WAVES - 1) / pgsm::WAVES)), dim3(pgsm::THREADS), 0, st, pa);
+        PG_LAUNCH_CHECK(h, "body model pose kernel");
+        if (!body) continue;
+        pgsm::BodyArgs ba{};
+        ba.blend = m->blend; ba.skin = m->skin; ba.regress = regress; ba.feat = d_feat; ba.A = d_A;
+        ba.verts = verts ? verts + (size_t)b0 * V * 3 : nullptr;
+        ba.part = d_part; ba.n = n; ba.V = V; ba.K = rows; ba.KP = KP; ba.KR = KR; ba.chunks = chunks; ba.tiles = tiles;
+        hipLaunchKernelGGL(pgsm::smpl_body_kernel, dim3((unsigned)chunks, (unsigned)((n + pgsm::PT - 1) / pgsm::PT)), dim3(pgsm::THREADS), 0, st,
+                           ba);
+        PG_LAUNCH_CHECK(h, "body model kernel");
+        if (KR > 0) {
+            const long long per_chunk = n * KR * 3;
+            hipLaunchKernelGGL(pgsm::smpl_regress_sum, dim3((unsigned)((per_chunk + pgsm::THREADS - 1) / pgsm::THREADS)), dim3(pgsm::THREADS), 0,
+                               st, d_part, per_chunk, chunks, regressed + (size_t)b0 * KR * 3);
+            PG_LAUNCH_CHECK(h, "body model regressor sum kernel");
+        }
+    }
+    return PG_OK;
+}
+
+extern "C" int pg_vertex_errors(pg_handle* h, void* stream, int64_t B, int V, const float* a, const float* b, double* per_pose,
+                                double* summary) {
+    const char* who = "pg_vertex_errors";
+    if (!h) return pg_fail(nullptr, PG_EINVAL, "null handle");
+    if (!a || !b || !per_pose) return pg_fail(h, PG_EINVAL, "%s: a, b and per_pose are required", who);
+    if (B < 1 || V < 1) return pg_fail(h, PG_EINVAL, "%s: B = %lld, V = %d", who, (long long)B, V);
+    PG_HIP(h, hipSetDevice(h->device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(pgsm::vertex_err_kernel, dim3((unsigned)((B + pgsm::WAVES - 1) / pgsm::WAVES)), dim3(pgsm::THREADS), 0, st, a, b,
+                       (long long)B, V, per_pose);
+    PG_LAUNCH_CHECK(h, "vertex error kernel");
+    if (summary) {
+        hipLaunchKernelGGL(pgsm::vertex_err_mean, dim3(1), dim3(pgsm::THREADS), 0, st, per_pose, (long long)B, summary);
+        PG_LAUNCH_CHECK(h, "vertex error mean kernel");
+    }
+    return PG_OK;
+}
+
+extern "C" int pg_pose_kinematics_rot(pg_handle* h, void* stream, int64_t n_poses, const float* rotmats, const double* bone_offsets,
+                                      const int32_t* parents, float* kps, float* skts, double* l2ws) {
+    const char* who = "pg_pose_kinematics_rot";
+    if (!h) return pg_fail(nullptr, PG_EINVAL, "null handle");
+    if (n_poses < 0 || !rotmats || !bone_offsets || !parents) return pg_fail(h, PG_EINVAL, "%s: null/negative argument", who);
+    pgsm::KinConst kc;
+    kc.depth = tree_depth(parents);
+    if (kc.depth < 0) return pg_fail(h, PG_EINVAL, "%s: parents[0] must be -1 and every joint must come after its parent", who);
+    if (n_poses == 0) return PG_OK;
+    for (int i = 0; i < pgsm::NJ * 3; ++i) kc.offs[i] = bone_offsets[i];
+    for (int i = 0; i < pgsm::NJ; ++i) kc.parent[i] = parents[i];
+    PG_HIP(h, hipSetDevice(h->device));
+    hipLaunchKernelGGL(pgsm::kin_rot_kernel, dim3((unsigned)((n_poses + pgsm::WAVES - 1) / pgsm::WAVES)), dim3(pgsm::THREADS), 0,
+                       static_cast<hipStream_t>(stream), kc, rotmats, (long long)n_poses, kps, skts, l2ws);
+    PG_LAUNCH_CHECK(h, "rotation-matrix kinematics kernel");
+    return PG_OK;
+}

@@ -89,6 +89,17 @@ def render_for_regressor(caster, bones: torch.Tensor, rest_pose, c2w, H: int, W:
 
 
 @torch.no_grad()
+def regressor_keypoints(renderer, pred_rotmat: torch.Tensor, rest_pose=None, scale: float = 0.4) -> torch.Tensor:
+    """The regressor's rotation matrices [F,24,3,3] as key points [F,24,3] on the device: the
+    `pose[ii] = get_smpl_l2ws_torch(pred_rotmat, axis_to_matrix=False, scale=0.4)[:, :, :3, -1]` line of the loop
+    (run_gan.py:2081), by pg_pose_kinematics_rot.  `rest_pose`: None = smpl_rest_pose in float32, as there.  What comes out goes
+    into `regressor_feedback`."""
+    from .skeleton import smpl_rest_pose
+    rest = smpl_rest_pose.astype(np.float32) if rest_pose is None else rest_pose
+    return renderer.pose_kinematics_rot(pred_rotmat, rest, scale=scale)[0]
+
+
+@torch.no_grad()
 def regressor_feedback(pred_kps: torch.Tensor, gt_kps: torch.Tensor, scorer=None) -> torch.Tensor:
     """The number the loop feeds back from the regressor (run_gan.py:2085-2091): both [F,24,3] pose sets centred on joint 0, the
     14 joints of run_gan.py:2087, `spin_loss = 1 - mpjpe(pose, pose_gt)` -- as a float64 device scalar from `pg_pose_scores`

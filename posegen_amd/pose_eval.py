@@ -9,8 +9,13 @@ stay on the device: `pg_pose_scores` (csrc/pg_posescore.hip) aligns one pose per
 `pa_mpjpe`, `n_mpjpe`, `reconstruction_error` and `refinement_scores` have the reference's call shapes; they run on a scorer of
 their own per device (a `HipRenderer` without weights: the entry point needs none) unless one is passed.
 
-Not built, refused or simply not offered: SMPL mesh and joint regressors (SMPLEvalHelper), kinematics from rotation matrices,
-gradients through the scores, `procrustes(scaling=False)`, scoring across several devices.
+`evaluate_smpl_predictions` (evaluate.test, run_gan.py:1584-1634) and `pampjpe_from_smpl_params`
+(evaluate_pampjpe_from_smpl_params, evaluation_helpers.py:542-612) put the SMPL body in front of the scorer: `smpl.BodyModel`
+(pg_smpl_forward) regresses the joints on the device and they go into `PoseScorer` without leaving it; kinematics from rotation
+matrices are `HipRenderer.pose_kinematics_rot`.
+
+Not built, refused or simply not offered: gradients through the scores, `procrustes(scaling=False)`, scoring across several
+devices.
 """
 from __future__ import annotations
 
@@ -269,3 +274,79 @@ def refinement_scores(layer, kp_idx, anchor_kps, gt_kps=None, ext_scale=0.001, s
         s = scorer.score(kps, pick(gt_kps), align="best", unit=unit, pck_threshold=None, auc_thresholds=None)
         out.update({"PA-MPJPE": s["aligned"], "MPJPE": s["mpjpe"], "d": s["d"]})
     return out
+
+
+# the 14 of the 17 regressed H36M joints evaluate.test scores (run_gan.py:1608, constants.H36M_TO_J14) and the order in which
+# evaluate_pampjpe_from_smpl_params compares them (evaluation_helpers.py:538)
+H36M_TO_J14 = (6, 5, 4, 1, 2, 3, 16, 15, 14, 11, 12, 13, 8, 10)
+SPIN_TO_CANON = (10, 8, 14, 15, 16, 11, 12, 13, 4, 5, 6, 1, 2, 3, 0, 7, 9)
+
+
+def _pelvis_j14(regressed: torch.Tensor) -> torch.Tensor:
+    """run_gan.py:1606-1609: the regressed joint 0 subtracted as pelvis, the 14 joints selected"""
+    idx = torch.as_tensor(H36M_TO_J14, device=regressed.device)
+    return (regressed[:, idx] - regressed[:, :1]).contiguous()
+
+
+@torch.no_grad()
+def evaluate_smpl_predictions(body_neutral, body_male, body_female, pred_rotmat, pred_betas, gt_pose, gt_betas, gender, h36m="h36m",
+                              scorer: Optional[PoseScorer] = None, alpha=0.15):
+    """`evaluate.test` behind the regressor (run_gan.py:1596-1634): `pred_rotmat` [B,24,3,3], `pred_betas` [B,NB] through the
+    neutral body, `gt_pose` [B,72] axis-angle, `gt_betas` through the male body and, where `gender` == 1, the female one (a
+    `torch.where` on the two bodies' outputs); regressor `h36m` of each body on its vertices, joint 0 as pelvis, H36M_TO_J14.
+    Returns float64 numpy arrays [B] from one copy: "mpjpe", "pa-mpjpe" (reconstruction_error: det R = +1), "pck" (every pose's
+    share of unaligned distances below `alpha`; the reference keeps the last pose's only), "ume" and "pme" (mean vertex distance of
+    the unposed and the posed meshes).  Six passes through pg_smpl_forward, as the reference makes six through lbs."""
+    from . import smpl
+    dev = body_neutral.device
+    B = int(np.shape(pred_rotmat)[0])
+    g = torch.as_tensor(gender).to(dev).reshape(-1)
+    if g.shape[0] != B:
+        raise ValueError(f"evaluate_smpl_predictions: {g.shape[0]} genders for {B} poses")
+    female = (g == 1).view(B, 1, 1)
+    sc = scorer if scorer is not None else PoseScorer(body_neutral.renderer)
+    pred = body_neutral.forward(pred_betas, pred_rotmat, pose2rot=False, regressor=h36m, want_vertices=True, joints=False)
+    gt_pose = torch.as_tensor(gt_pose).reshape(B, 24, 3)
+    gm = body_male.forward(gt_betas, gt_pose, regressor=h36m, want_vertices=True, joints=False)
+    gf = body_female.forward(gt_betas, gt_pose, regressor=h36m, want_vertices=True, joints=False)
+    gt_vertices = torch.where(female, gf.vertices, gm.vertices)
+    gt_kps = _pelvis_j14(torch.where(female, gf.regressed, gm.regressed))
+    pred_kps = _pelvis_j14(pred.regressed)
+    eye = torch.eye(3, device=dev).expand(B, 24, 3, 3).contiguous()
+    un_pred = body_neutral.forward(pred_betas, eye, pose2rot=False, want_vertices=True, joints=False).vertices
+    un_gt = torch.where(female, body_female.forward(gt_betas, eye, pose2rot=False, want_vertices=True, joints=False).vertices,
+                        body_male.forward(gt_betas, eye, pose2rot=False, want_vertices=True, joints=False).vertices)
+    per_pose = sc.enqueue(pred_kps, gt_kps, align="rotation", ret_per_pose=True)["per_pose"]
+    raw = sc.enqueue(pred_kps, gt_kps, align="none", ret_joint_err=True)["joint_err"]
+    ume = smpl.vertex_errors(body_neutral.renderer, un_gt, un_pred)[0]
+    pme = smpl.vertex_errors(body_neutral.renderer, gt_vertices, pred.vertices)[0]
+    out = torch.stack([per_pose[:, 0], per_pose[:, 1], (raw < alpha).double().mean(dim=1), ume, pme]).cpu().numpy()     # the one copy
+    return dict(zip(("mpjpe", "pa-mpjpe", "pck", "ume", "pme"), out))
+
+
+@torch.no_grad()
+def pampjpe_from_smpl_params(body, gt_kps, betas, bones, regressor="h36m", pck_threshold=150., use_normalize=False,
+                             scorer: Optional[PoseScorer] = None):
+    """`evaluate_pampjpe_from_smpl_params(gt_kps, betas, bones, ret_kp=True, ret_pck=True)` (evaluation_helpers.py:542-603):
+    `bones` [B,24,3] axis-angle become rotation matrices as axisang_to_rot forms them, go through `body` (pose2rot=False) and its
+    17-row `regressor`, in the order SPIN_TO_CANON.  `gt_kps` [B,17,3] in millimetres.  Returns floats {"pampjpe": the mean joint
+    distance after `procrustes` against gt_kps (in its unit), "mpjpe": both sets centred on joint 14, gt / 1000, times 1000
+    (N-MPJPE with `use_normalize`), "pck": the share of aligned joint distances below `pck_threshold`, "auc": the mean share over
+    linspace(0, 150, 31)}, and "pred_kps" [B,17,3] on the device."""
+    from . import smpl
+    B = int(np.shape(bones)[0])
+    if tuple(np.shape(gt_kps)) != (B, len(SPIN_TO_CANON), 3):
+        raise ValueError(f"pampjpe_from_smpl_params: gt_kps {tuple(np.shape(gt_kps))}; [{B},{len(SPIN_TO_CANON)},3] expected")
+    rots = smpl.bones_to_rotmats(torch.as_tensor(bones).reshape(B, 24, 3))
+    reg = body.forward(torch.as_tensor(betas), rots, pose2rot=False, regressor=regressor, joints=False).regressed
+    if reg.shape[1] != len(SPIN_TO_CANON):
+        raise ValueError(f"pampjpe_from_smpl_params: regressor {regressor!r} has {reg.shape[1]} rows, not {len(SPIN_TO_CANON)}")
+    pred_kps = reg[:, torch.as_tensor(SPIN_TO_CANON, device=reg.device)].contiguous()
+    sc = scorer if scorer is not None else PoseScorer(body.renderer)
+    gt = sc._to_device(gt_kps)
+    pa = sc.score(pred_kps, gt, align="best", pck_threshold=pck_threshold, auc_thresholds=np.linspace(0, 150, 31))
+    gt_m = (gt.double() / 1000.0).float()                     # (a float32 division by a scalar is a product with its reciprocal on the device)
+    mp = sc.score(pred_kps, gt_m, root=14, align="scale" if use_normalize else "none", unit=1000., pck_threshold=None,
+                  auc_thresholds=None)
+    return {"pampjpe": pa["aligned"], "mpjpe": mp["aligned"] if use_normalize else mp["mpjpe"], "pck": pa["pck"], "auc": pa["auc"],
+            "pred_kps": pred_kps}

@@ -727,6 +727,36 @@ class HipRenderer:
                                                 par.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(kps), _ptr(skts), _ptr(l2ws)))
         return (kps, skts, l2ws) if want_l2ws else (kps, skts)
 
+    def pose_kinematics_rot(self, rotmats: torch.Tensor, rest_pose, scale: float = 1.0, parents=None, want_l2ws: bool = False):
+        """`pose_kinematics` with the rotations given: rotmats [F,24,3,3] (any device/dtype; float32 on the device) -> device kps
+        [F,24,3] f32, skts [F,24,4,4] f32 (+ l2ws f64), get_smpl_l2ws_torch(pose, rest_pose, scale, axis_to_matrix=False)
+        (core/utils/skeleton_utils.py:379-463; pg_pose_kinematics_rot).  `scale` multiplies the rest pose in its own dtype, as
+        the reference's `rest_pose * scale` does."""
+        from .skeleton import SMPLSkeleton
+        shape = tuple(np.shape(rotmats))
+        if len(shape) != 4 or shape[1:] != (24, 3, 3):
+            raise ValueError(f"pose_kinematics_rot: rotmats {shape}; [F,24,3,3] expected")
+        par = np.asarray(SMPLSkeleton.joint_trees if parents is None else parents)
+        if par.dtype.kind not in "iu" or par.shape != (24,):
+            raise ValueError("pose_kinematics_rot: parents must be 24 integers")
+        par = np.ascontiguousarray(par.astype(np.int32))
+        par[0] = -1
+        if any(not 0 <= par[j] < j for j in range(1, 24)):
+            raise ValueError("pose_kinematics_rot: every joint must come after its parent")
+        rp = np.asarray(rest_pose).reshape(24, 3)
+        rp = rp * np.asarray(scale, dtype=rp.dtype)
+        offs = rp.copy()
+        offs[1:] = rp[1:] - rp[par[1:]]
+        rest = np.ascontiguousarray(offs.astype(np.float64))
+        m = _dev_f32(torch.as_tensor(rotmats), self.device)
+        F = m.shape[0]
+        kps = torch.empty(F, 24, 3, device=self.device)
+        skts = torch.empty(F, 24, 4, 4, device=self.device)
+        l2ws = torch.empty(F, 24, 4, 4, device=self.device, dtype=torch.float64) if want_l2ws else None
+        self._check(self.lib.pg_pose_kinematics_rot(self.handle, self._stream(), F, _ptr(m), rest.ctypes.data_as(C.POINTER(C.c_double)),
+                                                    par.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(kps), _ptr(skts), _ptr(l2ws)))
+        return (kps, skts, l2ws) if want_l2ws else (kps, skts)
+
     def pose_boxes(self, kps: torch.Tensor, c2ws, H: int, W: int, focal, ext_scale: float, center=None,
                    extend_mm: float = 250., top_expand_ratio: float = 1.60, bot_expand_ratio: float = 1.10):
         """Device bounding cylinders [F,5] f32 and integer boxes [F,4] i32 (tl_x, tl_y, br_x, br_y) of device

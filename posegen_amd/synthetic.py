@@ -118,3 +118,38 @@ def make_camera(n_frames: int, H: int = 512, W: int = 512) -> Tuple[np.ndarray, 
     c2ws = np.repeat(c2w[None], n_frames, axis=0)
     focals = np.full((n_frames,), 500.0 * H / 512.0, dtype=np.float32)
     return c2ws, focals
+
+
+def make_body_model(V: int, NB: int = 10, seed: int = 0, regress_rows=(17, 9)) -> Dict[str, np.ndarray]:
+    """A seeded body-like model in smplx's layout, every array dense (there is no SMPL file in the build environment, and none is
+    needed): `v_template` [V,3] points around the rest skeleton (vertex i near joint i % 24), `shapedirs` [V,3,NB] ~ 1e-2,
+    `posedirs` [207,3V] ~ 5e-3, `J_regressor` [24,V], `lbs_weights` [V,24] and the extra regressors `regressor_<K>` [K,V]
+    (one per entry of `regress_rows`): non-negative rows summing to 1, a dense floor under a bump on the vertices of the row's
+    own joint (so that every column carries weight somewhere), `parents` of SMPLSkeleton.  float32 like the model files.  The
+    scales are part of what tests/test_smpl_ref.py's ablations mean."""
+    from .skeleton import SMPLSkeleton
+    rng = np.random.RandomState(seed)
+    rest = np.asarray(smpl_rest_pose, dtype=np.float64) * 0.4           # the GAN loop's scale (run_gan.py:2081): a body ~1.7 long
+    owner = np.arange(V) % 24
+    v_template = rest[owner] + rng.randn(V, 3) * 0.08
+
+    def rows_to_one(n_rows, group):
+        """[n_rows, V]: floor U(0,1) / V everywhere, U(0.5,1) on the vertices of the row's group"""
+        w = rng.uniform(0.0, 1.0, size=(n_rows, V)) / V
+        w += rng.uniform(0.5, 1.0, size=(n_rows, V)) * (group[None, :] == np.arange(n_rows)[:, None])
+        return w / w.sum(axis=1, keepdims=True)
+
+    model = {
+        "v_template": v_template,
+        "shapedirs": rng.randn(V, 3, NB) * 1e-2,
+        "posedirs": rng.randn(207, 3 * V) * 5e-3,
+        "J_regressor": rows_to_one(24, owner),
+    }
+    skin = rng.uniform(0.0, 1.0, size=(V, 24)) ** 4 + 2.0 * (owner[:, None] == np.arange(24)[None, :])
+    model["lbs_weights"] = skin / skin.sum(axis=1, keepdims=True)
+    for K in regress_rows:
+        model[f"regressor_{K}"] = rows_to_one(K, np.arange(V) % K)
+    model = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in model.items()}
+    model["parents"] = np.asarray(SMPLSkeleton.joint_trees, dtype=np.int32).copy()
+    model["parents"][0] = -1
+    return model
