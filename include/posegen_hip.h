@@ -795,6 +795,51 @@ int pg_vertex_errors(pg_handle* h, void* stream, int64_t B, int V, const float* 
 int pg_pose_kinematics_rot(pg_handle* h, void* stream, int64_t n_poses, const float* rotmats, const double* bone_offsets,
                            const int32_t* parents, float* kps, float* skts, double* l2ws);
 
+/* ---- training on pose error (posegen_amd/pose_losses.py) -----------------------------------------------------------
+ * The transpose of pg_pose_kinematics for its `kps` output: d_bones = (d kps / d bones)^T d_kps.
+ *   bones     device [n_poses,24,3] float64 axis-angle, bone_offsets / parents HOST, as in the forward
+ *   d_kps     device [n_poses,24,3] float32: the cotangent of kps
+ *   d_bones   device [n_poses,24,3] float64
+ * The rotation map is the forward's own (rotation vector -> unit quaternion -> matrix, k = sin(theta/2) / theta); below theta = 1e-3
+ * the gradient is the derivative of the series the forward uses there, written in theta^2: k = 1/2 - theta^2/48 + theta^4/3840,
+ * q_w = 1 - theta^2/8 + theta^4/384 (cos(theta/2) to below 1e-22), so the gradient at a zero rotation vector is finite: the rotation
+ * generators'.  No cotangents for skts / l2ws (pg_poseopt_backward has those for the training path).
+ * float64 arithmetic; the forward is computed again from `bones`, nothing is kept between calls.  Asynchronous on `stream`; no
+ * atomics, every sum in a fixed order: two calls give the same bytes, and a pose's rows are the same bytes whatever n_poses is and
+ * wherever the pose sits.  A non-finite value in one pose stays in that pose's rows.
+ * PG_EINVAL, nothing launched and nothing written: a NULL pointer, n_poses < 0, a joint that does not come after its parent. */
+int pg_pose_kinematics_bwd(pg_handle* h, void* stream, int64_t n_poses, const double* bones, const double* bone_offsets,
+                           const int32_t* parents, const float* d_kps, double* d_bones);
+
+/* The transpose of pg_pose_kinematics_rot for `kps`: the nine entries of every matrix are free variables, as in the reference's
+ * autograd through get_smpl_l2ws_torch(axis_to_matrix=False); the matrices are used as given, not re-orthogonalised.
+ *   rotmats, d_rotmats   device [n_poses,24,3,3] float32;   d_kps device [n_poses,24,3] float32
+ * float64 arithmetic on the float32 inputs, rounded once; otherwise as pg_pose_kinematics_bwd. */
+int pg_pose_kinematics_rot_bwd(pg_handle* h, void* stream, int64_t n_poses, const float* rotmats, const double* bone_offsets,
+                               const int32_t* parents, const float* d_kps, float* d_rotmats);
+
+/* The pose losses of the GAN loop with their gradients.  p, g: rows `joints` of pred, gt after row `root` of each was subtracted
+ * (root = -1: nothing subtracted; joints = NULL: all J_in rows), float64 on the float32 inputs, as in pg_pose_scores.  Per pose
+ *   MPJPE         e_b = (1/J) sum_j |p_j - g_j|                                        (mpjpe, run_gan.py:1458-1464, :2091)
+ *   NORM_MATCHED  s_b = |g|_F / |p|_F,  e_b = (1/J) sum_j |s_b p_j - g_j|              (train_spin, run_gan.py:1902-1906)
+ * per_pose[b] = weight e_b.  cap = +inf keeps every pose and NaN propagates; a finite cap keeps the poses with per_pose[b] < cap
+ * (strict; a NaN pose is not kept; :1907-1908).  loss = sum of the kept per_pose / n_kept: NaN when nothing is kept, as torch.mean of
+ * an empty tensor is.
+ *   summary   device [3] float64: loss, n_kept, B
+ *   per_pose  device [B] float64, may be NULL
+ *   d_pred, d_gt   device [B,J_in,3] float32, each may be NULL: the gradients of `loss` (upstream 1).  Rows that are not selected and
+ *             poses that are not kept are exactly zero; the root row receives minus the sum of the selected rows' gradients; a zero
+ *             distance contributes a zero gradient (as torch's norm backward); with nothing kept everything is zero.  The gradient
+ *             rows of a pose that is itself non-finite are unspecified.
+ * A pose with |p|_F = 0 is NaN under NORM_MATCHED, that pose only.  Asynchronous on `stream`; no atomics, every sum in a fixed
+ * order: two calls give the same bytes.  Workspace: B doubles of the handle's grow-only buffer where per_pose is NULL.
+ * PG_EINVAL, nothing launched and nothing written: pred, gt or summary NULL; B < 1; J outside [1, 64]; a joint or root index outside
+ * J_in; a joint selected twice; an unknown kind; weight or cap NaN; cap <= 0. */
+#define PG_POSE_LOSS_MPJPE        0
+#define PG_POSE_LOSS_NORM_MATCHED 1
+int pg_pose_loss(pg_handle* h, void* stream, int64_t B, int J_in, const float* pred, const float* gt, const int32_t* joints, int J,
+                 int root, int kind, double weight, double cap, double* per_pose, double* summary, float* d_pred, float* d_gt);
+
 /* Test / measurement aid: on = 0 makes the fused 16-bit and compensated kernels compute every limb of the density input
  * for every point instead of leaving out the limbs a wave / a pass is out of cutoff range of (a joint farther than
  * cutoff_dist + 24 / (tau log2 e) has a cutoff weight 1 - sigmoid(tau (v - c)) below 2^-24, cutoff_embedder.py:139-146:

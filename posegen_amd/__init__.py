@@ -21,6 +21,7 @@ _EVALUATE_NAMES = ("FrameScorer", "evaluate_frames", "evaluate_metric", "Validat
 _POSE_EVAL_NAMES = ("PoseScorer", "pa_mpjpe", "n_mpjpe", "reconstruction_error", "refinement_scores", "evaluate_smpl_predictions",
                     "pampjpe_from_smpl_params")
 _SMPL_NAMES = ("BodyModel", "vertex_errors")
+_POSE_LOSS_NAMES = ("keypoints_from_axis_angle", "keypoints_from_rotmats", "pose_loss")
 _SCENE_NAMES = ("ScenePerson", "render_scene", "render_scenes", "place_people")
 
 
@@ -44,6 +45,9 @@ def __getattr__(name):
     if name in _SMPL_NAMES:                    # the SMPL body on the device (imports torch as well)
         from . import smpl
         return getattr(smpl, name)
+    if name in _POSE_LOSS_NAMES:               # differentiable key points and pose losses (imports torch as well)
+        from . import pose_losses
+        return getattr(pose_losses, name)
     if name in _SCENE_NAMES:                  # several people in one frame (imports torch as well)
         from . import scene
         return getattr(scene, name)

@@ -23,6 +23,7 @@ PG_COMP_PLAIN, PG_COMP_IS_ONLY, PG_COMP_MERGED = 0, 1, 2
 PG_ABI_VERSION = 11
 PG_METRICS_BG = 1
 PG_POSE_ALIGN_NONE, PG_POSE_ALIGN_SCALE, PG_POSE_ALIGN_BEST, PG_POSE_ALIGN_ROTATION = 0, 1, 2, 3
+PG_POSE_LOSS_MPJPE, PG_POSE_LOSS_NORM_MATCHED = 0, 1
 
 
 class HipLibraryError(RuntimeError):
@@ -194,6 +195,11 @@ PROTOTYPES = {
     "pg_vertex_errors": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, _FP, _FP, C.c_void_p, C.c_void_p]),
     "pg_pose_kinematics_rot": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _FP, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_void_p,
                                          C.c_void_p, C.c_void_p]),
+    "pg_pose_kinematics_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int32), _FP,
+                                         C.c_void_p]),
+    "pg_pose_kinematics_rot_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _FP, C.POINTER(C.c_double), C.POINTER(C.c_int32), _FP, _FP]),
+    "pg_pose_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, _FP, _FP, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int,
+                               C.c_double, C.c_double, C.c_void_p, C.c_void_p, _FP, _FP]),
     "pg_plan_frames": (C.c_int, [C.c_int, C.POINTER(C.c_int64), C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int,
                                  C.POINTER(C.c_int)]),
     "pg_render_scene": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float,

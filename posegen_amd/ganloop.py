@@ -109,3 +109,33 @@ def regressor_feedback(pred_kps: torch.Tensor, gt_kps: torch.Tensor, scorer=None
     sc = pose_eval._scorer_for(scorer, pred_kps, gt_kps)
     out = sc.enqueue(pred_kps, gt_kps, joints=pose_eval.GAN_LOOP_JOINTS, root=0, align="none")
     return 1.0 - out["summary"][1]
+
+
+def generator_feedback(renderer, pred_kps: torch.Tensor, bones: torch.Tensor, rest_pose=None, scale: float = 0.4) -> torch.Tensor:
+    """`regressor_feedback` as the generator trains on it (run_gan.py:2032-2034, 2085-2091): `1 - mpjpe(pose, pose_gt)` on the loop's 14
+    joints, both sets centred on joint 0, with `pose_gt = get_smpl_l2ws_torch(bones, scale=0.4)[..., :3, -1]` differentiable in the
+    generator's axis-angle output `bones` [F,24,3] and `pose` = `pred_kps` [F,24,3] a constant (the regressor runs under no_grad
+    there).  A float64 device scalar; its backward is two launches (pg_pose_loss's gradient, pg_pose_kinematics_bwd).  `rest_pose`:
+    None = smpl_rest_pose in float32."""
+    from . import pose_eval, pose_losses
+    from .skeleton import smpl_rest_pose
+    rest = smpl_rest_pose.astype(np.float32) if rest_pose is None else rest_pose
+    gt_kps = pose_losses.keypoints_from_axis_angle(renderer, bones, rest, scale=scale)
+    return 1.0 - pose_losses.pose_loss(pred_kps.detach(), gt_kps, joints=pose_eval.GAN_LOOP_JOINTS, root=0, kind="mpjpe", renderer=renderer)
+
+
+def regressor_loss(renderer, pred_rotmat: torch.Tensor, gt: torch.Tensor, gt_is_axis_angle: bool = False, cap: float = 0.02,
+                   weight: float = 0.1) -> torch.Tensor:
+    """The loss `train_spin` trains the regressor on (run_gan.py:1896-1908): key points of `pred_rotmat` [F,24,3,3] at scale 0.4, both
+    sets centred on joint 0, the loop's 14 joints, the prediction rescaled to the ground truth's Frobenius norm, `weight` times the
+    per-pose mean joint distance, poses at or above `cap` dropped, the mean of the rest -- differentiable in `pred_rotmat`.  `gt`: key
+    points [F,24,3]; with `gt_is_axis_angle` axis-angle vectors [F,24,3] that go through the same kinematics first, which with
+    `cap=math.inf` is the MPII branch (:1924-1934)."""
+    from . import pose_eval, pose_losses
+    from .skeleton import smpl_rest_pose
+    pred_kps = pose_losses.keypoints_from_rotmats(renderer, pred_rotmat, None, scale=0.4)
+    if gt_is_axis_angle:
+        with torch.no_grad():
+            gt = renderer.pose_kinematics(gt, smpl_rest_pose.astype(np.float32) * np.float32(0.4))[0]
+    return pose_losses.pose_loss(pred_kps, gt.detach(), joints=pose_eval.GAN_LOOP_JOINTS, root=0, kind="norm_matched", weight=weight,
+                                 cap=cap, renderer=renderer)

@@ -14,7 +14,8 @@ their own per device (a `HipRenderer` without weights: the entry point needs non
 (pg_smpl_forward) regresses the joints on the device and they go into `PoseScorer` without leaving it; kinematics from rotation
 matrices are `HipRenderer.pose_kinematics_rot`.
 
-Not built, refused or simply not offered: gradients through the scores, `procrustes(scaling=False)`, scoring across several
+Not built, refused or simply not offered: gradients through the aligned scores (the unaligned and norm-matched losses with their
+gradients are `pose_losses`), `procrustes(scaling=False)`, scoring across several
 devices.
 """
 from __future__ import annotations
