@@ -211,6 +211,28 @@ __device__ __forceinline__ unsigned lds_addr_of(const void* p) {
     return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) void*)p;
 }
 
+// The (a, b) rows of one joint slot of a per-ray record (32 bytes: a | distance, b | 0) read beside the ring pipe: slot jj of the
+// lane group's six goes into the instruction's offset field, like a bias tile of BiasPipe (pg_eval16r.hip).
+struct AbRowPipe {
+    a128 lo, hi;
+    __device__ __forceinline__ void fetch(unsigned base, int jj) {          // jj < 6 (constant after unrolling)
+        switch (jj) {
+#define PG_ROW_CASE(K, A, B) case K: asm volatile("ds_read_b128 %0, %2 offset:0+" #A "\n\tds_read_b128 %1, %2 offset:0+" #B : "=&v"(lo), "=&v"(hi) : "v"(base)); break;
+            PG_ROW_CASE(0, 0, 16) PG_ROW_CASE(1, 32, 48) PG_ROW_CASE(2, 64, 80) PG_ROW_CASE(3, 96, 112) PG_ROW_CASE(4, 128, 144) PG_ROW_CASE(5, 160, 176)
+#undef PG_ROW_CASE
+            default: __builtin_unreachable();
+        }
+    }
+    // q = a + z b, QFromAB's arithmetic; the caller has waited for the reads (or a retire of the ring pipe behind them has)
+    __device__ __forceinline__ void q(float z, float& qx, float& qy, float& qz) {
+        typedef __attribute__((ext_vector_type(4))) float row4;
+        lds_landed(lo); lds_landed(hi);
+        // (whole vectors: __builtin_bit_cast of a vector ELEMENT reads element 0 whatever the index)
+        const row4 a = __builtin_bit_cast(row4, lo), b = __builtin_bit_cast(row4, hi);
+        qx = fmaf(z, b[0], a[0]); qy = fmaf(z, b[1], a[1]); qz = fmaf(z, b[2], a[2]);
+    }
+};
+
 // Units of a segment that CONTINUES a chunk already entered and whose refill pieces are all out (the rgb head behind
 // the alpha / view segment): positions Q0 .. Q0+T-1 of the current chunk, no chunk entry, no refill pieces.
 template <typename V, int T, int NS, int Q0, typename ST>
@@ -381,7 +403,8 @@ __device__ __forceinline__ void dump_frags(const EvalArgs& a, int stage, long lo
 #if defined(PG_STAMPS)
 // (the scheduling barriers keep register-only work -- a ReLU + pack, conversions -- on its own side of the stamp: the asm's
 // memory clobber orders loads and stores only)
-#define PG_STAMP(k) do { unsigned long long t_; __builtin_amdgcn_sched_barrier(0); asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); __builtin_amdgcn_sched_barrier(0); stamps[k] = t_; } while (0)
+#define PG_STAMP_TO(dst) do { unsigned long long t_; __builtin_amdgcn_sched_barrier(0); asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); __builtin_amdgcn_sched_barrier(0); (dst) = t_; } while (0)
+#define PG_STAMP(k) PG_STAMP_TO(stamps[k])
 #else
 #define PG_STAMP(k) do {} while (0)
 #endif

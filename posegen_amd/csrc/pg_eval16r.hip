@@ -126,9 +126,13 @@ __device__ __forceinline__ void mma_row16(f32x4 (*acc)[2], APipe<V, NS>& p, ST& 
 // `gmask` bit jj (the same in every wave of the workgroup): NO point of the pass is in range of limb jj; its chunk is
 // not in this pass's chunk sequence at all (Stream MASK_NX: never fetched, no entry, no barrier).
 // `hook` runs once behind the segment's first chunk entry (the per-pass record fetch of layer 0 hangs there).
+// `xdir` = the B fragments of the three direction units, formed once per pass (dir_operands16): both x phases of a pass take
+// them ready, so the direction units are A reads and MFMAs only.
+// `xst` (PG_STAMPS builds): two stamps, in front of the direction units and behind their last MFMA.
 template <typename V, typename ST, typename HOOK>
 __device__ __forceinline__ void x_segment16(f32x4 (*acc)[2], ST& st, const float* abp0, const float* abp1, float z0, float z1,
-                                            const float* cutv, float tau, int farmask, int gmask, HOOK hook) {
+                                            const float* cutv, float tau, int farmask, int gmask, const V (*xdir)[2], HOOK hook,
+                                            unsigned long long* xst = nullptr) {
     APipeX<V> p;
     constexpr int T = XU16 * NT16;
     static_assert(2 * NT16 == pgp::R::UPC, "a limb's two unit rows are exactly one chunk of the stream");
@@ -155,23 +159,66 @@ __device__ __forceinline__ void x_segment16(f32x4 (*acc)[2], ST& st, const float
         if (!hooked) { hook(); hooked = true; }
         mma_row16<V, NT16, T>(acc, p, st, 2 * jj + 1, Op<V>::cvt(x0 + 8), Op<V>::cvt(x1 + 8));
     }
-    // r = q / max(|q|, 1e-12) of every joint (VecNormEncoder on the bone-local position, encoders.py:172-193): not
-    // cutoff-weighted, always there
-    auto dir = [](const QFromAB& q, int jj, float* r3) {
-        float qx, qy, qz;
-        q(jj, qx, qy, qz);
-        const float rinv = __builtin_amdgcn_rsqf(fmaxf(qx * qx + qy * qy + qz * qz, 1e-24f));
-        r3[0] = qx * rinv; r3[1] = qy * rinv; r3[2] = qz * rinv;
-    };
+    // the directions r = q / max(|q|, 1e-12) of every joint: not cutoff-weighted, always there
+#if defined(PG_STAMPS)
+    if (xst) PG_STAMP_TO(xst[0]);
+#endif
 #pragma clang loop unroll(full)
     for (int pr = 0; pr < JG / 2; ++pr) {
-        float v0[8], v1[8];
-        dir(q0, 2 * pr, v0); dir(q0, 2 * pr + 1, v0 + 3);
-        dir(q1, 2 * pr, v1); dir(q1, 2 * pr + 1, v1 + 3);
-        v0[6] = v0[7] = v1[6] = v1[7] = 0.0f;
-        mma_row16<V, NT16, T>(acc, p, st, XV16 + pr, Op<V>::cvt(v0), Op<V>::cvt(v1));
+        mma_row16<V, NT16, T>(acc, p, st, XV16 + pr, xdir[pr][0], xdir[pr][1]);
         if (!hooked) { hook(); hooked = true; }
     }
+#if defined(PG_STAMPS)
+    if (xst) PG_STAMP_TO(xst[1]);
+#endif
+}
+
+// The direction operands of a pass and the wave's limb mask, from ONE bone-local position q = a + z b per (joint slot,
+// point) of the lane: r = q / max(|q|, 1e-12) (VecNormEncoder, encoders.py:172-193) as the B fragments of the three
+// direction units -- unit pr holds joint slots 2 pr, 2 pr + 1 of the lane group, three values each, two zeros -- for the
+// wave's two column tiles, and `farmask` bit jj: |q|^2 >= far^2 of slot jj in all four lane groups and both points
+// (x_segment16).  ab0 / ab1 = LDS addresses of the lane group's rows of the two points' rays, read beside the ring pipe
+// (AbRowPipe), far2 = the lane group's six squared far radii.  The arithmetic is what every earlier use of q spelled
+// out, with the contractions hipcc chose there written as fmaf: |q|^2 = fma(qz, qz, fma(qx, qx, qy qy)).
+template <typename V>
+__device__ __forceinline__ int dir_operands16(V (*xdir)[2], unsigned ab0, unsigned ab1, float z0, float z1, const float* far2) {
+    AbRowPipe rp[JG][2];
+    float f2[JG];
+#pragma unroll
+    for (int jj = 0; jj < JG; ++jj) { rp[jj][0].fetch(ab0, jj); rp[jj][1].fetch(ab1, jj); }
+#pragma unroll
+    for (int jj = 0; jj < JG; ++jj) f2[jj] = far2[jj];
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    int farmask = 0;
+    float v[2][8];
+#pragma unroll
+    for (int jj = 0; jj < JG; ++jj) {
+        float s2[2];
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            float qx, qy, qz;
+            rp[jj][c].q(c ? z1 : z0, qx, qy, qz);
+            s2[c] = fmaf(qz, qz, fmaf(qx, qx, qy * qy));
+            const float rinv = __builtin_amdgcn_rsqf(fmaxf(s2[c], 1e-24f));
+            float* r3 = v[c] + 3 * (jj & 1);
+            r3[0] = qx * rinv; r3[1] = qy * rinv; r3[2] = qz * rinv;
+        }
+        if (__builtin_amdgcn_ballot_w64(fminf(s2[0], s2[1]) < f2[jj]) == 0ull) farmask |= 1 << jj;
+        if (jj & 1) {
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                v[c][6] = v[c][7] = 0.0f;
+                // formed HERE: the three live words of a fragment are opaque from now on (hipcc would sink the conversions to
+                // their first use, in front of layer 0's direction MFMAs), the fourth stays the constant it is
+                const u32x4 w = __builtin_bit_cast(u32x4, Op<V>::cvt(v[c]));
+                unsigned w0 = w[0], w1 = w[1], w2 = w[2];
+                asm volatile("" : "+v"(w0), "+v"(w1), "+v"(w2));
+                const u32x4 o = {w0, w1, w2, 0u};
+                xdir[jj / 2][c] = __builtin_bit_cast(V, o);
+            }
+        }
+    }
+    return farmask;
 }
 
 // On-chip variant: the view layer's direction part Y[ray][joint][out] = sum_k W_vd[out, (joint, k)] T[ray][joint][k]
@@ -290,7 +337,9 @@ __device__ __forceinline__ int pass_far_mask(const uint8_t* ab, int nrm1, const 
 struct BiasPipe {
     unsigned base;          // LDS byte address of the lane group's rows of the segment's first bias tile
     a128 r;
-    __device__ __forceinline__ BiasPipe(unsigned bbase, int tile0) : base(bbase + tile0 * 64) { asm volatile("" : "+v"(base)); }
+    // (opaque BEFORE the tile offset is added: made opaque behind the add, hipcc formed the ten bases of a pass ahead of the pass
+    // loop and carried them through it -- ten registers, or scratch -- where one add per layer does)
+    __device__ __forceinline__ BiasPipe(unsigned bbase, int tile0) { asm volatile("" : "+v"(bbase)); base = bbase + tile0 * 64; }
     __device__ __forceinline__ void fetch(int k) {          // tile0 + k, k < 16 (constant after unrolling)
         switch (k) {
 #define PG_BIAS_CASE(K) case K: asm volatile("ds_read_b128 %0, %1 offset:0+" #K "*64" : "=v"(r) : "v"(base)); break;
@@ -482,16 +531,19 @@ __global__ __launch_bounds__(NTHR, 2) void eval16r_kernel(const EvalArgs a) {
 
     // depths of the next pass, fetched a pass ahead (consumed at the top of the pass: one wait finds them there)
     float nx_z[2] = {0.0f, 0.0f};
-#define PG_PREFETCH_Z(itn)                                                                         \
+#define PG_PREFETCH_Z(itn, col_)                                                                   \
     do {                                                                                           \
-        const long long p0n_ = (long long)(itn) * PTS + wave * 32 + col;                           \
+        const long long p0n_ = (long long)(itn) * PTS + wave * 32 + (col_);                        \
         nx_z[0] = a.z[min(p0n_, a.n_points - 1)];                                                  \
         nx_z[1] = a.z[min(p0n_ + 16, a.n_points - 1)];                                             \
     } while (0)
-    if ((int)blockIdx.x < a.n_iters) PG_PREFETCH_Z(blockIdx.x);
+    if ((int)blockIdx.x < a.n_iters) PG_PREFETCH_Z(blockIdx.x, col);
 
 #if defined(PG_STAMPS)
-    unsigned long long stamps[12];
+    unsigned long long stamps[16];          // 12 .. 15: inside the two x phases (x_segment16 xst)
+#define PG_XSTAMPS(k) (stamps + (k))
+#else
+#define PG_XSTAMPS(k) nullptr
 #endif
 #if defined(PG_WALK_STAMPS)
     // how even the walk is (tools/diag_pass_walk.py): the workgroup's clock at entry and exit, its passes and its limbs in range
@@ -517,7 +569,7 @@ __global__ __launch_bounds__(NTHR, 2) void eval16r_kernel(const EvalArgs a) {
         const float* abp[2];
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
-            const int i = wave * 32 + 16 * c + col;
+            const int i = wave * 32 + 16 * c + (lane_p & 15);       // (from the per-pass copy: not a value carried through the pass)
             myr[c] = min(ray_of(off0 + i), nrm1);
             zz[c] = nx_z[c];
             abp[c] = opaque_ptr(reinterpret_cast<const float*>(smem + LDSR_AB + abuf * LDS_AB_BYTES + myr[c] * REC_AB_BYTES) + JG * g_p * 8);
@@ -527,25 +579,17 @@ __global__ __launch_bounds__(NTHR, 2) void eval16r_kernel(const EvalArgs a) {
         const int off0n = pw.off0n, r0n = pw.r0n;
         const float* cutd = opaque_ptr(cut + J + JG * g_p);
         const QFromAB q0{abp[0], zz[0]}, q1{abp[1], zz[1]};
-        float cutv[JG];                         // the lane group's folded cutoff constants (6 registers)
-#pragma unroll
-        for (int jj = 0; jj < JG; ++jj) cutv[jj] = cut[JG * g_p + jj];
-        // limbs out of cutoff range of every point of the wave (x_segment16): one ballot per joint slot over the four
-        // lane groups' joints and the 2 x 16 points
-        int farmask = 0;
-#if !defined(PG_NO_FAR_SKIP)
-        {
-            const float* far2 = opaque_ptr(cut + 2 * J + JG * g_p);
-#pragma unroll
-            for (int jj = 0; jj < JG; ++jj) {
-                float ax, ay, az, bx, by, bz;
-                q0(jj, ax, ay, az);
-                q1(jj, bx, by, bz);
-                const bool near = fminf(ax * ax + ay * ay + az * az, bx * bx + by * by + bz * bz) < far2[jj];
-                if (__builtin_amdgcn_ballot_w64(near) == 0ull) farmask |= 1 << jj;
-            }
-            farmask = __builtin_amdgcn_readfirstlane(a.far_skip ? farmask : 0);
-        }
+        // the lane group's folded cutoff constants: read where a limb in range needs one, beside that limb's (a, b) rows
+        // (carried as six registers before: they are what the direction operands' registers would have pushed into scratch)
+        const float* cutv = opaque_ptr(cut + JG * g_p);
+        // The pass's direction operands and, from the same |q|^2, the limbs out of cutoff range of every point of the wave
+        // (dir_operands16): q of the lane's 12 (joint slot, point) pairs is formed here once for both x phases of the pass.
+        V xdir[JG / 2][2];
+        int farmask = dir_operands16<V>(xdir, lds_addr_of(abp[0]), lds_addr_of(abp[1]), zz[0], zz[1], opaque_ptr(cut + 2 * J + JG * g_p));
+#if defined(PG_NO_FAR_SKIP)
+        farmask = 0;
+#else
+        farmask = __builtin_amdgcn_readfirstlane(a.far_skip ? farmask : 0);
 #endif
 #if defined(PG_WALK_STAMPS)
         walk_passes += 1; walk_limbs += (unsigned)__builtin_popcount(~gmask & 63);
@@ -590,16 +634,16 @@ __global__ __launch_bounds__(NTHR, 2) void eval16r_kernel(const EvalArgs a) {
             f32x4 acc[NT16][2];
 #pragma unroll
             for (int o = 0; o < NT16; ++o) acc[o][0] = acc[o][1] = load_bias16(bias, BS_LAYER0 + o, g);
-            x_segment16<V>(acc, st, abp[0], abp[1], zz[0], zz[1], cutv, tlv, farmask, gmask, fetch_records);
+            x_segment16<V>(acc, st, abp[0], abp[1], zz[0], zz[1], cutv, tlv, farmask, gmask, xdir, fetch_records, PG_XSTAMPS(12));
             if (TAPS && a.dbg && a.dbg_stage == 0) {
 #pragma unroll
                 for (int c = 0; c < 2; ++c) {
-                    const int i = wave * 32 + 16 * c + col;
+                    const int i = wave * 32 + 16 * c + (lane_p & 15);
                     if (i <= last) {
 #pragma unroll
                         for (int o = 0; o < NT16; ++o)
 #pragma unroll
-                            for (int r = 0; r < 4; ++r) a.dbg[(p0 + i) * W + 16 * o + 4 * g + r] = acc[o][c][r];
+                            for (int r = 0; r < 4; ++r) a.dbg[(p0 + i) * W + 16 * o + 4 * g_p + r] = acc[o][c][r];
                     }
                 }
             }
@@ -657,7 +701,7 @@ __global__ __launch_bounds__(NTHR, 2) void eval16r_kernel(const EvalArgs a) {
                     if (u == PG_R_BIAS_AT && o + 1 < NT16) bp.fetch(o + 1);
                 }
             }
-            x_segment16<V>(acc, st, abp[0], abp[1], zz[0], zz[1], cutv, tlv, farmask, gmask, [] {});
+            x_segment16<V>(acc, st, abp[0], abp[1], zz[0], zz[1], cutv, tlv, farmask, gmask, xdir, [] {}, PG_XSTAMPS(14));
 #pragma unroll
             for (int u = 0; u < HU16; ++u)
 #pragma unroll
@@ -727,7 +771,7 @@ __global__ __launch_bounds__(NTHR, 2) void eval16r_kernel(const EvalArgs a) {
                 PG_STAMP(6);
                 skip_units<TAV, HU16>(st, C_AV);
                 PG_STAMP(7);
-                PG_PREFETCH_Z(itn);
+                PG_PREFETCH_Z(itn, lane_p & 15);
                 c0 = c1 = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
             } else {
                 f32x4 vacc[NTV16][2];
@@ -755,7 +799,7 @@ __global__ __launch_bounds__(NTHR, 2) void eval16r_kernel(const EvalArgs a) {
                 PG_STAMP(7);
                 // the next pass's depths: in flight through the rgb head and the pass boundary (defined on both
                 // branches: a conditional re-definition would keep registers live through the whole pass)
-                PG_PREFETCH_Z(itn);
+                PG_PREFETCH_Z(itn, lane_p & 15);
                 APipe<V> pr;
                 BiasPipe bpr(bbase, BS_RGB);
                 bpr.fetch(0);
@@ -768,8 +812,8 @@ __global__ __launch_bounds__(NTHR, 2) void eval16r_kernel(const EvalArgs a) {
                 }
             }
         }
-        if (g == 0) {       // rows 0..2 of the rgb tile and row 0 of the alpha tile live in lane group 0
-            const int i = wave * 32 + col;      // (the pass's point index is recomputed here rather than kept for the whole pass)
+        if (g_p == 0) {     // rows 0..2 of the rgb tile and row 0 of the alpha tile live in lane group 0
+            const int i = wave * 32 + (lane_p & 15);    // (the pass's point index is recomputed here, from the per-pass lane copy, rather than kept for the whole pass)
             if (i <= last) *reinterpret_cast<float4*>(a.raw + (p0 + i) * 4) = make_float4(c0[0], c0[1], c0[2], sigma[0]);
             if (i + 16 <= last) *reinterpret_cast<float4*>(a.raw + (p0 + i + 16) * 4) = make_float4(c1[0], c1[1], c1[2], sigma[1]);
         }
@@ -786,6 +830,7 @@ __global__ __launch_bounds__(NTHR, 2) void eval16r_kernel(const EvalArgs a) {
                 for (int k = 0; k < 9; ++k) rec[k] = stamps[k];
                 rec[9] = st.t_vm; rec[10] = st.t_bar;
                 rec[11] = stamps[11];           // in front of y_segment16
+                for (int k = 12; k < 16; ++k) rec[k] = stamps[k];
             }
             st.t_vm = 0; st.t_bar = 0;
         }

@@ -19,8 +19,14 @@ from posegen_amd.raycaster import HipRayCaster
 SLOTS = 1024
 # stamp order in a pass: 0 | prologue | 1 | layer 0 (x) | 11 | Y limb chunks (on-chip form) | 2 | layers 1-4 | 3 | layer 5 | 4 | ..
 ORDER = [0, 1, 11, 2, 3, 4, 5, 6, 7, 8]
-NAMES = ["pass prologue", "L0 (x) + pack", "Y limb chunks", "L1-4", "L5 (h+x) + pack", "L6-7", "alpha tile", "view (trunk+Y)", "rgb+store"]
-MFMA = [0, 448, 0, 1024, 704, 512, 16, 144, 8]          # per wave, 16x16x32, every limb in range (Y: 4 per limb chunk)
+# (stamp 6 sits behind the eight view tiles since the empty-wave skip: the row in front of it is the alpha tile AND the view tiles'
+# trunk part, 9 x 8 units; the row behind it the view layer's second stage, y_apply16, with its pack)
+NAMES = ["pass prologue", "L0 (x) + pack", "Y limb chunks", "L1-4", "L5 (h+x) + pack", "L6-7", "alpha + view tiles", "view 2nd stage (Y)", "rgb+store"]
+MFMA = [0, 448, 0, 1024, 704, 512, 144, 16, 8]          # per wave, 16x16x32, every limb in range (Y: 4 per limb chunk)
+# inside the two x phases (x_segment16): record words 12 / 13 = in front of layer 0's direction units / behind their last MFMA,
+# 14 / 15 = the same in the skip layer; a phase starts at stamp 1 / 3 and ends, behind its ReLU + pack, at stamp 11 / 4
+X_PHASES = (("layer 0", 1, 12, 13, 11, "bias + limb units"), ("skip layer", 3, 14, 15, 4, "hidden part + limb units"))
+DIR_MFMA = 96                                           # three direction units x 16 out tiles x 2 column tiles
 
 
 def table(full, label):
@@ -43,6 +49,30 @@ def table(full, label):
     if has.any():
         print(f"Y limb chunks: {100 * has.mean():.1f}% of the passes have a limb in range; there {d[has][:, :, 2].mean():.0f} cycles per pass "
               f"(slowest wave {y[has].mean():.0f}), elsewhere {d[~has][:, :, 2].mean() if (~has).any() else 0:.0f}")
+    x_rows(full, has if has.any() else None)
+
+
+def x_rows(full, has):
+    """The two x phases by stretch: what is in front of the direction units, the direction units (96 MFMAs per wave), the ReLU +
+    pack behind them -- for passes with and without a limb in range (the record form has no Y segment to tell them by: there a
+    pass counts as 'with' when layer 0's limb stretch of its slowest wave is past a chunk entry)."""
+    if not (full[:, :, 12:16] != 0).all():
+        print("x phases: this build has no stamps inside x_segment16")
+        return
+    f = full.astype(np.float64)
+    if has is None:
+        has = (f[:, :, 12] - f[:, :, 1]).max(1) > 600
+    for label, sel in (("no limb in range", ~has), ("a limb in range", has)):
+        if not sel.any():
+            continue
+        g = f[sel]
+        print(f"x phases, passes with {label} ({100 * sel.mean():.1f}% of the passes):")
+        for name, s0, sd, sm, s1, front in X_PHASES:
+            a, b, c = (g[:, :, sd] - g[:, :, s0]).mean(), (g[:, :, sm] - g[:, :, sd]).mean(), (g[:, :, s1] - g[:, :, sm]).mean()
+            print(f"   {name:10s} {front:24s} {a:7.0f}   direction units {b:6.0f} ({b / DIR_MFMA:5.1f} cyc/mfma)   ReLU + pack {c:6.0f}   "
+                  f"phase {a + b + c:7.0f}")
+        pro = (g[:, :, 1] - g[:, :, 0]).mean()
+        print(f"   pass prologue {pro:6.0f}   pass total {(g[:, :, 8] - g[:, :, 0]).mean():7.0f}")
 
 
 def main():
