@@ -840,6 +840,73 @@ int pg_pose_kinematics_rot_bwd(pg_handle* h, void* stream, int64_t n_poses, cons
 int pg_pose_loss(pg_handle* h, void* stream, int64_t B, int J_in, const float* pred, const float* gt, const int32_t* joints, int J,
                  int root, int kind, double weight, double cap, double* per_pose, double* summary, float* d_pred, float* d_gt);
 
+/* ---- what a training step optimises (posegen_amd/train_losses.py, posegen_amd/trainer.py) ---------------------------
+ * The reference Trainer's losses, pose regulariser and gradient norms (core/trainer.py:193-205, 321-443).  All three entry points:
+ * asynchronous on `stream`, no host synchronisation; no atomics, every sum in a fixed order that depends on the sizes alone (not on
+ * the device, not on where an array lies), so two calls give the same bytes on every machine; float64 arithmetic on the float32
+ * inputs, outputs rounded once; at most three launches; nothing is kept between calls except grow-only scratch in the handle.
+ * PG_EINVAL means nothing was launched and nothing written.
+ *
+ * pg_train_loss: Trainer._compute_nerf_loss for the fine pass and, with rgb0 / acc0, the coarse pass, summed as compute_loss sums
+ * them (trainer.py:321-383).
+ *   rgb_map [n,3], acc_map [n], target [n,3]   device float32;  rgb0 [n,3], acc0 [n]: both NULL = no coarse pass
+ *   bgs [n,3] or NULL (then the scalar base_bg);  fgs [n] (batch['fgs'][..., 0]), may be NULL with PG_TRAIN_REG_NONE
+ *   pred = rgb + (1 - acc) bg with use_background, else rgb; the loss is the mean over the 3n elements of (pred - target)^2 (MSE),
+ *   |pred - target| (L1) or F.smooth_l1_loss(beta) (HUBER: quadratic strictly below beta; beta = 0 is L1); the coarse pass's loss is
+ *   multiplied by coarse_weight.  PG_TRAIN_REG_BCE: acc2bce(acc, fgs, reduction='off') reg_coef per pass, i.e. the mean of
+ *   -(y log(x + 1e-8) + (1 - y) log(1 - x + 1e-8)) over the rays with y < 1.0 only; with no such ray that term (and the total) is NaN
+ *   and its gradient zero, the convention of pg_pose_loss.  PG_TRAIN_REG_L1 / PG_TRAIN_REG_MSE are refused: the reference calls them
+ *   with reduction='off', which they answer with the unreduced tensor, and its backward() raises.
+ *   summary   device [10] float64: total, rgb_loss, rgb_loss0, reg_loss, reg_loss0, psnr, psnr0, mean(acc_map), and the two passes'
+ *             BCE ray counts; psnr = -10 log10(mean((pred - target)^2)) of the composited prediction whatever the loss kind; the
+ *             entries of a pass or a term that is absent are 0
+ *   d_rgb_map [n,3], d_acc_map [n], d_rgb0, d_acc0   device float32, each may be NULL: the gradient of `total` at upstream 1, in the
+ *             shapes pg_train_backward takes, overwritten.  The L1 derivative at a zero difference is 0, as in torch.
+ * A NaN in an input reaches the sums, as in the reference.  PG_EINVAL: a required pointer NULL; rgb0 without acc0 or the reverse;
+ * n outside [1, 2^31 - 1]; an unknown kind; HUBER with beta < 0 or NaN; BCE without fgs; REG_L1 / REG_MSE. */
+#define PG_TRAIN_LOSS_MSE   0
+#define PG_TRAIN_LOSS_L1    1
+#define PG_TRAIN_LOSS_HUBER 2
+#define PG_TRAIN_REG_NONE 0
+#define PG_TRAIN_REG_BCE  1
+#define PG_TRAIN_REG_L1   2
+#define PG_TRAIN_REG_MSE  3
+int pg_train_loss(pg_handle* h, void* stream, int64_t n, const float* rgb_map, const float* acc_map, const float* rgb0, const float* acc0,
+                  const float* target, const float* bgs, double base_bg, const float* fgs, int loss_kind, double beta, int use_background,
+                  double coarse_weight, int reg_kind, double reg_coef, double* summary, float* d_rgb_map, float* d_acc_map, float* d_rgb0,
+                  float* d_acc0);
+
+/* Trainer._compute_kp_loss for opt_rot6d (trainer.py:384-443).
+ *   rots [n,24,3,3], kps [n,24,3]   device float32, per ray (the pose layer's outputs)
+ *   anchor_rots [N,24,3,3], anchor_kps [N,24,3]   device float32;  kp_idx HOST int32 [n], every entry in [0, N): checked before
+ *             anything is launched and copied into the handle (as pg_poseopt_forward's ray_pose)
+ *   The 6-D bone of a joint is the first two columns of its matrix ([..., :3, :2].flatten(-2)).  x = (anchor - bone)^2 over joints
+ *   1..23; an element contributes x - tol where x > tol (strict; tol is rounded to float32 first, the value the reference compares
+ *   with) and 0 elsewhere (a NaN stays a NaN); kp_loss = coef times the mean over n 23 of the per-joint sums.
+ *   prev_rots, prev_kps, next_rots, next_kps (per ray, constants; all four or none) with temp_val [n] and temp_coef add
+ *   temp_loss = temp_coef mean over n 24 of (sum_6 ((b - b_prev) - (b_next - b))^2 + sum_3 likewise on kps) temp_val, all 24 joints.
+ *   summary   device [4] float64: kp_loss, temp_loss (0 without the term), MPJPC = mean |anchor_kps - kps| / ext_scale (no
+ *             gradient), kp_loss + temp_loss
+ *   d_rots [n,24,3,3], d_kps [n,24,3]   device float32, each may be NULL, overwritten: the gradient of the total.  The third column
+ *             of every d_rots matrix is zero; the root joint gets only the temporal term.
+ * PG_EINVAL: a required pointer NULL; n or N < 1; a kp_idx entry outside [0, N); some but not all of prev / next; the temporal term
+ * without temp_val; a NaN scalar; ext_scale <= 0. */
+int pg_pose_reg_loss(pg_handle* h, void* stream, int64_t n, const float* rots, const float* kps, int64_t N, const float* anchor_rots,
+                     const float* anchor_kps, const int32_t* kp_idx, double tol, double coef, double ext_scale, const float* prev_rots,
+                     const float* prev_kps, const float* next_rots, const float* next_kps, const float* temp_val, double temp_coef,
+                     double* summary, float* d_rots, float* d_kps);
+
+/* get_gradnorm (trainer.py:193-205) without its launch and host synchronisation per tensor.
+ *   grads     HOST table of n_tensors device pointers to float32 gradients, counts HOST [n_tensors] their element counts.  A pointer
+ *             need only be 4-byte aligned (a parameter may be a view): the 16-byte loads peel heads and tails, and an element's place
+ *             in the sum does not depend on the alignment.
+ *   out       device [2 + n_tensors] float64: total_norm = sqrt(sum_t |g_t|^2), avg_norm = sqrt(total_norm^2 / n_tensors), then every
+ *             tensor's own norm
+ * One difference from the reference, stated: it rounds every tensor's norm to float32 before squaring; here nothing is rounded.
+ * PG_EINVAL: n_tensors outside [1, PG_GRAD_NORMS_MAX] (the reference divides by zero at 0); a NULL pointer with a positive count. */
+#define PG_GRAD_NORMS_MAX 256
+int pg_grad_norms(pg_handle* h, void* stream, int n_tensors, const float* const* grads, const int64_t* counts, double* out);
+
 /* Test / measurement aid: on = 0 makes the fused 16-bit and compensated kernels compute every limb of the density input
  * for every point instead of leaving out the limbs a wave / a pass is out of cutoff range of (a joint farther than
  * cutoff_dist + 24 / (tau log2 e) has a cutoff weight 1 - sigmoid(tau (v - c)) below 2^-24, cutoff_embedder.py:139-146:

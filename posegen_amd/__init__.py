@@ -22,6 +22,8 @@ _POSE_EVAL_NAMES = ("PoseScorer", "pa_mpjpe", "n_mpjpe", "reconstruction_error",
                     "pampjpe_from_smpl_params")
 _SMPL_NAMES = ("BodyModel", "vertex_errors")
 _POSE_LOSS_NAMES = ("keypoints_from_axis_angle", "keypoints_from_rotmats", "pose_loss")
+_TRAIN_LOSS_NAMES = ("photometric_loss", "pose_regulariser", "grad_norms")
+_TRAINER_NAMES = ("HipTrainer",)
 _SCENE_NAMES = ("ScenePerson", "render_scene", "render_scenes", "place_people")
 
 
@@ -48,6 +50,12 @@ def __getattr__(name):
     if name in _POSE_LOSS_NAMES:               # differentiable key points and pose losses (imports torch as well)
         from . import pose_losses
         return getattr(pose_losses, name)
+    if name in _TRAIN_LOSS_NAMES:              # the trainer's losses, pose regulariser and gradient norms (imports torch as well)
+        from . import train_losses
+        return getattr(train_losses, name)
+    if name in _TRAINER_NAMES:                 # the training step: the reference's Trainer (imports torch as well)
+        from . import trainer
+        return getattr(trainer, name)
     if name in _SCENE_NAMES:                  # several people in one frame (imports torch as well)
         from . import scene
         return getattr(scene, name)

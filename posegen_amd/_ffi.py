@@ -24,6 +24,9 @@ PG_ABI_VERSION = 11
 PG_METRICS_BG = 1
 PG_POSE_ALIGN_NONE, PG_POSE_ALIGN_SCALE, PG_POSE_ALIGN_BEST, PG_POSE_ALIGN_ROTATION = 0, 1, 2, 3
 PG_POSE_LOSS_MPJPE, PG_POSE_LOSS_NORM_MATCHED = 0, 1
+PG_TRAIN_LOSS_MSE, PG_TRAIN_LOSS_L1, PG_TRAIN_LOSS_HUBER = 0, 1, 2
+PG_TRAIN_REG_NONE, PG_TRAIN_REG_BCE, PG_TRAIN_REG_L1, PG_TRAIN_REG_MSE = 0, 1, 2, 3
+PG_GRAD_NORMS_MAX = 256
 
 
 class HipLibraryError(RuntimeError):
@@ -200,6 +203,11 @@ PROTOTYPES = {
     "pg_pose_kinematics_rot_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _FP, C.POINTER(C.c_double), C.POINTER(C.c_int32), _FP, _FP]),
     "pg_pose_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, _FP, _FP, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int,
                                C.c_double, C.c_double, C.c_void_p, C.c_void_p, _FP, _FP]),
+    "pg_train_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _FP, _FP, _FP, _FP, _FP, _FP, C.c_double, _FP, C.c_int, C.c_double, C.c_int,
+                                C.c_double, C.c_int, C.c_double, C.c_void_p, _FP, _FP, _FP, _FP]),
+    "pg_pose_reg_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _FP, _FP, C.c_int64, _FP, _FP, C.POINTER(C.c_int32), C.c_double,
+                                   C.c_double, C.c_double, _FP, _FP, _FP, _FP, _FP, C.c_double, C.c_void_p, _FP, _FP]),
+    "pg_grad_norms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_void_p]),
     "pg_plan_frames": (C.c_int, [C.c_int, C.POINTER(C.c_int64), C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int,
                                  C.POINTER(C.c_int)]),
     "pg_render_scene": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float,

@@ -735,6 +735,7 @@ void pg_destroy(pg_handle* h) {
     pg_posescore_release(h);
     pg_smpl_release(h);
     pg_kploss_release(h);
+    pg_trainloss_release(h);
     pg_frames_release(h);
     pg_scene_release(h);
     for (auto& pr : h->ev_aux) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }

@@ -1,6 +1,6 @@
 // pg_handle.h -- the renderer handle behind the C ABI (include/posegen_hip.h), shared by the translation units that implement
 // its entry points: pg_api.hip (handle, weights, ray-level rendering), pg_frames.hip (frames), pg_train.hip (the training step),
-// pg_mesh.hip, pg_poseopt.hip, pg_batch.hip, pg_metrics.hip, pg_scene.hip, pg_posescore.hip, pg_smpl.hip, pg_kploss.hip.  Each of the last ten keeps its own state behind a void* of the handle.
+// pg_mesh.hip, pg_poseopt.hip, pg_batch.hip, pg_metrics.hip, pg_scene.hip, pg_posescore.hip, pg_smpl.hip, pg_kploss.hip, pg_trainloss.hip.  Each of the last eleven keeps its own state behind a void* of the handle.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -65,6 +65,7 @@ struct pg_handle : Subject {
     void* posescore = nullptr;       // pose scores (pg_posescore.hip): the waves' partial sums and threshold counts of pg_pose_scores
     void* smpl = nullptr;            // the body model (pg_smpl.hip): feature rows, joint transforms and regressor partial sums of a pose slice
     void* kploss = nullptr;          // pose losses (pg_kploss.hip): the per-pose values of a pg_pose_loss call that passes no per_pose
+    void* trainloss = nullptr;       // training losses (pg_trainloss.hip): partial sums, the device copies of kp_idx and of the norms' tensor table
     void* frames = nullptr;          // pg_render_frames (pg_frames.hip): per-device buffers, copy stream and events kept between calls
     void* scene = nullptr;           // pg_render_scene (pg_scene.hip): the people's sample lists and the maps of the boxes' bounding rectangle
     std::vector<float> grid_t;       // pg_grid_density: the host copy of the axis table t[R] while its upload is in flight
@@ -79,6 +80,7 @@ void pg_metrics_release(pg_handle* h);
 void pg_posescore_release(pg_handle* h);
 void pg_smpl_release(pg_handle* h);
 void pg_kploss_release(pg_handle* h);
+void pg_trainloss_release(pg_handle* h);
 void pg_frames_release(pg_handle* h);
 void pg_scene_release(pg_handle* h);
 // scratch of pg_launch_sample_coarse for n rays in chunks of `chunk` (null when the one-launch form runs)
