@@ -158,8 +158,11 @@ __device__ __forceinline__ void glds16(const void* g, void* l) {
 // workgroup point is within cutoff range of the limb: nothing would read it); MASK_X2 >= 0: a third such range.  The mask must be the same in every
 // wave.  `pf_mask` is the mask of the pass the prefetch pointer is in, `nx_mask` that of the pass behind it (taken
 // over when the pointer wraps to the head of the stream).
-template <int NWAVE, int NCHUNK_, int NDMA = NWAVE, int MASK_NX = 0, int MASK_X0 = 0, int MASK_X1 = 0, int MASK_X2 = -1>
+// AHEAD_ (pg_eval16r.hip): the A pipe may run across chunk entries (enter_split fl, issue_next; pg_eval16_common.h next_a XM,
+// which also says where a chunk's refill pieces then go out: an entry whose chunk reads ahead waits for the NEXT chunk's as well).
+template <int NWAVE, int NCHUNK_, int NDMA = NWAVE, int MASK_NX = 0, int MASK_X0 = 0, int MASK_X1 = 0, int MASK_X2 = -1, bool AHEAD_ = false>
 struct Stream {
+    static constexpr bool AHEAD = AHEAD_;
     static constexpr int NSLOT = PG_RING_SLOTS;
     static constexpr int DEPTH = NSLOT - 1;
     static constexpr int PER = CHUNK_BYTES / 1024 / NDMA;    // DMA instructions per DMA wave per chunk
@@ -218,10 +221,25 @@ struct Stream {
 #pragma unroll
         for (int i = 0; i < DEPTH; ++i) prefetch_next();
         rd_off = (uint32_t)(NSLOT - 1) * CHUNK_BYTES + lane * 16;   // advanced by the first enter()
-        rd_nxt = lane * 16;
     }
 #if defined(PG_STAMPS)
     unsigned long long t_vm = 0, t_bar = 0;
+    // The restart of the A pipe behind a chunk entry: from the release of the entry's barrier (enter_split) to the retire of the
+    // entry's first A fragment (next_a), summed over the entries, and their number.  The stamp's own lgkmcnt(0) drains the reads
+    // issued behind the first one: it lengthens the chunk, not the stretch it measures.
+    // PRIMED (enter_split fl bit 1): the entry could not wait for its own stamps -- reads were in flight -- and left them in
+    // t_s0 / t_s1 / t_rel; they have landed behind this stamp's lgkmcnt(0) and are accounted for here (named as operands of the
+    // wait, so that no use of them is scheduled in front of it).
+    unsigned long long t_rel = 0, t_rst = 0, t_s0 = 0, t_s1 = 0;
+    unsigned n_rst = 0;
+    template <bool PRIMED = false>
+    __device__ __forceinline__ void restart_stamp() {
+        unsigned long long t;
+        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t), "+s"(t_s0), "+s"(t_s1), "+s"(t_rel)::"memory");
+        if (PRIMED) { t_vm += t_s1 - t_s0; t_bar += t_rel - t_s1; }
+        t_rst += t - t_rel;
+        n_rst += 1u;
+    }
 #endif
     __device__ __forceinline__ void enter(int /*chunk index, documentation only*/) {
 #if defined(PG_STAMPS)
@@ -249,7 +267,6 @@ struct Stream {
     // relies on it).  Issued as one burst right after the barrier, the 8 waves' pieces queue up
     // in the texture addresser and every wave stalls on the issue.
     uint32_t cur_src, cur_dst;   // stream byte offset / ring byte offset of this wave's share
-    uint32_t rd_nxt;             // this lane's ring offset for the chunk AFTER the current one (enter_ahead / issue_ahead)
     // plain_ok(c): at the entry of stream chunk c the ring bookkeeping is known at compile time -- no masked chunk lies between c
     // and the chunk behind the one fetched now, and the stream does not wrap there -- so `next_off += CHUNK_BYTES` replaces
     // advance() (the wrap test, the mask hand-over and skip_masked: ~20 scalar instructions per entry)
@@ -264,23 +281,25 @@ struct Stream {
         }
         return true;
     }
-    __device__ __forceinline__ void enter_split(bool plain = false) {
-#if defined(PG_STAMPS)
-        unsigned long long s0, s1, s2;
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(s0)::"memory");
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"((DEPTH - 1) * PER) : "memory");
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(s1)::"memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(s2)::"memory");
-        t_vm += s1 - s0;
-        t_bar += s2 - s1;
-#else
-        if (dma_wave()) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((DEPTH - 1) * PER) : "memory");
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#if !defined(PG_ABL_NOBARRIER)      // timing ablation only (racy, wrong results): what ANY scheme without a workgroup barrier per chunk could gain at most
-        __builtin_amdgcn_s_barrier();
-#endif
-#endif
+    // fl (AHEAD streams; 0 = the entry as it always was).  With B(k) the barrier of the entry into chunk k:
+    //   bit 0, "wait next": the tail of chunk k will read the head of chunk k+1 ahead of B(k+1) (issue_next), so behind B(k)
+    //     both chunks must be in LDS and visible.  An LDS-DMA is ordered against another wave's ds_read only by the issuing
+    //     wave's covering vmcnt plus a barrier: the wave waits for everything it has issued, vmcnt(0) -- its pieces of chunk
+    //     k+1 are the youngest of them (those of chunk k+2 go out behind B(k)), and whatever else rides on the count (record,
+    //     ray, depth and frame-code DMAs, raw stores) is older.  Every wave of the workgroup takes the same flavour at the
+    //     same entry: the flag is a property of the entry's place in the stream, not of what the wave does with the chunk.
+    //   bit 1, "primed": the tail of chunk k-1 has issued the reads of this chunk's first units and they may still be in
+    //     flight: no lgkmcnt(0).  The wave's reads of chunk k-1 have returned all the same -- its last MFMA of that chunk
+    //     waited for the chunk's last fragment and LGKM returns in order -- which is what the refill of that chunk's slot,
+    //     behind this barrier, needs of every wave.
+    // (fl: a constant where the entry is inlined; one body for all flavours keeps the unrolled pass within hipcc's unroll budget)
+    static constexpr int WAIT_NEXT = 1, PRIMED = 2;
+    __device__ __forceinline__ void wait_pieces(int fl) {
+        if (AHEAD && (fl & WAIT_NEXT)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        else asm volatile("s_waitcnt vmcnt(%0)" ::"n"((DEPTH - 1) * PER) : "memory");
+    }
+    // the ring bookkeeping of an entry: scalar, and one vector add
+    __device__ __forceinline__ void ring_step(bool plain) {
         cur_src = next_off + (wave - dma_base()) * (PER * 1024);
         cur_dst = fill_slot * CHUNK_BYTES + (wave - dma_base()) * (PER * 1024);
         if (plain) next_off += CHUNK_BYTES; else advance();
@@ -290,27 +309,41 @@ struct Stream {
                                                                                   : rd_off + CHUNK_BYTES;
         asm volatile("" : "+v"(rd_off)::"memory");
     }
-    // Chunk entry with the data of the NEXT chunk confirmed as well (needs DEPTH >= 3, i.e. a ring of >= 4
-    // slots): a wave waits for its pieces of chunk c+1 too before the barrier, so behind the barrier every wave
-    // knows that chunks c and c+1 have landed, and reads of chunk c+1 may be issued BEFORE the barrier of its own
-    // entry (issue_ahead).  The A-fragment pipe then runs across chunk boundaries instead of restarting empty
-    // behind every barrier (an LDS latency exposed per chunk with one wave per SIMD).  The barrier of entry(c+1)
-    // still says "everyone is done reading chunk c" before its slot is refilled; this wave's reads of chunk c
-    // are complete by then because its last MFMA of the chunk waited for them (LGKM returns in order), so
-    // no lgkmcnt(0) is needed and the reads already in flight for chunk c+1 stay in flight.
-    __device__ __forceinline__ void enter_ahead() {
-        static_assert(DEPTH >= 3 || NSLOT < 4, "enter_ahead needs three chunks in flight");
-        if (dma_wave()) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((DEPTH >= 3 ? DEPTH - 2 : 0) * PER) : "memory");
+    __device__ __forceinline__ void enter_split(bool plain = false, int fl = 0) {
+        static_assert(!AHEAD || NDMA == NWAVE, "chunk entries of the A pipe that runs across them: every wave refills");
+#if defined(PG_STAMPS)
+        if (AHEAD && (fl & PRIMED)) {
+            // Reads are in flight, so the entry cannot wait for its own stamps: they land behind the lgkmcnt(0) of restart_stamp<true>,
+            // which accounts for them.  Until then hipcc must neither copy nor spill the three register pairs (the value is not there
+            // yet, and a freed pair would be overwritten when it arrives): the three stamps, the wait and the barrier are ONE statement,
+            // the ring bookkeeping comes in front of it (nothing reads the ring in between), and from here to restart_stamp the entry
+            // is asm statements only -- the unit's read, its refill piece, the retire.
+            ring_step(plain);
+            if (fl & WAIT_NEXT)
+                asm volatile("s_memtime %0\n\ts_waitcnt vmcnt(0)\n\ts_memtime %1\n\ts_barrier\n\ts_memtime %2" : "=&s"(t_s0), "=&s"(t_s1), "=&s"(t_rel)::"memory");
+            else
+                asm volatile("s_memtime %0\n\ts_waitcnt vmcnt(%3)\n\ts_memtime %1\n\ts_barrier\n\ts_memtime %2" : "=&s"(t_s0), "=&s"(t_s1), "=&s"(t_rel) : "n"((DEPTH - 1) * PER) : "memory");
+            return;
+        }
+        {
+            unsigned long long s0, s1, s2;
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(s0)::"memory");
+            wait_pieces(fl);
+            asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(s1)::"memory");
+            __builtin_amdgcn_s_barrier();
+            asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(s2)::"memory");
+            t_vm += s1 - s0;
+            t_bar += s2 - s1;
+            t_rel = s2;
+        }
+#else
+        if (dma_wave()) wait_pieces(fl);
+        if (!(AHEAD && (fl & PRIMED))) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#if !defined(PG_ABL_NOBARRIER)      // timing ablation only (racy, wrong results): what ANY scheme without a workgroup barrier per chunk could gain at most
         __builtin_amdgcn_s_barrier();
-        cur_src = next_off + (wave - dma_base()) * (PER * 1024);
-        cur_dst = fill_slot * CHUNK_BYTES + (wave - dma_base()) * (PER * 1024);
-        next_off = next_off + CHUNK_BYTES == (uint32_t)NCHUNK_ * CHUNK_BYTES ? 0u : next_off + CHUNK_BYTES;
-        fill_slot = fill_slot + 1 == NSLOT ? 0u : fill_slot + 1;
-        asm volatile("" : "+s"(next_off), "+s"(fill_slot), "+s"(cur_src), "+s"(cur_dst));
-        rd_off = rd_nxt;
-        rd_nxt = rd_nxt + CHUNK_BYTES >= (uint32_t)NSLOT * CHUNK_BYTES + lane * 16 ? rd_nxt - (NSLOT - 1) * CHUNK_BYTES
-                                                                                  : rd_nxt + CHUNK_BYTES;
-        asm volatile("" : "+v"(rd_off), "+v"(rd_nxt)::"memory");
+#endif
+#endif
+        ring_step(plain);
     }
     // One refill piece, issued by asm in the SGPR-base + 32-bit lane offset form: through the
     // builtin hipcc forms a 64-bit VGPR address (a v_lshl_add_u64) for every one of the ~224
@@ -349,14 +382,16 @@ struct Stream {
             default: __builtin_unreachable();
         }
     }
-    // the same read from the chunk AFTER the current one (enter_ahead)
+    // The same read from the chunk BEHIND the current one, whose entry is still to come (the current entry was taken with
+    // "wait next").  Chunks that are fetched take the ring's slots in turn, so that chunk sits in the next slot; behind its
+    // entry `fill_slot` is the current chunk's slot (the slot freed by the entry, plus one).  The address is formed here, in
+    // a temporary: a register carried from entry to entry does not fit pg_eval16r.hip.
     template <typename R>
-    __device__ __forceinline__ void issue_ahead(R& dst, int pos) const {
-        const unsigned addr = ring_lds + rd_nxt;
+    __device__ __forceinline__ void issue_next(R& dst, int pos) const {
+        const unsigned addr = ring_lds + rd_off + (fill_slot == (uint32_t)(NSLOT - 1) ? 0u - (uint32_t)((NSLOT - 1) * CHUNK_BYTES) : (uint32_t)CHUNK_BYTES);
         switch (pos) {
 #define PG_ISSUE_CASE(P) case P: asm volatile("ds_read_b128 %0, %1 offset:" #P "*1024" : "=v"(dst) : "v"(addr)); break;
-            PG_ISSUE_CASE(0) PG_ISSUE_CASE(1) PG_ISSUE_CASE(2) PG_ISSUE_CASE(3) PG_ISSUE_CASE(4) PG_ISSUE_CASE(5)
-            PG_ISSUE_CASE(6) PG_ISSUE_CASE(7) PG_ISSUE_CASE(8) PG_ISSUE_CASE(9) PG_ISSUE_CASE(10) PG_ISSUE_CASE(11)
+            PG_ISSUE_CASE(0) PG_ISSUE_CASE(1) PG_ISSUE_CASE(2) PG_ISSUE_CASE(3)
 #undef PG_ISSUE_CASE
             default: __builtin_unreachable();
         }

@@ -86,8 +86,9 @@ __device__ __forceinline__ V unit_of(ST& st, int c, int pos) {
 // pass and the MFMA pipe idles ~45 %.  The reads are therefore issued by inline asm, two units
 // ahead into a 3-register-set rotation, and retired by COUNTED lgkmcnt waits (the asm is
 // invisible to hipcc's own waitcnt bookkeeping, whose waits for its own LDS reads only become
-// more conservative).  The lookahead never crosses a chunk boundary (the next chunk is only
-// readable after its enter(), which also drains lgkmcnt).
+// more conservative).  The lookahead stops at a chunk boundary (the next chunk is only readable
+// after its enter(), which also drains lgkmcnt) unless the segment asks for the pipe that runs
+// across entries (next_a XM).
 typedef __attribute__((ext_vector_type(4))) unsigned a128;
 #ifndef PG_EARLY_RETIRE
 #define PG_EARLY_RETIRE 0
@@ -116,12 +117,39 @@ __device__ __forceinline__ void lds_retire(a128& r, int younger) {
     }
 }
 
+// Where the refill pieces of the slot a chunk entry frees go out: piece i at unit PG_DMA_PHASE + i * step of the chunk entered,
+// step = UPC / PER (spread over the whole chunk), or PG_AHEAD_STEP in a chunk whose pieces are waited for one entry earlier -- by
+// an entry of the A pipe that runs across entries, next_a XM: its own chunks and, XM_FRONT, the chunk in front of its first one.
+// They go out at the front of the chunk there, every other unit, not one burst (Stream::enter_split).  piece_at(q): the piece of
+// unit q, or -1; pieces_from(q): the first piece still to come behind unit q.
+#ifndef PG_AHEAD_STEP
+#define PG_AHEAD_STEP 2
+#endif
+constexpr int XM_IN_SEGMENT = 1, XM_PRIMED = 2, XM_HANDS_ON = 4, XM_FRONT = 8;
+template <typename ST, int XM> __device__ __forceinline__ constexpr int piece_step() {
+    return ST::AHEAD && (XM & (XM_IN_SEGMENT | XM_FRONT)) != 0 ? PG_AHEAD_STEP : UPC / ST::PER;
+}
+template <typename ST, int XM> __device__ __forceinline__ constexpr int piece_at(int q) {
+    return q >= PG_DMA_PHASE && (q - PG_DMA_PHASE) % piece_step<ST, XM>() == 0 && (q - PG_DMA_PHASE) / piece_step<ST, XM>() < ST::PER ? (q - PG_DMA_PHASE) / piece_step<ST, XM>() : -1;
+}
+template <typename ST, int XM> __device__ __forceinline__ constexpr int pieces_from(int q) { return q < PG_DMA_PHASE ? 0 : (q - PG_DMA_PHASE) / piece_step<ST, XM>() + 1; }
+
 // A fragment of unit L (compile-time after unrolling) of a segment with T units: NS register
 // sets, reads issued NS-1 units ahead.  ASYNC = false: a plain (compiler-scheduled) read.
 // c0: the segment's first chunk in the stream when the caller knows it (Stream::plain_ok: static ring bookkeeping), else -1
-template <typename V, int T, bool ASYNC, int NS, typename ST>
+// XM (streams with ST::AHEAD; 0 and every other stream: the lookahead stops at a chunk's last unit and restarts behind the next
+// entry, as above): bit 0 -- the pipe runs across the chunk entries INSIDE the segment: the last LA units of a chunk issue the
+// reads of the first LA units of the next one from the next ring slot (Stream::issue_next), the entry in between keeps them in
+// flight (enter_split fl "primed") and the entry of the chunk that reads ahead has waited for the next chunk as well ("wait
+// next"); bit 1 -- the segment is entered with the reads of its first LA units in flight, issued by the segment in front of it
+// through the same pipe `p`; bit 2 -- the segment ends with its last chunk and issues the reads of the first LA units of the
+// segment behind it, which takes the pipe over (bit 1 there) and whose first chunk follows in the stream, never masked.
+// Between such reads and their retire the code is straight-line (tools/audit_asm_loads.py walks it so).  XM_FRONT alone: only
+// the refill pieces move (piece_step).
+template <typename V, int T, bool ASYNC, int NS, typename ST, int XM = 0>
 __device__ __forceinline__ V next_a(APipe<V, NS>& p, ST& st, int L, int c0 = -1) {
-    constexpr int PER = ST::PER, PSTRIDE = UPC / PER, LA = NS - 1;
+    constexpr int LA = NS - 1;
+    static_assert(PG_DMA_PHASE + piece_step<ST, XM>() * (ST::PER - 1) < UPC, "the pieces of a chunk go out inside it");
     const int q = L % UPC;
     if (!ASYNC) {
         if (q == 0) st.enter(L / UPC);
@@ -131,13 +159,39 @@ __device__ __forceinline__ V next_a(APipe<V, NS>& p, ST& st, int L, int c0 = -1)
 #if defined(PG_ABL_NOREAD)      // timing ablation only (wrong results): no ring reads, no waits
     if (q == 0) { if (PG_SPREAD_DMA) st.enter_split(); else st.enter(L / UPC); }
     if (PG_SPREAD_DMA) {
-        if (q % PSTRIDE == PG_DMA_PHASE) st.piece(q / PSTRIDE);
+        if (piece_at<ST, XM>(q) >= 0) st.piece(piece_at<ST, XM>(q));
         if (L == T - 1)
-            for (int i = (q < PG_DMA_PHASE ? 0 : (q - PG_DMA_PHASE) / PSTRIDE + 1); i < PER; ++i) st.piece(i);
+            for (int i = pieces_from<ST, XM>(q); i < ST::PER; ++i) st.piece(i);
     }
     asm volatile("" : "+v"(p.r[L % NS]));
     return __builtin_bit_cast(V, p.r[L % NS]);
 #endif
+    if constexpr (ST::AHEAD && (XM & XM_IN_SEGMENT) != 0) {
+        static_assert(PG_SPREAD_DMA && !PG_EARLY_RETIRE && !PG_PROGRESS_PRIO && LA < UPC, "the pipe across chunk entries");
+        static_assert(!(XM & XM_HANDS_ON) || (T % UPC == 0 && T % NS == 0), "the next segment starts a chunk, at register set 0");
+        constexpr bool ON = (XM & XM_HANDS_ON) != 0;
+        if (q == 0) {
+            const bool primed = L > 0 || (XM & XM_PRIMED) != 0;     // this chunk's first reads are out
+            const bool wait_next = L + UPC < T || ON;              // this chunk's tail reads the next chunk's head
+            const bool plain = c0 >= 0 && ST::plain_ok(c0 + L / UPC);
+            st.enter_split(plain, (wait_next ? ST::WAIT_NEXT : 0) | (primed ? ST::PRIMED : 0));
+            if (!primed)
+                for (int k = 0; k < LA; ++k)
+                    if (k <= T - 1 - L) st.issue(p.r[(L + k) % NS], k);
+        }
+        if (L + LA < T || ON) {     // unit L + LA: of this chunk, or of the next one (of this segment or of the one behind it)
+            if (q + LA < UPC) st.issue(p.r[(L + LA) % NS], q + LA);
+            else st.issue_next(p.r[(L + LA) % NS], q + LA - UPC);
+        }
+        if (piece_at<ST, XM>(q) >= 0) st.piece(piece_at<ST, XM>(q));
+        if (L == T - 1)
+            for (int i = pieces_from<ST, XM>(q); i < ST::PER; ++i) st.piece(i);
+        lds_retire(p.r[L % NS], ON ? LA : min(LA, T - 1 - L));
+#if defined(PG_STAMPS)
+        if (q == 0) { if (L > 0 || (XM & XM_PRIMED) != 0) st.template restart_stamp<true>(); else st.restart_stamp(); }
+#endif
+        return __builtin_bit_cast(V, p.r[L % NS]);
+    }
     if (q == 0) {
         if (PG_SPREAD_DMA) st.enter_split(c0 >= 0 && ST::plain_ok(c0 + L / UPC)); else st.enter(L / UPC);
         for (int k = 0; k < LA; ++k)
@@ -160,11 +214,11 @@ __device__ __forceinline__ V next_a(APipe<V, NS>& p, ST& st, int L, int c0 = -1)
 #endif
     if (LA <= rem) st.issue(p.r[(L + LA) % NS], q + LA);
     if (PG_SPREAD_DMA) {
-        // refill piece i of the freed slot goes out at unit i*PSTRIDE+PG_DMA_PHASE of this
-        // chunk; a segment ending inside the chunk flushes the rest with its last unit
-        if (q % PSTRIDE == PG_DMA_PHASE) st.piece(q / PSTRIDE);
+        // refill piece i of the freed slot goes out at its unit of this chunk (piece_at); a segment ending inside the
+        // chunk flushes the rest with its last unit
+        if (piece_at<ST, XM>(q) >= 0) st.piece(piece_at<ST, XM>(q));
         if (L == T - 1)
-            for (int i = (q < PG_DMA_PHASE ? 0 : (q - PG_DMA_PHASE) / PSTRIDE + 1); i < PER; ++i) st.piece(i);
+            for (int i = pieces_from<ST, XM>(q); i < ST::PER; ++i) st.piece(i);
     }
     if (PG_EARLY_RETIRE) {
         // The retire "writes" its register as far as hipcc knows, and a VALU write directly
@@ -175,24 +229,31 @@ __device__ __forceinline__ V next_a(APipe<V, NS>& p, ST& st, int L, int c0 = -1)
     } else {
         lds_retire(p.r[L % NS], min(LA, rem));
     }
+#if defined(PG_STAMPS)
+    if (q == 0 && PG_SPREAD_DMA) st.restart_stamp();      // the entry's first fragment is in its register
+#endif
     return __builtin_bit_cast(V, p.r[L % NS]);
 }
 
 // Units L0 .. T-1 of a segment WITHOUT reading them: the chunk entries and refill pieces next_a would issue at those units,
 // nothing else (pg_eval16r.hip: a wave that leaves a segment's remaining tiles out still keeps the shared ring going --
 // every entry, barrier and piece at the unit next_a places it, so the counted vmcnt of the entries holds).  The caller
-// has retired (or abandoned behind an lgkmcnt(0)) whatever the pipe had in flight.
-template <int T, int L0, typename ST>
+// has retired (or abandoned behind an lgkmcnt(0)) whatever the pipe had in flight.  XM: that of the segment's next_a -- the
+// entries whose chunk the other waves read ahead from wait for the next chunk here too ("wait next" is every wave's duty).
+template <int T, int L0, typename ST, int XM = 0>
 __device__ __forceinline__ void skip_units(ST& st, int c0 = -1) {
     static_assert(PG_SPREAD_DMA, "the bulk enter() refills by itself");
-    constexpr int PER = ST::PER, PSTRIDE = UPC / PER;
+    static_assert(!(XM & XM_HANDS_ON) || T % UPC == 0, "the next segment starts a chunk");
 #pragma unroll
     for (int L = L0; L < T; ++L) {
         const int q = L % UPC;
-        if (q == 0) st.enter_split(c0 >= 0 && ST::plain_ok(c0 + L / UPC));
-        if (q % PSTRIDE == PG_DMA_PHASE) st.piece(q / PSTRIDE);
+        if (q == 0) {
+            const bool plain = c0 >= 0 && ST::plain_ok(c0 + L / UPC);
+            st.enter_split(plain, ST::AHEAD && (XM & XM_IN_SEGMENT) != 0 && (L + UPC < T || (XM & XM_HANDS_ON) != 0) ? ST::WAIT_NEXT : 0);
+        }
+        if (piece_at<ST, XM>(q) >= 0) st.piece(piece_at<ST, XM>(q));
         if (L == T - 1)
-            for (int i = (q < PG_DMA_PHASE ? 0 : (q - PG_DMA_PHASE) / PSTRIDE + 1); i < PER; ++i) st.piece(i);
+            for (int i = pieces_from<ST, XM>(q); i < ST::PER; ++i) st.piece(i);
     }
 }
 

@@ -55,9 +55,16 @@ template <> struct Op16<f16x8> {
     }
 };
 
-using StreamR = Stream<NWAVE, pgp::R::NCHUNK, PG_DMA_WAVES, pgp::R::NLIMB, 0, pgp::R::C_L5X>;
+// The A pipe of the hidden layers runs across chunk entries (next_a XM, Stream AHEAD_); -DPG_NO_AHEAD: it restarts behind every
+// entry and the refill pieces are spread over the chunk, as in the other kernels
+#if defined(PG_NO_AHEAD)
+constexpr bool R_AHEAD = false;
+#else
+constexpr bool R_AHEAD = true;
+#endif
+using StreamR = Stream<NWAVE, pgp::R::NCHUNK, PG_DMA_WAVES, pgp::R::NLIMB, 0, pgp::R::C_L5X, -1, R_AHEAD>;
 // on-chip variant (no per-ray records in HBM): the limb chunks of the view layer's direction weights sit behind layer 0
-using StreamRO = Stream<NWAVE, pgp::R::NCHUNK_OC, PG_DMA_WAVES, pgp::R::NLIMB, 0, pgp::R::C_L5X_OC, pgp::R::C_Y>;
+using StreamRO = Stream<NWAVE, pgp::R::NCHUNK_OC, PG_DMA_WAVES, pgp::R::NLIMB, 0, pgp::R::C_L5X_OC, pgp::R::C_Y, R_AHEAD>;
 // where the ring bookkeeping of a chunk entry is static (Stream::plain_ok): not where a maskable chunk or the wrap is within reach
 static_assert(StreamRO::plain_ok(14) && StreamRO::plain_ok(30) && !StreamRO::plain_ok(31) && StreamRO::plain_ok(42) && StreamRO::plain_ok(49) &&
               !StreamRO::plain_ok(50) && StreamRO::plain_ok(13) && !StreamRO::plain_ok(5) && !StreamRO::plain_ok(2), "on-chip stream");
@@ -106,11 +113,11 @@ __device__ __forceinline__ void dma_piece(const uint8_t* src, uint32_t lds_dst, 
 }
 
 // one k-unit (two B fragments, one per column tile) against NO out tiles of a k-major segment
-template <typename V, int NO, int T, int NS, typename ST>
+template <typename V, int NO, int T, int XM = 0, int NS, typename ST>
 __device__ __forceinline__ void mma_row16(f32x4 (*acc)[2], APipe<V, NS>& p, ST& st, int uu, V b0, V b1) {
 #pragma unroll
     for (int o = 0; o < NO; ++o) {
-        const V av = next_a<V, T, true, NS>(p, st, uu * NO + o);
+        const V av = next_a<V, T, true, NS, ST, XM>(p, st, uu * NO + o);
         acc[o][0] = Op16<V>::mfma(av, b0, acc[o][0]);
         acc[o][1] = Op16<V>::mfma(av, b1, acc[o][1]);
     }
@@ -165,7 +172,8 @@ __device__ __forceinline__ void x_segment16(f32x4 (*acc)[2], ST& st, const float
 #endif
 #pragma clang loop unroll(full)
     for (int pr = 0; pr < JG / 2; ++pr) {
-        mma_row16<V, NT16, T>(acc, p, st, XV16 + pr, xdir[pr][0], xdir[pr][1]);
+        // (XM_FRONT: the segment's last chunk is the one in front of a hidden layer's first -- or of the Y limb chunks)
+        mma_row16<V, NT16, T, XM_FRONT>(acc, p, st, XV16 + pr, xdir[pr][0], xdir[pr][1]);
         if (!hooked) { hook(); hooked = true; }
     }
 #if defined(PG_STAMPS)
@@ -340,15 +348,16 @@ struct BiasPipe {
     // (opaque BEFORE the tile offset is added: made opaque behind the add, hipcc formed the ten bases of a pass ahead of the pass
     // loop and carried them through it -- ten registers, or scratch -- where one add per layer does)
     __device__ __forceinline__ BiasPipe(unsigned bbase, int tile0) { asm volatile("" : "+v"(bbase)); base = bbase + tile0 * 64; }
-    __device__ __forceinline__ void fetch(int k) {          // tile0 + k, k < 16 (constant after unrolling)
+    __device__ __forceinline__ void fetch(int k) {          // tile0 + k, k <= 16: the layer's tiles and the first one of the layer behind it (constant after unrolling)
         switch (k) {
 #define PG_BIAS_CASE(K) case K: asm volatile("ds_read_b128 %0, %1 offset:0+" #K "*64" : "=v"(r) : "v"(base)); break;
             PG_BIAS_CASE(0) PG_BIAS_CASE(1) PG_BIAS_CASE(2) PG_BIAS_CASE(3) PG_BIAS_CASE(4) PG_BIAS_CASE(5) PG_BIAS_CASE(6) PG_BIAS_CASE(7)
-            PG_BIAS_CASE(8) PG_BIAS_CASE(9) PG_BIAS_CASE(10) PG_BIAS_CASE(11) PG_BIAS_CASE(12) PG_BIAS_CASE(13) PG_BIAS_CASE(14) PG_BIAS_CASE(15)
+            PG_BIAS_CASE(8) PG_BIAS_CASE(9) PG_BIAS_CASE(10) PG_BIAS_CASE(11) PG_BIAS_CASE(12) PG_BIAS_CASE(13) PG_BIAS_CASE(14) PG_BIAS_CASE(15) PG_BIAS_CASE(16)
 #undef PG_BIAS_CASE
             default: __builtin_unreachable();
         }
     }
+    __device__ __forceinline__ void next_layer() { base += NT16 * 64; }        // (a tile fetched for that layer stays what it is)
     __device__ __forceinline__ f32x4 take() { lds_landed(r); return __builtin_bit_cast(f32x4, r); }
 };
 
@@ -373,19 +382,29 @@ static_assert(PG_R_BIAS_AT <= HU16 - 3, "the bias fetch needs two more retires o
 // fout = relu(W fin + b): 16 out tiles of 16 channels, out-tile-major.  The ReLU + 16-bit packing of a finished
 // tile pair (VALU, needs the pair's last MFMA to retire) is placed behind the first MFMAs of the next tile, and the
 // next tile's bias is read mid-tile, so that neither sits at a tile boundary where the matrix pipe would drain.
-template <typename V, typename ST>
-__device__ __forceinline__ void hidden_layer16(const V (*fin)[2], V (*fout)[2], ST& st, unsigned bbase, int tile0, int c0) {
-    APipe<V> p;
-    constexpr int T = HU16 * NT16;
+// XM (next_a): the A pipe `p` runs across the layer's chunk entries and, with XM_HANDS_ON / XM_PRIMED, from a layer into
+// the next one of a run of consecutive layers.  Such a run shares one BiasPipe, moved on by a layer's tiles where a layer takes
+// the pipes over.  A layer that hands them on also fetches the next layer's first bias tile, mid-way through its own last
+// tile: issued behind the reads of the next layer's first units it would be younger than they are, and the retire of the first
+// of them would not cover it.
+// C0 = the layer's first chunk in the stream: an entry taken with reads in flight must be straight-line, i.e. its ring
+// bookkeeping static (Stream::plain_ok) -- advance() has scalar conditionals, and hipcc copies a register whose hand-issued load
+// is in flight where it crosses a branch merge.
+template <typename V, int XM, int C0, typename ST>
+__device__ __forceinline__ void hidden_layer16(const V (*fin)[2], V (*fout)[2], ST& st, APipe<V>& p, BiasPipe& bp) {
+    constexpr int T = HU16 * NT16, c0 = C0;
+    static_assert(!(ST::AHEAD && (XM & XM_IN_SEGMENT)) || (ST::plain_ok(C0) && ST::plain_ok(C0 + 1) && ST::plain_ok(C0 + 2) && ST::plain_ok(C0 + 3) && T == 4 * pgp::R::UPC),
+                  "the entries of a layer whose pipe runs across them are straight-line");
+    constexpr bool PRIMED = ST::AHEAD && (XM & XM_PRIMED) != 0, ON = ST::AHEAD && (XM & XM_HANDS_ON) != 0;
     f32x4 lo0, lo1, hi0, hi1;
-    BiasPipe bp(bbase, tile0);
-    bp.fetch(0);
+    if ((XM & XM_PRIMED) != 0) bp.next_layer();     // the run's bias pipe, whether or not the reads run across (PG_NO_AHEAD)
+    if (!PRIMED) bp.fetch(0);
 #pragma unroll
     for (int o = 0; o < NT16; ++o) {
         f32x4 acc0, acc1;
 #pragma unroll
         for (int u = 0; u < HU16; ++u) {
-            const V av = next_a<V, T, true, PG_PIPE_H>(p, st, o * HU16 + u, c0);
+            const V av = next_a<V, T, true, PG_PIPE_H, ST, XM>(p, st, o * HU16 + u, c0);
             if (u == 0) acc0 = acc1 = bp.take();
             acc0 = Op16<V>::mfma(av, fin[u][0], acc0);
             acc1 = Op16<V>::mfma(av, fin[u][1], acc1);
@@ -395,7 +414,7 @@ __device__ __forceinline__ void hidden_layer16(const V (*fin)[2], V (*fout)[2], 
                 fout[o / 2 - 1][1] = relu_pack16<V>(lo1, hi1, true);
                 if (PG_PIN_TILE) __builtin_amdgcn_sched_barrier(0);
             }
-            if (u == PG_R_BIAS_AT && o + 1 < NT16) bp.fetch(o + 1);     // in front of the next unit's next_a
+            if (u == PG_R_BIAS_AT && (o + 1 < NT16 || ON)) bp.fetch(o + 1);     // in front of the next unit's next_a
         }
         if (o & 1) { hi0 = acc0; hi1 = acc1; } else { lo0 = acc0; lo1 = acc1; }
     }
@@ -465,7 +484,14 @@ __global__ __launch_bounds__(NTHR, 2) void eval16r_kernel(const EvalArgs a) {
     const float* stage = reinterpret_cast<const float*>(smem + LDSR_STAGE);
 
     for (int i = tid; i < BIAS16_FLOATS; i += NTHR) bias[i] = a.bias[i];
-    const float tlv = a.tau_v * 1.4426950408889634f, tld = a.tau_d * 1.4426950408889634f;
+    // (wave-uniform and live through the whole kernel: held in scalar registers, the vector file is full)
+    // (by asm: hipcc folds the builtin away on a value it knows to be uniform, and keeps the vector register; volatile: it stays
+    // here, in front of the first divergent branch, where every lane holds the value.  The wait states are hipcc's own on gfx950,
+    // which it does not insert around inline asm: one between a VALU write of a VGPR and a v_readlane / v_readfirstlane of it --
+    // directly behind the multiply the asm read the register's OLD value, log2 e itself, i.e. tau = 1 -- and two between a VALU
+    // write of an SGPR and a VALU read of it; tools/audit_asm_hazards.py checks both.)
+    auto uniform = [](float x) { float s; asm volatile("s_nop 0\n\tv_readfirstlane_b32 %0, %1\n\ts_nop 1" : "=s"(s) : "v"(x)); return s; };
+    const float tlv = uniform(a.tau_v * 1.4426950408889634f), tld = uniform(a.tau_d * 1.4426950408889634f);
     // by joint SLOT (pg_layout.h slot16_joint): the folded sigmoid constants of both embedders, and the squared distance
     // beyond which a joint's cutoff weight 1 / (1 + 2^(v tl + cs)) is below 2^-24
     if (tid < 48) cut[tid] = -a.cutoff[(tid < J ? 0 : J) + slot_joint_dev(tid < J ? tid : tid - J)] * (tid < J ? tlv : tld);
@@ -542,8 +568,15 @@ __global__ __launch_bounds__(NTHR, 2) void eval16r_kernel(const EvalArgs a) {
 #if defined(PG_STAMPS)
     unsigned long long stamps[16];          // 12 .. 15: inside the two x phases (x_segment16 xst)
 #define PG_XSTAMPS(k) (stamps + (k))
+    // the A pipe's restarts (Stream::restart_stamp) inside layers 1-4 [0] and layers 6-7 [1]: cycles and entries
+    unsigned long long rst_t[2];
+    unsigned rst_n[2];
+#define PG_RST_OPEN(k) do { rst_t[k] = st.t_rst; rst_n[k] = st.n_rst; } while (0)
+#define PG_RST_CLOSE(k) do { rst_t[k] = st.t_rst - rst_t[k]; rst_n[k] = st.n_rst - rst_n[k]; } while (0)
 #else
 #define PG_XSTAMPS(k) nullptr
+#define PG_RST_OPEN(k) do {} while (0)
+#define PG_RST_CLOSE(k) do {} while (0)
 #endif
 #if defined(PG_WALK_STAMPS)
     // how even the walk is (tools/diag_pass_walk.py): the workgroup's clock at entry and exit, its passes and its limbs in range
@@ -659,8 +692,14 @@ __global__ __launch_bounds__(NTHR, 2) void eval16r_kernel(const EvalArgs a) {
             if (FC) y_code16<V>(reinterpret_cast<const float*>(smem + LDSR_YC + abuf * LDSR_YC_BYTES), smem + LDSR_Y, nrm1, wave * 64 + lane_p);
         }
         PG_STAMP(2);
+        PG_RST_OPEN(0);
         // ---- layers 1..4 ----
-        hidden_layer16<V>(fa, fb, st, bbase, BS_LAYER0 + 1 * NT16, C_L1);
+        // The A pipe runs across the chunk entries inside a layer, and from layer 2 into 3 into 4 and from 6 into 7 (XM_HANDS_ON ->
+        // XM_PRIMED).  Not from layer 1 into 2: the on-chip form's rows of the next pass lie in between, with branches of their own.
+        constexpr int XM_H = XM_IN_SEGMENT;
+        APipe<V> ph;
+        BiasPipe bp1(bbase, BS_LAYER0 + 1 * NT16);
+        hidden_layer16<V, XM_H, C_L1>(fa, fb, st, ph, bp1);
         if constexpr (OC) {
             // The NEXT pass's (a, b) rows from the staged rays.  The fetch was issued in layer 0's first chunk, possibly
             // between that chunk's refill pieces: the counted wait of the SECOND entry behind it covers it, and that
@@ -681,9 +720,11 @@ __global__ __launch_bounds__(NTHR, 2) void eval16r_kernel(const EvalArgs a) {
                        reinterpret_cast<float4*>(smem + LDSR_AB + (abuf ^ 1) * LDS_AB_BYTES + k * REC_AB_BYTES + sl * 32));
             }
         }
-        hidden_layer16<V>(fb, fa, st, bbase, BS_LAYER0 + 2 * NT16, C_L1 + CH);
-        hidden_layer16<V>(fa, fb, st, bbase, BS_LAYER0 + 3 * NT16, C_L1 + 2 * CH);
-        hidden_layer16<V>(fb, fa, st, bbase, BS_LAYER0 + 4 * NT16, C_L1 + 3 * CH);
+        BiasPipe bp2(bbase, BS_LAYER0 + 2 * NT16);
+        hidden_layer16<V, XM_H | XM_HANDS_ON, C_L1 + CH>(fb, fa, st, ph, bp2);
+        hidden_layer16<V, XM_H | XM_PRIMED | XM_HANDS_ON, C_L1 + 2 * CH>(fa, fb, st, ph, bp2);
+        hidden_layer16<V, XM_H | XM_PRIMED, C_L1 + 3 * CH>(fb, fa, st, ph, bp2);
+        PG_RST_CLOSE(0);
         PG_STAMP(3);
         {   // ---- layer 5: [x(432), h4(256)] -> 256 (skip connection, nerf.py:99-101) ----
             f32x4 acc[NT16][2];
@@ -708,8 +749,11 @@ __global__ __launch_bounds__(NTHR, 2) void eval16r_kernel(const EvalArgs a) {
                 for (int c = 0; c < 2; ++c) fb[u][c] = relu_pack16<V>(acc[2 * u][c], acc[2 * u + 1][c], true);
         }
         PG_STAMP(4);
-        hidden_layer16<V>(fb, fa, st, bbase, BS_LAYER0 + 6 * NT16, C_L6);
-        hidden_layer16<V>(fa, fb, st, bbase, BS_LAYER0 + 7 * NT16, C_L6 + CH);
+        PG_RST_OPEN(1);
+        BiasPipe bp6(bbase, BS_LAYER0 + 6 * NT16);
+        hidden_layer16<V, XM_H | XM_HANDS_ON, C_L6>(fb, fa, st, ph, bp6);
+        hidden_layer16<V, XM_H | XM_PRIMED, C_L6 + CH>(fa, fb, st, ph, bp6);
+        PG_RST_CLOSE(1);
         PG_STAMP(5);
         // the NEXT pass's limb mask, from its (a, b) records (in LDS since this pass's second chunk entry): the ring's
         // prefetch pointer wraps to the head of the stream two chunk entries from here and must know it by then
@@ -826,13 +870,18 @@ __global__ __launch_bounds__(NTHR, 2) void eval16r_kernel(const EvalArgs a) {
         {   // kept: the stamps of 1024 passes spread evenly over the launch (tools/diag_stamps.py)
             const int every = max(1, a.n_iters / 1024), slot = it / every;
             if (a.dbg && a.dbg_stage == 99 && lane == 0 && slot * every == it && slot < 1024) {
-                unsigned long long* rec = reinterpret_cast<unsigned long long*>(a.dbg) + ((long long)slot * NWAVE + wave) * 16;
+                unsigned long long* rec = reinterpret_cast<unsigned long long*>(a.dbg) + ((long long)slot * NWAVE + wave) * 24;
                 for (int k = 0; k < 9; ++k) rec[k] = stamps[k];
                 rec[9] = st.t_vm; rec[10] = st.t_bar;
                 rec[11] = stamps[11];           // in front of y_segment16
                 for (int k = 12; k < 16; ++k) rec[k] = stamps[k];
+                // the A pipe's restarts behind chunk entries: every next_a entry of the pass, layers 1-4, layers 6-7 (cycles, entries)
+                rec[16] = st.t_rst; rec[17] = st.n_rst;
+                rec[18] = rst_t[0]; rec[19] = rst_n[0];
+                rec[20] = rst_t[1]; rec[21] = rst_n[1];
+                rec[22] = rec[23] = 0;
             }
-            st.t_vm = 0; st.t_bar = 0;
+            st.t_vm = 0; st.t_bar = 0; st.t_rst = 0; st.n_rst = 0u;
         }
 #endif
     }

@@ -30,6 +30,12 @@ Fifth check: "SALU writes M0 -> an LDS-DMA instruction (global_load_lds_* / buff
 M0) reads it" needs one wait state on gfx9-family parts (LLVM: hasReadM0LdsDmaHazard).  hipcc pads its own LDS-DMA issues,
 not an inline-asm `s_mov_b32 m0, ..` directly followed by the load in the same statement.  The audit fails on any LDS-DMA
 instruction with no wait state between it and the last write of M0, in every kernel (not only the MFMA ones).
+
+Sixth check: two wait-state rules of the gfx940 family around lane reads (LLVM: VALUWriteVGPRReadlaneRead = 1,
+VALUWriteSGPRVALURead = 2), which hipcc keeps for its own instructions and not around inline asm: an inline-asm `v_readlane` /
+`v_readfirstlane` directly behind the VALU instruction that wrote its source VGPR reads the register's old value (pg_eval16r.hip:
+tau log2 e read as log2 e, the limb masks of a whole launch off in some workgroups), and a VALU instruction that reads, as an
+operand, an SGPR an inline-asm VALU instruction wrote fewer than two wait states before may read it stale.
 usage: audit_asm_hazards.py kernel.s"""
 import re
 import sys
@@ -164,6 +170,42 @@ def mfma_valu_hazards(kernel_text):
     return hits
 
 
+def lane_read_hazards(kernel_text):
+    """inline-asm v_readlane / v_readfirstlane with no wait state behind the VALU write of its source VGPR; VALU reads of an SGPR
+    that an inline-asm VALU instruction wrote fewer than two wait states before"""
+    hits = []
+    prev_vdst = set()           # VGPRs the VALU instruction in the slot right in front wrote
+    asm_sgpr = []               # (wait states ago, SGPRs written by an inline-asm VALU instruction)
+    in_asm = False
+    for ln in kernel_text.split("\n"):
+        if "#ASMSTART" in ln:
+            in_asm = True
+            continue
+        if "#ASMEND" in ln:
+            in_asm = False
+            continue
+        code = ln.split(";")[0].strip()
+        if not code or code.startswith(".") or code.endswith(":"):
+            continue
+        toks = [t for t in re.split(r"[,\s]+", code) if t]
+        lane_read = toks[0].startswith(("v_readlane", "v_readfirstlane"))
+        if in_asm and lane_read and len(toks) > 2 and vregs(toks[2]) & prev_vdst:
+            hits.append(code)
+        if code.startswith("v_") and not lane_read:
+            srcs = set()
+            for t in toks[2:]:
+                srcs |= sregs(t)
+            if any(age < 2 and regs & srcs for age, regs in asm_sgpr):
+                hits.append(code)
+        m = re.match(r"s_nop\s+(\d+)", code)
+        states = int(m.group(1)) + 1 if m else 1
+        asm_sgpr = [(a + states, r) for a, r in asm_sgpr if a + states < 2]
+        if in_asm and lane_read and len(toks) > 1:
+            asm_sgpr.append((0, sregs(toks[1])))
+        prev_vdst = vregs(toks[1]) if code.startswith("v_") and not lane_read and len(toks) > 1 else set()
+    return hits
+
+
 LDS_DMA = re.compile(r"(?:global|buffer|flat|scratch)_load_lds_\w+|buffer_load_\w+\s.*\blds\b")
 M0_WRITE = re.compile(r"s_\w+\s+m0\s*,|v_readfirstlane_b32\s+m0\s*,|v_readlane_b32\s+m0\s*,")
 
@@ -221,5 +263,9 @@ for k in re.split(r'\n(?=_Z\w+:)', txt):
     for t in mh[:5]:
         print(f"   inline-asm VALU instruction reads an MFMA result too early: {t}")
     bad += len(mh)
+    lh = lane_read_hazards(k)
+    for t in lh[:5]:
+        print(f"   lane read without its wait states around inline asm: {t}")
+    bad += len(lh)
 print("HAZARD AUDIT", "FAILED" if bad else "OK", bad)
 sys.exit(1 if bad else 0)

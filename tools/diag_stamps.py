@@ -17,6 +17,10 @@ from posegen_amd import surreal_config, synthetic as syn
 from posegen_amd.raycaster import HipRayCaster
 
 SLOTS = 1024
+WORDS = 24                                              # 64-bit words of one wave's record of a pass
+# The A pipe's restart behind a chunk entry: barrier release -> retire of the entry's first A fragment (Stream::restart_stamp),
+# summed per wave and pass; record words (cycles, entries) of every next_a entry of the pass, of layers 1-4 and of layers 6-7
+RESTARTS = (("every segment", 16, 17), ("L1-4", 18, 19), ("L6-7", 20, 21))
 # stamp order in a pass: 0 | prologue | 1 | layer 0 (x) | 11 | Y limb chunks (on-chip form) | 2 | layers 1-4 | 3 | layer 5 | 4 | ..
 ORDER = [0, 1, 11, 2, 3, 4, 5, 6, 7, 8]
 # (stamp 6 sits behind the eight view tiles since the empty-wave skip: the row in front of it is the alpha tile AND the view tiles'
@@ -43,6 +47,7 @@ def table(full, label):
         lo, hi = d[:, :4, k].mean(), d[:, 4:, k].mean()
         per = f"{m / MFMA[k]:6.1f} cyc/mfma" if MFMA[k] else ""
         print(f"{name:18s} {m:9.0f} cycles {100 * m / tot.mean():5.1f}%   waves 0-3 {lo:8.0f}  waves 4-7 {hi:8.0f}  {per}")
+    restart_rows(full, tot.mean())
     # the Y segment by passes with and without a limb in range (no limb: the segment is two stamps apart)
     y = d[:, :, 2].max(1)
     has = y > 300
@@ -50,6 +55,16 @@ def table(full, label):
         print(f"Y limb chunks: {100 * has.mean():.1f}% of the passes have a limb in range; there {d[has][:, :, 2].mean():.0f} cycles per pass "
               f"(slowest wave {y[has].mean():.0f}), elsewhere {d[~has][:, :, 2].mean() if (~has).any() else 0:.0f}")
     x_rows(full, has if has.any() else None)
+
+
+def restart_rows(full, tot):
+    if not (full[:, :, 17] != 0).all():
+        print("chunk-entry restart: this build has no restart stamps")
+        return
+    for name, wt, wn in RESTARTS:
+        t, n = full[:, :, wt].astype(np.float64), full[:, :, wn].astype(np.float64)
+        print(f"chunk-entry restart, {name:13s} {t.mean():7.0f} cycles {100 * t.mean() / tot:5.2f}%   {n.mean():5.1f} entries, {t.sum() / n.sum():6.1f} cycles each   "
+              f"waves 0-3 {t[:, :4].mean():7.0f}  waves 4-7 {t[:, 4:].mean():7.0f}   by wave {t.mean(0).astype(int).tolist()}")
 
 
 def x_rows(full, has):
@@ -89,10 +104,10 @@ def main():
     ex = r.render_rays(rb, skts, cyl, n_samples=cfg.n_samples, n_importance=cfg.n_importance, want_alpha=False, extras=True)["extras"]
     for which, z, label in ((0, ex["z_coarse"], "coarse"), (1, ex["z_fine"], "fine")):
         for rep in range(2):
-            dbg = torch.zeros(SLOTS * 8 * 16, device=dev, dtype=torch.int64)
+            dbg = torch.zeros(SLOTS * 8 * WORDS, device=dev, dtype=torch.int64)
             r.stage_eval(which, rb, z, skts, dbg_stage=99, dbg=dbg)
         torch.cuda.synchronize()
-        table(dbg.cpu().numpy().reshape(SLOTS, 8, 16), f"{a.form} form, {a.prec}, {label} launch (S = {z.shape[1]})")
+        table(dbg.cpu().numpy().reshape(SLOTS, 8, WORDS), f"{a.form} form, {a.prec}, {label} launch (S = {z.shape[1]})")
     r.close()
 
 
