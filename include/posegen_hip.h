@@ -781,6 +781,32 @@ typedef struct pg_body_model {
 int pg_smpl_forward(pg_handle* h, void* stream, const pg_body_model* m, int64_t B, const float* betas, int64_t betas_stride,
                     const float* pose, int pose_is_rotmat, const float* regress, int K, float* verts, float* joints, float* regressed);
 
+/* The transpose of pg_smpl_forward for the same inputs: the gradients that the reference gets by autograd through
+ * smplx.lbs.lbs and vertices2joints.  The forward is computed again from (betas, pose), nothing is kept between calls.
+ *   betas, betas_stride, pose, pose_is_rotmat, regress, K   as for pg_smpl_forward
+ *   blend_t      device [3V, 1+NB+207] float32: m->blend transposed, built once per model by the caller; NULL: the kernel reads
+ *                m->blend strided (slow, the same sums)
+ *   d_verts      device [B,V,3], d_joints device [B,24,3], d_regressed device [B,K,3] float32: the cotangents of the forward's three
+ *                outputs; any may be NULL (zero), not all three; d_regressed requires K > 0 and regress
+ *   d_betas      device [B,NB] float32, ALWAYS one row per pose (with betas_stride = 0 the caller adds the rows); may be NULL
+ *   d_pose       device [B,24,3] (axis-angle: the derivative of batch_rodrigues exactly as written, angle = |r + 1e-8|, in float64,
+ *                finite at r = 0) or [B,24,3,3] (pose_is_rotmat: the nine entries of every matrix are free variables, as in
+ *                pg_pose_kinematics_rot_bwd; joint 0's matrix gets no pose-feature term); may be NULL, not both outputs
+ * Per 64-vertex tile v_posed again (the forward's GEMM), dv = d_verts + regress^T d_regressed, d v_posed = T_R^T dv,
+ * dA += skin (dv (x) [v_posed; 1]) and d feat += blend d v_posed, all on v_mfma_f32_16x16x4_f32: one tile is added in float32, tiles
+ * in float64 in tile order per vertex chunk (min(tiles, 64) chunks, a function of V alone).  A closing kernel, float64, one wave per
+ * pose: the chunks in chunk order, d_joints, A = [G_R | G_t - G_R J] undone, the chain walked back, dJ into d_betas through
+ * rest_joints, the d feat rows, Rodrigues; rounded to float32 once.  With d_joints alone no vertex-tile kernel is launched.
+ * Asynchronous on `stream`; no atomics, every sum in a fixed order: two calls give the same bytes, and a pose's rows are the same
+ * bytes whatever B is and wherever the pose sits.  A non-finite value in one pose's input or cotangent stays in that pose's rows.
+ * Workspace: the handle's grow-only buffer, at most 96 MiB plus the carving's alignment (a pose and chunk leave 512 doubles; a long
+ * batch is walked in slices inside the call, each a whole number of rounds of one workgroup per CU where the batch is that long).
+ * PG_EINVAL, nothing launched and nothing written: the cases of pg_smpl_forward (its outputs' cases apart); all three cotangents
+ * NULL; d_regressed with K = 0; both outputs NULL. */
+int pg_smpl_backward(pg_handle* h, void* stream, const pg_body_model* m, int64_t B, const float* betas, int64_t betas_stride,
+                     const float* pose, int pose_is_rotmat, const float* regress, int K, const float* blend_t, const float* d_verts,
+                     const float* d_joints, const float* d_regressed, float* d_betas, float* d_pose);
+
 /* Mesh errors per pose: per_pose[b] = mean_v |a[b,v] - b[b,v]|, the `ume` / `pme` lines of evaluate.test (run_gan.py:1630-1631).
  *   a, b device [B,V,3] float32; per_pose device [B] float64; summary device [2] float64 = B, the mean of per_pose (may be NULL)
  * float64 arithmetic, ordered sums, no atomics; a non-finite coordinate makes its own pose NaN and the mean with it.

@@ -195,6 +195,8 @@ PROTOTYPES = {
                                  C.POINTER(C.c_double), C.c_int, C.c_void_p, _FP, _FP, C.c_void_p]),
     "pg_smpl_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(PgBodyModel), C.c_int64, _FP, C.c_int64, _FP, C.c_int, _FP, C.c_int,
                                   _FP, _FP, _FP]),
+    "pg_smpl_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(PgBodyModel), C.c_int64, _FP, C.c_int64, _FP, C.c_int, _FP, C.c_int,
+                                   _FP, _FP, _FP, _FP, _FP, _FP]),
     "pg_vertex_errors": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, _FP, _FP, C.c_void_p, C.c_void_p]),
     "pg_pose_kinematics_rot": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _FP, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_void_p,
                                          C.c_void_p, C.c_void_p]),

@@ -13,6 +13,7 @@
 //                        vertices in float32; everything above that is added in double, in tile order, per vertex chunk.
 //   smpl_regress_sum   : the chunks' doubles added in chunk order, rounded to float32 once.
 //   vertex_err_kernel, vertex_err_mean, kin_rot_kernel: one wave per pose, float64.
+//   smpl_body_bwd_kernel, smpl_close_kernel: the transpose of the body (pg_smpl_backward), described where they stand.
 // The vertex range is cut into 64-vertex tiles and min(tiles, 256) chunks (chunk c owns tiles c, c + chunks, ..): a function of V
 // only.  A pose is a row of the first two MFMAs and three columns of the third, so its bytes do not depend on the batch around it.
 // No atomics, no loop that depends on a value of the data.
@@ -424,6 +425,499 @@ __global__ __launch_bounds__(THREADS) void kin_rot_kernel(const KinConst kc, con
     }
 }
 
+// ---- the transpose of the body -------------------------------------------------------------------------------------
+//   smpl_body_bwd_kernel : the forward's tiling.  Per 64-vertex tile: v_posed again (the forward's blend GEMM, the same bytes); the
+//                          vertex cotangent dv = d_verts + regress^T d_regressed (an MFMA over the regressor rows); T again and
+//                          d v_posed = T_R^T dv; dA[pose, entry; joint] += skin (dv (x) [v_posed; 1]) (an MFMA over the tile's
+//                          vertices, rows = 16 poses x one entry of the 3 x 4); d feat[pose, k] += blend[k, :] d v_posed (an MFMA
+//                          over the tile's 192 columns, B from blend_t, or from blend strided).  One tile is added in float32
+//                          inside the MFMAs; tiles are added in double, in tile order, per vertex chunk.
+//   smpl_close_kernel    : one wave per pose, lane = joint, float64.  The chunks' partials in chunk order, d_joints into the
+//                          translation cotangent of G, A = [G_R | G_t - G_R J] undone, the chain walked back level by level in LDS
+//                          (as kin_bwd_kernel, pg_kploss.hip), dJ into d_betas through rest_joints, the d feat rows for beta and
+//                          R_j - I, Rodrigues transposed or the nine entries; rounded to float32 once.
+constexpr int BWD_MAX_CHUNKS = 64;           // a pose and chunk leave BWD_PART doubles, ten times the forward's partials
+constexpr int BWD_PART = NJ * 12 + KP_MAX;   // dA [24][12], then d feat [224]
+constexpr size_t BWD_WS_TARGET = (size_t)96 << 20;
+constexpr int LDR = MAX_K + 4;               // row stride of the d_regressed tile: lanes (l & 15, l >> 4) on 64 different banks
+constexpr int FCT = (KP_MAX / 16 + WAVES - 1) / WAVES;   // d feat column tiles of a wave
+
+struct BwdArgs {
+    const float* blend;          // [K, 3V]
+    const float* blend_t;        // [3V, K] or null
+    const float* skin;           // [V, 24]
+    const float* regress;        // [KR, V]
+    const float* feat;           // [n, KP]
+    const float* A;              // [n, 24, 12]
+    const float* d_verts;        // [n, V, 3] or null
+    const float* d_reg;          // [n, KR, 3] or null (KR = 0)
+    double* part;                // [chunks, n, BWD_PART]
+    long long n;
+    int V, K, KP, KR, chunks, tiles;
+};
+
+__global__ __launch_bounds__(THREADS) void smpl_body_bwd_kernel(BwdArgs a) {
+    __shared__ float sf[PT * LDF];
+    __shared__ float sv[PT * LDV];               // v_posed
+    __shared__ float sd[PT * LDV];               // dv
+    __shared__ float sp[PT * LDV];               // d v_posed
+    __shared__ float sr[3 * PT * LDR];           // d_regressed: row (pose, xyz), column = regressor row
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l15 = lane & 15, l4 = lane >> 4;
+    const long long pose0 = (long long)blockIdx.y * PT;
+    const int V = a.V, KP = a.KP, KR = a.KR;
+    const size_t ncol = (size_t)3 * V;
+
+    for (int i0 = tid; i0 < PT * KP; i0 += THREADS * 8) {
+        float fv[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int i = i0 + u * THREADS, row = i / KP;
+            fv[u] = (i < PT * KP && pose0 + row < a.n) ? a.feat[(size_t)pose0 * KP + i] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int i = i0 + u * THREADS, row = i / KP;
+            if (i < PT * KP) sf[row * LDF + (i - row * KP)] = fv[u];
+        }
+    }
+    if (KR > 0) {
+        for (int i = tid; i < 3 * PT * MAX_K; i += THREADS) {
+            const int jj = i / MAX_K, k = i - jj * MAX_K, p = jj / 3, c = jj - p * 3;
+            sr[jj * LDR + k] = (k < KR && pose0 + p < a.n) ? a.d_reg[((size_t)(pose0 + p) * KR + k) * 3 + c] : 0.f;
+        }
+    }
+    __syncthreads();
+
+    double accA[6][2][4], accF[FCT][2][4];
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) accA[i][t][r] = 0.0;
+#pragma unroll
+    for (int i = 0; i < FCT; ++i)
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) accF[i][m][r] = 0.0;
+
+    for (int tile = blockIdx.x; tile < a.tiles; tile += a.chunks) {
+        const int v0 = tile * VT;
+        // ---- (a) v_posed[32 poses, the wave's 48 columns]: the forward's blend GEMM, step for step ----
+        {
+            f32x4 acc[2][3];
+#pragma unroll
+            for (int m = 0; m < 2; ++m)
+#pragma unroll
+                for (int t = 0; t < 3; ++t) acc[m][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+            const size_t c0 = (size_t)3 * v0 + w * 48 + l15;
+            for (int k0 = 0; k0 < KP; k0 += 32) {
+                float b[8][3];
+#pragma unroll
+                for (int s = 0; s < 8; ++s) {
+                    const int kk = k0 + 4 * s + l4;
+#pragma unroll
+                    for (int t = 0; t < 3; ++t) {
+                        const size_t col = c0 + t * 16;
+                        b[s][t] = (kk < a.K && col < ncol) ? a.blend[(size_t)kk * ncol + col] : 0.f;
+                    }
+                }
+#pragma unroll
+                for (int s = 0; s < 8; ++s) {
+                    const int kk = k0 + 4 * s + l4;
+                    const float a0 = kk < KP ? sf[l15 * LDF + kk] : 0.f, a1 = kk < KP ? sf[(16 + l15) * LDF + kk] : 0.f;
+#pragma unroll
+                    for (int t = 0; t < 3; ++t) {
+                        acc[0][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b[s][t], acc[0][t], 0, 0, 0);
+                        acc[1][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b[s][t], acc[1][t], 0, 0, 0);
+                    }
+                }
+            }
+#pragma unroll
+            for (int m = 0; m < 2; ++m)
+#pragma unroll
+                for (int t = 0; t < 3; ++t)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) sv[(m * 16 + l4 * 4 + r) * LDV + w * 48 + t * 16 + l15] = acc[m][t][r];
+        }
+        // the tile of d_verts: a pose's 192 values are contiguous (zero past the last vertex, past the last pose, or without d_verts)
+        for (int i0 = tid; i0 < PT * 3 * VT; i0 += THREADS * 8) {
+            float dvv[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int i = i0 + u * THREADS, p = i / (3 * VT);
+                const size_t col = (size_t)3 * v0 + (i - p * 3 * VT);
+                dvv[u] = (a.d_verts && pose0 + p < a.n && col < ncol) ? a.d_verts[(size_t)(pose0 + p) * ncol + col] : 0.f;
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int i = i0 + u * THREADS, p = i / (3 * VT);
+                sd[p * LDV + (i - p * 3 * VT)] = dvv[u];
+            }
+        }
+        __syncthreads();
+
+        const int v = v0 + w * 16 + l15;                 // the wave's own 16 vertices, as in the forward
+        const bool vlive = v < V;
+        // ---- (b) dv += regress^T d_regressed: rows (pose, xyz), columns the wave's vertices, k over the regressor rows ----
+        if (KR > 0) {
+            float rb[MAX_K / 4];
+#pragma unroll
+            for (int s = 0; s < MAX_K / 4; ++s) rb[s] = (4 * s + l4 < KR && vlive) ? a.regress[(size_t)(4 * s + l4) * V + v] : 0.f;
+#pragma unroll
+            for (int nt = 0; nt < 6; ++nt) {
+                f32x4 d = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int s = 0; s < MAX_K / 4; ++s)
+                    if (4 * s < KR) d = __builtin_amdgcn_mfma_f32_16x16x4f32(sr[(nt * 16 + l15) * LDR + 4 * s + l4], rb[s], d, 0, 0, 0);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int jj = nt * 16 + l4 * 4 + r, jb = jj / 3, jc = jj - jb * 3;
+                    sd[jb * LDV + 3 * (w * 16 + l15) + jc] += d[r];
+                }
+            }
+            __syncthreads();
+        }
+
+        // ---- (c) T = sum_j skin[v,j] A_j as in the forward; d v_posed = T_R^T dv ----
+        {
+            float sk[NJ / 4];
+#pragma unroll
+            for (int ks = 0; ks < NJ / 4; ++ks) sk[ks] = vlive ? a.skin[(size_t)v * NJ + 4 * ks + l4] : 0.f;
+            for (int pb = 0; pb < PT / 4; ++pb) {
+                const long long apose = pose0 + 4 * pb + (l15 >> 2);
+                const bool alive = apose < a.n;
+                const float* Ar = a.A + (size_t)(alive ? apose : 0) * (NJ * 12) + 12 * l4 + (l15 & 3);
+                const int at = (4 * pb + l4) * LDV + 3 * (w * 16 + l15);
+                float g0 = 0.f, g1 = 0.f, g2 = 0.f;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    f32x4 T = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int ks = 0; ks < NJ / 4; ++ks)
+                        T = __builtin_amdgcn_mfma_f32_16x16x4f32(alive ? Ar[48 * ks + 4 * c] : 0.f, sk[ks], T, 0, 0, 0);
+                    const float dvc = sd[at + c];
+                    g0 = fmaf(T[0], dvc, g0); g1 = fmaf(T[1], dvc, g1); g2 = fmaf(T[2], dvc, g2);
+                }
+                sp[at] = vlive ? g0 : 0.f; sp[at + 1] = vlive ? g1 : 0.f; sp[at + 2] = vlive ? g2 : 0.f;
+            }
+        }
+        __syncthreads();
+
+        // ---- (d) dA: row tile = (entry of the 3 x 4, 16 poses), the wave's six; columns = joints; k over the tile's vertices ----
+        {
+            float skb[VT / 4][2];
+#pragma unroll
+            for (int s = 0; s < VT / 4; ++s)
+#pragma unroll
+                for (int t = 0; t < 2; ++t) {
+                    const int vv = v0 + 4 * s + l4, j = t * 16 + l15;
+                    skb[s][t] = (vv < V && j < NJ) ? a.skin[(size_t)vv * NJ + j] : 0.f;
+                }
+#pragma unroll
+            for (int i = 0; i < 6; ++i) {
+                const int rt = w * 6 + i, e = rt >> 1, er = e >> 2, ec = e & 3;
+                const int base = ((rt & 1) * 16 + l15) * LDV + 3 * l4;
+                f32x4 d0 = f32x4{0.f, 0.f, 0.f, 0.f}, d1 = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int s = 0; s < VT / 4; ++s) {
+                    const float x = sd[base + 12 * s + er] * (ec < 3 ? sv[base + 12 * s + ec] : 1.f);
+                    d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(x, skb[s][0], d0, 0, 0, 0);
+                    d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(x, skb[s][1], d1, 0, 0, 0);
+                }
+#pragma unroll
+                for (int r = 0; r < 4; ++r) { accA[i][0][r] += (double)d0[r]; accA[i][1][r] += (double)d1[r]; }
+            }
+        }
+
+        // ---- (e) d feat: rows = poses, columns = blend rows (the wave's tiles w, w + 4, ..), k over the tile's 192 columns ----
+        {
+            f32x4 acc[FCT][2];
+#pragma unroll
+            for (int i = 0; i < FCT; ++i) { acc[i][0] = f32x4{0.f, 0.f, 0.f, 0.f}; acc[i][1] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+            for (int s0 = 0; s0 < 3 * VT / 4; s0 += 8) {
+                float b[8][FCT];
+#pragma unroll
+                for (int s = 0; s < 8; ++s) {
+                    const size_t col = (size_t)3 * v0 + 4 * (s0 + s) + l4;
+#pragma unroll
+                    for (int i = 0; i < FCT; ++i) {
+                        const int k = (w + WAVES * i) * 16 + l15;
+                        b[s][i] = (k < a.K && col < ncol) ? (a.blend_t ? a.blend_t[col * a.K + k] : a.blend[(size_t)k * ncol + col]) : 0.f;
+                    }
+                }
+#pragma unroll
+                for (int s = 0; s < 8; ++s) {
+                    const float a0 = sp[l15 * LDV + 4 * (s0 + s) + l4], a1 = sp[(16 + l15) * LDV + 4 * (s0 + s) + l4];
+#pragma unroll
+                    for (int i = 0; i < FCT; ++i)
+                        if ((w + WAVES * i) * 16 < KP_MAX) {
+                            acc[i][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b[s][i], acc[i][0], 0, 0, 0);
+                            acc[i][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b[s][i], acc[i][1], 0, 0, 0);
+                        }
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < FCT; ++i)
+#pragma unroll
+                for (int m = 0; m < 2; ++m)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) accF[i][m][r] += (double)acc[i][m][r];
+        }
+        __syncthreads();
+    }
+
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        const int rt = w * 6 + i, e = rt >> 1;
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int j = t * 16 + l15;
+                const long long pose = pose0 + (rt & 1) * 16 + l4 * 4 + r;
+                if (j < NJ && pose < a.n) a.part[((size_t)blockIdx.x * a.n + pose) * BWD_PART + j * 12 + e] = accA[i][t][r];
+            }
+    }
+#pragma unroll
+    for (int i = 0; i < FCT; ++i) {
+        const int k = (w + WAVES * i) * 16 + l15;
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const long long pose = pose0 + m * 16 + l4 * 4 + r;
+                if (k < KP_MAX && pose < a.n) a.part[((size_t)blockIdx.x * a.n + pose) * BWD_PART + NJ * 12 + k] = accF[i][m][r];
+            }
+    }
+}
+
+struct CloseArgs {
+    const float* betas;
+    long long betas_stride;
+    const float* pose;
+    const double* rest;          // [1 + NB, 24, 3]
+    const double* part;          // [chunks, n, BWD_PART] (chunks = 0: no vertex-tile kernel ran)
+    const float* d_joints;       // [n, 24, 3] or null
+    float* d_betas;              // [n, NB] or null
+    float* d_pose;               // [n, 24, 3] or [n, 24, 3, 3], or null
+    long long n;
+    int is_rotmat, NB, chunks, depth;
+    int parent[NJ], level[NJ];
+};
+
+__global__ __launch_bounds__(THREADS) void smpl_close_kernel(CloseArgs a) {
+    __shared__ double rel[WAVES][NJ][12], l2w[WAVES][NJ][12], Gc[WAVES][NJ][12];
+    __shared__ double sJ[WAVES][NJ][3], sfe[WAVES][KP_MAX];
+    __shared__ int spar[NJ], slev[NJ];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (threadIdx.x < NJ) { spar[threadIdx.x] = a.parent[threadIdx.x]; slev[threadIdx.x] = a.level[threadIdx.x]; }
+    long long pose = (long long)blockIdx.x * WAVES + w;
+    const bool live = pose < a.n;                       // the whole wave
+    if (!live) pose = a.n - 1;                          // walks the last pose again and writes nothing
+    const bool jl = lane < NJ;
+    const int j = jl ? lane : 0;
+    const int par = a.parent[j], lev = a.level[j];
+    const float* bp = a.betas + pose * a.betas_stride;
+
+    // 1. the forward in double, as smpl_pre_kernel: rest joints, R, the relative transform [R | J - J_parent]
+    double Jr[3], Jp[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        Jr[c] = a.rest[j * 3 + c];
+        Jp[c] = par >= 0 ? a.rest[par * 3 + c] : 0.0;
+    }
+    for (int l = 0; l < a.NB; ++l) {
+        const double b = (double)bp[l];
+        const double* rl = a.rest + (size_t)(1 + l) * NJ * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            Jr[c] += b * rl[j * 3 + c];
+            if (par >= 0) Jp[c] += b * rl[par * 3 + c];
+        }
+    }
+    double M[12], Km[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    double rv[3] = {0.0, 0.0, 0.0}, angle = 1.0, sn = 0.0, cs = 1.0;
+    if (a.is_rotmat) {
+        const float* rp = a.pose + ((size_t)pose * NJ + j) * 9;
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) M[4 * r + c] = (double)rp[3 * r + c];
+    } else {
+        const float* rp = a.pose + ((size_t)pose * NJ + j) * 3;
+        rv[0] = (double)rp[0]; rv[1] = (double)rp[1]; rv[2] = (double)rp[2];
+        const double e0 = rv[0] + 1e-8, e1 = rv[1] + 1e-8, e2 = rv[2] + 1e-8;
+        angle = sqrt(e0 * e0 + e1 * e1 + e2 * e2);
+        const double x = rv[0] / angle, y = rv[1] / angle, z = rv[2] / angle;
+        sn = sin(angle); cs = cos(angle);
+        Km[1] = -z; Km[2] = y; Km[3] = z; Km[5] = -x; Km[6] = -y; Km[7] = x;
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const double kk = Km[3 * r] * Km[c] + Km[3 * r + 1] * Km[3 + c] + Km[3 * r + 2] * Km[6 + c];
+                M[4 * r + c] = (r == c ? 1.0 : 0.0) + sn * Km[3 * r + c] + (1.0 - cs) * kk;
+            }
+    }
+#pragma unroll
+    for (int r = 0; r < 3; ++r) M[4 * r + 3] = Jr[r] - Jp[r];
+    if (jl) {
+#pragma unroll
+        for (int e = 0; e < 12; ++e) rel[w][j][e] = M[e];
+        if (lev == 0) {
+#pragma unroll
+            for (int e = 0; e < 12; ++e) l2w[w][j][e] = M[e];
+        }
+    }
+    __syncthreads();
+    for (int d = 1; d <= a.depth; ++d) {
+        if (jl && lev == d) {
+            const double* P = l2w[w][par];
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+                const double a0 = P[4 * r], a1 = P[4 * r + 1], a2 = P[4 * r + 2], a3 = P[4 * r + 3];
+#pragma unroll
+                for (int c = 0; c < 4; ++c) l2w[w][j][4 * r + c] = a0 * M[c] + a1 * M[4 + c] + a2 * M[8 + c] + (c == 3 ? a3 : 0.0);
+            }
+        }
+        __syncthreads();
+    }
+
+    // 2. the chunks' partials in chunk order: dA of the lane's joint, d feat four columns a lane
+    double dA[12];
+#pragma unroll
+    for (int e = 0; e < 12; ++e) dA[e] = 0.0;
+    for (int k = lane; k < KP_MAX; k += 64) {
+        double s = 0.0;
+        for (int c = 0; c < a.chunks; ++c) s += a.part[((size_t)c * a.n + pose) * BWD_PART + NJ * 12 + k];
+        sfe[w][k] = s;
+    }
+    if (jl) {
+        for (int c = 0; c < a.chunks; ++c) {
+            const double* p = a.part + ((size_t)c * a.n + pose) * BWD_PART + j * 12;
+#pragma unroll
+            for (int e = 0; e < 12; ++e) dA[e] += p[e];
+        }
+    }
+
+    // 3. A = [G_R | G_t - G_R J] undone: dG_R = dA_R - dA_t (x) J, dG_t = dA_t + d_joints, dJ = -G_R^T dA_t
+    double dJ[3] = {0.0, 0.0, 0.0};
+    if (jl) {
+        const double* G = l2w[w][j];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            const double t = dA[4 * r + 3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                Gc[w][j][4 * r + c] = dA[4 * r + c] - t * Jr[c];
+                dJ[c] -= G[4 * r + c] * t;
+            }
+            Gc[w][j][4 * r + 3] = t + (a.d_joints ? (double)a.d_joints[((size_t)pose * NJ + j) * 3 + r] : 0.0);
+        }
+    }
+    __syncthreads();
+    // 4. the chain backwards, children before parents, a parent collecting its children in joint order
+    for (int d = a.depth; d >= 1; --d) {
+        if (jl && lev == d - 1) {
+            double acc[12];
+#pragma unroll
+            for (int e = 0; e < 12; ++e) acc[e] = Gc[w][j][e];
+            for (int c = j + 1; c < NJ; ++c) {
+                if (spar[c] != j) continue;
+                const double* g = Gc[w][c];
+                const double* L = rel[w][c];
+#pragma unroll
+                for (int r = 0; r < 3; ++r) {
+                    const double g0 = g[4 * r], g1 = g[4 * r + 1], g2 = g[4 * r + 2], g3 = g[4 * r + 3];
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) acc[4 * r + k] += g0 * L[4 * k] + g1 * L[4 * k + 1] + g2 * L[4 * k + 2] + g3 * L[4 * k + 3];
+                    acc[4 * r + 3] += g3;
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < 12; ++e) Gc[w][j][e] = acc[e];
+        }
+        __syncthreads();
+    }
+    // 5. the cotangent of the relative transform: G_parent_R^T dG (the root's parent is the identity); its column 3 is d(J - J_parent)
+    double D[12];
+    if (lev == 0) {
+#pragma unroll
+        for (int e = 0; e < 12; ++e) D[e] = Gc[w][j][e];
+    } else {
+        const double* P = l2w[w][par];
+        const double* g = Gc[w][j];
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) D[4 * k + c] = P[k] * g[c] + P[4 + k] * g[4 + c] + P[8 + k] * g[8 + c];
+    }
+    __syncthreads();                                    // every lane has read l2w and Gc: rel's rows now carry d(J - J_parent)
+    if (jl) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { rel[w][j][c] = D[4 * c + 3]; dJ[c] += D[4 * c + 3]; }
+    }
+    __syncthreads();
+    if (jl) {
+        for (int c = j + 1; c < NJ; ++c) {
+            if (spar[c] != j) continue;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) dJ[k] -= rel[w][c][k];
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) sJ[w][j][c] = dJ[c];
+    }
+    __syncthreads();
+    if (!live) return;
+
+    // 6. d_betas: the d feat row of beta_l plus dJ through rest_joints[1 + l]
+    if (a.d_betas && lane < a.NB) {
+        double s = sfe[w][1 + lane];
+        const double* rl = a.rest + (size_t)(1 + lane) * NJ * 3;
+        for (int q = 0; q < NJ * 3; ++q) s += rl[q] * sJ[w][q / 3][q - (q / 3) * 3];
+        a.d_betas[(size_t)pose * a.NB + lane] = (float)s;
+    }
+    if (!a.d_pose || !jl) return;
+    // 7. dR: the chain's plus, for joints 1.., the d feat rows of R_j - I; the nine entries, or through batch_rodrigues as written
+    double dR[9];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) dR[3 * r + c] = D[4 * r + c] + (j >= 1 ? sfe[w][1 + a.NB + (j - 1) * 9 + 3 * r + c] : 0.0);
+    if (a.is_rotmat) {
+        float* dst = a.d_pose + ((size_t)pose * NJ + j) * 9;
+#pragma unroll
+        for (int e = 0; e < 9; ++e) dst[e] = (float)dR[e];
+        return;
+    }
+    // R = I + sin K + (1 - cos) K K, K = skew(r / angle), angle = |r + 1e-8|
+    const double oc = 1.0 - cs;
+    double dK[9], dth = 0.0;
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            // (D K^T + K^T D)[r][c] = sum_k D[r][k] K[c][k] + K[k][r] D[k][c]
+            double t = 0.0, kk = 0.0;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                t += dR[3 * r + k] * Km[3 * c + k] + Km[3 * k + r] * dR[3 * k + c];
+                kk += Km[3 * r + k] * Km[3 * k + c];
+            }
+            dK[3 * r + c] = sn * dR[3 * r + c] + oc * t;
+            dth += dR[3 * r + c] * (cs * Km[3 * r + c] + sn * kk);
+        }
+    const double dd[3] = {dK[7] - dK[5], dK[2] - dK[6], dK[3] - dK[1]};
+    dth -= (dd[0] * rv[0] + dd[1] * rv[1] + dd[2] * rv[2]) / (angle * angle);
+    float* dst = a.d_pose + ((size_t)pose * NJ + j) * 3;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) dst[c] = (float)(dd[c] / angle + dth * (rv[c] + 1e-8) / angle);
+}
+
 }  // namespace pgsm
 
 // ---- the host side --------------------------------------------------------------------------------------------------------------------
@@ -532,6 +1026,101 @@ extern "C" int pg_smpl_forward(pg_handle* h, void* stream, const pg_body_model* 
                                st, d_part, per_chunk, chunks, regressed + (size_t)b0 * KR * 3);
             PG_LAUNCH_CHECK(h, "body model regressor sum kernel");
         }
+    }
+    return PG_OK;
+}
+
+extern "C" int pg_smpl_backward(pg_handle* h, void* stream, const pg_body_model* m, int64_t B, const float* betas, int64_t betas_stride,
+                                const float* pose, int pose_is_rotmat, const float* regress, int K, const float* blend_t,
+                                const float* d_verts, const float* d_joints, const float* d_regressed, float* d_betas, float* d_pose) {
+    const char* who = "pg_smpl_backward";
+    if (!h) return pg_fail(nullptr, PG_EINVAL, "null handle");
+    if (!m || !betas || !pose) return pg_fail(h, PG_EINVAL, "%s: model, betas and pose are required", who);
+    if (!d_verts && !d_joints && !d_regressed) return pg_fail(h, PG_EINVAL, "%s: no cotangent given", who);
+    if (!d_betas && !d_pose) return pg_fail(h, PG_EINVAL, "%s: no output asked for", who);
+    if (B < 1) return pg_fail(h, PG_EINVAL, "%s: B = %lld", who, (long long)B);
+    if (m->NB < 1 || m->NB > pgsm::MAX_NB) return pg_fail(h, PG_EINVAL, "%s: NB = %d is outside [1, %d]", who, m->NB, pgsm::MAX_NB);
+    const int rows = 1 + m->NB + pgsm::POSE_ROWS;
+    if (m->V < 1 || (long long)rows * 3 * (long long)m->V >= (1ll << 31))
+        return pg_fail(h, PG_EINVAL, "%s: V = %d (at least 1, and %d blend rows of 3 V below 2^31 elements)", who, m->V, rows);
+    if (!m->blend || !m->skin || !m->rest_joints) return pg_fail(h, PG_EINVAL, "%s: the model has a NULL array", who);
+    if (K < 0 || K > pgsm::MAX_K) return pg_fail(h, PG_EINVAL, "%s: K = %d is outside [0, %d]", who, K, pgsm::MAX_K);
+    if (K > 0 && !regress) return pg_fail(h, PG_EINVAL, "%s: K = %d without regress", who, K);
+    if (d_regressed && K == 0) return pg_fail(h, PG_EINVAL, "%s: d_regressed given with K = 0", who);
+    if (betas_stride != 0 && betas_stride != m->NB)
+        return pg_fail(h, PG_EINVAL, "%s: betas_stride = %lld (NB = %d, or 0 for one row)", who, (long long)betas_stride, m->NB);
+    const int depth = tree_depth(m->parents);
+    if (depth < 0) return pg_fail(h, PG_EINVAL, "%s: parents[0] must be -1 and every joint must come after its parent", who);
+
+    const int V = m->V, KP = (rows + 3) & ~3;
+    const int KR = d_regressed ? K : 0;
+    const bool body = d_verts || d_regressed;            // with d_joints alone no vertex-tile kernel runs
+    const int tiles = (V + pgsm::VT - 1) / pgsm::VT;
+    const int chunks = !body ? 0 : tiles < pgsm::BWD_MAX_CHUNKS ? tiles : pgsm::BWD_MAX_CHUNKS;
+    const size_t per_pose = body ? ((size_t)KP + pgsm::NJ * 12) * sizeof(float) + (size_t)chunks * pgsm::BWD_PART * sizeof(double) : 0;
+    // the poses of one slice: what keeps the workspace at BWD_WS_TARGET, in whole pose tiles, at least one; the kernel's LDS admits one
+    // workgroup per CU, so a slice of more workgroups than CUs is cut to a whole number of rounds of them
+    long long S = body ? (long long)(pgsm::BWD_WS_TARGET / per_pose) / pgsm::PT * pgsm::PT : B;
+    if (S < pgsm::PT) S = pgsm::PT;
+    if (S > 4096 && body) S = 4096;
+    if (body) {
+        const long long wgs = S / pgsm::PT * chunks, cus = h->n_cu > 0 ? h->n_cu : 256;
+        const long long whole = wgs / cus * cus / chunks;          // pose tiles of the whole rounds
+        if (whole >= 1) S = whole * pgsm::PT;
+    }
+    if (S > B) S = B;
+
+    PG_HIP(h, hipSetDevice(h->device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    float *d_feat = nullptr, *d_A = nullptr;
+    double* d_part = nullptr;
+    if (body) {
+        if (!h->smpl) h->smpl = new SmplState();
+        auto* s = static_cast<SmplState*>(h->smpl);
+        auto carve = [&](Carver& c) {
+            d_part = c.take<double>((size_t)chunks * S * pgsm::BWD_PART);
+            d_feat = c.take<float>((size_t)S * KP);
+            d_A = c.take<float>((size_t)S * pgsm::NJ * 12);
+        };
+        Carver count, real;
+        carve(count);
+        PG_TRY(pg_grow(h, s->ws, count.off, "body model workspace"));
+        real.base = s->ws.p;
+        carve(real);
+    }
+    int level[pgsm::NJ] = {0};
+    for (int j = 1; j < pgsm::NJ; ++j) level[j] = level[m->parents[j]] + 1;
+
+    for (long long b0 = 0; b0 < B; b0 += S) {
+        const long long n = B - b0 < S ? B - b0 : S;
+        const float* sl_betas = betas + b0 * betas_stride;
+        const float* sl_pose = pose + (size_t)b0 * pgsm::NJ * (pose_is_rotmat ? 9 : 3);
+        if (body) {
+            pgsm::PreArgs pa{};
+            pa.betas = sl_betas; pa.betas_stride = betas_stride; pa.pose = sl_pose;
+            pa.rest = m->rest_joints; pa.feat = d_feat; pa.A = d_A; pa.joints = nullptr;
+            pa.n = n; pa.is_rotmat = pose_is_rotmat ? 1 : 0; pa.NB = m->NB; pa.K = rows; pa.KP = KP; pa.depth = depth;
+            for (int j = 0; j < pgsm::NJ; ++j) pa.parent[j] = m->parents[j];
+            hipLaunchKernelGGL(pgsm::smpl_pre_kernel, dim3((unsigned)((n + pgsm::WAVES - 1) / pgsm::WAVES)), dim3(pgsm::THREADS), 0, st, pa);
+            PG_LAUNCH_CHECK(h, "body model pose kernel");
+            pgsm::BwdArgs ba{};
+            ba.blend = m->blend; ba.blend_t = blend_t; ba.skin = m->skin; ba.regress = regress; ba.feat = d_feat; ba.A = d_A;
+            ba.d_verts = d_verts ? d_verts + (size_t)b0 * V * 3 : nullptr;
+            ba.d_reg = d_regressed ? d_regressed + (size_t)b0 * KR * 3 : nullptr;
+            ba.part = d_part; ba.n = n; ba.V = V; ba.K = rows; ba.KP = KP; ba.KR = KR; ba.chunks = chunks; ba.tiles = tiles;
+            hipLaunchKernelGGL(pgsm::smpl_body_bwd_kernel, dim3((unsigned)chunks, (unsigned)((n + pgsm::PT - 1) / pgsm::PT)), dim3(pgsm::THREADS),
+                               0, st, ba);
+            PG_LAUNCH_CHECK(h, "body model backward kernel");
+        }
+        pgsm::CloseArgs ca{};
+        ca.betas = sl_betas; ca.betas_stride = betas_stride; ca.pose = sl_pose; ca.rest = m->rest_joints; ca.part = d_part;
+        ca.d_joints = d_joints ? d_joints + (size_t)b0 * pgsm::NJ * 3 : nullptr;
+        ca.d_betas = d_betas ? d_betas + (size_t)b0 * m->NB : nullptr;
+        ca.d_pose = d_pose ? d_pose + (size_t)b0 * pgsm::NJ * (pose_is_rotmat ? 9 : 3) : nullptr;
+        ca.n = n; ca.is_rotmat = pose_is_rotmat ? 1 : 0; ca.NB = m->NB; ca.chunks = chunks; ca.depth = depth;
+        for (int j = 0; j < pgsm::NJ; ++j) { ca.parent[j] = m->parents[j]; ca.level[j] = level[j]; }
+        hipLaunchKernelGGL(pgsm::smpl_close_kernel, dim3((unsigned)((n + pgsm::WAVES - 1) / pgsm::WAVES)), dim3(pgsm::THREADS), 0, st, ca);
+        PG_LAUNCH_CHECK(h, "body model backward closing kernel");
     }
     return PG_OK;
 }

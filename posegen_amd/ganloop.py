@@ -13,6 +13,7 @@ device.  The caster comes from `load_raycaster` (memoised: no checkpoint reload 
 """
 from __future__ import annotations
 
+import math
 from typing import Optional, Tuple
 
 import numpy as np
@@ -139,3 +140,17 @@ def regressor_loss(renderer, pred_rotmat: torch.Tensor, gt: torch.Tensor, gt_is_
             gt = renderer.pose_kinematics(gt, smpl_rest_pose.astype(np.float32) * np.float32(0.4))[0]
     return pose_losses.pose_loss(pred_kps, gt.detach(), joints=pose_eval.GAN_LOOP_JOINTS, root=0, kind="norm_matched", weight=weight,
                                  cap=cap, renderer=renderer)
+
+
+def regressor_body_loss(body, pred_rotmat: torch.Tensor, pred_betas: torch.Tensor, gt_kps: torch.Tensor, regressor: str, joints=None,
+                        root: int = 0, kind: str = "mpjpe", cap: float = math.inf, weight: float = 1.0) -> torch.Tensor:
+    """The pose loss on the joints the regressor is scored on: `regressor` (a name in `body.regressors`, e.g. the h36m regressor)
+    applied to the body's vertices for `pred_rotmat` [F,24,3,3] and `pred_betas` [F,NB] (or one row), against `gt_kps` [F,K,3] -- the
+    same regressor's joints of the ground-truth body --, rows `joints` (None: H36M_TO_J14) after row `root` (the pelvis) is subtracted:
+    what `evaluate_smpl_predictions` scores as MPJPE (evaluate.test, run_gan.py:1596-1634).  `body.differentiable(...).regressed` into
+    `pose_losses.pose_loss`: a float64 device scalar whose gradients reach `pred_rotmat` (nine free entries a matrix) and `pred_betas`
+    through pg_pose_loss's gradient and one pg_smpl_backward call."""
+    from . import pose_eval, pose_losses
+    pred = body.differentiable(pred_betas, pred_rotmat, pose2rot=False, regressor=regressor, joints=False).regressed
+    return pose_losses.pose_loss(pred, gt_kps.detach(), joints=pose_eval.H36M_TO_J14 if joints is None else joints, root=root, kind=kind,
+                                 weight=weight, cap=cap, renderer=body.renderer)

@@ -7,8 +7,12 @@ blends, skins and regresses in one kernel; vertices reach memory only when they 
 into `pose_eval.PoseScorer`.  There is no torch fallback and no CPU path.
 
 Not built, refused or simply not offered: reading the licensed model .pkl (pass the arrays), SMPL-H / SMPL-X / hands / face /
-landmarks, a joint count other than 24, more than 16 shape coefficients, `transl`, gradients through the body, per-pose model
-selection inside one call, several devices.
+landmarks, a joint count other than 24, more than 16 shape coefficients, `transl`, second derivatives, per-pose model selection
+inside one call, several devices.
+
+Gradients through the body: `BodyModel.differentiable` is `forward` behind a once-differentiable autograd function
+whose backward is one `pg_smpl_backward` call -- the transpose of the same kernels, the forward computed again, into `betas` and
+`pose` (axis-angle through `batch_rodrigues` as written, or the nine free entries of every rotation matrix).
 """
 from __future__ import annotations
 
@@ -18,6 +22,8 @@ from typing import Optional
 
 import numpy as np
 import torch
+
+from torch.autograd.function import once_differentiable
 
 from . import _ffi
 
@@ -161,7 +167,8 @@ class BodyModel:
             if x.is_cuda and x.device != self.device:
                 raise NotImplementedError(f"BodyModel: {who} on {x.device}, the body on {self.device}; several devices are not built")
             if x.requires_grad:
-                raise NotImplementedError(f"BodyModel: {who} requires grad; gradients through the body are not built")
+                raise NotImplementedError(f"BodyModel: {who} requires grad; forward gives no gradients through the body: call "
+                                          "BodyModel.differentiable")
             if not x.dtype.is_floating_point:
                 raise TypeError(f"BodyModel: {who} of dtype {x.dtype}; floating point expected")
             x = x.detach()
@@ -205,10 +212,90 @@ class BodyModel:
 
     __call__ = forward
 
+    def differentiable(self, betas, pose=None, pose2rot=True, regressor: Optional[str] = None, want_vertices=False, joints=True, *,
+                       global_orient=None, body_pose=None, transl=None):
+        """`forward` with gradients: the same BodyOutput, the same bytes, differentiable once in `betas` and `pose` (or
+        `global_orient` and `body_pose`).  The backward is one pg_smpl_backward call; an output that no cotangent reaches is passed as
+        NULL.  Axis-angle poses get the derivative of `batch_rodrigues` as written (finite at a zero vector), rotation matrices a
+        gradient in each of their nine entries.  One betas row for all poses gets the poses' rows added in float64 in pose order,
+        rounded once (B - 1 small additions on the device, one after the other).  `betas` and `pose` must be floating-point tensors on the body's device."""
+        if transl is not None:
+            raise NotImplementedError("BodyModel.differentiable: transl is not built")
+        if pose is None:
+            if global_orient is None or body_pose is None:
+                raise ValueError("BodyModel.differentiable: pose, or global_orient and body_pose")
+            go, bp = self._on_device(global_orient, "global_orient"), self._on_device(body_pose, "body_pose")
+            tail = (3, 3) if not pose2rot else (3,)
+            pose = torch.cat([go.reshape(go.shape[0], -1, *tail), bp.reshape(bp.shape[0], -1, *tail)], dim=1)
+        betas, pose = self._on_device(betas, "betas"), self._on_device(pose, "pose")
+        self._check_inputs(betas, pose, pose2rot, regressor, want_vertices, joints)
+        outs = list(_BodyFn.apply(self, betas, pose, bool(pose2rot), regressor, bool(want_vertices), bool(joints)))
+        return BodyOutput(outs.pop(0) if want_vertices else None, outs.pop(0) if joints else None,
+                          outs.pop(0) if regressor is not None else None)
+
+    def _on_device(self, x, who) -> torch.Tensor:
+        if not torch.is_tensor(x):
+            raise NotImplementedError(f"BodyModel.differentiable: {who} is a host array; a tensor on {self.device} is expected")
+        if x.device != self.device:
+            raise NotImplementedError(f"BodyModel.differentiable: {who} on {x.device}, the body on {self.device}; host tensors and "
+                                      "several devices are not built")
+        if not x.dtype.is_floating_point:
+            raise TypeError(f"BodyModel.differentiable: {who} of dtype {x.dtype}; floating point expected")
+        return x
+
+    def _blend_transposed(self) -> torch.Tensor:
+        """blend as [3V, 1+NB+207], what pg_smpl_backward reads its d feat operand from; made on first use"""
+        if getattr(self, "_blend_t", None) is None:
+            self._blend_t = self._blend.t().contiguous()
+        return self._blend_t
+
     @torch.no_grad()
     def vertex_errors(self, a, b):
         """(per_pose float64 [B], mean float64 scalar) of mean_v |a_v - b_v| (`ume` / `pme`, run_gan.py:1630-1631): device tensors"""
         return vertex_errors(self.renderer, a, b)
+
+
+class _BodyFn(torch.autograd.Function):
+    """pg_smpl_forward / pg_smpl_backward: the outputs that were asked for, in BodyOutput's order"""
+
+    @staticmethod
+    def forward(ctx, body, betas, pose, pose2rot, regressor, want_vertices, joints):
+        f32 = lambda t: t.detach().to(dtype=torch.float32).contiguous()
+        b32, p32 = f32(betas), f32(pose)
+        out = body.forward(b32, p32, pose2rot=pose2rot, regressor=regressor, want_vertices=want_vertices, joints=joints)
+        ctx.body, ctx.saved, ctx.regressor, ctx.pose2rot = body, (b32, p32), regressor, pose2rot
+        ctx.which = [k for k, t in zip(BodyOutput._fields, out) if t is not None]
+        ctx.meta = ((betas.dtype, tuple(betas.shape)), (pose.dtype, tuple(pose.shape)))
+        ctx.set_materialize_grads(False)
+        return tuple(t for t in out if t is not None)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        body, (b32, p32) = ctx.body, ctx.saved
+        need_b, need_p = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        g = {k: None if t is None else t.to(device=body.device, dtype=torch.float32).contiguous() for k, t in zip(ctx.which, grads)}
+        if not (need_b or need_p) or all(t is None for t in g.values()):
+            return (None,) * 7
+        B = p32.shape[0]
+        reg = None if ctx.regressor is None else body.regressors[ctx.regressor]
+        d_betas = torch.empty(B, body.NB, dtype=torch.float32, device=body.device) if need_b else None
+        d_pose = torch.empty_like(p32) if need_p else None
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        r = body.renderer
+        with torch.cuda.device(body.device):
+            r._check(r.lib.pg_smpl_backward(r.handle, r._stream(), C.byref(body._model), B, ptr(b32), body.NB if b32.shape[0] == B and B > 1 else 0,
+                                            ptr(p32), 0 if ctx.pose2rot else 1, ptr(reg), 0 if reg is None else reg.shape[0],
+                                            ptr(body._blend_transposed()), ptr(g.get("vertices")), ptr(g.get("joints")), ptr(g.get("regressed")),
+                                            ptr(d_betas), ptr(d_pose)))
+        (bt, bs), (pt, ps) = ctx.meta
+        if need_b and bs[0] != B:                            # one row for all poses: the rows in pose order, in float64, rounded once
+            rows = d_betas.to(torch.float64)
+            total = rows[0]
+            for i in range(1, B):
+                total = total + rows[i]
+            d_betas = total[None].to(torch.float32)
+        return (None, d_betas.to(bt).reshape(bs) if need_b else None, d_pose.to(pt).reshape(ps) if need_p else None, None, None, None, None)
 
 
 @torch.no_grad()
