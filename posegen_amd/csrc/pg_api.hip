@@ -16,6 +16,7 @@
 #include "../../include/posegen_hip.h"
 #include "pg_device.h"
 #include "pg_handle.h"
+#include "pg_kin.h"
 #include "pg_launch.h"
 #include "pg_pack.h"
 
@@ -1579,11 +1580,12 @@ int pg_pose_kinematics(pg_handle* h, void* stream, int64_t n_poses, const double
     if (!h) return pg_fail(nullptr, PG_EINVAL, "null handle");
     if (n_poses < 0 || !bones || !rest_pose || !parents) return pg_fail(h, PG_EINVAL, "pg_pose_kinematics: null/negative argument");
     if (h->cfg.n_joints != 24) return pg_fail(h, PG_EINVAL, "pg_pose_kinematics: 24-joint SMPL skeleton only");
-    for (int j = 0; j < 24; ++j)
-        if (parents[j] < 0 || parents[j] > j || (j > 0 && parents[j] == j))
-            return pg_fail(h, PG_EINVAL, "pg_pose_kinematics: joint %d must come after its parent (%d)", j, parents[j]);
+    pgkin::KinTree tree;
+    int bad = 0;                        // the root's own entry is 0 here (the skeleton's table)
+    if (parents[0] != 0 || !pgkin::pg_kin_tree(parents, tree, &bad))
+        return pg_fail(h, PG_EINVAL, "pg_pose_kinematics: joint %d must come after its parent (%d)", bad, parents[bad]);
     PG_HIP(h, hipSetDevice(h->device));
-    PG_TRY_LAUNCH(h, "pose kinematics kernel", pg_launch_pose_kinematics(rest_pose, parents, bones, n_poses, kps, skts, l2ws, stream));
+    PG_TRY_LAUNCH(h, "pose kinematics kernel", pg_launch_pose_kinematics(rest_pose, &tree, bones, n_poses, kps, skts, l2ws, stream));
     return PG_OK;
 }
 

@@ -15,86 +15,25 @@
 //   loss_grad_kernel     : the gradients of `loss` at upstream 1 -> d_pred / d_gt [B,J_in,3]; one wave per pose.  Every row is
 //                          written once, by one lane: selected rows get their lane's value by a wave shuffle, the root row minus the
 //                          sum of them, the others and the poses that are not kept zero.
-// float64 arithmetic, outputs rounded once; no atomics, every sum in a fixed order; nothing is kept between calls.
+// float64 arithmetic, outputs rounded once; no atomics, every sum in a fixed order; nothing is kept between calls.  The chain, its
+// transpose and the rotation-vector map with its transpose are pg_kin.h's, shared with the forward kernels they belong to.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <cmath>
 
 #include "pg_handle.h"
+#include "pg_kin.h"
 
 namespace pgkl {
 
-constexpr int NJ = 24;
 constexpr int THREADS = 256;
 constexpr int WAVES = THREADS / 64;
 constexpr int MAXJ = 64;
 
-struct KinConst { double offs[NJ * 3]; int parent[NJ]; int level[NJ]; int depth; };   // parent[root] = -1; level = distance from the root
-
-// the sum over the wave's 64 lanes, the same bits in every lane
-__device__ __forceinline__ double wave_all_sum(double v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
-
-// what the rotation-vector map leaves for its transpose: the unit quaternion, the vector, and the factors of dq -> dr
-struct Quat {
-    double r[3], q[4];       // q = x y z w, normalised
-    double k, nrm, A, Bw;    // q_xyz = r k / nrm;  dk/dr_i = A r_i;  dq_w/dr_i = Bw r_i (before the normalisation)
-};
-
-// pose_kinematics_kernel's map (pg_kernels.hip:664-675): rows 0..2 of [R | .] into rel[0..2][0..2]
-__device__ __forceinline__ void rotvec(const double* __restrict__ b, Quat& s, double rel[12]) {
-    s.r[0] = b[0]; s.r[1] = b[1]; s.r[2] = b[2];
-    const double t2 = s.r[0] * s.r[0] + s.r[1] * s.r[1] + s.r[2] * s.r[2], th = sqrt(t2);
-    const bool small = th < 1e-3;
-    double qw;
-    if (small) {
-        s.k = 0.5 - t2 / 48.0 + t2 * t2 / 3840.0;
-        s.A = 2.0 * (-1.0 / 48.0 + t2 / 1920.0);
-        s.Bw = 2.0 * (-1.0 / 8.0 + t2 / 192.0);
-        qw = cos(0.5 * th);                                 // (the series 1 - t/8 + t^2/384 to below 1e-22: the forward's value)
-    } else {
-        const double sh = sin(0.5 * th);
-        qw = cos(0.5 * th);
-        s.k = sh / th;
-        s.A = (0.5 * qw * th - sh) / (t2 * th);             // k'(theta) / theta
-        s.Bw = -0.5 * s.k;
-    }
-    double qx = s.r[0] * s.k, qy = s.r[1] * s.k, qz = s.r[2] * s.k;
-    s.nrm = sqrt(qx * qx + qy * qy + qz * qz + qw * qw);
-    qx /= s.nrm; qy /= s.nrm; qz /= s.nrm; qw /= s.nrm;
-    s.q[0] = qx; s.q[1] = qy; s.q[2] = qz; s.q[3] = qw;
-    const double xx = qx * qx, yy = qy * qy, zz = qz * qz, ww = qw * qw;
-    const double xy = qx * qy, zw = qz * qw, xz = qx * qz, yw = qy * qw, yz = qy * qz, xw = qx * qw;
-    rel[0] = xx - yy - zz + ww; rel[1] = 2.0 * (xy - zw);    rel[2] = 2.0 * (xz + yw);
-    rel[4] = 2.0 * (xy + zw);   rel[5] = -xx + yy - zz + ww; rel[6] = 2.0 * (yz - xw);
-    rel[8] = 2.0 * (xz - yw);   rel[9] = 2.0 * (yz + xw);    rel[10] = -xx - yy + zz + ww;
-}
-
-// the transpose of rotvec: D = the cotangent of R (row-major 3 x 3) -> the cotangent of the rotation vector
-__device__ __forceinline__ void rotvec_bwd(const Quat& s, const double D[9], double o[3]) {
-    const double x = s.q[0], y = s.q[1], z = s.q[2], w = s.q[3];
-    const double s01 = D[1] + D[3], s02 = D[2] + D[6], s12 = D[5] + D[7];
-    const double a21 = D[7] - D[5], a02 = D[2] - D[6], a10 = D[3] - D[1];
-    double dq[4];
-    dq[0] = 2.0 * (x * (D[0] - D[4] - D[8]) + y * s01 + z * s02 + w * a21);
-    dq[1] = 2.0 * (y * (-D[0] + D[4] - D[8]) + x * s01 + z * s12 + w * a02);
-    dq[2] = 2.0 * (z * (-D[0] - D[4] + D[8]) + x * s02 + y * s12 + w * a10);
-    dq[3] = 2.0 * (w * (D[0] + D[4] + D[8]) + x * a21 + y * a02 + z * a10);
-    // q = u / |u|
-    const double t = x * dq[0] + y * dq[1] + z * dq[2] + w * dq[3];
-    double du[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) du[i] = (dq[i] - s.q[i] * t) / s.nrm;
-    // u_xyz = r k(theta), u_w = c(theta)
-    const double dr = du[0] * s.r[0] + du[1] * s.r[1] + du[2] * s.r[2];
-    const double f = s.A * dr + s.Bw * du[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) o[i] = s.k * du[i] + s.r[i] * f;
-}
+using pgkin::KinConst;
+using pgkin::NJ;
+using pgkin::wave_all_sum;
 
 // One wave per pose, lane = joint.  `in`: bones [n,24,3] double (AXIS) or rotmats [n,24,3,3] float; `out`: the same shape and type.
 template <bool AXIS>
@@ -103,7 +42,7 @@ __global__ __launch_bounds__(THREADS) void kin_bwd_kernel(const KinConst kc, con
     __shared__ double rel[WAVES][NJ][12], l2w[WAVES][NJ][12], G[WAVES][NJ][12];
     __shared__ int spar[NJ], slev[NJ];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (threadIdx.x < NJ) { spar[threadIdx.x] = kc.parent[threadIdx.x]; slev[threadIdx.x] = kc.level[threadIdx.x]; }
+    if (threadIdx.x < NJ) { spar[threadIdx.x] = kc.tree.parent[threadIdx.x]; slev[threadIdx.x] = kc.tree.level[threadIdx.x]; }
     long long pose = (long long)blockIdx.x * WAVES + w;
     const bool live = pose < n;
     if (!live) pose = n - 1;                                 // (a wave past the end walks the last pose again and writes nothing)
@@ -112,86 +51,33 @@ __global__ __launch_bounds__(THREADS) void kin_bwd_kernel(const KinConst kc, con
     const size_t at = (size_t)pose * NJ + j;
 
     // 1. the forward: the joint's relative transform, then the chain level by level
-    Quat s;
+    pgkin::Quat s;
     double R[12];
     if constexpr (AXIS) {
-        rotvec(static_cast<const double*>(in) + at * 3, s, R);
+        pgkin::rotvec_to_rows(static_cast<const double*>(in) + at * 3, s, R);
     } else {
-        const float* rp = static_cast<const float*>(in) + at * 9;
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) R[4 * r + c] = (double)rp[3 * r + c];
+        pgkin::rotmat_to_rows(static_cast<const float*>(in) + at * 9, R);
     }
 #pragma unroll
     for (int r = 0; r < 3; ++r) R[4 * r + 3] = kc.offs[3 * j + r];
     __syncthreads();                                         // spar / slev
     const int par = spar[j], lev = slev[j];
-    if (jl) {
+    if (jl) {                                                // the cotangent of the l2w rows: only column 3, the key point, is fed
 #pragma unroll
-        for (int e = 0; e < 12; ++e) { rel[w][j][e] = R[e]; G[w][j][e] = 0.0; }
-        if (lev == 0) {
-#pragma unroll
-            for (int e = 0; e < 12; ++e) l2w[w][j][e] = R[e];
-        }
+        for (int e = 0; e < 12; ++e) G[w][j][e] = 0.0;
 #pragma unroll
         for (int r = 0; r < 3; ++r) G[w][j][4 * r + 3] = (double)d_kps[at * 3 + r];
     }
-    __syncthreads();
-    for (int d = 1; d <= kc.depth; ++d) {
-        if (jl && lev == d) {
-            const double* P = l2w[w][par];
-#pragma unroll
-            for (int r = 0; r < 3; ++r) {
-                const double a0 = P[4 * r], a1 = P[4 * r + 1], a2 = P[4 * r + 2], a3 = P[4 * r + 3];
-#pragma unroll
-                for (int c = 0; c < 4; ++c) l2w[w][j][4 * r + c] = a0 * R[c] + a1 * R[4 + c] + a2 * R[8 + c] + (c == 3 ? a3 : 0.0);
-            }
-        }
-        __syncthreads();
-    }
-    // 2. the chain backwards, children before parents: l2w_c = l2w_p rel_c gives G_p += G_c rel_c^T (rows 0..2; row 3 of rel_c is 0 0 0 1)
-    for (int d = kc.depth; d >= 1; --d) {
-        if (jl && lev == d - 1) {
-            double acc[12];
-#pragma unroll
-            for (int e = 0; e < 12; ++e) acc[e] = G[w][j][e];
-            for (int c = j + 1; c < NJ; ++c) {
-                if (spar[c] != j) continue;
-                const double* g = G[w][c];
-                const double* L = rel[w][c];
-#pragma unroll
-                for (int r = 0; r < 3; ++r) {
-                    const double g0 = g[4 * r], g1 = g[4 * r + 1], g2 = g[4 * r + 2], g3 = g[4 * r + 3];
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) acc[4 * r + k] += g0 * L[4 * k] + g1 * L[4 * k + 1] + g2 * L[4 * k + 2] + g3 * L[4 * k + 3];
-                    acc[4 * r + 3] += g3;
-                }
-            }
-#pragma unroll
-            for (int e = 0; e < 12; ++e) G[w][j][e] = acc[e];
-        }
-        __syncthreads();
-    }
+    pgkin::chain_forward(rel[w], l2w[w], R, j, jl, par, lev, kc.tree.depth);       // (its first barrier covers G)
+    // 2. the chain backwards, children before parents
+    pgkin::chain_backward(G[w], rel[w], spar, j, jl, lev, kc.tree.depth);
     if (!live || !jl) return;
     // 3. dR_j = (l2w_parent^T G_j)[:3,:3] (the root's parent is the identity)
     double D[9];
-    if (lev == 0) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) D[3 * k + c] = G[w][j][4 * k + c];
-    } else {
-        const double* P = l2w[w][par];
-        const double* g = G[w][j];
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) D[3 * k + c] = P[k] * g[c] + P[4 + k] * g[4 + c] + P[8 + k] * g[8 + c];
-    }
+    pgkin::parent_transpose<3>(l2w[w], par, G[w][j], D);
     if constexpr (AXIS) {
         double o[3];
-        rotvec_bwd(s, D, o);
+        pgkin::rotvec_bwd(s, D, o);
         double* dst = static_cast<double*>(out) + at * 3;
         dst[0] = o[0]; dst[1] = o[1]; dst[2] = o[2];
     } else {
@@ -348,21 +234,6 @@ struct KpLossState {
     DevBuf vals;
 };
 
-// fills kc from the host arrays; false for a tree that is not ordered parent before child.  parents[0] is the root's own entry (0 in
-// the skeleton's table, -1 in a body model's): both are taken.
-bool fill_tree(pgkl::KinConst& kc, const double* bone_offsets, const int32_t* parents) {
-    if (parents[0] != 0 && parents[0] != -1) return false;
-    kc.parent[0] = -1; kc.level[0] = 0; kc.depth = 0;
-    for (int j = 1; j < pgkl::NJ; ++j) {
-        if (parents[j] < 0 || parents[j] >= j) return false;
-        kc.parent[j] = parents[j];
-        kc.level[j] = kc.level[parents[j]] + 1;
-        if (kc.level[j] > kc.depth) kc.depth = kc.level[j];
-    }
-    for (int i = 0; i < pgkl::NJ * 3; ++i) kc.offs[i] = bone_offsets[i];
-    return true;
-}
-
 template <bool AXIS>
 int kin_bwd(pg_handle* h, const char* who, void* stream, int64_t n_poses, const void* in, const double* bone_offsets, const int32_t* parents,
             const float* d_kps, void* out) {
@@ -370,8 +241,11 @@ int kin_bwd(pg_handle* h, const char* who, void* stream, int64_t n_poses, const 
     if (n_poses < 0 || !in || !bone_offsets || !parents || !d_kps || !out) return pg_fail(h, PG_EINVAL, "%s: null/negative argument", who);
     if (n_poses > 0x7fffffffll * pgkl::WAVES) return pg_fail(h, PG_EINVAL, "%s: n_poses = %lld", who, (long long)n_poses);
     pgkl::KinConst kc;
-    if (!fill_tree(kc, bone_offsets, parents)) return pg_fail(h, PG_EINVAL, "%s: every joint must come after its parent", who);
+    // the root's own entry: 0 in the skeleton's table, -1 in a body model's, and both are taken
+    if ((parents[0] != 0 && parents[0] != -1) || !pgkin::pg_kin_tree(parents, kc.tree))
+        return pg_fail(h, PG_EINVAL, "%s: every joint must come after its parent", who);
     if (n_poses == 0) return PG_OK;
+    for (int i = 0; i < pgkl::NJ * 3; ++i) kc.offs[i] = bone_offsets[i];
     PG_HIP(h, hipSetDevice(h->device));
     hipLaunchKernelGGL(pgkl::kin_bwd_kernel<AXIS>, dim3((unsigned)((n_poses + pgkl::WAVES - 1) / pgkl::WAVES)), dim3(pgkl::THREADS), 0,
                        static_cast<hipStream_t>(stream), kc, in, (long long)n_poses, d_kps, out);

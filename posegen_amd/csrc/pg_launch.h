@@ -7,6 +7,7 @@
 #include "../../include/posegen_hip.h"
 
 namespace pgd { struct EvalArgs; struct RecArgs; }      // pg_device.h
+namespace pgkin { struct KinTree; }                     // pg_kin.h
 
 namespace pgk {
 
@@ -91,7 +92,7 @@ int pg_launch_mfma_rate(int f16, int lds_fed, int blocks, int iters, float* sink
 int pg_launch_frame_rays(const pgk::FrameGeom* g, long long i0, long long n, float* rays, float* cams, void* stream);
 int pg_launch_frame_compose(const pgk::FrameGeom* g, const float* rgb_map, const float* disp_map, const float* acc_map,
                             const float* bg, float base_bg, float* rgb, float* disp, float* acc, uint8_t* rgb8, void* stream);
-int pg_launch_pose_kinematics(const double* offs72, const int* parents24, const double* bones, long long n,
+int pg_launch_pose_kinematics(const double* offs72, const pgkin::KinTree* tree, const double* bones, long long n,
                               float* kps, float* skts, double* l2ws, void* stream);
 int pg_launch_pose_boxes(const float* kps, long long n, const double* w2c, long long w2c_stride, const double* ring,
                          float ext_r, float ext_top, float ext_bot, double fx, double fy, int H, int W, int offx, int offy,

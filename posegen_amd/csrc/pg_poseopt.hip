@@ -15,16 +15,18 @@
 //   gradients are bitwise repeatable (the rule of sc_partial_kernel / reduce_parts_kernel: fixed order, no atomics).
 //
 // Arithmetic: float64 inside, float32 in and out (rounded once).  One workgroup per pose; the joint tree is walked level by level
-// with the pose's matrices in LDS (lane = joint).  The work is a few hundred poses of 24 joints: its cost is the launch.
+// with the pose's matrices in LDS (lane = joint; chain_forward / chain_backward, pg_kin.h).  The work is a few hundred poses of 24
+// joints: its cost is the launch.
 #include <hip/hip_runtime.h>
 
 #include <vector>
 
 #include "pg_handle.h"
+#include "pg_kin.h"
 
 namespace pgp {
 
-constexpr int NJ = 24;
+using pgkin::NJ;
 constexpr int THREADS = 256;
 constexpr int N_ROT = NJ * 9, N_MAT = NJ * 16, N_KP = NJ * 3;
 constexpr double EPS = 1e-12;          // F.normalize's eps (skeleton_utils.py:520-521)
@@ -59,32 +61,21 @@ __device__ inline void rot6d(const float* __restrict__ x, Rot6& q) {
 }
 
 // Rows 0..2 of every joint's relative transform and of its chain product WITHOUT the pelvis shift (pose_opt.py:399-414), in LDS.
-// Called by every thread of the workgroup (barriers inside); lanes 0..23 are the joints.  parent / depth: LDS copies of the tree.
-__device__ inline void pose_chain(int u, int tid, const float* __restrict__ bones, const float* __restrict__ rest, int rest_stride,
-                                  const int* parent, const int* depth, int max_depth, double (*rel)[12], double (*l2w)[12], Rot6& q) {
-    if (tid < NJ) {
-        rot6d(bones + ((long long)u * NJ + tid) * 6, q);
+// Called by every thread of the workgroup (barriers inside); lanes 0..23 are the joints (j: the thread's, 0 for the others).
+// parent / level: LDS copies of the tree.
+__device__ inline void pose_chain(int u, int j, bool jl, const float* __restrict__ bones, const float* __restrict__ rest, int rest_stride,
+                                  const int* parent, const int* level, int max_depth, double (*rel)[12], double (*l2w)[12], Rot6& q) {
+    const int p = parent[j];
+    double R[12];
+    if (jl) {
+        rot6d(bones + ((long long)u * NJ + j) * 6, q);
         const float* rp = rest + (long long)u * rest_stride;
-        const int p = parent[tid];
-        const bool root = depth[tid] == 0;
         for (int r = 0; r < 3; ++r) {
-            rel[tid][4 * r] = q.b1[r]; rel[tid][4 * r + 1] = q.b2[r]; rel[tid][4 * r + 2] = q.b3[r];
-            rel[tid][4 * r + 3] = root ? (double)rp[3 * tid + r] : (double)rp[3 * tid + r] - (double)rp[3 * p + r];
+            R[4 * r] = q.b1[r]; R[4 * r + 1] = q.b2[r]; R[4 * r + 2] = q.b3[r];
+            R[4 * r + 3] = p < 0 ? (double)rp[3 * j + r] : (double)rp[3 * j + r] - (double)rp[3 * p + r];
         }
-        if (root)
-            for (int e = 0; e < 12; ++e) l2w[tid][e] = rel[tid][e];
     }
-    __syncthreads();
-    for (int d = 1; d <= max_depth; ++d) {
-        if (tid < NJ && depth[tid] == d) {
-            const double* P = l2w[parent[tid]];
-            const double* L = rel[tid];
-            for (int r = 0; r < 3; ++r)
-                for (int c = 0; c < 4; ++c)
-                    l2w[tid][4 * r + c] = P[4 * r] * L[c] + P[4 * r + 1] * L[4 + c] + P[4 * r + 2] * L[8 + c] + (c == 3 ? P[4 * r + 3] : 0.0);
-        }
-        __syncthreads();
-    }
+    pgkin::chain_forward(rel, l2w, R, j, jl, p, level[j], max_depth);
 }
 
 // rows 0..2 of m^-1 for m = [A | t; 0 0 0 1] given as its rows 0..2 (pose_opt.py:435, torch.inverse): [A^-1 | -A^-1 t]
@@ -97,8 +88,8 @@ __device__ inline void inverse_rows(const double* m, double* s) {
     for (int r = 0; r < 3; ++r) s[4 * r + 3] = -(s[4 * r] * m[3] + s[4 * r + 1] * m[7] + s[4 * r + 2] * m[11]);
 }
 
-__device__ inline void load_tree(int tid, const int* __restrict__ tree, int* parent, int* depth) {
-    if (tid < NJ) { parent[tid] = tree[tid]; depth[tid] = tree[NJ + tid]; }
+__device__ inline void load_tree(int tid, const int* __restrict__ tree, int* parent, int* level) {
+    if (tid < NJ) { parent[tid] = tree[tid]; level[tid] = tree[NJ + tid]; }
     __syncthreads();
 }
 
@@ -110,11 +101,13 @@ __global__ __launch_bounds__(THREADS) void poseopt_fwd_kernel(const float* __res
                                                               float* __restrict__ kps) {
     __shared__ double rel[NJ][12], l2w[NJ][12];
     __shared__ float o_rot[N_ROT], o_l2w[N_MAT], o_skt[N_MAT], o_kp[N_KP];
-    __shared__ int parent[NJ], depth[NJ];
+    __shared__ int parent[NJ], level[NJ];
     const int u = blockIdx.x, tid = threadIdx.x;
-    load_tree(tid, tree, parent, depth);
+    const bool jl = tid < NJ;
+    const int j = jl ? tid : 0;
+    load_tree(tid, tree, parent, level);
     Rot6 q;
-    pose_chain(u, tid, bones, rest, rest_stride, parent, depth, max_depth, rel, l2w, q);
+    pose_chain(u, j, jl, bones, rest, rest_stride, parent, level, max_depth, rel, l2w, q);
     if (tid < NJ) {
         double m[12], s[12];
         for (int e = 0; e < 12; ++e) m[e] = l2w[tid][e];
@@ -165,9 +158,11 @@ __global__ __launch_bounds__(THREADS) void poseopt_bwd_kernel(const float* __res
     __shared__ double rel[NJ][12], l2w[NJ][12], G[NJ][12];
     __shared__ double c_rot[N_ROT], c_l2w[N_MAT], c_skt[N_MAT], c_kp[N_KP];
     __shared__ double pel[NJ][3];
-    __shared__ int parent[NJ], depth[NJ];
+    __shared__ int parent[NJ], level[NJ];
     const int u = blockIdx.x, tid = threadIdx.x;
-    load_tree(tid, tree, parent, depth);
+    const bool jl = tid < NJ;
+    const int j = jl ? tid : 0;
+    load_tree(tid, tree, parent, level);
     // 1. the ordered segment sums: one thread per entry
     const int i0 = seg_start[u], i1 = seg_start[u + 1];
     for (int e = tid; e < N_ROT; e += THREADS) c_rot[e] = segment_sum(d_rots, N_ROT, e, seg_rays, i0, i1);
@@ -175,7 +170,7 @@ __global__ __launch_bounds__(THREADS) void poseopt_bwd_kernel(const float* __res
     for (int e = tid; e < N_MAT; e += THREADS) c_skt[e] = segment_sum(d_skts, N_MAT, e, seg_rays, i0, i1);
     for (int e = tid; e < N_KP; e += THREADS) c_kp[e] = segment_sum(d_kps, N_KP, e, seg_rays, i0, i1);
     Rot6 q;
-    pose_chain(u, tid, bones, rest, rest_stride, parent, depth, max_depth, rel, l2w, q);      // (its first barrier covers the sums)
+    pose_chain(u, j, jl, bones, rest, rest_stride, parent, level, max_depth, rel, l2w, q);     // (its first barrier covers the sums)
     if (tid < NJ) {
         // 2. dL2W = -S^T dS S^T (rows 0..2; row 3 of l2w is constant) + d_l2ws, d_kps into column 3
         double m[12], s[12];
@@ -200,28 +195,12 @@ __global__ __launch_bounds__(THREADS) void poseopt_bwd_kernel(const float* __res
         d_pelvis[(long long)u * 3 + tid] = (float)acc;
     }
     // 4. the chain backwards, children before parents: a parent collects its children in joint order
-    for (int d = max_depth; d >= 1; --d) {
-        if (tid < NJ && depth[tid] == d - 1) {
-            for (int j = tid + 1; j < NJ; ++j) {
-                if (parent[j] != tid || depth[j] != d) continue;
-                for (int r = 0; r < 3; ++r) {
-                    const double g0 = G[j][4 * r], g1 = G[j][4 * r + 1], g2 = G[j][4 * r + 2], g3 = G[j][4 * r + 3];
-                    for (int k = 0; k < 3; ++k) G[tid][4 * r + k] += g0 * rel[j][4 * k] + g1 * rel[j][4 * k + 1] + g2 * rel[j][4 * k + 2] + g3 * rel[j][4 * k + 3];
-                    G[tid][4 * r + 3] += g3;
-                }
-            }
-        }
-        __syncthreads();
-    }
+    pgkin::chain_backward(G, rel, parent, j, jl, level[j], max_depth);
     if (tid < NJ) {
         // 5. dR = (l2w_parent^T dL2W)[:3,:3] + d_rots (the root's parent is the identity)
-        double dR[9];
-        const bool root = depth[tid] == 0;
-        const double* P = l2w[parent[tid]];
-        for (int k = 0; k < 3; ++k)
-            for (int c = 0; c < 3; ++c)
-                dR[3 * k + c] = c_rot[9 * tid + 3 * k + c] +
-                                (root ? G[tid][4 * k + c] : P[k] * G[tid][c] + P[4 + k] * G[tid][4 + c] + P[8 + k] * G[tid][8 + c]);
+        double D[9], dR[9];
+        pgkin::parent_transpose<3>(l2w, parent[tid], G[tid], D);
+        for (int e = 0; e < 9; ++e) dR[e] = c_rot[9 * tid + e] + D[e];
         // 6. the columns of R are b1, b2, b3 = b1 x b2
         double g1[3], g2[3], g3[3], t[3];
         for (int i = 0; i < 3; ++i) { g1[i] = dR[3 * i]; g2[i] = dR[3 * i + 1]; g3[i] = dR[3 * i + 2]; }
@@ -249,7 +228,7 @@ struct State {
     std::vector<int32_t> host;
 };
 
-constexpr int TREE_WORDS = 64;         // parent [24] | depth [24] | pad
+constexpr int TREE_WORDS = 64;         // parent [24] (the root's: -1) | level [24] | pad
 
 State* state_of(pg_handle* h) {
     if (!h->poseopt) h->poseopt = new State();
@@ -266,14 +245,12 @@ int check_common(pg_handle* h, const char* who, int64_t n_poses, int rot_dim, co
     if (rest_stride != 0 && rest_stride != NJ * 3)
         return pg_fail(h, PG_EINVAL, "%s: rest_stride must be 0 (one rest pose) or 72 (one per pose), got %lld", who, (long long)rest_stride);
     idx.assign(TREE_WORDS + (size_t)n_poses + 1 + (size_t)n_rays, 0);
-    *max_depth = 0;
-    for (int j = 0; j < NJ; ++j) {
-        if (parents[j] < 0 || parents[j] > j || (j > 0 && parents[j] == j))
-            return pg_fail(h, PG_EINVAL, "%s: joint %d must come after its parent (%d)", who, j, parents[j]);
-        idx[j] = parents[j];
-        idx[NJ + j] = j == 0 ? 0 : idx[NJ + parents[j]] + 1;
-        if (idx[NJ + j] > *max_depth) *max_depth = idx[NJ + j];
-    }
+    pgkin::KinTree kt;
+    int bad = 0;                        // the root's own entry is 0 here (the skeleton's table)
+    if (parents[0] != 0 || !pgkin::pg_kin_tree(parents, kt, &bad))
+        return pg_fail(h, PG_EINVAL, "%s: joint %d must come after its parent (%d)", who, bad, parents[bad]);
+    for (int j = 0; j < NJ; ++j) { idx[j] = kt.parent[j]; idx[NJ + j] = kt.level[j]; }
+    *max_depth = kt.depth;
     return PG_OK;
 }
 

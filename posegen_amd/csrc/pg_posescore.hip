@@ -16,6 +16,7 @@
 #include <stdint.h>
 
 #include "pg_handle.h"
+#include "pg_kin.h"
 #include "pg_pose_align.h"
 
 namespace pgq {
@@ -42,13 +43,7 @@ struct Args {
     double thr[MAXT];
 };
 
-// the sum over the wave's 64 lanes, the same bits in every lane (a + b and b + a are the same number)
-__device__ __forceinline__ double wave_all_sum(double v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
-
+using pgkin::wave_all_sum;
 __global__ __launch_bounds__(THREADS) void pose_scores_kernel(Args a) {
     const int lane = threadIdx.x & 63;
     const long long wave = (long long)blockIdx.x * WAVES + (threadIdx.x >> 6);

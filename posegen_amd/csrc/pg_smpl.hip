@@ -16,11 +16,13 @@
 //   smpl_body_bwd_kernel, smpl_close_kernel: the transpose of the body (pg_smpl_backward), described where they stand.
 // The vertex range is cut into 64-vertex tiles and min(tiles, 256) chunks (chunk c owns tiles c, c + chunks, ..): a function of V
 // only.  A pose is a row of the first two MFMAs and three columns of the third, so its bytes do not depend on the batch around it.
-// No atomics, no loop that depends on a value of the data.
+// No atomics, no loop that depends on a value of the data.  The chain product and its transpose, the Rodrigues pair, the output writer
+// of kin_rot_kernel and the check of a parents table are pg_kin.h's.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "pg_handle.h"
+#include "pg_kin.h"
 
 namespace pgsm {
 
@@ -28,7 +30,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int THREADS = 256;
 constexpr int WAVES = THREADS / 64;
-constexpr int NJ = 24;
+using pgkin::NJ;
 constexpr int POSE_ROWS = 207;               // 23 joints x 9
 constexpr int MAX_NB = 16, MAX_K = 64;
 constexpr int PT = 32;                       // poses per workgroup: two MFMA row tiles
@@ -39,34 +41,25 @@ constexpr int LDV = 3 * VT + 4;              // row stride of the vertex tile
 constexpr int MAX_CHUNKS = 256;
 constexpr size_t WS_TARGET = (size_t)48 << 20;
 
-__device__ __forceinline__ double wave_all_sum(double v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
+using pgkin::KinConst;
+using pgkin::KinTree;
+using pgkin::wave_all_sum;
 
-// The lane's joint-to-parent transform G (rows of a 3 x 4) becomes joint-to-world: every lane leaves its own in the wave's LDS
-// rows, then walks up its ancestors, `depth` steps for every lane (a lane that has reached the root keeps what it has).
-__device__ __forceinline__ void chain_to_world(double (*srel)[12], const int* spar, int j, bool jl, int depth, double G[12]) {
-    if (jl) {
+// the rest joint of joint j and of its parent (zero for the root): linear in beta
+__device__ __forceinline__ void rest_joint(const double* __restrict__ rest, const float* __restrict__ bp, int NB, int j, int par, double Jr[3],
+                                           double Jp[3]) {
 #pragma unroll
-        for (int e = 0; e < 12; ++e) srel[j][e] = G[e];
+    for (int c = 0; c < 3; ++c) {
+        Jr[c] = rest[j * 3 + c];
+        Jp[c] = par >= 0 ? rest[par * 3 + c] : 0.0;
     }
-    __syncthreads();
-    int p = spar[j];
-    for (int s = 0; s < depth; ++s) {
-        if (p >= 0) {
-            double P[12], N[12];
+    for (int l = 0; l < NB; ++l) {
+        const double b = (double)bp[l];
+        const double* rl = rest + (size_t)(1 + l) * NJ * 3;
 #pragma unroll
-            for (int e = 0; e < 12; ++e) P[e] = srel[p][e];
-#pragma unroll
-            for (int r = 0; r < 3; ++r)
-#pragma unroll
-                for (int c = 0; c < 4; ++c)
-                    N[4 * r + c] = P[4 * r] * G[c] + P[4 * r + 1] * G[4 + c] + P[4 * r + 2] * G[8 + c] + (c == 3 ? P[4 * r + 3] : 0.0);
-#pragma unroll
-            for (int e = 0; e < 12; ++e) G[e] = N[e];
-            p = spar[p];
+        for (int c = 0; c < 3; ++c) {
+            Jr[c] += b * rl[j * 3 + c];
+            if (par >= 0) Jp[c] += b * rl[par * 3 + c];
         }
     }
 }
@@ -80,83 +73,51 @@ struct PreArgs {
     float* A;                    // [n, 24, 12] or null
     float* joints;               // [n, 24, 3] or null
     long long n;
-    int is_rotmat, NB, K, KP, depth;
-    int parent[NJ];
+    int is_rotmat, NB, K, KP;
+    KinTree tree;
 };
 
 __global__ __launch_bounds__(THREADS) void smpl_pre_kernel(PreArgs a) {
     __shared__ double srel[WAVES][NJ][12];
     __shared__ int spar[NJ];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (threadIdx.x < NJ) spar[threadIdx.x] = a.parent[threadIdx.x];
+    if (threadIdx.x < NJ) spar[threadIdx.x] = a.tree.parent[threadIdx.x];
     long long pose = (long long)blockIdx.x * WAVES + w;
     const bool live = pose < a.n;                       // the whole wave
     if (!live) pose = a.n - 1;                          // computes a pose again and writes nothing
     const bool jl = lane < NJ;
     const int j = jl ? lane : 0;
-    const int par = a.parent[j];
+    const int par = a.tree.parent[j];
     const float* bp = a.betas + pose * a.betas_stride;
 
-    // the rest joint of the lane and of its parent: linear in beta
     double Jr[3], Jp[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        Jr[c] = a.rest[j * 3 + c];
-        Jp[c] = par >= 0 ? a.rest[par * 3 + c] : 0.0;
-    }
-    for (int l = 0; l < a.NB; ++l) {
-        const double b = (double)bp[l];
-        const double* rl = a.rest + (size_t)(1 + l) * NJ * 3;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            Jr[c] += b * rl[j * 3 + c];
-            if (par >= 0) Jp[c] += b * rl[par * 3 + c];
-        }
-    }
+    rest_joint(a.rest, bp, a.NB, j, par, Jr, Jp);
 
-    double R[9];
+    double G[12];                                       // the joint-to-parent transform [R | J - J_parent]
     if (a.is_rotmat) {
-        const float* rp = a.pose + ((size_t)pose * NJ + j) * 9;
-#pragma unroll
-        for (int e = 0; e < 9; ++e) R[e] = (double)rp[e];
+        pgkin::rotmat_to_rows(a.pose + ((size_t)pose * NJ + j) * 9, G);
     } else {
-        // batch_rodrigues (lbs.py:295-329) as written: angle = |r + 1e-8|, rot_dir = r / angle, R = I + sin K + (1 - cos) K K
-        const float* rp = a.pose + ((size_t)pose * NJ + j) * 3;
-        const double r0 = (double)rp[0], r1 = (double)rp[1], r2 = (double)rp[2];
-        const double e0 = r0 + 1e-8, e1 = r1 + 1e-8, e2 = r2 + 1e-8;
-        const double angle = sqrt(e0 * e0 + e1 * e1 + e2 * e2);
-        const double x = r0 / angle, y = r1 / angle, z = r2 / angle;
-        const double sn = sin(angle), oc = 1.0 - cos(angle);
-        const double Km[9] = {0.0, -z, y, z, 0.0, -x, -y, x, 0.0};
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const double kk = Km[3 * r] * Km[c] + Km[3 * r + 1] * Km[3 + c] + Km[3 * r + 2] * Km[6 + c];
-                R[3 * r + c] = (r == c ? 1.0 : 0.0) + sn * Km[3 * r + c] + oc * kk;
-            }
+        pgkin::Rodrigues rg;                            // (what the map leaves for its transpose: not used here)
+        pgkin::rodrigues_as_written(a.pose + ((size_t)pose * NJ + j) * 3, rg, G);
     }
+#pragma unroll
+    for (int r = 0; r < 3; ++r) G[4 * r + 3] = Jr[r] - Jp[r];
 
     // the feature row of the blend GEMM
     if (a.feat && live) {
         float* f = a.feat + (size_t)pose * a.KP;
         if (jl && j >= 1) {
 #pragma unroll
-            for (int e = 0; e < 9; ++e) f[1 + a.NB + (j - 1) * 9 + e] = (float)(R[e] - ((e & 3) == 0 ? 1.0 : 0.0));
+            for (int r = 0; r < 3; ++r)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) f[1 + a.NB + (j - 1) * 9 + 3 * r + c] = (float)(G[4 * r + c] - (r == c ? 1.0 : 0.0));
         }
         if (lane == 0) f[0] = 1.f;
         if (lane >= 24 && lane < 24 + a.NB) f[1 + lane - 24] = bp[lane - 24];
         if (lane >= 48 && a.K + (lane - 48) < a.KP) f[a.K + (lane - 48)] = 0.f;
     }
 
-    double G[12];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) G[4 * r + c] = R[3 * r + c];
-        G[4 * r + 3] = Jr[r] - Jp[r];
-    }
-    chain_to_world(srel[w], spar, j, jl, a.depth, G);
+    pgkin::chain_to_world(srel[w], spar, j, jl, a.tree.depth, G);
 
     if (live && jl) {
         if (a.joints) {
@@ -382,47 +343,25 @@ __global__ __launch_bounds__(THREADS) void vertex_err_mean(const double* __restr
     }
 }
 
-struct KinConst { double offs[NJ * 3]; int parent[NJ]; int depth; };
-
 // get_smpl_l2ws_torch(axis_to_matrix=False): l2w_j = l2w_parent [R_j | rest_j - rest_parent], float64 on the float32 matrices
 __global__ __launch_bounds__(THREADS) void kin_rot_kernel(const KinConst kc, const float* __restrict__ rot, long long n, float* __restrict__ kps,
                                                           float* __restrict__ skts, double* __restrict__ l2ws) {
     __shared__ double srel[WAVES][NJ][12];
     __shared__ int spar[NJ];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (threadIdx.x < NJ) spar[threadIdx.x] = kc.parent[threadIdx.x];
+    if (threadIdx.x < NJ) spar[threadIdx.x] = kc.tree.parent[threadIdx.x];
     long long pose = (long long)blockIdx.x * WAVES + w;
     const bool live = pose < n;
     if (!live) pose = n - 1;
     const bool jl = lane < NJ;
     const int j = jl ? lane : 0;
-    const float* rp = rot + ((size_t)pose * NJ + j) * 9;
     double G[12];
+    pgkin::rotmat_to_rows(rot + ((size_t)pose * NJ + j) * 9, G);
 #pragma unroll
-    for (int r = 0; r < 3; ++r) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) G[4 * r + c] = (double)rp[3 * r + c];
-        G[4 * r + 3] = kc.offs[3 * j + r];
-    }
-    chain_to_world(srel[w], spar, j, jl, kc.depth, G);
+    for (int r = 0; r < 3; ++r) G[4 * r + 3] = kc.offs[3 * j + r];
+    pgkin::chain_to_world(srel[w], spar, j, jl, kc.tree.depth, G);
     if (!live || !jl) return;
-    const size_t at = (size_t)pose * NJ + j;
-    if (kps) { kps[at * 3] = (float)G[3]; kps[at * 3 + 1] = (float)G[7]; kps[at * 3 + 2] = (float)G[11]; }
-    if (l2ws) {
-        double* o = l2ws + at * 16;
-#pragma unroll
-        for (int e = 0; e < 12; ++e) o[e] = G[e];
-        o[12] = 0.0; o[13] = 0.0; o[14] = 0.0; o[15] = 1.0;
-    }
-    if (skts) {
-        float* o = skts + at * 16;
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            o[4 * r] = (float)G[r]; o[4 * r + 1] = (float)G[4 + r]; o[4 * r + 2] = (float)G[8 + r];
-            o[4 * r + 3] = (float)(-(G[r] * G[3] + G[4 + r] * G[7] + G[8 + r] * G[11]));
-        }
-        o[12] = 0.f; o[13] = 0.f; o[14] = 0.f; o[15] = 1.f;
-    }
+    pgkin::write_pose_outputs(G, (size_t)pose * NJ + j, kps, l2ws, skts);
 }
 
 // ---- the transpose of the body -------------------------------------------------------------------------------------
@@ -434,7 +373,7 @@ __global__ __launch_bounds__(THREADS) void kin_rot_kernel(const KinConst kc, con
 //                          inside the MFMAs; tiles are added in double, in tile order, per vertex chunk.
 //   smpl_close_kernel    : one wave per pose, lane = joint, float64.  The chunks' partials in chunk order, d_joints into the
 //                          translation cotangent of G, A = [G_R | G_t - G_R J] undone, the chain walked back level by level in LDS
-//                          (as kin_bwd_kernel, pg_kploss.hip), dJ into d_betas through rest_joints, the d feat rows for beta and
+//                          (chain_backward, pg_kin.h), dJ into d_betas through rest_joints, the d feat rows for beta and
 //                          R_j - I, Rodrigues transposed or the nine entries; rounded to float32 once.
 constexpr int BWD_MAX_CHUNKS = 64;           // a pose and chunk leave BWD_PART doubles, ten times the forward's partials
 constexpr int BWD_PART = NJ * 12 + KP_MAX;   // dA [24][12], then d feat [224]
@@ -705,87 +644,37 @@ struct CloseArgs {
     float* d_betas;              // [n, NB] or null
     float* d_pose;               // [n, 24, 3] or [n, 24, 3, 3], or null
     long long n;
-    int is_rotmat, NB, chunks, depth;
-    int parent[NJ], level[NJ];
+    int is_rotmat, NB, chunks;
+    KinTree tree;
 };
 
 __global__ __launch_bounds__(THREADS) void smpl_close_kernel(CloseArgs a) {
     __shared__ double rel[WAVES][NJ][12], l2w[WAVES][NJ][12], Gc[WAVES][NJ][12];
     __shared__ double sJ[WAVES][NJ][3], sfe[WAVES][KP_MAX];
-    __shared__ int spar[NJ], slev[NJ];
+    __shared__ int spar[NJ];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (threadIdx.x < NJ) { spar[threadIdx.x] = a.parent[threadIdx.x]; slev[threadIdx.x] = a.level[threadIdx.x]; }
+    if (threadIdx.x < NJ) spar[threadIdx.x] = a.tree.parent[threadIdx.x];
     long long pose = (long long)blockIdx.x * WAVES + w;
     const bool live = pose < a.n;                       // the whole wave
     if (!live) pose = a.n - 1;                          // walks the last pose again and writes nothing
     const bool jl = lane < NJ;
     const int j = jl ? lane : 0;
-    const int par = a.parent[j], lev = a.level[j];
+    const int par = a.tree.parent[j], lev = a.tree.level[j];
     const float* bp = a.betas + pose * a.betas_stride;
 
-    // 1. the forward in double, as smpl_pre_kernel: rest joints, R, the relative transform [R | J - J_parent]
+    // 1. the forward in double, as smpl_pre_kernel: rest joints, R, the relative transform [R | J - J_parent], the chain
     double Jr[3], Jp[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        Jr[c] = a.rest[j * 3 + c];
-        Jp[c] = par >= 0 ? a.rest[par * 3 + c] : 0.0;
-    }
-    for (int l = 0; l < a.NB; ++l) {
-        const double b = (double)bp[l];
-        const double* rl = a.rest + (size_t)(1 + l) * NJ * 3;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            Jr[c] += b * rl[j * 3 + c];
-            if (par >= 0) Jp[c] += b * rl[par * 3 + c];
-        }
-    }
-    double M[12], Km[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    double rv[3] = {0.0, 0.0, 0.0}, angle = 1.0, sn = 0.0, cs = 1.0;
+    rest_joint(a.rest, bp, a.NB, j, par, Jr, Jp);
+    double M[12];
+    pgkin::Rodrigues rg{};
     if (a.is_rotmat) {
-        const float* rp = a.pose + ((size_t)pose * NJ + j) * 9;
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) M[4 * r + c] = (double)rp[3 * r + c];
+        pgkin::rotmat_to_rows(a.pose + ((size_t)pose * NJ + j) * 9, M);
     } else {
-        const float* rp = a.pose + ((size_t)pose * NJ + j) * 3;
-        rv[0] = (double)rp[0]; rv[1] = (double)rp[1]; rv[2] = (double)rp[2];
-        const double e0 = rv[0] + 1e-8, e1 = rv[1] + 1e-8, e2 = rv[2] + 1e-8;
-        angle = sqrt(e0 * e0 + e1 * e1 + e2 * e2);
-        const double x = rv[0] / angle, y = rv[1] / angle, z = rv[2] / angle;
-        sn = sin(angle); cs = cos(angle);
-        Km[1] = -z; Km[2] = y; Km[3] = z; Km[5] = -x; Km[6] = -y; Km[7] = x;
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const double kk = Km[3 * r] * Km[c] + Km[3 * r + 1] * Km[3 + c] + Km[3 * r + 2] * Km[6 + c];
-                M[4 * r + c] = (r == c ? 1.0 : 0.0) + sn * Km[3 * r + c] + (1.0 - cs) * kk;
-            }
+        pgkin::rodrigues_as_written(a.pose + ((size_t)pose * NJ + j) * 3, rg, M);
     }
 #pragma unroll
     for (int r = 0; r < 3; ++r) M[4 * r + 3] = Jr[r] - Jp[r];
-    if (jl) {
-#pragma unroll
-        for (int e = 0; e < 12; ++e) rel[w][j][e] = M[e];
-        if (lev == 0) {
-#pragma unroll
-            for (int e = 0; e < 12; ++e) l2w[w][j][e] = M[e];
-        }
-    }
-    __syncthreads();
-    for (int d = 1; d <= a.depth; ++d) {
-        if (jl && lev == d) {
-            const double* P = l2w[w][par];
-#pragma unroll
-            for (int r = 0; r < 3; ++r) {
-                const double a0 = P[4 * r], a1 = P[4 * r + 1], a2 = P[4 * r + 2], a3 = P[4 * r + 3];
-#pragma unroll
-                for (int c = 0; c < 4; ++c) l2w[w][j][4 * r + c] = a0 * M[c] + a1 * M[4 + c] + a2 * M[8 + c] + (c == 3 ? a3 : 0.0);
-            }
-        }
-        __syncthreads();
-    }
+    pgkin::chain_forward(rel[w], l2w[w], M, j, jl, par, lev, a.tree.depth);
 
     // 2. the chunks' partials in chunk order: dA of the lane's joint, d feat four columns a lane
     double dA[12];
@@ -820,42 +709,11 @@ __global__ __launch_bounds__(THREADS) void smpl_close_kernel(CloseArgs a) {
         }
     }
     __syncthreads();
-    // 4. the chain backwards, children before parents, a parent collecting its children in joint order
-    for (int d = a.depth; d >= 1; --d) {
-        if (jl && lev == d - 1) {
-            double acc[12];
-#pragma unroll
-            for (int e = 0; e < 12; ++e) acc[e] = Gc[w][j][e];
-            for (int c = j + 1; c < NJ; ++c) {
-                if (spar[c] != j) continue;
-                const double* g = Gc[w][c];
-                const double* L = rel[w][c];
-#pragma unroll
-                for (int r = 0; r < 3; ++r) {
-                    const double g0 = g[4 * r], g1 = g[4 * r + 1], g2 = g[4 * r + 2], g3 = g[4 * r + 3];
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) acc[4 * r + k] += g0 * L[4 * k] + g1 * L[4 * k + 1] + g2 * L[4 * k + 2] + g3 * L[4 * k + 3];
-                    acc[4 * r + 3] += g3;
-                }
-            }
-#pragma unroll
-            for (int e = 0; e < 12; ++e) Gc[w][j][e] = acc[e];
-        }
-        __syncthreads();
-    }
+    // 4. the chain backwards, children before parents
+    pgkin::chain_backward(Gc[w], rel[w], spar, j, jl, lev, a.tree.depth);
     // 5. the cotangent of the relative transform: G_parent_R^T dG (the root's parent is the identity); its column 3 is d(J - J_parent)
     double D[12];
-    if (lev == 0) {
-#pragma unroll
-        for (int e = 0; e < 12; ++e) D[e] = Gc[w][j][e];
-    } else {
-        const double* P = l2w[w][par];
-        const double* g = Gc[w][j];
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) D[4 * k + c] = P[k] * g[c] + P[4 + k] * g[4 + c] + P[8 + k] * g[8 + c];
-    }
+    pgkin::parent_transpose<4>(l2w[w], par, Gc[w][j], D);
     __syncthreads();                                    // every lane has read l2w and Gc: rel's rows now carry d(J - J_parent)
     if (jl) {
 #pragma unroll
@@ -894,28 +752,11 @@ __global__ __launch_bounds__(THREADS) void smpl_close_kernel(CloseArgs a) {
         for (int e = 0; e < 9; ++e) dst[e] = (float)dR[e];
         return;
     }
-    // R = I + sin K + (1 - cos) K K, K = skew(r / angle), angle = |r + 1e-8|
-    const double oc = 1.0 - cs;
-    double dK[9], dth = 0.0;
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            // (D K^T + K^T D)[r][c] = sum_k D[r][k] K[c][k] + K[k][r] D[k][c]
-            double t = 0.0, kk = 0.0;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                t += dR[3 * r + k] * Km[3 * c + k] + Km[3 * k + r] * dR[3 * k + c];
-                kk += Km[3 * r + k] * Km[3 * k + c];
-            }
-            dK[3 * r + c] = sn * dR[3 * r + c] + oc * t;
-            dth += dR[3 * r + c] * (cs * Km[3 * r + c] + sn * kk);
-        }
-    const double dd[3] = {dK[7] - dK[5], dK[2] - dK[6], dK[3] - dK[1]};
-    dth -= (dd[0] * rv[0] + dd[1] * rv[1] + dd[2] * rv[2]) / (angle * angle);
+    double o[3];
+    pgkin::rodrigues_as_written_bwd(rg, dR, o);
     float* dst = a.d_pose + ((size_t)pose * NJ + j) * 3;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) dst[c] = (float)(dd[c] / angle + dth * (rv[c] + 1e-8) / angle);
+    for (int c = 0; c < 3; ++c) dst[c] = (float)o[c];
 }
 
 }  // namespace pgsm
@@ -927,16 +768,71 @@ struct SmplState {
     DevBuf ws;
 };
 
-// the deepest joint's distance from the root, or -1 for a tree that is not ordered parent before child
-int tree_depth(const int32_t* parents) {
-    if (parents[0] != -1) return -1;
-    int depth[pgsm::NJ] = {0}, deepest = 0;
-    for (int j = 1; j < pgsm::NJ; ++j) {
-        if (parents[j] < 0 || parents[j] >= j) return -1;
-        depth[j] = depth[parents[j]] + 1;
-        if (depth[j] > deepest) deepest = depth[j];
-    }
-    return deepest;
+// what pg_smpl_forward and pg_smpl_backward share of a call, once it is valid
+struct BodyPlan {
+    int rows, KP, tiles;         // blend rows 1 + NB + 207, rounded up to a multiple of 4; 64-vertex tiles
+    pgkin::KinTree tree;
+    float* feat = nullptr;       // the slice's workspace
+    float* A = nullptr;
+    double* part = nullptr;
+};
+
+// The checks of a body call.  `missing`: what the entry point found it was not given or asked for (null: nothing); `reg`: how it
+// names its regressor-side array when it has one (null: none).
+int body_plan(pg_handle* h, const char* who, const pg_body_model* m, int64_t B, const float* betas, int64_t betas_stride, const float* pose,
+              const float* regress, int K, const char* missing, const char* reg, BodyPlan& p) {
+    if (!h) return pg_fail(nullptr, PG_EINVAL, "null handle");
+    if (!m || !betas || !pose) return pg_fail(h, PG_EINVAL, "%s: model, betas and pose are required", who);
+    if (missing) return pg_fail(h, PG_EINVAL, "%s: %s", who, missing);
+    if (B < 1) return pg_fail(h, PG_EINVAL, "%s: B = %lld", who, (long long)B);
+    if (m->NB < 1 || m->NB > pgsm::MAX_NB) return pg_fail(h, PG_EINVAL, "%s: NB = %d is outside [1, %d]", who, m->NB, pgsm::MAX_NB);
+    p.rows = 1 + m->NB + pgsm::POSE_ROWS;
+    if (m->V < 1 || (long long)p.rows * 3 * (long long)m->V >= (1ll << 31))
+        return pg_fail(h, PG_EINVAL, "%s: V = %d (at least 1, and %d blend rows of 3 V below 2^31 elements)", who, m->V, p.rows);
+    if (!m->blend || !m->skin || !m->rest_joints) return pg_fail(h, PG_EINVAL, "%s: the model has a NULL array", who);
+    if (K < 0 || K > pgsm::MAX_K) return pg_fail(h, PG_EINVAL, "%s: K = %d is outside [0, %d]", who, K, pgsm::MAX_K);
+    if (K > 0 && !regress) return pg_fail(h, PG_EINVAL, "%s: K = %d without regress", who, K);
+    if (reg && K == 0) return pg_fail(h, PG_EINVAL, "%s: %s with K = 0", who, reg);
+    if (betas_stride != 0 && betas_stride != m->NB)
+        return pg_fail(h, PG_EINVAL, "%s: betas_stride = %lld (NB = %d, or 0 for one row)", who, (long long)betas_stride, m->NB);
+    if (m->parents[0] != -1 || !pgkin::pg_kin_tree(m->parents, p.tree))
+        return pg_fail(h, PG_EINVAL, "%s: parents[0] must be -1 and every joint must come after its parent", who);
+    p.KP = (p.rows + 3) & ~3;
+    p.tiles = (m->V + pgsm::VT - 1) / pgsm::VT;
+    return PG_OK;
+}
+
+// the poses of one slice: what keeps a workspace of per_pose bytes a pose at `target`, in whole pose tiles, at least one, 4096 at most
+long long slice_poses(size_t per_pose, size_t target) {
+    const long long S = (long long)(target / per_pose) / pgsm::PT * pgsm::PT;
+    return S < pgsm::PT ? pgsm::PT : S > 4096 ? 4096 : S;
+}
+
+// the workspace of a slice of S poses: the chunks' partials (part_doubles of them; none: null), the feature rows and A
+int carve_body(pg_handle* h, BodyPlan& p, size_t part_doubles, long long S) {
+    if (!h->smpl) h->smpl = new SmplState();
+    auto* s = static_cast<SmplState*>(h->smpl);
+    auto carve = [&](Carver& c) {
+        p.part = c.take<double>(part_doubles, part_doubles > 0);
+        p.feat = c.take<float>((size_t)S * p.KP);
+        p.A = c.take<float>((size_t)S * pgsm::NJ * 12);
+    };
+    Carver count, real;
+    carve(count);
+    PG_TRY(pg_grow(h, s->ws, count.off, "body model workspace"));
+    real.base = s->ws.p;
+    carve(real);
+    return PG_OK;
+}
+
+int launch_pre(pg_handle* h, hipStream_t st, const BodyPlan& p, const pg_body_model* m, const float* betas, int64_t betas_stride,
+               const float* pose, int pose_is_rotmat, float* joints, long long n) {
+    pgsm::PreArgs pa{};
+    pa.betas = betas; pa.betas_stride = betas_stride; pa.pose = pose; pa.rest = m->rest_joints; pa.feat = p.feat; pa.A = p.A;
+    pa.joints = joints; pa.n = n; pa.is_rotmat = pose_is_rotmat ? 1 : 0; pa.NB = m->NB; pa.K = p.rows; pa.KP = p.KP; pa.tree = p.tree;
+    hipLaunchKernelGGL(pgsm::smpl_pre_kernel, dim3((unsigned)((n + pgsm::WAVES - 1) / pgsm::WAVES)), dim3(pgsm::THREADS), 0, st, pa);
+    PG_LAUNCH_CHECK(h, "body model pose kernel");
+    return PG_OK;
 }
 
 }  // namespace
@@ -952,78 +848,35 @@ void pg_smpl_release(pg_handle* h) {
 extern "C" int pg_smpl_forward(pg_handle* h, void* stream, const pg_body_model* m, int64_t B, const float* betas, int64_t betas_stride,
                                const float* pose, int pose_is_rotmat, const float* regress, int K, float* verts, float* joints,
                                float* regressed) {
-    const char* who = "pg_smpl_forward";
-    if (!h) return pg_fail(nullptr, PG_EINVAL, "null handle");
-    if (!m || !betas || !pose) return pg_fail(h, PG_EINVAL, "%s: model, betas and pose are required", who);
-    if (!verts && !joints && !regressed) return pg_fail(h, PG_EINVAL, "%s: no output asked for", who);
-    if (B < 1) return pg_fail(h, PG_EINVAL, "%s: B = %lld", who, (long long)B);
-    if (m->NB < 1 || m->NB > pgsm::MAX_NB) return pg_fail(h, PG_EINVAL, "%s: NB = %d is outside [1, %d]", who, m->NB, pgsm::MAX_NB);
-    const int rows = 1 + m->NB + pgsm::POSE_ROWS;
-    if (m->V < 1 || (long long)rows * 3 * (long long)m->V >= (1ll << 31))
-        return pg_fail(h, PG_EINVAL, "%s: V = %d (at least 1, and %d blend rows of 3 V below 2^31 elements)", who, m->V, rows);
-    if (!m->blend || !m->skin || !m->rest_joints) return pg_fail(h, PG_EINVAL, "%s: the model has a NULL array", who);
-    if (K < 0 || K > pgsm::MAX_K) return pg_fail(h, PG_EINVAL, "%s: K = %d is outside [0, %d]", who, K, pgsm::MAX_K);
-    if (K > 0 && !regress) return pg_fail(h, PG_EINVAL, "%s: K = %d without regress", who, K);
-    if (regressed && K == 0) return pg_fail(h, PG_EINVAL, "%s: regressed asked for with K = 0", who);
-    if (betas_stride != 0 && betas_stride != m->NB)
-        return pg_fail(h, PG_EINVAL, "%s: betas_stride = %lld (NB = %d, or 0 for one row)", who, (long long)betas_stride, m->NB);
-    const int depth = tree_depth(m->parents);
-    if (depth < 0) return pg_fail(h, PG_EINVAL, "%s: parents[0] must be -1 and every joint must come after its parent", who);
-
-    const int V = m->V, KP = (rows + 3) & ~3;
-    const int KR = regressed ? K : 0;
+    BodyPlan p;
+    PG_TRY(body_plan(h, "pg_smpl_forward", m, B, betas, betas_stride, pose, regress, K,
+                     !verts && !joints && !regressed ? "no output asked for" : nullptr, regressed ? "regressed asked for" : nullptr, p));
+    const int V = m->V, KR = regressed ? K : 0;
     const bool body = verts || regressed;
-    const int tiles = (V + pgsm::VT - 1) / pgsm::VT;
-    const int chunks = tiles < pgsm::MAX_CHUNKS ? tiles : pgsm::MAX_CHUNKS;
-    // the poses of one slice: what keeps the workspace at WS_TARGET, in whole pose tiles, at least one
-    const size_t per_pose = body ? ((size_t)KP + pgsm::NJ * 12) * sizeof(float) + (size_t)chunks * KR * 3 * sizeof(double) : 0;
-    long long S = body ? (long long)(pgsm::WS_TARGET / per_pose) / pgsm::PT * pgsm::PT : B;
-    if (S < pgsm::PT) S = pgsm::PT;
-    if (S > 4096 && body) S = 4096;
+    const int chunks = p.tiles < pgsm::MAX_CHUNKS ? p.tiles : pgsm::MAX_CHUNKS;
+    long long S = body ? slice_poses(((size_t)p.KP + pgsm::NJ * 12) * sizeof(float) + (size_t)chunks * KR * 3 * sizeof(double), pgsm::WS_TARGET) : B;
     if (S > B) S = B;
 
     PG_HIP(h, hipSetDevice(h->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    float *d_feat = nullptr, *d_A = nullptr;
-    double* d_part = nullptr;
-    if (body) {
-        if (!h->smpl) h->smpl = new SmplState();
-        auto* s = static_cast<SmplState*>(h->smpl);
-        auto carve = [&](Carver& c) {
-            d_part = c.take<double>((size_t)chunks * S * KR * 3, KR > 0);
-            d_feat = c.take<float>((size_t)S * KP);
-            d_A = c.take<float>((size_t)S * pgsm::NJ * 12);
-        };
-        Carver count, real;
-        carve(count);
-        PG_TRY(pg_grow(h, s->ws, count.off, "body model workspace"));
-        real.base = s->ws.p;
-        carve(real);
-    }
+    if (body) PG_TRY(carve_body(h, p, (size_t)chunks * S * KR * 3, S));
 
     for (long long b0 = 0; b0 < B; b0 += S) {
         const long long n = B - b0 < S ? B - b0 : S;
-        pgsm::PreArgs pa{};
-        pa.betas = betas + b0 * betas_stride; pa.betas_stride = betas_stride;
-        pa.pose = pose + (size_t)b0 * pgsm::NJ * (pose_is_rotmat ? 9 : 3);
-        pa.rest = m->rest_joints; pa.feat = d_feat; pa.A = d_A;
-        pa.joints = joints ? joints + (size_t)b0 * pgsm::NJ * 3 : nullptr;
-        pa.n = n; pa.is_rotmat = pose_is_rotmat ? 1 : 0; pa.NB = m->NB; pa.K = rows; pa.KP = KP; pa.depth = depth;
-        for (int j = 0; j < pgsm::NJ; ++j) pa.parent[j] = m->parents[j];
-        hipLaunchKernelGGL(pgsm::smpl_pre_kernel, dim3((unsigned)((n + pgsm::WAVES - 1) / pgsm::WAVES)), dim3(pgsm::THREADS), 0, st, pa);
-        PG_LAUNCH_CHECK(h, "body model pose kernel");
+        PG_TRY(launch_pre(h, st, p, m, betas + b0 * betas_stride, betas_stride, pose + (size_t)b0 * pgsm::NJ * (pose_is_rotmat ? 9 : 3),
+                          pose_is_rotmat, joints ? joints + (size_t)b0 * pgsm::NJ * 3 : nullptr, n));
         if (!body) continue;
         pgsm::BodyArgs ba{};
-        ba.blend = m->blend; ba.skin = m->skin; ba.regress = regress; ba.feat = d_feat; ba.A = d_A;
+        ba.blend = m->blend; ba.skin = m->skin; ba.regress = regress; ba.feat = p.feat; ba.A = p.A;
         ba.verts = verts ? verts + (size_t)b0 * V * 3 : nullptr;
-        ba.part = d_part; ba.n = n; ba.V = V; ba.K = rows; ba.KP = KP; ba.KR = KR; ba.chunks = chunks; ba.tiles = tiles;
+        ba.part = p.part; ba.n = n; ba.V = V; ba.K = p.rows; ba.KP = p.KP; ba.KR = KR; ba.chunks = chunks; ba.tiles = p.tiles;
         hipLaunchKernelGGL(pgsm::smpl_body_kernel, dim3((unsigned)chunks, (unsigned)((n + pgsm::PT - 1) / pgsm::PT)), dim3(pgsm::THREADS), 0, st,
                            ba);
         PG_LAUNCH_CHECK(h, "body model kernel");
         if (KR > 0) {
             const long long per_chunk = n * KR * 3;
             hipLaunchKernelGGL(pgsm::smpl_regress_sum, dim3((unsigned)((per_chunk + pgsm::THREADS - 1) / pgsm::THREADS)), dim3(pgsm::THREADS), 0,
-                               st, d_part, per_chunk, chunks, regressed + (size_t)b0 * KR * 3);
+                               st, p.part, per_chunk, chunks, regressed + (size_t)b0 * KR * 3);
             PG_LAUNCH_CHECK(h, "body model regressor sum kernel");
         }
     }
@@ -1033,37 +886,17 @@ extern "C" int pg_smpl_forward(pg_handle* h, void* stream, const pg_body_model* 
 extern "C" int pg_smpl_backward(pg_handle* h, void* stream, const pg_body_model* m, int64_t B, const float* betas, int64_t betas_stride,
                                 const float* pose, int pose_is_rotmat, const float* regress, int K, const float* blend_t,
                                 const float* d_verts, const float* d_joints, const float* d_regressed, float* d_betas, float* d_pose) {
-    const char* who = "pg_smpl_backward";
-    if (!h) return pg_fail(nullptr, PG_EINVAL, "null handle");
-    if (!m || !betas || !pose) return pg_fail(h, PG_EINVAL, "%s: model, betas and pose are required", who);
-    if (!d_verts && !d_joints && !d_regressed) return pg_fail(h, PG_EINVAL, "%s: no cotangent given", who);
-    if (!d_betas && !d_pose) return pg_fail(h, PG_EINVAL, "%s: no output asked for", who);
-    if (B < 1) return pg_fail(h, PG_EINVAL, "%s: B = %lld", who, (long long)B);
-    if (m->NB < 1 || m->NB > pgsm::MAX_NB) return pg_fail(h, PG_EINVAL, "%s: NB = %d is outside [1, %d]", who, m->NB, pgsm::MAX_NB);
-    const int rows = 1 + m->NB + pgsm::POSE_ROWS;
-    if (m->V < 1 || (long long)rows * 3 * (long long)m->V >= (1ll << 31))
-        return pg_fail(h, PG_EINVAL, "%s: V = %d (at least 1, and %d blend rows of 3 V below 2^31 elements)", who, m->V, rows);
-    if (!m->blend || !m->skin || !m->rest_joints) return pg_fail(h, PG_EINVAL, "%s: the model has a NULL array", who);
-    if (K < 0 || K > pgsm::MAX_K) return pg_fail(h, PG_EINVAL, "%s: K = %d is outside [0, %d]", who, K, pgsm::MAX_K);
-    if (K > 0 && !regress) return pg_fail(h, PG_EINVAL, "%s: K = %d without regress", who, K);
-    if (d_regressed && K == 0) return pg_fail(h, PG_EINVAL, "%s: d_regressed given with K = 0", who);
-    if (betas_stride != 0 && betas_stride != m->NB)
-        return pg_fail(h, PG_EINVAL, "%s: betas_stride = %lld (NB = %d, or 0 for one row)", who, (long long)betas_stride, m->NB);
-    const int depth = tree_depth(m->parents);
-    if (depth < 0) return pg_fail(h, PG_EINVAL, "%s: parents[0] must be -1 and every joint must come after its parent", who);
-
-    const int V = m->V, KP = (rows + 3) & ~3;
-    const int KR = d_regressed ? K : 0;
+    BodyPlan p;
+    PG_TRY(body_plan(h, "pg_smpl_backward", m, B, betas, betas_stride, pose, regress, K,
+                     !d_verts && !d_joints && !d_regressed ? "no cotangent given" : !d_betas && !d_pose ? "no output asked for" : nullptr,
+                     d_regressed ? "d_regressed given" : nullptr, p));
+    const int V = m->V, KR = d_regressed ? K : 0;
     const bool body = d_verts || d_regressed;            // with d_joints alone no vertex-tile kernel runs
-    const int tiles = (V + pgsm::VT - 1) / pgsm::VT;
-    const int chunks = !body ? 0 : tiles < pgsm::BWD_MAX_CHUNKS ? tiles : pgsm::BWD_MAX_CHUNKS;
-    const size_t per_pose = body ? ((size_t)KP + pgsm::NJ * 12) * sizeof(float) + (size_t)chunks * pgsm::BWD_PART * sizeof(double) : 0;
-    // the poses of one slice: what keeps the workspace at BWD_WS_TARGET, in whole pose tiles, at least one; the kernel's LDS admits one
-    // workgroup per CU, so a slice of more workgroups than CUs is cut to a whole number of rounds of them
-    long long S = body ? (long long)(pgsm::BWD_WS_TARGET / per_pose) / pgsm::PT * pgsm::PT : B;
-    if (S < pgsm::PT) S = pgsm::PT;
-    if (S > 4096 && body) S = 4096;
+    const int chunks = !body ? 0 : p.tiles < pgsm::BWD_MAX_CHUNKS ? p.tiles : pgsm::BWD_MAX_CHUNKS;
+    long long S = B;
     if (body) {
+        S = slice_poses(((size_t)p.KP + pgsm::NJ * 12) * sizeof(float) + (size_t)chunks * pgsm::BWD_PART * sizeof(double), pgsm::BWD_WS_TARGET);
+        // the kernel's LDS admits one workgroup per CU, so a slice of more workgroups than CUs is cut to a whole number of rounds of them
         const long long wgs = S / pgsm::PT * chunks, cus = h->n_cu > 0 ? h->n_cu : 256;
         const long long whole = wgs / cus * cus / chunks;          // pose tiles of the whole rounds
         if (whole >= 1) S = whole * pgsm::PT;
@@ -1072,53 +905,29 @@ extern "C" int pg_smpl_backward(pg_handle* h, void* stream, const pg_body_model*
 
     PG_HIP(h, hipSetDevice(h->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    float *d_feat = nullptr, *d_A = nullptr;
-    double* d_part = nullptr;
-    if (body) {
-        if (!h->smpl) h->smpl = new SmplState();
-        auto* s = static_cast<SmplState*>(h->smpl);
-        auto carve = [&](Carver& c) {
-            d_part = c.take<double>((size_t)chunks * S * pgsm::BWD_PART);
-            d_feat = c.take<float>((size_t)S * KP);
-            d_A = c.take<float>((size_t)S * pgsm::NJ * 12);
-        };
-        Carver count, real;
-        carve(count);
-        PG_TRY(pg_grow(h, s->ws, count.off, "body model workspace"));
-        real.base = s->ws.p;
-        carve(real);
-    }
-    int level[pgsm::NJ] = {0};
-    for (int j = 1; j < pgsm::NJ; ++j) level[j] = level[m->parents[j]] + 1;
+    if (body) PG_TRY(carve_body(h, p, (size_t)chunks * S * pgsm::BWD_PART, S));
 
     for (long long b0 = 0; b0 < B; b0 += S) {
         const long long n = B - b0 < S ? B - b0 : S;
         const float* sl_betas = betas + b0 * betas_stride;
         const float* sl_pose = pose + (size_t)b0 * pgsm::NJ * (pose_is_rotmat ? 9 : 3);
         if (body) {
-            pgsm::PreArgs pa{};
-            pa.betas = sl_betas; pa.betas_stride = betas_stride; pa.pose = sl_pose;
-            pa.rest = m->rest_joints; pa.feat = d_feat; pa.A = d_A; pa.joints = nullptr;
-            pa.n = n; pa.is_rotmat = pose_is_rotmat ? 1 : 0; pa.NB = m->NB; pa.K = rows; pa.KP = KP; pa.depth = depth;
-            for (int j = 0; j < pgsm::NJ; ++j) pa.parent[j] = m->parents[j];
-            hipLaunchKernelGGL(pgsm::smpl_pre_kernel, dim3((unsigned)((n + pgsm::WAVES - 1) / pgsm::WAVES)), dim3(pgsm::THREADS), 0, st, pa);
-            PG_LAUNCH_CHECK(h, "body model pose kernel");
+            PG_TRY(launch_pre(h, st, p, m, sl_betas, betas_stride, sl_pose, pose_is_rotmat, nullptr, n));
             pgsm::BwdArgs ba{};
-            ba.blend = m->blend; ba.blend_t = blend_t; ba.skin = m->skin; ba.regress = regress; ba.feat = d_feat; ba.A = d_A;
+            ba.blend = m->blend; ba.blend_t = blend_t; ba.skin = m->skin; ba.regress = regress; ba.feat = p.feat; ba.A = p.A;
             ba.d_verts = d_verts ? d_verts + (size_t)b0 * V * 3 : nullptr;
             ba.d_reg = d_regressed ? d_regressed + (size_t)b0 * KR * 3 : nullptr;
-            ba.part = d_part; ba.n = n; ba.V = V; ba.K = rows; ba.KP = KP; ba.KR = KR; ba.chunks = chunks; ba.tiles = tiles;
+            ba.part = p.part; ba.n = n; ba.V = V; ba.K = p.rows; ba.KP = p.KP; ba.KR = KR; ba.chunks = chunks; ba.tiles = p.tiles;
             hipLaunchKernelGGL(pgsm::smpl_body_bwd_kernel, dim3((unsigned)chunks, (unsigned)((n + pgsm::PT - 1) / pgsm::PT)), dim3(pgsm::THREADS),
                                0, st, ba);
             PG_LAUNCH_CHECK(h, "body model backward kernel");
         }
         pgsm::CloseArgs ca{};
-        ca.betas = sl_betas; ca.betas_stride = betas_stride; ca.pose = sl_pose; ca.rest = m->rest_joints; ca.part = d_part;
+        ca.betas = sl_betas; ca.betas_stride = betas_stride; ca.pose = sl_pose; ca.rest = m->rest_joints; ca.part = p.part;
         ca.d_joints = d_joints ? d_joints + (size_t)b0 * pgsm::NJ * 3 : nullptr;
         ca.d_betas = d_betas ? d_betas + (size_t)b0 * m->NB : nullptr;
         ca.d_pose = d_pose ? d_pose + (size_t)b0 * pgsm::NJ * (pose_is_rotmat ? 9 : 3) : nullptr;
-        ca.n = n; ca.is_rotmat = pose_is_rotmat ? 1 : 0; ca.NB = m->NB; ca.chunks = chunks; ca.depth = depth;
-        for (int j = 0; j < pgsm::NJ; ++j) { ca.parent[j] = m->parents[j]; ca.level[j] = level[j]; }
+        ca.n = n; ca.is_rotmat = pose_is_rotmat ? 1 : 0; ca.NB = m->NB; ca.chunks = chunks; ca.tree = p.tree;
         hipLaunchKernelGGL(pgsm::smpl_close_kernel, dim3((unsigned)((n + pgsm::WAVES - 1) / pgsm::WAVES)), dim3(pgsm::THREADS), 0, st, ca);
         PG_LAUNCH_CHECK(h, "body model backward closing kernel");
     }
@@ -1149,11 +958,10 @@ extern "C" int pg_pose_kinematics_rot(pg_handle* h, void* stream, int64_t n_pose
     if (!h) return pg_fail(nullptr, PG_EINVAL, "null handle");
     if (n_poses < 0 || !rotmats || !bone_offsets || !parents) return pg_fail(h, PG_EINVAL, "%s: null/negative argument", who);
     pgsm::KinConst kc;
-    kc.depth = tree_depth(parents);
-    if (kc.depth < 0) return pg_fail(h, PG_EINVAL, "%s: parents[0] must be -1 and every joint must come after its parent", who);
+    if (parents[0] != -1 || !pgkin::pg_kin_tree(parents, kc.tree))
+        return pg_fail(h, PG_EINVAL, "%s: parents[0] must be -1 and every joint must come after its parent", who);
     if (n_poses == 0) return PG_OK;
     for (int i = 0; i < pgsm::NJ * 3; ++i) kc.offs[i] = bone_offsets[i];
-    for (int i = 0; i < pgsm::NJ; ++i) kc.parent[i] = parents[i];
     PG_HIP(h, hipSetDevice(h->device));
     hipLaunchKernelGGL(pgsm::kin_rot_kernel, dim3((unsigned)((n_poses + pgsm::WAVES - 1) / pgsm::WAVES)), dim3(pgsm::THREADS), 0,
                        static_cast<hipStream_t>(stream), kc, rotmats, (long long)n_poses, kps, skts, l2ws);

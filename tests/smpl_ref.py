@@ -105,10 +105,10 @@ def bound_regressed(ref_out, NB, V):
     return (n_vertex_products(NB) + (V + 3) // 4) * U * ref_out["mag_regressed"]
 
 
-def bound_chain(value64, mag):
-    """posed joints and key points: one float32 ulp of the restatement's rounded value plus 9 u mag for the float32 inputs' own
-    rounding through a chain of depth <= 9"""
-    return np.spacing(np.abs(f64(value64).astype(np.float32))).astype(np.float64) + 9 * U * mag
+def bound_chain(value64, mag, links=9):
+    """posed joints and key points: one float32 ulp of the restatement's rounded value plus `links` u mag for the float32 inputs' own
+    rounding through a chain of that many joints (root to leaf: the SMPL tree's longest has 9, its depth + 1)"""
+    return np.spacing(np.abs(f64(value64).astype(np.float32))).astype(np.float64) + links * U * mag
 
 
 def rot_chain(rotmats, rest_pose, scale=1.0, parents=None):
