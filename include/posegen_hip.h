@@ -345,7 +345,9 @@ int pg_render_frame_range(pg_handle* h, void* stream, int H, int W, const float*
 
 /* render_path's scatter of a box's maps over the background frame (run_nerf.py:98-137), alone: device maps of the
  * WHOLE box (rgb_map [n_box,3], disp_map, acc_map [n_box], e.g. assembled from pg_render_frame_range pieces) ->
- * rgb [H*W,3], disp, acc [H*W] (may be NULL), rgb8 (may be NULL), background as in pg_render_frame. */
+ * rgb [H*W,3], disp, acc [H*W] (may be NULL), rgb8 (may be NULL), background as in pg_render_frame.  A box that reaches
+ * outside the frame is clamped to it (tl to >= 0, br to <= W, H), and the maps are read as those of the CLAMPED box, row-major
+ * with the clamped width: what pg_render_frame_range produces for the same box.  The maps of a box without pixels may be NULL. */
 int pg_compose_frame(pg_handle* h, void* stream, int H, int W, const int* box, const float* rgb_map, const float* disp_map,
                      const float* acc_map, const float* bg, float base_bg, float* rgb, float* disp, float* acc, uint8_t* rgb8);
 
@@ -442,6 +444,16 @@ int pg_pose_boxes(pg_handle* h, void* stream, int64_t n_poses, const float* kps,
                   int H, int W, int off_x, int off_y, float* cyls, int32_t* boxes);
 
 /* ---- stage entry points (same kernels, exposed for parity tests and profiling) ---- */
+
+/* get_rays + the bounding-box gather of kp_to_valid_rays + render()'s ray_batch packing (ray_utils.py:6-28, 83-136,
+ * trainer.py:118-137): the frame front end of pg_render_frame alone, nothing rendered.  Rays [ray_begin, ray_end) of the
+ * box's row-major ray list -> rays [ray_end-ray_begin,11] (origin, direction, near, far, unit direction) and, unless NULL,
+ * cams [ray_end-ray_begin] = cam: the caller's device buffers.  H, W, c2w, intrinsics, box (clamped to the frame) as in
+ * pg_render_frame.  No nanmean alignment of ray_begin.  PG_EINVAL, nothing launched: a null handle or pointer, a range
+ * outside the box, ray_begin > ray_end.  An empty range launches nothing.  Asynchronous on `stream`. */
+int pg_stage_frame_rays(pg_handle* h, void* stream, int H, int W, const float* c2w, const float* intrinsics, const int* box,
+                        float near, float far, float cam, int64_t ray_begin, int64_t ray_end, float* rays /*[n,11]*/,
+                        float* cams /*[n] or NULL*/);
 
 /* get_near_far_in_cylinder + sample_from_lineseg (ray_utils.py:204-251, 292-344). */
 int pg_stage_sample_coarse(pg_handle* h, void* stream, int64_t n, const float* ray_batch,

@@ -1,6 +1,6 @@
 // pg_frames.hip -- the frame level of the C ABI, host side only (the kernels are pg_kernels.hip's): the frame front and back end
 // (rays of a box generated, rendered and composed into the frame on the device: pg_render_frame, pg_render_frame_range,
-// pg_compose_frame) and in-process multi-device rendering of a batch of frames (pg_render_frames, pg_render_frames_subjects) over
+// pg_compose_frame; the front end alone for tests: pg_stage_frame_rays) and in-process multi-device rendering of a batch of frames (pg_render_frames, pg_render_frames_subjects) over
 // the plan of pg_frames_plan.h.  What a device keeps between calls of the latter is FramesState, behind the handle's `frames`.
 #include <hip/hip_runtime.h>
 
@@ -338,6 +338,21 @@ int pg_compose_frame(pg_handle* h, void* stream, int H, int W, const int* box, c
     PG_HIP(h, hipSetDevice(h->device));
     const FrameMaps maps{const_cast<float*>(rgb_map), const_cast<float*>(disp_map), const_cast<float*>(acc_map)};
     return frame_compose(h, stream, g, maps, bg, base_bg, rgb, disp, acc, rgb8);
+}
+
+int pg_stage_frame_rays(pg_handle* h, void* stream, int H, int W, const float* c2w, const float* intrinsics, const int* box,
+                        float near, float far, float cam, int64_t ray_begin, int64_t ray_end, float* rays, float* cams) {
+    // the host arguments first (pg_fail takes a null handle): what is refused does not depend on there being a device
+    if (!rays) return pg_fail(h, PG_EINVAL, "pg_stage_frame_rays: null argument");
+    pgk::FrameGeom g{};
+    PG_TRY(frame_geom(h, H, W, c2w, intrinsics, box, near, far, cam, &g));
+    const int64_t n = (int64_t)g.bw * g.bh;
+    if (ray_begin < 0 || ray_end > n || ray_begin > ray_end)
+        return pg_fail(h, PG_EINVAL, "frame range [%lld, %lld) outside the box of %lld rays", (long long)ray_begin, (long long)ray_end, (long long)n);
+    if (!h) return pg_fail(nullptr, PG_EINVAL, "null handle");
+    PG_HIP(h, hipSetDevice(h->device));
+    PG_TRY_LAUNCH(h, "frame ray kernel", pg_launch_frame_rays(&g, ray_begin, ray_end - ray_begin, rays, cams, stream));
+    return PG_OK;
 }
 
 int pg_plan_frames(int n_frames, const int64_t* n_rays, int n_workers, int chunk, int32_t* out_tasks /*[cap,5]*/, int cap, int* n_tasks) {

@@ -583,11 +583,11 @@ class HipRenderer:
     def compose_frame(self, H: int, W: int, box, rgb_map: torch.Tensor, disp_map: torch.Tensor, acc_map: torch.Tensor,
                       bg: Optional[torch.Tensor] = None, base_bg: float = 0., want_uint8: bool = False):
         """The maps of a whole box over the background (pg_compose_frame): device tensors rgb [H,W,3],
-        disp [H,W,1], acc [H,W,1] (+ rgb8)."""
+        disp [H,W,1], acc [H,W,1] (+ rgb8).  The maps of a box without pixels may be None."""
         dev = self.device
         (tlx, tly), (brx, bry) = box
         rgb, disp, acc, rgb8, bgt = self._frame_outputs(H, W, bg, want_uint8)
-        rm, dm, am = (_dev_f32(rgb_map, dev), _dev_f32(disp_map, dev), _dev_f32(acc_map, dev))
+        rm, dm, am = (None if m is None else _dev_f32(m, dev) for m in (rgb_map, disp_map, acc_map))
         self._check(self.lib.pg_compose_frame(
             self.handle, self._stream(), int(H), int(W), (C.c_int * 4)(int(tlx), int(tly), int(brx), int(bry)),
             _ptr(rm), _ptr(dm), _ptr(am), _ptr(bgt), float(base_bg), _ptr(rgb), _ptr(disp), _ptr(acc), _ptr(rgb8)))
@@ -785,6 +785,18 @@ class HipRenderer:
         return cyls, boxes
 
     # -- stage entry points (tests / profiling) ---------------------------------------
+    def stage_frame_rays(self, H, W, focal, c2w, box, r0, r1, center=None, cam=None, near=0., far=1., want_cams=False):
+        """Rays [r0, r1) of the box's row-major ray list as the frame front end writes them (pg_stage_frame_rays) ->
+        ray_batch rows [r1 - r0, 11] (+ their frame codes [r1 - r0] with want_cams); nothing is rendered."""
+        n = max(int(r1) - int(r0), 0)
+        rays = torch.empty(max(n, 1), 11, device=self.device)              # (an empty range still hands a buffer over)
+        cams = torch.empty(max(n, 1), device=self.device) if want_cams else None
+        c2w_h, intr, bx = self._frame_args(H, W, focal, c2w, box, center)
+        self._check(self.lib.pg_stage_frame_rays(
+            self.handle, self._stream(), int(H), int(W), c2w_h.ctypes.data_as(C.POINTER(C.c_float)), intr, bx, float(near),
+            float(far), -1.0 if cam is None else float(cam), int(r0), int(r1), _ptr(rays), _ptr(cams)))
+        return (rays[:n], cams[:n]) if want_cams else rays[:n]
+
     def stage_sample_coarse(self, ray_batch, cyls, n_samples, lindisp=False):
         rb = _dev_f32(ray_batch, self.device)
         n = rb.shape[0]
