@@ -575,6 +575,30 @@ typedef struct pg_image_bank {
 int pg_batch_gather(pg_handle* h, void* stream, const pg_image_bank* bank, const int32_t* img_rows, const int32_t* cam_rows, int64_t n_img,
                     int k, const int32_t* pixel_idxs, float* target_s, float* fgs, float* bgs, float* rays_o, float* rays_d, float* ray_batch);
 
+/* ---- the regressor's input batch from uint8 pictures on the device: what pose_dataset, mpii_dataset and mpii_nerf_dataset
+ * (run_gan.py:1636-1735) and the inner loop of train_gan (:2057-2081) do per image on the host -- slice the crop, process_sample
+ * (divide by 255, normalise), skimage.transform.resize(image, (3, R, R), anti_aliasing=True) -- for a batch of (image, crop box)
+ * items in one launch.  Relative to the crop (the image outside the box does not exist, as after the reference's slice):
+ *   v[c,y,x] = (u8 / 255 - mean[c]) / std[c]
+ *   per axis n -> R (rows n = y1 - y0, columns n = x1 - x0): sigma = max(0, (n / R - 1) / 2), r = int(4 sigma + 0.5);
+ *     g = v when r = 0, else g[i] = sum_{t = -r..r} k_t v[m(i + t)], k_t = exp(-t^2 / (2 sigma^2)) / (their sum);
+ *     m mirrors about the centres of the first and the last pixel (period 2 (n - 1); m = 0 for n = 1);
+ *     output o samples x = (o + 0.5) n / R - 0.5 (double): i0 = floor(x), t = x - i0, (1 - t) g[m(i0)] + t g[m(i0 + 1)]
+ * which is scipy.ndimage.gaussian_filter(v, (0, sigma_y, sigma_x), mode='mirror') followed by scipy.ndimage.zoom(..., order=1,
+ * mode='mirror', grid_mode=True): the two calls skimage >= 0.19 makes.  Per axis the two steps run as one filter of 2 r + 2 taps
+ * whose weights are formed in double and rounded to float32 once; sums are float32 fmas, columns first, then rows.
+ *   pixels   device uint8, n_bytes of it: RGB-interleaved images [H,W,3] at the items' byte offsets
+ *   items    HOST [n]: offset (bytes into pixels), the image's H and W, the box 0 <= x0 < x1 <= W, 0 <= y0 < y1 <= H; copied into
+ *            a buffer of the handle, so every check runs on the host
+ *   out_res  R;  mean, std  HOST float [3];  out  device float32 [n,3,R,R]
+ * Asynchronous on `stream`; needs no loaded weights; no atomics, two calls give the same bytes, and an item's bytes do not depend
+ * on the other items of the launch.  PG_EINVAL, nothing launched and nothing written, on a NULL pointer, n < 0, R outside [1, 512],
+ * a mean or std that is not finite or a std of 0, an image that leaves the n_bytes of pixels, a box that is empty or leaves its
+ * image, a crop side above 16 R (so sigma <= 7.5 and r <= 30).  n = 0 is PG_OK and does nothing. */
+typedef struct pg_crop_item { int64_t offset; int32_t H, W, x0, y0, x1, y1; } pg_crop_item;
+int pg_regressor_input(pg_handle* h, void* stream, const uint8_t* pixels, int64_t n_bytes, const pg_crop_item* items, int32_t n,
+                       int32_t out_res, const float mean[3], const float std[3], float* out);
+
 /* ---- scoring a rendered frame against its ground truth: the sums behind the PSNR, the SSIM and their foreground-masked variants of
  * the reference's two evaluate_metric functions (run_render.py:888-974 -- in the frame's 2-D box, :910-961;
  * core/utils/evaluation_helpers.py:257-385 -- whole frames, box = the frame), with the SSIM map of the vendored

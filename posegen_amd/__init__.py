@@ -24,6 +24,7 @@ _SMPL_NAMES = ("BodyModel", "vertex_errors")
 _POSE_LOSS_NAMES = ("keypoints_from_axis_angle", "keypoints_from_rotmats", "pose_loss")
 _TRAIN_LOSS_NAMES = ("photometric_loss", "pose_regulariser", "grad_norms")
 _TRAINER_NAMES = ("HipTrainer",)
+_REGRESSOR_BATCH_NAMES = ("PixelStore", "RegressorBatchSource", "regressor_input", "fixed_crop_boxes", "mpii_crop_boxes", "REFERENCE_NORM")
 _SCENE_NAMES = ("ScenePerson", "render_scene", "render_scenes", "place_people")
 
 
@@ -56,6 +57,9 @@ def __getattr__(name):
     if name in _TRAINER_NAMES:                 # the training step: the reference's Trainer (imports torch as well)
         from . import trainer
         return getattr(trainer, name)
+    if name in _REGRESSOR_BATCH_NAMES:         # the regressor's input batches on the device (imports torch as well)
+        from . import regressor_batches
+        return getattr(regressor_batches, name)
     if name in _SCENE_NAMES:                  # several people in one frame (imports torch as well)
         from . import scene
         return getattr(scene, name)

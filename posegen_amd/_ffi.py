@@ -86,6 +86,11 @@ class PgBodyModel(C.Structure):
                 ("parents", C.c_int32 * 24)]
 
 
+class PgCropItem(C.Structure):
+    """pg_crop_item: one (image, crop box) item of a pg_regressor_input call (offset: bytes into the pixel buffer)."""
+    _fields_ = [("offset", C.c_int64)] + [(k, C.c_int32) for k in ("H", "W", "x0", "y0", "x1", "y1")]
+
+
 class PgOutputs(C.Structure):
     _fields_ = [(k, _FP) for k in ("rgb_map", "disp_map", "acc_map", "alpha", "rgb0", "disp0", "acc0",
                                    "alpha0", "near_far", "z_coarse", "z_fine", "raw_coarse", "raw_fine",
@@ -190,6 +195,8 @@ PROTOTYPES = {
                                          C.POINTER(C.c_int32), C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
     "pg_batch_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(PgImageBank), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int64,
                                   C.c_int, C.c_void_p, _FP, _FP, _FP, _FP, _FP, _FP]),
+    "pg_regressor_input": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(PgCropItem), C.c_int32, C.c_int32,
+                                     C.POINTER(C.c_float), C.POINTER(C.c_float), _FP]),
     "pg_frame_metrics": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(PgImageBank), C.c_int32, C.POINTER(C.c_int32), _FP, C.c_int,
                                    C.c_void_p]),
     "pg_frame_metrics_val": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(PgImageBank), C.c_int32, C.POINTER(C.c_int32), _FP, C.c_int32,

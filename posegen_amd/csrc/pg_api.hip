@@ -59,6 +59,28 @@ int pg_grow_pinned(pg_handle* h, PinBuf& b, size_t need, const char* what, size_
     return PG_OK;
 }
 
+int pg_ring_upload(pg_handle* h, UploadRing& ring, const void* src, size_t bytes, size_t alloc, const char* what, hipStream_t st, const void** dev) {
+    UploadRing::Slot& sl = ring.slot[ring.next++ % UploadRing::SLOTS];
+    if (!sl.done) PG_HIP(h, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
+    else PG_HIP(h, hipEventSynchronize(sl.done));
+    PG_TRY(pg_grow_pinned(h, sl.host, bytes, what, alloc));
+    PG_TRY(pg_grow(h, sl.dev, sl.host.bytes, what));
+    std::memcpy(sl.host.p, src, bytes);
+    PG_HIP(h, hipMemcpyAsync(sl.dev.p, sl.host.p, bytes, hipMemcpyHostToDevice, st));
+    PG_HIP(h, hipEventRecord(sl.done, st));
+    *dev = sl.dev.p;
+    return PG_OK;
+}
+
+void pg_ring_release(UploadRing& ring) {
+    for (auto& sl : ring.slot) {
+        if (sl.done) (void)hipEventDestroy(sl.done);
+        pg_release(sl.host);
+        pg_release(sl.dev);
+    }
+    ring = UploadRing();
+}
+
 namespace {
 
 // state setters are forwarded to the sub-handles of a multi-device handle (message of a failing one is kept)
@@ -737,6 +759,7 @@ void pg_destroy(pg_handle* h) {
     pg_smpl_release(h);
     pg_kploss_release(h);
     pg_trainloss_release(h);
+    pg_regressor_release(h);
     pg_frames_release(h);
     pg_scene_release(h);
     for (auto& pr : h->ev_aux) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }

@@ -271,19 +271,12 @@ int pg_launch_batch_gather(const pgk::BatchGather* g, void* stream) {
 namespace {
 
 // what the four entry points keep in the handle: the tile offsets of the last pg_pixel_index_count (and what they were counted on),
-// and a ring of pinned host / device buffer pairs for a call's image rows.  A slot is reused only after the copy out of its host
-// buffer has finished (its event), so a call neither waits for the stream nor overwrites rows still in flight.
+// and the upload ring (pg_handle.h) of a call's image rows
 struct BatchState {
     DevBuf tiles;
     const void* masks = nullptr;
     int64_t F = 0, P = 0;
-    static constexpr int SLOTS = 8;
-    struct Slot {
-        PinBuf host;
-        DevBuf dev;
-        hipEvent_t done = nullptr;
-    } slot[SLOTS];
-    unsigned next = 0;
+    UploadRing rows;
 };
 
 BatchState* batch_state(pg_handle* h) {
@@ -293,17 +286,10 @@ BatchState* batch_state(pg_handle* h) {
 
 // `words` (checked by the caller) -> the next slot's device buffer, on stream st
 int batch_upload(pg_handle* h, const std::vector<int32_t>& words, hipStream_t st, const int** dev) {
-    BatchState* s = batch_state(h);
-    BatchState::Slot& sl = s->slot[s->next++ % BatchState::SLOTS];
-    if (!sl.done) PG_HIP(h, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
-    else PG_HIP(h, hipEventSynchronize(sl.done));
-    const size_t bytes = words.size() * sizeof(int32_t);
-    PG_TRY(pg_grow_pinned(h, sl.host, bytes, "batch row staging", (words.size() + words.size() / 2 + 64) * sizeof(int32_t)));
-    PG_TRY(pg_grow(h, sl.dev, sl.host.bytes, "batch row buffer"));
-    std::memcpy(sl.host.p, words.data(), bytes);
-    PG_HIP(h, hipMemcpyAsync(sl.dev.p, sl.host.p, bytes, hipMemcpyHostToDevice, st));
-    PG_HIP(h, hipEventRecord(sl.done, st));
-    *dev = sl.dev.as<const int>();
+    const void* p = nullptr;
+    PG_TRY(pg_ring_upload(h, batch_state(h)->rows, words.data(), words.size() * sizeof(int32_t),
+                          (words.size() + words.size() / 2 + 64) * sizeof(int32_t), "batch row buffer", st, &p));
+    *dev = static_cast<const int*>(p);
     return PG_OK;
 }
 
@@ -329,11 +315,7 @@ void pg_batch_release(pg_handle* h) {
     if (!h || !h->batch) return;
     auto* s = static_cast<BatchState*>(h->batch);
     pg_release(s->tiles);
-    for (auto& sl : s->slot) {
-        if (sl.done) (void)hipEventDestroy(sl.done);
-        pg_release(sl.host);
-        pg_release(sl.dev);
-    }
+    pg_ring_release(s->rows);
     delete s;
     h->batch = nullptr;
 }

@@ -1,6 +1,6 @@
 // pg_handle.h -- the renderer handle behind the C ABI (include/posegen_hip.h), shared by the translation units that implement
 // its entry points: pg_api.hip (handle, weights, ray-level rendering), pg_frames.hip (frames), pg_train.hip (the training step),
-// pg_mesh.hip, pg_poseopt.hip, pg_batch.hip, pg_metrics.hip, pg_scene.hip, pg_posescore.hip, pg_smpl.hip, pg_kploss.hip, pg_trainloss.hip.  Each of the last eleven keeps its own state behind a void* of the handle.
+// pg_mesh.hip, pg_poseopt.hip, pg_batch.hip, pg_metrics.hip, pg_scene.hip, pg_posescore.hip, pg_smpl.hip, pg_kploss.hip, pg_trainloss.hip, pg_regressor.hip.  Each of the last twelve keeps its own state behind a void* of the handle.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -66,6 +66,7 @@ struct pg_handle : Subject {
     void* smpl = nullptr;            // the body model (pg_smpl.hip): feature rows, joint transforms and regressor partial sums of a pose slice
     void* kploss = nullptr;          // pose losses (pg_kploss.hip): the per-pose values of a pg_pose_loss call that passes no per_pose
     void* trainloss = nullptr;       // training losses (pg_trainloss.hip): partial sums, the device copies of kp_idx and of the norms' tensor table
+    void* regressor = nullptr;       // the regressor's input batches (pg_regressor.hip): the item-upload ring of pg_regressor_input
     void* frames = nullptr;          // pg_render_frames (pg_frames.hip): per-device buffers, copy stream and events kept between calls
     void* scene = nullptr;           // pg_render_scene (pg_scene.hip): the people's sample lists and the maps of the boxes' bounding rectangle
     std::vector<float> grid_t;       // pg_grid_density: the host copy of the axis table t[R] while its upload is in flight
@@ -81,6 +82,7 @@ void pg_posescore_release(pg_handle* h);
 void pg_smpl_release(pg_handle* h);
 void pg_kploss_release(pg_handle* h);
 void pg_trainloss_release(pg_handle* h);
+void pg_regressor_release(pg_handle* h);
 void pg_frames_release(pg_handle* h);
 void pg_scene_release(pg_handle* h);
 // scratch of pg_launch_sample_coarse for n rays in chunks of `chunk` (null when the one-launch form runs)
@@ -97,6 +99,22 @@ int pg_fail(pg_handle* h, int code, const char* fmt, ...);
 // out of it have finished.
 int pg_grow(pg_handle* h, DevBuf& b, size_t need, const char* what, size_t alloc = 0);
 int pg_grow_pinned(pg_handle* h, PinBuf& b, size_t need, const char* what, size_t alloc = 0);
+
+// A ring of pinned host / device buffer pairs for a call's small host arrays (a batch's image rows, a regressor batch's crop items).
+// A slot is reused only after the copy out of its host buffer has finished (its event), so a call neither waits for the stream nor
+// overwrites data still in flight.  pg_ring_upload copies `bytes` of `src` into the next slot (grown to `alloc` bytes when too small)
+// and returns the slot's device buffer.
+struct UploadRing {
+    static constexpr int SLOTS = 8;
+    struct Slot {
+        PinBuf host;
+        DevBuf dev;
+        hipEvent_t done = nullptr;
+    } slot[SLOTS];
+    unsigned next = 0;
+};
+int pg_ring_upload(pg_handle* h, UploadRing& ring, const void* src, size_t bytes, size_t alloc, const char* what, hipStream_t st, const void** dev);
+void pg_ring_release(UploadRing& ring);
 
 // A buffer carved into arrays, each on a 256-byte boundary.  The list of take<T>(count) calls runs twice: over a Carver without a
 // base, which only adds the sizes up (the pointers come out null), then over the allocation -- an array cannot be carved without
