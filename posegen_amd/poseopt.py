@@ -70,6 +70,15 @@ def ray_segments(idxs) -> RaySegments:
     return RaySegments(unique, np.ascontiguousarray(inverse, dtype=np.int32), seg_start, np.ascontiguousarray(seg_rays))
 
 
+def _index_tensor(a, device) -> torch.Tensor:
+    """host integers as a long tensor on `device`; on a HIP device through pinned memory, so that the upload is enqueued on the
+    current stream like the kernels that follow it instead of making the host wait for that stream"""
+    t = torch.as_tensor(np.asarray(a), dtype=torch.long)
+    if torch.device(device).type == "cuda":
+        return t.pin_memory().to(device, non_blocking=True)
+    return t.to(device)
+
+
 def _i32(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(_I32P)
 
@@ -209,7 +218,7 @@ class HipPoseOptLayer(torch.nn.Module):
 
     # ---- the reference's accessors (pose_opt.py:318-369) ---------------------------------------------------------------
     def idx_to_params(self, idx):
-        idx = torch.as_tensor(np.asarray(idx), dtype=torch.long, device=self.pelvis.device)
+        idx = _index_tensor(idx, self.pelvis.device)
         pelvis = self.pelvis[idx]
         if self.kp_map is None:
             return pelvis, self.bones[idx]
@@ -226,7 +235,7 @@ class HipPoseOptLayer(torch.nn.Module):
             return self.rest_pose
         if rest_pose_idxs is None:
             rest_pose_idxs = np.asarray(self.rest_pose_idxs)[kp_idxs]
-        return self.rest_pose[torch.as_tensor(np.asarray(rest_pose_idxs), dtype=torch.long, device=self.rest_pose.device)]
+        return self.rest_pose[_index_tensor(rest_pose_idxs, self.rest_pose.device)]
 
     def forward(self, idxs=None, rest_pose_idxs=None):
         """`calculate_kinematic` (pose_opt.py:372-445): (kps [n,24,3], bones [n,24,6], skts [n,24,4,4], l2ws [n,24,4,4],
@@ -244,5 +253,5 @@ class HipPoseOptLayer(torch.nn.Module):
             raise ValueError(f"{rest.shape[0]} rest poses for {len(seg.unique)} unique poses")
         pelvis, bone = self.idx_to_params(seg.unique)
         kps, skts, l2ws, rots = _KinematicsFn.apply(self, seg, pelvis, bone, rest)
-        inverse = torch.as_tensor(seg.inverse, dtype=torch.long, device=bone.device)
+        inverse = _index_tensor(seg.inverse, bone.device)
         return kps, bone[inverse], skts, l2ws, rots

@@ -43,6 +43,18 @@ def model_for(cfg: RenderConfig, seed: int):
     return wc, wf, tv, td
 
 
+def single_cfg(g) -> RenderConfig:
+    """the model of a single-net fixture, from its own keys"""
+    return RenderConfig(n_samples=int(g["n_samples"]), n_importance=int(g["n_importance"]), single_net=bool(int(g["single_net"])),
+                        multires_views=int(g["multires_views"]))
+
+
+def single_model(cfg, g):
+    w, _, tv, td = syn.make_model(cfg, int(g["seed_model"]))
+    assert weights_digest(w) == str(g["digest_coarse"]), "synthetic weight recipe drifted"
+    return w, tv, td
+
+
 def weights_digest(w):
     import hashlib
     h = hashlib.sha256()

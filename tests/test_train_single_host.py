@@ -11,22 +11,11 @@ import torch
 from oracle import anerf_oracle as orc
 from posegen_amd import synthetic as syn
 from posegen_amd.config import RenderConfig, surreal_config, surreal_single_config
-from tests.helpers import GOLDEN, default_dtype, golden_draws, load_golden, loss_of, oracle_cfg, weights_digest
+from tests.helpers import (GOLDEN, default_dtype, golden_draws, load_golden, loss_of, oracle_cfg, single_cfg, single_model,  # noqa: F401
+                           weights_digest)
 from tools.gen_golden import grad_sample_index
 
 FIXTURES = ["train_grads_single", "train_grads_single_v4", "train_grads_single_pose"]
-
-
-def single_cfg(g) -> RenderConfig:
-    """the fixture's model, from its own keys"""
-    return RenderConfig(n_samples=int(g["n_samples"]), n_importance=int(g["n_importance"]), single_net=bool(int(g["single_net"])),
-                        multires_views=int(g["multires_views"]))
-
-
-def single_model(cfg, g):
-    w, _, tv, td = syn.make_model(cfg, int(g["seed_model"]))
-    assert weights_digest(w) == str(g["digest_coarse"]), "synthetic weight recipe drifted"
-    return w, tv, td
 
 
 def single_net_render(rb, skts, cyls, ocfg, w, S, N, draws=None):
