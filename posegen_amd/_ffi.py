@@ -12,6 +12,8 @@ import ctypes as C
 import os
 from typing import Optional
 
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "_lib", "libposegen_hip.so")
 
@@ -264,3 +266,24 @@ def check(lib: C.CDLL, handle, rc: int):
     if rc != PG_OK:
         msg = lib.pg_last_error(handle)
         raise PgError(rc, msg.decode() if msg else "unknown error")
+
+
+def ptr(t):
+    """a tensor's device pointer as the c_void_p an entry point takes; None stays None (NULL)"""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def call(renderer, name: str, *args):
+    """The stream-taking entry point `name` on `renderer`'s handle and current stream: tensors among `args` go as their pointers,
+    everything else as given; a negative return code raises (`renderer._check`).  No device guard is entered: the caller's covers
+    its allocations as well."""
+    fn = getattr(renderer.lib, name)
+    return renderer._check(fn(renderer.handle, renderer._stream(), *[ptr(a) if isinstance(a, torch.Tensor) else a for a in args]))
+
+
+def device_of(renderer, who: str, what: str) -> torch.device:
+    """The renderer's device, which must be a HIP one; `what` ends the refusal's "not on a HIP device" clause in the caller's words."""
+    device = torch.device(getattr(renderer, "device", "cpu"))
+    if device.type != "cuda":
+        raise NotImplementedError(f"{who}: the renderer is on {device}, not on a HIP device{what} there is no CPU path")
+    return device

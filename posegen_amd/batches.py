@@ -28,10 +28,6 @@ POSE_KEYS = ("kp3d", "bones", "skts", "cyls")
 CHOICE_MESSAGE = "Cannot take a larger sample than population when 'replace=False'"
 
 
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
 def _i32p(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(_I32P)
 
@@ -128,14 +124,13 @@ class DeviceImageBank:
         r, F, P = self.renderer, self.F, self.P
         with torch.cuda.device(self.device):
             counts = torch.empty(F, dtype=torch.int64, device=self.device)
-            r._check(r.lib.pg_pixel_index_count(r.handle, r._stream(), _ptr(self.sampling_masks), F, P, _ptr(counts)))
+            _ffi.call(r, "pg_pixel_index_count", self.sampling_masks, F, P, counts)
             self.start = torch.zeros(F + 1, dtype=torch.int64, device=self.device)
             torch.cumsum(counts, 0, out=self.start[1:])
             self.counts = counts.cpu().numpy()                             # the one copy back
             self.total = int(self.counts.sum())
             self.ids = torch.empty(max(self.total, 1), dtype=torch.int32, device=self.device)
-            r._check(r.lib.pg_pixel_index_emit(r.handle, r._stream(), _ptr(self.sampling_masks), F, P, _ptr(self.start), self.total,
-                                               _ptr(self.ids)))
+            _ffi.call(r, "pg_pixel_index_emit", self.sampling_masks, F, P, self.start, self.total, self.ids)
 
     @property
     def nbytes(self) -> int:
@@ -280,8 +275,8 @@ class RayBatchSource:
         with torch.cuda.device(self.device):
             draws = torch.rand(len(q), k, dtype=torch.float64, device=self.device, generator=self.generator)
             pix = torch.empty(len(q) * k, dtype=torch.int32, device=self.device)
-            r._check(r.lib.pg_batch_sample_pixels(r.handle, r._stream(), _ptr(bank.ids), _ptr(bank.start), bank.counts.ctypes.data_as(_I64P),
-                                                  bank.F, _i32p(img_rows), len(q), k, _ptr(draws), _ptr(pix)))
+            _ffi.call(r, "pg_batch_sample_pixels", bank.ids, bank.start, bank.counts.ctypes.data_as(_I64P), bank.F, _i32p(img_rows), len(q), k,
+                      draws, pix)
             return self._gather(q, img_rows, pix)
 
     def gather(self, img_idxs, pixel_idxs) -> RayBatch:
@@ -321,9 +316,8 @@ class RayBatchSource:
                        ray_batch=torch.empty(n, 11, device=dev), pixel_idxs=pix)
         if bank.bkgds is not None:
             out["bgs"] = torch.empty(n, 3, device=dev)
-        r._check(r.lib.pg_batch_gather(r.handle, r._stream(), C.byref(bank.struct), _i32p(img_rows), _i32p(cam_rows), n_img, k, _ptr(pix),
-                                       _ptr(out["target_s"]), _ptr(out["fgs"]), _ptr(out.get("bgs")), _ptr(out["rays_o"]),
-                                       _ptr(out["rays_d"]), _ptr(out["ray_batch"])))
+        _ffi.call(r, "pg_batch_gather", C.byref(bank.struct), _i32p(img_rows), _i32p(cam_rows), n_img, k, pix, out["target_s"], out["fgs"],
+                  out.get("bgs"), out["rays_o"], out["rays_d"], out["ray_batch"])
         # the per-image integers go up in one pinned array; everything per ray is formed from it on the device
         host = torch.from_numpy(np.stack([q, self._rows("kp_idx", q), self._rows("cam_idx", q), self._rows("pose_row", q)]).astype(np.int64))
         per_img = host.pin_memory().to(dev, non_blocking=True)

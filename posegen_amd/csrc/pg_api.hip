@@ -640,6 +640,19 @@ int pg_check_cyl_stride(pg_handle* h, long long v, bool stage) {
     if (v == 0 || v == 5) return PG_OK;
     return pg_fail(h, PG_EINVAL, stage ? "cyl_stride must be 0 or 5" : "cyl_stride must be 0 (shared) or 5 (per ray)");
 }
+int pg_check_joint_selection(pg_handle* h, const char* who, int J_in, const int32_t* joints, int* J, int root, bool once) {
+    if (J_in < 1) return pg_fail(h, PG_EINVAL, "%s: J_in = %d", who, J_in);
+    if (!joints) *J = J_in;
+    if (*J < 1 || *J > PG_POSE_MAX_JOINTS) return pg_fail(h, PG_EINVAL, "%s: J = %d is outside [1, %d]", who, *J, PG_POSE_MAX_JOINTS);
+    if (joints)
+        for (int j = 0; j < *J; ++j) {
+            if (joints[j] < 0 || joints[j] >= J_in) return pg_fail(h, PG_EINVAL, "%s: joints[%d] = %d is outside [0, %d)", who, j, joints[j], J_in);
+            for (int k = 0; once && k < j; ++k)
+                if (joints[k] == joints[j]) return pg_fail(h, PG_EINVAL, "%s: joints[%d] = joints[%d] = %d (a joint is selected once)", who, k, j, joints[j]);
+        }
+    if (root < -1 || root >= J_in) return pg_fail(h, PG_EINVAL, "%s: root = %d is outside [-1, %d)", who, root, J_in);
+    return PG_OK;
+}
 
 int pg_sc_scratch(pg_handle* h, long long n, int chunk, double** out) {
     *out = nullptr;
@@ -750,18 +763,9 @@ void pg_destroy(pg_handle* h) {
     (void)hipDeviceSynchronize();
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
     for (DevBuf* b : {&h->fws, &h->rec, &h->sc_part}) pg_release(*b);
-    pg_train_release(h);
-    pg_mesh_release(h);
-    pg_poseopt_release(h);
-    pg_batch_release(h);
-    pg_metrics_release(h);
-    pg_posescore_release(h);
-    pg_smpl_release(h);
-    pg_kploss_release(h);
-    pg_trainloss_release(h);
-    pg_regressor_release(h);
-    pg_frames_release(h);
-    pg_scene_release(h);
+    // the modules' states, in slot order; their destructors free device memory, streams and events of h->device, which is current
+    // here (no module sets the device again)
+    h->mods.clear();
     for (auto& pr : h->ev_aux) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
     release_subject(*h);
     for (Subject& sub : h->bank.parked) release_subject(sub);
@@ -1465,7 +1469,7 @@ struct RayBufs {
         const size_t n = (size_t)r.n, S = r.S, SF = r.S + r.N;
         const bool hier = r.N > 0, single = NP > 0;
         const pg_outputs* o = r.out;
-        auto in_place = [](float* p) { return p && reinterpret_cast<uintptr_t>(p) % 256 == 0; };
+        auto in_place = [](float* p) { return p && !pg_misaligned(p, 256); };
         return carve_ws(h, [&](Carver& c) {
             nf = c.take<float>(n * 2);
             zc = in_place(o->z_coarse) ? o->z_coarse : c.take<float>(n * S);

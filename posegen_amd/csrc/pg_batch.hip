@@ -272,22 +272,21 @@ namespace {
 
 // what the four entry points keep in the handle: the tile offsets of the last pg_pixel_index_count (and what they were counted on),
 // and the upload ring (pg_handle.h) of a call's image rows
-struct BatchState {
+struct BatchState : ModuleState {
+    static constexpr ModuleSlot SLOT = MOD_BATCH;
+    ~BatchState() override { pg_release(tiles); pg_ring_release(rows); }
     DevBuf tiles;
     const void* masks = nullptr;
     int64_t F = 0, P = 0;
     UploadRing rows;
 };
 
-BatchState* batch_state(pg_handle* h) {
-    if (!h->batch) h->batch = new BatchState();
-    return static_cast<BatchState*>(h->batch);
-}
-
 // `words` (checked by the caller) -> the next slot's device buffer, on stream st
 int batch_upload(pg_handle* h, const std::vector<int32_t>& words, hipStream_t st, const int** dev) {
     const void* p = nullptr;
-    PG_TRY(pg_ring_upload(h, batch_state(h)->rows, words.data(), words.size() * sizeof(int32_t),
+    BatchState* s = nullptr;
+    PG_TRY(pg_state(h, s));
+    PG_TRY(pg_ring_upload(h, s->rows, words.data(), words.size() * sizeof(int32_t),
                           (words.size() + words.size() / 2 + 64) * sizeof(int32_t), "batch row buffer", st, &p));
     *dev = static_cast<const int*>(p);
     return PG_OK;
@@ -311,22 +310,14 @@ int check_rows(pg_handle* h, const char* who, const char* what, const int32_t* r
 
 }  // namespace
 
-void pg_batch_release(pg_handle* h) {
-    if (!h || !h->batch) return;
-    auto* s = static_cast<BatchState*>(h->batch);
-    pg_release(s->tiles);
-    pg_ring_release(s->rows);
-    delete s;
-    h->batch = nullptr;
-}
-
 extern "C" {
 
 int pg_pixel_index_count(pg_handle* h, void* stream, const uint8_t* sampling_masks, int64_t F, int64_t P, int64_t* counts) {
     if (!h) return pg_fail(nullptr, PG_EINVAL, "null handle");
     PG_TRY(check_index_args(h, "pg_pixel_index_count", sampling_masks, F, P));
     if (!counts) return pg_fail(h, PG_EINVAL, "pg_pixel_index_count: counts is null");
-    BatchState* s = batch_state(h);
+    BatchState* s = nullptr;
+    PG_TRY(pg_state(h, s));
     s->masks = nullptr;
     const int64_t ntiles = (P + pg_batch_tile_pixels() - 1) / pg_batch_tile_pixels();
     PG_HIP(h, hipSetDevice(h->device));
@@ -342,7 +333,8 @@ int pg_pixel_index_emit(pg_handle* h, void* stream, const uint8_t* sampling_mask
     if (!h) return pg_fail(nullptr, PG_EINVAL, "null handle");
     PG_TRY(check_index_args(h, "pg_pixel_index_emit", sampling_masks, F, P));
     if (!start || total < 0 || (total > 0 && !ids)) return pg_fail(h, PG_EINVAL, "pg_pixel_index_emit: null start / ids or negative total");
-    BatchState* s = batch_state(h);
+    BatchState* s = nullptr;
+    PG_TRY(pg_state(h, s));
     if (s->masks != sampling_masks || s->F != F || s->P != P)
         return pg_fail(h, PG_ESTATE, "pg_pixel_index_emit: masks, F and P are not those of the last pg_pixel_index_count");
     if (total == 0) return PG_OK;

@@ -88,7 +88,18 @@ namespace {
 constexpr int NBUF = 2;                 // frame buffers in rotation: frame k+1 composes while frame k copies out
 constexpr size_t POSE_BYTES = (384 + 8) * sizeof(float);    // skts + cyl of one frame
 
-struct FramesState {
+struct FramesState : ModuleState {
+    static constexpr ModuleSlot SLOT = MOD_FRAMES;
+    ~FramesState() override {
+        for (int b = 0; b < NBUF; ++b) {
+            pg_release(frame[b]);
+            if (copied[b]) (void)hipEventDestroy(copied[b]);
+            if (composed[b]) (void)hipEventDestroy(composed[b]);
+        }
+        if (copy_stream) (void)hipStreamDestroy(copy_stream);
+        for (DevBuf* b : {&bg, &poses, &part}) pg_release(*b);
+        pg_release(stage);
+    }
     size_t hw = 0;                      // pixels the frame buffers were sized for
     DevBuf frame[NBUF];                 // FrameLayout
     hipEvent_t composed[NBUF] = {};     // buffer b holds a finished frame (render stream)
@@ -100,14 +111,14 @@ struct FramesState {
     PinBuf stage;                       // pinned host staging of NBUF frames (results that land in pageable memory)
 };
 
-FramesState& frames_of(pg_handle* h) {
-    if (!h->frames) h->frames = new FramesState();
-    return *static_cast<FramesState*>(h->frames);
-}
+// the state of a device of the running call (frames_ensure has created it)
+FramesState& frames_of(pg_handle* h) { return *h->mods.peek<FramesState>(); }
 
 // grow-only: nothing is allocated or freed by a call whose sizes an earlier call has seen
 int frames_ensure(pg_handle* h, size_t hw, size_t n_frames, size_t part_rays, const float* bg_host, bool staged) {
-    FramesState& c = frames_of(h);
+    FramesState* cp = nullptr;
+    PG_TRY(pg_state(h, cp));
+    FramesState& c = *cp;
     const FrameLayout lay{hw};
     PG_HIP(h, hipSetDevice(h->device));
     if (!c.copy_stream) PG_HIP(h, hipStreamCreateWithFlags(&c.copy_stream, hipStreamNonBlocking));
@@ -283,22 +294,6 @@ struct FramesCall {
 };
 
 }  // namespace
-
-void pg_frames_release(pg_handle* h) {
-    if (!h || !h->frames) return;
-    auto* c = static_cast<FramesState*>(h->frames);
-    (void)hipSetDevice(h->device);
-    for (int b = 0; b < NBUF; ++b) {
-        pg_release(c->frame[b]);
-        if (c->copied[b]) (void)hipEventDestroy(c->copied[b]);
-        if (c->composed[b]) (void)hipEventDestroy(c->composed[b]);
-    }
-    if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
-    for (DevBuf* b : {&c->bg, &c->poses, &c->part}) pg_release(*b);
-    pg_release(c->stage);
-    delete c;
-    h->frames = nullptr;
-}
 
 extern "C" {
 

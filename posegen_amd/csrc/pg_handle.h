@@ -1,6 +1,8 @@
 // pg_handle.h -- the renderer handle behind the C ABI (include/posegen_hip.h), shared by the translation units that implement
 // its entry points: pg_api.hip (handle, weights, ray-level rendering), pg_frames.hip (frames), pg_train.hip (the training step),
-// pg_mesh.hip, pg_poseopt.hip, pg_batch.hip, pg_metrics.hip, pg_scene.hip, pg_posescore.hip, pg_smpl.hip, pg_kploss.hip, pg_trainloss.hip, pg_regressor.hip.  Each of the last twelve keeps its own state behind a void* of the handle.
+// pg_mesh.hip, pg_poseopt.hip, pg_batch.hip, pg_metrics.hip, pg_scene.hip, pg_posescore.hip, pg_smpl.hip, pg_kploss.hip,
+// pg_trainloss.hip, pg_regressor.hip.  Each of the last twelve keeps its state in its slot of the handle's table (pg_modules.h):
+// pg_state creates it on first use, h->mods.peek reads it, and the state's destructor frees what it owns.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,6 +12,7 @@
 #include "../../include/posegen_hip.h"
 #include "pg_bank.h"
 #include "pg_layout.h"
+#include "pg_modules.h"
 
 // A buffer that only ever grows (pg_grow / pg_grow_pinned below): on the device, or page-locked on the host (two types: neither
 // is ever freed as the other).
@@ -57,42 +60,30 @@ struct pg_handle : Subject {
     int64_t aux_n = 0;               // record launches / their device time already folded in by a pg_profile_read
     double aux_ms = 0.0;
     int64_t prof_points = 0;
-    void* train = nullptr;           // the training tape (pg_train.hip): activations of the last pg_train_forward
-    void* mesh = nullptr;            // marching-cubes state of the last pg_mesh_count (pg_mesh.hip): flags, cases, scans
-    void* poseopt = nullptr;         // the pose layer's index buffer (pg_poseopt.hip): joint tree and ray segments of the last call
-    void* batch = nullptr;           // training batches (pg_batch.hip): tile offsets of the last pg_pixel_index_count, the row-upload ring
-    void* metrics = nullptr;         // frame scores (pg_metrics.hip): the tiles' partial sums of pg_frame_metrics
-    void* posescore = nullptr;       // pose scores (pg_posescore.hip): the waves' partial sums and threshold counts of pg_pose_scores
-    void* smpl = nullptr;            // the body model (pg_smpl.hip): feature rows, joint transforms and regressor partial sums of a pose slice
-    void* kploss = nullptr;          // pose losses (pg_kploss.hip): the per-pose values of a pg_pose_loss call that passes no per_pose
-    void* trainloss = nullptr;       // training losses (pg_trainloss.hip): partial sums, the device copies of kp_idx and of the norms' tensor table
-    void* regressor = nullptr;       // the regressor's input batches (pg_regressor.hip): the item-upload ring of pg_regressor_input
-    void* frames = nullptr;          // pg_render_frames (pg_frames.hip): per-device buffers, copy stream and events kept between calls
-    void* scene = nullptr;           // pg_render_scene (pg_scene.hip): the people's sample lists and the maps of the boxes' bounding rectangle
+    Modules mods;                    // the twelve modules' states (pg_modules.h; pg_state below): each struct says beside its code what it keeps
     std::vector<float> grid_t;       // pg_grid_density: the host copy of the axis table t[R] while its upload is in flight
     bool tape_out = false;           // a pg_train_forward whose backward has not run yet: the bank stays as it is until then
 };
 
-extern "C" void pg_train_release(pg_handle* h);
-extern "C" void pg_mesh_release(pg_handle* h);
-extern "C" void pg_poseopt_release(pg_handle* h);
-void pg_batch_release(pg_handle* h);
-void pg_metrics_release(pg_handle* h);
-void pg_posescore_release(pg_handle* h);
-void pg_smpl_release(pg_handle* h);
-void pg_kploss_release(pg_handle* h);
-void pg_trainloss_release(pg_handle* h);
-void pg_regressor_release(pg_handle* h);
-void pg_frames_release(pg_handle* h);
-void pg_scene_release(pg_handle* h);
 // scratch of pg_launch_sample_coarse for n rays in chunks of `chunk` (null when the one-launch form runs)
 int pg_sc_scratch(pg_handle* h, long long n, int chunk, double** out);
 // the pose / cylinder stride of a ray-level call (`stage`: the stage entry points' shorter wording)
 int pg_check_pose_stride(pg_handle* h, long long v, bool stage);
 int pg_check_cyl_stride(pg_handle* h, long long v, bool stage);
+// the joint selection of a pose call `who` (pg_pose_scores, pg_pose_loss): J_in, `joints` (null: all, and *J becomes J_in), *J against
+// PG_POSE_MAX_JOINTS, the entries' range, `root`, and with `once` that no joint is named twice
+constexpr int PG_POSE_MAX_JOINTS = 64;
+int pg_check_joint_selection(pg_handle* h, const char* who, int J_in, const int32_t* joints, int* J, int root, bool once);
+// p is not on a multiple of `a` bytes (a: the size of the element it points to)
+inline bool pg_misaligned(const void* p, size_t a) { return reinterpret_cast<uintptr_t>(p) % a != 0; }
 
 // records the message (handle and thread-local "last error") and returns `code`
 int pg_fail(pg_handle* h, int code, const char* fmt, ...);
+// the module's state S on the handle, created on first use
+template <class S> int pg_state(pg_handle* h, S*& out) {
+    out = h->mods.get<S>();
+    return out ? PG_OK : pg_fail(h, PG_ENOMEM, "out of memory for a module's state");
+}
 // `need` bytes in a buffer that only ever grows, on the current device: one that is too small is freed (after a
 // hipDeviceSynchronize: what read it has to finish first; its contents are void) and allocated again with `alloc` bytes (0: need).
 // A failing allocation leaves the buffer empty.  The pinned twin frees without the synchronise: its owner knows when the copies

@@ -230,9 +230,12 @@ namespace {
 
 // the per-pose values of a pg_pose_loss call that passes no per_pose.  One buffer per handle: calls on one handle are serialised by
 // the caller (as pg_posescore.hip).
-struct KpLossState {
+struct KpLossState : ModuleState {
+    static constexpr ModuleSlot SLOT = MOD_KPLOSS;
+    ~KpLossState() override { pg_release(vals); }
     DevBuf vals;
 };
+static_assert(pgkl::MAXJ == PG_POSE_MAX_JOINTS, "pg_check_joint_selection bounds J for the kernel's joint table");
 
 template <bool AXIS>
 int kin_bwd(pg_handle* h, const char* who, void* stream, int64_t n_poses, const void* in, const double* bone_offsets, const int32_t* parents,
@@ -255,14 +258,6 @@ int kin_bwd(pg_handle* h, const char* who, void* stream, int64_t n_poses, const 
 
 }  // namespace
 
-void pg_kploss_release(pg_handle* h) {
-    if (!h || !h->kploss) return;
-    auto* s = static_cast<KpLossState*>(h->kploss);
-    pg_release(s->vals);
-    delete s;
-    h->kploss = nullptr;
-}
-
 extern "C" int pg_pose_kinematics_bwd(pg_handle* h, void* stream, int64_t n_poses, const double* bones, const double* bone_offsets,
                                       const int32_t* parents, const float* d_kps, double* d_bones) {
     return kin_bwd<true>(h, "pg_pose_kinematics_bwd", stream, n_poses, bones, bone_offsets, parents, d_kps, d_bones);
@@ -279,28 +274,18 @@ extern "C" int pg_pose_loss(pg_handle* h, void* stream, int64_t B, int J_in, con
     if (!h) return pg_fail(nullptr, PG_EINVAL, "null handle");
     if (!pred || !gt || !summary) return pg_fail(h, PG_EINVAL, "%s: pred, gt and summary are required", who);
     if (B < 1 || B > 0x7fffffffll * pgkl::WAVES) return pg_fail(h, PG_EINVAL, "%s: B = %lld", who, (long long)B);
-    if (J_in < 1) return pg_fail(h, PG_EINVAL, "%s: J_in = %d", who, J_in);
-    if (!joints) J = J_in;
-    if (J < 1 || J > pgkl::MAXJ) return pg_fail(h, PG_EINVAL, "%s: J = %d is outside [1, %d]", who, J, pgkl::MAXJ);
-    if (joints)
-        for (int j = 0; j < J; ++j) {
-            if (joints[j] < 0 || joints[j] >= J_in) return pg_fail(h, PG_EINVAL, "%s: joints[%d] = %d is outside [0, %d)", who, j, joints[j], J_in);
-            for (int k = 0; k < j; ++k)
-                if (joints[k] == joints[j]) return pg_fail(h, PG_EINVAL, "%s: joints[%d] = joints[%d] = %d (a joint is selected once)", who, k, j, joints[j]);
-        }
-    if (root < -1 || root >= J_in) return pg_fail(h, PG_EINVAL, "%s: root = %d is outside [-1, %d)", who, root, J_in);
+    PG_TRY(pg_check_joint_selection(h, who, J_in, joints, &J, root, true));
     if (kind != PG_POSE_LOSS_MPJPE && kind != PG_POSE_LOSS_NORM_MATCHED) return pg_fail(h, PG_EINVAL, "%s: unknown kind %d", who, kind);
     if (std::isnan(weight) || std::isnan(cap) || cap <= 0.0) return pg_fail(h, PG_EINVAL, "%s: weight = %g, cap = %g (no NaN; cap > 0)", who, weight, cap);
-    if (reinterpret_cast<uintptr_t>(pred) % sizeof(float) || reinterpret_cast<uintptr_t>(gt) % sizeof(float) ||
-        reinterpret_cast<uintptr_t>(d_pred) % sizeof(float) || reinterpret_cast<uintptr_t>(d_gt) % sizeof(float) ||
-        reinterpret_cast<uintptr_t>(per_pose) % sizeof(double) || reinterpret_cast<uintptr_t>(summary) % sizeof(double))
+    if (pg_misaligned(pred, sizeof(float)) || pg_misaligned(gt, sizeof(float)) || pg_misaligned(d_pred, sizeof(float)) ||
+        pg_misaligned(d_gt, sizeof(float)) || pg_misaligned(per_pose, sizeof(double)) || pg_misaligned(summary, sizeof(double)))
         return pg_fail(h, PG_EINVAL, "%s: an array is not aligned to its element", who);
 
     PG_HIP(h, hipSetDevice(h->device));
     double* vals = per_pose;
     if (!vals) {
-        if (!h->kploss) h->kploss = new KpLossState();
-        auto* s = static_cast<KpLossState*>(h->kploss);
+        KpLossState* s = nullptr;
+        PG_TRY(pg_state(h, s));
         PG_TRY(pg_grow(h, s->vals, (size_t)B * sizeof(double), "pose loss values", (size_t)(B + B / 2) * sizeof(double)));
         vals = s->vals.as<double>();
     }

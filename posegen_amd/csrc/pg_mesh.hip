@@ -169,7 +169,9 @@ unsigned blocks_for(long long n) {
 }
 
 // what pg_mesh_count leaves in the handle for pg_mesh_emit
-struct MeshState {
+struct MeshState : ModuleState {
+    static constexpr ModuleSlot SLOT = MOD_MESH;
+    ~MeshState() override { pg_release(arrays); pg_release(tmp); }
     DevBuf arrays;                      // the six arrays below (carve)
     unsigned char* flags = nullptr;     // [N]
     unsigned char* cases = nullptr;     // [N]
@@ -216,15 +218,6 @@ int pg_launch_gather_sigma(const float* raw, long long n, float* sigma, void* st
     return (int)hipGetLastError();
 }
 
-void pg_mesh_release(pg_handle* h) {
-    if (!h || !h->mesh) return;
-    auto* s = static_cast<pgm::MeshState*>(h->mesh);
-    pg_release(s->arrays);
-    pg_release(s->tmp);
-    delete s;
-    h->mesh = nullptr;
-}
-
 int pg_mesh_count(pg_handle* h, void* stream, const float* grid, int nx, int ny, int nz, float threshold, float clamp,
                   int64_t* n_vertices, int64_t* n_triangles) {
     using namespace pgm;
@@ -236,8 +229,8 @@ int pg_mesh_count(pg_handle* h, void* stream, const float* grid, int nx, int ny,
     if (N > MAX_POINTS) return pg_fail(h, PG_EINVAL, "pg_mesh_count: at most %lld grid points per call, got %lld", MAX_POINTS, N);
     if (threshold != threshold || clamp != clamp) return pg_fail(h, PG_EINVAL, "pg_mesh_count: threshold / clamp is NaN");
     PG_HIP(h, hipSetDevice(h->device));
-    if (!h->mesh) h->mesh = new MeshState();
-    auto* s = static_cast<MeshState*>(h->mesh);
+    MeshState* s = nullptr;
+    PG_TRY(pg_state(h, s));
     s->valid = false;
     hipStream_t st = static_cast<hipStream_t>(stream);
     Carver sizes;
@@ -269,7 +262,7 @@ int pg_mesh_emit(pg_handle* h, void* stream, const float* grid, int nx, int ny, 
     using namespace pgm;
     if (!h) return pg_fail(nullptr, PG_EINVAL, "null handle");
     if (!grid) return pg_fail(h, PG_EINVAL, "pg_mesh_emit: null grid");
-    auto* s = static_cast<MeshState*>(h->mesh);
+    const MeshState* s = h->mods.peek<MeshState>();
     if (!s || !s->valid || s->dims.nx != nx || s->dims.ny != ny || s->dims.nz != nz || !same_float(s->thr, threshold) || !same_float(s->clamp, clamp))
         return pg_fail(h, PG_ESTATE, "pg_mesh_emit: no pg_mesh_count of this grid shape, threshold and clamp precedes the call");
     if (nv != s->nv || nt != s->nt)

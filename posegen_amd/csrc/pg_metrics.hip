@@ -225,21 +225,11 @@ namespace {
 
 // the tiles' partial sums.  One buffer per handle: calls on one handle are serialised by the caller, and calls enqueued on different
 // streams have to be ordered by the caller as well.
-struct MetricsState {
+struct MetricsState : ModuleState {
+    static constexpr ModuleSlot SLOT = MOD_METRICS;
+    ~MetricsState() override { pg_release(slots); }
     DevBuf slots;
 };
-
-}  // namespace
-
-void pg_metrics_release(pg_handle* h) {
-    if (!h || !h->metrics) return;
-    auto* s = static_cast<MetricsState*>(h->metrics);
-    pg_release(s->slots);
-    delete s;
-    h->metrics = nullptr;
-}
-
-namespace {
 
 template <bool UP, bool VALID>
 void launch_tiles(const pgs::Args& a, int ntiles, hipStream_t st) {
@@ -268,7 +258,7 @@ int frame_metrics(pg_handle* h, const char* who, bool wide, void* stream, const 
             return pg_fail(h, PG_EINVAL, "%s: valid (%d, %d, %d, %d) is inverted or outside the %d x %d frame", who, valid[0], valid[1], valid[2],
                            valid[3], bank->H, bank->W);
     }
-    if (reinterpret_cast<uintptr_t>(rgb) % sizeof(float) || reinterpret_cast<uintptr_t>(sums) % sizeof(double))
+    if (pg_misaligned(rgb, sizeof(float)) || pg_misaligned(sums, sizeof(double)))
         return pg_fail(h, PG_EINVAL, "%s: rgb / sums are not aligned to their element", who);
     const uint8_t* bg = nullptr;
     if (flags & PG_METRICS_BG) {
@@ -278,8 +268,8 @@ int frame_metrics(pg_handle* h, const char* who, bool wide, void* stream, const 
         if (b < 0 || b >= bank->n_bkgd) return pg_fail(h, PG_EINVAL, "%s: bkgd_idxs[%d] = %d is outside [0, %lld)", who, img_row, b, (long long)bank->n_bkgd);
         bg = bank->bkgds + (size_t)b * bank->P * 3;
     }
-    if (!h->metrics) h->metrics = new MetricsState();
-    auto* s = static_cast<MetricsState*>(h->metrics);
+    MetricsState* s = nullptr;
+    PG_TRY(pg_state(h, s));
     const int w = box[2] - box[0], hh = box[3] - box[1];
     const int ntx = pgsp::tiles_along(w), nty = pgsp::tiles_along(hh);
     const bool up = wide && (rgb_h != bank->H || rgb_w != bank->W), val = wide && valid;

@@ -223,17 +223,14 @@ __global__ __launch_bounds__(THREADS) void poseopt_bwd_kernel(const float* __res
 
 // what the two entry points keep in the handle: the device copy of the joint tree and of the ray segments, and the host copy the
 // upload reads while it is in flight
-struct State {
+struct State : ModuleState {
+    static constexpr ModuleSlot SLOT = MOD_POSEOPT;
+    ~State() override { pg_release(d_idx); }
     DevBuf d_idx;
     std::vector<int32_t> host;
 };
 
 constexpr int TREE_WORDS = 64;         // parent [24] (the root's: -1) | level [24] | pad
-
-State* state_of(pg_handle* h) {
-    if (!h->poseopt) h->poseopt = new State();
-    return static_cast<State*>(h->poseopt);
-}
 
 // the checks both entry points share; fills words [0, 64) of `idx` with the tree, *max_depth with its depth
 int check_common(pg_handle* h, const char* who, int64_t n_poses, int rot_dim, const float* bones, const float* pelvis, const float* rest_pose,
@@ -265,20 +262,13 @@ int upload(pg_handle* h, State* s, hipStream_t st) {
 
 extern "C" {
 
-void pg_poseopt_release(pg_handle* h) {
-    if (!h || !h->poseopt) return;
-    auto* s = static_cast<pgp::State*>(h->poseopt);
-    pg_release(s->d_idx);
-    delete s;
-    h->poseopt = nullptr;
-}
-
 int pg_poseopt_forward(pg_handle* h, void* stream, int64_t n_poses, int rot_dim, const float* bones, const float* pelvis,
                        const float* rest_pose, int64_t rest_stride, const int32_t* parents, int64_t n_rays, const int32_t* ray_pose,
                        float* rots, float* l2ws, float* skts, float* kps) {
     using namespace pgp;
     if (!h) return pg_fail(nullptr, PG_EINVAL, "null handle");
-    State* s = state_of(h);
+    State* s = nullptr;
+    PG_TRY(pg_state(h, s));
     int max_depth = 0;
     PG_TRY(check_common(h, "pg_poseopt_forward", n_poses, rot_dim, bones, pelvis, rest_pose, rest_stride, parents, n_rays, s->host, &max_depth));
     if (!ray_pose && n_rays != n_poses)
@@ -315,7 +305,8 @@ int pg_poseopt_backward(pg_handle* h, void* stream, int64_t n_poses, int rot_dim
                         float* d_bones, float* d_pelvis) {
     using namespace pgp;
     if (!h) return pg_fail(nullptr, PG_EINVAL, "null handle");
-    State* s = state_of(h);
+    State* s = nullptr;
+    PG_TRY(pg_state(h, s));
     int max_depth = 0;
     PG_TRY(check_common(h, "pg_poseopt_backward", n_poses, rot_dim, bones, pelvis, rest_pose, rest_stride, parents, n_rays, s->host, &max_depth));
     if (!seg_start || (n_rays > 0 && !seg_rays) || !d_bones || !d_pelvis) return pg_fail(h, PG_EINVAL, "pg_poseopt_backward: null argument");

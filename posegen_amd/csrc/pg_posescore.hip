@@ -182,19 +182,14 @@ __global__ __launch_bounds__(THREADS) void pose_scores_sum_kernel(const uint8_t*
 namespace {
 
 // the waves' slots.  One buffer per handle: calls on one handle are serialised by the caller (as pg_metrics.hip).
-struct PoseScoreState {
+struct PoseScoreState : ModuleState {
+    static constexpr ModuleSlot SLOT = MOD_POSESCORE;
+    ~PoseScoreState() override { pg_release(slots); }
     DevBuf slots;
 };
+static_assert(pgq::MAXJ == PG_POSE_MAX_JOINTS, "pg_check_joint_selection bounds J for the kernel's joint table");
 
 }  // namespace
-
-void pg_posescore_release(pg_handle* h) {
-    if (!h || !h->posescore) return;
-    auto* s = static_cast<PoseScoreState*>(h->posescore);
-    pg_release(s->slots);
-    delete s;
-    h->posescore = nullptr;
-}
 
 extern "C" int pg_pose_scores(pg_handle* h, void* stream, int64_t B, int J_in, const float* pred, const float* gt, const int32_t* joints, int J,
                               int root, int align, const double* thresholds, int T, double* per_pose, float* aligned, float* joint_err,
@@ -203,23 +198,16 @@ extern "C" int pg_pose_scores(pg_handle* h, void* stream, int64_t B, int J_in, c
     if (!h) return pg_fail(nullptr, PG_EINVAL, "null handle");
     if (!pred || !gt || !summary) return pg_fail(h, PG_EINVAL, "%s: pred, gt and summary are required", who);
     if (B < 1) return pg_fail(h, PG_EINVAL, "%s: B = %lld", who, (long long)B);
-    if (J_in < 1) return pg_fail(h, PG_EINVAL, "%s: J_in = %d", who, J_in);
-    if (!joints) J = J_in;
-    if (J < 1 || J > pgq::MAXJ) return pg_fail(h, PG_EINVAL, "%s: J = %d is outside [1, %d]", who, J, pgq::MAXJ);
-    if (joints)
-        for (int j = 0; j < J; ++j)
-            if (joints[j] < 0 || joints[j] >= J_in) return pg_fail(h, PG_EINVAL, "%s: joints[%d] = %d is outside [0, %d)", who, j, joints[j], J_in);
-    if (root < -1 || root >= J_in) return pg_fail(h, PG_EINVAL, "%s: root = %d is outside [-1, %d)", who, root, J_in);
+    PG_TRY(pg_check_joint_selection(h, who, J_in, joints, &J, root, false));
     if (align < PG_POSE_ALIGN_NONE || align > PG_POSE_ALIGN_ROTATION) return pg_fail(h, PG_EINVAL, "%s: unknown alignment mode %d", who, align);
     if (T < 0 || T > pgq::MAXT) return pg_fail(h, PG_EINVAL, "%s: T = %d is outside [0, %d]", who, T, pgq::MAXT);
     if (T > 0 && !thresholds) return pg_fail(h, PG_EINVAL, "%s: T = %d without thresholds", who, T);
-    if (reinterpret_cast<uintptr_t>(pred) % sizeof(float) || reinterpret_cast<uintptr_t>(gt) % sizeof(float) ||
-        reinterpret_cast<uintptr_t>(aligned) % sizeof(float) || reinterpret_cast<uintptr_t>(joint_err) % sizeof(float) ||
-        reinterpret_cast<uintptr_t>(per_pose) % sizeof(double) || reinterpret_cast<uintptr_t>(summary) % sizeof(double))
+    if (pg_misaligned(pred, sizeof(float)) || pg_misaligned(gt, sizeof(float)) || pg_misaligned(aligned, sizeof(float)) ||
+        pg_misaligned(joint_err, sizeof(float)) || pg_misaligned(per_pose, sizeof(double)) || pg_misaligned(summary, sizeof(double)))
         return pg_fail(h, PG_EINVAL, "%s: an array is not aligned to its element", who);
 
-    if (!h->posescore) h->posescore = new PoseScoreState();
-    auto* s = static_cast<PoseScoreState*>(h->posescore);
+    PoseScoreState* s = nullptr;
+    PG_TRY(pg_state(h, s));
     const long long want = (B + pgq::WAVES - 1) / pgq::WAVES;
     const int blocks = (int)(want < pgq::MAX_BLOCKS ? want : pgq::MAX_BLOCKS);
     const int n_slots = blocks * pgq::WAVES;

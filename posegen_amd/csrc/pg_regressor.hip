@@ -168,13 +168,16 @@ __global__ __launch_bounds__(THREADS) void regressor_input_kernel(Args a) {
 }  // namespace pgr
 
 // ---- the host side ------------------------------------------------------------------------------------------------------------------
-void pg_regressor_release(pg_handle* h) {
-    if (!h || !h->regressor) return;
-    auto* ring = static_cast<UploadRing*>(h->regressor);
-    pg_ring_release(*ring);
-    delete ring;
-    h->regressor = nullptr;
-}
+namespace {
+
+// what pg_regressor_input keeps in the handle: the upload ring (pg_handle.h) of a call's crop items
+struct RegressorState : ModuleState {
+    static constexpr ModuleSlot SLOT = MOD_REGRESSOR;
+    ~RegressorState() override { pg_ring_release(ring); }
+    UploadRing ring;
+};
+
+}  // namespace
 
 extern "C" int pg_regressor_input(pg_handle* h, void* stream, const uint8_t* pixels, int64_t n_bytes, const pg_crop_item* items, int32_t n,
                                   int32_t out_res, const float mean[3], const float stdev[3], float* out) {
@@ -209,9 +212,10 @@ extern "C" int pg_regressor_input(pg_handle* h, void* stream, const uint8_t* pix
     if (n == 0) return PG_OK;
     PG_HIP(h, hipSetDevice(h->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (!h->regressor) h->regressor = new UploadRing();          // the items go up through the handle's ring: no wait for the stream
+    RegressorState* s = nullptr;                                 // the items go up through the handle's ring: no wait for the stream
+    PG_TRY(pg_state(h, s));
     const void* d_items = nullptr;
-    PG_TRY(pg_ring_upload(h, *static_cast<UploadRing*>(h->regressor), items, (size_t)n * sizeof(pg_crop_item),
+    PG_TRY(pg_ring_upload(h, s->ring, items, (size_t)n * sizeof(pg_crop_item),
                           ((size_t)n + (size_t)n / 2 + 16) * sizeof(pg_crop_item), "crop item buffer", st, &d_items));
     a.items = static_cast<const pg_crop_item*>(d_items);
     hipLaunchKernelGGL(regressor_input_kernel, dim3((unsigned)(n * tiles)), dim3(THREADS), 0, st, a);

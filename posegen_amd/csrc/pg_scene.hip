@@ -238,26 +238,13 @@ int launch(const Args& a, bool frame, int n_cu, void* stream) {
 
 // What a handle keeps between pg_render_scene calls, grow-only: the people's lists (20 B per sample) and the maps of the bounding
 // rectangle (20 B per pixel).
-struct SceneState {
+struct SceneState : ModuleState {
+    static constexpr ModuleSlot SLOT = MOD_SCENE;
+    ~SceneState() override { pg_release(lists); pg_release(maps); }
     DevBuf lists, maps;
 };
 
-SceneState& scene_of(pg_handle* h) {
-    if (!h->scene) h->scene = new SceneState();
-    return *static_cast<SceneState*>(h->scene);
-}
-
 }  // namespace pgsc
-
-void pg_scene_release(pg_handle* h) {
-    if (!h || !h->scene) return;
-    auto* c = static_cast<pgsc::SceneState*>(h->scene);
-    (void)hipSetDevice(h->device);
-    pg_release(c->lists);
-    pg_release(c->maps);
-    delete c;
-    h->scene = nullptr;
-}
 
 extern "C" {
 
@@ -294,7 +281,9 @@ int pg_render_scene(pg_handle* h, void* stream, int H, int W, const float* c2w, 
     a.g.bw = x1 > x0 ? x1 - x0 : 0; a.g.bh = y1 > y0 ? y1 - y0 : 0;
     a.npix = (long long)a.g.bw * a.g.bh;
     PG_HIP(h, hipSetDevice(h->device));
-    SceneState& st = scene_of(h);
+    SceneState* stp = nullptr;
+    PG_TRY(pg_state(h, stp));
+    SceneState& st = *stp;
     float* zs[MAXP];
     float* raws[MAXP];
     auto carve_lists = [&](Carver& c) {
@@ -356,7 +345,7 @@ int pg_stage_scene_composite(pg_handle* h, void* stream, int64_t n_pix, int n_pe
     a.P = n_people; a.S = n_samples; a.den = pgk::density_of(h->cfg);
     for (int p = 0; p < n_people; ++p) {
         if (n_rows[p] < 0 || (n_rows[p] > 0 && (!z[p] || !raw[p]))) return pg_fail(h, PG_EINVAL, "pg_stage_scene_composite: list %d is null or of negative length", p);
-        if (reinterpret_cast<uintptr_t>(raw[p]) % 16) return pg_fail(h, PG_EINVAL, "pg_stage_scene_composite: raw of list %d is not 16-byte aligned", p);
+        if (pg_misaligned(raw[p], 16)) return pg_fail(h, PG_EINVAL, "pg_stage_scene_composite: raw of list %d is not 16-byte aligned", p);
         a.z[p] = z[p]; a.raw[p] = reinterpret_cast<const float4*>(raw[p]); a.n_rows[p] = n_rows[p];
     }
     a.npix = n_pix; a.rows = rows; a.dirs = dirs;

@@ -764,7 +764,9 @@ __global__ __launch_bounds__(THREADS) void smpl_close_kernel(CloseArgs a) {
 // ---- the host side --------------------------------------------------------------------------------------------------------------------
 namespace {
 
-struct SmplState {
+struct SmplState : ModuleState {
+    static constexpr ModuleSlot SLOT = MOD_SMPL;
+    ~SmplState() override { pg_release(ws); }
     DevBuf ws;
 };
 
@@ -810,8 +812,8 @@ long long slice_poses(size_t per_pose, size_t target) {
 
 // the workspace of a slice of S poses: the chunks' partials (part_doubles of them; none: null), the feature rows and A
 int carve_body(pg_handle* h, BodyPlan& p, size_t part_doubles, long long S) {
-    if (!h->smpl) h->smpl = new SmplState();
-    auto* s = static_cast<SmplState*>(h->smpl);
+    SmplState* s = nullptr;
+    PG_TRY(pg_state(h, s));
     auto carve = [&](Carver& c) {
         p.part = c.take<double>(part_doubles, part_doubles > 0);
         p.feat = c.take<float>((size_t)S * p.KP);
@@ -836,14 +838,6 @@ int launch_pre(pg_handle* h, hipStream_t st, const BodyPlan& p, const pg_body_mo
 }
 
 }  // namespace
-
-void pg_smpl_release(pg_handle* h) {
-    if (!h || !h->smpl) return;
-    auto* s = static_cast<SmplState*>(h->smpl);
-    pg_release(s->ws);
-    delete s;
-    h->smpl = nullptr;
-}
 
 extern "C" int pg_smpl_forward(pg_handle* h, void* stream, const pg_body_model* m, int64_t B, const float* betas, int64_t betas_stride,
                                const float* pose, int pose_is_rotmat, const float* regress, int K, float* verts, float* joints,

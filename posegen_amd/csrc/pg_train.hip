@@ -1255,7 +1255,10 @@ struct Pass {               // one network evaluation kept for the backward pass
     float *raw = nullptr, *z = nullptr, *noise = nullptr, *pn = nullptr;
 };
 
-struct Tape {
+// the training tape: activations of the last pg_train_forward
+struct Tape : ModuleState {
+    static constexpr ModuleSlot SLOT = MOD_TRAIN;
+    ~Tape() override { pg_release(buf); pg_release(pbuf); }
     DevBuf buf;
     bool valid = false;
     int64_t generation = 0;     // id of the forward pass the tape holds (pg_train_forward returns it, pg_train_backward checks it)
@@ -1305,10 +1308,8 @@ inline const void* el_off(const void* p, long long elems, int es) { return stati
 constexpr size_t PART_FLOATS = 20u << 20;        // split-K scratch: slices x M x N of the largest weight gradient (80 MB)
 constexpr size_t RS_FLOATS = 1u << 20;
 
-inline Tape* tape_of(pg_handle* h) {
-    if (!h->train) h->train = new Tape();
-    return static_cast<Tape*>(h->train);
-}
+// the tape of the step that is running (pg_train_forward has created it; the step's helpers below read it)
+inline Tape& tape_of(pg_handle* h) { return *h->mods.peek<Tape>(); }
 
 // C += row (x) col in fp32, row[m ld] a column of another array (gemm(): persistent layer kernel only)
 struct Rank1 { const float* row; long long ld; const float* col; };
@@ -1368,7 +1369,7 @@ bool lgemm_takes(const Tape& t, const Gemm& g) {
 int gemm(pg_handle* h, hipStream_t s, const Gemm& desc) {
     Gemm g = desc;      // (cin and ksplit are settled below)
     if (g.M <= 0 || g.N <= 0 || g.K <= 0) return PG_OK;
-    Tape& t = *tape_of(h);
+    Tape& t = tape_of(h);
     if ((g.flags & GEMM_ACC) && !g.cin) {
         if (g.dt & DT_C) return pg_fail(h, PG_EINVAL, "accumulating GEMM into a bf16 result needs an fp32 input array");
         g.cin = static_cast<const float*>(g.C); g.ldcin = g.ldc;
@@ -1521,7 +1522,7 @@ int linear_fwd2(pg_handle* h, hipStream_t s, long long P, int out, int in1, cons
                 float* tmp) {
     const KSeg2 sg{static_cast<const bf16_t*>(X2), static_cast<const bf16_t*>(W2), ldx2, ldw2, in2};
     const int ABC = DT_A | DT_B | DT_C;
-    const Tape& t = *tape_of(h);
+    const Tape& t = tape_of(h);
     Gemm g = fwd_gemm(P, out, in1, X1, ldx1, W1, ldw1, Y, ldy, b, flags, ABC);
     g.seg2 = &sg;
     if (lgemm_takes(t, g) || (tile128_ok(g) && seg2_tile_ok(t, g))) return gemm(h, s, g);
@@ -1568,7 +1569,7 @@ int linear_bwd_x(pg_handle* h, hipStream_t s, long long P, int out, int in, cons
 int linear_bwd_w(pg_handle* h, hipStream_t s, long long P, int out, int in, const void* dY, long long ldy, const void* X, long long ldx,
                  float* dW, long long ldw, float* db = nullptr, int dt = 0) {      // db[out] += column sums of dY (the bias gradient, fused)
     {   // the heads' weight gradients (1 or 3 rows, dY fp32): one pass over X, per-block shares summed in order
-        Tape& t = *tape_of(h);
+        Tape& t = tape_of(h);
         const bool xbf = dt & DT_B;
         const int vec = xbf ? 8 : 4, lpr = in / vec;
         if ((out == 1 || out == 3) && !db && !(dt & DT_A) && ldw == in && in % vec == 0 && lpr >= 1 && lpr <= 64 && (lpr & (lpr - 1)) == 0 &&
@@ -1603,7 +1604,7 @@ int linear_bwd_w(pg_handle* h, hipStream_t s, long long P, int out, int in, cons
     return gemm(h, s, g);
 }
 int colsum(pg_handle* h, hipStream_t s, const float* d, long long rows, int N, long long ld, float* out) {
-    Tape& t = *tape_of(h);
+    Tape& t = tape_of(h);
     if (N > 4) return pg_fail(h, PG_EINVAL, "colsum: at most 4 columns (the heads' bias gradients)");
     const unsigned blocks = (unsigned)((rows + CS_ROWS - 1) / CS_ROWS);
     if ((size_t)blocks * N > RS_FLOATS) return pg_fail(h, PG_EINVAL, "column-sum scratch too small");
@@ -1985,16 +1986,6 @@ int launch_embed_bwd(pg_handle* h, hipStream_t s, const Tape& t, int S, const fl
 
 extern "C" {
 
-void pg_train_release(pg_handle* h) {
-    if (!h || !h->train) return;
-    pgt::Tape* t = static_cast<pgt::Tape*>(h->train);
-    pg_release(t->buf);
-    pg_release(t->pbuf);
-    delete t;
-    h->train = nullptr;
-    h->tape_out = false;
-}
-
 int pg_train_forward(pg_handle* h, void* stream, int64_t n, const float* ray_batch, const float* skts, int64_t pose_stride,
                      const float* cyls, int64_t cyl_stride, const float* cams, int n_samples, int n_importance, int flags,
                      const pg_train_draws* dr, const pg_net_params* coarse, const pg_net_params* fine, const pg_outputs* out,
@@ -2021,7 +2012,9 @@ int pg_train_forward(pg_handle* h, void* stream, int64_t n, const float* ray_bat
         if (fc && (!p->codes || p->n_codes <= 0)) return pg_fail(h, PG_EINVAL, "pg_train_forward: frame codes of net %d missing", k);
     }
     const Step a{h, static_cast<hipStream_t>(stream), n, pose_stride, cyl_stride, ray_batch, skts, cyls, cams, S, N, flags, dr, out, tape_id};
-    Tape& t = *tape_of(h);
+    Tape* tp = nullptr;
+    PG_TRY(pg_state(h, tp));
+    Tape& t = *tp;
     PG_TRY(tape_begin(a, t));
     // one net, S + N rows per ray on one tape pass (`fine` is not read: network_fine is network), or two
     const int rc = single ? forward_single(a, t, *coarse) : forward_two_nets(a, t, *coarse, fine);
@@ -2033,8 +2026,9 @@ int pg_train_forward(pg_handle* h, void* stream, int64_t n, const float* ray_bat
 static int train_backward(pg_handle* h, void* stream, int64_t tape_id, const float* d_rgb_map, const float* d_acc_map, const float* d_rgb0,
                           const float* d_acc0, const pg_net_grads* coarse, const pg_net_grads* fine, float* d_skts, int64_t d_pose_stride) {
     using namespace pgt;
-    if (!h->train || !static_cast<Tape*>(h->train)->valid) return pg_fail(h, PG_ESTATE, "pg_train_backward: no forward pass on the tape (pg_train_forward)");
-    Tape& t = *static_cast<Tape*>(h->train);
+    Tape* tp = h->mods.peek<Tape>();
+    if (!tp || !tp->valid) return pg_fail(h, PG_ESTATE, "pg_train_backward: no forward pass on the tape (pg_train_forward)");
+    Tape& t = *tp;
     // ONE forward is outstanding per handle: a later pg_train_forward reuses the tape, and its activations must not be
     // taken for those of the pass this backward belongs to (two batches summed into one loss, a delayed backward)
     if (tape_id != t.generation)
@@ -2118,7 +2112,7 @@ int pg_train_backward_pose(pg_handle* h, void* stream, int64_t tape_id, const fl
     if (d_pose_stride != 0 && d_pose_stride != 384)
         return pg_fail(h, PG_EINVAL, "pg_train_backward_pose: d_pose_stride must be 0 (the sum over the rays) or 384 (one 4 x 4 per joint and ray), not %lld",
                        (long long)d_pose_stride);
-    if (!d_skts || reinterpret_cast<uintptr_t>(d_skts) % 16 != 0)
+    if (!d_skts || pg_misaligned(d_skts, 16))
         return pg_fail(h, PG_EINVAL, "pg_train_backward_pose: d_skts must be a non-null, 16-byte aligned device array");
     return train_backward(h, stream, tape_id, d_rgb_map, d_acc_map, d_rgb0, d_acc0, coarse, fine, d_skts, d_pose_stride);
 }
@@ -2153,7 +2147,7 @@ int pg_stage_merged_composite_bwd(pg_handle* h, void* stream, int64_t n, int n_s
         return pg_fail(h, PG_EINVAL, "%s: N_samples %d / N_importance %d outside the supported range", fn, S, N);
     if (N > 0 && S < 3) return pg_fail(h, PG_EINVAL, "%s: importance sampling needs N_samples >= 3", fn);
     if (N > 0 && (!z_fine || !order)) return pg_fail(h, PG_EINVAL, "%s: importance samples need z_fine and order", fn);
-    if (reinterpret_cast<uintptr_t>(raw) % 16 != 0 || reinterpret_cast<uintptr_t>(d_raw) % 16 != 0)
+    if (pg_misaligned(raw, 16) || pg_misaligned(d_raw, 16))
         return pg_fail(h, PG_EINVAL, "%s: raw and d_raw must be 16-byte aligned", fn);
     if (n == 0) return PG_OK;
     PG_HIP(h, hipSetDevice(h->device));

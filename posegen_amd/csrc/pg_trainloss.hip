@@ -358,33 +358,16 @@ __global__ __launch_bounds__(THREADS) void norm_final_kernel(const NormEntry* __
 
 // what the three entry points keep in the handle: their partial sums, the device copies of kp_idx and of the tensor table, and the
 // host copies an upload reads while it is in flight (as pg_poseopt.hip).  Calls on one handle are serialised by the caller.
-struct State {
+struct State : ModuleState {
+    static constexpr ModuleSlot SLOT = MOD_TRAINLOSS;
+    ~State() override { for (DevBuf* b : {&loss_part, &reg_part, &norm_part, &d_idx, &d_tab}) pg_release(*b); }
     DevBuf loss_part, reg_part, norm_part;
     DevBuf d_idx, d_tab;
     std::vector<int32_t> host_idx;
     std::vector<NormEntry> host_tab;
 };
 
-State* state_of(pg_handle* h) {
-    if (!h->trainloss) h->trainloss = new State();
-    return static_cast<State*>(h->trainloss);
-}
-
-bool misaligned(const void* p, size_t a) { return reinterpret_cast<uintptr_t>(p) % a != 0; }
-
 }  // namespace pgtl
-
-void pg_trainloss_release(pg_handle* h) {
-    if (!h || !h->trainloss) return;
-    auto* s = static_cast<pgtl::State*>(h->trainloss);
-    pg_release(s->loss_part);
-    pg_release(s->reg_part);
-    pg_release(s->norm_part);
-    pg_release(s->d_idx);
-    pg_release(s->d_tab);
-    delete s;
-    h->trainloss = nullptr;
-}
 
 extern "C" int pg_train_loss(pg_handle* h, void* stream, int64_t n, const float* rgb_map, const float* acc_map, const float* rgb0,
                              const float* acc0, const float* target, const float* bgs, double base_bg, const float* fgs, int loss_kind,
@@ -409,11 +392,12 @@ extern "C" int pg_train_loss(pg_handle* h, void* stream, int64_t n, const float*
     if (std::isnan(base_bg) && use_background && !bgs) return pg_fail(h, PG_EINVAL, "%s: base_bg is NaN", who);
     const void* f32s[] = {rgb_map, acc_map, rgb0, acc0, target, bgs, fgs, d_rgb_map, d_acc_map, d_rgb0, d_acc0};
     for (const void* p : f32s)
-        if (misaligned(p, sizeof(float))) return pg_fail(h, PG_EINVAL, "%s: an array is not aligned to its element", who);
-    if (misaligned(summary, sizeof(double))) return pg_fail(h, PG_EINVAL, "%s: summary is not aligned to a double", who);
+        if (pg_misaligned(p, sizeof(float))) return pg_fail(h, PG_EINVAL, "%s: an array is not aligned to its element", who);
+    if (pg_misaligned(summary, sizeof(double))) return pg_fail(h, PG_EINVAL, "%s: summary is not aligned to a double", who);
 
     PG_HIP(h, hipSetDevice(h->device));
-    State* s = state_of(h);
+    State* s = nullptr;
+    PG_TRY(pg_state(h, s));
     const long long nblocks = (n + THREADS - 1) / THREADS;
     PG_TRY(pg_grow(h, s->loss_part, (size_t)nblocks * NQ * sizeof(double), "training loss partial sums", (size_t)(nblocks + nblocks / 2) * NQ * sizeof(double)));
     LossArgs a{};
@@ -452,13 +436,14 @@ extern "C" int pg_pose_reg_loss(pg_handle* h, void* stream, int64_t n, const flo
         return pg_fail(h, PG_EINVAL, "%s: tol = %g, coef = %g, temp_coef = %g, ext_scale = %g (no NaN; ext_scale > 0)", who, tol, coef, temp_coef, ext_scale);
     const void* f32s[] = {rots, kps, anchor_rots, anchor_kps, prev_rots, prev_kps, next_rots, next_kps, temp_val, d_rots, d_kps};
     for (const void* p : f32s)
-        if (misaligned(p, sizeof(float))) return pg_fail(h, PG_EINVAL, "%s: an array is not aligned to its element", who);
-    if (misaligned(summary, sizeof(double))) return pg_fail(h, PG_EINVAL, "%s: summary is not aligned to a double", who);
+        if (pg_misaligned(p, sizeof(float))) return pg_fail(h, PG_EINVAL, "%s: an array is not aligned to its element", who);
+    if (pg_misaligned(summary, sizeof(double))) return pg_fail(h, PG_EINVAL, "%s: summary is not aligned to a double", who);
     for (int64_t i = 0; i < n; ++i)
         if (kp_idx[i] < 0 || kp_idx[i] >= N) return pg_fail(h, PG_EINVAL, "%s: kp_idx[%lld] = %d is outside [0, %lld)", who, (long long)i, kp_idx[i], (long long)N);
 
     PG_HIP(h, hipSetDevice(h->device));
-    State* s = state_of(h);
+    State* s = nullptr;
+    PG_TRY(pg_state(h, s));
     const long long nblocks = (n * NJ + THREADS - 1) / THREADS;
     PG_TRY(pg_grow(h, s->reg_part, (size_t)nblocks * RQ * sizeof(double), "pose regulariser partial sums", (size_t)(nblocks + nblocks / 2) * RQ * sizeof(double)));
     PG_TRY(pg_grow(h, s->d_idx, (size_t)n * sizeof(int32_t), "pose regulariser indices", (size_t)(n + n / 2) * sizeof(int32_t)));
@@ -487,13 +472,14 @@ extern "C" int pg_grad_norms(pg_handle* h, void* stream, int n_tensors, const fl
         return pg_fail(h, PG_EINVAL, "%s: n_tensors = %d is outside [1, %d] (the reference divides by zero without a gradient)", who, n_tensors,
                        PG_GRAD_NORMS_MAX);
     if (!grads || !counts || !out) return pg_fail(h, PG_EINVAL, "%s: grads, counts and out are required", who);
-    if (misaligned(out, sizeof(double))) return pg_fail(h, PG_EINVAL, "%s: out is not aligned to a double", who);
-    State* s = state_of(h);
+    if (pg_misaligned(out, sizeof(double))) return pg_fail(h, PG_EINVAL, "%s: out is not aligned to a double", who);
+    State* s = nullptr;
+    PG_TRY(pg_state(h, s));
     s->host_tab.resize((size_t)n_tensors);
     long long nblocks = 0;
     for (int t = 0; t < n_tensors; ++t) {
         if (counts[t] < 0 || (counts[t] > 0 && !grads[t])) return pg_fail(h, PG_EINVAL, "%s: tensor %d: %lld elements at %p", who, t, (long long)counts[t], (const void*)grads[t]);
-        if (misaligned(grads[t], sizeof(float))) return pg_fail(h, PG_EINVAL, "%s: tensor %d is not aligned to a float", who, t);
+        if (pg_misaligned(grads[t], sizeof(float))) return pg_fail(h, PG_EINVAL, "%s: tensor %d is not aligned to a float", who, t);
         s->host_tab[t] = NormEntry{grads[t], (long long)counts[t], nblocks};
         nblocks += ((long long)counts[t] + SEG - 1) / SEG;
         if (nblocks > 0x7fffffffll) return pg_fail(h, PG_EINVAL, "%s: more than 2^31 - 1 segments of %d elements", who, SEG);

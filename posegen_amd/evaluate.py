@@ -107,8 +107,7 @@ class _SumsScorer:
         r = self.bank.renderer
         with torch.cuda.device(self.device):
             row = self._row(int(k))
-            r._check(getattr(r.lib, self.ENTRY)(r.handle, r._stream(), C.byref(self._struct()), int(img_idx), box,
-                                                C.c_void_p(rgb.data_ptr()), *resampling, self.flags, C.c_void_p(row.data_ptr())))
+            _ffi.call(r, self.ENTRY, C.byref(self._struct()), int(img_idx), box, rgb, *resampling, self.flags, row)
         self.n_frames = max(self.n_frames, int(k) + 1)
 
     def sums(self) -> np.ndarray:

@@ -113,12 +113,10 @@ class PoseScorer:
         """pg_pose_scores on the current stream of the scorer's device; nothing waits for it"""
         r = self.renderer
         B, J_in = pred.shape[:2]
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
         jarr = None if joints is None else (C.c_int32 * J)(*joints)
         tarr = (C.c_double * max(len(th), 1))(*th)
         with torch.cuda.device(self.device):
-            r._check(r.lib.pg_pose_scores(r.handle, r._stream(), B, J_in, ptr(pred), ptr(gt), jarr, J, root, align, tarr, len(th),
-                                          ptr(per_pose), ptr(aligned), ptr(joint_err), ptr(summary)))
+            _ffi.call(r, "pg_pose_scores", B, J_in, pred, gt, jarr, J, root, align, tarr, len(th), per_pose, aligned, joint_err, summary)
 
     def enqueue(self, pred, gt, *, joints=None, root=None, align="best", thresholds=(), ret_per_pose=False, ret_aligned=False,
                 ret_joint_err=False):

@@ -27,15 +27,8 @@ from . import _ffi
 
 LOSS_KINDS = {"mpjpe": _ffi.PG_POSE_LOSS_MPJPE, "norm_matched": _ffi.PG_POSE_LOSS_NORM_MATCHED}
 
-_ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _device_of(renderer, who: str) -> torch.device:
-    device = torch.device(getattr(renderer, "device", "cpu"))
-    if device.type != "cuda":
-        raise NotImplementedError(f"{who}: the renderer is on {device}, not on a HIP device (torch 'cuda:N'); key-point gradients and "
-                                  "pose losses run in the library only, there is no CPU path")
-    return device
+# this module's clause of the refusal of a renderer that is not on a HIP device (_ffi.device_of)
+NO_CPU = " (torch 'cuda:N'); key-point gradients and pose losses run in the library only,"
 
 
 def _tree(rest_pose, scale, parents, root_parent: int):
@@ -65,8 +58,8 @@ class _AxisAngleFn(torch.autograd.Function):
         g = g_kps.to(device=r.device, dtype=torch.float32).contiguous()
         d_bones = torch.empty_like(b64)
         with torch.cuda.device(r.device):
-            r._check(r.lib.pg_pose_kinematics_bwd(r.handle, r._stream(), b64.shape[0], _ptr(b64), offs.ctypes.data_as(C.POINTER(C.c_double)),
-                                                  par.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(g), _ptr(d_bones)))
+            _ffi.call(r, "pg_pose_kinematics_bwd", b64.shape[0], b64, offs.ctypes.data_as(C.POINTER(C.c_double)),
+                      par.ctypes.data_as(C.POINTER(C.c_int32)), g, d_bones)
         dtype, device = ctx.meta
         return None, d_bones.to(device=device, dtype=dtype), None, None, None
 
@@ -86,9 +79,8 @@ class _RotmatFn(torch.autograd.Function):
         g = g_kps.to(device=r.device, dtype=torch.float32).contiguous()
         d_rot = torch.empty_like(m32)
         with torch.cuda.device(r.device):
-            r._check(r.lib.pg_pose_kinematics_rot_bwd(r.handle, r._stream(), m32.shape[0], _ptr(m32),
-                                                      offs.ctypes.data_as(C.POINTER(C.c_double)), par.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                      _ptr(g), _ptr(d_rot)))
+            _ffi.call(r, "pg_pose_kinematics_rot_bwd", m32.shape[0], m32, offs.ctypes.data_as(C.POINTER(C.c_double)),
+                      par.ctypes.data_as(C.POINTER(C.c_int32)), g, d_rot)
         dtype, device = ctx.meta
         return None, d_rot.to(device=device, dtype=dtype), None, None, None, None
 
@@ -98,7 +90,7 @@ def keypoints_from_axis_angle(renderer, bones: torch.Tensor, rest_pose, scale: f
     `get_smpl_l2ws_torch(bones, rest_pose, scale)[..., :3, -1]` (run_gan.py:2032-2034).  The forward is
     `renderer.pose_kinematics` on `rest_pose * scale` (in the rest pose's own dtype); the backward is pg_pose_kinematics_bwd, finite at a
     zero rotation vector.  The gradient comes back in the dtype and on the device of `bones`."""
-    _device_of(renderer, "keypoints_from_axis_angle")
+    _ffi.device_of(renderer, "keypoints_from_axis_angle", NO_CPU)
     bones = torch.as_tensor(bones)
     if bones.dim() != 3 or tuple(bones.shape[1:]) != (24, 3):
         raise ValueError(f"keypoints_from_axis_angle: bones {tuple(bones.shape)}; [F,24,3] expected")
@@ -112,7 +104,7 @@ def keypoints_from_rotmats(renderer, rotmats: torch.Tensor, rest_pose=None, scal
     (run_gan.py:1897).  `rest_pose`: None = smpl_rest_pose in float32, as there.  Forward `renderer.pose_kinematics_rot`, backward
     pg_pose_kinematics_rot_bwd."""
     from .skeleton import smpl_rest_pose
-    _device_of(renderer, "keypoints_from_rotmats")
+    _ffi.device_of(renderer, "keypoints_from_rotmats", NO_CPU)
     rotmats = torch.as_tensor(rotmats)
     if rotmats.dim() != 4 or tuple(rotmats.shape[1:]) != (24, 3, 3):
         raise ValueError(f"keypoints_from_rotmats: rotmats {tuple(rotmats.shape)}; [F,24,3,3] expected")
@@ -137,8 +129,8 @@ class _PoseLossFn(torch.autograd.Function):
         per_pose = torch.empty(B, dtype=torch.float64, device=dev)
         jarr = None if joints is None else (C.c_int32 * J)(*joints)
         with torch.cuda.device(dev):
-            renderer._check(renderer.lib.pg_pose_loss(renderer.handle, renderer._stream(), B, J_in, _ptr(p32), _ptr(g32), jarr, J, root, kind,
-                                                      float(weight), float(cap), _ptr(per_pose), _ptr(summary), _ptr(d_pred), _ptr(d_gt)))
+            _ffi.call(renderer, "pg_pose_loss", B, J_in, p32, g32, jarr, J, root, kind, float(weight), float(cap), per_pose, summary,
+                      d_pred, d_gt)
         ctx.grads = (d_pred, d_gt)
         ctx.meta = ((pred.dtype, pred.device), (gt.dtype, gt.device))
         loss, n_kept = summary[0], summary[1]
@@ -177,7 +169,7 @@ def pose_loss(pred_kps, gt_kps, *, joints=None, root=None, kind: str = "mpjpe", 
         raise ValueError(f"pose_loss: weight = {weight}, cap = {cap} (no NaN; cap > 0)")
     if renderer is None:
         renderer = pose_eval._scorer_for(None, pred_kps, gt_kps).renderer
-    dev = _device_of(renderer, "pose_loss")
+    dev = _ffi.device_of(renderer, "pose_loss", NO_CPU)
     for t in (pred_kps, gt_kps):
         if t.is_cuda and t.device != dev:
             raise NotImplementedError(f"pose_loss: key points on {t.device}, the renderer on {dev}")

@@ -97,10 +97,8 @@ class _KinematicsFn(torch.autograd.Function):
         skts = torch.empty(n, 24, 4, 4, device=dev)
         l2ws = torch.empty(n, 24, 4, 4, device=dev)
         rots = torch.empty(n, 24, 3, 3, device=dev)
-        ptr = lambda t: C.c_void_p(t.data_ptr())
-        r._check(r.lib.pg_poseopt_forward(r.handle, r._stream(), U, 6, ptr(bone_c), ptr(pelvis_c), ptr(rest_c),
-                                          0 if rest_c.shape[0] == 1 else 72, _i32(layer._parents), n, _i32(seg.inverse),
-                                          ptr(rots), ptr(l2ws), ptr(skts), ptr(kps)))
+        _ffi.call(r, "pg_poseopt_forward", U, 6, bone_c, pelvis_c, rest_c, 0 if rest_c.shape[0] == 1 else 72, _i32(layer._parents), n,
+                  _i32(seg.inverse), rots, l2ws, skts, kps)
         ctx.layer, ctx.seg, ctx.saved = layer, seg, (pelvis_c, bone_c, rest_c)
         ctx.meta = (pelvis.dtype, pelvis.device, bone.dtype, bone.device)
         ctx.set_materialize_grads(False)
@@ -114,12 +112,10 @@ class _KinematicsFn(torch.autograd.Function):
         pelvis_c, bone_c, rest_c = ctx.saved
         U, n = len(seg.unique), len(seg.inverse)
         cot = [None if g is None else g.to(device=dev, dtype=torch.float32).contiguous() for g in (g_rots, g_l2ws, g_skts, g_kps)]
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
         d_bone = torch.empty(U, 24, 6, device=dev)
         d_pelvis = torch.empty(U, 3, device=dev)
-        r._check(r.lib.pg_poseopt_backward(r.handle, r._stream(), U, 6, ptr(bone_c), ptr(pelvis_c), ptr(rest_c),
-                                           0 if rest_c.shape[0] == 1 else 72, _i32(layer._parents), n, _i32(seg.seg_start),
-                                           _i32(seg.seg_rays), *[ptr(t) for t in cot], ptr(d_bone), ptr(d_pelvis)))
+        _ffi.call(r, "pg_poseopt_backward", U, 6, bone_c, pelvis_c, rest_c, 0 if rest_c.shape[0] == 1 else 72, _i32(layer._parents), n,
+                  _i32(seg.seg_start), _i32(seg.seg_rays), *cot, d_bone, d_pelvis)
         pd, pdev, bd, bdev = ctx.meta
         return None, None, d_pelvis.to(device=pdev, dtype=pd), d_bone.to(device=bdev, dtype=bd), None
 

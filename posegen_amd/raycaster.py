@@ -51,10 +51,6 @@ def _dev_f32(t: torch.Tensor, device) -> torch.Tensor:
     return t.to(device=device, dtype=torch.float32).contiguous()
 
 
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
 def _net_key(which: int) -> str:
     """the reference checkpoint's key of net 0 (coarse) / 1 (fine)"""
     return "network_fn_state_dict" if which == 0 else "network_fine_state_dict"
@@ -393,7 +389,7 @@ class HipRenderer:
             if not (codes.is_cuda and codes.dtype == torch.float32 and codes.is_contiguous()):
                 raise ValueError("load_network_device: contiguous float32 device frame codes expected")
             cptr, ncodes = codes.data_ptr(), codes.shape[0]
-        self._check(self.lib.pg_load_weights_device(self.handle, self._stream(), which, ptrs, len(ts), cptr, ncodes))
+        _ffi.call(self, "pg_load_weights_device", which, ptrs, len(ts), cptr, ncodes)
         self._state_lazy[_net_key(which)] = state_provider
 
     def _refresh_state(self):
@@ -510,11 +506,11 @@ class HipRenderer:
         t_rand [n,S], u_rand [n,N], noise0 [n,S], noise1 [n,S+N], ray_noise [n,S+N,3]."""
         c = marshal_ray_call(self.cfg, self.device, ray_batch, skts, cyls, cams, n_samples, n_importance, lindisp, draws)
         out, ex, po = alloc_ray_outputs(c.n, c.S, c.N, self.device, want_alpha, extras)
-        args = (self.handle, self._stream(), c.n, _ptr(c.rb), _ptr(c.sk), c.ps, _ptr(c.cy), c.cs, _ptr(c.cam), c.S, c.N, c.flags)
+        args = (c.n, c.rb, c.sk, c.ps, c.cy, c.cs, c.cam, c.S, c.N, c.flags)
         if c.n > 0 and c.draws is not None:
-            self._check(self.lib.pg_render_rays_train(*args, C.byref(c.draws), C.byref(po)))
+            _ffi.call(self, "pg_render_rays_train", *args, C.byref(c.draws), C.byref(po))
         elif c.n > 0:
-            self._check(self.lib.pg_render_rays(*args, C.byref(po)))
+            _ffi.call(self, "pg_render_rays", *args, C.byref(po))
         if extras:
             out["extras"] = ex
         return out
@@ -531,11 +527,9 @@ class HipRenderer:
         sk, _ = self._pose_args(skts, 1)
         cy_t, _ = self._cyl_args(cyl, 1)
         rgb, disp, acc, rgb8, bgt = self._frame_outputs(H, W, bg, want_uint8)
-        self._check(self.lib.pg_render_frame(
-            self.handle, self._stream(), int(H), int(W), c2w_h.ctypes.data_as(C.POINTER(C.c_float)), intr, bx,
-            float(near), float(far), _ptr(sk), _ptr(cy_t), -1.0 if cam is None else float(cam), S, N,
-            _ffi.PG_FLAG_LINDISP if lindisp else 0, _ptr(bgt), float(base_bg), _ptr(rgb), _ptr(disp), _ptr(acc),
-            _ptr(rgb8)))
+        _ffi.call(self, "pg_render_frame", int(H), int(W), c2w_h.ctypes.data_as(C.POINTER(C.c_float)), intr, bx, float(near), float(far),
+                  sk, cy_t, -1.0 if cam is None else float(cam), S, N, _ffi.PG_FLAG_LINDISP if lindisp else 0, bgt, float(base_bg), rgb,
+                  disp, acc, rgb8)
         return (rgb, disp, acc, rgb8) if want_uint8 else (rgb, disp, acc)
 
     def _frame_args(self, H, W, focal, c2w, box, center):
@@ -573,11 +567,9 @@ class HipRenderer:
             sk, _ = self._pose_args(skts, 1)
             cy_t, _ = self._cyl_args(cyl, 1)
             flat = buf.view(-1)
-            self._check(self.lib.pg_render_frame_range(
-                self.handle, self._stream(), int(H), int(W), c2w_h.ctypes.data_as(C.POINTER(C.c_float)), intr, bx,
-                float(near), float(far), _ptr(sk), _ptr(cy_t), -1.0 if cam is None else float(cam), S, N,
-                _ffi.PG_FLAG_LINDISP if lindisp else 0, int(ray_begin), int(ray_end),
-                _ptr(flat[:3 * n]), _ptr(flat[3 * n:4 * n]), _ptr(flat[4 * n:])))
+            _ffi.call(self, "pg_render_frame_range", int(H), int(W), c2w_h.ctypes.data_as(C.POINTER(C.c_float)), intr, bx, float(near),
+                      float(far), sk, cy_t, -1.0 if cam is None else float(cam), S, N, _ffi.PG_FLAG_LINDISP if lindisp else 0,
+                      int(ray_begin), int(ray_end), flat[:3 * n], flat[3 * n:4 * n], flat[4 * n:])
         return buf
 
     def compose_frame(self, H: int, W: int, box, rgb_map: torch.Tensor, disp_map: torch.Tensor, acc_map: torch.Tensor,
@@ -588,9 +580,8 @@ class HipRenderer:
         (tlx, tly), (brx, bry) = box
         rgb, disp, acc, rgb8, bgt = self._frame_outputs(H, W, bg, want_uint8)
         rm, dm, am = (None if m is None else _dev_f32(m, dev) for m in (rgb_map, disp_map, acc_map))
-        self._check(self.lib.pg_compose_frame(
-            self.handle, self._stream(), int(H), int(W), (C.c_int * 4)(int(tlx), int(tly), int(brx), int(bry)),
-            _ptr(rm), _ptr(dm), _ptr(am), _ptr(bgt), float(base_bg), _ptr(rgb), _ptr(disp), _ptr(acc), _ptr(rgb8)))
+        _ffi.call(self, "pg_compose_frame", int(H), int(W), (C.c_int * 4)(int(tlx), int(tly), int(brx), int(bry)), rm, dm, am, bgt,
+                  float(base_bg), rgb, disp, acc, rgb8)
         return (rgb, disp, acc, rgb8) if want_uint8 else (rgb, disp, acc)
 
     def render_scene(self, H: int, W: int, focal, c2w, people, **kw):
@@ -657,7 +648,7 @@ class HipRenderer:
         sk, _ = self._pose_args(skts, 1)
         raw = torch.empty(n, 4, device=self.device)
         if n > 0:
-            self._check(self.lib.pg_query_density(self.handle, self._stream(), int(which), n, _ptr(p), _ptr(sk), _ptr(raw)))
+            _ffi.call(self, "pg_query_density", int(which), n, p, sk, raw)
         return raw[:, 3:4].reshape(*torch.as_tensor(pts).shape[:-1], 1)
 
     def mesh_density(self, kps: torch.Tensor, skts: torch.Tensor, radius: float = 1.0, res: int = 64,
@@ -687,8 +678,8 @@ class HipRenderer:
         root = _np32(torch.as_tensor(kps).reshape(-1, 24, 3)[0, 0])
         sk, _ = self._pose_args(torch.as_tensor(skts).detach(), 1)
         sigma = torch.empty(R, R, R, device=self.device) if res >= 1 else None
-        self._check(self.lib.pg_grid_density(self.handle, self._stream(), self._density_net(which), int(res), float(radius),
-                                             root.ctypes.data_as(C.POINTER(C.c_float)), _ptr(sk), int(slab_rays), _ptr(sigma)))
+        _ffi.call(self, "pg_grid_density", self._density_net(which), int(res), float(radius), root.ctypes.data_as(C.POINTER(C.c_float)), sk,
+                  int(slab_rays), sigma)
         return sigma
 
     def marching_cubes(self, grid: torch.Tensor, threshold: float, clamp: float = 0.0):
@@ -699,12 +690,11 @@ class HipRenderer:
         if g.dim() != 3:
             raise ValueError(f"marching_cubes: a 3-D grid expected, got {tuple(g.shape)}")
         nv, nt = C.c_int64(), C.c_int64()
-        args = (self.handle, self._stream(), _ptr(g), *(int(n) for n in g.shape), float(threshold), float(clamp))
-        self._check(self.lib.pg_mesh_count(*args, C.byref(nv), C.byref(nt)))
+        args = (g, *(int(n) for n in g.shape), float(threshold), float(clamp))
+        _ffi.call(self, "pg_mesh_count", *args, C.byref(nv), C.byref(nt))
         verts = torch.empty(nv.value, 3, device=self.device)
         tris = torch.empty(nt.value, 3, device=self.device, dtype=torch.int32)
-        self._check(self.lib.pg_mesh_emit(*args, _ptr(verts) if nv.value else None, _ptr(tris) if nt.value else None,
-                                          nv.value, nt.value))
+        _ffi.call(self, "pg_mesh_emit", *args, verts if nv.value else None, tris if nt.value else None, nv.value, nt.value)
         return verts, tris
 
     def pose_kinematics(self, bones: torch.Tensor, rest_pose, parents=None, want_l2ws: bool = False):
@@ -722,9 +712,8 @@ class HipRenderer:
         kps = torch.empty(F, 24, 3, device=self.device)
         skts = torch.empty(F, 24, 4, 4, device=self.device)
         l2ws = torch.empty(F, 24, 4, 4, device=self.device, dtype=torch.float64) if want_l2ws else None
-        self._check(self.lib.pg_pose_kinematics(self.handle, self._stream(), F, _ptr(b),
-                                                rest.ctypes.data_as(C.POINTER(C.c_double)),
-                                                par.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(kps), _ptr(skts), _ptr(l2ws)))
+        _ffi.call(self, "pg_pose_kinematics", F, b, rest.ctypes.data_as(C.POINTER(C.c_double)), par.ctypes.data_as(C.POINTER(C.c_int32)),
+                  kps, skts, l2ws)
         return (kps, skts, l2ws) if want_l2ws else (kps, skts)
 
     def pose_kinematics_rot(self, rotmats: torch.Tensor, rest_pose, scale: float = 1.0, parents=None, want_l2ws: bool = False):
@@ -753,8 +742,8 @@ class HipRenderer:
         kps = torch.empty(F, 24, 3, device=self.device)
         skts = torch.empty(F, 24, 4, 4, device=self.device)
         l2ws = torch.empty(F, 24, 4, 4, device=self.device, dtype=torch.float64) if want_l2ws else None
-        self._check(self.lib.pg_pose_kinematics_rot(self.handle, self._stream(), F, _ptr(m), rest.ctypes.data_as(C.POINTER(C.c_double)),
-                                                    par.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(kps), _ptr(skts), _ptr(l2ws)))
+        _ffi.call(self, "pg_pose_kinematics_rot", F, m, rest.ctypes.data_as(C.POINTER(C.c_double)),
+                  par.ctypes.data_as(C.POINTER(C.c_int32)), kps, skts, l2ws)
         return (kps, skts, l2ws) if want_l2ws else (kps, skts)
 
     def pose_boxes(self, kps: torch.Tensor, c2ws, H: int, W: int, focal, ext_scale: float, center=None,
@@ -779,9 +768,8 @@ class HipRenderer:
         d_ring = torch.tensor(ring, dtype=torch.float64, device=self.device)
         cyls = torch.empty(F, 5, device=self.device)
         boxes = torch.empty(F, 4, device=self.device, dtype=torch.int32)
-        self._check(self.lib.pg_pose_boxes(self.handle, self._stream(), F, _ptr(kp), _ptr(d_w2c), 16 if w2c.shape[0] > 1 else 0,
-                                           _ptr(d_ring), float(ext), float(ext * top_expand_ratio), float(ext * bot_expand_ratio),
-                                           fx, fy, int(H), int(W), offx, offy, _ptr(cyls), _ptr(boxes)))
+        _ffi.call(self, "pg_pose_boxes", F, kp, d_w2c, 16 if w2c.shape[0] > 1 else 0, d_ring, float(ext), float(ext * top_expand_ratio),
+                  float(ext * bot_expand_ratio), fx, fy, int(H), int(W), offx, offy, cyls, boxes)
         return cyls, boxes
 
     # -- stage entry points (tests / profiling) ---------------------------------------
@@ -792,9 +780,8 @@ class HipRenderer:
         rays = torch.empty(max(n, 1), 11, device=self.device)              # (an empty range still hands a buffer over)
         cams = torch.empty(max(n, 1), device=self.device) if want_cams else None
         c2w_h, intr, bx = self._frame_args(H, W, focal, c2w, box, center)
-        self._check(self.lib.pg_stage_frame_rays(
-            self.handle, self._stream(), int(H), int(W), c2w_h.ctypes.data_as(C.POINTER(C.c_float)), intr, bx, float(near),
-            float(far), -1.0 if cam is None else float(cam), int(r0), int(r1), _ptr(rays), _ptr(cams)))
+        _ffi.call(self, "pg_stage_frame_rays", int(H), int(W), c2w_h.ctypes.data_as(C.POINTER(C.c_float)), intr, bx, float(near),
+                  float(far), -1.0 if cam is None else float(cam), int(r0), int(r1), rays, cams)
         return (rays[:n], cams[:n]) if want_cams else rays[:n]
 
     def stage_sample_coarse(self, ray_batch, cyls, n_samples, lindisp=False):
@@ -803,9 +790,7 @@ class HipRenderer:
         cy, cs = self._cyl_args(cyls, n)
         nf = torch.empty(n, 2, device=self.device)
         z = torch.empty(n, n_samples, device=self.device)
-        self._check(self.lib.pg_stage_sample_coarse(self.handle, self._stream(), n, _ptr(rb), _ptr(cy), cs,
-                                                    int(n_samples), _ffi.PG_FLAG_LINDISP if lindisp else 0,
-                                                    _ptr(nf), _ptr(z)))
+        _ffi.call(self, "pg_stage_sample_coarse", n, rb, cy, cs, int(n_samples), _ffi.PG_FLAG_LINDISP if lindisp else 0, nf, z)
         return nf, z
 
     def stage_eval(self, which, ray_batch, z, skts, cams=None, want_dbg=False, dbg_stage=0, dbg=None):
@@ -817,8 +802,7 @@ class HipRenderer:
         raw = torch.empty(n, S, 4, device=self.device)
         if want_dbg:
             dbg = torch.zeros(n * S, 256, device=self.device)
-        self._check(self.lib.pg_stage_eval(self.handle, self._stream(), int(which), n, S, _ptr(c.rb), _ptr(zz),
-                                           _ptr(c.sk), c.ps, _ptr(c.cam), _ptr(raw), _ptr(dbg), int(dbg_stage)))
+        _ffi.call(self, "pg_stage_eval", int(which), n, S, c.rb, zz, c.sk, c.ps, c.cam, raw, dbg, int(dbg_stage))
         return (raw, dbg) if want_dbg else raw
 
     def limb_skip_stats(self, which, ray_batch, z, skts, cams=None):
@@ -838,9 +822,8 @@ class HipRenderer:
         o = {"rgb_map": new(n, 3), "disp_map": new(n), "acc_map": new(n), "alpha": new(n, S),
              "weights": new(n, S)}
         zf = new(n, S + n_importance) if n_importance > 0 else None
-        self._check(self.lib.pg_stage_composite(self.handle, self._stream(), n, S, _ptr(rb), _ptr(zz), _ptr(rw),
-                                                _ptr(o["rgb_map"]), _ptr(o["disp_map"]), _ptr(o["acc_map"]),
-                                                _ptr(o["alpha"]), _ptr(o["weights"]), int(n_importance), _ptr(zf)))
+        _ffi.call(self, "pg_stage_composite", n, S, rb, zz, rw, o["rgb_map"], o["disp_map"], o["acc_map"], o["alpha"], o["weights"],
+                  int(n_importance), zf)
         if zf is not None:
             o["z_fine"] = zf
         return o
@@ -854,9 +837,8 @@ class HipRenderer:
         tr = None if t_rand is None else _dev_f32(t_rand, self.device)
         nf = torch.empty(n, 2, device=self.device)
         z = torch.empty(n, n_samples, device=self.device)
-        self._check(self.lib.pg_stage_sample_coarse_draws(self.handle, self._stream(), n, _ptr(rb), _ptr(cy), cs, int(n_samples),
-                                                          (_ffi.PG_FLAG_LINDISP if lindisp else 0) | (_ffi.PG_FLAG_STAGE_ONE_LAUNCH if one_launch else 0),
-                                                          _ptr(tr), _ptr(nf), _ptr(z)))
+        _ffi.call(self, "pg_stage_sample_coarse_draws", n, rb, cy, cs, int(n_samples),
+                  (_ffi.PG_FLAG_LINDISP if lindisp else 0) | (_ffi.PG_FLAG_STAGE_ONE_LAUNCH if one_launch else 0), tr, nf, z)
         return nf, z
 
     def stage_composite_form(self, form, ray_batch, z, raw, n_importance=0, noise=None, u_rand=None, ld_new=None, fill=None):
@@ -876,10 +858,9 @@ class HipRenderer:
             o["z_fine"], o["order"] = new(n, S + N), new(n, S + N, dtype=torch.int32)
             if iso:
                 o["z_new"] = new(n, ld)
-        self._check(self.lib.pg_stage_composite_form(
-            self.handle, self._stream(), _ffi.PG_COMP_IS_ONLY if iso else _ffi.PG_COMP_PLAIN, n, S, N, _ptr(rb), _ptr(zz), _ptr(rw),
-            _ptr(nz), _ptr(ur), _ptr(o["rgb_map"]), _ptr(o["disp_map"]), _ptr(o["acc_map"]), _ptr(o["alpha"]), _ptr(o["weights"]),
-            _ptr(o.get("z_fine")), _ptr(o.get("order")), _ptr(o.get("z_new")), ld, None, None))
+        _ffi.call(self, "pg_stage_composite_form", _ffi.PG_COMP_IS_ONLY if iso else _ffi.PG_COMP_PLAIN, n, S, N, rb, zz, rw, nz, ur,
+                  o["rgb_map"], o["disp_map"], o["acc_map"], o["alpha"], o["weights"], o.get("z_fine"), o.get("order"), o.get("z_new"), ld,
+                  None, None)
         return o
 
     def stage_composite_merged(self, ray_batch, z_fine, raw, raw_new, order, noise=None, fill=None):
@@ -892,9 +873,8 @@ class HipRenderer:
         nz = None if noise is None else _dev_f32(noise, self.device)
         new = lambda *s: (torch.empty(*s, device=self.device) if fill is None else torch.full(s, fill, device=self.device))
         o = {"rgb_map": new(n, 3), "disp_map": new(n), "acc_map": new(n), "alpha": new(n, S + N), "raw_out": new(n, S + N, 4)}
-        self._check(self.lib.pg_stage_composite_form(
-            self.handle, self._stream(), _ffi.PG_COMP_MERGED, n, S, N, _ptr(rb), _ptr(zf), _ptr(rw), _ptr(nz), None, _ptr(o["rgb_map"]),
-            _ptr(o["disp_map"]), _ptr(o["acc_map"]), _ptr(o["alpha"]), None, None, _ptr(od), None, ld, _ptr(rn), _ptr(o["raw_out"])))
+        _ffi.call(self, "pg_stage_composite_form", _ffi.PG_COMP_MERGED, n, S, N, rb, zf, rw, nz, None, o["rgb_map"], o["disp_map"],
+                  o["acc_map"], o["alpha"], None, None, od, None, ld, rn, o["raw_out"])
         return o
 
     def stage_composite_bwd(self, ray_batch, z, raw, noise=None, d_rgb=None, d_acc=None):
@@ -904,8 +884,7 @@ class HipRenderer:
         nz, gr, ga = opt(noise), opt(d_rgb), opt(d_acc)
         n, S = zz.shape
         d_raw = torch.empty(n, S, 4, device=self.device)
-        self._check(self.lib.pg_stage_composite_bwd(self.handle, self._stream(), n, S, _ptr(rb), _ptr(zz), _ptr(rw), _ptr(nz), _ptr(gr),
-                                                    _ptr(ga), _ptr(d_raw)))
+        _ffi.call(self, "pg_stage_composite_bwd", n, S, rb, zz, rw, nz, gr, ga, d_raw)
         return d_raw
 
     def stage_merged_composite_bwd(self, ray_batch, z, z_fine, raw, order, noise0=None, noise1=None, d_rgb=None, d_acc=None,
@@ -919,9 +898,7 @@ class HipRenderer:
         N = zf.shape[1] - S
         keep = [opt(t) for t in (noise0, noise1, d_rgb, d_acc, d_rgb0, d_acc0)]
         d_raw = torch.empty(n * (S + N), 4, device=self.device)
-        self._check(self.lib.pg_stage_merged_composite_bwd(self.handle, self._stream(), n, S, N, _ptr(rb), _ptr(zz), _ptr(zf), _ptr(rw),
-                                                           _ptr(keep[0]), _ptr(keep[1]), _ptr(od), *[_ptr(t) for t in keep[2:]],
-                                                           _ptr(d_raw)))
+        _ffi.call(self, "pg_stage_merged_composite_bwd", n, S, N, rb, zz, zf, rw, keep[0], keep[1], od, *keep[2:], d_raw)
         return d_raw
 
 

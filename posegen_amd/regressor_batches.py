@@ -205,8 +205,7 @@ def _launch(store, items: np.ndarray, out_res: int, mean, std, out: Optional[tor
         return out
     m, s = (C.c_float * 3)(*(float(v) for v in mean)), (C.c_float * 3)(*(float(v) for v in std))
     with torch.cuda.device(dev):
-        r._check(r.lib.pg_regressor_input(r.handle, r._stream(), C.c_void_p(store.pixels.data_ptr()), store.capacity,
-                                          items.ctypes.data_as(C.POINTER(_ffi.PgCropItem)), B, R, m, s, C.c_void_p(out.data_ptr())))
+        _ffi.call(r, "pg_regressor_input", store.pixels, store.capacity, items.ctypes.data_as(C.POINTER(_ffi.PgCropItem)), B, R, m, s, out)
     return out
 
 

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _ffi
-from .raycaster import _check_subject_range, _ptr, _resolve_sn, _subject_values
+from .raycaster import _check_subject_range, _resolve_sn, _subject_values
 from .render import _caster_device, frame_background, emit_frame, frame_setup, frame_stacks, frames_to_host
 
 MAX_PEOPLE = _ffi.PG_SCENE_MAX_PEOPLE
@@ -90,9 +90,8 @@ def render_scene(renderer, H: int, W: int, focal, c2w, people, center=None, near
     if return_lists:
         lists = [(torch.empty(n, S + N, device=r.device), torch.empty(n, S + N, 4, device=r.device)) for n in n_rows]
         lp = (C.c_void_p * (2 * P))(*[t.data_ptr() for zr in lists for t in zr])
-    r._check(r.lib.pg_render_scene(
-        r.handle, r._stream(), H, W, c2w_h.ctypes.data_as(C.POINTER(C.c_float)), intr, float(near), float(far), P, arr, S, N,
-        _ffi.PG_FLAG_LINDISP if lindisp else 0, _ptr(bgt), float(base_bg), _ptr(rgb), _ptr(disp), _ptr(acc), _ptr(rgb8), _ptr(pacc), lp))
+    _ffi.call(r, "pg_render_scene", H, W, c2w_h.ctypes.data_as(C.POINTER(C.c_float)), intr, float(near), float(far), P, arr, S, N,
+              _ffi.PG_FLAG_LINDISP if lindisp else 0, bgt, float(base_bg), rgb, disp, acc, rgb8, pacc, lp)
     out = (rgb, disp, acc)
     for want, x in ((want_uint8, rgb8), (want_person_acc, pacc), (return_lists, lists)):
         if want:
@@ -117,9 +116,8 @@ def stage_scene_composite(renderer, z, raw, rows, dirs, want_person_acc=True):
     if want_person_acc:
         out["person_acc"] = torch.empty(P, n, device=dev)
     vp = lambda ts: (C.c_void_p * P)(*[t.data_ptr() for t in ts])
-    r._check(r.lib.pg_stage_scene_composite(
-        r.handle, r._stream(), n, P, S, vp(z), vp(raw), (C.c_int64 * P)(*[int(t.shape[0]) for t in z]), _ptr(rows), _ptr(dirs),
-        _ptr(out["rgb_map"]), _ptr(out["disp_map"]), _ptr(out["acc_map"]), _ptr(out.get("person_acc"))))
+    _ffi.call(r, "pg_stage_scene_composite", n, P, S, vp(z), vp(raw), (C.c_int64 * P)(*[int(t.shape[0]) for t in z]), rows, dirs,
+              out["rgb_map"], out["disp_map"], out["acc_map"], out.get("person_acc"))
     return out
 
 

@@ -203,11 +203,9 @@ class BodyModel:
         new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=self.device)
         out = BodyOutput(new(B, self.V, 3) if want_vertices else None, new(B, N_JOINTS, 3) if joints else None,
                          new(B, K, 3) if reg is not None else None)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        r = self.renderer
         with torch.cuda.device(self.device):
-            r._check(r.lib.pg_smpl_forward(r.handle, r._stream(), C.byref(self._model), B, ptr(betas), self.NB if betas.shape[0] == B and B > 1 else 0,
-                                           ptr(pose), 0 if pose2rot else 1, ptr(reg), K, ptr(out.vertices), ptr(out.joints), ptr(out.regressed)))
+            _ffi.call(self.renderer, "pg_smpl_forward", C.byref(self._model), B, betas, self.NB if betas.shape[0] == B and B > 1 else 0,
+                      pose, 0 if pose2rot else 1, reg, K, out.vertices, out.joints, out.regressed)
         return out
 
     __call__ = forward
@@ -281,13 +279,10 @@ class _BodyFn(torch.autograd.Function):
         reg = None if ctx.regressor is None else body.regressors[ctx.regressor]
         d_betas = torch.empty(B, body.NB, dtype=torch.float32, device=body.device) if need_b else None
         d_pose = torch.empty_like(p32) if need_p else None
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        r = body.renderer
         with torch.cuda.device(body.device):
-            r._check(r.lib.pg_smpl_backward(r.handle, r._stream(), C.byref(body._model), B, ptr(b32), body.NB if b32.shape[0] == B and B > 1 else 0,
-                                            ptr(p32), 0 if ctx.pose2rot else 1, ptr(reg), 0 if reg is None else reg.shape[0],
-                                            ptr(body._blend_transposed()), ptr(g.get("vertices")), ptr(g.get("joints")), ptr(g.get("regressed")),
-                                            ptr(d_betas), ptr(d_pose)))
+            _ffi.call(body.renderer, "pg_smpl_backward", C.byref(body._model), B, b32, body.NB if b32.shape[0] == B and B > 1 else 0,
+                      p32, 0 if ctx.pose2rot else 1, reg, 0 if reg is None else reg.shape[0], body._blend_transposed(), g.get("vertices"),
+                      g.get("joints"), g.get("regressed"), d_betas, d_pose)
         (bt, bs), (pt, ps) = ctx.meta
         if need_b and bs[0] != B:                            # one row for all poses: the rows in pose order, in float64, rounded once
             rows = d_betas.to(torch.float64)
@@ -301,9 +296,7 @@ class _BodyFn(torch.autograd.Function):
 @torch.no_grad()
 def vertex_errors(renderer, a, b):
     """pg_vertex_errors on `renderer`'s handle: a, b [B,V,3] -> (per_pose float64 [B], their mean, a float64 device scalar)"""
-    device = torch.device(getattr(renderer, "device", "cpu"))
-    if device.type != "cuda":
-        raise NotImplementedError(f"vertex_errors: the renderer is on {device}, not on a HIP device; there is no CPU path")
+    device = _ffi.device_of(renderer, "vertex_errors", ";")
     sa, sb = tuple(np.shape(a)), tuple(np.shape(b))
     if len(sa) != 3 or sa[2] != 3 or sa != sb or sa[0] < 1 or sa[1] < 1:
         raise ValueError(f"vertex_errors: a {sa} and b {sb} must both be [B,V,3]")
@@ -312,7 +305,5 @@ def vertex_errors(renderer, a, b):
     per_pose = torch.empty(sa[0], dtype=torch.float64, device=device)
     summary = torch.empty(2, dtype=torch.float64, device=device)
     with torch.cuda.device(device):
-        renderer._check(renderer.lib.pg_vertex_errors(renderer.handle, renderer._stream(), sa[0], sa[1], C.c_void_p(a.data_ptr()),
-                                                      C.c_void_p(b.data_ptr()), C.c_void_p(per_pose.data_ptr()),
-                                                      C.c_void_p(summary.data_ptr())))
+        _ffi.call(renderer, "pg_vertex_errors", sa[0], sa[1], a, b, per_pose, summary)
     return per_pose, summary[1]

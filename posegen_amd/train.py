@@ -16,7 +16,7 @@ from typing import Dict, Optional
 import torch
 
 from . import _ffi
-from .raycaster import (NET_TENSOR_ORDER, HipRayCaster, _dev_f32, _ptr, _resolve_sn, alloc_ray_outputs,
+from .raycaster import (NET_TENSOR_ORDER, HipRayCaster, _dev_f32, _resolve_sn, alloc_ray_outputs,
                         check_single_net_states, make_training_draws, marshal_ray_call, one_nanmean_group,
                         refuse_reference_kwargs)
 
@@ -31,7 +31,7 @@ class _RenderRaysFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, caster, call, skts, *params):
         r = caster.renderer
-        lib, dev = r.lib, r.device
+        dev = r.device
         n, S, N = call.n, call.S, call.N                 # (`call`: the RayCall of raycaster.marshal_ray_call)
         ctx.skts_shape, ctx.skts_dtype, ctx.skts_device = tuple(skts.shape), skts.dtype, skts.device
         nper = 24 + (1 if caster.cfg.framecode_ch > 0 else 0)
@@ -55,10 +55,9 @@ class _RenderRaysFn(torch.autograd.Function):
         # the maps always; the alphas for a single-net caster, whose call in the reference returns them besides the maps
         out, _, po = alloc_ray_outputs(n, S, N, dev, want_alpha=single)
         tape = C.c_int64(0)
-        r._check(lib.pg_train_forward(r.handle, r._stream(), n, _ptr(call.rb), _ptr(call.sk), call.ps, _ptr(call.cy), call.cs,
-                                      _ptr(call.cam), S, N, call.flags,
-                                      None if call.draws is None else C.byref(call.draws), C.byref(structs[0]),
-                                      C.byref(structs[1]) if len(structs) > 1 else None, C.byref(po), C.byref(tape)))
+        _ffi.call(r, "pg_train_forward", n, call.rb, call.sk, call.ps, call.cy, call.cs, call.cam, S, N, call.flags,
+                  None if call.draws is None else C.byref(call.draws), C.byref(structs[0]),
+                  C.byref(structs[1]) if len(structs) > 1 else None, C.byref(po), C.byref(tape))
         ctx.caster, ctx.n_nets, ctx.nper, ctx.keep, ctx.tape_id = caster, len(nets), nper, keep, tape.value
         ctx.shapes = [tuple(p.shape) for p in params]
         zero = lambda k: out[k] if k in out else torch.zeros(0, device=dev)
@@ -91,11 +90,10 @@ class _RenderRaysFn(torch.autograd.Function):
             shape = ctx.skts_shape
             per_ray = len(shape) == 4 and shape[0] > 1
             d_skts = torch.empty((shape[0] if per_ray else 1, 24, 4, 4), device=dev, dtype=torch.float32)
-            r._check(r.lib.pg_train_backward_pose(r.handle, r._stream(), ctx.tape_id, _ptr(a), _ptr(b), _ptr(c), _ptr(d), *nets,
-                                                  _ptr(d_skts), 384 if per_ray else 0))
+            _ffi.call(r, "pg_train_backward_pose", ctx.tape_id, a, b, c, d, *nets, d_skts, 384 if per_ray else 0)
             d_skts = d_skts.reshape(shape).to(device=ctx.skts_device, dtype=ctx.skts_dtype)
         else:
-            r._check(r.lib.pg_train_backward(r.handle, r._stream(), ctx.tape_id, _ptr(a), _ptr(b), _ptr(c), _ptr(d), *nets))
+            _ffi.call(r, "pg_train_backward", ctx.tape_id, a, b, c, d, *nets)
         caster._stale = True                            # (an optimiser step follows: the inference kernels' packed weights lag from here)
         return (None, None, d_skts) + tuple(grads)
 

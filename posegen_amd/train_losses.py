@@ -32,7 +32,8 @@ REG_REFUSAL = ("reg_fn = {0!r} is refused: the reference calls it with reduction
                "with the unreduced [n] tensor, so its total_loss has shape [n] and backward() raises; only reg_fn = 'BCE' trains there")
 SUMMARY = ("total_loss", "rgb_loss", "rgb_loss0", "reg_loss", "reg_loss0", "psnr", "psnr0", "alpha", "n_bce", "n_bce0")
 
-_ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+# this module's clause of the refusal of a renderer that is not on a HIP device (_ffi.device_of)
+NO_CPU = " (torch 'cuda:N'); the training losses run in the library only,"
 
 
 def check_loss_settings(loss_fn, reg_fn, loss_beta=0.1):
@@ -46,14 +47,6 @@ def check_loss_settings(loss_fn, reg_fn, loss_beta=0.1):
     if loss_fn == "Huber" and not float(loss_beta) >= 0.0:
         raise ValueError(f"photometric_loss: loss_beta = {loss_beta} (smooth-L1 needs beta >= 0)")
     return LOSS_KINDS[loss_fn], REG_KINDS[reg_fn]
-
-
-def _device_of(renderer, who: str) -> torch.device:
-    device = torch.device(getattr(renderer, "device", "cpu"))
-    if device.type != "cuda":
-        raise NotImplementedError(f"{who}: the renderer is on {device}, not on a HIP device (torch 'cuda:N'); the training losses run in "
-                                  "the library only, there is no CPU path")
-    return device
 
 
 def _on_device(t, dev, who, name):
@@ -92,9 +85,8 @@ class _PhotometricFn(torch.autograd.Function):
         loss_kind, reg_kind = kinds
         beta, use_background, coarse_weight, reg_coef, base_bg = scalars
         with torch.cuda.device(dev):
-            renderer._check(renderer.lib.pg_train_loss(renderer.handle, renderer._stream(), n, *[_ptr(t) for t in maps], _ptr(target), _ptr(bgs),
-                                                       float(base_bg), _ptr(fgs), loss_kind, float(beta), int(bool(use_background)),
-                                                       float(coarse_weight), reg_kind, float(reg_coef), _ptr(summary), *[_ptr(g) for g in grads]))
+            _ffi.call(renderer, "pg_train_loss", n, *maps, target, bgs, float(base_bg), fgs, loss_kind, float(beta), int(bool(use_background)),
+                      float(coarse_weight), reg_kind, float(reg_coef), summary, *grads)
         ctx.grads = grads
         ctx.meta = [None if t is None else (tuple(t.shape), t.dtype) for t in (rgb_map, acc_map, rgb0, acc0)]
         outs = tuple(summary[i] for i in range(len(SUMMARY)))
@@ -116,7 +108,7 @@ def photometric_loss(preds: Dict[str, torch.Tensor], batch, *, loss_fn: str, los
     `batch`: target_s [n,3], fgs [n,1] (with reg_fn), bgs [n,3] (optional: otherwise the scalar `base_bg`).  reg_fn 'L1' / 'MSE' are
     refused (see REG_REFUSAL).  With BCE and no ray of fgs < 1 the regulariser and the total are NaN and its gradient zero."""
     kinds = check_loss_settings(loss_fn, reg_fn, loss_beta)
-    dev = _device_of(renderer, "photometric_loss")
+    dev = _ffi.device_of(renderer, "photometric_loss", NO_CPU)
     who = "photometric_loss"
     rgb, acc = _on_device(preds["rgb_map"], dev, who, "rgb_map"), _on_device(preds["acc_map"], dev, who, "acc_map")
     rgb0, acc0 = (_on_device(preds[k], dev, who, k) for k in ("rgb0", "acc0")) if "rgb0" in preds else (None, None)
@@ -173,10 +165,8 @@ class _PoseRegFn(torch.autograd.Function):
         tol, coef, ext_scale, temp_coef = scalars
         keep = [_f32(a_rots), _f32(a_kps)] + [_f32(t) for t in (temporal or (None,) * 5)]
         with torch.cuda.device(dev):
-            renderer._check(renderer.lib.pg_pose_reg_loss(renderer.handle, renderer._stream(), n, _ptr(r32), _ptr(k32), keep[0].shape[0], _ptr(keep[0]),
-                                                          _ptr(keep[1]), idx.ctypes.data_as(C.POINTER(C.c_int32)), float(tol), float(coef),
-                                                          float(ext_scale), *[_ptr(t) for t in keep[2:]], float(temp_coef), _ptr(summary),
-                                                          _ptr(d_rots), _ptr(d_kps)))
+            _ffi.call(renderer, "pg_pose_reg_loss", n, r32, k32, keep[0].shape[0], keep[0], keep[1], idx.ctypes.data_as(C.POINTER(C.c_int32)),
+                      float(tol), float(coef), float(ext_scale), *keep[2:], float(temp_coef), summary, d_rots, d_kps)
         ctx.grads = (d_rots, d_kps)
         ctx.meta = [(tuple(rots.shape), rots.dtype), (tuple(kps.shape), kps.dtype)]
         outs = (summary[3], summary[0], summary[1], summary[2])
@@ -214,7 +204,7 @@ def pose_regulariser(rots, kps, kp_idx_host, anchors, *, tol: float, coef: float
                 raise ValueError(f"{who}: a temporal tensor is {tuple(t.shape)}, {shape} expected")
     if any(math.isnan(float(x)) for x in (tol, coef, temp_coef)) or not float(ext_scale) > 0.0:
         raise ValueError(f"{who}: tol = {tol}, coef = {coef}, temp_coef = {temp_coef}, ext_scale = {ext_scale} (no NaN; ext_scale > 0)")
-    dev = _device_of(renderer, who)
+    dev = _ffi.device_of(renderer, who, NO_CPU)
     for name, t in (("rots", rots), ("kps", kps), ("anchors['rots']", a_rots), ("anchors['kps']", a_kps)) + tuple(("temporal", t) for t in temp or ()):
         _on_device(t, dev, who, name)
     total, kp_loss, temp_loss, mpjpc = _PoseRegFn.apply(renderer, rots, kps, idx, a_rots, a_kps, temp, (tol, coef, ext_scale, temp_coef))
@@ -233,7 +223,7 @@ def grad_norms(module_or_params, renderer):
     grads = [p.grad for p in params if p.grad is not None]
     if not grads:
         raise ValueError("grad_norms: no parameter has a gradient (the reference divides by zero here)")
-    dev = _device_of(renderer, "grad_norms")
+    dev = _ffi.device_of(renderer, "grad_norms", NO_CPU)
     keep = []
     for g in grads:
         _on_device(g, dev, "grad_norms", "a gradient")
@@ -245,5 +235,5 @@ def grad_norms(module_or_params, renderer):
     counts = (C.c_int64 * k)(*[g.numel() for g in keep])
     out = torch.empty(2 + k, dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
-        renderer._check(renderer.lib.pg_grad_norms(renderer.handle, renderer._stream(), k, ptrs, counts, _ptr(out)))
+        _ffi.call(renderer, "pg_grad_norms", k, ptrs, counts, out)
     return out[0], out[1], out[2:]

@@ -398,6 +398,26 @@ def test_frame_plan_partition_and_layout_are_clean_under_address_and_ub_sanitize
     assert "1152 frame plans clean under ASan/UBSan" in run.stdout
 
 
+def test_module_slot_table_is_clean_under_address_and_ub_sanitizers(tmp_path):
+    """pg_modules.h (where the twelve modules keep their state on the handle; what pg_state and pg_destroy run) as a stand-alone
+    program with its own main: peek before get is null, get twice is one object, clear destroys in slot order, leaves every slot
+    null and is a no-op the second time, and a table that goes out of scope with live slots frees them."""
+    clang = "/opt/rocm/lib/llvm/bin/clang++"
+    if not os.path.exists(clang):
+        pytest.skip("ROCm clang++ not found")
+    exe = str(tmp_path / "module_slots_asan")
+    csrc = os.path.join(REPO, "posegen_amd", "csrc")
+    build = subprocess.run([clang, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                            "-fno-omit-frame-pointer", "-I", csrc, os.path.join(REPO, "tools", "sanitize", "module_slots_asan.cpp"),
+                            "-o", exe], capture_output=True, text=True)
+    if build.returncode != 0 and "sanitizer" in build.stderr.lower() and "cannot find" in build.stderr.lower():
+        pytest.skip("sanitizer runtime not installed")
+    assert build.returncode == 0, build.stderr[-2000:]
+    run = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert run.returncode == 0, (run.stdout[-1500:], run.stderr[-3000:])
+    assert "module slots clean under ASan/UBSan" in run.stdout
+
+
 def test_bench_launches_itself_for_n_gpus_dry_run():
     """`python bench.py --gpus 2` with no rendezvous in the environment starts its own two
     ranks (as a child process) and relays rank 0's single JSON line; --dry-run swaps the renderer
