@@ -1,4 +1,4 @@
-"""ctypes binding of libposegen_hip.so (include/posegen_hip.h).
+"""ctypes binding of libposegen_hip.so (include/posegen_hip.h, include/posegen_gan.h).
 
 north_star asks for a "thin C-ABI cffi layer"; cffi is not installed in the build
 image (and cannot be: no network), so the same C ABI is bound with ctypes from the
@@ -97,6 +97,24 @@ class PgOutputs(C.Structure):
     _fields_ = [(k, _FP) for k in ("rgb_map", "disp_map", "acc_map", "alpha", "rgb0", "disp0", "acc0",
                                    "alpha0", "near_far", "z_coarse", "z_fine", "raw_coarse", "raw_fine",
                                    "weights0")]
+
+
+PG_DISC_MAX_PATHS, PG_DISC_MAX_POINTS, PG_DISC_LAYERS = 8, 24, 5
+
+
+class PgDiscPath(C.Structure):
+    """pg_disc_path (include/posegen_gan.h): one five-layer path over the rows sel[:n_sel] of a pose"""
+    _fields_ = [("n_sel", C.c_int32), ("sel", C.c_int32 * PG_DISC_MAX_POINTS), ("width", C.c_int32), ("mid", C.c_int32)]
+
+
+class PgDiscSpec(C.Structure):
+    _fields_ = [("n_paths", C.c_int32), ("n_points", C.c_int32), ("point_dim", C.c_int32), ("path", PgDiscPath * PG_DISC_MAX_PATHS),
+                ("slope", C.c_float)]
+
+
+class PgDiscParams(C.Structure):
+    """pg_disc_params / pg_disc_grads: per path five weight and five bias device pointers, where torch keeps them"""
+    _fields_ = [("w", (_FP * PG_DISC_LAYERS) * PG_DISC_MAX_PATHS), ("b", (_FP * PG_DISC_LAYERS) * PG_DISC_MAX_PATHS)]
 
 
 # every symbol include/posegen_hip.h declares: (restype, argtypes)
@@ -231,6 +249,18 @@ PROTOTYPES = {
                                            C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_void_p, _FP, _FP, _FP, _FP, _FP]),
 }
 
+# every symbol include/posegen_gan.h declares (the second public header: PROTOTYPES stays the table of posegen_hip.h alone, which
+# its tests compare with that header symbol for symbol); bound by load_library and called through `call` like the others
+GAN_PROTOTYPES = {
+    "pg_disc_tape_floats": (C.c_int, [C.POINTER(PgDiscSpec), C.c_int64, C.POINTER(C.c_int64)]),
+    "pg_disc_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(PgDiscSpec), C.POINTER(PgDiscParams), _FP, C.c_int64, _FP, _FP]),
+    "pg_disc_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(PgDiscSpec), C.POINTER(PgDiscParams), _FP, C.c_int64, _FP, _FP, _FP,
+                                   C.POINTER(PgDiscParams)]),
+    "pg_disc_loss": (C.c_int, [C.c_void_p, C.c_void_p, _FP, C.c_int64, C.c_float, C.c_double, C.c_void_p, _FP]),
+    "pg_pool_exchange": (C.c_int, [C.c_void_p, C.c_void_p, _FP, C.c_int64, C.c_int32, C.c_int64, _FP, C.c_int64, C.c_void_p, C.c_void_p,
+                                   _FP]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -248,7 +278,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         lib = C.CDLL(p)
     except OSError as e:  # pragma: no cover - depends on the box
         raise HipLibraryError(f"cannot load {p}: {e}") from e
-    for name, (res, args) in PROTOTYPES.items():
+    for name, (res, args) in list(PROTOTYPES.items()) + list(GAN_PROTOTYPES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

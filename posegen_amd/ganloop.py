@@ -6,6 +6,9 @@ In the reference every `run_render` call of the training loop (run_gan.py:2041-2
   * renders rpi = 20 frames through nn.DataParallel(RayCaster),
   * writes them as PNG files, reads them back, crops [100:412]^2, normalises, and resizes to 224 x 224
     with skimage (anti_aliasing=True) for the SPIN / HMR regressor.
+The adversarial game that runs on every batch -- the pose discriminators, their losses and the pool of generated poses -- is
+`discriminators.py`; `generator_adversarial_loss` and `discriminator_step` below are the loop's two call sites of it.
+
 `render_for_regressor` is that call with the HIP renderer: poses stay on the GPU (pg_pose_kinematics ->
 pg_pose_boxes -> pg_render_frame with a uint8 frame), no files, and one 16-byte-per-frame device->host copy
 (the integer boxes size the launches); the crop / normalise / anti-aliased resize run as torch ops on the
@@ -154,3 +157,27 @@ def regressor_body_loss(body, pred_rotmat: torch.Tensor, pred_betas: torch.Tenso
     pred = body.differentiable(pred_betas, pred_rotmat, pose2rot=False, regressor=regressor, joints=False).regressed
     return pose_losses.pose_loss(pred, gt_kps.detach(), joints=pose_eval.H36M_TO_J14 if joints is None else joints, root=root, kind=kind,
                                  weight=weight, cap=cap, renderer=body.renderer)
+
+
+def generator_adversarial_loss(disc, real: Optional[torch.Tensor], fake: torch.Tensor, accuracies: bool = False):
+    """The generator step's call of `get_adv_loss` (run_gan.py:1117-1140, 2016-2021): 0.5 mse(D(fake), 1) as a float64 device scalar whose
+    backward reaches `fake` through pg_disc_backward -- with `requires_grad` off on the discriminator's parameters (`set_grad([model_d3d],
+    False)`) no weight-gradient product runs.  `disc`: a `discriminators.PartDiscriminator`.  Returns (loss, real_acc, fake_acc); the
+    accuracies (device scalars) and the real pass only with `accuracies`."""
+    from . import discriminators
+    return discriminators.adversarial_loss(disc, real, fake, accuracies)
+
+
+def discriminator_step(disc, optimizer, real: torch.Tensor, fake: torch.Tensor, pool, rng=None, max_norm: float = 1.0):
+    """`train_dis` (run_gan.py:1143-1177): zero_grad, the generated poses through the pool (`discriminators.FakePool`; `rng`: its draws,
+    None = the global np.random as the reference), 0.5 (mse(D(real), 1) + mse(D(fake), 0)), backward, clip_grad_norm_(max_norm),
+    optimizer.step().  Returns (real_acc, fake_acc, loss) as device scalars; nothing synchronises (the reference's three copies to the
+    host are gone)."""
+    from . import discriminators
+    optimizer.zero_grad()
+    fake = pool(fake.detach(), rng)
+    loss, real_acc, fake_acc = discriminators.discriminator_loss(disc, real.detach(), fake)
+    loss.backward()
+    torch.nn.utils.clip_grad_norm_(disc.parameters(), max_norm=max_norm)
+    optimizer.step()
+    return real_acc, fake_acc, loss.detach()

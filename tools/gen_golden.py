@@ -842,9 +842,10 @@ def gen_frame_metrics_val(out):
     print(f"[frame_metrics_val] {n} cases")
 
 
-def _reference_definitions(path, names):
+def _reference_definitions(path, names, extra=None):
     """The top-level functions and classes `names` of the reference file `path`, compiled from its syntax tree into a namespace
-    that holds numpy and torch only: the file itself is never imported (run_gan.py parses argv and loads model files when it is)."""
+    that holds numpy and torch only (and `extra`, the further globals those definitions name): the file itself is never imported
+    (run_gan.py parses argv and loads model files when it is)."""
     import ast
     import torch
     with open(path) as f:
@@ -854,6 +855,7 @@ def _reference_definitions(path, names):
     if missing:
         sys.exit(f"gen_golden: {path} does not define {sorted(missing)}")
     ns = {"np": np, "torch": torch}
+    ns.update(extra or {})
     exec(compile(ast.Module(body=body, type_ignores=[]), path, "exec"), ns)
     return ns
 
@@ -926,6 +928,104 @@ def gen_pose_scores(out, ref_root):
     path = os.path.join(out, "pose_scores.npz")
     np.savez_compressed(path, **d)
     print(f"[pose_scores] {sum(len(d[f'pred_{t}']) for t in POSE_SCORE_SETS)} poses, {redrawn} drawn again, {os.path.getsize(path)} bytes")
+
+
+class _RecordingNumpy:
+    """numpy with a `random` whose ranf / randint calls are written down (Sample_from_Pool draws from the global np.random)"""
+
+    class _Random:
+        def __init__(self):
+            self.log = []
+
+        def ranf(self):
+            v = np.random.ranf()
+            self.log.append(("ranf", v))
+            return v
+
+        def randint(self, lo, hi):
+            v = np.random.randint(lo, hi)
+            self.log.append(("randint", v))
+            return v
+
+    def __init__(self):
+        self.random = self._Random()
+
+    def __getattr__(self, item):
+        return getattr(np, item)
+
+
+POSE_DISC_WEIGHT_SEED, POSE_DISC_INPUT_SEED, POSE_DISC_POOL_SEED = 20241020, 77, 5
+
+
+def gen_pose_discriminators(out, ref_root):
+    """The adversarial game (posegen_amd/discriminators.py, include/posegen_gan.h): Disc_Joint_Path, Pos3dDiscriminator,
+    Pos2dDiscriminator, Sample_from_Pool and get_discriminator_accuracy lifted out of run_gan.py (:578-599, :982-1046, :1101-1115) and run
+    in float64 on the CPU.  Weights come from the project's own generator (tests/gan_ref.make_params at a stored seed, loaded through
+    the reference's state-dict keys); B = 5 poses.  Stored: the seeds, the inputs, both models' predictions, for the 3-D model under
+    get_adv_loss's 0.5 mse(D(x), 1) the gradient of the input and per parameter the gradient's sum, abs-sum and sampled entries, the
+    state-dict key lists, an accuracy case, and a pool trace (capacity 6, rows of 4 floats, three calls of 5 items under
+    np.random.seed) with the draws the reference consumed.  Only arrays are stored."""
+    import copy
+    import torch
+    import torch.nn as nn
+    from posegen_amd import discriminators as disc
+    from tests import gan_ref
+    rec = _RecordingNumpy()
+    rg = _reference_definitions(os.path.join(ref_root, "run_gan.py"),
+                                ["Disc_Joint_Path", "Pos3dDiscriminator", "Pos2dDiscriminator", "Sample_from_Pool", "get_discriminator_accuracy"],
+                                extra={"nn": nn, "copy": copy})
+    d = {"weight_seed": np.int64(POSE_DISC_WEIGHT_SEED), "input_seed": np.int64(POSE_DISC_INPUT_SEED), "pool_seed": np.int64(POSE_DISC_POOL_SEED)}
+    for tag, cls, spec in (("3d", "Pos3dDiscriminator", disc.pos3d_spec()), ("2d", "Pos2dDiscriminator", disc.pos2d_spec())):
+        model = rg[cls]().double()
+        keys = list(model.state_dict().keys())
+        params = gan_ref.make_params(spec, POSE_DISC_WEIGHT_SEED)
+        sd = {}
+        for p, (name, _, _, _) in enumerate(spec.paths):
+            for lname, (w, b) in zip(disc.LAYER_NAMES, params[p]):
+                prefix = f"{name}.{lname}" if name else lname
+                sd[prefix + ".weight"], sd[prefix + ".bias"] = torch.tensor(w).double(), torch.tensor(b).double()
+        model.load_state_dict(sd, strict=True)
+        x = gan_ref.make_inputs(spec, 5, POSE_DISC_INPUT_SEED)
+        xt = torch.tensor(x).double().requires_grad_(True)
+        pred = model(xt)
+        d[f"keys_{tag}"] = np.asarray(keys)
+        d[f"x_{tag}"], d[f"pred_{tag}"] = x, pred.detach().numpy()
+        if tag == "3d":
+            loss = 0.5 * nn.MSELoss()(pred, torch.ones_like(pred))
+            loss.backward()
+            d["loss_3d"], d["d_x_3d"] = np.float64(loss.item()), xt.grad.numpy()
+            named = dict(model.named_parameters())
+            d["grad_sum_3d"] = np.asarray([named[k].grad.sum().item() for k in keys])
+            d["grad_abs_sum_3d"] = np.asarray([named[k].grad.abs().sum().item() for k in keys])
+            d["grad_samples_3d"] = np.concatenate([named[k].grad.reshape(-1)[gan_ref.grad_sample_index(named[k].numel())].numpy() for k in keys])
+            acc_pred = pred.detach().reshape(-1).float()
+            acc_pred[:4] = torch.tensor([0.5, 1.5, 0.49999997, 1.5000001])
+            d["acc_pred"] = acc_pred.numpy()
+            d["acc_real"] = np.float64(rg["get_discriminator_accuracy"](acc_pred, torch.ones_like(acc_pred)))
+            d["acc_fake"] = np.float64(rg["get_discriminator_accuracy"](acc_pred, torch.zeros_like(acc_pred)))
+    # the pool: three calls of five rows on a pool of six, the global generator seeded, its draws written down
+    rg_pool = _reference_definitions(os.path.join(ref_root, "run_gan.py"), ["Sample_from_Pool"], extra={"np": rec, "copy": copy})
+    pool = rg_pool["Sample_from_Pool"](max_elements=6)
+    items = np.random.RandomState(9).standard_normal((3, 5, 4)).astype(np.float32)
+    np.random.seed(POSE_DISC_POOL_SEED)
+    returned, swap, slot = [], np.zeros((3, 5), np.uint8), np.zeros((3, 5), np.int32)
+    for c in range(3):
+        full_from = min(5, max(0, 6 - pool.cur_elements))
+        rec.random.log.clear()
+        returned.append(np.stack(pool(items[c])))
+        i = full_from - 1
+        for kind, v in rec.random.log:
+            if kind == "ranf":
+                i += 1
+                swap[c, i] = v > 0.5
+            else:
+                slot[c, i] = v
+        assert i == 4
+    d["pool_items"], d["pool_returned"], d["pool_final"] = items, np.stack(returned), np.stack(pool.items)
+    d["pool_swap"], d["pool_slot"] = swap, slot
+    path = os.path.join(out, "pose_discriminators.npz")
+    np.savez_compressed(path, **d)
+    print(f"[pose_discriminators] {os.path.getsize(path)} bytes; pool swaps {swap.sum(1)}")
 
 
 def main():
@@ -1024,6 +1124,9 @@ def main():
     # pose scores: the reference's Procrustes / MPJPE functions on seeded poses (consumes no torch RNG state)
     if want("pose_scores"):
         gen_pose_scores(a.out, a.ref)
+    # the adversarial game: the reference's discriminators, accuracy and pool in float64 (consumes no torch RNG state)
+    if want("pose_discriminators"):
+        gen_pose_discriminators(a.out, a.ref)
 
 
 if __name__ == "__main__":
