@@ -58,8 +58,14 @@ def _check_against_ref(renderer, grid, thr, clamp=NINF):
     assert v.shape == rv.shape and t.shape == rt.shape
     assert np.array_equal(t, rt)
     # the index part of a vertex (the integer coordinates, the edge's lower point) exactly, the position within the tolerance
-    assert np.array_equal(np.floor(v), np.floor(rv))
-    assert (np.abs(v.astype(np.float64) - v64) <= mr.position_tolerance(v64)).all()
+    assert np.array_equal(np.floor(v), np.floor(rv), equal_nan=True)
+    ok64 = np.isfinite(v64)
+    assert (np.abs(v.astype(np.float64) - v64) <= mr.position_tolerance(v64))[ok64].all()
+    # the kernel's tt and i + tt are the restatement's float32 operations: the same bits wherever the restatement has a number, and a
+    # NaN (an edge with an end that is no number) in the same element -- of either sign, hosts differ in the NaN they generate
+    fin = np.isfinite(rv)
+    assert v[fin].tobytes() == rv[fin].tobytes()
+    assert np.array_equal(v, rv, equal_nan=True)
     return v, t
 
 
