@@ -300,8 +300,9 @@ template <typename V> __device__ __forceinline__ V wave_sum(V x) {
 
 // act_fn of raw2outputs (get_density_fn, core/raycasters.py:230-238): F.relu, or F.softplus(x - shift, beta=1) with
 // torch's threshold of 20 (the linear branch above it)
+// (a NaN comes out as NaN, as from both of them: fmaxf would return its other operand)
 __device__ __forceinline__ float density_act(float x, int act, float shift) {
-    if (act == 0) return fmaxf(x, 0.0f);
+    if (act == 0) return x < 0.0f ? 0.0f : x;
     const float t = x - shift;
     return t > 20.0f ? t : log1pf(expf(t));
 }
@@ -397,12 +398,14 @@ __device__ __forceinline__ void composite_ray(
     if (lane == 0) {
         if (rgb_out) { rgb_out[ray * 3 + 0] = sr; rgb_out[ray * 3 + 1] = sg; rgb_out[ray * 3 + 2] = sb; }
         if (disp_out) {
-            float disp = 1.0f / fmaxf(1e-10f, sd / (sw + 1e-10f));
+            // (comparisons, not fmaxf / fminf, here and for acc: NaN sums give NaN maps, as the reference's torch.max / torch.minimum)
+            const float depth = sd / (sw + 1e-10f);
+            float disp = 1.0f / (depth < 1e-10f ? 1e-10f : depth);
             // invalid_mask: torch.isclose(sum w, 0) with default rtol/atol -> |sum w| <= 1e-8
             if (fabsf(sw) <= 1e-8f) disp = 0.0f;
             disp_out[ray] = disp;
         }
-        if (acc_out) acc_out[ray] = fminf(sw, 1.0f);
+        if (acc_out) acc_out[ray] = sw > 1.0f ? 1.0f : sw;
     }
     if (n_imp <= 0 || z_fine == nullptr) return;
 

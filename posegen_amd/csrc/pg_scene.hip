@@ -71,8 +71,9 @@ template <typename V> __device__ __forceinline__ V wave_sum(V x) {
     for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
     return x;
 }
+// (a NaN comes out as NaN, as from F.relu / F.softplus: fmaxf would return its other operand)
 __device__ __forceinline__ float density_act(float x, int act, float shift) {
-    if (act == 0) return fmaxf(x, 0.0f);
+    if (act == 0) return x < 0.0f ? 0.0f : x;
     const float t = x - shift;
     return t > 20.0f ? t : log1pf(expf(t));
 }
@@ -198,7 +199,7 @@ __global__ __launch_bounds__(waves_for(PMAX) * 64) void scene_composite_kernel(c
             swd += swp;
             if (a.pacc) {
                 const float pw = (float)wave_sum(swp);
-                if (lane == 0) a.pacc[p * pacc_ld + opix] = fminf(pw, 1.0f);
+                if (lane == 0) a.pacc[p * pacc_ld + opix] = pw > 1.0f ? 1.0f : pw;
             }
         }
         sr = wave_sum(sr); sg = wave_sum(sg); sb = wave_sum(sb); sd = wave_sum(sd);
@@ -206,10 +207,12 @@ __global__ __launch_bounds__(waves_for(PMAX) * 64) void scene_composite_kernel(c
         if (lane == 0) {
             // (a pixel nobody covers: all sums are 0 -- disp 0 by the invalid mask below)
             a.rgb[pix * 3 + 0] = sr; a.rgb[pix * 3 + 1] = sg; a.rgb[pix * 3 + 2] = sb;
-            float disp = 1.0f / fmaxf(1e-10f, sd / (sw + 1e-10f));
+            // composite_ray's closing lines, comparisons instead of fmaxf / fminf: NaN sums give NaN maps, as torch.max / torch.minimum
+            const float depth = sd / (sw + 1e-10f);
+            float disp = 1.0f / (depth < 1e-10f ? 1e-10f : depth);
             if (fabsf(sw) <= 1e-8f) disp = 0.0f;        // torch.isclose(sum w, 0): |sum w| <= 1e-8
             a.disp[pix] = disp;
-            a.acc[pix] = fminf(sw, 1.0f);
+            a.acc[pix] = sw > 1.0f ? 1.0f : sw;
         }
         wave_sync();                        // the wave's LDS rows are reused by its next pixel
     }

@@ -99,10 +99,11 @@ def render_scene(renderer, H: int, W: int, focal, c2w, people, center=None, near
     return out
 
 
-def stage_scene_composite(renderer, z, raw, rows, dirs, want_person_acc=True):
+def stage_scene_composite(renderer, z, raw, rows, dirs, want_person_acc=True, fill=None):
     """scene_composite_kernel on the caller's lists (pg_stage_scene_composite): z / raw = P device tensors [n_p,S] / [n_p,S,4],
     rows int32 [P,n_pix] (outside [0, n_p): absent), dirs [n_pix,3].  Returns a dict of device tensors rgb_map [n_pix,3], disp_map,
-    acc_map [n_pix] (, person_acc [P,n_pix]).  The density line follows the renderer's config."""
+    acc_map [n_pix] (, person_acc [P,n_pix]).  The density line follows the renderer's config.  `fill`: the outputs are prefilled
+    with this value (a test's sentinel) instead of left uninitialised."""
     r = renderer
     dev = r.device
     P = len(z)
@@ -112,9 +113,10 @@ def stage_scene_composite(renderer, z, raw, rows, dirs, want_person_acc=True):
     dirs = dirs.to(dev, torch.float32).contiguous()
     n, S = int(dirs.shape[0]), int(z[0].shape[1])
     assert rows.shape == (P, n) and all(t.shape[1] == S for t in z)
-    out = {"rgb_map": torch.empty(n, 3, device=dev), "disp_map": torch.empty(n, device=dev), "acc_map": torch.empty(n, device=dev)}
+    new = (lambda *shape: torch.empty(*shape, device=dev)) if fill is None else (lambda *shape: torch.full(shape, float(fill), device=dev))
+    out = {"rgb_map": new(n, 3), "disp_map": new(n), "acc_map": new(n)}
     if want_person_acc:
-        out["person_acc"] = torch.empty(P, n, device=dev)
+        out["person_acc"] = new(P, n)
     vp = lambda ts: (C.c_void_p * P)(*[t.data_ptr() for t in ts])
     _ffi.call(r, "pg_stage_scene_composite", n, P, S, vp(z), vp(raw), (C.c_int64 * P)(*[int(t.shape[0]) for t in z]), rows, dirs,
               out["rgb_map"], out["disp_map"], out["acc_map"], out.get("person_acc"))

@@ -189,13 +189,20 @@ def test_unsorted_draws_equal_sorted_draws(renderers, form):
 @pytest.mark.parametrize("form", cr.FORMS)
 def test_a_nan_ray_leaves_the_others_alone(renderers, form):
     """one ray with NaN depths among 69 finite ones, outputs prefilled: the call succeeds and the finite rays are bitwise those of
-    the call without it (nothing is asserted about the NaN ray's own rows); then the merged form on the same rays"""
+    the call without it; the NaN ray's own maps are NaN where the float64 oracle's are (every one: not acc = 1, disp = 1e10 beside a
+    NaN colour, which is what fminf / fmaxf make of NaN sums); then the merged form on the same rays"""
     r = renderers["relu"]
     c, without, keep = cr.make_case_nan_ray(65, 16, form)
     a, b = forward(r, c, fill=SENTINEL), forward(r, without, fill=SENTINEL)
     for k in b:
         assert np.array_equal(a[k][keep], b[k]), k
         assert not np.any(b[k] == SENTINEL), k
+    nan_ray = {k: (v[~keep] if isinstance(v, np.ndarray) else v) for k, v in c.items()}
+    want = cr.reference({**nan_ray, "N": 0, "u_rand": None}, F64)           # the composite alone: the maps do not depend on the new depths
+    for k in ("rgb_map", "disp_map", "acc_map"):
+        print(f"[C] NaN ray {form} {k}: device {a[k][~keep].reshape(-1)}, float64 oracle {want[k].reshape(-1)}")
+        assert np.isnan(want[k]).all(), k
+        assert np.array_equal(np.isnan(a[k][~keep]), np.isnan(want[k])), k
     raw_new = cr.f32(np.random.default_rng(9).normal(0, 1, (cr.N_RAYS, 16, 4)))
     m = {"rays": c["rays"], "z_fine": a["z_fine"], "raw": c["raw"], "raw_new": raw_new, "order": a["order"], "noise1": None}
     mw = {k: (v[keep] if v is not None else None) for k, v in m.items()}

@@ -71,6 +71,46 @@ def test_two_identical_lists_follow_the_tie_rule():
     assert cr.deviation(swapped["rgb_map"], got["rgb_map"]) > 1e-3, "with ties, who comes first is visible"
 
 
+@pytest.mark.parametrize("case", sr.TIE_CASES, ids=lambda c: "P%d-S%d-%s-%s" % c)
+def test_tie_scenes_have_ties_whose_order_is_visible(case):
+    """every tie scene the device is measured on (tests/test_gpu_scene_edges.py): people share depths, the reversed people give
+    another picture, and -- by construction of the bound; asserted so that no generator change can hide a case -- the float32
+    restatement is within composite_ref.bound of the float64 one"""
+    P, S, density, kind = case
+    s = sr.make_scene_ties(*case)
+    assert sr.cross_list_ties(s)
+    assert all(z.dtype == np.float32 and np.all(np.diff(z, axis=-1) >= 0) for z in s["z"]), "every list is non-decreasing"
+    here = np.stack([sr._present(s, p)[1] for p in range(P)])
+    assert all(z.shape[0] == h.sum() + 2 for z, h in zip(s["z"], here)), "two rows no pixel refers to"
+    assert not here[:, [3, 40]].any() and here[:, 5].all() and (here.sum(0) >= 2).sum() > 10
+    r64, r32 = sr.reference(s, F64), sr.reference(s, torch.float32)
+    back = sr.reference(sr.permuted(s, tuple(reversed(range(P)))), F64)
+    assert cr.deviation(back["rgb_map"], r64["rgb_map"]) > 1e-3, "with ties, who comes first is visible"
+    for k in MAPS + ("person_acc",):
+        assert np.isfinite(r64[k]).all() and cr.deviation(r32[k], r64[k]) <= cr.bound(r32[k], r64[k]), k
+    if kind == "flat":
+        i = 5                   # everybody covers it, all depths are equal: only each list's last sample has a delta
+        zs = np.stack([s["z"][p][s["rows"][p, i]] for p in range(P)])
+        assert np.all(zs == zs[0, 0])
+    if kind == "runs":
+        z0 = s["z"][0][s["rows"][0, 5]]
+        assert np.all(z0[1:2 * (S // 2):2] == z0[0:2 * (S // 2):2]) and np.array_equal(s["z"][1][s["rows"][1, 5]], z0)
+
+
+def test_the_many_pixel_scene_and_the_disparity_scene_are_what_they_say():
+    n = 1000
+    s = sr.make_scene_many(5, n)
+    here = np.stack([sr._present(s, p)[1] for p in range(5)])
+    assert s["S"] == 3 and s["dirs"].shape == (n, 3) and not sr.cross_list_ties({**s, "dirs": s["dirs"][:70]})
+    assert (~here.any(0))[600:].sum() > 10 and here.all(0)[600:].sum() > 10 and 0.4 < here.mean() < 0.7
+    d = sr.make_scene_disp()
+    w = sr.reference(d, F64)
+    even = np.arange(sr.N_PIX) % 2 == 0
+    assert np.abs(w["wsum"][even] / cr.DISP_TARGETS[0] - 1).max() <= 1e-3 and np.abs(w["wsum"][~even] / cr.DISP_TARGETS[1] - 1).max() <= 1e-3
+    assert np.abs(w["person_acc"] / (0.5 * w["wsum"]) - 1).max() <= 1e-3, "the weight is split between the two people"
+    assert np.all(w["disp_map"][~even] == 0) and np.all(w["disp_map"][even] > 0)
+
+
 def test_an_opaque_front_sample_hides_the_person_behind():
     s = sr.make_scene(2, 33, "relu", "all", overlap=False)
     assert np.all(s["z"][0].max(-1)[s["rows"][0]] < s["z"][1].min(-1)[s["rows"][1]]), "person 1 stands behind person 0"
