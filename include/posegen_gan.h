@@ -31,8 +31,8 @@ extern "C" {
 typedef struct pg_disc_path {
     int32_t n_sel;                         /* 1 .. n_points */
     int32_t sel[PG_DISC_MAX_POINTS];       /* each in [0, n_points); a row may repeat */
-    int32_t width;                         /* >= 1 */
-    int32_t mid;                           /* >= 1 */
+    int32_t width;                         /* 1 .. 2^20 */
+    int32_t mid;                           /* 1 .. 2^20 */
 } pg_disc_path;
 
 typedef struct pg_disc_spec {
@@ -40,7 +40,7 @@ typedef struct pg_disc_spec {
     int32_t n_points;                      /* 1 .. PG_DISC_MAX_POINTS: rows of a pose */
     int32_t point_dim;                     /* 3 or 2 */
     pg_disc_path path[PG_DISC_MAX_PATHS];
-    float slope;                           /* LeakyReLU's negative slope (nn.LeakyReLU(): 0.01) */
+    float slope;                           /* LeakyReLU's negative slope (nn.LeakyReLU(): 0.01); finite and >= 0, see pg_disc_backward */
 } pg_disc_spec;
 
 /* Per path the five weights [out,in] row-major float32 and the five biases [out], nn.Linear's own layout, read where torch keeps
@@ -67,13 +67,16 @@ int pg_disc_tape_floats(const pg_disc_spec* spec, int64_t B, int64_t* n_floats);
  * float32 products with float32 accumulation on v_mfma_f32_16x16x4_f32 (K in chunks of 16 round four accumulators that are added
  * at the end), bias and LeakyReLU in the epilogue, the head a per-row reduction.  A row's pred and tape bytes depend on that row of x and the parameters alone, not on B or the row's position; a
  * non-finite row stays in its row.  Asynchronous on `stream`.
- * PG_EINVAL, nothing launched: a NULL handle, spec, params, x or pred; a spec outside its limits; B < 1; a NULL parameter pointer
- * of a path in use; a misaligned array. */
+ * PG_EINVAL, nothing launched: a NULL handle, spec, params, x or pred; a spec outside its limits (a width or mid above 2^20 and a
+ * negative, infinite or NaN slope among them); B < 1 or B > 64 * 65535 = 4194240 (a launch has at most 65535 row tiles of 64); a
+ * NULL parameter pointer of a path in use; a misaligned array. */
 int pg_disc_forward(pg_handle* h, void* stream, const pg_disc_spec* spec, const pg_disc_params* params, const float* x, int64_t B,
                     float* pred, float* tape);
 
 /* The backward of pg_disc_forward at the cotangent d_pred [B,n_paths]: dZ = dH (tape > 0 ? 1 : slope) (at exactly 0 the slope, as
- * torch), layer by layer.
+ * torch), layer by layer.  The mask is read off the TAPE's sign, not the pre-activation's: with slope >= 0 the two agree (a negative
+ * z leaves z slope <= 0), with a negative slope a negative z would leave a positive tape value and the mask would say 1 where the
+ * derivative is `slope`.  Hence a negative slope is refused, here and in pg_disc_forward.
  *   d_x     device [B,n_points,point_dim] or NULL.  Every element is written exactly once: the contributions of the paths that select
  *           a row are added in path order (and within a path in selection order); a row that no path selects is zero.  Bitwise the
  *           same with and without `grads`, and a row's bytes do not depend on B or its position.
@@ -107,7 +110,8 @@ int pg_disc_loss(pg_handle* h, void* stream, const float* pred, int64_t n, float
  * was before the call, which includes rows appended by this call -- and takes its place; the last swapped item of a slot is what the
  * pool keeps.  Other items pass through.  The caller advances cur by min(n, cap - cur).  One launch, no atomics: a workgroup per
  * item scans the other items' draws.  A slot outside [0, cap) is treated as no swap.  Asynchronous on `stream`.
- * PG_EINVAL: a NULL handle or array; cap < 1; row_floats < 1; n < 1; cur outside [0, cap]. */
+ * PG_EINVAL: a NULL handle or array; cap < 1 or cap > INT32_MAX (slots are int32); row_floats < 1; n < 1 or n > 8192 (the items'
+ * effective slots sit in the workgroup's LDS, 4 bytes each); cur outside [0, cap]; a misaligned array. */
 int pg_pool_exchange(pg_handle* h, void* stream, float* pool, int64_t cap, int32_t row_floats, int64_t cur, const float* items, int64_t n,
                      const uint8_t* swap, const int32_t* slot, float* out);
 

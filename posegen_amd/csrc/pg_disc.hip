@@ -452,7 +452,8 @@ const char* spec_fault(const pg_disc_spec* s) {
     if (s->n_paths < 1 || s->n_paths > MAXP) return "n_paths outside [1, 8]";
     if (s->n_points < 1 || s->n_points > MAXS) return "n_points outside [1, 24]";
     if (s->point_dim != 2 && s->point_dim != 3) return "point_dim is neither 2 nor 3";
-    if (!(s->slope == s->slope)) return "slope is NaN";
+    // (the backward reads LeakyReLU's mask off the tape's sign: with a negative slope a negative pre-activation leaves a positive tape)
+    if (!(s->slope >= 0.f) || isinf(s->slope)) return "slope is negative or not finite";
     for (int p = 0; p < s->n_paths; ++p) {
         const pg_disc_path& q = s->path[p];
         if (q.n_sel < 1 || q.n_sel > s->n_points) return "a path's n_sel outside [1, n_points]";

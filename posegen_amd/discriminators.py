@@ -32,7 +32,9 @@ from . import _ffi
 LAYER_NAMES = ("layer_1", "layer_2", "layer_3", "layer_last", "layer_pred")
 
 # this module's clause of the refusal of tensors that are not on a HIP device
-NO_CPU = " (torch 'cuda:N'); the discriminators, their loss and the pool run in the library only,"
+POOL_MAX_ITEMS = 8192                      # items of one pg_pool_exchange call (include/posegen_gan.h)
+
+NO_CPU =" (torch 'cuda:N'); the discriminators, their loss and the pool run in the library only,"
 
 
 class PartSpec:
@@ -51,6 +53,9 @@ class PartSpec:
             raise ValueError(f"PartSpec: n_points = {self.n_points} (1 .. {_ffi.PG_DISC_MAX_POINTS}), point_dim = {self.point_dim} (2 or 3)")
         if sorted(self.module_order) != sorted(p[0] for p in self.paths) or len(set(self.module_order)) != len(self.paths):
             raise ValueError("PartSpec: module_order does not name every path once")
+        if not (np.isfinite(self.slope) and self.slope >= 0.0):
+            # the backward reads LeakyReLU's mask off the tape's sign, which a negative slope turns round
+            raise ValueError(f"PartSpec: slope = {self.slope}; a finite slope >= 0 expected")
         for name, sel, width, mid in self.paths:
             if not 1 <= len(sel) <= self.n_points or min(sel) < 0 or max(sel) >= self.n_points or width < 1 or mid < 1:
                 raise ValueError(f"PartSpec: path {name!r}: rows {sel}, width {width}, mid {mid}")
@@ -330,6 +335,8 @@ class FakePool:
         n = int(items.shape[0])
         if n < 1:
             raise ValueError("FakePool: no items")
+        if n > POOL_MAX_ITEMS:
+            raise ValueError(f"FakePool: {n} items in one call; at most {POOL_MAX_ITEMS} (pg_pool_exchange)")
         flat = items.detach().to(torch.float32).reshape(n, -1).contiguous()
         row = int(flat.shape[1])
         if self.pool is None:

@@ -1,6 +1,7 @@
 """The adversarial game without a GPU: the float64 restatement (tests/gan_ref.py) against the reference's own numbers
 (tests/golden/pose_discriminators.npz, written by tools/gen_golden.py from run_gan.py's classes), its hand-written backward against
-float64 autograd, the pool and the host draw order against the reference's trace, the modules' state-dict keys, and the C ABI of
+float64 autograd, its carried backward bound against torch's float32 arithmetic on the ragged spec, the refusal of a negative or
+non-finite slope, the pool (out-of-range slots included) and the host draw order against the reference's trace, the modules' state-dict keys, and the C ABI of
 include/posegen_gan.h as the library exports it."""
 import os
 import re
@@ -97,6 +98,90 @@ def test_the_hand_written_backward_equals_float64_autograd(make_spec):
     if make_spec is gan_ref.toy_spec_sparse:
         unselected = [j for j in range(24) if j not in (0, 5, 7, 23)]
         assert not d_x[:, unselected].any() and d_x[:, [0, 5, 7, 23]].abs().min() > 0
+
+
+def test_the_ragged_specs_hit_the_shapes_they_are_for():
+    s3, s2 = gan_ref.ragged3_spec(), gan_ref.ragged2_spec()
+    assert [(len(sel) * 3, w, m) for _, sel, w, m in s3.paths] == [(3, 1, 1), (9, 67, 130), (15, 64, 16), (6, 129, 65), (3, 17, 80),
+                                                                  (6, 80, 63), (9, 16, 64), (6, 33, 5)]
+    assert s3.n_points == 5 and s3.point_dim == 3 and s3.slope == 0.01 and len(s3.paths) == _ffi.PG_DISC_MAX_PATHS
+    assert [(len(sel) * 2, w, m) for _, sel, w, m in s2.paths] == [(48, 65, 3), (2, 3, 67)] and s2.n_points == 24 and s2.point_dim == 2
+    # rows 0, 1 and 3 are selected at most once within a path; 2 and 4 are repeated in one
+    assert all(sel.count(j) <= 1 for _, sel, _, _ in s3.paths for j in (0, 1, 3)) and s3.paths[1][1].count(4) == 2 and s3.paths[7][1].count(2) == 2
+    one = gan_ref.one_path_spec(s3, 3)
+    assert one.paths == [s3.paths[3]] and one.n_points == 5 and one.layer_shapes(0) == s3.layer_shapes(3)
+
+
+@pytest.mark.parametrize("B", [1, 63, 65, 129])
+def test_the_backward_bound_holds_torch_float32_on_the_ragged_spec(B):
+    """torch's own float32 arithmetic on the CPU stands in for the device: its tape and masks go in as the layer inputs, its dW and
+    d_x must lie within the carried bound.  Its db need not (torch sums the bias gradient in float32; the bound describes a double
+    sum rounded once), so db is checked on that: the float32 chain's own dZ summed in double and rounded once."""
+    spec = gan_ref.ragged3_spec()
+    params = gan_ref.make_params(spec, 18)
+    x = gan_ref.make_inputs(spec, B, 100 + B)
+    d_pred = np.random.RandomState(3).standard_normal((B, 8)).astype(np.float32)
+    _, tapes32 = gan_ref.forward(spec, params, x, torch.float32)
+    tapes32 = [[h.numpy() for h in tape] for tape in tapes32]
+    masks = gan_ref.masks_of(tapes32)
+    d_x, grads, e_dx, bounds = gan_ref.backward_with_bound(spec, params, x, tapes32, masks, d_pred)
+    plain_dx, plain = gan_ref.backward(spec, params, x, tapes32, masks, d_pred)
+    assert torch.equal(plain_dx, d_x) and all(torch.equal(a, b) for g, h in zip(grads, plain) for wb, vc in zip(g, h) for a, b in zip(wb, vc))
+    dzs = []
+    dx32, g32 = gan_ref.backward(spec, params, x, tapes32, masks, d_pred, torch.float32, dz_out=dzs)
+    err = (dx32.to(gan_ref.F64) - d_x).abs()
+    assert bool((err <= e_dx).all())
+    worst_w = 0.0
+    for p in range(8):
+        for l in range(5):
+            dw_err = (g32[p][l][0].to(gan_ref.F64) - grads[p][l][0]).abs()
+            assert bool((dw_err <= bounds[p][l][0]).all()), (p, l)
+            worst_w = max(worst_w, float((dw_err / bounds[p][l][0]).max()))
+            db_once = dzs[p][l].to(gan_ref.F64).sum(0).to(torch.float32).to(gan_ref.F64)
+            assert bool(((db_once - grads[p][l][1]).abs() <= bounds[p][l][1]).all()), (p, l)
+            assert bounds[p][l][0].shape == grads[p][l][0].shape and bounds[p][l][1].shape == grads[p][l][1].shape
+    assert 0.0 < worst_w <= 1.0 and 0.0 < float((err / e_dx).max()) <= 1.0
+
+
+def test_the_bound_is_zero_on_rows_that_no_path_selects():
+    spec = gan_ref.toy_spec_sparse()
+    params = gan_ref.make_params(spec, 3)
+    x = gan_ref.make_inputs(spec, 4, 4)
+    _, tapes = gan_ref.forward(spec, params, x)
+    d_x, _, e_dx, _ = gan_ref.backward_with_bound(spec, params, x, tapes, gan_ref.masks_of(tapes), np.ones((4, 2)))
+    unselected = [j for j in range(24) if j not in (0, 5, 7, 23)]
+    assert not e_dx[:, unselected].any() and not d_x[:, unselected].any() and e_dx[:, [0, 5, 7, 23]].min() > 0
+
+
+def test_a_slot_outside_the_pool_passes_through():
+    rng = np.random.RandomState(6)
+    pool0 = rng.standard_normal((4, 3)).astype(np.float32)
+    items = rng.standard_normal((6, 3)).astype(np.float32)
+    swap, slot = np.uint8([1, 1, 1, 1, 0, 1]), np.int32([-1, 4, 2, 2 ** 31 - 1, 1, 2])
+    out, pool, cur = gan_ref.pool_exchange(pool0, 4, items, swap, slot)
+    assert cur == 4 and np.array_equal(out[[0, 1, 3, 4]], items[[0, 1, 3, 4]])
+    assert np.array_equal(out[2], pool0[2]) and np.array_equal(out[5], items[2]) and np.array_equal(pool[2], items[5])
+    assert np.array_equal(pool[[0, 1, 3]], pool0[[0, 1, 3]])
+    # while the pool fills nothing is read from `slot`
+    out, pool, cur = gan_ref.pool_exchange(np.zeros((8, 3), np.float32), 3, items, np.ones(6, np.uint8), np.int32([-5] * 5 + [8]))
+    assert cur == 8 and np.array_equal(out, items) and np.array_equal(pool[3:8], items[:5])
+
+
+@pytest.mark.parametrize("slope", [-0.01, float("inf"), float("-inf"), float("nan")])
+def test_a_negative_or_non_finite_slope_is_refused(slope):
+    """the backward reads LeakyReLU's mask off the tape's sign, which only a slope >= 0 preserves"""
+    with pytest.raises(ValueError, match="slope"):
+        disc.PartSpec(5, 3, [("p", [0, 1], 20, 8)], slope=slope)
+    cs = disc.PartSpec(5, 3, [("p", [0, 1], 20, 8)]).c_spec()
+    n = _ffi.C.c_int64(-1)
+    lib = _ffi.load_library()
+    assert lib.pg_disc_tape_floats(_ffi.C.byref(cs), 4, _ffi.C.byref(n)) == _ffi.PG_OK and n.value == 4 * 68
+    cs.slope, n.value = slope, -1
+    assert lib.pg_disc_tape_floats(_ffi.C.byref(cs), 4, _ffi.C.byref(n)) == _ffi.PG_EINVAL and n.value == -1
+    for ok in (0.0, 1.0, 0.2):
+        cs.slope = ok
+        assert lib.pg_disc_tape_floats(_ffi.C.byref(cs), 4, _ffi.C.byref(n)) == _ffi.PG_OK
+        assert disc.PartSpec(5, 3, [("p", [0, 1], 20, 8)], slope=ok).slope == ok
 
 
 def test_the_accuracy_compares_in_float32_like_the_reference():

@@ -93,12 +93,9 @@ def same_bytes(a, b):
 
 
 # ---- layer-local ---------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name,B", LAYER_CASES)
-def test_every_layer_is_within_the_float32_dot_product_bound_of_the_float64_layer(renderer, name, B):
-    spec, params, x, pdev, xdev = case(name, B)
-    pred, tape = dev_forward(renderer, spec, pdev, xdev)
-    views = tape_views(spec, B, tape)
-    pred = pred.cpu().numpy()
+def assert_layer_local(tag, spec, params, x, views, pred):
+    """the layer-local criterion of the docstring on a forward's tape `views` and host `pred`; -> the worst error / bound.  Where
+    the bound is 0 (a zero row of W with a zero bias) the error must be 0 as well."""
     worst = 0.0
     for p, layers in enumerate(params):
         h_in = gan_ref.path_input(spec, p, gan_ref.t64(x))
@@ -108,10 +105,19 @@ def test_every_layer_is_within_the_float32_dot_product_bound_of_the_float64_laye
             got = gan_ref.t64(views[p][l] if l < 4 else pred[:, p:p + 1])
             K = w.shape[1]
             bound = (K + 2) * U * (h_in.abs() @ w64.abs().T + b64.abs()) + U * want.abs()
-            ratio = float(((got - want).abs() / bound).max())
+            err = (got - want).abs()
+            ratio = float(torch.where(bound > 0, err / bound, torch.where(err > 0, float("inf"), 0.0).to(gan_ref.F64)).max())
             worst = max(worst, ratio)
-            assert ratio <= 1.0, (name, B, p, l, ratio)
+            assert ratio <= 1.0, (tag, p, l, ratio)
             h_in = got                                                       # the next layer starts from the device's own values
+    return worst
+
+
+@pytest.mark.parametrize("name,B", LAYER_CASES)
+def test_every_layer_is_within_the_float32_dot_product_bound_of_the_float64_layer(renderer, name, B):
+    spec, params, x, pdev, xdev = case(name, B)
+    pred, tape = dev_forward(renderer, spec, pdev, xdev)
+    worst = assert_layer_local((name, B), spec, params, x, tape_views(spec, B, tape), pred.cpu().numpy())
     print(f"layer-local {name} B={B}: worst error / bound {worst:.3f}")
 
 
@@ -253,10 +259,14 @@ def test_the_loss_and_its_count_equal_the_restatement(renderer, n, label):
 
 
 # ---- the pool --------------------------------------------------------------------------------------------------------------------------------
-def run_pool_trace(renderer, cap, row, calls):
-    """`calls`: (items, swap, slot) in turn through pg_pool_exchange (FakePool.exchange) and through the restatement, bitwise"""
+def run_pool_trace(renderer, cap, row, calls, start=None):
+    """`calls`: (items, swap, slot) in turn through pg_pool_exchange (FakePool.exchange) and through the restatement, bitwise.
+    `start`: a full pool [cap,row] to begin from (cur = cap from the first call); None = an empty one"""
     pool = disc.FakePool(cap, renderer)
     ref_pool, cur = np.zeros((cap, row), np.float32), 0
+    if start is not None:
+        ref_pool, cur = np.array(start, dtype=np.float32).reshape(cap, row), cap
+        pool.pool, pool.cur = torch.tensor(ref_pool, device=DEV), cap
     for c, (items, swap, slot) in enumerate(calls):
         got = pool.exchange(torch.tensor(items, device=DEV), swap, slot)
         want, ref_pool, cur = gan_ref.pool_exchange(ref_pool, cur, items, swap, slot)
