@@ -26,6 +26,7 @@ _TRAIN_LOSS_NAMES = ("photometric_loss", "pose_regulariser", "grad_norms")
 _TRAINER_NAMES = ("HipTrainer",)
 _REGRESSOR_BATCH_NAMES = ("PixelStore", "RegressorBatchSource", "regressor_input", "fixed_crop_boxes", "mpii_crop_boxes", "REFERENCE_NORM")
 _SCENE_NAMES = ("ScenePerson", "render_scene", "render_scenes", "place_people")
+_GENERATOR_NAMES = ("HipBAGenerator", "HipRTGenerator", "HipPoseGenerator")
 
 
 def __getattr__(name):
@@ -63,4 +64,7 @@ def __getattr__(name):
     if name in _SCENE_NAMES:                  # several people in one frame (imports torch as well)
         from . import scene
         return getattr(scene, name)
+    if name in _GENERATOR_NAMES:              # the pose generator of the GAN loop (imports torch as well)
+        from . import generators
+        return getattr(generators, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

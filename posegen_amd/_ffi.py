@@ -1,4 +1,4 @@
-"""ctypes binding of libposegen_hip.so (include/posegen_hip.h, include/posegen_gan.h).
+"""ctypes binding of libposegen_hip.so (include/posegen_hip.h, include/posegen_gan.h, include/posegen_generator.h).
 
 north_star asks for a "thin C-ABI cffi layer"; cffi is not installed in the build
 image (and cannot be: no network), so the same C ABI is bound with ctypes from the
@@ -116,6 +116,33 @@ class PgDiscParams(C.Structure):
     """pg_disc_params / pg_disc_grads: per path five weight and five bias device pointers, where torch keeps them"""
     _fields_ = [("w", (_FP * PG_DISC_LAYERS) * PG_DISC_MAX_PATHS), ("b", (_FP * PG_DISC_LAYERS) * PG_DISC_MAX_PATHS)]
 
+
+PG_GEN_MAX_TRUNKS, PG_GEN_MAX_STAGES, PG_GEN_MAX_LAYERS, PG_GEN_MAX_DIM, PG_GEN_MAX_ROWS, PG_GEN_MAX_JOINTS = 4, 4, 9, 512, 1048576, 64
+
+
+class PgGenTrunk(C.Structure):
+    """pg_gen_trunk (include/posegen_generator.h): nz -> width, then n_stages blocks of two width -> width layers"""
+    _fields_ = [("nz", C.c_int32), ("width", C.c_int32), ("n_stages", C.c_int32)]
+
+
+class PgGenSpec(C.Structure):
+    _fields_ = [("n_trunks", C.c_int32), ("trunk", PgGenTrunk * PG_GEN_MAX_TRUNKS), ("slope", C.c_float), ("eps", C.c_float),
+                ("momentum", C.c_float)]
+
+
+_GEN_TABLE = (_FP * PG_GEN_MAX_LAYERS) * PG_GEN_MAX_TRUNKS
+
+
+class PgGenParams(C.Structure):
+    """pg_gen_params: per trunk and layer the device pointers of the Linear's and the BatchNorm1d's tensors, where torch keeps them"""
+    _fields_ = [(k, _GEN_TABLE) for k in ("w", "b", "gamma", "beta", "running_mean", "running_var")]
+
+
+class PgGenGrads(C.Structure):
+    _fields_ = [(k, _GEN_TABLE) for k in ("w", "b", "gamma", "beta")]
+
+
+_GEN_PTRS = _FP * PG_GEN_MAX_TRUNKS          # a host array of per-trunk device pointers (noise, d_out)
 
 # every symbol include/posegen_hip.h declares: (restype, argtypes)
 PROTOTYPES = {
@@ -261,6 +288,21 @@ GAN_PROTOTYPES = {
                                    _FP]),
 }
 
+# every symbol include/posegen_generator.h declares (the third public header), bound and called like the others
+GENERATOR_PROTOTYPES = {
+    "pg_gen_tape_size": (C.c_int, [C.POINTER(PgGenSpec), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "pg_gen_trunk_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(PgGenSpec), C.POINTER(PgGenParams), C.POINTER(_FP), C.c_int64,
+                                       C.c_int32, _FP, C.c_void_p]),
+    "pg_gen_trunk_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(PgGenSpec), C.POINTER(PgGenParams), C.POINTER(_FP), C.c_int64,
+                                        C.c_int32, _FP, C.c_void_p, C.POINTER(_FP), C.POINTER(PgGenGrads)]),
+    "pg_gen_ba_head_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(PgGenSpec), C.c_int32, _FP, C.c_int64, C.c_int32, _FP, _FP, _FP,
+                                         _FP]),
+    "pg_gen_ba_head_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(PgGenSpec), C.c_int32, _FP, C.c_int64, C.c_int32, _FP, _FP, _FP,
+                                          _FP, _FP, _FP]),
+    "pg_gen_rt_head": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(PgGenSpec), C.c_int32, C.c_int32, _FP, C.c_int64, C.c_int32, _FP, _FP,
+                                 _FP, _FP, _FP, _FP, _FP]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -278,7 +320,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         lib = C.CDLL(p)
     except OSError as e:  # pragma: no cover - depends on the box
         raise HipLibraryError(f"cannot load {p}: {e}") from e
-    for name, (res, args) in list(PROTOTYPES.items()) + list(GAN_PROTOTYPES.items()):
+    for name, (res, args) in list(PROTOTYPES.items()) + list(GAN_PROTOTYPES.items()) + list(GENERATOR_PROTOTYPES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -14,8 +14,8 @@ launches forward and several times that backward.  Here:
                         both with get_discriminator_accuracy's two numbers as device tensors (pg_disc_loss); nothing synchronises
   FakePool              Sample_from_Pool on the device: host draws in the reference's order, one pg_pool_exchange launch
 
-Differentiable once.  There is no torch fallback and no CPU path: inputs on a CPU device raise NotImplementedError.  Not built: the
-generators (their BatchNorm statistics and in-module RNG are another problem), Adam, clipping, 16-bit operands.
+Differentiable once.  There is no torch fallback and no CPU path: inputs on a CPU device raise NotImplementedError.  The generators
+are `generators.py`.  Not built: Adam, clipping, 16-bit operands.
 """
 from __future__ import annotations
 

@@ -7,7 +7,8 @@ In the reference every `run_render` call of the training loop (run_gan.py:2041-2
   * writes them as PNG files, reads them back, crops [100:412]^2, normalises, and resizes to 224 x 224
     with skimage (anti_aliasing=True) for the SPIN / HMR regressor.
 The adversarial game that runs on every batch -- the pose discriminators, their losses and the pool of generated poses -- is
-`discriminators.py`; `generator_adversarial_loss` and `discriminator_step` below are the loop's two call sites of it.
+`discriminators.py`; `generator_adversarial_loss` and `discriminator_step` below are the loop's two call sites of it.  The pose
+generator itself is `generators.py`; `generator_step` is the generator half of a batch.
 
 `render_for_regressor` is that call with the HIP renderer: poses stay on the GPU (pg_pose_kinematics ->
 pg_pose_boxes -> pg_render_frame with a uint8 frame), no files, and one 16-byte-per-frame device->host copy
@@ -181,3 +182,21 @@ def discriminator_step(disc, optimizer, real: torch.Tensor, fake: torch.Tensor, 
     torch.nn.utils.clip_grad_norm_(disc.parameters(), max_norm=max_norm)
     optimizer.step()
     return real_acc, fake_acc, loss.detach()
+
+
+def generator_step(gen, disc, optimizer, real: torch.Tensor, feedback=None, max_norm: float = 1.0):
+    """The generator half of `train_gan` (run_gan.py:2001-2107): zero_grad, `gen(real)` (a `generators.HipPoseGenerator`, which draws
+    its noise with torch.randn in the reference's order), `generator_adversarial_loss` of `pose_ba` against `disc` (whose parameters the
+    caller has frozen, `set_grad([model_d3d], False)`), plus 0.1 times `feedback(pose_ba)` when a feedback term is given (a callable
+    that returns a scalar differentiable in `pose_ba`, e.g. `generator_feedback` on the rendered subset; None = the reference's
+    `spin_loss = 0`), backward, clip_grad_norm_(max_norm), optimizer.step().  Returns (the detached `pose_ba` for `discriminator_step`,
+    the loss as a device scalar); nothing synchronises."""
+    optimizer.zero_grad()
+    out = gen(real)
+    loss, _, _ = generator_adversarial_loss(disc, real, out["pose_ba"])
+    if feedback is not None:
+        loss = loss + 0.1 * feedback(out["pose_ba"])
+    loss.backward()
+    torch.nn.utils.clip_grad_norm_(gen.parameters(), max_norm=max_norm)
+    optimizer.step()
+    return out["pose_ba"].detach(), loss.detach()
