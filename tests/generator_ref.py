@@ -22,6 +22,29 @@ def shipped_spec():
     return gen.GenSpec([(32, 256, 2), (72, 256, 2), (72, 256, 2)])
 
 
+def deep_spec():
+    """four trunks of nine layers: 36 groups, the grouped weight-gradient launch's whole table; width 1, nz 1, K at and one past a
+    64-wide step of the product"""
+    return gen.GenSpec([(3, 1, 4), (1, 17, 4), (64, 16, 4), (65, 48, 4)])
+
+
+def wide_spec():
+    """nz and width at PG_GEN_MAX_DIM: the largest weight slab in LDS, 32 column tiles, 8 x 8 weight-gradient tiles"""
+    return gen.GenSpec([(512, 512, 1)])
+
+
+def flat_spec():
+    """no stages: the stem alone; an R trunk exactly 7 wide, a T trunk narrower than a wave, one ragged trunk for a head"""
+    return gen.GenSpec([(4, 7, 0), (2, 3, 0), (5, 40, 0)])
+
+
+def respec(spec, **kw):
+    """the same trunks with another slope, eps or momentum"""
+    args = {"slope": spec.slope, "eps": spec.eps, "momentum": spec.momentum}
+    args.update(kw)
+    return gen.GenSpec(spec.trunks, **args)
+
+
 def make_trunk(nz, width, n_stages, rng, dtype=np.float32):
     """the layers of one trunk: w, b, gamma, beta and running statistics that are not the initial ones"""
     layers = []
@@ -227,3 +250,261 @@ def pose_generator_backward(sd, out, tapes, trunks, d_pose, slope=0.01, eps=1e-5
 def grad_sample_index(numel, k=8):
     """the k flat entries of a parameter gradient the fixture keeps"""
     return np.unique(np.linspace(0, numel - 1, k).astype(np.int64))
+
+
+# ---- parameter edits: the degenerate columns of training ---------------------------------------------------------------------------------
+def _copied(params):
+    return [[{k: (np.array(v, copy=True) if isinstance(v, np.ndarray) else v) for k, v in layer.items()} for layer in layers] for layers in params]
+
+
+def zero_weight_row(params, t, l, col):
+    """a copy of `params` with row `col` of layer l of trunk t's weight zeroed: that column's Z is the bias on every row, its variance 0"""
+    out = _copied(params)
+    out[t][l]["w"][col, :] = 0.0
+    return out
+
+
+def dead_gamma(params, t, l, cols, betas):
+    """a copy with gamma = 0 and beta = `betas` on the columns `cols` of layer l of trunk t: the pre-activation is exactly beta"""
+    out = _copied(params)
+    out[t][l]["gamma"][list(cols)] = 0.0
+    out[t][l]["beta"][list(cols)] = np.asarray(betas, out[t][l]["beta"].dtype)
+    return out
+
+
+def last_layer_output(params, t, pre):
+    """a copy whose trunk t puts out exactly lrelu(pre) on its first len(pre) columns: gamma = 0, beta = pre on the last layer"""
+    return dead_gamma(params, t, len(params[t]) - 1, range(len(pre)), pre)
+
+
+# On the top layer of each trunk: below a BatchNorm the column sums of dZ are 0, so the d_beta of a column whose mask is the same on
+# every row is 0 whatever the mask says; only the top layer's d_beta = s sum(cot) shows which way an exactly-zero pre-activation went.
+GAMMA0_BETAS = (0.0, -0.0, 0.3, -0.3)
+
+
+def gamma0_columns(width):
+    """the four columns the gamma = 0 cases use: the first tile's ends and the last two of the trunk (a ragged tile's where there is one)"""
+    return (0, min(3, width - 3), width - 2, width - 1)
+
+
+# ---- the backward with a carried bound -----------------------------------------------------------------------------------------------------
+D53 = 2.0 ** -53
+
+
+def rebuilt_tape(noise, records, slope):
+    """A tape for the backward from per-layer records {z, mean, var, scale, shift} (the device's own, read back, or
+    emulate32_forward's): h_in of layer l is lrelu(z scale + shift) of layer l - 1 in float64 -- the product of two float32 values
+    is exact in double, so this is the device's fmaf up to its one rounding -- and y the layer's own pre-activation."""
+    tape, h = [], np.asarray(noise, F64)
+    for r in records:
+        z, sc, sh = (np.asarray(r[k], F64) for k in ("z", "scale", "shift"))
+        y = z * sc + sh
+        tape.append({"h_in": h, "z": z, "mean": np.asarray(r["mean"], F64), "var": np.asarray(r["var"], F64), "scale": sc, "shift": sh, "y": y})
+        h = leaky(y, slope)
+    return tape
+
+
+def trunk_backward_with_bound(layers, tape, masks, d_out, slope, eps):
+    """The float64 backward of one trunk from a GIVEN tape (rebuilt_tape of the device's Z, mean, var, scale, shift: the forward's
+    error does not enter) and GIVEN masks (the device's fmaf(Z, scale, shift) > 0), at the cotangent d_out [B,width], with an
+    elementwise bound on what pg_gen.hip's float32 backward of the same chain may differ by, carried down the chain.
+    slope, eps: as the kernels hold them (float32 values).  u = 2^-24; E_X bounds the device's X; a float32 reduction of length n
+    is bounded by (n + 2) u sum |a| |b| (tests/test_gpu_generator.py's _layer_bound); sums run over the B rows of a column.
+        top layer      dY = fl32(cot s), s = 1 or the slope per the mask                E_Y = u |dY|
+        below it       dH_l = dZ_{l+1} W_{l+1}  (N = width products, float32)           E_H = E_Z |W| + (N + 2) u (|dZ| + E_Z) |W|
+                       dY = fl32(dH s)                                                   E_Y = E_H |s| + u |dY|
+        d_beta         = sum dY in double, rounded once                                  E_beta  = sum E_Y + u (|d_beta| + sum E_Y) + B 2^-53 sum |dY|
+        d_gamma        = sum dY x^ in double, x^ = (Z - mean) / sqrt(var + eps)          E_gamma = sum E_Y |x^| + u (|d_gamma| + sum E_Y |x^|)
+                         from the tape's doubles, rounded once                                     + B 2^-53 sum |dY| |x^|
+        dZ             = fl32(k (B dY - d_beta - x^ d_gamma)), k = gamma / sqrt(var + eps) / B, in double from the unrounded sums
+                                                                                         E_Z = |k| (B E_Y + sum E_Y + |x^| sum E_Y |x^|) + u |dZ|
+                                                                                               + (B + 8) 2^-53 |k| (B |dY| + sum |dY| + |x^| sum |dY| |x^|)
+        dW_l           = dZ_l^T H_{l-1}, H recomputed on load (one fused multiply-add and one product: dH = 2 u |H|; the stem's
+                         H is the noise itself, dH = 0), B products in float32       E_W = E_Z^T |H| + (|dZ| + E_Z)^T dH + (B + 2) u (|dZ| + E_Z)^T |H|
+        db_l           = colsum(dZ) in double, rounded once.  The exact value is 0 whatever dY was (the unrounded terms of a column
+                         of dZ sum to -d_gamma k sum x^ = 0), so what the device has is the float32 rounding of each dZ:
+                                                                                         E_b = (2 u + 2^-40) sum |dZ| + 2^-149   (absolute)
+    A column whose variance is 0 has x^ = 0 exactly: its d_gamma is 0 with a bound of 0.  A column with gamma = 0 has k = 0: dZ,
+    its dW row and db are 0 with a bound of 0 (db: 2^-149).
+    -> grads: per layer (dw, db, dgamma, dbeta); bounds: the same shapes"""
+    dh = np.asarray(d_out, F64)
+    B = dh.shape[0]
+    e_h = np.zeros_like(dh)
+    grads, bounds = [None] * len(layers), [None] * len(layers)
+    for l in range(len(layers) - 1, -1, -1):
+        t = tape[l]
+        s = np.where(masks[l], 1.0, slope)
+        dy = dh * s
+        e_y = e_h * np.abs(s) + U32 * np.abs(dy)
+        invstd = 1.0 / np.sqrt(t["var"] + eps)
+        xh = (t["z"] - t["mean"]) * invstd
+        axh, ady = np.abs(xh), np.abs(dy)
+        dbeta, dgamma = dy.sum(0), (dy * xh).sum(0)
+        se, sex, sa, sax = e_y.sum(0), (e_y * axh).sum(0), ady.sum(0), (ady * axh).sum(0)
+        e_beta = se + U32 * (np.abs(dbeta) + se) + B * D53 * sa
+        e_gamma = sex + U32 * (np.abs(dgamma) + sex) + B * D53 * sax
+        k = np.asarray(layers[l]["gamma"], F64) * invstd / B
+        dz = k * (B * dy - dbeta - xh * dgamma)
+        e_z = np.abs(k) * (B * e_y + se + axh * sex) + U32 * np.abs(dz) + (B + 8) * D53 * np.abs(k) * (B * ady + sa + axh * sax)
+        h = np.asarray(t["h_in"], F64)
+        ah, mag = np.abs(h), np.abs(dz) + e_z
+        d_h = 2 * U32 * ah if l else np.zeros_like(ah)
+        w = np.asarray(layers[l]["w"], F64)
+        grads[l] = (dz.T @ h, dz.sum(0), dgamma, dbeta)
+        bounds[l] = (e_z.T @ ah + mag.T @ d_h + (B + 2) * U32 * (mag.T @ ah), (2 * U32 + 2.0 ** -40) * np.abs(dz).sum(0) + 2.0 ** -149, e_gamma, e_beta)
+        dh = dz @ w
+        e_h = e_z @ np.abs(w) + (w.shape[0] + 2) * U32 * (mag @ np.abs(w))
+    return grads, bounds
+
+
+def ba_head_backward_with_bound(h, w2, y, d_pose):
+    """The float64 backward of the bone-angle head from the device's own y [B,4J] and the trunk's output h rebuilt from the device's
+    tape, with the bound on pg_gen.hip's float32 results:
+        dy     formed in double from y and d_pose, rounded once          E_dy = u |dy| + 16 2^-53 |f| (|g| + |a^| sum |a^| |g|)   (f = s theta / |a|; the
+                                                                                angle's entry: 16 2^-53 s sum |a^| |g|)
+        d_b2   = colsum(dy) in double, rounded once                       E = sum E_dy + u (|d_b2| + sum E_dy) + B 2^-53 sum |dy|
+        d_w2   = dy^T H, H recomputed on load (dH = 2 u |H|)              E = E_dy^T |H| + (|dy| + E_dy)^T dH + (B + 2) u (|dy| + E_dy)^T |H|
+        d_h    = dy w2, a float32 reduction of length 4J                  E = E_dy |w2| + (4J + 2) u (|dy| + E_dy) |w2|
+    A joint with |a| = 0 has a NaN dy: its entries of d_w2 and d_b2 and every d_h of the row are NaN in value and in bound.
+    -> (d_w2, d_b2, d_h), (their bounds)"""
+    h, w2, y = np.asarray(h, F64), np.asarray(w2, F64), np.asarray(y, F64)
+    B = h.shape[0]
+    y4, g = y.reshape(B, -1, 4), np.asarray(d_pose, F64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        dy = ba_head_dy(y, d_pose)
+        s = np.ones((1, y4.shape[1], 1))
+        s[0, 0, 0] = JOINT0_SCALE
+        nrm = np.linalg.norm(y4[:, :, :3], axis=-1, keepdims=True)
+        ua = np.abs(y4[:, :, :3] / nrm)
+        uag = (ua * np.abs(g)).sum(-1, keepdims=True)
+        dbl = np.concatenate([np.abs(s * y4[:, :, 3:4] / nrm) * (np.abs(g) + ua * uag), s * uag], -1).reshape(B, -1)
+        e_dy = U32 * np.abs(dy) + 16 * D53 * dbl
+        ah, mag = np.abs(h), np.abs(dy) + e_dy
+        d_b2 = dy.sum(0)
+        se = e_dy.sum(0)
+        grads = (dy.T @ h, d_b2, dy @ w2)
+        bounds = (e_dy.T @ ah + mag.T @ (2 * U32 * ah) + (B + 2) * U32 * (mag.T @ ah), se + U32 * (np.abs(d_b2) + se) + B * D53 * np.abs(dy).sum(0),
+                  e_dy @ np.abs(w2) + (w2.shape[0] + 2) * U32 * (mag @ np.abs(w2)))
+    return grads, bounds
+
+
+# ---- the same chain in float32 on the CPU: what honest float32 does inside the bound, and what planted errors do outside it ---------------
+F32 = np.float32
+MUTANTS = ("unbiased x^", "scale32 k", "no x^ d_gamma", "short last column")
+
+
+def _act32(z, scale, shift, slope):
+    """lrelu(fmaf(z, scale, shift)) as the kernels form it: the fused value rounded once (the product is exact in double), then
+    one float32 product by the slope"""
+    y = (np.asarray(z, F64) * np.asarray(scale, F64) + np.asarray(shift, F64)).astype(F32)
+    return np.where(y > 0, y, y * F32(slope))
+
+
+def emulate32_forward(layers, noise, slope, eps):
+    """the training-mode forward of a trunk the way the device runs it, in numpy: Z in float32 (plain `@`), mean and the biased
+    variance of that Z in double, scale and shift formed in double and rounded once -> per layer {z, mean, var, scale, shift}"""
+    h, out = np.asarray(noise, F32), []
+    for layer in layers:
+        z = h @ np.asarray(layer["w"], F32).T + np.asarray(layer["b"], F32)
+        z64 = z.astype(F64)
+        mean = z64.mean(0)
+        var = ((z64 - mean) ** 2).mean(0)
+        sc = np.asarray(layer["gamma"], F64) / np.sqrt(var + eps)
+        out.append({"z": z, "mean": mean, "var": var, "scale": sc.astype(F32), "shift": (np.asarray(layer["beta"], F64) - mean * sc).astype(F32)})
+        h = _act32(z, out[-1]["scale"], out[-1]["shift"], slope)
+    return out
+
+
+def emulate32_backward(layers, tape, masks, d_out, slope, eps, mutant=None):
+    """trunk_backward_with_bound's chain as pg_gen.hip runs it, in numpy float32 with the double sums kept in float64; plain `@` for
+    the products, not the device's order.  It exists so that the bound can be judged without a device: honest float32 must stay
+    inside it, and each planted error (`mutant`, one of MUTANTS) must leave it:
+        "unbiased x^"         x^ from the unbiased variance
+        "scale32 k"           k from the tape's rounded float32 scale in place of gamma / sqrt(var + eps)
+        "no x^ d_gamma"       dZ without its third term
+        "short last column"   the last live column of a ragged 16-column tile summed over B - 1 rows
+    -> per layer (dw, db, dgamma, dbeta) as float32"""
+    assert mutant is None or mutant in MUTANTS
+    dh = np.asarray(d_out, F32)
+    B = dh.shape[0]
+    grads = [None] * len(layers)
+    for l in range(len(layers) - 1, -1, -1):
+        t = tape[l]
+        dy = dh * np.where(masks[l], F32(1.0), F32(slope))
+        invstd = 1.0 / np.sqrt(t["var"] + eps)
+        xh = (t["z"] - t["mean"]) * (1.0 / np.sqrt(t["var"] * (B / (B - 1.0)) + eps) if mutant == "unbiased x^" else invstd)
+        dy64 = dy.astype(F64)
+        dbeta, dgamma = dy64.sum(0), (dy64 * xh).sum(0)
+        if mutant == "short last column" and dy.shape[1] % 16:
+            dbeta[-1] = dy64[:-1, -1].sum()
+        k = (np.asarray(t["scale"], F64) if mutant == "scale32 k" else np.asarray(layers[l]["gamma"], F64) * invstd) / B
+        dz = (k * (B * dy64 - dbeta - (0.0 if mutant == "no x^ d_gamma" else xh * dgamma))).astype(F32)
+        h = np.asarray(t["h_in"], F32) if l == 0 else _act32(tape[l - 1]["z"], tape[l - 1]["scale"], tape[l - 1]["shift"], slope)
+        grads[l] = (dz.T @ h, dz.astype(F64).sum(0).astype(F32), dgamma.astype(F32), dbeta.astype(F32))
+        dh = dz @ np.asarray(layers[l]["w"], F32)
+    return grads
+
+
+def emulate32_head_backward(tape_last, w2, y, d_pose, slope):
+    """ba_head_backward_with_bound's chain in float32: dy in double rounded once, H recomputed from the last layer's tape -> (d_w2, d_b2, d_h)"""
+    with np.errstate(invalid="ignore", divide="ignore"):
+        dy = ba_head_dy(np.asarray(y, F64), d_pose).astype(F32)
+        h = _act32(tape_last["z"], tape_last["scale"], tape_last["shift"], slope)
+        return dy.T @ h, dy.astype(F64).sum(0).astype(F32), dy @ np.asarray(w2, F32)
+
+
+# ---- the cases of tests/test_gpu_generator_edges.py, judged on the CPU by tests/test_generator_ref.py ---------------------------------------
+EDGE_SPECS = {"toy": toy_spec, "deep": deep_spec, "flat": flat_spec, "wide": wide_spec}
+EDGE_BATCHES = {"toy": (2, 17, 65, 257), "deep": (2, 17, 65, 257), "flat": (2, 17, 65, 257), "wide": (2, 18)}
+EDGE_SEEDS = {"toy": 200, "deep": 300, "flat": 400, "wide": 500}
+ROW_LIMIT_SPEC = [(2, 3, 0)]
+DEGENERATE = ("zero row stem", "zero row middle", "gamma 0", "twin rows") + tuple(f"slope {s} eps {e}" for s in (0.0, 1.0, 0.2) for e in (1e-12, 1.0))
+HEAD_CASES = (("toy", 65, 1), ("toy", 65, 5), ("toy", 65, 64), ("wide", 18, 64), ("wide", 18, 1))     # (spec, B, J), the head on trunk 0
+
+
+def zero_row_column(width, l):
+    """the column whose weight row the zero-row cases clear: column 1 in the stem, the last column (a ragged tile's) in layer 1"""
+    return 1 if l == 0 else width - 1
+
+
+def edge_case(name, B=None):
+    """-> (spec, params, noise, cots): one case of the edge tests by name -- a key of EDGE_SPECS at a batch of EDGE_BATCHES, "rows"
+    (the row limit; B may shorten it), or one of DEGENERATE (the toy spec at B = 65, edited)"""
+    if name in EDGE_SPECS:
+        spec, seed = EDGE_SPECS[name](), EDGE_SEEDS[name] + B
+        params = make_params(spec, EDGE_SEEDS[name])
+    elif name == "rows":
+        spec, B = gen.GenSpec(ROW_LIMIT_SPEC), (1 << 20) if B is None else B
+        params, seed = make_params(spec, 600), 601
+    else:
+        spec, B, seed = toy_spec(), 2 if name == "twin rows" else 65, 700 + DEGENERATE.index(name)
+        params = make_params(spec, 700)
+        if name.startswith("zero row"):
+            l = 0 if name.endswith("stem") else 1
+            for t, (_, width, _) in enumerate(spec.trunks):
+                params = zero_weight_row(params, t, l, zero_row_column(width, l))
+        elif name == "gamma 0":
+            for t, (_, width, _) in enumerate(spec.trunks):
+                params = dead_gamma(params, t, spec.layers(t) - 1, gamma0_columns(width), GAMMA0_BETAS)   # (the top layer: see GAMMA0_BETAS)
+        elif name.startswith("slope"):
+            spec = respec(spec, slope=float(name.split()[1]), eps=float(name.split()[3]))
+    noise = make_noise(spec, B, seed)
+    if name == "twin rows":
+        noise = [np.repeat(n[:1], 2, axis=0) for n in noise]
+    rng = np.random.RandomState(seed + 1)
+    return spec, params, noise, [rng.standard_normal((B, width)).astype(np.float32) for _, width, _ in spec.trunks]
+
+
+def held(spec):
+    """slope and eps as the kernels hold them: the float32 values, as doubles"""
+    return float(np.float32(spec.slope)), float(np.float32(spec.eps))
+
+
+def ragged_module_case(renderer=None):
+    """HipBAGenerator(noise 5, width 40, one stage) with a seeded state dict, its draws and the cotangent of its pose at B = 65
+    -> (module on the CPU, state dict, spec, the trunk's layers, noise [65,5], d_pose [65,24,3])"""
+    m = gen.HipBAGenerator(noise_channle=5, linear_size=40, num_stage=1, renderer=renderer)
+    sd = make_state_dict(m, 890)
+    rng = np.random.RandomState(891)
+    noise, d_pose = rng.standard_normal((65, 5)).astype(np.float32), rng.standard_normal((65, 24, 3)).astype(np.float32)
+    return m, sd, gen.GenSpec([(5, 40, 1)]), trunk_of_state(sd, "", "w1", "batch_norm1", "linear_stages", n_stages=1), noise, d_pose

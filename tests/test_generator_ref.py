@@ -294,3 +294,184 @@ def test_every_documented_refusal_of_the_compute_entry_points():
     narrow = gen.GenSpec([(5, 6, 1), (5, 40, 1)]).c_spec()
     _refused(rt(None, None, C.byref(narrow), 0, 1, P, 8, 24, P, P, P, P, P, P, P), lib, "narrower than 7")
     _refused(rt(None, None, C.byref(cs), 1, 2, P, 8, 24, P, P, P, P, P, P, P), lib, "null handle")
+
+
+# ---- the backward's carried bound, judged without a device ---------------------------------------------------------------------------------
+EDGE_CASES = [(name, B) for name, batches in ref.EDGE_BATCHES.items() for B in batches] + [("rows", None)] + [(name, None) for name in ref.DEGENERATE]
+NAMES = ("dw", "db", "dgamma", "dbeta")
+U = 2.0 ** -24
+WORST32 = {}
+
+
+def _ratio(err, bound):
+    with np.errstate(invalid="ignore", divide="ignore"):
+        r = np.where(bound > 0, err / np.where(bound > 0, bound, 1.0), np.where(err > 0, np.inf, 0.0))
+    return float(np.max(r)) if r.size else 0.0
+
+
+def _emulated(name, B):
+    """one case as the device would run it, in float32 on the CPU -> spec, params, per trunk (tape, masks), cots"""
+    spec, params, noise, cots = ref.edge_case(name, B)
+    slope, eps = ref.held(spec)
+    runs = []
+    for layers, n in zip(params, noise):
+        tape = ref.rebuilt_tape(n, ref.emulate32_forward(layers, n, slope, eps), slope)
+        runs.append((tape, [t["y"] > 0 for t in tape]))
+    return spec, params, runs, cots
+
+
+@pytest.mark.parametrize("name,B", EDGE_CASES)
+def test_the_bounded_backward_equals_the_hand_written_one_and_float64_autograd(name, B):
+    """on a float64 tape of its own the three agree to float64's rounding, on every spec and parameter edit of the edge tests (the row
+    limit at 4096 rows: autograd's time).  Two identical noise rows are compared with the hand-written backward alone: there every
+    variance is 0 and x^ = (z - mean) / sqrt(eps) turns the last bit of a forward's own z into 1e-14, which the k = gamma / sqrt(eps) / 2
+    of each layer below multiplies by 10^2 again, so autograd's gradients are its own forward's rounding noise (1e-7 of d_gamma on one
+    machine, 0 on another); the backward from a given tape has no such freedom, and that is what the device is compared with."""
+    spec, params, noise, cots = ref.edge_case(name, 4096 if name == "rows" else B)
+    for t, layers in enumerate(params):
+        _, tape = ref.trunk_forward(layers, noise[t], spec.slope, spec.eps, spec.momentum)
+        masks = ref.masks_of(tape)
+        mine, bound = ref.trunk_backward_with_bound(layers, tape, masks, cots[t], spec.slope, spec.eps)
+        old = ref.trunk_backward(layers, tape, cots[t], spec.slope, spec.eps)
+        _, auto = _autograd_trunk(layers, noise[t], cots[t].astype(np.float64), spec.slope, spec.eps)
+        for l in range(len(layers)):
+            for k, m, o, a, e in zip(NAMES, mine[l], old[l], auto[l], bound[l]):
+                # float64's rounding is relative to the sum of the magnitudes that an entry adds up, not to the entry (two identical
+                # rows: every dW is 0 exactly, the sum of two opposite products); the bound carries that sum at u = 2^-24, so 2^-20
+                # of the bound is 2^-44 of it
+                tol = 1e-12 * max(1.0, float(np.max(np.abs(o)))) + 2.0 ** -20 * e
+                assert np.all(np.abs(m - o) <= tol) and (name == "twin rows" or np.all(np.abs(m - a) <= 100 * tol)), (t, l, k)
+
+
+@pytest.mark.parametrize("name,B", EDGE_CASES)
+def test_honest_float32_stays_inside_the_backwards_bound(name, B):
+    spec, params, runs, cots = _emulated(name, B)
+    slope, eps = ref.held(spec)
+    worst = {}
+    for t, (layers, (tape, masks)) in enumerate(zip(params, runs)):
+        g64, bound = ref.trunk_backward_with_bound(layers, tape, masks, cots[t], slope, eps)
+        g32 = ref.emulate32_backward(layers, tape, masks, cots[t], slope, eps)
+        for l in range(len(layers)):
+            for k, a, b, e in zip(NAMES, g32[l], g64[l], bound[l]):
+                err = np.abs(a.astype(np.float64) - b)
+                worst[k] = max(worst.get(k, 0.0), _ratio(err, e))
+                assert np.all(np.isfinite(b)) and np.all(err <= e), (name, B, t, l, k, _ratio(err, e))
+    for k, v in worst.items():
+        WORST32[k] = max(WORST32.get(k, 0.0), v)
+    print(f"EMULATE32 {name} B={B}: " + ", ".join(f"{k} {v:.3f}" for k, v in worst.items()) + " | worst so far " + ", ".join(f"{k} {v:.3f}" for k, v in WORST32.items()))
+
+
+@pytest.mark.parametrize("name,B,J", ref.HEAD_CASES + (("rows", None, 1),))
+def test_honest_float32_stays_inside_the_heads_bound(name, B, J):
+    spec, params, runs, _ = _emulated(name, B)
+    slope, _ = ref.held(spec)
+    tape, rng = runs[0][0], np.random.RandomState(800 + J)
+    Bn, W = tape[-1]["z"].shape
+    w2, b2 = ref.make_head(4 * J, W, rng)
+    d_pose = rng.standard_normal((Bn, J, 3)).astype(np.float32)
+    h = ref.leaky(tape[-1]["y"], slope)
+    y = (ref._act32(tape[-1]["z"], tape[-1]["scale"], tape[-1]["shift"], slope) @ w2.T + b2).astype(np.float32)
+    g64, bound = ref.ba_head_backward_with_bound(h, w2, y, d_pose)
+    g32 = ref.emulate32_head_backward(tape[-1], w2, y, d_pose, slope)
+    old = ref.ba_head_backward(h, w2, y, d_pose)
+    for k, a, b, e, o in zip(("d_w2", "d_b2", "d_h"), g32, g64, bound, old):
+        err = np.abs(a.astype(np.float64) - b)
+        print(f"EMULATE32 head {name} J={J} {k}: {_ratio(err, e):.3f}")
+        assert np.array_equal(b, o) and np.all(err <= e), (k, _ratio(err, e))
+
+
+def test_honest_float32_stays_inside_the_bound_on_the_ragged_modules_parameters():
+    """the head of 24 joints and the three layers of HipBAGenerator(noise 5, width 40, one stage), as the device test chains them"""
+    _, sd, spec, layers, noise, d_pose = ref.ragged_module_case()
+    slope, eps = ref.held(spec)
+    tape = ref.rebuilt_tape(noise, ref.emulate32_forward(layers, noise, slope, eps), slope)
+    masks = [t["y"] > 0 for t in tape]
+    w2, b2 = sd["w2.weight"], sd["w2.bias"]
+    y = (ref._act32(tape[-1]["z"], tape[-1]["scale"], tape[-1]["shift"], slope) @ w2.T + b2).astype(np.float32)
+    g64, bound = ref.ba_head_backward_with_bound(ref.leaky(tape[-1]["y"], slope), w2, y, d_pose)
+    g32 = ref.emulate32_head_backward(tape[-1], w2, y, d_pose, slope)
+    worst = max(_ratio(np.abs(a.astype(np.float64) - b), e) for a, b, e in zip(g32, g64, bound))
+    assert all(np.all(np.abs(a.astype(np.float64) - b) <= e) for a, b, e in zip(g32, g64, bound))
+    t64, tbound = ref.trunk_backward_with_bound(layers, tape, masks, g32[2], slope, eps)
+    t32 = ref.emulate32_backward(layers, tape, masks, g32[2], slope, eps)
+    for l in range(3):
+        for k, a, b, e in zip(NAMES, t32[l], t64[l], tbound[l]):
+            err = np.abs(a.astype(np.float64) - b)
+            worst = max(worst, _ratio(err, e))
+            assert np.all(err <= e), (l, k)
+    print(f"EMULATE32 ragged module: {worst:.3f}")
+
+
+def _broken(name, B, mutant=None, masks_edit=None):
+    """per tensor name, the (trunk, layer) pairs where a planted error leaves the bound"""
+    spec, params, runs, cots = _emulated(name, B)
+    slope, eps = ref.held(spec)
+    out = {k: set() for k in NAMES}
+    for t, (layers, (tape, masks)) in enumerate(zip(params, runs)):
+        g64, bound = ref.trunk_backward_with_bound(layers, tape, masks, cots[t], slope, eps)
+        wrong = masks if masks_edit is None else masks_edit(tape, masks)
+        g32 = ref.emulate32_backward(layers, tape, wrong, cots[t], slope, eps, mutant)
+        for l in range(len(layers)):
+            for k, a, b, e in zip(NAMES, g32[l], g64[l], bound[l]):
+                if not np.all(np.abs(a.astype(np.float64) - b) <= e):
+                    out[k].add((t, l))
+    return spec, out
+
+
+MUTANT_CASES = [(name, B) for name, batches in ref.EDGE_BATCHES.items() for B in batches] + [(name, None) for name in ref.DEGENERATE if name != "twin rows"]
+
+
+@pytest.mark.parametrize("name,B", MUTANT_CASES)
+def test_the_bound_sees_x_hat_from_the_unbiased_variance(name, B):
+    """d_gamma and dW of every trunk's top layer leave the bound (slope 0 aside, where a dW can be all zero past the top layer only)"""
+    spec, out = _broken(name, B, "unbiased x^")
+    for t in range(len(spec.trunks)):
+        top = spec.layers(t) - 1
+        assert (t, top) in out["dgamma"] and (t, top) in out["dw"], (t, out)
+
+
+@pytest.mark.parametrize("name,B", MUTANT_CASES)
+def test_the_bound_sees_a_dropped_x_hat_d_gamma_term(name, B):
+    spec, out = _broken(name, B, "no x^ d_gamma")
+    for t in range(len(spec.trunks)):
+        assert (t, spec.layers(t) - 1) in out["dw"], (t, out)
+
+
+@pytest.mark.parametrize("name,B", [(n, B) for n, B in MUTANT_CASES if n in ("toy", "deep")])
+def test_the_bound_sees_a_ragged_tiles_last_column_summed_one_row_short(name, B):
+    """d_beta at width 17 (trunk 1 of the toy and of the deep spec), top layer"""
+    spec, out = _broken(name, B, "short last column")
+    assert spec.trunks[1][1] == 17 and (1, spec.layers(1) - 1) in out["dbeta"], out
+
+
+def test_the_bound_sees_an_exactly_zero_pre_activation_taken_as_positive():
+    """d_beta of the gamma = 0, beta = +-0 columns (the top layer of every trunk; the slope is 0.01)"""
+    def edit(tape, masks):
+        return [m | (t["y"] == 0) for t, m in zip(tape, masks)]
+    spec, params, runs, cots = _emulated("gamma 0", None)
+    slope, eps = ref.held(spec)
+    for t, (layers, (tape, masks)) in enumerate(zip(params, runs)):
+        cols = list(ref.gamma0_columns(spec.trunks[t][1])[:2])
+        assert np.all(tape[-1]["y"][:, cols] == 0) and not masks[-1][:, cols].any()
+        g64, bound = ref.trunk_backward_with_bound(layers, tape, masks, cots[t], slope, eps)
+        g32 = ref.emulate32_backward(layers, tape, edit(tape, masks), cots[t], slope, eps)
+        err = np.abs(g32[-1][3].astype(np.float64) - g64[-1][3])
+        assert np.all(err[cols] > bound[-1][3][cols]), t
+        others = np.setdiff1d(np.arange(err.size), cols)
+        assert np.all(err[others] <= bound[-1][3][others]), t
+
+
+@pytest.mark.parametrize("name,B", MUTANT_CASES)
+def test_k_from_the_rounded_scale_is_one_rounding_and_cannot_be_seen(name, B):
+    """The mutant the bound does not see, and why: a float32 scale is gamma / sqrt(var + eps) to within u / (1 + u) of it -- rounding
+    to nearest has no column that `rounds badly` -- so k from it moves dZ by less than the u |dZ| that dZ's own rounding is
+    allowed, and every dW by less than u |dW|: inside (B + 2) u |dZ|^T |H| by construction.  Asserted on every fixture: no column's
+    scale is further off than that, and the mutant stays inside the bound everywhere.  The mutant is dropped."""
+    spec, params, runs, _ = _emulated(name, B)
+    _, eps = ref.held(spec)
+    for layers, (tape, _) in zip(params, runs):
+        for layer, t in zip(layers, tape):
+            exact = np.asarray(layer["gamma"], np.float64) / np.sqrt(t["var"] + eps)
+            assert np.all(np.abs(t["scale"] - exact) <= U / (1 + U) * np.abs(exact) * (1 + 2.0 ** -50))
+    _, out = _broken(name, B, "scale32 k")
+    assert not any(out.values()), out

@@ -194,13 +194,14 @@ def _check_layers(run, params, noise, tag, before=None):
             assert np.all(np.abs(d["scale"] - scale64) <= 2 * _ulp32(scale64)) and np.all(np.abs(d["shift"] - shift64) <= 2 * _ulp32(shift64)), (tag, B, t, l)
 
 
-def _check_head(run, t, J, seed, tag):
+def _check_head(run, t, J, seed, tag, head=None, nan_joints=()):
     """the head's y against the float64 layer on the device's own last layer; pose against float64 from the device's own y: the
     epilogue is nine float32 operations in a row on a value (three squares and two sums, a root, a quotient, one or two products),
-    each within u: 8 u |pose| covers them (the root halves the error of the sum of squares)"""
+    each within u: 8 u |pose| covers them (the root halves the error of the sum of squares).  `head`: (w2, b2) in place of the
+    seed's; `nan_joints`: the joints whose axis the caller made exactly zero -- their pose must be NaN on every row."""
     spec = run.spec
     W = spec.trunks[t][1]
-    w2, b2 = ref.make_head(4 * J, W, np.random.RandomState(seed))
+    w2, b2 = ref.make_head(4 * J, W, np.random.RandomState(seed)) if head is None else head
     y, pose = run.head(t, J, w2, b2)
     h = run.h(t, spec.layers(t) - 1)
     y64 = h @ w2.astype(np.float64).T + b2.astype(np.float64)
@@ -209,6 +210,9 @@ def _check_head(run, t, J, seed, tag):
     assert np.all(err <= bound)
     pose64 = ref.ba_pose(y.astype(np.float64))
     err, bound = np.abs(pose - pose64), 8 * U * np.abs(pose64) + 2.0 ** -149
+    if len(nan_joints):
+        assert np.all(np.isnan(pose[:, list(nan_joints)])) and np.all(np.isnan(pose64[:, list(nan_joints)]))
+        err, bound = np.delete(err, list(nan_joints), axis=1), np.delete(bound, list(nan_joints), axis=1)
     _note(f"{tag} pose", err, bound)
     assert np.all(err <= bound)
     return w2, b2, y, pose
@@ -225,22 +229,32 @@ def test_layer_local_checks_on_the_ragged_toy_spec(renderer, B):
     _check_layers(ev, params, noise, "toy eval")
 
 
-def _rt_check(run, tr, tt, J, seed):
+def _rt_check(run, tr, tt, J, seed, eps_edit=None, nan_rows=()):
     """R, T and pose_rt against float64 from the device's own trunk outputs.  The device rounds r to float32 (dr = 2 u |r|), works in
     double from there and rounds R once: with the rotation 2-Lipschitz in its vector,  E_R = u + 2 (2 |r6| d_axis / |axis| + 2 u |r6|),
     d_axis = 2 u (|r_mean| + 2 r_std^2 |eps|) summed over the axis.  T is a float32 dot product over the width in wave order:
-    the layer bound, its third entry squared.  pose_rt adds three products and three sums in float32."""
+    the layer bound, its third entry squared.  pose_rt adds three products and three sums in float32.
+    `eps_edit`: a function that edits the drawn eps in place; `nan_rows`: the rows whose axis the caller made exactly zero -- their
+    R and pose_rt must be NaN and their T finite, and the bounds hold on the other rows.  -> (R, T, pose_rt) as read back"""
     spec, B = run.spec, run.B
     rng = np.random.RandomState(seed)
     WT = spec.trunks[tt][1]
     w2, b2 = ref.make_head(3, WT, rng)
     eps, x = rng.standard_normal((B, 3)).astype(np.float32), rng.standard_normal((B, J, 3)).astype(np.float32)
+    if eps_edit is not None:
+        eps_edit(eps)
     outs = [_guarded(n) for n in (B * 9, B * 3, B * J * 3)]
     _ffi.call(run.r, "pg_gen_rt_head", C.byref(run.cs), tr, tt, run.tape, B, J, _off(w2), _off(b2), _off(eps), _off(x), *[o[1] for o in outs])
     torch.cuda.synchronize()
     assert all(_intact(o[0], n) for o, n in zip(outs, (B * 9, B * 3, B * J * 3)))
     R, T, pose = outs[0][1].cpu().numpy().reshape(B, 3, 3), outs[1][1].cpu().numpy().reshape(B, 3), outs[2][1].cpu().numpy().reshape(B, J, 3)
+    read_back = (R, T, pose)
     r, ht = run.h(tr, spec.layers(tr) - 1), run.h(tt, spec.layers(tt) - 1)
+    if len(nan_rows):
+        bad = list(nan_rows)
+        assert np.all(np.isnan(R[bad])) and np.all(np.isnan(pose[bad])) and np.all(np.isfinite(T[bad]))
+        keep = np.setdiff1d(np.arange(B), bad)
+        R, T, pose, r, ht, eps, x = R[keep], T[keep], pose[keep], r[keep], ht[keep], eps[keep], x[keep]
     R64, T64, pose64 = ref.rt_head(r, ht, w2, b2, eps, x)
     d_axis = 2 * U * (np.abs(r[:, :3]) + 2 * r[:, 3:6] ** 2 * np.abs(eps)).sum(-1)
     axis = np.linalg.norm(r[:, :3] + r[:, 3:6] ** 2 * eps, axis=-1)
@@ -260,6 +274,7 @@ def _rt_check(run, tr, tt, J, seed):
     err = np.abs(pose - pose64)
     _note("rt pose_rt", err, e_p)
     assert np.all(err <= e_p)
+    return read_back
 
 
 def test_the_rotation_translation_head_on_the_toy_and_the_shipped_spec(renderer):
