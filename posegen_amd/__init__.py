@@ -27,6 +27,7 @@ _TRAINER_NAMES = ("HipTrainer",)
 _REGRESSOR_BATCH_NAMES = ("PixelStore", "RegressorBatchSource", "regressor_input", "fixed_crop_boxes", "mpii_crop_boxes", "REFERENCE_NORM")
 _SCENE_NAMES = ("ScenePerson", "render_scene", "render_scenes", "place_people")
 _GENERATOR_NAMES = ("HipBAGenerator", "HipRTGenerator", "HipPoseGenerator")
+_REGRESSOR_NAMES = ("HipHMRHead", "HipHMR")
 
 
 def __getattr__(name):
@@ -67,4 +68,7 @@ def __getattr__(name):
     if name in _GENERATOR_NAMES:              # the pose generator of the GAN loop (imports torch as well)
         from . import generators
         return getattr(generators, name)
+    if name in _REGRESSOR_NAMES:              # the regressor's head (imports torch as well)
+        from . import regressors
+        return getattr(regressors, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

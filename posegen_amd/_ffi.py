@@ -1,4 +1,5 @@
-"""ctypes binding of libposegen_hip.so (include/posegen_hip.h, include/posegen_gan.h, include/posegen_generator.h).
+"""ctypes binding of libposegen_hip.so (include/posegen_hip.h, include/posegen_gan.h, include/posegen_generator.h,
+include/posegen_regressor.h).
 
 north_star asks for a "thin C-ABI cffi layer"; cffi is not installed in the build
 image (and cannot be: no network), so the same C ABI is bound with ctypes from the
@@ -303,6 +304,33 @@ GENERATOR_PROTOTYPES = {
                                  _FP, _FP, _FP, _FP, _FP]),
 }
 
+PG_HMR_MAX_FEAT, PG_HMR_MAX_HIDDEN, PG_HMR_MAX_JOINTS, PG_HMR_MAX_SHAPE, PG_HMR_MAX_CAM, PG_HMR_MAX_ITER, PG_HMR_MAX_ROWS = 4096, 2048, 64, 64, 16, 8, 1048576
+HMR_TENSORS = ("fc1_w", "fc1_b", "fc2_w", "fc2_b", "decpose_w", "decpose_b", "decshape_w", "decshape_b", "deccam_w", "deccam_b")
+
+
+class PgHmrSpec(C.Structure):
+    """pg_hmr_spec (include/posegen_regressor.h): the widths of the regression head, its rounds and nn.Dropout's p"""
+    _fields_ = [(k, C.c_int32) for k in ("n_feat", "n_hidden", "n_joints", "n_shape", "n_cam", "n_iter")] + [("p_drop", C.c_float)]
+
+
+class PgHmrParams(C.Structure):
+    """pg_hmr_params: the device pointers of the five nn.Linears' tensors, where torch keeps them"""
+    _fields_ = [(k, _FP) for k in HMR_TENSORS]
+
+
+class PgHmrGrads(C.Structure):
+    _fields_ = [(k, _FP) for k in HMR_TENSORS]
+
+
+# every symbol include/posegen_regressor.h declares (the fourth public header, DESIGN.md 2.18), bound and called like the others
+REGRESSOR_PROTOTYPES = {
+    "pg_hmr_tape_size": (C.c_int, [C.POINTER(PgHmrSpec), C.c_int64, C.POINTER(C.c_int64)]),
+    "pg_hmr_head_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(PgHmrSpec), C.POINTER(PgHmrParams), _FP, _FP, C.c_int32, C.c_void_p,
+                                      C.c_int64, _FP, _FP, _FP, _FP]),
+    "pg_hmr_head_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(PgHmrSpec), C.POINTER(PgHmrParams), _FP, C.c_void_p, C.c_int64, _FP,
+                                       _FP, _FP, _FP, C.POINTER(PgHmrGrads), _FP, _FP]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -320,7 +348,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         lib = C.CDLL(p)
     except OSError as e:  # pragma: no cover - depends on the box
         raise HipLibraryError(f"cannot load {p}: {e}") from e
-    for name, (res, args) in list(PROTOTYPES.items()) + list(GAN_PROTOTYPES.items()) + list(GENERATOR_PROTOTYPES.items()):
+    for name, (res, args) in list(PROTOTYPES.items()) + list(GAN_PROTOTYPES.items()) + list(GENERATOR_PROTOTYPES.items()) + list(REGRESSOR_PROTOTYPES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

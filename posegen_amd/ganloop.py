@@ -8,7 +8,8 @@ In the reference every `run_render` call of the training loop (run_gan.py:2041-2
     with skimage (anti_aliasing=True) for the SPIN / HMR regressor.
 The adversarial game that runs on every batch -- the pose discriminators, their losses and the pool of generated poses -- is
 `discriminators.py`; `generator_adversarial_loss` and `discriminator_step` below are the loop's two call sites of it.  The pose
-generator itself is `generators.py`; `generator_step` is the generator half of a batch.
+generator itself is `generators.py`; `generator_step` is the generator half of a batch.  The regressor's head is `regressors.py`;
+`regressor_step` is one batch of `train_spin`.
 
 `render_for_regressor` is that call with the HIP renderer: poses stay on the GPU (pg_pose_kinematics ->
 pg_pose_boxes -> pg_render_frame with a uint8 frame), no files, and one 16-byte-per-frame device->host copy
@@ -158,6 +159,23 @@ def regressor_body_loss(body, pred_rotmat: torch.Tensor, pred_betas: torch.Tenso
     pred = body.differentiable(pred_betas, pred_rotmat, pose2rot=False, regressor=regressor, joints=False).regressed
     return pose_losses.pose_loss(pred, gt_kps.detach(), joints=pose_eval.H36M_TO_J14 if joints is None else joints, root=root, kind=kind,
                                  weight=weight, cap=cap, renderer=body.renderer)
+
+
+def regressor_step(hmr, optimizer, images: torch.Tensor, gt: torch.Tensor, renderer, gt_is_axis_angle: bool = False, cap: float = 0.02,
+                   max_norm: Optional[float] = None, masks=None):
+    """One batch of `train_spin` (run_gan.py:1880-1940): zero_grad, `hmr(images)` (a `regressors.HipHMR`, or a `regressors.HipHMRHead`
+    when `images` are the trunk's features already; in training mode its dropout is live), `regressor_loss` of `pred_rotmat` against
+    `gt`, backward -- pg_pose_loss's gradient, pg_pose_kinematics_rot_bwd, pg_hmr_head_backward, then torch's own backward of the trunk --,
+    clip_grad_norm_(max_norm) when a norm is given, optimizer.step().  `masks`: the call's dropout keep masks in place of the module's
+    own draws.  Returns the loss as a device scalar; nothing synchronises."""
+    optimizer.zero_grad()
+    pred_rotmat, _, _ = hmr(images, masks=masks)
+    loss = regressor_loss(renderer, pred_rotmat, gt, gt_is_axis_angle=gt_is_axis_angle, cap=cap)
+    loss.backward()
+    if max_norm is not None:
+        torch.nn.utils.clip_grad_norm_(hmr.parameters(), max_norm=max_norm)
+    optimizer.step()
+    return loss.detach()
 
 
 def generator_adversarial_loss(disc, real: Optional[torch.Tensor], fake: torch.Tensor, accuracies: bool = False):

@@ -1,0 +1,326 @@
+"""Float64 restatement of the HMR regression head (posegen_amd/regressors.py, include/posegen_regressor.h) in numpy on the CPU: the
+iterative fc stack with recorded dropout masks and rot6d_to_rotmat in the reference's layout, forward and a hand-written backward.
+It is tested against the reference's own numbers (tests/golden/hmr_head.npz, written by tools/gen_golden_hmr.py from run_gan.py's
+classes) and against float64 autograd of `regressors.stock_forward` (tests/test_hmr_ref.py), and is what the device tests compare
+with.  The `*_with_bound` functions give, beside each float64 value, the elementwise bound on what pg_hmr.hip's float32 result on the
+same operands may differ by."""
+import numpy as np
+
+from posegen_amd import _ffi
+from posegen_amd import regressors as reg
+
+F64 = np.float64
+U32 = 2.0 ** -24
+NORM_EPS = 1e-12
+DOUBLE_SUM = 2.0 ** -45                         # what a sum of a few thousand doubles may lose, relative to the sum of magnitudes
+LINEARS = reg.LINEARS
+HEAD_KEYS = tuple(f"{lin}.{leaf}" for lin in LINEARS for leaf in ("weight", "bias"))
+INIT_KEYS = ("init_pose", "init_shape", "init_cam")
+
+
+def toy_spec(n_iter=3, p_drop=0.5):
+    """every width ragged: F = 37 (K past two chunks of 16, short of a 64-wide step), H = 50, S = 18 + 5 + 3 = 26"""
+    return reg.HmrSpec(37, 50, 3, 5, 3, n_iter, p_drop)
+
+
+def shipped_spec(n_iter=3):
+    """the reference's HMR: 2048 features, 1024 hidden, 24 joints, 10 betas, 3 camera numbers"""
+    return reg.HmrSpec(2048, 1024, 24, 10, 3, n_iter, 0.5)
+
+
+def state_shapes(spec):
+    s = spec.shapes()
+    out = {"init_pose": (1, spec.n_pose), "init_shape": (1, spec.n_shape), "init_cam": (1, spec.n_cam)}
+    for lin in LINEARS:
+        out[f"{lin}.weight"], out[f"{lin}.bias"] = s[f"{lin}_w"], s[f"{lin}_b"]
+    return out
+
+
+def make_state_dict(spec, seed):
+    """the head's state dict from a seed, key by key in the order init_pose, init_shape, init_cam, fc1 .. deccam: init_pose N(0, 1) (so
+    that most joints' six numbers are well conditioned), the other two 0.3 N, Linear weights N(0, 1/in) -- the decoders a fifth of
+    that --, biases 0.1 N"""
+    rng = np.random.RandomState(seed)
+    sd = {}
+    for key, shape in state_shapes(spec).items():
+        if key == "init_pose":
+            sd[key] = rng.standard_normal(shape).astype(np.float32)
+        elif key.startswith("init_"):
+            sd[key] = (0.3 * rng.standard_normal(shape)).astype(np.float32)
+        elif len(shape) == 2:
+            k = 0.2 if key.startswith("dec") else 1.0
+            sd[key] = (k * rng.standard_normal(shape) / np.sqrt(shape[1])).astype(np.float32)
+        else:
+            sd[key] = (0.1 * rng.standard_normal(shape)).astype(np.float32)
+    return sd
+
+
+def params_of(sd):
+    """the ten tensors of a state dict under pg_hmr_params' names"""
+    return {f"{lin}_{'w' if leaf == 'weight' else 'b'}": np.asarray(sd[f"{lin}.{leaf}"]) for lin in LINEARS for leaf in ("weight", "bias")}
+
+
+def init_of(sd):
+    """the shared state before round 0, [S]"""
+    return np.concatenate([np.asarray(sd[k]).reshape(-1) for k in INIT_KEYS])
+
+
+def make_masks(spec, B, seed):
+    """keep masks uint8 [n_iter, 2, B, H]: an element is kept with probability 1 - p"""
+    rng = np.random.RandomState(seed)
+    return (rng.uniform(size=(spec.n_iter, 2, B, spec.n_hidden)) >= spec.p_drop).astype(np.uint8)
+
+
+def pack_masks(masks):
+    return np.packbits(np.asarray(masks, np.uint8).reshape(-1))
+
+
+def unpack_masks(bits, shape):
+    n = int(np.prod(shape))
+    return np.unpackbits(np.asarray(bits, np.uint8))[:n].reshape(shape)
+
+
+def grad_sample_index(n):
+    """eight (fewer for a tensor smaller than that) element indices spread over a flat tensor of n elements"""
+    return np.unique(np.linspace(0, n - 1, num=min(8, n)).astype(np.int64))
+
+
+def drop_scale(p):
+    """fl32(1 / (1 - p)) with p the float32 the spec carries"""
+    return float(np.float32(1.0 / (1.0 - float(np.float32(p)))))
+
+
+def decoder_matrix(P):
+    """the three decoders side by side: Wd [S,H], bd [S]"""
+    return (np.concatenate([np.asarray(P[f"{k}_w"], F64).reshape(-1, P["fc2_w"].shape[0]) for k in ("decpose", "decshape", "deccam")], 0),
+            np.concatenate([np.asarray(P[f"{k}_b"], F64).reshape(-1) for k in ("decpose", "decshape", "deccam")]))
+
+
+# ---- rot6d_to_rotmat ---------------------------------------------------------------------------------------------------------------------
+def _unit(v):
+    n = np.sqrt((v * v).sum(-1, keepdims=True))
+    return v / np.maximum(n, NORM_EPS), n
+
+
+def rot6d(x):
+    """[.., 6] -> [.., 3, 3] in the reference's layout: a1 = elements 0, 2, 4, a2 = elements 1, 3, 5; the columns are b1, b2, b3"""
+    x = np.asarray(x, F64)
+    a1, a2 = x[..., 0::2], x[..., 1::2]
+    b1, _ = _unit(a1)
+    b2, _ = _unit(a2 - (b1 * a2).sum(-1, keepdims=True) * b1)
+    return np.stack([b1, b2, np.cross(b1, b2)], -1)
+
+
+def rot6d_conditioning(x):
+    """(|a1| / |a|, |a2 perpendicular| / |a|) per six numbers: the device's float32 state is compared where both are >= 1e-3"""
+    x = np.asarray(x, F64)
+    a1, a2 = x[..., 0::2], x[..., 1::2]
+    b1, n1 = _unit(a1)
+    _, n2 = _unit(a2 - (b1 * a2).sum(-1, keepdims=True) * b1)
+    na = np.maximum(np.sqrt((x * x).sum(-1)), 1e-300)
+    return n1[..., 0] / na, n2[..., 0] / na
+
+
+def _unit_backward(v, g):
+    """the cotangent of v for v / max(|v|, eps), clamp_min's rule: the norm's own gradient passes where |v| >= eps"""
+    n = np.sqrt((v * v).sum(-1, keepdims=True))
+    b = v / np.maximum(n, NORM_EPS)
+    free = (g - b * (b * g).sum(-1, keepdims=True)) / np.where(n >= NORM_EPS, n, 1.0)
+    return np.where(n >= NORM_EPS, free, g / NORM_EPS)
+
+
+def rot6d_backward(x, G):
+    """the cotangent of x [.., 6] for the cotangent G [.., 3, 3] of rot6d(x)"""
+    x, G = np.asarray(x, F64), np.asarray(G, F64)
+    a1, a2 = x[..., 0::2], x[..., 1::2]
+    g1, g2, g3 = G[..., :, 0], G[..., :, 1], G[..., :, 2]
+    b1, _ = _unit(a1)
+    d = (b1 * a2).sum(-1, keepdims=True)
+    v = a2 - d * b1
+    b2, _ = _unit(v)
+    gb1 = g1 + np.cross(b2, g3)
+    gb2 = g2 + np.cross(g3, b1)
+    gv = _unit_backward(v, gb2)
+    t = (b1 * gv).sum(-1, keepdims=True)
+    ga2 = gv - b1 * t
+    gb1 = gb1 - d * gv - a2 * t
+    ga1 = _unit_backward(a1, gb1)
+    out = np.empty_like(x)
+    out[..., 0::2], out[..., 1::2] = ga1, ga2
+    return out
+
+
+# ---- forward -----------------------------------------------------------------------------------------------------------------------------
+def _drop(x, mask, scale):
+    return x if mask is None else np.where(mask != 0, x * scale, 0.0)
+
+
+def forward(P, xf, init, spec, masks=None):
+    """The head in float64.  init [S] or [B,S]; masks uint8 [n_iter,2,B,H] or None (eval mode).
+    -> dict: P [B,H], s (n_iter + 1 states), h1, h2 (per round, after dropout), rotmat [B,J,3,3], shape, cam"""
+    xf = np.asarray(xf, F64)
+    B, F_, S = xf.shape[0], spec.n_feat, spec.n_state
+    W1, W2 = np.asarray(P["fc1_w"], F64), np.asarray(P["fc2_w"], F64)
+    Wd, bd = decoder_matrix(P)
+    scale = drop_scale(spec.p_drop)
+    s = np.broadcast_to(np.asarray(init, F64), (B, S)).copy()
+    out = {"P": xf @ W1[:, :F_].T + np.asarray(P["fc1_b"], F64), "s": [s], "h1": [], "h2": []}
+    for i in range(spec.n_iter):
+        h1 = _drop(out["P"] + s @ W1[:, F_:].T, None if masks is None else masks[i, 0], scale)
+        h2 = _drop(h1 @ W2.T + np.asarray(P["fc2_b"], F64), None if masks is None else masks[i, 1], scale)
+        s = s + (h2 @ Wd.T + bd)
+        out["h1"].append(h1); out["h2"].append(h2); out["s"].append(s)
+    out["rotmat"] = rot6d(s[:, :spec.n_pose].reshape(B, spec.n_joints, 6))
+    out["shape"], out["cam"] = s[:, spec.n_pose:spec.n_pose + spec.n_shape], s[:, spec.n_pose + spec.n_shape:]
+    return out
+
+
+def final_cotangent(spec, s_final, d_rotmat=None, d_shape=None, d_cam=None):
+    """the cotangent of the final state [B,S] (a None cotangent = zero)"""
+    s_final = np.asarray(s_final, F64)
+    B = s_final.shape[0]
+    ds = np.zeros((B, spec.n_state))
+    if d_rotmat is not None:
+        ds[:, :spec.n_pose] = rot6d_backward(s_final[:, :spec.n_pose].reshape(B, spec.n_joints, 6), d_rotmat).reshape(B, -1)
+    if d_shape is not None and spec.n_shape:
+        ds[:, spec.n_pose:spec.n_pose + spec.n_shape] = d_shape
+    if d_cam is not None and spec.n_cam:
+        ds[:, spec.n_pose + spec.n_shape:] = d_cam
+    return ds
+
+
+def _split_decoders(spec, g_w, g_b):
+    a, b = spec.n_pose, spec.n_pose + spec.n_shape
+    return {"decpose_w": g_w[:a], "decshape_w": g_w[a:b], "deccam_w": g_w[b:], "decpose_b": g_b[:a], "decshape_b": g_b[a:b], "deccam_b": g_b[b:]}
+
+
+def data_step_with_bound(a, e_a, W, scale, mask, add=None, e_add=None):
+    """One data product of the backward, drop'(add + a W) with W [K,N] read down its columns, and its bound: (K + 2) u |a| |W|, the
+    operand's own error e_a through |W|, one rounding for a residual add (whose operand carries e_add), and on kept elements the
+    dropout scale times all that plus its own rounding; a dropped element is exactly zero."""
+    a, W = np.asarray(a, F64), np.asarray(W, F64)
+    c = a @ W
+    e = (a.shape[1] + 2) * U32 * (np.abs(a) @ np.abs(W)) + (0.0 if e_a is None else e_a @ np.abs(W))
+    if add is not None:
+        c = np.asarray(add, F64) + c
+        e = e + (0.0 if e_add is None else e_add) + U32 * np.abs(c)
+    if mask is None:
+        return c, e
+    v = np.where(mask != 0, c * scale, 0.0)
+    return v, np.where(mask != 0, e * scale + U32 * np.abs(v), 0.0)
+
+
+def backward_with_bound(P, xf, spec, masks, tape, ds_final, e_final=None):
+    """The backward in float64 from a forward's tape (`forward`'s dict, or the device's own arrays) and the cotangent of the final
+    state, and beside every value the bound on pg_hmr.hip's float32 result for the same tape and cotangent.  With u = 2^-24, a product
+    over K terms is within (K + 2) u |a| |W| of its float64 value whatever the order of the sum; an operand that carries an error e adds
+    e |W|; every residual add and every dropout scale rounds once more (u |result|); the sum D = sum_i dz1_i formed on load rounds
+    n_iter - 1 times; a double sum rounded once is within u |sum| (+ 2^-45 of the magnitudes).  The errors are carried down the chain to
+    first order.  -> (values, bounds): dicts with the ten gradients, d_xf, d_init and the lists ds, dz2, dz1."""
+    xf = np.asarray(xf, F64)
+    B, F_, H, S, n = xf.shape[0], spec.n_feat, spec.n_hidden, spec.n_state, spec.n_iter
+    W1, W2 = np.asarray(P["fc1_w"], F64), np.asarray(P["fc2_w"], F64)
+    Wd, _ = decoder_matrix(P)
+    scale = drop_scale(spec.p_drop)
+    u = U32
+
+    def step(a, e_a, W, K, m, add=None, e_add=None):
+        return data_step_with_bound(a, e_a, W, scale, m, add, e_add)
+    ds, e_ds = [None] * (n + 1), [None] * (n + 1)
+    ds[n] = np.asarray(ds_final, F64)
+    e_ds[n] = np.zeros_like(ds[n]) if e_final is None else e_final
+    dz2, dz1, e2, e1 = [None] * n, [None] * n, [None] * n, [None] * n
+    for i in range(n - 1, -1, -1):
+        m1, m2 = (None, None) if masks is None else (masks[i, 0], masks[i, 1])
+        dz2[i], e2[i] = step(ds[i + 1], e_ds[i + 1], Wd, S, m2)
+        dz1[i], e1[i] = step(dz2[i], e2[i], W2, H, m1)
+        ds[i], e_ds[i] = step(dz1[i], e1[i], W1[:, F_:], H, None, ds[i + 1], e_ds[i + 1])
+    h1, h2, s = ([np.asarray(a, F64) for a in tape[k]] for k in ("h1", "h2", "s"))
+
+    def stacked(As, eAs, Bs):
+        """sum_i A_i^T B_i over the n B stacked rows, the column sums of A in double, and their bounds"""
+        g = sum(a.T @ b for a, b in zip(As, Bs))
+        absprod = sum(np.abs(a).T @ np.abs(b) for a, b in zip(As, Bs))
+        e = (n * B + 2) * u * absprod + sum(ea.T @ np.abs(b) for ea, b in zip(eAs, Bs))
+        gb = sum(a.sum(0) for a in As)
+        eb = u * np.abs(gb) + sum(ea.sum(0) for ea in eAs) + DOUBLE_SUM * sum(np.abs(a).sum(0) for a in As)
+        return g, e, gb, eb
+    val, bnd = {}, {}
+    gw, ew, gb, eb = stacked(ds[1:], e_ds[1:], h2)
+    val.update(_split_decoders(spec, gw, gb)); bnd.update(_split_decoders(spec, ew, eb))
+    val["fc2_w"], bnd["fc2_w"], val["fc2_b"], bnd["fc2_b"] = stacked(dz2, e2, h1)
+    gws, ews, val["fc1_b"], bnd["fc1_b"] = stacked(dz1, e1, s[:n])
+    D, absD, eD = sum(dz1), sum(np.abs(a) for a in dz1), sum(e1) + (n - 1) * u * sum(np.abs(a) for a in dz1)
+    gwf = D.T @ xf
+    ewf = (B + 2) * u * (absD.T @ np.abs(xf)) + eD.T @ np.abs(xf)
+    val["fc1_w"], bnd["fc1_w"] = np.concatenate([gwf, gws], 1), np.concatenate([ewf, ews], 1)
+    val["d_xf"] = D @ W1[:, :F_]
+    bnd["d_xf"] = (H + 2) * u * (absD @ np.abs(W1[:, :F_])) + eD @ np.abs(W1[:, :F_])
+    val["d_init"], bnd["d_init"] = ds[0], e_ds[0]
+    val.update({"ds": ds, "dz2": dz2, "dz1": dz1}); bnd.update({"ds": e_ds, "dz2": e2, "dz1": e1})
+    return val, bnd
+
+
+def backward(P, xf, spec, masks, tape, d_rotmat=None, d_shape=None, d_cam=None):
+    """the hand-written backward in float64: the ten gradients, d_xf and d_init"""
+    return backward_with_bound(P, xf, spec, masks, tape, final_cotangent(spec, tape["s"][-1], d_rotmat, d_shape, d_cam))[0]
+
+
+# ---- the forward's layers with their bounds --------------------------------------------------------------------------------------------------
+def product_bound(a, W, bias=None):
+    """(K + 2) u (|a| |W|^T + |b|) for a W^T + b over K = a's columns"""
+    m = np.abs(np.asarray(a, F64)) @ np.abs(np.asarray(W, F64)).T
+    if bias is not None:
+        m = m + np.abs(np.asarray(bias, F64))
+    return (a.shape[1] + 2) * U32 * m
+
+
+def p_with_bound(P, xf, spec):
+    """P = xf W1[:, :F]^T + b1"""
+    xf, W = np.asarray(xf, F64), np.asarray(P["fc1_w"], F64)[:, :spec.n_feat]
+    return xf @ W.T + np.asarray(P["fc1_b"], F64), product_bound(xf, W, P["fc1_b"])
+
+
+def h1_with_bound(P, Pmat, s, spec, mask):
+    """h1 = drop(P + s W1[:, F:]^T): the product, one rounding for the add, one for the dropout scale"""
+    Pmat, s, W = np.asarray(Pmat, F64), np.asarray(s, F64), np.asarray(P["fc1_w"], F64)[:, spec.n_feat:]
+    pre = Pmat + s @ W.T
+    e = product_bound(s, W) + U32 * np.abs(pre)
+    if mask is None:
+        return pre, e
+    sc = drop_scale(spec.p_drop)
+    v = np.where(mask != 0, pre * sc, 0.0)
+    return v, np.where(mask != 0, e * sc + U32 * np.abs(v), 0.0)
+
+
+def h2_with_bound(P, h1, spec, mask):
+    """h2 = drop(h1 W2^T + b2)"""
+    h1 = np.asarray(h1, F64)
+    pre = h1 @ np.asarray(P["fc2_w"], F64).T + np.asarray(P["fc2_b"], F64)
+    e = product_bound(h1, P["fc2_w"], P["fc2_b"])
+    if mask is None:
+        return pre, e
+    sc = drop_scale(spec.p_drop)
+    v = np.where(mask != 0, pre * sc, 0.0)
+    return v, np.where(mask != 0, e * sc + U32 * np.abs(v), 0.0)
+
+
+def state_with_bound(P, s, h2):
+    """s' = s + (h2 Wd^T + bd): the product and one rounding for the residual add"""
+    s, h2 = np.asarray(s, F64), np.asarray(h2, F64)
+    Wd, bd = decoder_matrix(P)
+    v = s + (h2 @ Wd.T + bd)
+    return v, product_bound(h2, Wd, bd) + U32 * np.abs(v)
+
+
+def tape_arrays(spec, B, tape):
+    """a device tape (a flat float32 array) as `forward`'s dict of arrays"""
+    at, n_f = spec.tape_layout(B)
+    tape = np.asarray(tape)
+    assert tape.size == n_f
+    H, S = spec.n_hidden, spec.n_state
+    return {"P": tape[at["P"]:at["P"] + B * H].reshape(B, H), "s": [tape[o:o + B * S].reshape(B, S) for o in at["s"]],
+            "h1": [tape[o:o + B * H].reshape(B, H) for o in at["h1"]], "h2": [tape[o:o + B * H].reshape(B, H) for o in at["h2"]]}
+
+
+assert tuple(_ffi.HMR_TENSORS) == tuple(f"{lin}_{leaf}" for lin in LINEARS for leaf in ("w", "b"))
