@@ -3,7 +3,8 @@ iterative fc stack with recorded dropout masks and rot6d_to_rotmat in the refere
 It is tested against the reference's own numbers (tests/golden/hmr_head.npz, written by tools/gen_golden_hmr.py from run_gan.py's
 classes) and against float64 autograd of `regressors.stock_forward` (tests/test_hmr_ref.py), and is what the device tests compare
 with.  The `*_with_bound` functions give, beside each float64 value, the elementwise bound on what pg_hmr.hip's float32 result on the
-same operands may differ by."""
+same operands may differ by.  `emulate_forward` / `emulate_backward` are the head in float32 numpy, with switches that plant errors:
+what those bounds are confronted with on the CPU."""
 import numpy as np
 
 from posegen_amd import _ffi
@@ -26,6 +27,21 @@ def toy_spec(n_iter=3, p_drop=0.5):
 def shipped_spec(n_iter=3):
     """the reference's HMR: 2048 features, 1024 hidden, 24 joints, 10 betas, 3 camera numbers"""
     return reg.HmrSpec(2048, 1024, 24, 10, 3, n_iter, 0.5)
+
+
+def edge_specs():
+    """name -> spec: the widths the header allows that the toy and the shipped spec do not reach -- both decoders empty, each alone,
+    every K of the products (F, H, S) one short of, at, one past and at twice the 64-column step, and every limit at once"""
+    S = reg.HmrSpec
+    return {"minimum": S(1, 1, 1, 0, 0, 1, 0.5),              # K = 1 and N = 1 products; S = 6
+            "no_shape": S(37, 50, 3, 0, 3, 3, 0.5),           # the first two segments end together
+            "no_cam": S(37, 50, 3, 5, 0, 3, 0.5),             # the second segment ends the state
+            "pose_only": S(37, 50, 3, 0, 0, 3, 0.5),          # one segment
+            "step63": S(63, 63, 10, 3, 0, 3, 0.5),            # S = 63
+            "step64": S(64, 64, 10, 3, 1, 3, 0.5),            # S = 64, F + S = 128: every row of every operand 16-byte aligned
+            "step65": S(65, 65, 10, 3, 2, 3, 0.5),            # S = 65
+            "step128": S(128, 128, 21, 2, 0, 2, 0.5),         # S = 128
+            "limits": S(4096, 2048, 64, 64, 16, 8, 0.5)}      # S = 464
 
 
 def state_shapes(spec):
@@ -83,6 +99,14 @@ def unpack_masks(bits, shape):
 def grad_sample_index(n):
     """eight (fewer for a tensor smaller than that) element indices spread over a flat tensor of n elements"""
     return np.unique(np.linspace(0, n - 1, num=min(8, n)).astype(np.int64))
+
+
+def double_sum_term(rows):
+    """What a sum of `rows` doubles may lose in any order, relative to the sum of the magnitudes: each of the rows - 1 adds rounds a
+    partial sum that is at most the sum of the magnitudes, so the loss is below rows 2^-53 of it to first order.  DOUBLE_SUM = 2^-45
+    is this at 256 rows: it covers "a few thousand" only for sums that do not run in one chain (the device's run in chunks of 64 and
+    then over the chunks), so a check over more stacked rows than 256 passes this term to `backward_with_bound` in its place."""
+    return rows * 2.0 ** -53
 
 
 def drop_scale(p):
@@ -210,19 +234,31 @@ def data_step_with_bound(a, e_a, W, scale, mask, add=None, e_add=None):
     return v, np.where(mask != 0, e * scale + U32 * np.abs(v), 0.0)
 
 
-def backward_with_bound(P, xf, spec, masks, tape, ds_final, e_final=None):
+def chunk_fold_terms(rounds, B, chunk=64):
+    """The roundings of a weight gradient over `rounds` x B stacked rows in the order include/posegen_regressor.h documents -- rows in
+    chunks of 64, each from a zero accumulator, the partials added in chunk order -- in units of u |A|^T |B|: a chunk's own sum of up
+    to 64 products in any order ((64 + 2) u, the rule of every product here), then one rounding for each partial that joins the running
+    sum, each of at most the sum of the magnitudes.  Far below rounds B + 2 once there are many chunks."""
+    return chunk + 2 + rounds * (-(-B // chunk))
+
+
+def backward_with_bound(P, xf, spec, masks, tape, ds_final, e_final=None, double_sum=DOUBLE_SUM, row_terms=None):
     """The backward in float64 from a forward's tape (`forward`'s dict, or the device's own arrays) and the cotangent of the final
     state, and beside every value the bound on pg_hmr.hip's float32 result for the same tape and cotangent.  With u = 2^-24, a product
     over K terms is within (K + 2) u |a| |W| of its float64 value whatever the order of the sum; an operand that carries an error e adds
     e |W|; every residual add and every dropout scale rounds once more (u |result|); the sum D = sum_i dz1_i formed on load rounds
-    n_iter - 1 times; a double sum rounded once is within u |sum| (+ 2^-45 of the magnitudes).  The errors are carried down the chain to
-    first order.  -> (values, bounds): dicts with the ten gradients, d_xf, d_init and the lists ds, dz2, dz1."""
+    n_iter - 1 times; a double sum rounded once is within u |sum| (+ `double_sum` of the magnitudes: 2^-45, or `double_sum_term(rows)`).  The errors are carried down the chain to
+    first order.  `row_terms(rounds)`: the count a weight gradient over rounds x B rows is held to in place of rounds B + 2, the bound for
+    any order (`chunk_fold_terms` for the documented one).  -> (values, bounds): dicts with the ten gradients, d_xf, d_init and the lists ds, dz2, dz1."""
     xf = np.asarray(xf, F64)
     B, F_, H, S, n = xf.shape[0], spec.n_feat, spec.n_hidden, spec.n_state, spec.n_iter
     W1, W2 = np.asarray(P["fc1_w"], F64), np.asarray(P["fc2_w"], F64)
     Wd, _ = decoder_matrix(P)
     scale = drop_scale(spec.p_drop)
     u = U32
+    if row_terms is None:
+        def row_terms(rounds):
+            return rounds * B + 2
 
     def step(a, e_a, W, K, m, add=None, e_add=None):
         return data_step_with_bound(a, e_a, W, scale, m, add, e_add)
@@ -241,9 +277,9 @@ def backward_with_bound(P, xf, spec, masks, tape, ds_final, e_final=None):
         """sum_i A_i^T B_i over the n B stacked rows, the column sums of A in double, and their bounds"""
         g = sum(a.T @ b for a, b in zip(As, Bs))
         absprod = sum(np.abs(a).T @ np.abs(b) for a, b in zip(As, Bs))
-        e = (n * B + 2) * u * absprod + sum(ea.T @ np.abs(b) for ea, b in zip(eAs, Bs))
+        e = row_terms(n) * u * absprod + sum(ea.T @ np.abs(b) for ea, b in zip(eAs, Bs))
         gb = sum(a.sum(0) for a in As)
-        eb = u * np.abs(gb) + sum(ea.sum(0) for ea in eAs) + DOUBLE_SUM * sum(np.abs(a).sum(0) for a in As)
+        eb = u * np.abs(gb) + sum(ea.sum(0) for ea in eAs) + double_sum * sum(np.abs(a).sum(0) for a in As)
         return g, e, gb, eb
     val, bnd = {}, {}
     gw, ew, gb, eb = stacked(ds[1:], e_ds[1:], h2)
@@ -252,7 +288,7 @@ def backward_with_bound(P, xf, spec, masks, tape, ds_final, e_final=None):
     gws, ews, val["fc1_b"], bnd["fc1_b"] = stacked(dz1, e1, s[:n])
     D, absD, eD = sum(dz1), sum(np.abs(a) for a in dz1), sum(e1) + (n - 1) * u * sum(np.abs(a) for a in dz1)
     gwf = D.T @ xf
-    ewf = (B + 2) * u * (absD.T @ np.abs(xf)) + eD.T @ np.abs(xf)
+    ewf = row_terms(1) * u * (absD.T @ np.abs(xf)) + eD.T @ np.abs(xf)
     val["fc1_w"], bnd["fc1_w"] = np.concatenate([gwf, gws], 1), np.concatenate([ewf, ews], 1)
     val["d_xf"] = D @ W1[:, :F_]
     bnd["d_xf"] = (H + 2) * u * (absD @ np.abs(W1[:, :F_])) + eD @ np.abs(W1[:, :F_])
@@ -321,6 +357,122 @@ def tape_arrays(spec, B, tape):
     H, S = spec.n_hidden, spec.n_state
     return {"P": tape[at["P"]:at["P"] + B * H].reshape(B, H), "s": [tape[o:o + B * S].reshape(B, S) for o in at["s"]],
             "h1": [tape[o:o + B * H].reshape(B, H) for o in at["h1"]], "h2": [tape[o:o + B * H].reshape(B, H) for o in at["h2"]]}
+
+
+# ---- the head in float32 on the CPU ------------------------------------------------------------------------------------------------------------
+F32 = np.float32
+MUTANTS = ("tail16", "segment", "mask_swap", "d_short", "init_no_residual", "bias_round0")
+
+
+def _mm32(a, w, mutant=None):
+    """a [M,K] w [K,N] accumulated and rounded in float32 (numpy's own order of summation, not the device's); the planted error
+    `tail16` drops the columns of K past the last multiple of 16"""
+    a, w = np.ascontiguousarray(a, F32), np.ascontiguousarray(w, F32)
+    if mutant == "tail16":
+        k = a.shape[1] - a.shape[1] % 16
+        a, w = np.ascontiguousarray(a[:, :k]), np.ascontiguousarray(w[:k])
+    if a.shape[1] == 0:
+        return np.zeros((a.shape[0], w.shape[1]), F32)
+    return np.matmul(a, w, dtype=F32)
+
+
+def _decoders32(P, spec, mutant=None):
+    """Wd [S,H], bd [S] in float32; the planted error `segment` routes with <= where < belongs: a column that starts a segment reads
+    the row one past the end of the tensor before it (stood in for by that tensor's row 0: the device would read whatever lies there)"""
+    H = P["fc2_w"].shape[0]
+    parts = [(np.asarray(P[f"{k}_w"], F32).reshape(-1, H), np.asarray(P[f"{k}_b"], F32).reshape(-1)) for k in ("decpose", "decshape", "deccam")]
+    Wd, bd = np.concatenate([w for w, _ in parts], 0), np.concatenate([b for _, b in parts])
+    if mutant == "segment":
+        n1, n2 = spec.n_pose, spec.n_pose + spec.n_shape
+        for r in range(spec.n_state):
+            if r <= n1:
+                seg, rr = 0, r
+            elif r <= n2:
+                seg, rr = 1, r - n1
+            else:
+                seg, rr = 2, r - n2
+            w, b = parts[seg]
+            if rr >= w.shape[0]:
+                rr = 0
+            if w.shape[0]:
+                Wd[r], bd[r] = w[rr], b[rr]
+    return Wd, bd
+
+
+def _drop32(x, mask, scale):
+    return x if mask is None else np.where(mask != 0, x * F32(scale), F32(0.0)).astype(F32)
+
+
+def emulate_forward(P, xf, init, spec, masks=None, mutant=None):
+    """The head as honest float32 arithmetic on the operands the device gets: every product accumulated and rounded in float32, the
+    bias added to the rounded product, one rounding for the residual add and one for fl32(x fl32(1 / (1 - p))), the rotation epilogue
+    in double from the float32 state, rounded once.  -> (tape, a flat float32 array in the device's layout; rotmat; shape; cam)"""
+    xf = np.asarray(xf, F32)
+    B, F_, H, S, n = xf.shape[0], spec.n_feat, spec.n_hidden, spec.n_state, spec.n_iter
+    W1, W2 = np.asarray(P["fc1_w"], F32), np.asarray(P["fc2_w"], F32)
+    Wd, bd = _decoders32(P, spec, mutant)
+    scale = drop_scale(spec.p_drop)
+    at, n_f = spec.tape_layout(B)
+    tape = np.zeros(n_f, F32)
+
+    def put(o, a):
+        tape[o:o + a.size] = a.reshape(-1)
+    Pm = _mm32(xf, W1[:, :F_].T, mutant) + np.asarray(P["fc1_b"], F32)
+    put(at["P"], Pm)
+    s = np.broadcast_to(np.asarray(init, F32), (B, S)).copy()
+    put(at["s"][0], s)
+    for i in range(n):
+        m1, m2 = (None, None) if masks is None else (masks[i, 0], masks[i, 1])
+        h1 = _drop32(Pm + _mm32(s, W1[:, F_:].T, mutant), m1, scale)
+        h2 = _drop32(_mm32(h1, W2.T, mutant) + np.asarray(P["fc2_b"], F32), m2, scale)
+        s = s + (_mm32(h2, Wd.T, mutant) + bd)
+        put(at["h1"][i], h1); put(at["h2"][i], h2); put(at["s"][i + 1], s)
+    assert s.dtype == F32 and h1.dtype == F32
+    a, b = spec.n_pose, spec.n_pose + spec.n_shape
+    rotmat = rot6d(s[:, :a].astype(F64).reshape(B, spec.n_joints, 6)).astype(F32)
+    return tape, rotmat, s[:, a:b].copy(), s[:, b:].copy()
+
+
+def emulate_backward(P, xf, spec, masks, tape, d_rotmat=None, d_shape=None, d_cam=None, mutant=None):
+    """The backward as honest float32 arithmetic from a flat tape: the rot6d cotangent in double, rounded once; the data products and
+    the weight gradients accumulated and rounded in float32 (the stacked rows as one product); D summed in round order in float32; bias
+    gradients summed in double and rounded once.  -> the ten gradients, d_xf and d_init, float32.  `mutant`: one of MUTANTS."""
+    xf = np.asarray(xf, F32)
+    B, F_, H, S, n = xf.shape[0], spec.n_feat, spec.n_hidden, spec.n_state, spec.n_iter
+    t = tape_arrays(spec, B, tape)
+    W1, W2 = np.asarray(P["fc1_w"], F32), np.asarray(P["fc2_w"], F32)
+    Wd, _ = _decoders32(P, spec, mutant)
+    scale = drop_scale(spec.p_drop)
+    c64 = [None if c is None else np.asarray(c, F64) for c in (d_rotmat, d_shape, d_cam)]
+    ds = [None] * (n + 1)
+    ds[n] = final_cotangent(spec, t["s"][n].astype(F64), *c64).astype(F32)
+    dz2, dz1 = [None] * n, [None] * n
+    for i in range(n - 1, -1, -1):
+        m1, m2 = (None, None) if masks is None else (masks[i, 0], masks[i, 1])
+        dz2[i] = _drop32(_mm32(ds[i + 1], Wd, mutant), m1 if mutant == "mask_swap" else m2, scale)
+        dz1[i] = _drop32(_mm32(dz2[i], W2, mutant), m1, scale)
+        back = _mm32(dz1[i], W1[:, F_:], mutant)
+        ds[i] = back if (mutant == "init_no_residual" and i == 0) else ds[i + 1] + back
+    rounds = 1 if mutant == "bias_round0" else n
+
+    def stacked(As, Bs):
+        g = _mm32(np.concatenate(As, 0).T, np.concatenate(Bs, 0))
+        return g, np.concatenate(As[:rounds], 0).astype(F64).sum(0).astype(F32)
+    out = {}
+    gw, gb = stacked(ds[1:], t["h2"])
+    out.update(_split_decoders(spec, gw, gb))
+    out["fc2_w"], out["fc2_b"] = stacked(dz2, t["h1"])
+    gws, out["fc1_b"] = stacked(dz1, t["s"][:n])
+    D = dz1[0]
+    for i in range(1, n - 1 if mutant == "d_short" else n):
+        D = D + dz1[i]
+    if mutant == "d_short" and n == 1:
+        D = np.zeros_like(D)
+    out["fc1_w"] = np.concatenate([_mm32(D.T, xf), gws], 1)
+    out["d_xf"] = _mm32(D, W1[:, :F_], mutant)
+    out["d_init"] = ds[0]
+    assert all(v.dtype == F32 for v in out.values())
+    return out
 
 
 assert tuple(_ffi.HMR_TENSORS) == tuple(f"{lin}_{leaf}" for lin in LINEARS for leaf in ("w", "b"))

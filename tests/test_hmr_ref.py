@@ -1,7 +1,9 @@
 """The HMR regression head without a GPU: the float64 restatement (tests/hmr_ref.py) against the reference's own numbers
 (tests/golden/hmr_head.npz, written by tools/gen_golden_hmr.py from run_gan.py's classes) in both modes, outputs and gradients; its
-hand-written backward against float64 autograd of `regressors.stock_forward`; rot6d_to_rotmat at its degenerate inputs; the module's
-state-dict keys and shapes; and the C ABI of include/posegen_regressor.h as the library exports it."""
+hand-written backward against float64 autograd of `regressors.stock_forward`, at the toy and the shipped spec and at the nine of
+`hmr_ref.edge_specs`; rot6d_to_rotmat at its degenerate inputs; the module's state-dict keys and shapes; the C ABI of
+include/posegen_regressor.h as the library exports it; and the bounds the device is held to (tests/hmr_checks.py) confronted with a
+float32 emulation of the head: honest rounding stays inside them at every spec, planted errors leave them."""
 import ctypes as C
 import os
 import re
@@ -11,6 +13,7 @@ import pytest
 import torch
 
 from posegen_amd import _ffi, regressors as reg
+from tests import hmr_checks as chk
 from tests import hmr_ref as ref
 from tests import stream_harness as sh
 
@@ -19,6 +22,7 @@ GOLDEN = np.load(os.path.join(REPO, "tests", "golden", "hmr_head.npz"))
 HEADER = os.path.join(REPO, "include", "posegen_regressor.h")
 COMPUTE = ("pg_hmr_head_forward", "pg_hmr_head_backward")
 OUTS = ("pred_rotmat", "pred_shape", "pred_cam")
+EDGE_SMALL = ("minimum", "no_shape", "no_cam", "pose_only", "step64")        # (eval mode with a per-row init as well)
 
 
 def _rel(a, b):
@@ -82,10 +86,27 @@ def _module(spec, sd, dtype=torch.float64):
     return head.to(dtype)
 
 
+def _spec(which, n_iter=None):
+    if which in ("toy", "shipped"):
+        return (ref.toy_spec if which == "toy" else ref.shipped_spec)(*(() if n_iter is None else (n_iter,)))
+    spec = ref.edge_specs()[which]
+    return spec if n_iter is None else spec.with_iter(n_iter)
+
+
+def _grad_equals(mine, theirs, shape):
+    """1e-12 on a gradient; one without elements (an empty decoder's, which autograd may leave None) has only its shape to compare"""
+    assert mine.shape == tuple(shape)
+    if not mine.size:
+        return theirs is None or tuple(theirs.shape) == tuple(shape)
+    return _rel(mine, theirs.numpy()) <= 1e-12
+
+
 @pytest.mark.parametrize("which,n_iter,with_masks,per_row", [("toy", 3, True, False), ("toy", 1, False, True), ("toy", 8, True, True),
-                                                            ("shipped", 3, True, False)])
+                                                            ("shipped", 3, True, False)]
+                         + [(name, None, True, False) for name in ref.edge_specs()] + [(name, None, False, True) for name in EDGE_SMALL])
 def test_the_hand_written_backward_equals_float64_autograd_of_stock_forward(which, n_iter, with_masks, per_row):
-    spec = ref.toy_spec(n_iter) if which == "toy" else ref.shipped_spec(n_iter)
+    spec = _spec(which, n_iter)
+    n_iter = spec.n_iter
     B = 6
     sd = ref.make_state_dict(spec, 51)
     rng = np.random.RandomState(52)
@@ -104,15 +125,17 @@ def test_the_hand_written_backward_equals_float64_autograd_of_stock_forward(whic
     torch.autograd.backward(outs, [torch.tensor(c) for c in cot])
     P = ref.params_of(sd)
     mine = ref.forward(P, xf, init, spec, masks)
-    for o, m in zip(outs, (mine["rotmat"], mine["shape"], mine["cam"])):
-        assert _rel(m, o.detach().numpy()) <= 1e-12
+    for o, m, cols in zip(outs, (mine["rotmat"], mine["shape"], mine["cam"]), (None, spec.n_shape, spec.n_cam)):
+        assert m.shape == tuple(o.shape) and (cols is None or m.shape == (B, cols))
+        assert (m.size == 0 and cols == 0) or _rel(m, o.detach().numpy()) <= 1e-12
     g = ref.backward(P, xf, spec, masks, mine, *cot)
     assert _rel(g["d_xf"], xt.grad.numpy()) <= 1e-12
     if per_row:
         assert _rel(g["d_init"], it.grad.numpy()) <= 1e-12
     for lin in ref.LINEARS:
-        assert _rel(g[f"{lin}_w"], getattr(head, lin).weight.grad.numpy()) <= 1e-12, lin
-        assert _rel(g[f"{lin}_b"], getattr(head, lin).bias.grad.numpy()) <= 1e-12, lin
+        assert _grad_equals(g[f"{lin}_w"], getattr(head, lin).weight.grad, spec.shapes()[f"{lin}_w"]), lin
+        assert _grad_equals(g[f"{lin}_b"], getattr(head, lin).bias.grad, spec.shapes()[f"{lin}_b"]), lin
+    assert sum(g[f"{lin}_w"].size == 0 for lin in ref.LINEARS) == (spec.n_shape == 0) + (spec.n_cam == 0)
 
 
 def test_rot6d_at_a_zero_first_axis_at_parallel_axes_and_through_the_clamp():
@@ -235,3 +258,95 @@ def test_the_tape_size_and_the_host_side_refusals():
     assert lib.pg_hmr_tape_size(C.byref(cs), 4, None) == _ffi.PG_EINVAL and lib.pg_hmr_tape_size(None, 4, C.byref(n)) == _ffi.PG_EINVAL
     cs.n_iter = 9
     assert lib.pg_hmr_tape_size(C.byref(cs), 4, C.byref(n)) == _ffi.PG_EINVAL
+
+
+# ---- honest float32 against the bounds, and planted errors -----------------------------------------------------------------------------------
+# The bounds of hmr_ref.*_with_bound are what the device tests hold pg_hmr.hip to.  Here the same checks (tests/hmr_checks.py) judge
+# a float32 emulation of the head in numpy: honest rounding in another order of summation must stay inside every bound at every spec,
+# and each planted error must leave them at the spec named for it.
+ALL_SPECS = ("toy", "shipped") + tuple(ref.edge_specs())
+_JUDGED = {}
+
+
+def _judged(which, training=True, mutant=None, B=17):
+    """the shared checks on one emulated run -> [(check, context, offending indices)]; the honest runs are kept"""
+    key = (which, training, mutant, B)
+    if key in _JUDGED:
+        return _JUDGED[key]
+    spec = _spec(which)
+    sd = ref.make_state_dict(spec, 51)
+    rng = np.random.RandomState(52)
+    xf = rng.standard_normal((B, spec.n_feat)).astype(np.float32)
+    masks = ref.make_masks(spec, B, 53) if training else None
+    init = None if training else rng.standard_normal((B, spec.n_state)).astype(np.float32)
+    rng = np.random.RandomState(54)
+    cots = [rng.standard_normal(shape).astype(np.float32) for shape in ((B, spec.n_joints, 3, 3), (B, spec.n_shape), (B, spec.n_cam))]
+    run = chk.Emulated(spec, sd, xf, masks, init, mutant)
+    run.forward()
+    tag = f"emulated {which} {'train' if training else 'eval'}" + (f" [{mutant}]" if mutant else "")
+    with chk.collecting() as failed:
+        _, well = chk.check_forward(run, tag)
+        chk.check_backward(run, cots, tag)
+    assert np.mean(well) >= 0.9
+    names = sorted({name[len(tag) + 1:] for name, _, _ in failed})
+    print(f"FAILED {tag}: {names}")
+    _JUDGED[key] = failed
+    return failed
+
+
+def _names(failed):
+    return {name.split(" ")[-1] for name, _, _ in failed}
+
+
+FORWARD_NAMES = {"P", "h1", "h2", "s", "rotmat"}
+
+
+@pytest.mark.parametrize("which", ALL_SPECS)
+def test_honest_float32_stays_inside_every_bound(which):
+    assert _judged(which) == []
+
+
+def test_honest_float32_stays_inside_every_bound_in_eval_mode_with_a_per_row_init():
+    assert _judged("step65", training=False) == []
+
+
+def test_a_product_that_drops_the_tail_of_k_past_a_multiple_of_16_is_caught_at_step63_and_step65_and_not_at_step64():
+    for which in ("step63", "step65"):
+        assert {"P", "h1", "h2", "s"} <= _names(_judged(which, mutant="tail16")), which
+    assert _judged("step64", mutant="tail16") == []                            # F = H = S = 64: there is no tail, so only the spec shows it
+
+
+def test_a_segment_compare_off_by_one_is_caught_on_toy_and_differently_on_no_shape():
+    def state_columns(which):
+        failed = _judged(which, mutant="segment")
+        assert "s" in _names(failed)
+        return sorted({int(c) for name, _, where in failed if name.endswith(" s") for c in where[:, 1]})
+    assert state_columns("toy") == [18, 23]                                    # the first shape column and the first cam column
+    assert state_columns("no_shape") == [18]                                   # n1 == n2: the first cam column alone, taken for pose
+    assert _judged("pose_only", mutant="segment") == []                       # (one segment: nothing to confuse)
+
+
+def test_drop1s_mask_in_drop2s_place_in_the_backward_is_caught_on_toy():
+    names = _names(_judged("toy", mutant="mask_swap"))
+    assert not names & FORWARD_NAMES and {"fc1_w", "fc2_w", "fc1_b", "fc2_b", "d_xf", "d_init"} <= names
+
+
+def test_d_without_the_last_round_is_caught_in_d_xf_and_the_feature_columns_of_d_fc1_w_alone():
+    failed = _judged("toy", mutant="d_short")
+    assert _names(failed) == {"d_xf", "fc1_w"}
+    cols = {int(c) for name, _, where in failed if name.endswith(" fc1_w") for c in where[:, 1]}
+    assert cols and max(cols) < _spec("toy").n_feat
+
+
+def test_d_init_without_the_residual_is_caught_in_d_init_alone():
+    assert _names(_judged("toy", mutant="init_no_residual")) == {"d_init"}
+
+
+def test_bias_gradients_over_round_0_only_are_invisible_at_minimum_and_caught_on_no_cam():
+    assert _judged("minimum", mutant="bias_round0") == []                      # one round: the planted error changes nothing
+    assert _names(_judged("no_cam", mutant="bias_round0")) == {"fc1_b", "fc2_b", "decpose_b", "decshape_b"}
+
+
+def test_every_planted_error_has_its_test():
+    tested = {"tail16", "segment", "mask_swap", "d_short", "init_no_residual", "bias_round0"}
+    assert set(ref.MUTANTS) == tested
