@@ -28,6 +28,7 @@ _REGRESSOR_BATCH_NAMES = ("PixelStore", "RegressorBatchSource", "regressor_input
 _SCENE_NAMES = ("ScenePerson", "render_scene", "render_scenes", "place_people")
 _GENERATOR_NAMES = ("HipBAGenerator", "HipRTGenerator", "HipPoseGenerator")
 _REGRESSOR_NAMES = ("HipHMRHead", "HipHMR")
+_OPTIM_NAMES = ("HipAdam",)
 
 
 def __getattr__(name):
@@ -71,4 +72,7 @@ def __getattr__(name):
     if name in _REGRESSOR_NAMES:              # the regressor's head (imports torch as well)
         from . import regressors
         return getattr(regressors, name)
+    if name in _OPTIM_NAMES:                  # the optimiser step on the device (imports torch as well)
+        from . import optim
+        return getattr(optim, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -1,5 +1,5 @@
 """ctypes binding of libposegen_hip.so (include/posegen_hip.h, include/posegen_gan.h, include/posegen_generator.h,
-include/posegen_regressor.h).
+include/posegen_regressor.h, include/posegen_optim.h).
 
 north_star asks for a "thin C-ABI cffi layer"; cffi is not installed in the build
 image (and cannot be: no network), so the same C ABI is bound with ctypes from the
@@ -331,6 +331,25 @@ REGRESSOR_PROTOTYPES = {
                                        _FP, _FP, _FP, C.POINTER(PgHmrGrads), _FP, _FP]),
 }
 
+PG_ADAM_MAX_TENSORS, PG_ADAM_MAX_GROUPS, PG_ADAM_SEGMENT, PG_ADAM_NO_CLIP = 4096, 64, 16384, -1.0
+
+
+class PgAdamGroup(C.Structure):
+    """pg_adam_group (include/posegen_optim.h): torch.optim.Adam's hyperparameters of one param_group"""
+    _fields_ = [(k, C.c_double) for k in ("lr", "beta1", "beta2", "eps", "weight_decay")]
+
+
+class PgAdamTensor(C.Structure):
+    """pg_adam_tensor: one parameter's device pointers, its element count, its group and the step being taken"""
+    _fields_ = [(k, C.c_void_p) for k in ("param", "grad", "exp_avg", "exp_avg_sq")] + [("count", C.c_int64), ("group", C.c_int32), ("step", C.c_int32)]
+
+
+# every symbol include/posegen_optim.h declares (the fifth public header, DESIGN.md 2.19), bound and called like the others
+OPTIM_PROTOTYPES = {
+    "pg_adam_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(PgAdamTensor), C.c_int, C.POINTER(PgAdamGroup), C.c_double, C.c_int,
+                               C.c_void_p]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -348,7 +367,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         lib = C.CDLL(p)
     except OSError as e:  # pragma: no cover - depends on the box
         raise HipLibraryError(f"cannot load {p}: {e}") from e
-    for name, (res, args) in list(PROTOTYPES.items()) + list(GAN_PROTOTYPES.items()) + list(GENERATOR_PROTOTYPES.items()) + list(REGRESSOR_PROTOTYPES.items()):
+    for name, (res, args) in (list(PROTOTYPES.items()) + list(GAN_PROTOTYPES.items()) + list(GENERATOR_PROTOTYPES.items()) + list(REGRESSOR_PROTOTYPES.items())
+                               + list(OPTIM_PROTOTYPES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -1,7 +1,7 @@
 // pg_handle.h -- the renderer handle behind the C ABI (include/posegen_hip.h), shared by the translation units that implement
 // its entry points: pg_api.hip (handle, weights, ray-level rendering), pg_frames.hip (frames), pg_train.hip (the training step),
 // pg_mesh.hip, pg_poseopt.hip, pg_batch.hip, pg_metrics.hip, pg_scene.hip, pg_posescore.hip, pg_smpl.hip, pg_kploss.hip,
-// pg_trainloss.hip, pg_regressor.hip, pg_disc.hip (include/posegen_gan.h), pg_gen.hip (include/posegen_generator.h), pg_hmr.hip (include/posegen_regressor.h).  Each of the last fifteen keeps its state in its slot of the handle's table (pg_modules.h):
+// pg_trainloss.hip, pg_regressor.hip, pg_disc.hip (include/posegen_gan.h), pg_gen.hip (include/posegen_generator.h), pg_hmr.hip (include/posegen_regressor.h), pg_optim.hip (include/posegen_optim.h).  Each of the last sixteen keeps its state in its slot of the handle's table (pg_modules.h):
 // pg_state creates it on first use, h->mods.peek reads it, and the state's destructor frees what it owns.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -60,7 +60,7 @@ struct pg_handle : Subject {
     int64_t aux_n = 0;               // record launches / their device time already folded in by a pg_profile_read
     double aux_ms = 0.0;
     int64_t prof_points = 0;
-    Modules mods;                    // the fifteen modules' states (pg_modules.h; pg_state below): each struct says beside its code what it keeps
+    Modules mods;                    // the sixteen modules' states (pg_modules.h; pg_state below): each struct says beside its code what it keeps
     std::vector<float> grid_t;       // pg_grid_density: the host copy of the axis table t[R] while its upload is in flight
     bool tape_out = false;           // a pg_train_forward whose backward has not run yet: the bank stays as it is until then
 };

@@ -13,7 +13,7 @@ struct ModuleState { virtual ~ModuleState() = default; };
 
 // (the order in which a handle's states are destroyed)
 enum ModuleSlot { MOD_TRAIN, MOD_MESH, MOD_POSEOPT, MOD_BATCH, MOD_METRICS, MOD_POSESCORE, MOD_SMPL, MOD_KPLOSS, MOD_TRAINLOSS,
-                  MOD_REGRESSOR, MOD_FRAMES, MOD_SCENE, MOD_DISC, MOD_HMR, MOD_GEN, MOD_COUNT };
+                  MOD_REGRESSOR, MOD_FRAMES, MOD_SCENE, MOD_DISC, MOD_HMR, MOD_OPTIM, MOD_GEN, MOD_COUNT };
 
 struct Modules {
     std::unique_ptr<ModuleState> slot[MOD_COUNT];

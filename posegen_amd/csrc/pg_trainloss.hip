@@ -23,15 +23,16 @@
 #include <vector>
 
 #include "pg_handle.h"
+#include "pg_sumsq.h"
 
 namespace pgtl {
 
 constexpr int NJ = 24;
-constexpr int THREADS = 256;
+constexpr int THREADS = pgsq::THREADS;
 constexpr int NQ = 9;             // loss_part_kernel's columns: pass p at 4 p + (0 loss, 1 squared error, 2 BCE sum, 3 BCE count); 8 = sum of acc_map
 constexpr int RQ = 3;             // reg_kernel's columns: kp, temporal, per-joint change
-constexpr int SEG = 16384;        // elements of one norm_part_kernel workgroup
-constexpr int SLOTS = 4 * THREADS;
+constexpr int SEG = pgsq::SEG;    // elements of one norm_part_kernel workgroup
+constexpr int SLOTS = pgsq::SLOTS;
 constexpr double BCE_EPS = 1e-8;  // acc2bce's eps (trainer.py:44)
 
 // the sum of the workgroup's 256 values in a fixed tree, the same bits in every thread
@@ -310,32 +311,8 @@ __global__ __launch_bounds__(THREADS) void norm_part_kernel(const NormEntry* __r
     const float* base = en.p + seg * SEG;
     const long long rest = en.count - seg * SEG;
     const int len = rest < SEG ? (int)rest : SEG;
-    const int m = (int)((reinterpret_cast<uintptr_t>(base) >> 2) & 3);   // elements between the 16-byte boundary below `base` and `base`
-    const float4* quads = reinterpret_cast<const float4*>(base - m);
-    const int end = m + len;                                             // positions [m, end) are the segment's elements
-    double acc[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int q = tid; 4 * q < end; q += THREADS) {
-        const int p0 = 4 * q;
-        if (p0 >= m && p0 + 4 <= end) {
-            const float4 f = quads[q];
-            acc[0] += (double)f.x * (double)f.x; acc[1] += (double)f.y * (double)f.y;
-            acc[2] += (double)f.z * (double)f.z; acc[3] += (double)f.w * (double)f.w;
-        } else {                                                         // the head and the tail quad: only the elements inside
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const int p = p0 + c;
-                if (p >= m && p < end) { const double f = (double)base[p - m]; acc[c] += f * f; }
-            }
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < 4; ++c) lds[(4 * tid + c - m + SLOTS) % SLOTS] = acc[c];     // element i of the segment is in slot i mod 1024
-    __syncthreads();
-    for (int d = SLOTS / 2; d >= 1; d >>= 1) {
-        for (int k = tid; k < d; k += THREADS) lds[k] += lds[k + d];
-        __syncthreads();
-    }
-    if (tid == 0) part[blockIdx.x] = lds[0];
+    const double sq = pgsq::segment_sumsq(base, len, lds);                // (pg_sumsq.h: shared with pg_adam_step's clipping norm)
+    if (tid == 0) part[blockIdx.x] = sq;
 }
 
 // out = total_norm, avg_norm, then every tensor's norm

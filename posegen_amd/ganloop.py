@@ -161,6 +161,13 @@ def regressor_body_loss(body, pred_rotmat: torch.Tensor, pred_betas: torch.Tenso
                                  weight=weight, cap=cap, renderer=body.renderer)
 
 
+def _is_hip_adam(optimizer) -> bool:
+    """`optimizer` is an `optim.HipAdam`: its step clips and updates in one device call (pg_adam_step), and the norm is over the
+    optimiser's own parameters that have a gradient -- the module's, where the optimiser was built on `module.parameters()`"""
+    from . import optim
+    return isinstance(optimizer, optim.HipAdam)
+
+
 def regressor_step(hmr, optimizer, images: torch.Tensor, gt: torch.Tensor, renderer, gt_is_axis_angle: bool = False, cap: float = 0.02,
                    max_norm: Optional[float] = None, masks=None):
     """One batch of `train_spin` (run_gan.py:1880-1940): zero_grad, `hmr(images)` (a `regressors.HipHMR`, or a `regressors.HipHMRHead`
@@ -172,6 +179,9 @@ def regressor_step(hmr, optimizer, images: torch.Tensor, gt: torch.Tensor, rende
     pred_rotmat, _, _ = hmr(images, masks=masks)
     loss = regressor_loss(renderer, pred_rotmat, gt, gt_is_axis_angle=gt_is_axis_angle, cap=cap)
     loss.backward()
+    if max_norm is not None and _is_hip_adam(optimizer):
+        optimizer.step(max_norm=max_norm)
+        return loss.detach()
     if max_norm is not None:
         torch.nn.utils.clip_grad_norm_(hmr.parameters(), max_norm=max_norm)
     optimizer.step()
@@ -197,6 +207,9 @@ def discriminator_step(disc, optimizer, real: torch.Tensor, fake: torch.Tensor, 
     fake = pool(fake.detach(), rng)
     loss, real_acc, fake_acc = discriminators.discriminator_loss(disc, real.detach(), fake)
     loss.backward()
+    if max_norm is not None and _is_hip_adam(optimizer):
+        optimizer.step(max_norm=max_norm)
+        return real_acc, fake_acc, loss.detach()
     torch.nn.utils.clip_grad_norm_(disc.parameters(), max_norm=max_norm)
     optimizer.step()
     return real_acc, fake_acc, loss.detach()
@@ -215,6 +228,9 @@ def generator_step(gen, disc, optimizer, real: torch.Tensor, feedback=None, max_
     if feedback is not None:
         loss = loss + 0.1 * feedback(out["pose_ba"])
     loss.backward()
+    if max_norm is not None and _is_hip_adam(optimizer):
+        optimizer.step(max_norm=max_norm)
+        return out["pose_ba"].detach(), loss.detach()
     torch.nn.utils.clip_grad_norm_(gen.parameters(), max_norm=max_norm)
     optimizer.step()
     return out["pose_ba"].detach(), loss.detach()
